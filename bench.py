@@ -14,7 +14,11 @@ shards by trajectory (4096 per rank, weak scaling); the only collective is the a
 [sum cost, max |J^T r|, trajectories still running] after every persistent launch of the LM kernel (`check_every`
 iterations; default = max_iter, i.e. one launch and one all-reduce per solve; RCCL, `nccl` backend).
 
-Besides the contract fields the line carries
+A plain run does the headline only: set-up, warm-up, the timed steps, the line (its `roofline` from the HIP events of the timed
+steps).  --dump-outputs DIR writes what the last timed step returned (cost, iters, status, q of every fit) as DIR/<name>.npy.
+--full adds every other record below, each with runs of its own (the --no-* options and --config3-batch then leave some out).
+
+Besides the contract fields the --full line carries
   roofline          the dominant kernel (fit_lm_kernel: the whole LM loop, J^T J on the fp32 MFMA), HIP events around each of
                     its launches inside the timed region: algorithmic flop = 200*48*49 per J^T J evaluation
                     x evaluations / summed HIP-event kernel time
@@ -559,6 +563,23 @@ def compact_line(line, roof, cpu, detail_file=None):
     raise ValueError(f'bench line is {len(s)} bytes, limit {LINE_LIMIT}: too many hoisted keys')
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: `arrays` (one row per fit) as d/<name>.npy in float64.  Above `limit` bytes in all, the same fixed sample of
+    rows (seed 0, in index order) of every array instead, and the sampled row numbers as d/row_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(out.values())))
+    per_row = sum(v.nbytes for v in out.values()) // max(n, 1) + 8
+    if n * per_row > limit:
+        idx = np.sort(np.random.default_rng(0).choice(n, limit // per_row, replace=False))
+        out = dict({k: v[idx] for k, v in out.items()}, row_index=idx.astype(np.float64))
+    for k, v in out.items():
+        np.save(os.path.join(d, k + '.npy'), v)
+
+
 def emit(line, detail, roof, cpu):
     """Side file (gpurun_out/ when it exists, so that it travels back from a GPU box) + prefixed detail line, THEN the small line."""
     d = os.path.join(ROOT, 'gpurun_out')
@@ -607,6 +628,11 @@ def main():
                          'fast = rounds 1-2\'s loop (reported beside it in any case)')
     ap.add_argument('--no-extra-modes', action='store_true', help='skip the fast_mode / minpack_pure / order-hint records')
     ap.add_argument('--dump-costs', default=None, help='(tests) every rank writes the costs / iteration counts of its last headline solve to <prefix>_rank<r>.npz')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step returned (cost, iters, status, q of every fit; float64) as DIR/<name>.npy (DIR/<name>_rank<r>.npy with N > 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the records beside the headline (cpu_baseline + parity, solver variants, roofline_isolated, config2, config3, sim, nlp, '
+                         'long_horizon), each with runs of its own; without it the run does the headline only')
     a = ap.parse_args()
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -618,11 +644,11 @@ def main():
         return
     B = a.batch
     cpu = keep = cpu_g = cpu_t = cpu_n = cpu_l = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         # (rank 0 of ANY world size: a --gpus N line carries the same cpu_baseline / parity records as the N = 1 line -- the other
         # ranks wait in init_process_group meanwhile; the simulation / collocation / long-horizon legs stay single-rank records)
         cpu, keep = cpu_baseline(B, a.cpu_sample)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         if not a.no_sim:
             cpu_g, cpu_t = cpu_baseline_sim_gvf(), cpu_baseline_sim_track()
         if not a.no_nlp:
@@ -728,13 +754,16 @@ def main():
     headline = summary(B, a.steps, dt, glob, prof, n_evals)
     if a.dump_costs:
         np.savez(f'{a.dump_costs}_rank{rank}.npz', cost=cost.cpu().numpy(), iters=iters.cpu().numpy(), status=status.cpu().numpy(), q=q.cpu().numpy())
+    if a.dump_outputs:
+        sfx = '' if world == 1 else f'_rank{rank}'
+        dump_outputs(a.dump_outputs, {n + sfx: v.cpu().numpy() for n, v in (('cost', cost), ('iters', iters), ('status', status), ('q', q))})
     q_head = q[:a.cpu_sample].clone() if keep is not None else None
     z_head = plan.coeffs(dsc[:a.cpu_sample], q[:a.cpu_sample]).cpu().numpy() if keep is not None else None
     c_head = cost[:a.cpu_sample].cpu().numpy() if keep is not None else None
     # the other solver / hand-out combinations on the same batch, same timing discipline (every rank takes part: barriers inside)
     variants = {}
     gpu_sol = {}
-    if not a.no_extra_modes:
+    if a.full and not a.no_extra_modes:
         other = 'index' if a.handout == 'predicted' else 'predicted'
         for name, (mode_v, order_v, mi) in {'default_with_order_hint': (a.mode, not a.order_hint, None),
                                             'default_' + other + '_handout': ('minpack_' + other, False, None),
@@ -810,23 +839,24 @@ def main():
             tf = ALG_FLOP_PER_EVAL * Bi / (us * 1e-6) / 1e12
             return {'units_per_launch': Bi, 'avg_launch_us': us, 'launches': int(nit), 'achieved': tf, 'frac': tf / FP32_PEAK_TFLOPS,
                     'alg_hbm_gbs': JTJ_BYTES_PER_UNIT * Bi / (us * 1e-6) / 1e9}
-        i4 = iso(dsc, q0, 40)
-        roof_iso = {'bound': 'mfma', 'kernel': 'fit_jtj_kernel<3,24> (contraction only: fp32 row records HBM -> LDS, J^T J on v_mfma_f32_16x16x4_f32, '
-                                               'tile-major store)', 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                    'alg_flop_per_unit': ALG_FLOP_PER_EVAL, 'alg_bytes_per_unit': JTJ_BYTES_PER_UNIT,
-                    'traffic': pmc_traffic('fit_jtj_kernel')[0], 'traffic_source': pmc_traffic('fit_jtj_kernel')[1],
-                    'alg_bytes_per_launch': JTJ_BYTES_PER_UNIT * B, **i4,
-                    'note': 'the whole kernel is the contraction (one HIP event pair around back-to-back launches; rocprofv3 kernel trace in profiles/); '
-                            'ceiling of frac = 0.766: the three diagonal 16x16 tiles are computed whole'}
-        if world == 1 and a.config3_batch > B:
-            dsci = ctx.dev(bench_scenarios(a.config3_batch, 0))
-            roof_iso['large'] = iso(dsci, plan.init(dsci), 20)
-            del dsci
-            torch.cuda.empty_cache()
+        if a.full:
+            i4 = iso(dsc, q0, 40)
+            roof_iso = {'bound': 'mfma', 'kernel': 'fit_jtj_kernel<3,24> (contraction only: fp32 row records HBM -> LDS, J^T J on v_mfma_f32_16x16x4_f32, '
+                                                   'tile-major store)', 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                        'alg_flop_per_unit': ALG_FLOP_PER_EVAL, 'alg_bytes_per_unit': JTJ_BYTES_PER_UNIT,
+                        'traffic': pmc_traffic('fit_jtj_kernel')[0], 'traffic_source': pmc_traffic('fit_jtj_kernel')[1],
+                        'alg_bytes_per_launch': JTJ_BYTES_PER_UNIT * B, **i4,
+                        'note': 'the whole kernel is the contraction (one HIP event pair around back-to-back launches; rocprofv3 kernel trace in profiles/); '
+                                'ceiling of frac = 0.766: the three diagonal 16x16 tiles are computed whole'}
+            if world == 1 and a.config3_batch > B:
+                dsci = ctx.dev(bench_scenarios(a.config3_batch, 0))
+                roof_iso['large'] = iso(dsci, plan.init(dsci), 20)
+                del dsci
+                torch.cuda.empty_cache()
 
     # ---- BASELINE configs[3]: 32 768 fits per rank (256 k at N = 8), every rank, same timing discipline -------------------
     config3 = None
-    if a.config3_batch > 0:
+    if a.full and a.config3_batch > 0:
         B3 = a.config3_batch
         dt3, r3, ne3, prof3, glob3 = timed_solves(B3, a.config3_steps, 1, a.order_hint, a.mode, keep=False)
         tot3 = B3 * world
@@ -842,7 +872,7 @@ def main():
 
     # ---- BASELINE configs[2]: multi_opt_planner's 8-drone circular formation x 8192 replicas, collision rows between all pairs ----
     config2 = None
-    if rank == 0 and world == 1 and not a.no_groups:
+    if rank == 0 and world == 1 and a.full and not a.no_groups:
         from d2dhip import synth
         n_ac, Rg = 8, 8192
         plan_g = d2dhip.FitPlan(ctx, S_, K, dur, synth.default_wref(1.0, K))
@@ -967,12 +997,12 @@ def main():
 
     # ---- BASELINE configs[4] ---------------------------------------------------------------------------------------------
     sim = None
-    if rank == 0 and world == 1 and not a.no_sim:
+    if rank == 0 and world == 1 and a.full and not a.no_sim:
         del dsc, q0, q, cost, iters, status
         torch.cuda.empty_cache()
         sim = sim_records(ctx, torch, cpu_g, cpu_t)
     nlp = longh = None
-    if rank == 0 and world == 1 and not a.no_nlp:
+    if rank == 0 and world == 1 and a.full and not a.no_nlp:
         torch.cuda.empty_cache()
         nlp = nlp_record(ctx, torch, cpu_n)
         longh = long_horizon_record(ctx, torch, d2dhip, cpu_long=cpu_l)
@@ -1011,9 +1041,12 @@ def main():
             'collective': reducer.collective, 'rccl_ranks': reducer.rccl_ranks,
             'rank_kernel_ms_per_step_min_max': list(head_rank_ms),
         }
-        detail = dict(line, variants=variants, roofline=roof, roofline_isolated=roof_iso, config2=config2, config3=config3, parity=parity, sim=sim, nlp=nlp,
-                      long_horizon=longh, cpu_baseline=cpu)
-        emit(line, detail, roof, cpu)
+        if a.full:
+            detail = dict(line, variants=variants, roofline=roof, roofline_isolated=roof_iso, config2=config2, config3=config3, parity=parity, sim=sim, nlp=nlp,
+                          long_horizon=longh, cpu_baseline=cpu)
+            emit(line, detail, roof, cpu)
+        else:
+            print(compact_line(line, roof, cpu), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 

@@ -53,3 +53,25 @@ def test_emit_prints_the_small_line_last(capsys, tmp_path, monkeypatch):
     assert len(out) == 2 and out[0].startswith(bench.DETAIL_PREFIX) and len(out[0]) > 20000
     assert len(out[1]) <= bench.LINE_LIMIT and json.loads(out[1])['detail'] == 'bench_detail.json'
     assert json.load(open(tmp_path / 'bench_detail.json'))['parity']['others'][0].startswith('zzz')
+
+
+def test_dump_outputs_float64_and_bounded(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; above the limit the same seeded rows of every array (and their numbers),
+    the same rows from call to call, within the limit."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    arrays = {'cost': rng.random(1000), 'iters': np.arange(1000, dtype=np.int32), 'q': rng.random((1000, 96))}
+    bench.dump_outputs(str(tmp_path / 'all'), arrays)
+    assert sorted(os.listdir(tmp_path / 'all')) == ['cost.npy', 'iters.npy', 'q.npy']
+    for k, v in arrays.items():
+        d = np.load(tmp_path / 'all' / (k + '.npy'))
+        assert d.dtype == np.float64 and np.array_equal(d, v)
+    for run in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / run), arrays, limit=50000)
+    names = sorted(os.listdir(tmp_path / 's1'))
+    assert names == ['cost.npy', 'iters.npy', 'q.npy', 'row_index.npy'] and sum(os.path.getsize(tmp_path / 's1' / n) for n in names) <= 50000 + 4 * 128
+    idx = np.load(tmp_path / 's1' / 'row_index.npy').astype(np.int64)
+    assert 0 < len(idx) < 1000 and np.all(np.diff(idx) > 0)
+    for k, v in arrays.items():
+        d = np.load(tmp_path / 's1' / (k + '.npy'))
+        assert d.dtype == np.float64 and np.array_equal(d, v[idx]) and np.array_equal(d, np.load(tmp_path / 's2' / (k + '.npy')))
