@@ -143,6 +143,15 @@ struct NlpProb {
   const double *partner;     // [2][N] or null
   double *lds;               // this wavefront's NLP_LDS_DOUBLES doubles of LDS (nlp_assemble: neighbour hand-over, record transposition)
 };
+// Objective model of d2d_nlp_solve_model (user cost plug-ins, opty/direct_collocation.py): this problem's planes.  The objective of
+// that instantiation is  m(W) = sum_i g_i.d_i + 1/2 d_i^T H_i d_i,  d_i = W_i - Wc_i, on top of the structured terms (which the
+// host's row zeroes); H_i is held as its upper triangle, row by row (nlp_hidx).
+struct NlpModel {
+  const double *g;           // [5][N]
+  const double *H;           // [15][N]
+  const double *Wc;          // [5][N]
+};
+__host__ __device__ constexpr int nlp_hidx(int a, int c) { return a * NLP_NV - a * (a - 1) / 2 + (c - a); }     // a <= c
 // LDS of one wavefront: up [65][9] (what a node hands to the node before it; row 64 = the first node of the chunk processed before),
 // then rec [64][19] (the reduced-node records of a chunk, odd stride: conflict-free both ways)
 #define NLP_LDS_UP 0
@@ -185,8 +194,9 @@ __device__ __forceinline__ bool nlp_fixed(int i, int N, int c) { return c < 3 &&
 
 // Merit function of the inner problem at W + a*dw: objective + rho sum (c + mu)^2 - mub sum log(slacks); +inf outside the box.
 // Node-parallel (lane = node, chunks of 64) + wave reductions.  All results are wave-uniform.
+template <bool MODEL>
 __device__ double nlp_merit(const NlpProb &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
-                            double mub, double *cost_ref_out, double *feas_out) {
+                            double mub, double *cost_ref_out, double *feas_out, const NlpModel &md) {
   const int N = pb.N;
   double val = 0.0, bar = 0.0, cref = 0.0, feas = 0.0, phi2max = 0.0;
   int outside = 0;
@@ -218,6 +228,18 @@ __device__ double nlp_merit(const NlpProb &pb, const NlpScen &s, const double *_
       bar += log(prod);               // one log per node: at most ten slacks in [1e-12, 1e3], their product stays in range
       const double dv = w[4] - s.vsp;
       double obj = s.skv * dv * dv + s.skphi * w[3] * w[3];
+      if constexpr (MODEL) {          // g.d + 1/2 d^T H d
+        double d[NLP_NV];
+#pragma unroll
+        for (int c = 0; c < NLP_NV; ++c) d[c] = w[c] - md.Wc[c * N + i];
+#pragma unroll
+        for (int r = 0; r < NLP_NV; ++r) {
+          double t = md.g[r * N + i] + 0.5 * md.H[nlp_hidx(r, r) * N + i] * d[r];
+#pragma unroll
+          for (int c = r + 1; c < NLP_NV; ++c) t += md.H[nlp_hidx(r, c) * N + i] * d[c];
+          obj += d[r] * t;
+        }
+      }
       phi2max = fmax(phi2max, w[3] * w[3]);
       cref += obj;
       nlp_exp_terms(s, sc, pb.partner, i, N, w[0], w[1], obj, cref, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -278,8 +300,9 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // imax (CostBank max mode, s.sbank > 0): the node whose bank angle is the largest at the current iterate -- the reference's
 // cost_grad is one-hot there (2 obj_scale kbank phi_imax), the step's model carries the term sbank * phi_imax^2 on that node
 // alone (the maximiser frozen for the step; the merit function of the line search is the true max)
+template <bool MODEL>
 __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
-                               double lam, bool *pd_out, int imax, bool rec_lds) {
+                               double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md) {
   const int N = pb.N;
   const double h = pb.h, ih = 1.0 / h;
   double err = 0.0;
@@ -320,6 +343,20 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
     D[4][4] += s.skv; g[4] += s.skv * (wc[4] - s.vsp);
     D[3][3] += s.skphi; g[3] += s.skphi * wc[3];
     if (i == imax) { D[3][3] += s.sbank; g[3] += s.sbank * wc[3]; }
+    if constexpr (MODEL) {            // half gradient 1/2 (g + H d), half Hessian 1/2 H (H loaded here, not with the node's other values)
+      double d[NLP_NV];
+#pragma unroll
+      for (int c = 0; c < NLP_NV; ++c) { d[c] = wc[c] - md.Wc[c * N + i]; g[c] += 0.5 * md.g[c * N + i]; }
+#pragma unroll
+      for (int r = 0; r < NLP_NV; ++r) {
+#pragma unroll
+        for (int c = r; c < NLP_NV; ++c) {
+          const double hv = 0.5 * md.H[nlp_hidx(r, c) * N + i];
+          D[r][c] += hv; g[r] += hv * d[c];
+          if (c != r) { D[c][r] += hv; g[c] += hv * d[r]; }
+        }
+      }
+    }
     {
       double obj = 0.0, cref = 0.0;
       nlp_exp_terms(s, sc, pb.partner, i, N, wc[0], wc[1], obj, cref, &g[0], &g[1], &D[0][0], &D[0][1], &D[1][1]);
@@ -1019,9 +1056,11 @@ struct NlpOut { double cost, feas; int iters, status; };
 
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
+// MODEL: the objective is the quadratic model md (d2d_nlp_solve_model) on top of the row's structured terms; cost = its value.
+template <bool MODEL = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
-                                              const double *__restrict__ bnd) {
+                                              const double *__restrict__ bnd, const NlpModel &md = NlpModel{nullptr, nullptr, nullptr}) {
   // diagnostics (D2D_NLP_STAMPS): cycles per phase -- merit, assembly, factorisation, back substitution, ratio tests, update
   unsigned long long st_t = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define NLP_STAMP(k) if (st_on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t; st_t = t_; }
@@ -1041,6 +1080,16 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   {
     bool bad = !(s.hi[3] > s.lo[3]) || !(s.hi[4] > s.lo[4]) || !(s.lo[4] > 0.0) || !(s.hi[0] > s.lo[0]) || !(s.hi[1] > s.lo[1]) || !(s.hi[2] > s.lo[2]);
     for (int c = 0; c < 3; ++c) bad = bad || !(fabs(s.p0[c]) <= 1.79e308) || !(fabs(s.p1[c]) <= 1.79e308);
+    if constexpr (MODEL) {            // a model with a non-finite entry is refused like a bad row
+      int nf = 0;
+      for (int i = lane; i < N; i += 64) {
+#pragma unroll
+        for (int c = 0; c < NLP_NV; ++c) nf |= !(fabs(md.g[c * N + i]) <= 1.79e308) || !(fabs(md.Wc[c * N + i]) <= 1.79e308);
+#pragma unroll
+        for (int k = 0; k < 15; ++k) nf |= !(fabs(md.H[k * N + i]) <= 1.79e308);
+      }
+      bad = bad || __builtin_amdgcn_ballot_w64(nf != 0) != 0ull;
+    }
     if (bad) {
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
       return;
@@ -1087,7 +1136,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     const double tol_in = fmax(fmax(o.opt_tol, fmin(1e-1, 10.0 * mub)), D2D_NLP_GRAD_FLOOR * rho);
     // merit value of the current point for this (mub, rho, mu): one pass here, afterwards the accepted trial's value
     NLP_STAMP(7)
-    double phi0 = nlp_merit(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr);
+    double phi0 = nlp_merit<MODEL>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1098,7 +1147,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       const int imax = s.sbank > 0.0 ? nlp_bank_argmax(pb, lane) : -1;
       for (int tr = 0; tr < 30; ++tr) {
         bool pd;
-        err = nlp_assemble(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<MODEL>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -1121,7 +1170,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         double a = amax, pt = 0.0;
         bool ok = false;
         for (int ls = 0; ls < 8; ++ls) {
-          pt = nlp_merit(pb, s, sc, lane, a, rho, mub, nullptr, nullptr);
+          pt = nlp_merit<MODEL>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
@@ -1139,7 +1188,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       }
       if (converged || !accepted) break;
     }
-    (void)nlp_merit(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas);
+    (void)nlp_merit<MODEL>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -1178,7 +1227,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     feas_prev = feas;
     mub = fmax(o.mub_min, fmin(0.2 * mub, mub * sqrt(mub)));
   }
-  (void)nlp_merit(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas);
+  (void)nlp_merit<MODEL>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -1303,9 +1352,50 @@ nlp_groups_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_swee
   }
 }
 
+// d2d_nlp_solve_model: the collocation NLP under the quadratic objective model of a cost that only the host can evaluate (a user's
+// cost plug-in, opty/direct_collocation.py).  One wavefront and one workspace per problem: the launch holds the few aircraft of one
+// Problem, so there is nothing to hand out and no second wave per SIMD to fill: it runs at one wave per SIMD (256 VGPRs + 74 AGPRs,
+// 240 B / lane of scratch -- what nlp_solve_kernel built for one wave has too -- against 528 B / lane at two; DESIGN measured one
+// wave per SIMD at the same speed for this solver).
+#ifndef NLP_MODEL_WAVES_PER_SIMD
+#define NLP_MODEL_WAVES_PER_SIMD 1
+#endif
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_MODEL_WAVES_PER_SIMD, NLP_MODEL_WAVES_PER_SIMD)))
+nlp_model_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, d2d_nlp_model m, double *W, double *work,
+                 double *mult, double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                 int32_t *__restrict__ status_out) {
+  const int lane = threadIdx.x, b = blockIdx.x;
+  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
+  const size_t pl = (size_t)b * N;
+  const NlpModel md{m.g + pl * NLP_NV, m.H + pl * 15, m.Wc + pl * NLP_NV};
+  NlpOut out;
+  nlp_solve_one<true>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + pl * NLP_NV, work + pl * WS_TOTAL, mult ? mult + pl * 3 : nullptr,
+                      lane, out, nullptr, nlp_lds, o.bounds ? o.bounds + (size_t)b * 4 : nullptr, md);
+  if (lane == 0) {
+    cost_out[b] = out.cost;
+    feas_out[b] = out.feas;
+    if (iters_out) iters_out[b] = out.iters;
+    if (status_out) status_out[b] = out.status;
+  }
+}
+
 extern "C" {
 
 int d2d_nlp_workspace_doubles(int N) { return N * WS_TOTAL; }
+
+int d2d_nlp_solve_model(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, const d2d_nlp_model *model,
+                        double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status) {
+  D2D_REQUIRE(ctx && scen && model && model->g && model->H && model->Wc && W && work && cost && feas, "d2d_nlp_solve_model: null argument");
+  D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_model: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
+  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
+  if (opts) o = *opts;
+  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_model: bad options");
+  o.order = nullptr;                                       // (one wavefront per problem: no hand-out)
+  hipLaunchKernelGGL(nlp_model_kernel, dim3(B), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, *model, W, work,
+                     mult, cost, feas, iters, status);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
 
 int d2d_nlp_solve(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W,
                   const double *partner, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status) {

@@ -56,6 +56,11 @@ class NlpOpts(C.Structure):
                 ('bounds', C.c_void_p), ('order', C.c_void_p)]
 
 
+class NlpModel(C.Structure):
+    """d2d_nlp_model: device pointers of the quadratic objective model (g [B][5][N], H [B][15][N] upper triangles, Wc [B][5][N])."""
+    _fields_ = [('g', C.c_void_p), ('H', C.c_void_p), ('Wc', C.c_void_p)]
+
+
 class FitOpts(C.Structure):
     _fields_ = [('max_iter', C.c_int32), ('check_every', C.c_int32), ('ftol', C.c_double),
                 ('gtol', C.c_double), ('xtol', C.c_double), ('so_lambda', C.c_double),
@@ -118,6 +123,7 @@ _SIGS = {
     'd2d_nlp_workspace_doubles': (C.c_int, [C.c_int]),
     'd2d_nlp_solve': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 8),
     'd2d_nlp_solve_groups': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9),
+    'd2d_nlp_solve_model': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.POINTER(NlpModel)] + [_P] * 7),
     'd2d_fit_plan_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(_P)]),
     'd2d_fit_plan_create_ex': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(FitPlanOpts), C.POINTER(_P)]),
     'd2d_fit_opts_default': (C.c_int, [C.POINTER(FitOpts)]),
@@ -449,6 +455,31 @@ class Context:
         _check(self.lib.d2d_nlp_solve_groups(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W), _ptr(work),
                                              None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps), _ptr(moved)))
         return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work)
+
+    def nlp_solve_model(self, scen, W, h, g, H, Wc, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
+                        outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None):
+        """The collocation NLP under a quadratic objective model (d2d_nlp_solve_model): minimise sum_i g_i.d_i + 1/2 d_i^T H_i d_i,
+        d_i = W_i - Wc_i, over the feasible set of scen's rows (their cost weights are the caller's business: the host-objective path
+        zeroes them).  g, Wc dev [B][5][N], H dev [B][15][N] (upper triangle of each node's 5x5 block, row by row), W dev [B][5][N]
+        in/out, bounds as nlp_solve.  Returns dict(cost (the model's value at the solution), feas, iters, status[, mult]) of device tensors."""
+        torch = _torch()
+        B, _, N = W.shape
+        assert W.is_contiguous() and scen.shape[0] == B
+        for t, k in ((g, 5), (H, 15), (Wc, 5)):
+            assert t.is_contiguous() and tuple(t.shape) == (B, k, N) and t.dtype == torch.float64 and t.device == W.device
+        work = self.empty(self.lib.d2d_nlp_workspace_doubles(N) * B)
+        cost, feas = self.empty(B), self.empty(B)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        mult = self.zeros(B, 3, N) if want_mult else None
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
+        m = NlpModel(g.data_ptr(), H.data_ptr(), Wc.data_ptr())
+        _check(self.lib.d2d_nlp_solve_model(self.h, B, N, float(h), _ptr(scen), C.byref(o), C.byref(m), _ptr(W), _ptr(work), _ptr(mult),
+                                            _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status)))
+        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work)
+        if want_mult:
+            out['mult'] = mult
+        return out
 
     def track_run(self, x_ref, y_ref, X0, dt, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), out=None, **kw):
         """x_ref, y_ref dev [T][n]; X0 dev [5][n] -> dict of device histories (out: reuse the buffers of an earlier

@@ -53,7 +53,9 @@ class Planner:
         self._slice_phi = [slice(o + i * N, o + (i + 1) * N, 1) for i in range(n)]
         o += n * N
         self._slice_v = [slice(o + i * N, o + (i + 1) * N, 1) for i in range(n)]
-        if initialize and self.backend == 'nlp':
+        # a cost plug-in without a lowering: the collocation problem with the host objective, unless the fit was asked for
+        self._host_cost = self.backend != 'fit' and not sop.lowerable(scen.cost)
+        if initialize and (self.backend == 'nlp' or self._host_cost):
             import itertools
             import opty.direct_collocation
 
@@ -100,6 +102,7 @@ class Planner:
         return g
 
     def _solve(self, x0):
+        sop.fit_cost(self.scen.cost)
         ctx = d2dhip.default_context()
         N, n = self.num_nodes, self.acs.nb_aicraft
         rows, plan, coupled = scenario_rows(self.scen, self.scen.p0s, self.scen.p1s, N, self.duration, self.obj_scale, self.wind.w)
@@ -137,8 +140,10 @@ class Planner:
         self.prob.add_option('tol', tol)
         self.prob.addOption('max_iter', max_iter)
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self.backend == 'nlp':
+        if self.backend == 'nlp' or self._host_cost:
             self.fit_q = self.fit_plan = self.fit_scen = self.fit_coefs = None
+            if self._host_cost:
+                self.info['backend_used'] = 'nlp'
         else:
             sop.Planner._harden(self)      # backend='auto': a plan that overshoots a bound is re-planned by the collocation backend
 

@@ -14,8 +14,11 @@ What is interpreted instead of compiled:
   * obj / obj_grad       -- the reference passes closures over a cost plug-in and the planner
                             (`lambda _free: obj.cost(_free, self)`); the plug-in is taken from the closure (or from the explicit
                             `cost=` / `planner=` keywords) and lowered structurally (single_opt_planner.lower_cost): the known
-                            classes of d2d.opty_utils / d2d.multiopty_utils have a kernel, anything else raises NotImplementedError.
+                            classes of d2d.opty_utils / d2d.multiopty_utils have a kernel ("lowered" objective).
                             The gradient the solver follows is the plug-in's cost_grad (reference quirks included, oracle/nlp.py).
+                            Any other plug-in, and plain callables with no plug-in behind them, select the HOST objective
+                            (`Problem.objective == 'host'`): the host calls obj / obj_grad, as IPOPT does, and the device solves a
+                            sequence of quadratic models of them over the exact feasible set (_solve_host, below).
 The whole Problem is ONE launch (d2d_nlp_solve_groups): wavefront a of a workgroup solves aircraft a.  The aircraft are coupled
 through the objective only -- CostCollision acts on the pair of aircraft 0 and 1, src/d2d/multiopty_utils.py:124-125 -- so the
 pair alternates on the device (each turn a full solve against the partner's frozen node positions) until neither moves by more than
@@ -24,6 +27,68 @@ pair that has not settled is reported 'max_iter'."""
 import numpy as np
 
 import d2dhip
+
+# status codes of include/d2d.h (D2D_ST_*)
+ST_CONVERGED, ST_MAXITER, ST_NONFINITE, ST_STALLED = 1, 2, 3, 4
+STATUS_MSG = {ST_CONVERGED: 'converged', ST_MAXITER: 'max_iter', ST_NONFINITE: 'non-finite', ST_STALLED: 'stalled'}
+# host objective: trust control of the quadratic models (sigma: proximal weight, relative to 1 + the largest curvature entry)
+ETA_REJECT, ETA_GOOD = 0.1, 0.75
+SIGMA_MIN, SIGMA_MAX, SIGMA_GROW = 1e-3, 1e6, 10.0
+STALL_AT_MAX = 2                    # rejections in a row at SIGMA_MAX: STALLED
+XTOL, FTOL = 1e-8, 1e-10            # convergence: largest move of an accepted step, change of f relative to 1 + |f|
+_HIDX = [(a, c) for a in range(5) for c in range(a, 5)]        # d2d_nlp_model.H planes: upper triangle, row by row
+
+
+def free_index(n_aircraft, num_nodes, planner=None):
+    """int array (n_aircraft, 5, num_nodes): position of (x, y, psi, phi, v)(t_i) of each aircraft in the free vector.  From the
+    planner's slices when there is one; otherwise the layout of this package's planners: five planes for one aircraft
+    (single_opt_planner), x_a, y_a, psi_a per aircraft then the phi and the v planes for several (multi_opt_planner)."""
+    n, N = n_aircraft, num_nodes
+    if planner is not None and hasattr(planner, '_slice_x'):
+        sl = [planner._slice_x, planner._slice_y, planner._slice_psi, planner._slice_phi, planner._slice_v]
+        if not isinstance(sl[0], (list, tuple)):
+            sl = [[s] for s in sl]
+        return np.stack([np.stack([np.arange(N * n * 5)[sl[c][a]] for c in range(5)]) for a in range(n)])
+    if n == 1:
+        return np.arange(5 * N).reshape(1, 5, N)
+    idx = np.zeros((n, 5, N), dtype=np.int64)
+    for a in range(n):
+        for c in range(3):
+            idx[a, c] = np.arange((c + 3 * a) * N, (c + 3 * a + 1) * N)
+        idx[a, 3] = np.arange(3 * n * N + a * N, 3 * n * N + (a + 1) * N)
+        idx[a, 4] = np.arange(4 * n * N + a * N, 4 * n * N + (a + 1) * N)
+    return idx
+
+
+def curvature_blocks(grad, x, idx, g0=None):
+    """Per-node 5x5 blocks of the Hessian of the function whose gradient is `grad`, by forward differences of grad along coloured
+    directions: for each aircraft a, residue r in {0, 1, 2} and component c, component c of every node i = r (mod 3) of aircraft a
+    is perturbed at once (step sqrt(eps) max(1, |w|)), and the gradient difference at node i is column c of block i.  Exact up to
+    the differencing error when the Hessian couples nodes at most two apart; 15 calls of grad per aircraft.  -> (n, N, 5, 5)
+    (not symmetrised).  g0: grad(x) if already known."""
+    n, _, N = idx.shape
+    g0 = np.asarray(grad(x), dtype=np.float64) if g0 is None else g0
+    H = np.zeros((n, N, 5, 5))
+    eps = np.sqrt(np.finfo(np.float64).eps)
+    for a in range(n):
+        for r in range(3):
+            nodes = np.arange(r, N, 3)
+            for c in range(5):
+                pos = idx[a, c, nodes]
+                xp = x.copy()
+                xp[pos] += eps * np.maximum(1.0, np.abs(x[pos]))
+                step = xp[pos] - x[pos]
+                dg = np.asarray(grad(xp), dtype=np.float64) - g0
+                H[a, nodes, :, c] = (dg[idx[a][:, nodes]] / step).T
+    return H
+
+
+def model_blocks(H, sigma):
+    """Symmetrised blocks with their eigenvalues clipped at 0, + sigma I, packed as d2d_nlp_model.H: (n, N, 5, 5) -> (n, 15, N)."""
+    S = 0.5 * (H + np.swapaxes(H, -1, -2))
+    lam, V = np.linalg.eigh(S)
+    S = (V * np.maximum(lam, 0.0)[..., None, :]) @ np.swapaxes(V, -1, -2) + sigma * np.eye(5)
+    return np.ascontiguousarray(np.stack([S[..., a, c] for a, c in _HIDX], axis=1))
 
 
 def _closure_objects(fn):
@@ -54,10 +119,16 @@ class Problem:
                     cost = o
                 if planner is None and hasattr(o, 'num_nodes') and hasattr(o, 'obj_scale'):
                     planner = o
-        if cost is None or planner is None:
-            raise NotImplementedError('Problem: pass the objective as a closure over a d2d cost plug-in and the planner (as the '
-                                      'reference does) or give cost= / planner= explicitly: arbitrary Python callables have no kernel')
         self.cost, self.planner = cost, planner
+        # a known plug-in behind a planner: its kernel ('lowered'); anything else: the host calls obj / obj_grad ('host')
+        self.objective = 'host'
+        if cost is not None and planner is not None:
+            import single_opt_planner as sop
+            try:
+                sop.lower_cost(cost)
+                self.objective = 'lowered'
+            except NotImplementedError:
+                pass
         # end conditions per aircraft from the instance constraints: names x<i>, y<i>, psi<i>
         ids = [str(s.sym.name)[1:] for s in state_symbols[0::3]]
         t_all = sorted({c.t for c in instance_constraints})
@@ -119,6 +190,8 @@ class Problem:
         return rows, coupled
 
     def solve(self, x0):
+        if self.objective == 'host':
+            return self._solve_host(np.asarray(x0, dtype=np.float64))
         ctx = d2dhip.default_context()
         n, N = self.n_aircraft, self.num_nodes
         x0 = np.asarray(x0, dtype=np.float64)
@@ -162,4 +235,144 @@ class Problem:
                 'iters': out['iters'].cpu().numpy().tolist(), 'sweeps': sweeps, 'moved': moved,
                 'obj_val': float(self.obj(sol)), 'status_msg': 'converged' if (st == 1).all() else 'max_iter',
                 'box_violation': 0.0, 'phi_violation': 0.0, 'v_violation': 0.0}       # hard bounds: an interior-point iterate never leaves its box
+        return sol, info
+
+    # ---- host objective ------------------------------------------------------------------------------------------------------
+    def _host_rows(self):
+        """Scenario rows with every structured cost weight 0 (the objective is the model alone) + the bounds beside them."""
+        import single_opt_planner as sop
+        low = (0., 0., 0., 0., (), float('nan'), 0., 0, 0)
+        rows = np.stack([sop.scen_row(tuple(self.p0s[a]) + (0., 0.), tuple(self.p1s[a]) + (0., 0.), 0., low, 1.0, self.wind,
+                                      bd['phi'], bd['v'], x_c=bd.get('x'), y_c=bd.get('y')) for a, bd in enumerate(self.bounds)])
+        bnd = None
+        if any('psi' in bd or abs(bd['phi'][0] + bd['phi'][1]) > 1e-12 for bd in self.bounds):
+            bnd = np.array([[bd['phi'][0], bd['phi'][1]] + list(bd.get('psi', (0.0, 0.0))) for bd in self.bounds], dtype=np.float64)
+        return rows, bnd
+
+    def _solve_host(self, x0):
+        """A sequence of quadratic models of the user's objective over the exact feasible set (the collocation equalities, end
+        conditions and hard boxes), each solved on the device by d2d_nlp_solve_model -- one launch for all aircraft:
+          0. restoration: the start projected onto the feasible set (g = 0, H = I), so that every iterate W_k is feasible;
+          1. at W_k: f_k = obj, g_k = obj_grad (one call each), per-node curvature blocks from 15 obj_grad calls per aircraft
+             (curvature_blocks), symmetrised, eigenvalues clipped at 0, + sigma I;
+          2. W_new = argmin g_k.d + 1/2 d^T H d over the feasible set, from W_k;
+          3. ratio test with the true obj (both points feasible): rho = (f_k - f(W_new)) / (m(W_k) - m(W_new)); rho < 0.1: rejected,
+             sigma grows and the model is solved again; rho > 0.75: sigma shrinks.
+        Stops: converged (an accepted step that changes f by <= FTOL (1 + |f|) and moves no variable by more than XTOL, or of which
+        the model itself predicted no more than that), max_iter (outer cap from options['max_iter']), stalled (the subproblem
+        found no feasible point, or STALL_AT_MAX rejections in a row at the largest sigma: e.g. an obj_grad that is not the gradient
+        of obj), non-finite (obj or obj_grad not finite at an iterate; a non-finite obj at a trial point is a rejection)."""
+        ctx = d2dhip.default_context()
+        n, N = self.n_aircraft, self.num_nodes
+        idx = free_index(n, N, self.planner)
+        rows, bnd = self._host_rows()
+        dsc = ctx.dev(rows)
+        dbnd = None if bnd is None else ctx.dev(bnd)
+        _im = d2dhip.NLP_INNER_MAX
+        tol = float(self.options.get('tol', 1e-8))
+        kw = dict(inner_max=_im, outer_max=int(min(max(self.options.get('max_iter', 3000) // _im, 720 // _im), 3600 // _im)),
+                  opt_tol=min(tol, 1e-7), feas_tol=min(1e-2 * tol, 1e-9), bounds=dbnd)
+        outer_cap = int(self.options.get('outer_max', min(max(int(self.options.get('max_iter', 3000)) // 20, 8), 100)))
+        calls = {'cost': 0, 'grad': 0}
+
+        def f_of(x):
+            calls['cost'] += 1
+            return float(np.asarray(self.obj(x), dtype=np.float64))
+
+        def g_of(x):
+            calls['grad'] += 1
+            return np.asarray(self.obj_grad(x), dtype=np.float64).reshape(-1)
+
+        def to_free(W):
+            x = x0.copy()
+            x[idx] = W
+            return x
+
+        iters = np.zeros(n, dtype=np.int64)
+        sub_iters = []
+        feas = np.zeros(n)
+
+        def sub(Wc, g, Hp):
+            dW = ctx.dev(np.ascontiguousarray(Wc))
+            out = ctx.nlp_solve_model(dsc, dW, self.time_step, ctx.dev(np.ascontiguousarray(g)), ctx.dev(Hp), ctx.dev(np.ascontiguousarray(Wc)), **kw)
+            ctx.sync()
+            it = out['iters'].cpu().numpy()
+            iters[:] += it
+            sub_iters.append(int(it.max()))
+            feas[:] = out['feas'].cpu().numpy()
+            return dW.cpu().numpy(), float(out['cost'].sum().item()), out['status'].cpu().numpy()
+
+        # 0. restoration of the start
+        W0 = x0[idx]
+        eye = np.zeros((n, 15, N))
+        for k, (a, c) in enumerate(_HIDX):
+            if a == c:
+                eye[:, k] = 1.0
+        Wk, _, st = sub(W0, np.zeros_like(W0), eye)
+        status, outer, f, sigma = ST_MAXITER, 0, float('nan'), 0.0
+        if (st == ST_NONFINITE).any() or not np.isfinite(Wk).all():
+            status = ST_NONFINITE
+        elif (st == ST_STALLED).any():
+            status = ST_STALLED
+        else:
+            xk = to_free(Wk)
+            f, g = f_of(xk), g_of(xk)
+            status = None
+            if not (np.isfinite(f) and np.isfinite(g).all()):
+                status = ST_NONFINITE
+            else:
+                Hraw = curvature_blocks(g_of, xk, idx, g0=g)
+            n_max = 0
+            while status is None:
+                if not np.isfinite(Hraw).all():
+                    status = ST_NONFINITE
+                    break
+                if outer >= outer_cap:
+                    status = ST_MAXITER
+                    break
+                outer += 1
+                hs = 1.0 + float(np.abs(Hraw).max())
+                Wn, m_new, st = sub(Wk, g[idx], model_blocks(Hraw, sigma * hs))
+                if (st == ST_STALLED).any():
+                    status = ST_STALLED
+                    break
+                ftol = FTOL * (1.0 + abs(f))
+                pred = -m_new
+                ok = not (st == ST_NONFINITE).any() and (st == ST_CONVERGED).all() and np.isfinite(Wn).all()
+                f_new = f_of(to_free(Wn)) if ok else float('nan')
+                ared = f - f_new
+                if not np.isfinite(f_new):
+                    accept, ratio = False, -np.inf
+                elif pred <= ftol:                  # the model sees nothing left to gain: a step that does not raise f is taken
+                    accept, ratio = ared >= -ftol, 1.0
+                else:
+                    ratio = ared / pred
+                    accept = ratio >= ETA_REJECT
+                if not accept:
+                    if sigma >= SIGMA_MAX:
+                        n_max += 1
+                        if n_max >= STALL_AT_MAX:
+                            status = ST_STALLED
+                            break
+                    sigma = min(max(sigma * SIGMA_GROW, SIGMA_MIN), SIGMA_MAX)
+                    continue
+                n_max = 0
+                move = float(np.abs(Wn - Wk).max())
+                Wk, xk = Wn, to_free(Wn)
+                if abs(ared) <= ftol and (move <= XTOL or pred <= ftol):
+                    f = f_new
+                    status = ST_CONVERGED
+                    break
+                f, g = f_new, g_of(xk)
+                if not np.isfinite(g).all():
+                    status = ST_NONFINITE
+                    break
+                Hraw = curvature_blocks(g_of, xk, idx, g0=g)
+                if ratio > ETA_GOOD:
+                    sigma = sigma / SIGMA_GROW if sigma > SIGMA_MIN else 0.0
+        sol = to_free(Wk)
+        info = {'status': int(status) if n == 1 else [int(status)] * n, 'feas': float(feas.max()), 'iters': iters.tolist(),
+                'sweeps': 0, 'moved': 0.0, 'obj_val': f, 'status_msg': STATUS_MSG[status],
+                'box_violation': 0.0, 'phi_violation': 0.0, 'v_violation': 0.0,
+                'objective': 'host', 'outer': outer, 'cost_calls': calls['cost'], 'grad_calls': calls['grad'], 'sub_iters': sub_iters}
         return sol, info

@@ -20,7 +20,9 @@ seed = None
 #            equalities, HARD bounds), built by the very call the reference makes (src/single_opt_planner.py:62-71)
 #   'auto' (default) -- the fit first; if its plan overshoots a bound of the scenario (phi, v or the x / y box: the fit's bounds are
 #            soft rows) by more than AUTO_TOL, the collocation problem is solved from that plan, so that what a script gets from
-#            Planner(scen).run() never violates a bound IPOPT would have enforced; info['backend_used'] says which one answered
+#            Planner(scen).run() never violates a bound IPOPT would have enforced; info['backend_used'] says which one answered.
+#            A cost plug-in that lower_cost does not know (a user's own objective) goes straight to the collocation problem, which
+#            calls its cost / cost_grad on the host (opty.direct_collocation, host objective): info['backend_used'] = 'nlp'
 BACKEND = 'auto'
 AUTO_TOL = 1e-6        # rad, m/s, m
 N_SEG = 6
@@ -41,6 +43,25 @@ def get_plan(K, duration, obj_scale_over_n, kv=5., kphi=1.):
     if key not in _plans:
         _plans[key] = d2dhip.FitPlan(ctx, N_SEG, K, duration, wref)
     return _plans[key]
+
+
+def lowerable(cost):
+    """True if lower_cost knows the plug-in (the fit and the lowered collocation kernel can express it)."""
+    try:
+        lower_cost(cost)
+        return True
+    except NotImplementedError:
+        return False
+
+
+def fit_cost(cost):
+    """lower_cost for the polynomial fit: a plug-in it does not know is refused with the reason."""
+    try:
+        return lower_cost(cost)
+    except NotImplementedError as e:
+        raise NotImplementedError(f"{e}: backend='fit' cannot plan with it -- the polynomial fit works on the structured cost terms "
+                                  "and has no form for a scalar objective; backend='nlp' or 'auto' solve it with its cost / "
+                                  "cost_grad on the host") from None
 
 
 def lower_cost(cost):
@@ -162,7 +183,9 @@ class Planner:
         self._slice_x, self._slice_y, self._slice_psi, self._slice_phi, self._slice_v = (
             slice(i * N, (i + 1) * N, 1) for i in range(5))
         self.obstacles = exp.obstacles
-        if initialize and self.backend == 'nlp':
+        # a cost plug-in without a lowering: the collocation problem with the host objective, unless the fit was asked for
+        self._host_cost = self.backend != 'fit' and not lowerable(exp.cost)
+        if initialize and (self.backend == 'nlp' or self._host_cost):
             import opty.direct_collocation
             _g = self.aircraft
             t0, (x0, y0, psi0, phi0, v0) = exp.t0, exp.p0
@@ -233,9 +256,9 @@ class Planner:
         return g
 
     def _solve(self, x0):
+        low = fit_cost(self.exp.cost)
         ctx = d2dhip.default_context()
         N = self.num_nodes
-        low = lower_cost(self.exp.cost)
         s = self.obj_scale / N
         plan = get_plan(N, self.duration, s, low[1], low[2])
         row = scen_row(self.exp.p0, self.exp.p1, self.exp.vref, low, s, self.wind.w, self.exp.phi_constraint,
@@ -260,7 +283,9 @@ class Planner:
         if initial_guess is None:
             initial_guess = self.get_initial_guess('tri')
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self.backend != 'nlp':
+        if self._host_cost:
+            self.info['backend_used'] = 'nlp'
+        elif self.backend != 'nlp':
             self._harden()
         self.interpret_solution()
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 109
+#define D2D_VERSION 110
 
 /* error codes */
 #define D2D_OK 0
@@ -624,6 +624,30 @@ int d2d_nlp_solve(d2d_ctx *ctx, int B, int N, double h, const double *scen, cons
 int d2d_nlp_solve_groups(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
                          double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
                          int32_t *sweeps, double *moved);
+
+/* The collocation NLP of d2d_nlp_solve under an objective the library cannot evaluate: the solve behind
+ * `opty.direct_collocation.Problem(obj, obj_grad, ...)` when obj / obj_grad are a user's cost plug-in (any object with cost(free,
+ * planner) and cost_grad(free, planner), src/single_opt_planner.py:62-71; src/test/test_objective.py:11-16) or plain callables.
+ * The host evaluates the user's functions; the device solves one subproblem of the host's sequence of quadratic models
+ * (opty/direct_collocation.py), with the exact feasible set:
+ *   minimise  sum_i g_i.(W_i - Wc_i) + 1/2 (W_i - Wc_i)^T H_i (W_i - Wc_i)   (+ the structured terms of the row: the host zeroes them)
+ *   subject to the collocation equalities, the end conditions and the hard boxes of d2d_nlp_solve.
+ * model->g  dev [B][5][N]  gradient of the cost at Wc (component planes, as W)
+ * model->H  dev [B][15][N] per-node symmetric 5x5 curvature blocks, upper triangle row by row: planes (0,0) (0,1) .. (0,4) (1,1) .. (1,4)
+ *                          (2,2) .. (4,4), i.e. plane a*5 - a*(a-1)/2 + (c-a) holds H[a][c], a <= c
+ * model->Wc dev [B][5][N]  centre of the model (the host's current iterate)
+ * W dev [B][5][N] in: the start (e.g. Wc), out: the solution; cost dev [B]: the model's value at the solution (0 at Wc); scen, opts,
+ * work (d2d_nlp_workspace_doubles(N) * B), mult, feas, iters as d2d_nlp_solve (opts->order and opts->slots are not used: one wavefront
+ * and one workspace per problem).  status: D2D_ST_CONVERGED / D2D_ST_MAXITER / D2D_ST_STALLED (no feasible point) as d2d_nlp_solve;
+ * D2D_ST_NONFINITE (cost = feas = NaN, at once) for an unusable row or a non-finite entry of g, H or Wc.  Asynchronous on the
+ * context's stream.  (version 110) */
+typedef struct {
+  const double *g;
+  const double *H;
+  const double *Wc;
+} d2d_nlp_model;
+int d2d_nlp_solve_model(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, const d2d_nlp_model *model,
+                        double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status);
 
 #ifdef __cplusplus
 }
