@@ -83,14 +83,18 @@ __device__ __forceinline__ int member_get_i(int v) {
 // live in scalar register pairs, of which there are ~50; what does not fit is fetched again in EVERY step (s_load: 19 per step, each
 // behind its own wait -- measured with SQ_WAIT_ANY: 30 % of the wave's cycles, a lone wave hides nothing) or re-made from literals
 // (s_mov_b32: a scalar instruction costs a lone wave the same issue slot as an fp64 FMA; 263 per step against 802 vector ones).
-template <int NAC, bool VCONST>
+// WIND (the general kernel only): the plant flies the field wf, step i starting at t_start + (i - 1) dt; the guidance law sees no wind
+// (GVFcontroller stores it and never reads it).  iter_max: the largest fixed-point sweep count (include/d2d.h D2D_WIND_*).
+template <int NAC, bool VCONST, bool WIND = false>
 __device__ __forceinline__ void
 gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double *__restrict__ X0,
              const double *__restrict__ centres, const double *__restrict__ radius,
              const double *__restrict__ Bz, const double *__restrict__ X0f,
              double *__restrict__ X_hist, double *__restrict__ U_hist,
              double *__restrict__ Rr_hist, double *__restrict__ eth_hist,
-             double *__restrict__ X_final, int32_t *__restrict__ stop_row, int32_t *__restrict__ conv_row) {
+             double *__restrict__ X_final, int32_t *__restrict__ stop_row, int32_t *__restrict__ conv_row,
+             const d2d_wind_field *wf = nullptr, double t_start = 0.0, int32_t *__restrict__ iter_max = nullptr) {
+  static_assert(!WIND || NAC == 0, "wind runs take the general kernel");
   extern __shared__ double lds[];
   constexpr bool QUAD = NAC != 0;
   double *sh_theta = lds;
@@ -176,6 +180,7 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
   // dependent chain from end to end.  The sums keep their order (terms beyond n_ac add 0 * x): bit-identical.  (Held in registers
   // across the steps instead, the matrix entries put the kernel at one wave per SIMD.)
   const bool small_form = n_ac <= GVF_FA;
+  WindCtx wc = {wf, t_start, 0};
   for (int i = 1; i < p.n_rows; ++i) {
     // src/11_full_sim_case1.py:140 -- `if np.all(stop)==1 and t>0: break` at the top of step i
     if (p.use_stop) {
@@ -256,7 +261,13 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
     double tan_c;
     const double phi_c = gvf_bank_cmd(s, sin_psi, cos_psi, cx, cy, Rr, p.ke, p.kd, nullptr, nullptr, &tan_c);
     double sn_n = sin_psi, cs_n = cos_psi;
-    State5 sn = plant_step<true>(s, phi_c, p.v_c, p.wx, p.wy, mesh, sn_n, cs_n, tan_c, &ga6, &gb6, fast6);
+    State5 sn;
+    if constexpr (WIND) {
+      wc.t = t_start + (i - 1) * p.dt;
+      sn = plant_step<true, true>(s, phi_c, p.v_c, 0.0, 0.0, mesh, sn_n, cs_n, tan_c, &ga6, &gb6, fast6, &wc);
+    } else {
+      sn = plant_step<true>(s, phi_c, p.v_c, p.wx, p.wy, mesh, sn_n, cs_n, tan_c, &ga6, &gb6, fast6);
+    }
     if (run) {
       if (U_hist && ph_prev == 0) {
         const long r = (long)row_prev * 2 * N;
@@ -322,6 +333,9 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
     X_final[4 * N + d] = s.v;
     if (a == 0 && stop_row) stop_row[f] = (p.use_stop == 2 && prev_all_ok && my_stop == p.n_rows) ? p.n_rows : my_stop;
     if (a == 0 && conv_row) conv_row[f] = first_true;
+  }
+  if constexpr (WIND) {
+    if (iter_max) atomicMax(iter_max, wc.iters);
   }
 }
 
@@ -395,6 +409,7 @@ dfff_kernel(d2d_track_params p, const double *__restrict__ X, const double *__re
   }
 }
 
+// (dfff_run_wind_kernel below is a copy of this kernel with the plant in a field: change the two together.)
 // run_simulation of src/05_test_simulation.py:21-34 with the legacy DFFFController (src/d2d/guidance.py:52-91):
 //   U[i-1] = ctl.get(X[i-1], t[i-1]);  X[i] = disc_dyn(X[i-1], U[i-1]) + perts[i];  U[T-1] = ctl.get(X[T-1], t[T-1])
 // Yref [n_rows][6][n] = the trajectory's flat outputs at the sample times (x, y, xd, yd, xdd, ydd).
@@ -455,7 +470,8 @@ gradient_kernel(int T, int n, double inv_dt, const double *__restrict__ f, doubl
   out[(long)i * n + d] = grad2(f, i, T, n, d) * inv_dt;
 }
 
-// Tracking loop, src/11_full_sim_case1.py:272-290.
+// Tracking loop, src/11_full_sim_case1.py:272-290.  track_run_wind_kernel below is a copy of this kernel with the plant in a field:
+// change the two together.
 __global__ void __launch_bounds__(64)
 track_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
                  const double *__restrict__ y_ref, const double *__restrict__ xd,
@@ -700,7 +716,139 @@ traj_sample_kernel(int n, int T, double t_start, double dt, const double *__rest
 }
 
 // ------------------------------------------------------------------------------------
+// Wind fields (include/d2d.h d2d_wind_field): batched evaluation and the wind twins of the plant step and of the three time loops.
+__global__ void __launch_bounds__(256)
+wind_sample_kernel(d2d_wind_field f, int n, const double *__restrict__ t, const double *__restrict__ xy, double *__restrict__ w) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const WindVec r = wind_at(f, t[i], xy[i], xy[n + i]);
+  w[i] = r.x; w[n + i] = r.y;
+}
+
+__global__ void __launch_bounds__(256) step_wind_kernel(int n, const double *__restrict__ X, const double *__restrict__ U, double t,
+                                                        d2d_wind_field f, GlMesh mesh, double *__restrict__ Xout,
+                                                        int32_t *__restrict__ iter_max) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  State5 s = {X[i], X[n + i], X[2 * n + i], X[3 * n + i], X[4 * n + i]};
+  WindCtx wc = {&f, t, 0};
+  s = plant_step_wind(s, U[i], U[n + i], mesh, wc);
+  Xout[i] = s.x; Xout[n + i] = s.y; Xout[2 * n + i] = s.psi; Xout[3 * n + i] = s.phi;
+  Xout[4 * n + i] = s.v;
+  if (iter_max) atomicMax(iter_max, wc.iters);
+}
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+gvf_run_wind_kernel(GVF_ARGS, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max) {
+  gvf_run_body<0, false, true>(GVF_PASS, &wf, t_start, iter_max);
+}
+
+// track_run_kernel in a field (a copy rather than a shared template body: the constant-wind kernels keep their exact code).  The
+// plant flies wf, step i from row i - 1 at t_start + (i - 1) dt; the controller keeps p.wx, p.wy, the constant of DiffController(w)
+// (src/11_full_sim_case1.py:241-291 hands w to the controller and WindField(w) to the plant separately).
+__global__ void __launch_bounds__(64)
+track_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
+                      const double *__restrict__ y_ref, const double *__restrict__ xd,
+                      const double *__restrict__ yd, const double *__restrict__ xdd,
+                      const double *__restrict__ ydd, const double *__restrict__ X0,
+                      double *__restrict__ X_hist, double *__restrict__ U_hist,
+                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
+                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
+                      double *__restrict__ X_final, d2d_wind_field wf, double t_start,
+                      int32_t *__restrict__ iter_max) {
+  WindCtx wc = {&wf, t_start, 0};
+  const long n = p.n;
+  long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const bool live = d < n;
+  if (!live) d = n - 1;
+  State5 s = {X0[d], X0[n + d], X0[2 * n + d], X0[3 * n + d], X0[4 * n + d]};
+  if (live && X_hist) {
+    X_hist[d] = s.x; X_hist[n + d] = s.y; X_hist[2 * n + d] = s.psi; X_hist[3 * n + d] = s.phi; X_hist[4 * n + d] = s.v;
+  }
+  for (int i = 1; i < p.n_rows; ++i) {
+    const long r = (long)i * n + d;
+    double Y[8] = {x_ref[r], y_ref[r], xd[r], yd[r], xdd[r], ydd[r], 0.0, 0.0};   // Yddd = [0,0] (:279)
+    const GainOut o = compute_gain(s, Y, p);
+    wc.t = t_start + (i - 1) * p.dt;
+    s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
+    if (live) {
+      const long q = (long)(i - 1);
+      if (U_hist) { U_hist[q * 2 * n + d] = o.U[0]; U_hist[q * 2 * n + n + d] = o.U[1]; }
+      if (dX_hist) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) dX_hist[q * 5 * n + c * n + d] = o.dX[c];
+      }
+      if (Xr_hist) {
+        double *o5 = Xr_hist + q * 5 * n;
+        o5[d] = o.Xr.x; o5[n + d] = o.Xr.y; o5[2 * n + d] = o.Xr.psi; o5[3 * n + d] = o.Xr.phi; o5[4 * n + d] = o.Xr.v;
+      }
+      if (Yd_hist) { Yd_hist[q * 2 * n + d] = Y[2]; Yd_hist[q * 2 * n + n + d] = Y[3]; }
+      if (Ydd_hist) { Ydd_hist[q * 2 * n + d] = Y[4]; Ydd_hist[q * 2 * n + n + d] = Y[5]; }
+      if (X_hist) {
+        double *o5 = X_hist + (long)i * 5 * n;
+        o5[d] = s.x; o5[n + d] = s.y; o5[2 * n + d] = s.psi; o5[3 * n + d] = s.phi; o5[4 * n + d] = s.v;
+      }
+    }
+  }
+  if (live && X_final) {
+    X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
+  }
+  if (iter_max) atomicMax(iter_max, wc.iters);
+}
+
+// dfff_run_kernel in a field (a copy, as above): the plant flies wf, step i from row i - 1 at t_start + (i - 1) dt, and the controller
+// sees the field at (t_i, the position of reference sample i), as DFFFController.get samples it (src/d2d/guidance.py:62-65).
+__global__ void __launch_bounds__(64)
+dfff_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref, const double *__restrict__ perts,
+                     const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist,
+                     double *__restrict__ Xr_hist, double *__restrict__ X_final, d2d_wind_field wf, double t_start,
+                     int32_t *__restrict__ iter_max) {
+  WindCtx wc = {&wf, t_start, 0};
+  const long n = p.n;
+  long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const bool live = d < n;
+  if (!live) d = n - 1;                               // (keeps the wave converged in care_sda's __all())
+  State5 s = {X0[d], X0[n + d], X0[2 * n + d], X0[3 * n + d], X0[4 * n + d]};
+  if (live && X_hist) {
+    X_hist[d] = s.x; X_hist[n + d] = s.y; X_hist[2 * n + d] = s.psi; X_hist[3 * n + d] = s.phi; X_hist[4 * n + d] = s.v;
+  }
+  for (int i = 1; i <= p.n_rows; ++i) {
+    const long q = i - 1;                             // the row the controller acts on
+    double Y[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) Y[c] = Yref[(q * 6 + c) * n + d];
+    d2d_track_params pq = p;
+    const WindVec w = wind_at(wf, t_start + q * p.dt, Y[0], Y[1]);
+    pq.wx = w.x; pq.wy = w.y;
+    const DfffOut o = dfff_gain(s, Y, pq);
+    if (live) {
+      if (U_hist) { U_hist[q * 2 * n + d] = o.U[0]; U_hist[q * 2 * n + n + d] = o.U[1]; }
+      if (Xr_hist) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) Xr_hist[(q * 5 + c) * n + d] = o.Xr[c];
+      }
+    }
+    if (i == p.n_rows) break;                         // the last row only gets its command (:33)
+    wc.t = t_start + q * p.dt;
+    s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
+    if (perts) {
+      const double *pr = perts + (long)i * 5 * n + d;
+      s.x += pr[0]; s.y += pr[n]; s.psi += pr[2 * n]; s.phi += pr[3 * n]; s.v += pr[4 * n];
+    }
+    if (live && X_hist) {
+      double *o5 = X_hist + (long)i * 5 * n;
+      o5[d] = s.x; o5[n + d] = s.y; o5[2 * n + d] = s.psi; o5[3 * n + d] = s.phi; o5[4 * n + d] = s.v;
+    }
+  }
+  if (live && X_final) {
+    X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
+  }
+  if (iter_max) atomicMax(iter_max, wc.iters);
+}
+
+// ------------------------------------------------------------------------------------
 static int upload_Bz(d2d_ctx *ctx, int n_ac, const double *Bmat, const double *z_des);
+static int check_wind(const d2d_wind_field *f, const char *who);
 
 extern "C" {
 
@@ -714,18 +862,51 @@ int d2d_step(d2d_ctx *ctx, int n, const double *X, const double *U, double wx, d
   return D2D_OK;
 }
 
-int d2d_sim_gvf_run(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
-                    const double *centres, const double *radius, const double *Bmat,
-                    const double *z_des, const double *X0f, double *X_hist, double *U_hist,
-                    double *Rr_hist, double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row) {
-  D2D_REQUIRE(ctx && p && X0 && centres && radius && X_final, "d2d_sim_gvf_run: null argument");
-  D2D_REQUIRE(p->use_stop >= 0 && p->use_stop <= 2 && p->stop_hold >= 0, "d2d_sim_gvf_run: use_stop in 0..2, stop_hold >= 0");
-  D2D_REQUIRE(p->n_ac >= 1 && p->n_ac <= 64, "d2d_sim_gvf_run: n_ac=%d not in 1..64", p->n_ac);
-  D2D_REQUIRE(p->n_form >= 1 && p->n_rows >= 1 && p->rec_stride >= 1, "d2d_sim_gvf_run: n_form, n_rows, rec_stride must be >= 1");
-  D2D_REQUIRE(p->n_ac == 1 || (Bmat && z_des), "d2d_sim_gvf_run: Bmat / z_des missing");
-  D2D_REQUIRE(p->use_stop != 1 || X0f, "d2d_sim_gvf_run: use_stop = 1 needs X0f");
-  D2D_REQUIRE(p->use_stop != 2 || p->n_ac >= 2, "d2d_sim_gvf_run: the phase-error rule needs at least two aircraft");
-  D2D_REQUIRE(p->dt > 0 && p->tau_phi > 0 && p->tau_v > 0, "d2d_sim_gvf_run: dt, tau_phi, tau_v must be > 0");
+int d2d_wind_sample(d2d_ctx *ctx, const d2d_wind_field *f, int n, const double *t, const double *xy, double *w) {
+  D2D_REQUIRE(ctx && t && xy && w, "d2d_wind_sample: null argument");
+  D2D_REQUIRE(n > 0, "d2d_wind_sample: n must be > 0");
+  if (int rc = check_wind(f, "d2d_wind_sample")) return rc;
+  hipLaunchKernelGGL(wind_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, *f, n, t, xy, w);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+int d2d_step_wind(d2d_ctx *ctx, int n, const double *X, const double *U, double t, const d2d_wind_field *f, double tau_phi,
+                  double tau_v, double dt, double *Xout, int32_t *iter_max) {
+  D2D_REQUIRE(ctx && X && U && Xout, "d2d_step_wind: null argument");
+  D2D_REQUIRE(n > 0 && tau_phi > 0 && tau_v > 0 && dt > 0, "d2d_step_wind: n, tau_phi, tau_v, dt must be > 0");
+  if (int rc = check_wind(f, "d2d_step_wind")) return rc;
+  const GlMesh mesh = make_mesh(dt, tau_phi, tau_v);
+  if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
+  hipLaunchKernelGGL(step_wind_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, X, U, t, *f, mesh, Xout, iter_max);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+static int check_wind(const d2d_wind_field *f, const char *who) {
+  D2D_REQUIRE(f && f->cp, "%s: null wind field", who);
+  D2D_REQUIRE(f->nx >= 4 && f->ny >= 4 && (f->nt == 1 || f->nt >= 4), "%s: wind field nt=%d, ny=%d, nx=%d (nx, ny >= 4; nt = 1 or >= 4)",
+              who, f->nt, f->ny, f->nx);
+  D2D_REQUIRE(f->hx > 0 && f->hy > 0 && (f->nt == 1 || f->ht > 0), "%s: wind field knot spacings must be > 0", who);
+  return D2D_OK;
+}
+
+// f == NULL: the constant-wind loop of d2d_sim_gvf_run; else its wind twin (always the general kernel)
+static int gvf_run_impl(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
+                        const double *Bmat, const double *z_des, const double *X0f, double *X_hist, double *U_hist, double *Rr_hist,
+                        double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const d2d_wind_field *f,
+                        double t_start, int32_t *iter_max, const char *who) {
+  D2D_REQUIRE(ctx && p && X0 && centres && radius && X_final, "%s: null argument", who);
+  D2D_REQUIRE(p->use_stop >= 0 && p->use_stop <= 2 && p->stop_hold >= 0, "%s: use_stop in 0..2, stop_hold >= 0", who);
+  D2D_REQUIRE(p->n_ac >= 1 && p->n_ac <= 64, "%s: n_ac=%d not in 1..64", who, p->n_ac);
+  D2D_REQUIRE(p->n_form >= 1 && p->n_rows >= 1 && p->rec_stride >= 1, "%s: n_form, n_rows, rec_stride must be >= 1", who);
+  D2D_REQUIRE(p->n_ac == 1 || (Bmat && z_des), "%s: Bmat / z_des missing", who);
+  D2D_REQUIRE(p->use_stop != 1 || X0f, "%s: use_stop = 1 needs X0f", who);
+  D2D_REQUIRE(p->use_stop != 2 || p->n_ac >= 2, "%s: the phase-error rule needs at least two aircraft", who);
+  D2D_REQUIRE(p->dt > 0 && p->tau_phi > 0 && p->tau_v > 0, "%s: dt, tau_phi, tau_v must be > 0", who);
+  if (f) {
+    if (int rc = check_wind(f, who)) return rc;
+  }
   const int n_ac = p->n_ac, nm = n_ac - 1;
   const size_t nb = (size_t)n_ac * nm + nm;
   if (int rc = upload_Bz(ctx, n_ac, Bmat, z_des)) return rc;
@@ -738,7 +919,11 @@ int d2d_sim_gvf_run(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
 #define GVF_LAUNCH(KERNEL)                                                                                             \
   hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius, ctx->Bmat_dev, \
                      X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row)
-  if (n_ac == 1 || n_ac == 2 || n_ac == 4) {
+  if (f) {
+    if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(gvf_run_wind_kernel, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius,
+                       ctx->Bmat_dev, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row, *f, t_start, iter_max);
+  } else if (n_ac == 1 || n_ac == 2 || n_ac == 4) {
     // formations inside a DPP quad: no LDS exchange, no barrier in the step; a launch of at most one wave per SIMD gets the
     // instantiation that may use the whole register file
     int n_cu = 256;
@@ -753,6 +938,23 @@ int d2d_sim_gvf_run(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
 #undef GVF_LAUNCH
   D2D_LAUNCH_CHECK();
   return D2D_OK;
+}
+
+int d2d_sim_gvf_run(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
+                    const double *centres, const double *radius, const double *Bmat,
+                    const double *z_des, const double *X0f, double *X_hist, double *U_hist,
+                    double *Rr_hist, double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row) {
+  return gvf_run_impl(ctx, p, X0, centres, radius, Bmat, z_des, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row,
+                      nullptr, 0.0, nullptr, "d2d_sim_gvf_run");
+}
+
+int d2d_sim_gvf_run_wind(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
+                         const double *Bmat, const double *z_des, const double *X0f, double *X_hist, double *U_hist, double *Rr_hist,
+                         double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const d2d_wind_field *f,
+                         double t_start, int32_t *iter_max) {
+  D2D_REQUIRE(f, "d2d_sim_gvf_run_wind: null wind field");
+  return gvf_run_impl(ctx, p, X0, centres, radius, Bmat, z_des, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row,
+                      f, t_start, iter_max, "d2d_sim_gvf_run_wind");
 }
 
 static int check_track(const d2d_track_params *p, const char *who) {
@@ -780,24 +982,48 @@ int d2d_dfff_eval(d2d_ctx *ctx, const d2d_track_params *p, const double *X, cons
   return D2D_OK;
 }
 
-int d2d_sim_dfff_run(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts,
-                     const double *X0, double *X_hist, double *U_hist, double *Xr_hist, double *X_final) {
-  D2D_REQUIRE(ctx && p && Yref && X0, "d2d_sim_dfff_run: null argument");
-  if (int rc = check_track(p, "d2d_sim_dfff_run")) return rc;
+static int dfff_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts, const double *X0,
+                         double *X_hist, double *U_hist, double *Xr_hist, double *X_final, const d2d_wind_field *f, double t_start,
+                         int32_t *iter_max, const char *who) {
+  D2D_REQUIRE(ctx && p && Yref && X0, "%s: null argument", who);
+  if (int rc = check_track(p, who)) return rc;
+  if (f) {
+    if (int rc = check_wind(f, who)) return rc;
+  }
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
-  hipLaunchKernelGGL(dfff_run_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist,
-                     U_hist, Xr_hist, X_final);
+  if (f) {
+    if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(dfff_run_wind_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist,
+                       U_hist, Xr_hist, X_final, *f, t_start, iter_max);
+  } else {
+    hipLaunchKernelGGL(dfff_run_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist,
+                       U_hist, Xr_hist, X_final);
+  }
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }
 
-int d2d_sim_track_run(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref,
-                      const double *y_ref, const double *X0, double *X_hist, double *U_hist,
-                      double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
-                      double *X_final) {
-  D2D_REQUIRE(ctx && p && x_ref && y_ref && X0, "d2d_sim_track_run: null argument");
-  if (int rc = check_track(p, "d2d_sim_track_run")) return rc;
-  D2D_REQUIRE(p->n_rows >= 3, "d2d_sim_track_run: n_rows must be >= 3 (second-order edge differences)");
+int d2d_sim_dfff_run(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts,
+                     const double *X0, double *X_hist, double *U_hist, double *Xr_hist, double *X_final) {
+  return dfff_run_impl(ctx, p, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, nullptr, 0.0, nullptr, "d2d_sim_dfff_run");
+}
+
+int d2d_sim_dfff_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts, const double *X0,
+                          double *X_hist, double *U_hist, double *Xr_hist, double *X_final, const d2d_wind_field *f, double t_start,
+                          int32_t *iter_max) {
+  D2D_REQUIRE(f, "d2d_sim_dfff_run_wind: null wind field");
+  return dfff_run_impl(ctx, p, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, f, t_start, iter_max, "d2d_sim_dfff_run_wind");
+}
+
+static int track_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
+                          double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
+                          double *X_final, const d2d_wind_field *f, double t_start, int32_t *iter_max, const char *who) {
+  D2D_REQUIRE(ctx && p && x_ref && y_ref && X0, "%s: null argument", who);
+  if (int rc = check_track(p, who)) return rc;
+  D2D_REQUIRE(p->n_rows >= 3, "%s: n_rows must be >= 3 (second-order edge differences)", who);
+  if (f) {
+    if (int rc = check_wind(f, who)) return rc;
+  }
   const size_t plane = (size_t)p->n_rows * p->n * sizeof(double);
   double *deriv = nullptr;
   D2D_CHECK_HIP(hipMallocAsync(reinterpret_cast<void **>(&deriv), 4 * plane, ctx->stream));
@@ -811,11 +1037,33 @@ int d2d_sim_track_run(d2d_ctx *ctx, const d2d_track_params *p, const double *x_r
   hipLaunchKernelGGL(gradient_kernel, g, b, 0, ctx->stream, p->n_rows, p->n, inv_dt, yd, ydd);
   D2D_LAUNCH_CHECK();
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
-  hipLaunchKernelGGL(track_run_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
-                     yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final);
+  if (f) {
+    if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(track_run_wind_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
+                       yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_start, iter_max);
+  } else {
+    hipLaunchKernelGGL(track_run_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
+                       yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final);
+  }
   D2D_LAUNCH_CHECK();
   D2D_CHECK_HIP(hipFreeAsync(deriv, ctx->stream));
   return D2D_OK;
+}
+
+int d2d_sim_track_run(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref,
+                      const double *y_ref, const double *X0, double *X_hist, double *U_hist,
+                      double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
+                      double *X_final) {
+  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, nullptr, 0.0, nullptr,
+                        "d2d_sim_track_run");
+}
+
+int d2d_sim_track_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
+                           double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
+                           double *X_final, const d2d_wind_field *f, double t_start, int32_t *iter_max) {
+  D2D_REQUIRE(f, "d2d_sim_track_run_wind: null wind field");
+  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, f, t_start, iter_max,
+                        "d2d_sim_track_run_wind");
 }
 
 int d2d_traj_sample(d2d_ctx *ctx, int n, int T, double t_start, double dt, const double *desc, double *Yref) {

@@ -31,11 +31,15 @@ class Aircraft:
                 -1 / self.tau_phi * (phi - phi_c), -1 / self.tau_v * (v - v_c)]
 
     def disc_dyn(self, Xk, Uk, W, t, dt):
-        """One zero-order-hold step (src/d2d/dynamic.py:25-28) on the GPU."""
+        """One zero-order-hold step (src/d2d/dynamic.py:25-28) on the GPU.  A d2d.wind.SplineWindField W is flown at the aircraft's
+        own position and time through the step (d2d_step_wind); any other W is sampled once at (t, Xk[:2]) and held."""
+        from d2d.wind import SplineWindField
         ctx = d2dhip.default_context()
-        wx, wy = _wind_of(W, t, Xk[:2])
         X = ctx.dev(np.asarray(Xk, dtype=np.float64).reshape(5, 1))
         U = ctx.dev(np.asarray(Uk, dtype=np.float64).reshape(2, 1))
+        if isinstance(W, SplineWindField):
+            return ctx.step_wind(X, U, float(t), W, self.tau_phi, self.tau_v, float(dt)).cpu().numpy()[:, 0]
+        wx, wy = _wind_of(W, t, Xk[:2])
         return ctx.step(X, U, (float(wx), float(wy)), self.tau_phi, self.tau_v, float(dt)).cpu().numpy()[:, 0]
 
     def cont_jac(self, Xr, Ur, t, W):

@@ -1,0 +1,184 @@
+"""Wind fields that vary in space and time (include/d2d.h d2d_wind_field).
+
+The reference's plant samples its wind field at the aircraft's own position and time on every right-hand-side evaluation
+(src/d2d/dynamic.py:14-16, 25-28); the only field it ships, WindField, is constant, and `sample(t, loc)` is the plug-point for a
+user's shear, vortex or gust.  The device loops cannot call back into Python, so a field reaches them as a uniform tensor-product
+cubic B-spline (C2: the Gauss panels of the plant step keep their order):
+
+  SplineWindField.from_samples(x, y, wx, wy, t=None)  the spline that interpolates gridded samples (natural end conditions)
+  SplineWindField.from_field(field, x, y, t=None)     tabulates any object with sample(t, loc) on a grid and fits it
+  SplineWindField.sample(t, loc)                      a numpy evaluation of the SAME spline the kernels evaluate: host code and
+                                                      device loops see one field
+
+Outside the spline's box every coordinate is clamped: the field is held at its boundary value, continuous but only C0 there.
+"""
+import weakref
+
+import numpy as np
+import scipy.linalg
+
+import d2dhip
+
+
+def _axis_system(n):
+    """Banded (2, 2) matrix of the interpolation along one axis with n control points and n - 2 samples: row 0 and row n-1 are the
+    natural end conditions (second derivative zero at the first and the last knot), row m + 1 is the spline's value at knot m."""
+    ab = np.zeros((5, n))
+    def put(i, j, v):
+        ab[2 + i - j, j] = v
+    put(0, 0, 1.0); put(0, 1, -2.0); put(0, 2, 1.0)
+    for i in range(1, n - 1):
+        put(i, i - 1, 1.0 / 6.0); put(i, i, 4.0 / 6.0); put(i, i + 1, 1.0 / 6.0)
+    put(n - 1, n - 3, 1.0); put(n - 1, n - 2, -2.0); put(n - 1, n - 1, 1.0)
+    return ab
+
+
+def _fit_axis(vals, axis):
+    """Control points along `axis` of the spline that interpolates vals (samples along that axis)."""
+    v = np.moveaxis(np.asarray(vals, dtype=np.float64), axis, 0)
+    m = v.shape[0]
+    rhs = np.zeros((m + 2,) + v.shape[1:])
+    rhs[1:-1] = v
+    c = scipy.linalg.solve_banded((2, 2), _axis_system(m + 2), rhs.reshape(m + 2, -1)).reshape(rhs.shape)
+    return np.moveaxis(c, 0, axis)
+
+
+def _grid(u, name):
+    u = np.asarray(u, dtype=np.float64).reshape(-1)
+    if len(u) < 2:
+        raise ValueError(f'{name}: at least two samples per axis')
+    h = u[1] - u[0]
+    if not h > 0 or not np.allclose(np.diff(u), h, rtol=1e-9, atol=0.0):
+        raise ValueError(f'{name}: the sample grid must be uniform and increasing')
+    return float(u[0]), float(h)
+
+
+def _weights(u, u0, h, n):
+    """Segment index and the four uniform cubic B-spline weights of coordinate(s) u (include/d2d.h; sim_device.h wind_axis)."""
+    s = (np.asarray(u, dtype=np.float64) - u0) / h
+    s = np.where(np.isnan(s), 0.0, np.clip(s, 0.0, n - 3.0))
+    fl = np.minimum(np.floor(s), n - 4.0)
+    r = s - fl
+    q = 1.0 - r; r2 = r * r; r3 = r2 * r
+    b = np.stack([q * q * q * (1.0 / 6.0), (3.0 * r3 - 6.0 * r2 + 4.0) * (1.0 / 6.0),
+                  (-3.0 * r3 + 3.0 * r2 + 3.0 * r + 1.0) * (1.0 / 6.0), r3 * (1.0 / 6.0)])
+    return fl.astype(np.int64), b
+
+
+class SplineWindField:
+    """A duck-typed WindField (sample(t, loc), summarize()) that the device loops can fly: control points cp (nt, 2, ny, nx) of a
+    uniform cubic B-spline over (x, y) (nt = 1, steady) or (t, x, y) (nt >= 4); knot spacings h*, first knots *0."""
+
+    def __init__(self, cp, x0, hx, y0, hy, t0=0.0, ht=1.0):
+        cp = np.asarray(cp, dtype=np.float64)
+        if cp.ndim == 3:
+            cp = cp[None]
+        nt, two, ny, nx = cp.shape
+        if two != 2 or nx < 4 or ny < 4 or not (nt == 1 or nt >= 4):
+            raise ValueError(f'control points (nt, 2, ny, nx) = {cp.shape}: nx, ny >= 4, nt = 1 or >= 4')
+        if not (hx > 0 and hy > 0 and (nt == 1 or ht > 0)):
+            raise ValueError('knot spacings must be > 0')
+        self.cp = np.ascontiguousarray(cp)
+        self.cp.setflags(write=False)
+        self.x0, self.hx, self.y0, self.hy = float(x0), float(hx), float(y0), float(hy)
+        self.t0, self.ht = float(t0), float(ht)
+        self._dev = weakref.WeakKeyDictionary()                                 # Context -> (device control points, WindFieldC)
+
+    @property
+    def steady(self):
+        return self.cp.shape[0] == 1
+
+    @classmethod
+    def from_samples(cls, x, y, wx, wy, t=None):
+        """The spline that interpolates wx, wy on the uniform grid x (M), y (K) -- arrays (K, M), indexed [y][x] -- or, with the
+        uniform sample times t (T), on (t, y, x) -- arrays (T, K, M).  Natural end conditions along every axis."""
+        x0, hx = _grid(x, 'x'); y0, hy = _grid(y, 'y')
+        w = np.stack([np.asarray(wx, dtype=np.float64), np.asarray(wy, dtype=np.float64)], axis=-3)   # (.., 2, K, M)
+        if t is None:
+            if w.shape != (2, len(np.ravel(y)), len(np.ravel(x))):
+                raise ValueError(f'steady samples: wx, wy must be (len(y), len(x)), got {w.shape[1:]}')
+            c = _fit_axis(_fit_axis(w, 2), 1)[None]
+            return cls(c, x0, hx, y0, hy)
+        t0, ht = _grid(t, 't')
+        if w.shape != (len(np.ravel(t)), 2, len(np.ravel(y)), len(np.ravel(x))):
+            raise ValueError(f'unsteady samples: wx, wy must be (len(t), len(y), len(x)), got {w.shape[:1] + w.shape[2:]}')
+        c = _fit_axis(_fit_axis(_fit_axis(w, 3), 2), 0)
+        return cls(c, x0, hx, y0, hy, t0, ht)
+
+    @classmethod
+    def from_field(cls, field, x, y, t=None):
+        """Tabulate any object with sample(t, loc) on the grid (t at 0.0 for a steady field) and fit it (from_samples)."""
+        x = np.asarray(x, dtype=np.float64).reshape(-1); y = np.asarray(y, dtype=np.float64).reshape(-1)
+        ts = [0.0] if t is None else list(np.asarray(t, dtype=np.float64).reshape(-1))
+        W = np.array([[[np.asarray(field.sample(tk, np.array([xi, yj])), dtype=np.float64).reshape(2) for xi in x] for yj in y]
+                      for tk in ts])                                          # (T, K, M, 2)
+        if t is None:
+            return cls.from_samples(x, y, W[0, ..., 0], W[0, ..., 1])
+        return cls.from_samples(x, y, W[..., 0], W[..., 1], t=t)
+
+    def sample_many(self, t, x, y):
+        """The field at arrays t, x, y (broadcast) -> wx, wy: the evaluation of sim_device.h wind_eval in numpy."""
+        t, x, y = np.broadcast_arrays(np.asarray(t, np.float64), np.asarray(x, np.float64), np.asarray(y, np.float64))
+        shape = x.shape
+        t, x, y = t.reshape(-1), x.reshape(-1), y.reshape(-1)
+        nt, _, ny, nx = self.cp.shape
+        ix, bx = _weights(x, self.x0, self.hx, nx)
+        iy, by = _weights(y, self.y0, self.hy, ny)
+        if nt == 1:
+            it, bt, kt = np.zeros_like(ix), np.ones((1, len(ix))), 1
+        else:
+            (it, bt), kt = _weights(t, self.t0, self.ht, nt), 4
+        out = np.zeros((2, len(ix)))
+        for c in range(kt):
+            acc = np.zeros((2, len(ix)))
+            for a in range(4):
+                s = 0.0
+                for b in range(4):
+                    s = s + bx[b] * self.cp[it + c, :, iy + a, ix + b].T            # (2, P)
+                acc = acc + by[a] * s
+            out = out + bt[c] * acc
+        return out[0].reshape(shape), out[1].reshape(shape)
+
+    def sample(self, t, loc):
+        """WindField.sample(t, loc): [wx, wy] at time t and position loc = (x, y)."""
+        wx, wy = self.sample_many(t, loc[0], loc[1])
+        return np.array([float(wx), float(wy)])
+
+    def summarize(self):
+        nt, _, ny, nx = self.cp.shape
+        kind = 'steady' if nt == 1 else f'unsteady, t in [{self.t0:g}, {self.t0 + (nt - 3) * self.ht:g}] s'
+        return (f'cubic B-spline wind field ({kind}), x in [{self.x0:g}, {self.x0 + (nx - 3) * self.hx:g}] m, '
+                f'y in [{self.y0:g}, {self.y0 + (ny - 3) * self.hy:g}] m, |w| <= {np.abs(self.cp).max():.3g} m/s')
+
+    def __str__(self):
+        return self.summarize()
+
+    def device_field(self, ctx):
+        """d2dhip.WindFieldC of this field for ctx.  The control points are uploaded once per context and kept while the context
+        lives: the cache holds the context weakly, so a long-lived field keeps neither the context nor its device copy alive."""
+        hit = self._dev.get(ctx)
+        if hit is None:
+            cp = ctx.dev(np.array(self.cp))                                        # (a writable copy for torch)
+            nt, _, ny, nx = self.cp.shape
+            f = d2dhip.WindFieldC(nt, ny, nx, 0, self.t0, self.ht, self.x0, self.hx, self.y0, self.hy, cp.data_ptr())
+            hit = (cp, f)
+            self._dev[ctx] = hit
+        return hit[1]
+
+
+def _is_constant_class(cls):
+    import d2d.guidance, d2d.utils, d2d.opty_utils      # noqa: E401
+    return getattr(cls, 'sample', None) in (None, d2d.guidance.WindField.sample) or cls in (d2d.utils.WindField, d2d.opty_utils.WindField)
+
+
+def plant_wind(windfield):
+    """How a batched device loop flies `windfield`: None / a constant class -> None (the constant-wind path, unchanged);
+    a SplineWindField -> the field.  Any other object whose class has its own sample(t, loc) cannot be flown as it is: the loops do
+    not call back into Python, and freezing it at one sample would fly a different field silently."""
+    if windfield is None or isinstance(windfield, SplineWindField):
+        return windfield
+    if _is_constant_class(type(windfield)):
+        return None
+    raise NotImplementedError(
+        f'{type(windfield).__name__}.sample varies the wind in space or time and the device loops cannot call it: tabulate it on a '
+        f'grid with d2d.wind.SplineWindField.from_field(field, x, y, t) and pass that field instead')

@@ -50,6 +50,16 @@ class TrackParams(C.Structure):
                 ('phi_lim', C.c_double), ('q_diag', C.c_double * 5), ('r_diag', C.c_double * 2)]
 
 
+class WindFieldC(C.Structure):
+    """d2d_wind_field (include/d2d.h): a uniform tensor-product cubic B-spline wind field; cp is a device address."""
+    _fields_ = [('nt', C.c_int32), ('ny', C.c_int32), ('nx', C.c_int32), ('pad', C.c_int32),
+                ('t0', C.c_double), ('ht', C.c_double), ('x0', C.c_double), ('hx', C.c_double), ('y0', C.c_double), ('hy', C.c_double),
+                ('cp', C.c_void_p)]
+
+
+WIND_TOL, WIND_MAX_ITERS = 1e-13, 8          # include/d2d.h D2D_WIND_*
+
+
 class NlpOpts(C.Structure):
     _fields_ = [('rho0', C.c_double), ('mub0', C.c_double), ('mub_min', C.c_double), ('feas_tol', C.c_double),
                 ('opt_tol', C.c_double), ('inner_max', C.c_int32), ('outer_max', C.c_int32), ('serial', C.c_int32), ('slots', C.c_int32),
@@ -114,6 +124,11 @@ _SIGS = {
     'd2d_dfff_eval': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 5),
     'd2d_sim_dfff_run': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 7),
     'd2d_sim_track_run': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 10),
+    'd2d_wind_sample': (C.c_int, [_P, C.POINTER(WindFieldC), C.c_int, _P, _P, _P]),
+    'd2d_step_wind': (C.c_int, [_P, C.c_int, _P, _P, C.c_double, C.POINTER(WindFieldC), C.c_double, C.c_double, C.c_double, _P, _P]),
+    'd2d_sim_gvf_run_wind': (C.c_int, [_P, C.POINTER(GvfParams)] + [_P] * 13 + [C.POINTER(WindFieldC), C.c_double, _P]),
+    'd2d_sim_track_run_wind': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 10 + [C.POINTER(WindFieldC), C.c_double, _P]),
+    'd2d_sim_dfff_run_wind': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 7 + [C.POINTER(WindFieldC), C.c_double, _P]),
     'd2d_traj_sample': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P]),
     'd2d_dcf_eval': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_double, _P, _P, _P, _P]),
     'd2d_gvf_eval': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, C.c_double, _P]),
@@ -191,6 +206,16 @@ def _ptr(t):
 
 def _hptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _wind_c(ctx, wind):
+    """A d2d_wind_field for `wind`: a WindFieldC (whose cp the caller keeps alive) or an object with device_field(ctx) -> WindFieldC
+    (d2d.wind.SplineWindField: its device copy is cached per context)."""
+    if isinstance(wind, WindFieldC):
+        return wind
+    if hasattr(wind, 'device_field'):
+        return wind.device_field(ctx)
+    raise TypeError(f'{type(wind).__name__} is not a device wind field: build one with d2d.wind.SplineWindField')
 
 
 class Comm:
@@ -288,15 +313,38 @@ class Context:
         _check(self.lib.d2d_step(self.h, n, _ptr(X), _ptr(U), W[0], W[1], tau_phi, tau_v, dt, _ptr(out)))
         return out
 
+    def wind_sample(self, wind, t, xy):
+        """d2d_wind_sample: the field at t dev [n], xy dev [2][n] -> w dev [2][n] (wx, wy)."""
+        n = t.shape[0]
+        assert t.is_contiguous() and xy.is_contiguous() and tuple(xy.shape) == (2, n)
+        w = self.empty(2, n)
+        f = _wind_c(self, wind)
+        _check(self.lib.d2d_wind_sample(self.h, C.byref(f), n, _ptr(t), _ptr(xy), _ptr(w)))
+        return w
+
+    def step_wind(self, X, U, t, wind, tau_phi=0.01, tau_v=1.0, dt=0.05, iter_max=None):
+        """X dev [5][n], U dev [2][n], the step's start time t, a field -> Xnext dev [5][n] (Aircraft.disc_dyn in a field, batched).
+        iter_max: dev int32 [1] that receives the largest fixed-point sweep count, or None."""
+        n = X.shape[1]
+        out = self.empty(5, n)
+        f = _wind_c(self, wind)
+        _check(self.lib.d2d_step_wind(self.h, n, _ptr(X), _ptr(U), float(t), C.byref(f), tau_phi, tau_v, dt, _ptr(out), _ptr(iter_max)))
+        return out
+
+    def _iter_max(self):
+        torch = _torch()
+        return torch.zeros(1, dtype=torch.int32, device=self.device)
+
     def gvf_run(self, X0, centres, radius, n_ac, n_rows, dt, v_c, ke=4e-4, kd=25.0, kr=20.0,
                 B=None, z_des=None, tau_phi=0.01, tau_v=1.0, W=(0.0, 0.0), X0f=None,
                 stop_tol=(3.0, 3.0, np.deg2rad(0.5)), rec_stride=1, record=('X', 'U', 'Rr', 'eth'), out=None,
-                etheta_tol_deg=None, stop_hold=0):
+                etheta_tol_deg=None, stop_hold=0, wind=None, t_start=0.0):
         """Circular-formation phase for N = n_form*n_ac drones.  X0 dev [5][N], centres dev
         [2][N], radius dev [N].  Returns dict of device tensors (plane-major).  out: the dictionary of an earlier
         call with the same shapes and `record` -- its buffers are written again instead of allocating new ones
         (without the stop rule every recorded row is rewritten; with it, rows behind the stop row keep their old
-        content)."""
+        content).  wind: a field the plant flies instead of W (d2d_sim_gvf_run_wind; row i at t_start + i dt); out['iter_max'] then
+        holds the largest fixed-point sweep count."""
         torch = _torch()
         N = X0.shape[1]
         assert N % n_ac == 0
@@ -325,9 +373,15 @@ class Context:
             out['conv_row'] = torch.empty(n_form, dtype=torch.int32, device=self.device)
         else:
             assert out['X_final'].shape == (5, N) and all(out[k] is None or out[k].shape[0] == n_rec for k in ('X', 'U', 'Rr', 'eth'))
-        _check(self.lib.d2d_sim_gvf_run(self.h, C.byref(p), _ptr(X0), _ptr(centres), _ptr(radius), _hptr(B), _hptr(z_des),
-                                        _ptr(X0f if use_stop == 1 else None), _ptr(out['X']), _ptr(out['U']), _ptr(out['Rr']), _ptr(out['eth']),
-                                        _ptr(out['X_final']), _ptr(out['stop_row']), _ptr(out.get('conv_row'))))
+        args = (self.h, C.byref(p), _ptr(X0), _ptr(centres), _ptr(radius), _hptr(B), _hptr(z_des), _ptr(X0f if use_stop == 1 else None),
+                _ptr(out['X']), _ptr(out['U']), _ptr(out['Rr']), _ptr(out['eth']), _ptr(out['X_final']), _ptr(out['stop_row']),
+                _ptr(out.get('conv_row')))
+        if wind is None:
+            _check(self.lib.d2d_sim_gvf_run(*args))
+        else:
+            f = _wind_c(self, wind)
+            out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
+            _check(self.lib.d2d_sim_gvf_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
 
     # -- single evaluations behind the reference's per-call helpers --------------------
@@ -399,18 +453,25 @@ class Context:
         _check(self.lib.d2d_traj_sample(self.h, n, T, float(t_start), float(dt), _ptr(desc), _ptr(Y)))
         return Y
 
-    def dfff_run(self, Yref, X0, dt, perts=None, record=('X', 'U', 'Xr'), w=(0.0, 0.0), tau_phi=0.01, tau_v=1.0, out=None):
+    def dfff_run(self, Yref, X0, dt, perts=None, record=('X', 'U', 'Xr'), w=(0.0, 0.0), tau_phi=0.01, tau_v=1.0, out=None, wind=None,
+                 t_start=0.0):
         """run_simulation of src/05_test_simulation.py with the legacy DFFFController for n aircraft: Yref dev [T][6][n]
         (x,y,xd,yd,xdd,ydd at the sample times), X0 dev [5][n], perts dev [T][5][n] or None -> dict of device histories
-        X [T][5][n], U [T][2][n], Xr [T][5][n] and X_final."""
+        X [T][5][n], U [T][2][n], Xr [T][5][n] and X_final.  wind: a field instead of w (d2d_sim_dfff_run_wind: the plant flies it, the
+        controller samples it at the reference point; row i at t_start + i dt); out['iter_max']: the largest fixed-point sweep count."""
         T, _, n = Yref.shape
         p = self.track_params(n, T, dt, w=w, tau_phi=tau_phi, tau_v=tau_v, phi_lim=np.deg2rad(45),
                               Q=(1, 1, 0.1, 0.0, 0.0), R=(8, 1))          # src/d2d/guidance.py:79,86
         if out is None:
             out = {k: (self.zeros(T, c, n) if k in record else None) for k, c in (('X', 5), ('U', 2), ('Xr', 5))}
             out['X_final'] = self.empty(5, n)
-        _check(self.lib.d2d_sim_dfff_run(self.h, C.byref(p), _ptr(Yref), _ptr(perts), _ptr(X0), _ptr(out['X']), _ptr(out['U']),
-                                         _ptr(out['Xr']), _ptr(out['X_final'])))
+        args = (self.h, C.byref(p), _ptr(Yref), _ptr(perts), _ptr(X0), _ptr(out['X']), _ptr(out['U']), _ptr(out['Xr']), _ptr(out['X_final']))
+        if wind is None:
+            _check(self.lib.d2d_sim_dfff_run(*args))
+        else:
+            f = _wind_c(self, wind)
+            out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
+            _check(self.lib.d2d_sim_dfff_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
 
     def nlp_solve(self, scen, W, h, partner=None, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
@@ -481,9 +542,10 @@ class Context:
             out['mult'] = mult
         return out
 
-    def track_run(self, x_ref, y_ref, X0, dt, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), out=None, **kw):
+    def track_run(self, x_ref, y_ref, X0, dt, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), out=None, wind=None, t_start=0.0, **kw):
         """x_ref, y_ref dev [T][n]; X0 dev [5][n] -> dict of device histories (out: reuse the buffers of an earlier
-        call with the same shapes and `record`)."""
+        call with the same shapes and `record`).  wind: a field the plant flies (d2d_sim_track_run_wind; the controller keeps the
+        constant w of kw; row i at t_start + i dt); out['iter_max']: the largest fixed-point sweep count."""
         T, n = x_ref.shape
         p = self.track_params(n, T, dt, **kw)
         if out is None:
@@ -492,9 +554,14 @@ class Context:
             out['X_final'] = self.empty(5, n)
         else:
             assert out['X_final'].shape == (5, n) and all(out[k] is None or out[k].shape[0] == T for k in ('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'))
-        _check(self.lib.d2d_sim_track_run(self.h, C.byref(p), _ptr(x_ref), _ptr(y_ref), _ptr(X0), _ptr(out['X']),
-                                          _ptr(out['U']), _ptr(out['Xr']), _ptr(out['dX']), _ptr(out['Yd']),
-                                          _ptr(out['Ydd']), _ptr(out['X_final'])))
+        args = (self.h, C.byref(p), _ptr(x_ref), _ptr(y_ref), _ptr(X0), _ptr(out['X']), _ptr(out['U']), _ptr(out['Xr']), _ptr(out['dX']),
+                _ptr(out['Yd']), _ptr(out['Ydd']), _ptr(out['X_final']))
+        if wind is None:
+            _check(self.lib.d2d_sim_track_run(*args))
+        else:
+            f = _wind_c(self, wind)
+            out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
+            _check(self.lib.d2d_sim_track_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
 
 

@@ -6,11 +6,16 @@ GPU, plus batched variants over many independent formations.
   implement_controller(n_ac, time, x_ref, y_ref, ..)  :241-291
   ConstructBMatrix, ComputeDerivatives, ExtractTrajData, ExtendTraj_symm   :81-91, :197-239
   run_simulation(time, aircraft, windfield, ctl, X0, perts)                src/05_test_simulation.py:21-34 (legacy DFFF loop)
+
+Wind: the constant WindField classes take the constant-wind loops as before; a d2d.wind.SplineWindField (windfield=) is flown by
+the plant at each aircraft's own position and time (the reference's WindField.sample plug-point); any other field with its own
+sample() raises NotImplementedError (d2d.wind.plant_wind) instead of being frozen at one sample.
 """
 import numpy as np
 
 import d2dhip
 import d2d.dynamic as ddyn
+from d2d.wind import plant_wind
 
 KE, KD, KR = 0.0004, 25, 20            # src/11_full_sim_case1.py:108-110
 X1_START = np.array([20, 30, -np.pi / 2, 0, 10])     # :113
@@ -39,11 +44,13 @@ def hold_steps(t_opt_comp, t_step):
 
 def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, t_end=1000, X0=None,
                                tau_phi=None, rec_stride=1, record=('X', 'U', 'Rr', 'eth'), W=(0., 0.), etheta_tol_deg=None,
-                               t_opt_comp=0.0):
+                               t_opt_comp=0.0, windfield=None):
     """Many formations at once.  c (n_form, n_ac, 2) centres; r scalar or (n_form, n_ac); X0
     (n_form, n_ac, 5) or None (every aircraft starts at the reference's X1); X0f (n_form, n_ac, >=3)
     or None.  etheta_tol_deg: stop by the phase-error rule of cases 2 / 3 instead of the state rule (after t_opt_comp more seconds on
-    which it holds).  Returns the raw device dictionary of d2dhip.Context.gvf_run plus `time`."""
+    which it holds).  windfield: a SplineWindField the plant flies instead of W (row i at t_start + i t_step; the GVF law never reads
+    the wind).  Returns the raw device dictionary of d2dhip.Context.gvf_run plus `time`."""
+    fld = plant_wind(windfield)
     ctx = d2dhip.default_context()
     c = np.asarray(c, dtype=np.float64).reshape(-1, n_ac, 2)
     n_form = c.shape[0]
@@ -57,7 +64,8 @@ def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, 
                       len(time), t_step, float(v), KE, KD, KR, B=ConstructBMatrix(n_ac), z_des=np.zeros(max(n_ac - 1, 0)),
                       tau_phi=ac.tau_phi if tau_phi is None else tau_phi, tau_v=ac.tau_v, W=W, X0f=x0f,
                       rec_stride=rec_stride, record=record, etheta_tol_deg=etheta_tol_deg,
-                      stop_hold=hold_steps(t_opt_comp, t_step) if etheta_tol_deg is not None else 0)
+                      stop_hold=hold_steps(t_opt_comp, t_step) if etheta_tol_deg is not None else 0,
+                      **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
     out['time'] = time
     return out
 
@@ -160,14 +168,17 @@ def ExtendTraj_symm(n_ac, x_ref, y_ref, psi_ref, time):
     return time, np.append(x_ref, xs, axis=0), np.append(y_ref, ys, axis=0), np.append(psi_ref, ys, axis=0)
 
 
-def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd')):
-    """x_ref, y_ref (T, n) for n independent drones; X0s (n, 5).  Device dictionary out."""
+def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), windfield=None):
+    """x_ref, y_ref (T, n) for n independent drones; X0s (n, 5).  Device dictionary out.  windfield: a SplineWindField the plant
+    flies (row i at time[i]); the controller keeps w, as DiffController(w) does (src/11_full_sim_case1.py:241-291)."""
+    fld = plant_wind(windfield)
     ctx = d2dhip.default_context()
     ac = ddyn.Aircraft()
     dt = time[1] - time[0]
     return ctx.track_run(ctx.dev(np.ascontiguousarray(x_ref, dtype=np.float64)), ctx.dev(np.ascontiguousarray(y_ref, dtype=np.float64)),
                          ctx.dev(_planes(np.asarray(X0s, dtype=np.float64))), float(dt), record=record,
-                         w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v)
+                         w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v,
+                         **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
 
 
 def implement_controller(n_ac, time, x_ref, y_ref, v, w, X0s):
@@ -265,9 +276,11 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     return out
 
 
-def run_simulation_batch(time, Yrefs, X0s, perts=None, w=(0., 0.), record=('X', 'U', 'Xr')):
+def run_simulation_batch(time, Yrefs, X0s, perts=None, w=(0., 0.), record=('X', 'U', 'Xr'), windfield=None):
     """The legacy DFFFController loop for n independent aircraft.  Yrefs (T, n, >=3, 2): each trajectory's traj.get(t) at
-    the sample times; X0s (n, 5); perts (T, n, 5) or None.  Device dictionary out (plane-major [T][.][n])."""
+    the sample times; X0s (n, 5); perts (T, n, 5) or None.  Device dictionary out (plane-major [T][.][n]).  windfield: a
+    SplineWindField instead of w: the plant flies it and the controller samples it at the reference point (row i at time[i])."""
+    fld = plant_wind(windfield)
     ctx = d2dhip.default_context()
     ac = ddyn.Aircraft()
     Y = np.asarray(Yrefs, dtype=np.float64)
@@ -275,16 +288,18 @@ def run_simulation_batch(time, Yrefs, X0s, perts=None, w=(0., 0.), record=('X', 
     Yd = np.ascontiguousarray(Y[:, :, :3, :].transpose(0, 2, 3, 1).reshape(T, 6, n))      # rows x, y, xd, yd, xdd, ydd
     dP = None if perts is None else ctx.dev(np.ascontiguousarray(np.asarray(perts, dtype=np.float64).transpose(0, 2, 1)))
     return ctx.dfff_run(ctx.dev(Yd), ctx.dev(_planes(np.asarray(X0s, dtype=np.float64))), float(time[1] - time[0]), perts=dP,
-                        record=record, w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v)
+                        record=record, w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v,
+                        **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
 
 
 def run_simulation(time, aircraft, windfield, ctl, X0, perts):
     """One aircraft, the reference's triple X (T,5), U (T,2), Yref (T,4,2) (src/05_test_simulation.py:21-34); ctl is a
     d2d.guidance.DFFFController (its trajectory is sampled on the host, the time loop runs on the GPU)."""
     Yref = np.array([ctl.traj.get(t) for t in time])
-    w = windfield.sample(time[0], Yref[0, 0])
+    fld = plant_wind(windfield)
+    w = windfield.sample(time[0], Yref[0, 0]) if fld is None else (0., 0.)
     out = run_simulation_batch(time, Yref[:, None], np.asarray(X0, dtype=np.float64)[None], None if perts is None else np.asarray(perts)[:, None],
-                               w=w, record=('X', 'U'))
+                               w=w, record=('X', 'U'), windfield=fld)
     d2dhip.default_context().sync()
     return out['X'].cpu().numpy()[:, :, 0], out['U'].cpu().numpy()[:, :, 0], Yref
 
@@ -320,11 +335,13 @@ def test_simulation(scen, record=('X', 'U')):
     n = len(scen.trajs)
     Y = sample_references_batch(scen.trajs, time)                                        # dev [T][6][n]
     ac = scen.aircrafts[0]
-    w = scen.windfield.sample(time[0], None)
+    fld = plant_wind(scen.windfield)
+    w = scen.windfield.sample(time[0], None) if fld is None else (0., 0.)
     perts = ctx.dev(np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.float64) for p in scen.perts[:n]], 2)))   # [T][5][n]
     X0 = np.stack([np.asarray(x, dtype=np.float64) for x in scen.X0s[:n]])
     out = ctx.dfff_run(Y, ctx.dev(_planes(X0)), float(time[1] - time[0]), perts=perts, record=record,
-                       w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v)
+                       w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v,
+                       **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
     ctx.sync()
     Xh, Uh, Yh = out['X'].cpu().numpy(), out['U'].cpu().numpy(), Y.cpu().numpy()
     Yrefs = Yh.transpose(0, 2, 1).reshape(len(time), n, 3, 2)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 110
+#define D2D_VERSION 111
 
 /* error codes */
 #define D2D_OK 0
@@ -211,6 +211,59 @@ int d2d_sim_dfff_run(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref
 #define D2D_TRAJ_STRIDE (4 + D2D_TRAJ_MAX_SEG * D2D_TRAJ_SEG_STRIDE)
 enum { D2D_TRAJ_LINE = 1, D2D_TRAJ_CIRCLE = 2, D2D_TRAJ_SLALOM = 3, D2D_TRAJ_POLY = 4 };
 int d2d_traj_sample(d2d_ctx *ctx, int n, int T, double t_start, double dt, const double *desc, double *Yref);
+
+/* Wind fields that vary in space and time: the plug-point WindField.sample(t, loc) of the reference's plant
+ * (src/d2d/dynamic.py:14-16, 25-28: the field at the aircraft's own position and time, on every right-hand-side evaluation).
+ * A field is a uniform tensor-product cubic B-spline (C2, so the Gauss panels keep their order) over (x, y) -- steady, nt = 1 --
+ * or over (t, x, y) -- unsteady, nt >= 4.  Along an axis with n control points, first knot u0 and spacing h the spline lives on
+ * [u0, u0 + (n - 3) h]: s = (u - u0) / h, segment i = min(floor(s), n - 4), r = s - i, and the value is
+ * sum_k B_k(r) c[i + k] with the uniform cubic B-spline weights B_0 = (1-r)^3/6, B_1 = (3r^3 - 6r^2 + 4)/6,
+ * B_2 = (-3r^3 + 3r^2 + 3r + 1)/6, B_3 = r^3/6.  A query outside the box is clamped to it coordinate by coordinate: the field is
+ * held at its boundary value there, which is continuous but only C0 across the boundary.
+ *   cp dev [nt][2][ny][nx]: control points, component 0 = wx, 1 = wy (the two components of a point share 128-byte lines).
+ * nx, ny < 4, nt not in {1} or [4, inf), hx, hy (and ht when nt > 1) not > 0, or cp NULL: D2D_EINVAL.  (version 111) */
+typedef struct {
+  int32_t nt, ny, nx;      /* control points per axis; nt = 1: steady (2-D spline), else nt >= 4 */
+  int32_t pad;
+  double t0, ht;           /* first knot and knot spacing in t (ignored when nt = 1) */
+  double x0, hx, y0, hy;   /* same in x, y */
+  const double *cp;        /* dev [nt][2][ny][nx] control points (component 0 = wx, 1 = wy) */
+} d2d_wind_field;
+
+/* In a field the stage positions of a Gauss panel are implicit: x_i = x + w sum_j A_ij (v_j cos psi_j + wx(t + c_j w, x_j, y_j)),
+ * the same for y (phi, v and the heading stay exact / explicit as in d2d_step).  They are solved by fixed-point iteration on the
+ * wind term, started from the field at the panel's start, until the largest update of a stage position over the wavefront is
+ * <= D2D_WIND_TOL (1 + |x|) (resp. |y|), or D2D_WIND_MAX_ITERS field sweeps; the panel's end takes the converged stage winds.
+ * iter_max (dev int32 [1] or NULL): the largest number of sweeps any stage solve of the call used. */
+#define D2D_WIND_TOL 1e-13
+#define D2D_WIND_MAX_ITERS 8
+
+/* Batched evaluation of a field: t dev [n], xy dev [2][n], w dev [2][n] (wx, wy). */
+int d2d_wind_sample(d2d_ctx *ctx, const d2d_wind_field *f, int n, const double *t, const double *xy, double *w);
+
+/* d2d_step in a field: the step starts at time t. */
+int d2d_step_wind(d2d_ctx *ctx, int n, const double *X, const double *U, double t, const d2d_wind_field *f, double tau_phi,
+                  double tau_v, double dt, double *Xout, int32_t *iter_max);
+
+/* The three time loops in a field.  Same arguments as their twins, plus the field, the time of row 0 (row i is at
+ * t_start + i dt, as np.arange makes it) and iter_max.  The plant flies the field; what the controller sees follows the reference:
+ *   d2d_sim_gvf_run_wind    no wind (GVFcontroller stores it and never reads it, src/d2d/guidance.py:149-181); p->wx, p->wy are
+ *                           not used.  Every formation size takes the general (LDS-exchange) kernel;
+ *   d2d_sim_track_run_wind  p->wx, p->wy: the constant of DiffController(w) (src/11_full_sim_case1.py:241-291 builds WindField(w)
+ *                           for the plant and hands w to the controller separately);
+ *   d2d_sim_dfff_run_wind   the field at (t_i, position of the reference sample i), as DFFFController.get samples it
+ *                           (src/d2d/guidance.py:62-65); p->wx, p->wy are not used.
+ * Wind derivatives stay zero in the flatness maps, as in the reference. */
+int d2d_sim_gvf_run_wind(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
+                         const double *Bmat, const double *z_des, const double *X0f, double *X_hist, double *U_hist, double *Rr_hist,
+                         double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const d2d_wind_field *f,
+                         double t_start, int32_t *iter_max);
+int d2d_sim_track_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
+                           double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
+                           double *X_final, const d2d_wind_field *f, double t_start, int32_t *iter_max);
+int d2d_sim_dfff_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts, const double *X0,
+                          double *X_hist, double *U_hist, double *Xr_hist, double *X_final, const d2d_wind_field *f, double t_start,
+                          int32_t *iter_max);
 
 /* Single batched evaluations behind the reference's per-call helper methods (the time
  * loops above fuse them; these exist so that host code written against the reference's
