@@ -40,3 +40,12 @@ void d2d_set_error(const char *fmt, ...);
   } while (0)
 
 #define D2D_LAUNCH_CHECK() D2D_CHECK_HIP(hipGetLastError())
+
+// a d2d_wind_field argument of an entry point (include/d2d.h: what makes one D2D_EINVAL)
+static inline int check_wind(const d2d_wind_field *f, const char *who) {
+  D2D_REQUIRE(f && f->cp, "%s: null wind field", who);
+  D2D_REQUIRE(f->nx >= 4 && f->ny >= 4 && (f->nt == 1 || f->nt >= 4), "%s: wind field nt=%d, ny=%d, nx=%d (nx, ny >= 4; nt = 1 or >= 4)",
+              who, f->nt, f->ny, f->nx);
+  D2D_REQUIRE(f->hx > 0 && f->hy > 0 && (f->nt == 1 || f->ht > 0), "%s: wind field knot spacings must be > 0", who);
+  return D2D_OK;
+}

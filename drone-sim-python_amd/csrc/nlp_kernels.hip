@@ -17,8 +17,12 @@
 
 #include "common.h"
 #include "fit_device.h"      // scenario row columns (D2D_SC_*), FIT_G, FIT_OBS_K
+#include "wind_device.h"     // wind_at, wind_eval2 (d2d_nlp_solve_wind)
 
 #define NLP_NV 5
+#ifndef NLP_WIND_NEXT_SHUFFLE
+#define NLP_WIND_NEXT_SHUFFLE 1    // (A/B: -DNLP_WIND_NEXT_SHUFFLE=0 evaluates the field at the next node a second time)
+#endif
 
 // per-problem scenario constants in registers
 struct NlpScen {
@@ -142,6 +146,8 @@ struct NlpProb {
   double *mu;                // [3][N]
   const double *partner;     // [2][N] or null
   double *lds;               // this wavefront's NLP_LDS_DOUBLES doubles of LDS (nlp_assemble: neighbour hand-over, record transposition)
+  const d2d_wind_field *wf;  // WIND instantiations (d2d_nlp_solve_wind): the field of the equalities, node i at t0 + i h; else null
+  double t0;
 };
 // Objective model of d2d_nlp_solve_model (user cost plug-ins, opty/direct_collocation.py): this problem's planes.  The objective of
 // that instantiation is  m(W) = sum_i g_i.d_i + 1/2 d_i^T H_i d_i,  d_i = W_i - Wc_i, on top of the structured terms (which the
@@ -161,6 +167,7 @@ __host__ __device__ constexpr int nlp_hidx(int a, int c) { return a * NLP_NV - a
 #define NLP_BCR_LDS_NODES 121
 #define NLP_LDS_DOUBLES 2304              // >= 65 * 9 + 64 * NLP_REC_STRIDE (assembly) and >= NLP_BCR_LDS_NODES * NLP_BCR_STRIDE (cyclic reduction)
 static_assert(64 * NLP_BCR_STRIDE >= 65 * 9 && NLP_REC_STRIDE == NLP_BCR_STRIDE, "nlp_assemble rec_lds: records of the chunks above the first lie behind the hand-over rows");
+#define NLP_T(i) (pb.t0 + (double)(i) * pb.h)       // (one multiply-add: not accumulated from node to node)
 #define NLP_W(c, i) pb.W[(c) * pb.N + (i)]
 #define NLP_P(plane, i) pb.ws[(plane) * pb.N + (i)]
 #define NLP_MU(k, i) pb.mu[(k) * pb.N + (i)]
@@ -181,12 +188,25 @@ __device__ __forceinline__ void nlp_phase_sync() {
 
 __device__ __forceinline__ double wave_min(double v) { return -wave_max(-v); }
 
-// collocation residual of node i (>= 1) from the states of node i-1 and the node itself (oracle/nlp.py constraints)
-__device__ __forceinline__ void nlp_constraint(const NlpScen &s, double h, const double wp[3], const double w[NLP_NV], double c[3]) {
+__device__ __forceinline__ double nlp_first_lane(double v) {              // the value lane 0 holds, in every lane
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+// collocation residual of node i (>= 1) from the states of node i-1 and the node itself (oracle/nlp.py constraints).
+// WIND: the wind of the equalities is + the field wf at the node's own time t and position (tests/nlp_wind_ref.py constraints)
+template <bool WIND = false>
+__device__ __forceinline__ void nlp_constraint(const NlpScen &s, double h, const double wp[3], const double w[NLP_NV], double c[3],
+                                               const d2d_wind_field *wf = nullptr, double t = 0.0) {
   double sp, cp;
   sincos(w[2], &sp, &cp);
-  c[0] = (w[0] - wp[0]) / h - w[4] * cp + s.wx;
-  c[1] = (w[1] - wp[1]) / h - w[4] * sp + s.wy;
+  if constexpr (WIND) {
+    const WindVec wv = wind_at(*wf, t, w[0], w[1]);
+    c[0] = (w[0] - wp[0]) / h - w[4] * cp + wv.x;
+    c[1] = (w[1] - wp[1]) / h - w[4] * sp + wv.y;
+  } else {
+    c[0] = (w[0] - wp[0]) / h - w[4] * cp + s.wx;
+    c[1] = (w[1] - wp[1]) / h - w[4] * sp + s.wy;
+  }
   c[2] = (w[2] - wp[2]) / h - FIT_G / w[4] * tan(w[3]);
 }
 
@@ -194,7 +214,7 @@ __device__ __forceinline__ bool nlp_fixed(int i, int N, int c) { return c < 3 &&
 
 // Merit function of the inner problem at W + a*dw: objective + rho sum (c + mu)^2 - mub sum log(slacks); +inf outside the box.
 // Node-parallel (lane = node, chunks of 64) + wave reductions.  All results are wave-uniform.
-template <bool MODEL>
+template <bool MODEL, bool WIND = false>
 __device__ double nlp_merit(const NlpProb &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
                             double mub, double *cost_ref_out, double *feas_out, const NlpModel &md) {
   const int N = pb.N;
@@ -246,7 +266,7 @@ __device__ double nlp_merit(const NlpProb &pb, const NlpScen &s, const double *_
       val += obj;
       if (i >= 1) {
         double c3[3];
-        nlp_constraint(s, pb.h, wp, w, c3);
+        nlp_constraint<WIND>(s, pb.h, wp, w, c3, pb.wf, NLP_T(i));
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           const double cm = c3[k] + muv[k];
@@ -300,7 +320,10 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // imax (CostBank max mode, s.sbank > 0): the node whose bank angle is the largest at the current iterate -- the reference's
 // cost_grad is one-hot there (2 obj_scale kbank phi_imax), the step's model carries the term sbank * phi_imax^2 on that node
 // alone (the maximiser frozen for the step; the merit function of the line search is the true max)
-template <bool MODEL>
+// WIND (d2d_nlp_solve_wind): the constraint that ends at node i reads the field at (t_i, x_i, y_i): with J = d(wx, wy)/d(x, y) there,
+// Ac gains J on its (x, y) columns and D the constraint curvature rho (c + mu)_0 Hess(wx) + rho (c + mu)_1 Hess(wy) on its (x, y)
+// block; node i+1's constraint sees node i through -1/h only, so the has_next terms and the structure of E do not change.
+template <bool MODEL, bool WIND = false>
 __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
                                double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md) {
   const int N = pb.N;
@@ -310,10 +333,12 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
   // The chunks of 64 nodes are visited from the LAST to the first: node i needs what node i+1 hands to it (the hand-over of the
   // elimination, below), and for the last lane of a chunk that is the first node of the chunk visited before.
   double *lds_up = pb.lds + NLP_LDS_UP, *lds_rec = pb.lds + NLP_LDS_REC;
+  [[maybe_unused]] double wnx_first = 0.0, wny_first = 0.0;      // WIND: the field at the first node of the chunk visited before (lane 63's next node)
   for (int i0 = ((N - 1) / 64) * 64; i0 >= 0; i0 -= 64) {
     const int i = i0 + lane;
     const bool live = i < N;
     double sinv[SIN_N], upv[9];
+    [[maybe_unused]] WindJet wj;                     // WIND: the field at this lane's node
     if (live) {
     const bool has_next = i + 1 < N;
     double rhsv[NLP_NV];
@@ -327,8 +352,31 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
 #pragma unroll
     for (int c = 0; c < 3; ++c) { wp[c] = NLP_W(c, im); mu_c[c] = NLP_MU(c, i); mu_n[c] = NLP_MU(c, ip); }
     if (i < 1) { wp[0] = 0.0; wp[1] = 0.0; wp[2] = 0.0; }
+    // WIND: the field at this node -- value, Jacobian, second derivatives in one pass -- for every live lane; the value at the
+    // NEXT node, which cn needs, comes from the neighbouring lane (NLP_WIND_NEXT_SHUFFLE, the default) or from a second, value-only
+    // evaluation: DESIGN.md 5.10 has the A/B
+    [[maybe_unused]] double wnx = 0.0, wny = 0.0;
+    if constexpr (WIND) {
+      wj = wind_eval2(*pb.wf, NLP_T(i), wc[0], wc[1]);
+#if NLP_WIND_NEXT_SHUFFLE
+      wnx = __shfl_down(wj.w[0], 1); wny = __shfl_down(wj.w[1], 1);
+      if (lane == 63) { wnx = wnx_first; wny = wny_first; }
+#endif
+    }
     if (has_next) {
-      nlp_constraint(s, h, wc, wn, cn);
+      if constexpr (WIND) {
+#if NLP_WIND_NEXT_SHUFFLE
+        double spn, cpn;
+        sincos(wn[2], &spn, &cpn);
+        cn[0] = (wn[0] - wc[0]) / h - wn[4] * cpn + wnx;
+        cn[1] = (wn[1] - wc[1]) / h - wn[4] * spn + wny;
+        cn[2] = (wn[2] - wc[2]) / h - FIT_G / wn[4] * tan(wn[3]);
+#else
+        nlp_constraint<true>(s, h, wc, wn, cn, pb.wf, NLP_T(i + 1));
+#endif
+      } else {
+        nlp_constraint(s, h, wc, wn, cn);
+      }
 #pragma unroll
       for (int k = 0; k < 3; ++k) cn[k] += mu_n[k];
     } else {
@@ -369,8 +417,13 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
       double sp, cp;
       sincos(wc[2], &sp, &cp);
       const double tp = tan(wc[3]), vi = wc[4], sec2 = 1.0 + tp * tp;
-      cc[0] = (wc[0] - wp[0]) * ih - vi * cp + s.wx + mu_c[0];
-      cc[1] = (wc[1] - wp[1]) * ih - vi * sp + s.wy + mu_c[1];
+      if constexpr (WIND) {
+        cc[0] = (wc[0] - wp[0]) * ih - vi * cp + wj.w[0] + mu_c[0];
+        cc[1] = (wc[1] - wp[1]) * ih - vi * sp + wj.w[1] + mu_c[1];
+      } else {
+        cc[0] = (wc[0] - wp[0]) * ih - vi * cp + s.wx + mu_c[0];
+        cc[1] = (wc[1] - wp[1]) * ih - vi * sp + s.wy + mu_c[1];
+      }
       cc[2] = (wc[2] - wp[2]) * ih - FIT_G / vi * tp + mu_c[2];
       double Ac[3][NLP_NV];                     // Jacobian of the constraint wrt this node
 #pragma unroll
@@ -380,6 +433,7 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
       Ac[0][0] = ih; Ac[0][2] = vi * sp; Ac[0][4] = -cp;
       Ac[1][1] = ih; Ac[1][2] = -vi * cp; Ac[1][4] = -sp;
       Ac[2][2] = ih; Ac[2][3] = -FIT_G * sec2 / vi; Ac[2][4] = FIT_G * tp / (vi * vi);
+      if constexpr (WIND) { Ac[0][0] += wj.dx[0]; Ac[0][1] = wj.dy[0]; Ac[1][0] = wj.dx[1]; Ac[1][1] += wj.dy[1]; }
 #pragma unroll
       for (int a = 0; a < NLP_NV; ++a) {
 #pragma unroll
@@ -397,6 +451,12 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
       const double d34 = m2 * FIT_G * sec2 / (vi * vi);
       D[3][4] += d34; D[4][3] += d34;
       D[4][4] += -m2 * 2.0 * FIT_G * tp / (vi * vi * vi);
+      if constexpr (WIND) {
+        D[0][0] += m0 * wj.xx[0] + m1 * wj.xx[1];
+        const double d01 = m0 * wj.xy[0] + m1 * wj.xy[1];
+        D[0][1] += d01; D[1][0] += d01;
+        D[1][1] += m0 * wj.yy[0] + m1 * wj.yy[1];
+      }
     }
     if (has_next) {
 #pragma unroll
@@ -470,6 +530,11 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
       sinv[SIN_T + a] = 0.5 * rhsv[a] - (Qt[0][a] * tt[0] + Qt[1][a] * tt[1]);
     }
     }
+#if NLP_WIND_NEXT_SHUFFLE
+    // (outside the live branch: every lane of the wave keeps the value, also the lanes beyond the end of the last chunk -- lane 63 of
+    // the chunk below reads its own copy; lane 0 of a chunk is always live)
+    if constexpr (WIND) { wnx_first = nlp_first_lane(wj.w[0]); wny_first = nlp_first_lane(wj.w[1]); }
+#endif
     // ---- hand-over between neighbours, D'_i -= (Rt^T Rt)_{i+1}, t'_i -= (Rt^T tt)_{i+1}, through the LDS (the records used to make
     // a round trip through HBM for it), then the node-major records of the chunk transposed through the LDS so that they leave as
     // full 512-byte rows: 8-byte stores at a stride of 144 bytes reached the memory as partial sectors (WRITE_SIZE 1.6 x algorithmic)
@@ -1057,10 +1122,12 @@ struct NlpOut { double cost, feas; int iters, status; };
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
 // MODEL: the objective is the quadratic model md (d2d_nlp_solve_model) on top of the row's structured terms; cost = its value.
-template <bool MODEL = false>
+// WIND: the equalities read the field wf at node i's own (t_start + i h, x_i, y_i) instead of the row's constant (d2d_nlp_solve_wind).
+template <bool MODEL = false, bool WIND = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
-                                              const double *__restrict__ bnd, const NlpModel &md = NlpModel{nullptr, nullptr, nullptr}) {
+                                              const double *__restrict__ bnd, const NlpModel &md = NlpModel{nullptr, nullptr, nullptr},
+                                              const d2d_wind_field *wf = nullptr, double t_start = 0.0) {
   // diagnostics (D2D_NLP_STAMPS): cycles per phase -- merit, assembly, factorisation, back substitution, ratio tests, update
   unsigned long long st_t = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define NLP_STAMP(k) if (st_on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t; st_t = t_; }
@@ -1075,6 +1142,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   pb.mu = multb ? multb : pb.ws + (size_t)WS_MU * N;
   pb.partner = partner;
   pb.lds = ldsw;
+  pb.wf = wf; pb.t0 = t_start;
   // (a row whose bounds are unset or inverted would give a zero-width box, infinite duals and NaN pivots for
   // outer_max x 30 assemblies -- refuse it at once)
   {
@@ -1136,7 +1204,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     const double tol_in = fmax(fmax(o.opt_tol, fmin(1e-1, 10.0 * mub)), D2D_NLP_GRAD_FLOOR * rho);
     // merit value of the current point for this (mub, rho, mu): one pass here, afterwards the accepted trial's value
     NLP_STAMP(7)
-    double phi0 = nlp_merit<MODEL>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    double phi0 = nlp_merit<MODEL, WIND>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1147,7 +1215,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       const int imax = s.sbank > 0.0 ? nlp_bank_argmax(pb, lane) : -1;
       for (int tr = 0; tr < 30; ++tr) {
         bool pd;
-        err = nlp_assemble<MODEL>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<MODEL, WIND>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -1170,7 +1238,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         double a = amax, pt = 0.0;
         bool ok = false;
         for (int ls = 0; ls < 8; ++ls) {
-          pt = nlp_merit<MODEL>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
+          pt = nlp_merit<MODEL, WIND>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
@@ -1188,7 +1256,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       }
       if (converged || !accepted) break;
     }
-    (void)nlp_merit<MODEL>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+    (void)nlp_merit<MODEL, WIND>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -1215,7 +1283,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       for (int c = 0; c < 3; ++c) wp[c] = NLP_W(c, i - 1);
 #pragma unroll
       for (int c = 0; c < NLP_NV; ++c) w[c] = NLP_W(c, i);
-      nlp_constraint(s, h, wp, w, c3);
+      nlp_constraint<WIND>(s, h, wp, w, c3, pb.wf, NLP_T(i));
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const double m = NLP_MU(k, i) + c3[k];
@@ -1227,7 +1295,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     feas_prev = feas;
     mub = fmax(o.mub_min, fmin(0.2 * mub, mub * sqrt(mub)));
   }
-  (void)nlp_merit<MODEL>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+  (void)nlp_merit<MODEL, WIND>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -1270,6 +1338,45 @@ nlp_solve_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restric
     nlp_solve_one(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, partner ? partner + (size_t)b * 2 * N : nullptr, W + (size_t)b * NLP_NV * N,
                   wsb, mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, b == 0 ? stamps : nullptr, nlp_lds,
                   o.bounds ? o.bounds + (size_t)b * 4 : nullptr);
+    if (lane == 0) {
+      cost_out[b] = out.cost;
+      feas_out[b] = out.feas;
+      if (iters_out) iters_out[b] = out.iters;
+      if (status_out) status_out[b] = out.status;
+    }
+    nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
+    int tn = 0;
+    if (lane == 0) tn = (int)gridDim.x + atomicAdd(queue, 1);
+    t = __builtin_amdgcn_readfirstlane(tn);
+  }
+}
+
+// d2d_nlp_solve_wind: nlp_solve_kernel's persistent hand-out around the WIND instantiation of the solve (no partner, no stamps).
+// The field is shared by the batch and travels as a kernel argument (scalar registers); its control points are a small table that
+// every wavefront reads and that stays in L2.
+#ifndef NLP_WIND_WAVES_PER_SIMD
+#define NLP_WIND_WAVES_PER_SIMD 2
+#endif
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                      double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                      int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, double t_start) {
+  const int lane = threadIdx.x;
+  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
+  double *wsb = work + (size_t)blockIdx.x * WS_TOTAL * N;
+  const int32_t *__restrict__ order = o.order;
+  for (int t = blockIdx.x; t < B;) {
+    const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
+    if ((unsigned)b >= (unsigned)B) {        // (an entry that is no problem index is skipped, not dereferenced)
+      int tn = 0;
+      if (lane == 0) tn = (int)gridDim.x + atomicAdd(queue, 1);
+      t = __builtin_amdgcn_readfirstlane(tn);
+      continue;
+    }
+    NlpOut out;
+    nlp_solve_one<false, true>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + (size_t)b * NLP_NV * N, wsb,
+                               mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds,
+                               o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpModel{nullptr, nullptr, nullptr}, &wf, t_start);
     if (lane == 0) {
       cost_out[b] = out.cost;
       feas_out[b] = out.feas;
@@ -1427,6 +1534,28 @@ int d2d_nlp_solve(d2d_ctx *ctx, int B, int N, double h, const double *scen, cons
     for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %llu", nm[k], hs[k]);
     fprintf(stderr, "\n");
   }
+  return D2D_OK;
+}
+
+int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
+                       double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f, double t_start) {
+  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_wind: null argument");
+  D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_wind: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
+  D2D_REQUIRE(fabs(t_start) <= 1.79e308, "d2d_nlp_solve_wind: t_start must be finite");
+  if (int rc = check_wind(f, "d2d_nlp_solve_wind")) return rc;
+  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
+  if (opts) o = *opts;
+  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_wind: bad options");
+  static int n_cu = 0;
+  if (n_cu == 0) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256; }
+  int slots = n_cu * 4 * NLP_WIND_WAVES_PER_SIMD;
+  if (o.slots > 0) slots = o.slots;
+  const int grid = B < slots ? B : (slots < 1 ? 1 : slots);
+  int32_t *queue = ctx->counter_dev + 2;
+  D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
+  hipLaunchKernelGGL(nlp_solve_wind_kernel, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work, mult, cost,
+                     feas, iters, status, queue, *f, t_start);
+  D2D_LAUNCH_CHECK();
   return D2D_OK;
 }
 

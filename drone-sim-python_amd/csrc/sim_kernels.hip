@@ -848,7 +848,6 @@ dfff_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__
 
 // ------------------------------------------------------------------------------------
 static int upload_Bz(d2d_ctx *ctx, int n_ac, const double *Bmat, const double *z_des);
-static int check_wind(const d2d_wind_field *f, const char *who);
 
 extern "C" {
 
@@ -880,14 +879,6 @@ int d2d_step_wind(d2d_ctx *ctx, int n, const double *X, const double *U, double 
   if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
   hipLaunchKernelGGL(step_wind_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, X, U, t, *f, mesh, Xout, iter_max);
   D2D_LAUNCH_CHECK();
-  return D2D_OK;
-}
-
-static int check_wind(const d2d_wind_field *f, const char *who) {
-  D2D_REQUIRE(f && f->cp, "%s: null wind field", who);
-  D2D_REQUIRE(f->nx >= 4 && f->ny >= 4 && (f->nt == 1 || f->nt >= 4), "%s: wind field nt=%d, ny=%d, nx=%d (nx, ny >= 4; nt = 1 or >= 4)",
-              who, f->nt, f->ny, f->nx);
-  D2D_REQUIRE(f->hx > 0 && f->hy > 0 && (f->nt == 1 || f->ht > 0), "%s: wind field knot spacings must be > 0", who);
   return D2D_OK;
 }
 

@@ -85,14 +85,17 @@ class InstanceConstraint:
 class Eom(tuple):
     """The symbolic model of the reference (src/d2d/opty_utils.py:38-50) as data: residual form, wind entering with a + sign
     (the reference's quirk: the plant, src/d2d/dynamic.py:18-19, has the opposite sign).  A tuple of printable equations that
-    also carries what the solver needs: the wind vector and g."""
+    also carries what the solver needs: the wind vector and g.  A wind that varies in space and time (what
+    d2d.wind.SplineWindField.sample_sym returns) is kept as eom.field; eom.wind is NaN then: no constant stands for a field."""
 
     def __new__(cls, wind, g=9.81, ids=('',)):
         eqs = []
         for i in ids:
             eqs += [f"x{i}' - v{i} cos(psi{i}) + {wind[0]}", f"y{i}' - v{i} sin(psi{i}) + {wind[1]}", f"psi{i}' - {g}/v{i} tan(phi{i})"]
         self = super().__new__(cls, eqs)
-        self.wind, self.g, self.n_aircraft = (float(wind[0]), float(wind[1])), g, len(ids)
+        self.field = getattr(wind, 'field', None)
+        self.wind = (float(wind[0]), float(wind[1])) if self.field is None else (float('nan'), float('nan'))
+        self.g, self.n_aircraft = g, len(ids)
         return self
 
 

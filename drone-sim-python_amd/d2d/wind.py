@@ -9,6 +9,10 @@ cubic B-spline (C2: the Gauss panels of the plant step keep their order):
   SplineWindField.from_field(field, x, y, t=None)     tabulates any object with sample(t, loc) on a grid and fits it
   SplineWindField.sample(t, loc)                      a numpy evaluation of the SAME spline the kernels evaluate: host code and
                                                       device loops see one field
+  SplineWindField.derivatives(t, x, y)                value, spatial Jacobian and second derivatives (the collocation planner's
+                                                      constraint Jacobian and curvature; sim_device.h wind_eval2 in numpy)
+  SplineWindField.sample_num / sample_sym / -field    the planner's wind protocol (src/d2d/opty_utils.py:16-29) and the field with the
+                                                      opposite sign (the planner's model has the wind with the opposite sign to the plant)
 
 Outside the spline's box every coordinate is clamped: the field is held at its boundary value, continuous but only C0 there.
 """
@@ -65,6 +69,33 @@ def _weights(u, u0, h, n):
     return fl.astype(np.int64), b
 
 
+def _weights_d(u, u0, h, n):
+    """_weights plus the derivative weights B_k'(r) / h and B_k''(r) / h^2.  Along a clamped coordinate (a query outside the box, or
+    NaN) both are zero: they are the derivatives of the clamped field."""
+    fl, b = _weights(u, u0, h, n)
+    s = (np.asarray(u, dtype=np.float64) - u0) / h
+    inside = (s >= 0.0) & (s <= n - 3.0)
+    r = np.where(np.isnan(s), 0.0, np.clip(s, 0.0, n - 3.0)) - fl
+    q = 1.0 - r; r2 = r * r
+    d1 = np.stack([-0.5 * q * q, 1.5 * r2 - 2.0 * r, -1.5 * r2 + r + 0.5, 0.5 * r2]) * np.where(inside, 1.0 / h, 0.0)
+    d2 = np.stack([q, 3.0 * r - 2.0, 1.0 - 3.0 * r, r]) * np.where(inside, 1.0 / (h * h), 0.0)
+    return fl, b, d1, d2
+
+
+class _FieldSym:
+    """What SplineWindField.sample_sym returns: stands where the reference's symbolic wind expressions stand in the equations of
+    motion (src/d2d/opty_utils.py:38-50).  Two printable components, and the field itself for the solver (d2d.opty_utils.Eom)."""
+
+    def __init__(self, field, args='t,x,y'):
+        self.field, self._args = field, args
+
+    def __getitem__(self, k):
+        return ('wx', 'wy')[k] + f'({self._args})'
+
+    def __len__(self):
+        return 2
+
+
 class SplineWindField:
     """A duck-typed WindField (sample(t, loc), summarize()) that the device loops can fly: control points cp (nt, 2, ny, nx) of a
     uniform cubic B-spline over (x, y) (nt = 1, steady) or (t, x, y) (nt >= 4); knot spacings h*, first knots *0."""
@@ -107,10 +138,14 @@ class SplineWindField:
 
     @classmethod
     def from_field(cls, field, x, y, t=None):
-        """Tabulate any object with sample(t, loc) on the grid (t at 0.0 for a steady field) and fit it (from_samples)."""
+        """Tabulate any object with sample(t, loc) -- or, a planner wind object, sample_num(t, x, y) -- on the grid (t at 0.0 for a steady field) and fit it (from_samples)."""
         x = np.asarray(x, dtype=np.float64).reshape(-1); y = np.asarray(y, dtype=np.float64).reshape(-1)
         ts = [0.0] if t is None else list(np.asarray(t, dtype=np.float64).reshape(-1))
-        W = np.array([[[np.asarray(field.sample(tk, np.array([xi, yj])), dtype=np.float64).reshape(2) for xi in x] for yj in y]
+        if hasattr(field, 'sample'):
+            at = lambda tk, xi, yj: field.sample(tk, np.array([xi, yj]))          # noqa: E731
+        else:                                                                 # (a planner wind object: sample_num(t, x, y), no sample)
+            at = field.sample_num
+        W = np.array([[[np.asarray(at(tk, xi, yj), dtype=np.float64).reshape(2) for xi in x] for yj in y]
                       for tk in ts])                                          # (T, K, M, 2)
         if t is None:
             return cls.from_samples(x, y, W[0, ..., 0], W[0, ..., 1])
@@ -143,6 +178,50 @@ class SplineWindField:
         """WindField.sample(t, loc): [wx, wy] at time t and position loc = (x, y)."""
         wx, wy = self.sample_many(t, loc[0], loc[1])
         return np.array([float(wx), float(wy)])
+
+    def derivatives(self, t, x, y):
+        """Value w (2, ...), spatial Jacobian J (2, 2, ...) = d(wx, wy)/d(x, y) and second derivatives H (2, 3, ...) = (xx, xy, yy) of
+        each component at arrays t, x, y (broadcast): sim_device.h wind_eval2 in numpy.  The value is sample_many's, sum for sum."""
+        t, x, y = np.broadcast_arrays(np.asarray(t, np.float64), np.asarray(x, np.float64), np.asarray(y, np.float64))
+        shape = x.shape
+        t, x, y = t.reshape(-1), x.reshape(-1), y.reshape(-1)
+        nt, _, ny, nx = self.cp.shape
+        ix, bx, dx, ddx = _weights_d(x, self.x0, self.hx, nx)
+        iy, by, dy, ddy = _weights_d(y, self.y0, self.hy, ny)
+        if nt == 1:
+            it, bt, kt = np.zeros_like(ix), np.ones((1, len(ix))), 1
+        else:
+            (it, bt), kt = _weights(t, self.t0, self.ht, nt), 4
+        P = len(ix)
+        out = np.zeros((6, 2, P))                                                   # value, d/dx, d/dy, xx, xy, yy
+        for c in range(kt):
+            acc = np.zeros((6, 2, P))
+            for a in range(4):
+                s = np.zeros((3, 2, P))                                                # row sums: value, d/dx, d2/dx2
+                for b in range(4):
+                    cpv = self.cp[it + c, :, iy + a, ix + b].T
+                    s = s + np.stack([bx[b] * cpv, dx[b] * cpv, ddx[b] * cpv])
+                acc = acc + np.stack([by[a] * s[0], by[a] * s[1], dy[a] * s[0], by[a] * s[2], dy[a] * s[1], ddy[a] * s[0]])
+            out = out + bt[c] * acc
+        w = out[0].reshape((2,) + shape)
+        J = np.stack([out[1], out[2]], axis=1).reshape((2, 2) + shape)               # J[k][0] = d w_k / dx, J[k][1] = d w_k / dy
+        H = np.stack([out[3], out[4], out[5]], axis=1).reshape((2, 3) + shape)
+        return w, J, H
+
+    # ---- the planner's wind protocol (src/d2d/opty_utils.py:16-29: sample_sym inside the equations of motion, sample_num per node)
+    def sample_num(self, t, x, y):
+        """[wx, wy] at (t, x, y): the same numbers as sample(t, (x, y))."""
+        return self.sample(t, (x, y))
+
+    def sample_sym(self, _t, _x, _y):
+        """The wind of the symbolic model: a marker that carries this field (d2d.opty_utils.Eom keeps it as eom.field)."""
+        return _FieldSym(self)
+
+    def __neg__(self):
+        """The field with the opposite sign (control points negated, same knots).  The planner's model adds its wind to the
+        RESIDUAL, xdot - v cos(psi) + wx = 0 (the reference's quirk, src/d2d/opty_utils.py:42-44), the plant to the velocity,
+        xdot = v cos(psi) + wx (src/d2d/dynamic.py:18-19): a plan consistent with a plant that flies F is planned in -F."""
+        return SplineWindField(-self.cp, self.x0, self.hx, self.y0, self.hy, self.t0, self.ht)
 
     def summarize(self):
         nt, _, ny, nx = self.cp.shape
@@ -181,4 +260,18 @@ def plant_wind(windfield):
         return None
     raise NotImplementedError(
         f'{type(windfield).__name__}.sample varies the wind in space or time and the device loops cannot call it: tabulate it on a '
+        f'grid with d2d.wind.SplineWindField.from_field(field, x, y, t) and pass that field instead')
+
+
+def planner_wind(wind):
+    """How the collocation planner plans in `wind`: a constant class (its sample_sym is the reference's, which returns w) -> None
+    (the constant-wind path, unchanged); a SplineWindField -> the field.  Any other object whose class has its own sample_sym varies
+    the wind inside the equations of motion, which the kernels cannot call: same rule as plant_wind."""
+    if wind is None or isinstance(wind, SplineWindField):
+        return wind
+    import d2d.opty_utils, d2d.utils      # noqa: E401
+    if getattr(type(wind), 'sample_sym', None) in (None, d2d.opty_utils.WindField.sample_sym, d2d.utils.WindField.sample_sym):
+        return None
+    raise NotImplementedError(
+        f'{type(wind).__name__}.sample_sym varies the wind in space or time and the planner cannot differentiate it: tabulate it on a '
         f'grid with d2d.wind.SplineWindField.from_field(field, x, y, t) and pass that field instead')

@@ -137,6 +137,7 @@ _SIGS = {
     'd2d_lqr': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     'd2d_nlp_workspace_doubles': (C.c_int, [C.c_int]),
     'd2d_nlp_solve': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 8),
+    'd2d_nlp_solve_wind': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7 + [C.POINTER(WindFieldC), C.c_double]),
     'd2d_nlp_solve_groups': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9),
     'd2d_nlp_solve_model': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.POINTER(NlpModel)] + [_P] * 7),
     'd2d_fit_plan_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(_P)]),
@@ -493,6 +494,30 @@ class Context:
                     None if order is None else order.data_ptr())
         _check(self.lib.d2d_nlp_solve(self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), _ptr(partner), _ptr(work), _ptr(mult),
                                       _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status)))
+        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work)
+        if want_mult:
+            out['mult'] = mult
+        return out
+
+    def nlp_solve_wind(self, scen, W, h, field, t_start=0.0, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7,
+                       inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None, slots=0, order=None):
+        """nlp_solve with the wind of the equalities read from `field` (a d2d.wind.SplineWindField or a WindFieldC) at every node's own
+        (t_start + i h, x_i, y_i) instead of the rows' constant (d2d_nlp_solve_wind; no partner).  The model ADDS the field to its
+        residual: a plan for a plant that flies F is solved in -F.  Returns dict(cost, feas, iters, status[, mult]) of device tensors."""
+        torch = _torch()
+        B, _, N = W.shape
+        assert W.is_contiguous() and scen.shape[0] == B
+        work = self.empty(self.lib.d2d_nlp_workspace_doubles(N) * B)
+        cost, feas = self.empty(B), self.empty(B)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        mult = self.zeros(B, 3, N) if want_mult else None
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        assert order is None or (order.is_contiguous() and tuple(order.shape) == (B,) and order.dtype == torch.int32)
+        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, int(slots), None if bounds is None else bounds.data_ptr(),
+                    None if order is None else order.data_ptr())
+        f = None if field is None else _wind_c(self, field)
+        _check(self.lib.d2d_nlp_solve_wind(self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), _ptr(work), _ptr(mult), _ptr(cost),
+                                           _ptr(feas), _ptr(iters), _ptr(status), None if f is None else C.byref(f), float(t_start)))
         out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work)
         if want_mult:
             out['mult'] = mult

@@ -42,6 +42,11 @@ class Planner:
         self.backend = backend or sop.BACKEND            # 'fit' | 'nlp' (single_opt_planner.BACKEND)
         self.obj_scale = scen.obj_scale
         self.wind = scen.wind
+        from d2d.wind import planner_wind
+        if planner_wind(self.wind) is not None:
+            raise NotImplementedError('the multi-aircraft planner takes a constant wind: a field that varies in space and time is planned '
+                                      'one aircraft at a time (single_opt_planner.Planner, d2d_nlp_solve_wind); the joint problem and its '
+                                      'CostCollision partner (d2d_nlp_solve_groups) have no field')
         self.acs = d2mou.AircraftSet(n=len(scen.p0s))
         self.num_nodes, self.time_step, self.duration = d2ou.planner_timing(scen.t0, scen.t1, scen.hz)
         N, n = self.num_nodes, self.acs.nb_aicraft

@@ -7,7 +7,9 @@
     .num_free, .addOption(k, v) / .add_option(k, v), .solve(x0) -> (solution, info)
 
 What is interpreted instead of compiled:
-  * eom / state_symbols  -- the fixed kinematic model of d2d.opty_utils.Aircraft.get_eom (an `Eom`: wind, g, aircraft count);
+  * eom / state_symbols  -- the fixed kinematic model of d2d.opty_utils.Aircraft.get_eom (an `Eom`: wind, g, aircraft count).  A wind
+                            that varies in space and time (eom.field, a d2d.wind.SplineWindField: what its sample_sym put into the
+                            equations) is solved by d2d_nlp_solve_wind: one aircraft, lowered objective; node i at t0 + i time_step;
   * instance_constraints -- `x(t) - value` objects: the end conditions of every aircraft;
   * bounds               -- {phi(t): (lo, hi), v(t): ..., x(t): ..., y(t): ..., psi(t): ...}: HARD boxes (primal-dual barrier); the phi
                             interval need not be symmetric (d2d_nlp_opts.bounds carries it and the psi box to the kernel);
@@ -110,8 +112,13 @@ class Problem:
         self.num_free = 5 * self.num_nodes * self.n_aircraft
         self.options = {'tol': 1e-8, 'max_iter': 3000}
         self.wind = tuple(getattr(eom, 'wind', (0., 0.)))
+        self.field = getattr(eom, 'field', None)
         if getattr(eom, 'n_aircraft', self.n_aircraft) != self.n_aircraft:
             raise ValueError('eom and state_symbols disagree on the number of aircraft')
+        if self.field is not None and self.n_aircraft != 1:
+            raise NotImplementedError('a wind field that varies in space and time is planned for one aircraft at a time '
+                                      '(d2d_nlp_solve_wind): the multi-aircraft Problem and its CostCollision partner '
+                                      '(d2d_nlp_solve_groups) take a constant wind')
         # the cost plug-in and the planner behind the obj closure (the reference's call sites close over both)
         if cost is None or planner is None:
             for o in _closure_objects(obj):
@@ -134,6 +141,7 @@ class Problem:
         t_all = sorted({c.t for c in instance_constraints})
         if len(t_all) != 2:
             raise NotImplementedError('instance constraints at exactly two times (t0 and t1) are supported')
+        self.t_start = float(t_all[0])                  # node i is at t_start + i time_step (what a field is sampled at)
         self.p0s = np.zeros((self.n_aircraft, 3)); self.p1s = np.zeros((self.n_aircraft, 3))
         seen = set()
         for c in instance_constraints:
@@ -191,6 +199,10 @@ class Problem:
 
     def solve(self, x0):
         if self.objective == 'host':
+            if self.field is not None:
+                raise NotImplementedError('a wind field that varies in space and time together with a host objective (a cost plug-in '
+                                          'without a kernel, d2d_nlp_solve_model) is not supported: use one of the cost classes of '
+                                          'd2d.opty_utils, or a constant wind')
             return self._solve_host(np.asarray(x0, dtype=np.float64))
         ctx = d2dhip.default_context()
         n, N = self.n_aircraft, self.num_nodes
@@ -220,10 +232,14 @@ class Problem:
         # alternates on the device (block Gauss-Seidel, d2d_nlp_solve_groups) until neither aircraft moves
         if not coupled:
             dsc[:, d2dhip.SC_KCOL] = 0.0
-        out = ctx.nlp_solve_groups(dsc, dW, self.time_step, n, max_sweeps=int(self.options.get('max_sweeps', 12)),
-                                   tol=float(self.options.get('sweep_tol', 1e-7)), bounds=bnd, **kw)
-        sweeps = int(out['sweeps'][0].item())
-        moved = float(out['moved'][0].item())
+        if self.field is not None:                # one aircraft in a field (the rows' NaN wind columns are not read)
+            out = ctx.nlp_solve_wind(dsc, dW, self.time_step, self.field, t_start=self.t_start, bounds=bnd, **kw)
+            sweeps, moved = 0, 0.0
+        else:
+            out = ctx.nlp_solve_groups(dsc, dW, self.time_step, n, max_sweeps=int(self.options.get('max_sweeps', 12)),
+                                       tol=float(self.options.get('sweep_tol', 1e-7)), bounds=bnd, **kw)
+            sweeps = int(out['sweeps'][0].item())
+            moved = float(out['moved'][0].item())
         ctx.sync()
         Wh = dW.cpu().numpy()
         sol = np.zeros(self.num_free)

@@ -22,7 +22,9 @@ seed = None
 #            soft rows) by more than AUTO_TOL, the collocation problem is solved from that plan, so that what a script gets from
 #            Planner(scen).run() never violates a bound IPOPT would have enforced; info['backend_used'] says which one answered.
 #            A cost plug-in that lower_cost does not know (a user's own objective) goes straight to the collocation problem, which
-#            calls its cost / cost_grad on the host (opty.direct_collocation, host objective): info['backend_used'] = 'nlp'
+#            calls its cost / cost_grad on the host (opty.direct_collocation, host objective): info['backend_used'] = 'nlp'.
+#            So does a wind that varies in space and time (exp.wind a d2d.wind.SplineWindField; d2d_nlp_solve_wind): the fit's speed
+#            and bank rows would depend on position through the field, and backend='fit' refuses it.
 BACKEND = 'auto'
 AUTO_TOL = 1e-6        # rad, m/s, m
 N_SEG = 6
@@ -178,6 +180,12 @@ class Planner:
         self.obj_scale = exp.obj_scale
         self.num_nodes, self.time_step, self.duration = d2ou.planner_timing(exp.t0, exp.t1, exp.hz)
         self.wind = exp.wind
+        from d2d.wind import planner_wind
+        self.field = planner_wind(self.wind)       # None: a constant wind; a class with its own sample_sym that is no spline raises
+        if self.field is not None and self.backend == 'fit':
+            raise NotImplementedError("backend='fit' cannot plan in a wind field that varies in space and time: the polynomial fit's "
+                                      "speed and bank rows would depend on position through the field.  backend='nlp' (or 'auto') "
+                                      "solves the collocation problem in the field")
         self.aircraft = d2ou.Aircraft()
         N = self.num_nodes
         self._slice_x, self._slice_y, self._slice_psi, self._slice_phi, self._slice_v = (
@@ -185,7 +193,7 @@ class Planner:
         self.obstacles = exp.obstacles
         # a cost plug-in without a lowering: the collocation problem with the host objective, unless the fit was asked for
         self._host_cost = self.backend != 'fit' and not lowerable(exp.cost)
-        if initialize and (self.backend == 'nlp' or self._host_cost):
+        if initialize and (self.backend == 'nlp' or self._host_cost or self.field is not None):
             import opty.direct_collocation
             _g = self.aircraft
             t0, (x0, y0, psi0, phi0, v0) = exp.t0, exp.p0
@@ -283,7 +291,7 @@ class Planner:
         if initial_guess is None:
             initial_guess = self.get_initial_guess('tri')
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self._host_cost:
+        if self._host_cost or self.field is not None:
             self.info['backend_used'] = 'nlp'
         elif self.backend != 'nlp':
             self._harden()

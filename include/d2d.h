@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 111
+#define D2D_VERSION 112
 
 /* error codes */
 #define D2D_OK 0
@@ -701,6 +701,20 @@ typedef struct {
 } d2d_nlp_model;
 int d2d_nlp_solve_model(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, const d2d_nlp_model *model,
                         double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status);
+
+/* d2d_nlp_solve in a wind field that varies in space and time: the plug-point `atm.sample_sym(t, x(t), y(t))` inside the reference's
+ * equations of motion (src/d2d/opty_utils.py:38-50), as d2d_step_wind is the plug-point sample(t, loc) of its plant.  The equalities read
+ *   (x_i - x_{i-1})/h - v_i cos psi_i + wx(t_i, x_i, y_i) = 0,  (y_i - y_{i-1})/h - v_i sin psi_i + wy(t_i, x_i, y_i) = 0,
+ * with t_i = t_start + i h (one multiply-add, not accumulated) and + the spline's value (the model's +wind quirk: a plan consistent with
+ * a plant that flies F is planned in -F); D2D_SC_WX / D2D_SC_WY of the rows are ignored.  The constraint Jacobian of a node gains
+ * d(wx, wy)/d(x, y) on its (x, y) columns and the Lagrangian Hessian the constraint curvature sum_k rho (c + mu)_k Hess(w_k); along a
+ * clamped coordinate (outside the spline's box) those derivatives are zero.  The field f is shared by the batch (host struct, cp a device
+ * address); an unusable field, or f NULL: D2D_EINVAL, as for the other *_wind entry points.  No partner.  opts (order, slots, bounds,
+ * serial, tolerances), W, work, mult, iters, status as d2d_nlp_solve; feas: the largest collocation residual IN THE FIELD; cost: the
+ * reference's cost().  tests/nlp_wind_ref.py is the CPU statement.  Asynchronous on the context's stream.  (version 112) */
+int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W,
+                       double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
+                       const d2d_wind_field *f, double t_start);
 
 #ifdef __cplusplus
 }
