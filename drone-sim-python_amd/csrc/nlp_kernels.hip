@@ -1459,6 +1459,93 @@ nlp_groups_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_swee
   }
 }
 
+// d2d_nlp_solve_groups_wind: nlp_groups_kernel in a field (a copy, as the tracking loops in a field are: the constant-wind kernel
+// keeps its exact code; change the two together).  Every solve is the WIND instantiation -- the first one with a partner: the
+// collision terms live in the objective and do not meet the field's terms, which live in the equalities.  The field is shared by the
+// launch and travels as a kernel argument (scalar registers); the start time is the SCENARIO's (t_start [R], device memory: the
+// mission chain computes it on the device), wave-uniform.  A scenario whose start time is not finite is refused before its first
+// solve, all its aircraft at once (the whole workgroup leaves: no barrier is left waiting).
+// Registers: 512 threads per workgroup are 8 wavefronts on 4 SIMDs, two per SIMD, so a wavefront gets at most 256 of the SIMD's 512
+// registers whatever amdgpu_waves_per_eu says -- the workgroup size binds, and (2, 2) states what the hardware does.
+#ifndef NLP_GROUPS_WIND_WAVES_PER_SIMD
+#define NLP_GROUPS_WIND_WAVES_PER_SIMD 2
+#endif
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
+nlp_groups_wind_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                       double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                       int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                       double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
+  __shared__ double moved_s[2];
+  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
+  const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int b = r * n_ac + wave;
+  const double t0 = nlp_first_lane(t_start[r]);
+  if (!(fabs(t0) <= 1.79e308)) {             // (uniform over the workgroup: before the first barrier)
+    if (lane == 0) {
+      cost_out[b] = feas_out[b] = __builtin_nan("");
+      if (iters_out) iters_out[b] = 0;
+      if (status_out) status_out[b] = D2D_ST_NONFINITE;
+      if (wave == 0) {
+        if (sweeps_out) sweeps_out[r] = 0;
+        if (moved_out) moved_out[r] = 0.0;
+      }
+    }
+    return;
+  }
+  const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE;
+  double *Wb = W + (size_t)b * NLP_NV * N;
+  double *wsb = work + (size_t)b * WS_TOTAL * N;
+  double *mb = mult ? mult + (size_t)b * 3 * N : nullptr;
+  const bool coupled = n_ac >= 2 && scen[(size_t)(r * n_ac) * D2D_SCEN_STRIDE + D2D_SC_KCOL] > 0.0;       // wave-uniform for the whole group
+  NlpOut out;
+  int iters_total = 0;
+  double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
+  const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
+  const NlpModel no_model{nullptr, nullptr, nullptr};
+  nlp_solve_one<false, true>(N, h, o, sc, nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, &wf, t0);
+  iters_total += out.iters;
+  if (threadIdx.x < 2) moved_s[threadIdx.x] = 0.0;
+  __threadfence_block();
+  __syncthreads();
+  int sweep = 0;
+  double moved = 0.0;
+  if (coupled) {
+    double *pv = prev + (size_t)r * 2 * N;
+    for (sweep = 1; sweep <= max_sweeps; ++sweep) {
+      for (int turn = 0; turn < 2; ++turn) {
+        if (wave == turn) {
+          const double *pw = W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;      // the partner's x and y planes
+          for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
+          nlp_solve_one<false, true>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, &wf, t0);
+          iters_total += out.iters;
+          double m = 0.0;
+          for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
+          m = wave_max(m);
+          if (lane == 0) moved_s[turn] = m;
+        }
+        __threadfence_block();
+        __syncthreads();
+      }
+      moved = fmax(moved_s[0], moved_s[1]);
+      __syncthreads();
+      if (moved <= tol) break;
+    }
+    if (sweep > max_sweeps) sweep = max_sweeps;
+    // not settled after the last sweep: the pair is reported as such (the inner solves each converged, the alternation did not)
+    if (moved > tol && wave < 2 && out.status == D2D_ST_CONVERGED) out.status = D2D_ST_MAXITER;
+  }
+  if (lane == 0) {
+    cost_out[b] = out.cost;
+    feas_out[b] = out.feas;
+    if (iters_out) iters_out[b] = iters_total;
+    if (status_out) status_out[b] = out.status;
+    if (wave == 0) {
+      if (sweeps_out) sweeps_out[r] = sweep;
+      if (moved_out) moved_out[r] = moved;
+    }
+  }
+}
+
 // d2d_nlp_solve_model: the collocation NLP under the quadratic objective model of a cost that only the host can evaluate (a user's
 // cost plug-in, opty/direct_collocation.py).  One wavefront and one workspace per problem: the launch holds the few aircraft of one
 // Problem, so there is nothing to hand out and no second wave per SIMD to fill: it runs at one wave per SIMD (256 VGPRs + 74 AGPRs,
@@ -1573,6 +1660,25 @@ int d2d_nlp_solve_groups(d2d_ctx *ctx, int R, int n_ac, int N, double h, const d
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
   hipLaunchKernelGGL(nlp_groups_kernel, dim3(R), dim3(64 * n_ac), (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double), ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev,
                      cost, feas, iters, status, sweeps, moved);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                              double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                              int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start) {
+  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_groups_wind: null argument");
+  D2D_REQUIRE(R >= 1 && n_ac >= 1 && n_ac <= 8 && N >= 3 && h > 0, "d2d_nlp_solve_groups_wind: R >= 1, 1 <= n_ac <= 8, N >= 3, h > 0 required (R=%d n_ac=%d N=%d h=%g)", R, n_ac, N, h);
+  D2D_REQUIRE(max_sweeps >= 1 && tol >= 0, "d2d_nlp_solve_groups_wind: max_sweeps >= 1 and tol >= 0 required");
+  if (int rc = check_wind(f, "d2d_nlp_solve_groups_wind")) return rc;
+  D2D_REQUIRE(t_start, "d2d_nlp_solve_groups_wind: null t_start (a device array [R]: one start time per scenario)");
+  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
+  if (opts) o = *opts;
+  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_groups_wind: bad options");
+  double *prev = work + (size_t)R * n_ac * WS_TOTAL * N;       // (behind the workspaces, as in d2d_nlp_solve_groups)
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_wind_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
+  hipLaunchKernelGGL(nlp_groups_wind_kernel, dim3(R), dim3(64 * n_ac), (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double), ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
+                     prev, cost, feas, iters, status, sweeps, moved, *f, t_start);
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }

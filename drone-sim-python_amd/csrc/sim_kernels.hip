@@ -470,8 +470,8 @@ gradient_kernel(int T, int n, double inv_dt, const double *__restrict__ f, doubl
   out[(long)i * n + d] = grad2(f, i, T, n, d) * inv_dt;
 }
 
-// Tracking loop, src/11_full_sim_case1.py:272-290.  track_run_wind_kernel below is a copy of this kernel with the plant in a field:
-// change the two together.
+// Tracking loop, src/11_full_sim_case1.py:272-290.  track_run_wind_kernel and track_run_wind_at_kernel below are copies of this kernel with the
+// plant in a field: change them together.
 __global__ void __launch_bounds__(64)
 track_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
                  const double *__restrict__ y_ref, const double *__restrict__ xd,
@@ -796,6 +796,60 @@ track_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict_
   if (iter_max) atomicMax(iter_max, wc.iters);
 }
 
+// d2d_sim_track_run_wind_at: track_run_wind_kernel with a start time per drone, t_at [n] (a copy again: the scalar kernel keeps its
+// exact code; change the three together).  The drones of the mission chain start phase 2 where their own formation ended phase 1.
+// The time of a step is written as in the scalar kernel, t_start + (i - 1) dt.
+__global__ void __launch_bounds__(64)
+track_run_wind_at_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
+                      const double *__restrict__ y_ref, const double *__restrict__ xd,
+                      const double *__restrict__ yd, const double *__restrict__ xdd,
+                      const double *__restrict__ ydd, const double *__restrict__ X0,
+                      double *__restrict__ X_hist, double *__restrict__ U_hist,
+                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
+                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
+                      double *__restrict__ X_final, d2d_wind_field wf, const double *__restrict__ t_at,
+                      int32_t *__restrict__ iter_max) {
+  const long n = p.n;
+  long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const bool live = d < n;
+  if (!live) d = n - 1;
+  const double t_start = t_at[d];
+  WindCtx wc = {&wf, t_start, 0};
+  State5 s = {X0[d], X0[n + d], X0[2 * n + d], X0[3 * n + d], X0[4 * n + d]};
+  if (live && X_hist) {
+    X_hist[d] = s.x; X_hist[n + d] = s.y; X_hist[2 * n + d] = s.psi; X_hist[3 * n + d] = s.phi; X_hist[4 * n + d] = s.v;
+  }
+  for (int i = 1; i < p.n_rows; ++i) {
+    const long r = (long)i * n + d;
+    double Y[8] = {x_ref[r], y_ref[r], xd[r], yd[r], xdd[r], ydd[r], 0.0, 0.0};   // Yddd = [0,0] (:279)
+    const GainOut o = compute_gain(s, Y, p);
+    wc.t = t_start + (i - 1) * p.dt;
+    s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
+    if (live) {
+      const long q = (long)(i - 1);
+      if (U_hist) { U_hist[q * 2 * n + d] = o.U[0]; U_hist[q * 2 * n + n + d] = o.U[1]; }
+      if (dX_hist) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) dX_hist[q * 5 * n + c * n + d] = o.dX[c];
+      }
+      if (Xr_hist) {
+        double *o5 = Xr_hist + q * 5 * n;
+        o5[d] = o.Xr.x; o5[n + d] = o.Xr.y; o5[2 * n + d] = o.Xr.psi; o5[3 * n + d] = o.Xr.phi; o5[4 * n + d] = o.Xr.v;
+      }
+      if (Yd_hist) { Yd_hist[q * 2 * n + d] = Y[2]; Yd_hist[q * 2 * n + n + d] = Y[3]; }
+      if (Ydd_hist) { Ydd_hist[q * 2 * n + d] = Y[4]; Ydd_hist[q * 2 * n + n + d] = Y[5]; }
+      if (X_hist) {
+        double *o5 = X_hist + (long)i * 5 * n;
+        o5[d] = s.x; o5[n + d] = s.y; o5[2 * n + d] = s.psi; o5[3 * n + d] = s.phi; o5[4 * n + d] = s.v;
+      }
+    }
+  }
+  if (live && X_final) {
+    X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
+  }
+  if (iter_max) atomicMax(iter_max, wc.iters);
+}
+
 // dfff_run_kernel in a field (a copy, as above): the plant flies wf, step i from row i - 1 at t_start + (i - 1) dt, and the controller
 // sees the field at (t_i, the position of reference sample i), as DFFFController.get samples it (src/d2d/guidance.py:62-65).
 __global__ void __launch_bounds__(64)
@@ -1008,7 +1062,8 @@ int d2d_sim_dfff_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double 
 
 static int track_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
                           double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
-                          double *X_final, const d2d_wind_field *f, double t_start, int32_t *iter_max, const char *who) {
+                          double *X_final, const d2d_wind_field *f, double t_start, int32_t *iter_max, const char *who,
+                          const double *t_at = nullptr) {
   D2D_REQUIRE(ctx && p && x_ref && y_ref && X0, "%s: null argument", who);
   if (int rc = check_track(p, who)) return rc;
   D2D_REQUIRE(p->n_rows >= 3, "%s: n_rows must be >= 3 (second-order edge differences)", who);
@@ -1030,8 +1085,12 @@ static int track_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double 
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
   if (f) {
     if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(track_run_wind_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
-                       yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_start, iter_max);
+    if (t_at)
+      hipLaunchKernelGGL(track_run_wind_at_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
+                         yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_at, iter_max);
+    else
+      hipLaunchKernelGGL(track_run_wind_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
+                         yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_start, iter_max);
   } else {
     hipLaunchKernelGGL(track_run_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
                        yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final);
@@ -1055,6 +1114,15 @@ int d2d_sim_track_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double
   D2D_REQUIRE(f, "d2d_sim_track_run_wind: null wind field");
   return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, f, t_start, iter_max,
                         "d2d_sim_track_run_wind");
+}
+
+int d2d_sim_track_run_wind_at(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
+                              double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
+                              double *X_final, const d2d_wind_field *f, const double *t_start, int32_t *iter_max) {
+  D2D_REQUIRE(f, "d2d_sim_track_run_wind_at: null wind field");
+  D2D_REQUIRE(t_start, "d2d_sim_track_run_wind_at: null t_start (a device array [n]: one start time per drone)");
+  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, f, 0.0, iter_max,
+                        "d2d_sim_track_run_wind_at", t_start);
 }
 
 int d2d_traj_sample(d2d_ctx *ctx, int n, int T, double t_start, double dt, const double *desc, double *Yref) {

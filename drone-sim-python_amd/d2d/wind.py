@@ -223,6 +223,13 @@ class SplineWindField:
         xdot = v cos(psi) + wx (src/d2d/dynamic.py:18-19): a plan consistent with a plant that flies F is planned in -F."""
         return SplineWindField(-self.cp, self.x0, self.hx, self.y0, self.hy, self.t0, self.ht)
 
+    def negated(self):
+        """-self, built once and kept: callers that plan in -F for a plant that flies F on every call (full_sim's mission chain) reuse
+        one field, and with it its device copy (device_field caches on the field object)."""
+        if getattr(self, '_neg', None) is None:
+            self._neg = -self
+        return self._neg
+
     def summarize(self):
         nt, _, ny, nx = self.cp.shape
         kind = 'steady' if nt == 1 else f'unsteady, t in [{self.t0:g}, {self.t0 + (nt - 3) * self.ht:g}] s'

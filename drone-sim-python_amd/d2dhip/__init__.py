@@ -129,6 +129,7 @@ _SIGS = {
     'd2d_sim_gvf_run_wind': (C.c_int, [_P, C.POINTER(GvfParams)] + [_P] * 13 + [C.POINTER(WindFieldC), C.c_double, _P]),
     'd2d_sim_track_run_wind': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 10 + [C.POINTER(WindFieldC), C.c_double, _P]),
     'd2d_sim_dfff_run_wind': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 7 + [C.POINTER(WindFieldC), C.c_double, _P]),
+    'd2d_sim_track_run_wind_at': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 10 + [C.POINTER(WindFieldC), _P, _P]),
     'd2d_traj_sample': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P]),
     'd2d_dcf_eval': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_double, _P, _P, _P, _P]),
     'd2d_gvf_eval': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, C.c_double, _P]),
@@ -139,6 +140,8 @@ _SIGS = {
     'd2d_nlp_solve': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 8),
     'd2d_nlp_solve_wind': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7 + [C.POINTER(WindFieldC), C.c_double]),
     'd2d_nlp_solve_groups': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9),
+    'd2d_nlp_solve_groups_wind': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
+                                  + [C.POINTER(WindFieldC), _P]),
     'd2d_nlp_solve_model': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.POINTER(NlpModel)] + [_P] * 7),
     'd2d_fit_plan_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(_P)]),
     'd2d_fit_plan_create_ex': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(FitPlanOpts), C.POINTER(_P)]),
@@ -542,6 +545,35 @@ class Context:
                                              None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps), _ptr(moved)))
         return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work)
 
+    def nlp_solve_groups_wind(self, scen, W, h, n_ac, field, t_start, max_sweeps=12, tol=1e-7, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9,
+                              opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0, bounds=None):
+        """nlp_solve_groups with the wind of the equalities read from `field` (a d2d.wind.SplineWindField or a WindFieldC) at every
+        node's own (t_start[r] + i h, x_i, y_i) instead of the rows' constant (d2d_nlp_solve_groups_wind).  t_start: device float64 [R],
+        one start time per scenario (a float is spread over the scenarios).  The model ADDS the field to its residual: a plan for a
+        plant that flies F is solved in -F.  Returns nlp_solve_groups's dict plus t_start and prev [R][2][N] (coupled scenarios: the
+        positions of aircraft 1 before its last turn -- the partner the reported cost of aircraft 0 was evaluated against)."""
+        torch = _torch()
+        B, _, N = W.shape
+        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
+        R = B // n_ac
+        if t_start is not None and not torch.is_tensor(t_start):
+            t_start = torch.full((R,), float(t_start), dtype=torch.float64, device=self.device)
+        assert t_start is None or (t_start.is_contiguous() and tuple(t_start.shape) == (R,) and t_start.dtype == torch.float64 and t_start.device == W.device)
+        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
+        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
+        f = None if field is None else _wind_c(self, field)
+        _check(self.lib.d2d_nlp_solve_groups_wind(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W),
+                                                  _ptr(work), None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps), _ptr(moved),
+                                                  None if f is None else C.byref(f), _ptr(t_start)))
+        # prev [R][2][N]: the kernel's scratch behind the workspaces; it is left holding the x, y planes aircraft 1 had BEFORE its last
+        # turn, i.e. the frozen partner that aircraft 0's last solve (and its reported cost) saw
+        prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
+        return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev)
+
     def nlp_solve_model(self, scen, W, h, g, H, Wc, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
                         outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None):
         """The collocation NLP under a quadratic objective model (d2d_nlp_solve_model): minimise sum_i g_i.d_i + 1/2 d_i^T H_i d_i,
@@ -570,7 +602,8 @@ class Context:
     def track_run(self, x_ref, y_ref, X0, dt, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), out=None, wind=None, t_start=0.0, **kw):
         """x_ref, y_ref dev [T][n]; X0 dev [5][n] -> dict of device histories (out: reuse the buffers of an earlier
         call with the same shapes and `record`).  wind: a field the plant flies (d2d_sim_track_run_wind; the controller keeps the
-        constant w of kw; row i at t_start + i dt); out['iter_max']: the largest fixed-point sweep count."""
+        constant w of kw; row i at t_start + i dt); out['iter_max']: the largest fixed-point sweep count.  t_start: a float, or a
+        device float64 tensor [n] with every drone's own start time (d2d_sim_track_run_wind_at)."""
         T, n = x_ref.shape
         p = self.track_params(n, T, dt, **kw)
         if out is None:
@@ -582,11 +615,16 @@ class Context:
         args = (self.h, C.byref(p), _ptr(x_ref), _ptr(y_ref), _ptr(X0), _ptr(out['X']), _ptr(out['U']), _ptr(out['Xr']), _ptr(out['dX']),
                 _ptr(out['Yd']), _ptr(out['Ydd']), _ptr(out['X_final']))
         if wind is None:
+            assert not hasattr(t_start, 'data_ptr'), 'per-drone start times (a tensor) need a wind field: without one the time is not read'
             _check(self.lib.d2d_sim_track_run(*args))
         else:
             f = _wind_c(self, wind)
             out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
-            _check(self.lib.d2d_sim_track_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
+            if hasattr(t_start, 'data_ptr'):
+                assert t_start.is_contiguous() and tuple(t_start.shape) == (n,) and t_start.dtype == _torch().float64 and t_start.device == x_ref.device
+                _check(self.lib.d2d_sim_track_run_wind_at(*args, C.byref(f), _ptr(t_start), _ptr(out['iter_max'])))
+            else:
+                _check(self.lib.d2d_sim_track_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
 
 

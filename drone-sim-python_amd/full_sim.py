@@ -190,20 +190,30 @@ def implement_controller(n_ac, time, x_ref, y_ref, v, w, X0s):
     return t('X'), t('U'), t('Xr'), t('Yd'), t('Ydd'), t('dX')
 
 
-def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, **solve_kw):
+def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
+               **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
     (d2d_nlp_solve_groups; CostCollision couples aircraft 0 and 1 of a scenario whose rows carry KCOL > 0): W0 (B, 5, K) node
     values of the initial guess, h the time step -> dict with device tensors W (the solution), cost, feas, iters, status per
-    aircraft and sweeps, moved per scenario."""
+    aircraft and sweeps, moved per scenario.  windfield (backend='nlp'): a SplineWindField the problems are planned in, AS GIVEN -- it is the
+    planner's field, whose model adds it to the residual, so a plan for a plant that flies F takes -F -- with node i of scenario r at
+    t_start[r] + i h (d2d_nlp_solve_groups_wind); t_start a float or a device tensor [B / n_ac]; the rows' wind columns are not read."""
     import single_opt_planner as sop
+    from d2d.wind import planner_wind
+    fld = planner_wind(windfield)
+    if fld is not None and backend != 'nlp':
+        raise NotImplementedError("the polynomial fit has no wind field: plan_batch(backend='nlp', windfield=...) plans in one")
     ctx = d2dhip.default_context()
     if backend == 'nlp':
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
         W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
         assert W.shape == (dsc.shape[0], 5, K) and h is not None
-        out = ctx.nlp_solve_groups(dsc, W, float(h), int(n_ac), **solve_kw)
+        if fld is None:
+            out = ctx.nlp_solve_groups(dsc, W, float(h), int(n_ac), **solve_kw)
+        else:
+            out = ctx.nlp_solve_groups_wind(dsc, W, float(h), int(n_ac), fld, t_start, **solve_kw)
         out.update(W=W, scen=dsc)
         return out
     plan = sop.get_plan(K, duration, obj_scale_over_n)
@@ -214,7 +224,7 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
 
 
 def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_sim_end=200., w=(0., 0.), t_step=0.05,
-                          t_end_1=1000., X0=None, max_sweeps=250, record2=('X', 'U'), record3=('X', 'U')):
+                          t_end_1=1000., X0=None, max_sweeps=250, record2=('X', 'U'), record3=('X', 'U'), windfield=None):
     """The three phases of src/11_full_sim_case1.py main() (:406-478) for many independent formations, chained ON THE
     DEVICE: the circular-formation phase hands its final states to the planner as a device tensor, the planner's sampled
     plan is the tracking reference of phase 2 without leaving HBM, and phase 3 restarts from phase 2's final states.
@@ -225,16 +235,31 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
                   (n_form, n_ac, >=3)), t1 = t_opt
       ref3        (time_3, x_ref_3, y_ref_3) of phase 3 -- e.g. ExtendTraj_symm(ExtractTrajData(csv)) -- or None
     Returns a dict of device tensors (plane-major, drone index = formation * n_ac + aircraft):
-      phase1 (gvf_run dict), plan (q, cost, Xs [N][5][K]), phase2 (track_run dict), phase3 (list of track_run dicts)."""
+      phase1 (gvf_run dict), plan (q, cost, Xs [N][5][K]), phase2 (track_run dict), phase3 (list of track_run dicts).
+    windfield: a SplineWindField F the PLANT flies through all three phases; None (or a constant class): the constant w, the chain
+    above.  In a field the chain differs in this:
+      phase 1   flies F (row i at i t_step);
+      the plan  starts, per formation, at the time its phase 1 ended, t2[r] = (min(stop_row[r], rows) - 1) t_step (computed on the
+                device), and is the collocation problem of all aircraft of the formation IN -F (the model adds its wind to the residual:
+                a plan consistent with a plant that flies F is planned in -F), collision pair included -- d2d_nlp_solve_groups_wind.
+                Its initial guess is the polynomial fit of the constant chain, each row's constant wind set to the field at that
+                aircraft's own start pose and time, sampled at the nodes: the fit proposes, the collocation problem decides (as
+                Planner._harden);
+      phase 2   tracks the plan's x, y node planes in F, every drone from its formation's t2; phase 3 likewise, repetition k from
+                t2 + dur2 + k time_3[-1].
+    No state visits the host between the phases.  plan gains W (= Xs, now the collocation plan [N][5][K]), cost_fit, feas, status,
+    iters, sweeps, moved, t_start [n_form] and field (-F, F.negated(): the planner's field; the entry also keeps its device copy
+    alive while the launches that read it are queued); plan['q'] is the fit's (the guess); the controllers keep the constant w."""
     import multi_opt_planner as mop
     import d2d.opty_utils as d2ou
+    F = plant_wind(windfield)
     ctx = d2dhip.default_context()
     torch = d2dhip._torch()
     c = np.asarray(c, dtype=np.float64).reshape(-1, n_ac, 2)
     n_form = c.shape[0]
     X1f = np.broadcast_to(np.asarray(X1_f, dtype=np.float64).reshape(-1, n_ac, np.shape(X1_f)[-1])[:, :, :3], (n_form, n_ac, 3))
     X2f = np.broadcast_to(np.asarray(X2_f, dtype=np.float64).reshape(-1, n_ac, np.shape(X2_f)[-1])[:, :, :3], (n_form, n_ac, 3))
-    ph1 = CircularFormationGVF_batch(c, r, v, n_ac, X0f=X1f, t_step=t_step, t_end=t_end_1, X0=X0, record=())
+    ph1 = CircularFormationGVF_batch(c, r, v, n_ac, X0f=X1f, t_step=t_step, t_end=t_end_1, X0=X0, record=(), windfield=F)
     Xs1 = ph1['X_final']                                            # dev [5][N]: state at each formation's stop row
     # ---- phase 2: plan from where phase 1 ended (scenario rows finished on the device) ----
     scen.t1 = t_opt
@@ -244,6 +269,11 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     rows[:, [d2dhip.SC_X1, d2dhip.SC_Y1, d2dhip.SC_PSI1]] = X2f.reshape(-1, 3)
     dsc = ctx.dev(rows)
     dsc[:, d2dhip.SC_X0], dsc[:, d2dhip.SC_Y0], dsc[:, d2dhip.SC_PSI0] = Xs1[0], Xs1[1], Xs1[2]
+    if F is not None:
+        t2 = (torch.clamp(ph1['stop_row'], max=len(ph1['time'])) - 1).to(torch.float64) * float(t_step)      # dev [n_form]
+        t2d = t2.repeat_interleave(n_ac).contiguous()                                                       # dev [N]: per drone
+        w0 = ctx.wind_sample(F, t2d, Xs1[:2].contiguous())         # (the rows store -w of the planner's wind: -(-F) = F)
+        dsc[:, d2dhip.SC_WX], dsc[:, d2dhip.SC_WY] = w0[0], w0[1]
     q = plan.init(dsc)
     if coupled:
         try:
@@ -253,11 +283,21 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     else:
         cost, iters, status, stats = plan.solve(dsc, q)
     _, Xs = plan.sample(dsc, q)                                     # dev [N][5][K]
-    x_ref2 = Xs[:, 0, :].t().contiguous(); y_ref2 = Xs[:, 1, :].t().contiguous()     # dev [K][N]
+    pl = dict(q=q, cost=cost, Xs=Xs, scen=dsc, stats=stats)
     ac = ddyn.Aircraft()
     kw = dict(w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v)
-    ph2 = ctx.track_run(x_ref2, y_ref2, Xs1, float(dt2), record=record2, **kw)
-    out = dict(phase1=ph1, plan=dict(q=q, cost=cost, Xs=Xs, scen=dsc, stats=stats), phase2=ph2, phase3=[])
+    kw2 = {}
+    if F is not None:                                               # the fit was the guess: the collocation problem in -F from t2
+        Fp = F.negated()
+        Xs = Xs.contiguous().clone()
+        sol = ctx.nlp_solve_groups_wind(dsc, Xs, float(dt2), n_ac, Fp, t2)
+        pl.update(cost_fit=cost, cost=sol['cost'], Xs=Xs, W=Xs, feas=sol['feas'], status=sol['status'], iters=sol['iters'],
+                  sweeps=sol['sweeps'], moved=sol['moved'], t_start=t2, field=Fp)
+        kw['wind'] = F
+        kw2 = dict(t_start=t2d)
+    x_ref2 = Xs[:, 0, :].t().contiguous(); y_ref2 = Xs[:, 1, :].t().contiguous()     # dev [K][N]
+    ph2 = ctx.track_run(x_ref2, y_ref2, Xs1, float(dt2), record=record2, **kw, **kw2)
+    out = dict(phase1=ph1, plan=pl, phase2=ph2, phase3=[])
     # ---- phase 3: the periodic formation-flight reference, restarted from the last state until t_sim_end (:466-474) ----
     if ref3 is not None:
         time_3, x3, y3 = ref3
@@ -268,11 +308,15 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
         stop = ph1['stop_row'].cpu().numpy()
         t_final = float((np.max(np.minimum(stop, len(ph1['time']))) - 1) * t_step + dur2)
         X_last = ph2['X_final']
+        k = 0
         while t_final <= t_sim_end:
-            ph3 = ctx.track_run(x3, y3, X_last, dt3, record=record3, **kw)
+            if F is not None:
+                kw2 = dict(t_start=t2d + (float(dur2) + k * float(time_3[-1])))
+            ph3 = ctx.track_run(x3, y3, X_last, dt3, record=record3, **kw, **kw2)
             out['phase3'].append(ph3)
             X_last = ph3['X_final']
             t_final += float(time_3[-1])
+            k += 1
     return out
 
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 112
+#define D2D_VERSION 113
 
 /* error codes */
 #define D2D_OK 0
@@ -264,6 +264,13 @@ int d2d_sim_track_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double
 int d2d_sim_dfff_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts, const double *X0,
                           double *X_hist, double *U_hist, double *Xr_hist, double *X_final, const d2d_wind_field *f, double t_start,
                           int32_t *iter_max);
+/* d2d_sim_track_run_wind with a start time PER DRONE: t_start dev [n], drone j flies step i from t_start[j] + (i - 1) dt (the
+ * drones of full_sim's mission chain start phase 2 at the row at which their own formation ended phase 1; the array is computed on
+ * the device).  Same validation as d2d_sim_track_run_wind; t_start NULL: D2D_EINVAL.  With all entries equal to t0 the histories
+ * are those of d2d_sim_track_run_wind(.., t0): the step's time is the same expression.  (version 113) */
+int d2d_sim_track_run_wind_at(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
+                              double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
+                              double *X_final, const d2d_wind_field *f, const double *t_start, int32_t *iter_max);
 
 /* Single batched evaluations behind the reference's per-call helper methods (the time
  * loops above fuse them; these exist so that host code written against the reference's
@@ -715,6 +722,23 @@ int d2d_nlp_solve_model(d2d_ctx *ctx, int B, int N, double h, const double *scen
 int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W,
                        double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
                        const d2d_wind_field *f, double t_start);
+
+/* d2d_nlp_solve_groups in a wind field: the multi-aircraft Problem of R scenarios whose equalities are those of d2d_nlp_solve_wind,
+ *   .. + wx(t_i, x_i, y_i) = 0,  .. + wy(t_i, x_i, y_i) = 0,   t_i = t_start[r] + i h  (one multiply-add, not accumulated),
+ * with the field's Jacobian in the constraint Jacobian, its curvature in the Lagrangian Hessian and zero derivatives along a clamped
+ * coordinate; D2D_SC_WX / D2D_SC_WY of the rows are not read.  Arguments, workspace size, statuses and the block Gauss-Seidel are
+ * d2d_nlp_solve_groups's: sweep 0 uncoupled and concurrent, then aircraft 0 and 1 take turns against the partner's frozen node
+ * positions (CostCollision lives in the objective and does not meet the field) until neither moved by more than tol or max_sweeps;
+ * an unsettled pair reports D2D_ST_MAXITER.  t_start is a DEVICE array [R], one start time per scenario (full_sim's mission chain
+ * computes it from each formation's stop row without a host round trip); a non-finite entry refuses that scenario's aircraft at
+ * once (D2D_ST_NONFINITE, cost = feas = NaN, sweeps = 0), like an unusable row.  f NULL, an unusable field or t_start NULL:
+ * D2D_EINVAL before anything is launched.  As in d2d_nlp_solve_groups, the last 2 * N doubles per scenario of work (behind the
+ * R * n_ac workspaces, scenario r at offset r * 2 * N) are left holding the x and y planes aircraft 1 had before its last turn: the
+ * frozen partner that the reported cost of aircraft 0 was evaluated against.  The model ADDS the field: a plan consistent with a plant that flies F is planned in -F.
+ * tests/nlp_groups_wind_ref.py is the CPU statement.  Asynchronous on the context's stream.  (version 113) */
+int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                              double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                              int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,12 @@
 d2dhip.synth.nlp_problems) and one problem alone, in constant wind through d2d_nlp_solve and in a steady (shear) and an unsteady
 (gust) field through d2d_nlp_solve_wind.  The fields are tests/wind_ref.py's with the planner's sign (-F: the plan of a plant that flies
 F; the shear then blows along the leg, and every problem stays feasible below v_max).  HIP events, best of 3 after a warm-up.
-python tools/bench_nlp_wind.py [B ...]     (default 4096 1)"""
+python tools/bench_nlp_wind.py [B ...]     (default 4096 1)
+python tools/bench_nlp_wind.py groups [R]  the multi-aircraft problem (d2d_nlp_solve_groups_wind): R (default 1024) perturbed copies of
+    the trap_4-like scenarios of tests/nlp_groups_wind_ref.py (4 aircraft, 61 nodes, the collision pair active) in the steady shear
+    and the unsteady gust, against d2d_nlp_solve_groups on the same scenarios in the constant wind of the field's mean; then the
+    wall time of the three-formation mission of tests/test_gpu_mission_wind.py (one pass of phase 3) with and without its field.  Median of 5 timed
+    launches after a warm-up, HIP events, one process."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 'tests')):
@@ -11,7 +16,67 @@ for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 
 import numpy as np
 
 
+def groups_leg(R):
+    import torch, d2dhip
+    import d2dhip as D
+    import nlp_groups_wind_ref as G
+    import nlp_wind_ref as NR
+    ctx = d2dhip.Context(0)
+    rng = np.random.default_rng(7)
+    base = G.group_scenarios()
+    rows = np.concatenate([base[r % 3].copy() for r in range(R)])
+    shift = np.repeat(rng.uniform(-3.0, 3.0, (R, 2)), G.N_AC, 0)              # a scenario moves as a whole: the pair keeps its gap
+    rows[:, [D.SC_X0, D.SC_X1]] += shift[:, :1]; rows[:, [D.SC_Y0, D.SC_Y1]] += shift[:, 1:]
+    W0 = np.stack([w.T for w in G.guesses(rows)])
+    fields = NR.fields()
+    for name, t_hi in (('shear', 0.0), ('gust', 6.0)):
+        F = fields[name]
+        mean = F.cp.mean(axis=(0, 2, 3))
+        rows_c = rows.copy(); rows_c[:, D.SC_WX], rows_c[:, D.SC_WY] = -mean[0], -mean[1]
+        t = ctx.dev(rng.uniform(0.0, t_hi, R) if t_hi > 0 else np.zeros(R))
+        res = {}
+        for kind in ('constant', 'field'):
+            dsc = ctx.dev(rows_c if kind == 'constant' else rows)
+            times = []
+            for rep in range(6):                             # the first launch is the warm-up
+                W = ctx.dev(np.ascontiguousarray(W0))
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                out = ctx.nlp_solve_groups(dsc, W, G.H, G.N_AC) if kind == 'constant' else ctx.nlp_solve_groups_wind(dsc, W, G.H, G.N_AC, F, t)
+                e1.record(); torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1) * 1e-3)
+            med = float(np.median(times[1:]))
+            st = out['status'].cpu().numpy(); it = out['iters'].cpu().numpy(); sw = out['sweeps'].cpu().numpy()
+            res[kind] = med
+            print(json.dumps({'leg': 'groups', 'R': R, 'n_ac': G.N_AC, 'nodes': G.N_NODES, 'field': name, 'wind': kind, 'seconds_median': med,
+                              'seconds_min': min(times[1:]), 'seconds_max': max(times[1:]), 'scenarios_per_s': R / med,
+                              'aircraft_problems_per_s': R * G.N_AC / med, 'vs_constant': med / res['constant'],
+                              'converged_frac': float((st == 1).mean()), 'mean_newton_steps': float(it.mean()), 'max_newton_steps': int(it.max()),
+                              'mean_sweeps': float(sw.mean()), 'max_sweeps': int(sw.max())}), flush=True)
+    ctx.close()
+    # the mission of tests/test_gpu_mission_wind.py (three formations, the plan, its tracking, ONE pass of phase 3), with and without its
+    # field: wall clock around the chain, device synchronised
+    import time
+    import full_sim as fs
+    import multi_opt_planner as mop
+    n_ac, c, X1_f, X2_f, X0B, ref3 = G.mission_inputs()
+    cB = np.stack([c, c, c])
+    dctx = d2dhip.default_context()
+    for name, F in (('none', None), ('mission_field', G.mission_field())):
+        ph1 = fs.CircularFormationGVF_batch(cB, 60, 15, n_ac, X0f=np.stack([X1_f] * 3)[:, :, :3], X0=X0B, record=(), windfield=F)
+        t_end = G.mission_t_end(ph1['stop_row'].cpu().numpy(), len(ph1['time']), 0.05, 6, ref3[0], 1)
+        times = []
+        for rep in range(6):
+            dctx.sync(); t0 = time.perf_counter()
+            out = fs.full_sim_phases_batch(cB, 60, 15, n_ac, X1_f, mop.trap_4, X2_f, 6, ref3=ref3, t_sim_end=t_end, X0=X0B, windfield=F)
+            dctx.sync(); times.append(time.perf_counter() - t0)
+        print(json.dumps({'leg': 'mission', 'formations': 3, 'field': name, 'phase3_passes': len(out['phase3']),
+                          'seconds_median': float(np.median(times[1:])), 'seconds_min': min(times[1:]), 'seconds_max': max(times[1:])}), flush=True)
+
+
 def main():
+    if sys.argv[1:2] == ['groups']:
+        return groups_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024)
     import torch, d2dhip
     from d2dhip import synth
     import wind_ref as WR
