@@ -74,9 +74,14 @@ __device__ __forceinline__ void nlp_obs(const double *__restrict__ sc, int i, do
 // position-dependent exp terms of one node (oracle/nlp.py _obst_terms): adds the objective value (the function whose
 // gradient is the reference's cost_grad: kind-1 terms scaled by (r/k)^2), its half gradient and half Gauss-Newton block;
 // cost_ref accumulates the reference's cost() value of the same terms.
+// PAIRS (d2d_nlp_solve_groups_pairs): `partner` is the base of the scenario's W ([n_ac][5][N], pstride = N) and pmask the set of
+// this aircraft's partners, bit j = aircraft j: a wave-uniform value (scalar register), walked bit by bit in a ROLLED loop -- one
+// partner's terms live at a time, whatever the count (an unrolled loop over seven partners would spill: the kernel already sits at
+// the register limit), and no lane diverges.  Ascending j: with the mask of one partner the sums are the frozen partner's above.
+template <bool PAIRS = false>
 __device__ __forceinline__ void nlp_exp_terms(const NlpScen &s, const double *__restrict__ sc, const double *__restrict__ partner,
                                               long pidx, long pstride, double x, double y, double &obj, double &cost_ref,
-                                              double *gx, double *gy, double *dxx, double *dxy, double *dyy) {
+                                              double *gx, double *gy, double *dxx, double *dxy, double *dyy, unsigned pmask = 0u) {
   for (int i = 0; i < s.n_obs; ++i) {
     double cx, cy, r;
     nlp_obs(sc, i, cx, cy, r);
@@ -103,7 +108,23 @@ __device__ __forceinline__ void nlp_exp_terms(const NlpScen &s, const double *__
       *dxx += k2 * k2 * we * dx * dx; *dxy += k2 * k2 * we * dx * dy; *dyy += k2 * k2 * we * dy * dy;
     }
   }
-  if (partner != nullptr && s.wcol > 0.0) {     // CostCollision against the frozen partner (src/d2d/multiopty_utils.py:120-153)
+  if constexpr (PAIRS) {
+    if (s.wcol > 0.0) {                         // CostCollision against every frozen partner of the set
+#pragma clang loop unroll(disable)
+      for (unsigned m = pmask; m != 0u; m &= m - 1u) {
+        const double *__restrict__ pj = partner + (size_t)__builtin_ctz(m) * NLP_NV * pstride;     // aircraft j's x plane; y follows
+        const double dx = x - pj[pidx], dy = y - pj[pidx + pstride];
+        const double e = exp(-(dx * dx + dy * dy) * s.kc2);
+        cost_ref += s.wcol * e;
+        const double we = s.wcol / s.kc2 * e;
+        obj += we;
+        if (gx) {
+          *gx += -s.kc2 * we * dx; *gy += -s.kc2 * we * dy;
+          *dxx += s.kc2 * s.kc2 * we * dx * dx; *dxy += s.kc2 * s.kc2 * we * dx * dy; *dyy += s.kc2 * s.kc2 * we * dy * dy;
+        }
+      }
+    }
+  } else if (partner != nullptr && s.wcol > 0.0) {     // CostCollision against the frozen partner (src/d2d/multiopty_utils.py:120-153)
     const double dx = x - partner[pidx], dy = y - partner[pidx + pstride];
     const double e = exp(-(dx * dx + dy * dy) * s.kc2);
     cost_ref += s.wcol * e;
@@ -144,7 +165,8 @@ struct NlpProb {
   double *W;                 // [5][N] node values
   double *ws;                // WS_TOTAL * N doubles (see above)
   double *mu;                // [3][N]
-  const double *partner;     // [2][N] or null
+  const double *partner;     // [2][N] or null; PAIRS instantiations: the scenario's W [n_ac][5][N]
+  unsigned pmask;            // PAIRS instantiations: the partner set (bit j = aircraft j of the scenario), wave-uniform; else 0
   double *lds;               // this wavefront's NLP_LDS_DOUBLES doubles of LDS (nlp_assemble: neighbour hand-over, record transposition)
   const d2d_wind_field *wf;  // WIND instantiations (d2d_nlp_solve_wind): the field of the equalities, node i at t0 + i h; else null
   double t0;
@@ -214,7 +236,7 @@ __device__ __forceinline__ bool nlp_fixed(int i, int N, int c) { return c < 3 &&
 
 // Merit function of the inner problem at W + a*dw: objective + rho sum (c + mu)^2 - mub sum log(slacks); +inf outside the box.
 // Node-parallel (lane = node, chunks of 64) + wave reductions.  All results are wave-uniform.
-template <bool MODEL, bool WIND = false>
+template <bool MODEL, bool WIND = false, bool PAIRS = false>
 __device__ double nlp_merit(const NlpProb &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
                             double mub, double *cost_ref_out, double *feas_out, const NlpModel &md) {
   const int N = pb.N;
@@ -262,7 +284,7 @@ __device__ double nlp_merit(const NlpProb &pb, const NlpScen &s, const double *_
       }
       phi2max = fmax(phi2max, w[3] * w[3]);
       cref += obj;
-      nlp_exp_terms(s, sc, pb.partner, i, N, w[0], w[1], obj, cref, nullptr, nullptr, nullptr, nullptr, nullptr);
+      nlp_exp_terms<PAIRS>(s, sc, pb.partner, i, N, w[0], w[1], obj, cref, nullptr, nullptr, nullptr, nullptr, nullptr, pb.pmask);
       val += obj;
       if (i >= 1) {
         double c3[3];
@@ -323,7 +345,7 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // WIND (d2d_nlp_solve_wind): the constraint that ends at node i reads the field at (t_i, x_i, y_i): with J = d(wx, wy)/d(x, y) there,
 // Ac gains J on its (x, y) columns and D the constraint curvature rho (c + mu)_0 Hess(wx) + rho (c + mu)_1 Hess(wy) on its (x, y)
 // block; node i+1's constraint sees node i through -1/h only, so the has_next terms and the structure of E do not change.
-template <bool MODEL, bool WIND = false>
+template <bool MODEL, bool WIND = false, bool PAIRS = false>
 __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
                                double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md) {
   const int N = pb.N;
@@ -407,7 +429,7 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
     }
     {
       double obj = 0.0, cref = 0.0;
-      nlp_exp_terms(s, sc, pb.partner, i, N, wc[0], wc[1], obj, cref, &g[0], &g[1], &D[0][0], &D[0][1], &D[1][1]);
+      nlp_exp_terms<PAIRS>(s, sc, pb.partner, i, N, wc[0], wc[1], obj, cref, &g[0], &g[1], &D[0][0], &D[0][1], &D[1][1], pb.pmask);
       D[1][0] = D[0][1];
     }
     double E[NLP_NV][3];                        // block (i, i-1): only the (x, y, psi) columns of node i-1 are non-zero
@@ -1123,11 +1145,12 @@ struct NlpOut { double cost, feas; int iters, status; };
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
 // MODEL: the objective is the quadratic model md (d2d_nlp_solve_model) on top of the row's structured terms; cost = its value.
 // WIND: the equalities read the field wf at node i's own (t_start + i h, x_i, y_i) instead of the row's constant (d2d_nlp_solve_wind).
-template <bool MODEL = false, bool WIND = false>
+// PAIRS: partner is the scenario's W and pmask this aircraft's partner set (nlp_exp_terms); pmask = 0: no partner.
+template <bool MODEL = false, bool WIND = false, bool PAIRS = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
                                               const double *__restrict__ bnd, const NlpModel &md = NlpModel{nullptr, nullptr, nullptr},
-                                              const d2d_wind_field *wf = nullptr, double t_start = 0.0) {
+                                              const d2d_wind_field *wf = nullptr, double t_start = 0.0, unsigned pmask = 0u) {
   // diagnostics (D2D_NLP_STAMPS): cycles per phase -- merit, assembly, factorisation, back substitution, ratio tests, update
   unsigned long long st_t = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define NLP_STAMP(k) if (st_on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t; st_t = t_; }
@@ -1141,6 +1164,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   pb.ws = wsb;
   pb.mu = multb ? multb : pb.ws + (size_t)WS_MU * N;
   pb.partner = partner;
+  pb.pmask = pmask;
   pb.lds = ldsw;
   pb.wf = wf; pb.t0 = t_start;
   // (a row whose bounds are unset or inverted would give a zero-width box, infinite duals and NaN pivots for
@@ -1204,7 +1228,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     const double tol_in = fmax(fmax(o.opt_tol, fmin(1e-1, 10.0 * mub)), D2D_NLP_GRAD_FLOOR * rho);
     // merit value of the current point for this (mub, rho, mu): one pass here, afterwards the accepted trial's value
     NLP_STAMP(7)
-    double phi0 = nlp_merit<MODEL, WIND>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    double phi0 = nlp_merit<MODEL, WIND, PAIRS>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1215,7 +1239,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       const int imax = s.sbank > 0.0 ? nlp_bank_argmax(pb, lane) : -1;
       for (int tr = 0; tr < 30; ++tr) {
         bool pd;
-        err = nlp_assemble<MODEL, WIND>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<MODEL, WIND, PAIRS>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -1238,7 +1262,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         double a = amax, pt = 0.0;
         bool ok = false;
         for (int ls = 0; ls < 8; ++ls) {
-          pt = nlp_merit<MODEL, WIND>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
+          pt = nlp_merit<MODEL, WIND, PAIRS>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
@@ -1256,7 +1280,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       }
       if (converged || !accepted) break;
     }
-    (void)nlp_merit<MODEL, WIND>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+    (void)nlp_merit<MODEL, WIND, PAIRS>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -1295,7 +1319,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     feas_prev = feas;
     mub = fmax(o.mub_min, fmin(0.2 * mub, mub * sqrt(mub)));
   }
-  (void)nlp_merit<MODEL, WIND>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+  (void)nlp_merit<MODEL, WIND, PAIRS>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -1546,6 +1570,119 @@ nlp_groups_wind_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max
   }
 }
 
+// d2d_nlp_solve_groups_pairs: the block Gauss-Seidel of nlp_groups_kernel / nlp_groups_wind_kernel over ANY set of coupled pairs (a
+// copy again: those two keep their exact code; WIND selects the instantiation of the solve -- the rows' constant wind or the field).
+// D2D_SC_PMASK of aircraft a's row is its partner set, bit j = aircraft j of the same scenario.  Sweep 0 solves every aircraft
+// uncoupled, concurrently; in sweeps 1.. the aircraft with a non-empty set take turns in index order (workgroup barriers between
+// the turns), each turn a full solve from the aircraft's current nodes against the frozen (x, y) planes of ALL its partners, which
+// nlp_exp_terms reads from their W in global memory (L2-resident: 2 x N doubles per partner, and no partner's wave writes meanwhile)
+// through a rolled loop over the set bits of the mask in a scalar register.  The coupling is in the objective only, so a fixed point
+// is a KKT point of the joint problem, as for one pair.  With the masks of the pair (0, 1) every solve, sum and barrier is that of
+// nlp_groups_kernel (tests/test_gpu_collision_pairs.py: equal bit for bit).
+// The masks of a scenario are checked before its first solve, by every wavefront alike (scalar loads): an entry that is no integer in
+// [0, 2^n_ac), a self bit or a bit j whose aircraft j does not name a back -- the term of a pair belongs to both objectives or to none
+// -- refuses the whole scenario at once (D2D_ST_NONFINITE, cost = feas = NaN, sweeps = 0, W untouched; the whole workgroup leaves
+// before the first barrier), like a non-finite start time: no mask ever indexes outside the scenario's W.
+template <bool WIND>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
+nlp_groups_pairs_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                        double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                        int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                        double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
+  __shared__ double moved_s[8];
+  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
+  const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int b = r * n_ac + wave;
+  double t0 = 0.0;
+  bool bad = false;
+  if constexpr (WIND) {
+    t0 = nlp_first_lane(t_start[r]);
+    bad = !(fabs(t0) <= 1.79e308);
+  }
+  // the scenario's masks, 8 bits per aircraft; cset: the aircraft that take turns
+  unsigned long long masks = 0ull;
+  unsigned cset = 0u;
+  for (int a = 0; a < n_ac; ++a) {
+    const double pm = scen[(size_t)(r * n_ac + a) * D2D_SCEN_STRIDE + D2D_SC_PMASK];
+    if (!(pm >= 0.0 && pm < (double)(1u << n_ac)) || pm != floor(pm)) { bad = true; continue; }
+    const unsigned m = (unsigned)pm;
+    if ((m >> a) & 1u) bad = true;
+    masks |= (unsigned long long)m << (8 * a);
+    if (m != 0u) cset |= 1u << a;
+  }
+  for (int a = 0; a < n_ac; ++a)
+    for (int j = 0; j < n_ac; ++j)
+      if (((masks >> (8 * a + j)) & 1ull) != ((masks >> (8 * j + a)) & 1ull)) bad = true;
+  bad = __builtin_amdgcn_readfirstlane((int)bad) != 0;
+  if (bad) {                                 // (uniform over the workgroup: before the first barrier)
+    if (lane == 0) {
+      cost_out[b] = feas_out[b] = __builtin_nan("");
+      if (iters_out) iters_out[b] = 0;
+      if (status_out) status_out[b] = D2D_ST_NONFINITE;
+      if (wave == 0) {
+        if (sweeps_out) sweeps_out[r] = 0;
+        if (moved_out) moved_out[r] = 0.0;
+      }
+    }
+    return;
+  }
+  cset = (unsigned)__builtin_amdgcn_readfirstlane((int)cset);
+  const unsigned pmask = (unsigned)__builtin_amdgcn_readfirstlane((int)((masks >> (8 * wave)) & 0xffull));
+  const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE;
+  double *Wb = W + (size_t)b * NLP_NV * N;
+  double *wsb = work + (size_t)b * WS_TOTAL * N;
+  double *mb = mult ? mult + (size_t)b * 3 * N : nullptr;
+  const double *Wr = W + (size_t)r * n_ac * NLP_NV * N;        // the scenario's W: partner j's planes at j * 5 * N
+  NlpOut out;
+  int iters_total = 0;
+  double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
+  const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
+  const NlpModel no_model{nullptr, nullptr, nullptr};
+  nlp_solve_one<false, WIND, true>(N, h, o, sc, Wr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, &wf, t0, 0u);
+  iters_total += out.iters;
+  if (threadIdx.x < 8) moved_s[threadIdx.x] = 0.0;
+  __threadfence_block();
+  __syncthreads();
+  int sweep = 0;
+  double moved = 0.0;
+  if (cset != 0u) {
+    double *pv = prev + (size_t)r * 2 * N;
+    for (sweep = 1; sweep <= max_sweeps; ++sweep) {
+      for (int turn = 0; turn < n_ac; ++turn) {
+        if (!((cset >> turn) & 1u)) continue;
+        if (wave == turn) {
+          for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
+          nlp_solve_one<false, WIND, true>(N, h, o, sc, Wr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, &wf, t0, pmask);
+          iters_total += out.iters;
+          double m = 0.0;
+          for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
+          m = wave_max(m);
+          if (lane == 0) moved_s[turn] = m;
+        }
+        __threadfence_block();
+        __syncthreads();
+      }
+      moved = 0.0;
+      for (int a = 0; a < n_ac; ++a) moved = fmax(moved, moved_s[a]);       // (the entries of aircraft outside cset stay 0)
+      __syncthreads();
+      if (moved <= tol) break;
+    }
+    if (sweep > max_sweeps) sweep = max_sweeps;
+    // not settled after the last sweep: the coupled aircraft are reported as such (the inner solves each converged, the alternation did not)
+    if (moved > tol && ((cset >> wave) & 1u) && out.status == D2D_ST_CONVERGED) out.status = D2D_ST_MAXITER;
+  }
+  if (lane == 0) {
+    cost_out[b] = out.cost;
+    feas_out[b] = out.feas;
+    if (iters_out) iters_out[b] = iters_total;
+    if (status_out) status_out[b] = out.status;
+    if (wave == 0) {
+      if (sweeps_out) sweeps_out[r] = sweep;
+      if (moved_out) moved_out[r] = moved;
+    }
+  }
+}
+
 // d2d_nlp_solve_model: the collocation NLP under the quadratic objective model of a cost that only the host can evaluate (a user's
 // cost plug-in, opty/direct_collocation.py).  One wavefront and one workspace per problem: the launch holds the few aircraft of one
 // Problem, so there is nothing to hand out and no second wave per SIMD to fill: it runs at one wave per SIMD (256 VGPRs + 74 AGPRs,
@@ -1679,6 +1816,33 @@ int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, co
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_wind_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
   hipLaunchKernelGGL(nlp_groups_wind_kernel, dim3(R), dim3(64 * n_ac), (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double), ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
                      prev, cost, feas, iters, status, sweeps, moved, *f, t_start);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+int d2d_nlp_solve_groups_pairs(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                               double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                               int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start) {
+  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_groups_pairs: null argument");
+  D2D_REQUIRE(R >= 1 && n_ac >= 1 && n_ac <= 8 && N >= 3 && h > 0, "d2d_nlp_solve_groups_pairs: R >= 1, 1 <= n_ac <= 8, N >= 3, h > 0 required (R=%d n_ac=%d N=%d h=%g)", R, n_ac, N, h);
+  D2D_REQUIRE(max_sweeps >= 1 && tol >= 0, "d2d_nlp_solve_groups_pairs: max_sweeps >= 1 and tol >= 0 required");
+  D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_groups_pairs: f and t_start go together (both NULL: the rows' constant wind)");
+  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_groups_pairs")) return rc; }
+  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
+  if (opts) o = *opts;
+  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_groups_pairs: bad options");
+  double *prev = work + (size_t)R * n_ac * WS_TOTAL * N;       // (behind the workspaces, as in d2d_nlp_solve_groups)
+  const size_t lds = (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double);
+  if (f) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_pairs_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
+    hipLaunchKernelGGL(nlp_groups_pairs_kernel<true>, dim3(R), dim3(64 * n_ac), lds, ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
+                       prev, cost, feas, iters, status, sweeps, moved, *f, t_start);
+  } else {
+    const d2d_wind_field none = {};
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_pairs_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
+    hipLaunchKernelGGL(nlp_groups_pairs_kernel<false>, dim3(R), dim3(64 * n_ac), lds, ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
+                       prev, cost, feas, iters, status, sweeps, moved, none, t_start);
+  }
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }

@@ -96,39 +96,95 @@ class CostObstacles:
         return np.sum([c.cost_grad(free, _p) for c in self.obss], axis=0)
 
 
+def collision_pairs(pairs, n):
+    """The unordered pairs (i, j), i < j, that a `pairs` argument selects among n aircraft: None -> the reference's pair (0, 1)
+    (src/d2d/multiopty_utils.py:124-125), 'all' -> every pair, an iterable of (i, j) -> those.  ValueError for i == j, an index
+    outside 0 .. n-1 or a repeated pair."""
+    if pairs is None:
+        return [(0, 1)]
+    if isinstance(pairs, str):
+        if pairs != 'all':
+            raise ValueError(f"pairs: None, 'all' or an iterable of (i, j), not {pairs!r}")
+        return [(i, j) for i in range(n) for j in range(i + 1, n)]
+    out = []
+    for p in pairs:
+        try:
+            i, j = p
+            ok = int(i) == i and int(j) == j
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f'pairs: {p!r} is not a pair of aircraft indices')
+        i, j = int(i), int(j)
+        if i == j:
+            raise ValueError(f'pairs: aircraft {i} paired with itself')
+        if not (0 <= i < n and 0 <= j < n):
+            raise ValueError(f'pairs: ({i}, {j}) names an aircraft outside 0 .. {n - 1}')
+        q = (min(i, j), max(i, j))
+        if q in out:
+            raise ValueError(f'pairs: {q} given twice')
+        out.append(q)
+    return out
+
+
+def pair_masks(pairs, n):
+    """Partner set of each of n aircraft (bit j: coupled with aircraft j -- D2D_SC_PMASK) for the pairs of collision_pairs."""
+    masks = [0] * n
+    for i, j in pairs:
+        masks[i] |= 1 << j
+        masks[j] |= 1 << i
+    return masks
+
+
 class CostCollision:
-    """Gaussian proximity penalty between aircraft 0 and 1 (src/d2d/multiopty_utils.py:120-153)."""
+    """Gaussian proximity penalty between aircraft 0 and 1 (src/d2d/multiopty_utils.py:120-153).  pairs: None -- that pair, as in
+    the reference; 'all' -- every unordered pair of the planner's aircraft; an iterable of (i, j) -- those pairs.  The same term
+    for every selected pair, each pair once, scale obj_scale / num_nodes."""
 
-    def __init__(self, r=3., k=2.):
-        self.r, self.k = r, k
+    def __init__(self, r=3., k=2., pairs=None):
+        self.r, self.k, self.pairs = r, k, pairs
 
-    def _d(self, free, _p):
-        return free[_p._slice_x[0]] - free[_p._slice_x[1]], free[_p._slice_y[0]] - free[_p._slice_y[1]]
+    def _pairs(self, _p):
+        return collision_pairs(self.pairs, len(_p._slice_x))
+
+    def _d(self, free, _p, i=0, j=1):
+        return free[_p._slice_x[i]] - free[_p._slice_x[j]], free[_p._slice_y[i]] - free[_p._slice_y[j]]
 
     def cost(self, free, _p):
-        dx, dy = self._d(free, _p)
-        return _p.obj_scale / _p.num_nodes * np.sum(d2ou._obstacle_field(dx, dy, self.r, 1, self.k))
+        if self.pairs is None:
+            dx, dy = self._d(free, _p)
+            return _p.obj_scale / _p.num_nodes * np.sum(d2ou._obstacle_field(dx, dy, self.r, 1, self.k))
+        return _p.obj_scale / _p.num_nodes * sum(np.sum(d2ou._obstacle_field(*self._d(free, _p, i, j), self.r, 1, self.k))
+                                                 for i, j in self._pairs(_p))
 
     def cost_grad(self, free, _p):
-        dx, dy = self._d(free, _p)
-        e = d2ou._obstacle_field(dx, dy, self.r, 1, self.k)
         f = _p.obj_scale / _p.num_nodes
         g = np.zeros_like(free)
-        g[_p._slice_x[0]], g[_p._slice_y[0]] = f * -2. * dx * e, f * -2. * dy * e
-        g[_p._slice_x[1]], g[_p._slice_y[1]] = f * 2. * dx * e, f * 2. * dy * e
+        if self.pairs is None:
+            dx, dy = self._d(free, _p)
+            e = d2ou._obstacle_field(dx, dy, self.r, 1, self.k)
+            g[_p._slice_x[0]], g[_p._slice_y[0]] = f * -2. * dx * e, f * -2. * dy * e
+            g[_p._slice_x[1]], g[_p._slice_y[1]] = f * 2. * dx * e, f * 2. * dy * e
+            return g
+        for i, j in self._pairs(_p):
+            dx, dy = self._d(free, _p, i, j)
+            e = d2ou._obstacle_field(dx, dy, self.r, 1, self.k)
+            g[_p._slice_x[i]] += f * -2. * dx * e; g[_p._slice_y[i]] += f * -2. * dy * e
+            g[_p._slice_x[j]] += f * 2. * dx * e; g[_p._slice_y[j]] += f * 2. * dy * e
         return g
 
 
 class CostComposit:
     """CostInput [+ kobs * obstacles] [+ kcol * collision]; a NaN weight switches a term off
-    (src/d2d/multiopty_utils.py:156-174)."""
+    (src/d2d/multiopty_utils.py:156-174).  col_pairs: CostCollision's `pairs`."""
 
-    def __init__(self, kvel=1., kbank=1., kobs=float('Nan'), kcol=float('NaN'), vsp=10., obss=[], obs_kind=0, rcol=3.):
+    def __init__(self, kvel=1., kbank=1., kobs=float('Nan'), kcol=float('NaN'), vsp=10., obss=[], obs_kind=0, rcol=3., col_pairs=None):
         self.kvel, self.kbank, self.kobs, self.kcol = kvel, kbank, kobs, kcol
         self.vsp, self.obss, self.obs_kind, self.rcol = vsp, obss, obs_kind, rcol
         self.ci = CostInput(vsp, kvel, kbank)
         self.cobs = CostObstacles(obss, obs_kind)      # always constructed, as in the reference (:160-161)
-        self.ccol = CostCollision(r=rcol)
+        self.col_pairs = col_pairs                     # CostCollision(pairs=): None = the reference's pair (0, 1)
+        self.ccol = CostCollision(r=rcol, pairs=col_pairs)
 
     def _extra(self):
         return [(k, c) for k, c in ((self.kobs, self.cobs), (self.kcol, self.ccol)) if not np.isnan(k)]

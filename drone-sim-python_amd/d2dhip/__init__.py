@@ -142,6 +142,8 @@ _SIGS = {
     'd2d_nlp_solve_groups': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9),
     'd2d_nlp_solve_groups_wind': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
                                   + [C.POINTER(WindFieldC), _P]),
+    'd2d_nlp_solve_groups_pairs': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
+                                   + [C.POINTER(WindFieldC), _P]),
     'd2d_nlp_solve_model': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.POINTER(NlpModel)] + [_P] * 7),
     'd2d_fit_plan_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(_P)]),
     'd2d_fit_plan_create_ex': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(FitPlanOpts), C.POINTER(_P)]),
@@ -571,6 +573,36 @@ class Context:
                                                   None if f is None else C.byref(f), _ptr(t_start)))
         # prev [R][2][N]: the kernel's scratch behind the workspaces; it is left holding the x, y planes aircraft 1 had BEFORE its last
         # turn, i.e. the frozen partner that aircraft 0's last solve (and its reported cost) saw
+        prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
+        return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev)
+
+    def nlp_solve_groups_pairs(self, scen, W, h, n_ac, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0, mub0=0.1, mub_min=1e-9,
+                               feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0, bounds=None):
+        """nlp_solve_groups / nlp_solve_groups_wind with CostCollision on any set of pairs (d2d_nlp_solve_groups_pairs): SC_PMASK of
+        aircraft a's row is its partner set (bit j: aircraft j of the scenario), and every aircraft with a partner takes turns against
+        the frozen positions of all of them.  field None: the rows' constant wind (t_start is not read); else as nlp_solve_groups_wind.
+        A scenario with a malformed mask (no integer in [0, 2^n_ac), a self bit, a bit its partner does not return) is refused on the
+        device: status ST_NONFINITE, cost = feas = NaN, sweeps 0, its W untouched.  Returns nlp_solve_groups_wind's dict."""
+        torch = _torch()
+        B, _, N = W.shape
+        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
+        R = B // n_ac
+        if field is None:
+            t_start = None
+        else:
+            if not torch.is_tensor(t_start):
+                t_start = torch.full((R,), float(0.0 if t_start is None else t_start), dtype=torch.float64, device=self.device)
+            assert t_start.is_contiguous() and tuple(t_start.shape) == (R,) and t_start.dtype == torch.float64 and t_start.device == W.device
+        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
+        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
+        f = None if field is None else _wind_c(self, field)
+        _check(self.lib.d2d_nlp_solve_groups_pairs(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W),
+                                                   _ptr(work), None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps), _ptr(moved),
+                                                   None if f is None else C.byref(f), _ptr(t_start)))
         prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
         return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev)
 

@@ -190,6 +190,16 @@ def implement_controller(n_ac, time, x_ref, y_ref, v, w, X0s):
     return t('X'), t('U'), t('Xr'), t('Yd'), t('Ydd'), t('dX')
 
 
+def _rows_select_pairs(scen_rows, n_ac):
+    """True when the rows' partner sets (SC_PMASK) are anything but what the default lowering writes -- 0b10 / 0b01 (or nothing) on
+    aircraft 0 and 1, nothing on the others: such rows are solved by d2d_nlp_solve_groups_pairs (multi_opt_planner.scenario_rows
+    writes them for CostCollision(pairs=) / CostComposit(col_pairs=))."""
+    pm = np.asarray(scen_rows, dtype=np.float64)[:, d2dhip.SC_PMASK].reshape(-1, n_ac)
+    if n_ac < 2:
+        return bool((pm != 0).any())
+    return bool((~np.isin(pm[:, 0], (0, 0b10))).any() or (~np.isin(pm[:, 1], (0, 0b01))).any() or (pm[:, 2:] != 0).any())
+
+
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
                **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
@@ -199,7 +209,9 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     values of the initial guess, h the time step -> dict with device tensors W (the solution), cost, feas, iters, status per
     aircraft and sweeps, moved per scenario.  windfield (backend='nlp'): a SplineWindField the problems are planned in, AS GIVEN -- it is the
     planner's field, whose model adds it to the residual, so a plan for a plant that flies F takes -F -- with node i of scenario r at
-    t_start[r] + i h (d2d_nlp_solve_groups_wind); t_start a float or a device tensor [B / n_ac]; the rows' wind columns are not read."""
+    t_start[r] + i h (d2d_nlp_solve_groups_wind); t_start a float or a device tensor [B / n_ac]; the rows' wind columns are not read.
+    Rows whose SC_PMASK name other partners than the pair (0, 1) (multi_opt_planner.scenario_rows for a cost with `pairs`) are solved
+    by d2d_nlp_solve_groups_pairs, with and without a field."""
     import single_opt_planner as sop
     from d2d.wind import planner_wind
     fld = planner_wind(windfield)
@@ -210,7 +222,9 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
         W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
         assert W.shape == (dsc.shape[0], 5, K) and h is not None
-        if fld is None:
+        if _rows_select_pairs(scen_rows, int(n_ac)):        # partner sets other than the reference's pair (0, 1)
+            out = ctx.nlp_solve_groups_pairs(dsc, W, float(h), int(n_ac), fld, t_start, **solve_kw)
+        elif fld is None:
             out = ctx.nlp_solve_groups(dsc, W, float(h), int(n_ac), **solve_kw)
         else:
             out = ctx.nlp_solve_groups_wind(dsc, W, float(h), int(n_ac), fld, t_start, **solve_kw)
@@ -249,7 +263,10 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
                 t2 + dur2 + k time_3[-1].
     No state visits the host between the phases.  plan gains W (= Xs, now the collocation plan [N][5][K]), cost_fit, feas, status,
     iters, sweeps, moved, t_start [n_form] and field (-F, F.negated(): the planner's field; the entry also keeps its device copy
-    alive while the launches that read it are queued); plan['q'] is the fit's (the guess); the controllers keep the constant w."""
+    alive while the launches that read it are queued); plan['q'] is the fit's (the guess); the controllers keep the constant w.
+    A scen.cost that selects its own collision pairs (CostComposit(col_pairs=...)): the fit couples those pairs (SC_PMASK) and the
+    plan is the collocation problem over all of them (d2d_nlp_solve_groups_pairs), in -F or, without a field, in the rows' constant
+    wind; plan gains `pairs` and, without a field too, W, cost_fit, feas, status, iters, sweeps, moved."""
     import multi_opt_planner as mop
     import d2d.opty_utils as d2ou
     F = plant_wind(windfield)
@@ -287,14 +304,25 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     ac = ddyn.Aircraft()
     kw = dict(w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v)
     kw2 = {}
+    pairs = mop.scenario_pairs(scen, n_ac)                          # None: the reference's pair (0, 1), the chain as it was
     if F is not None:                                               # the fit was the guess: the collocation problem in -F from t2
         Fp = F.negated()
         Xs = Xs.contiguous().clone()
-        sol = ctx.nlp_solve_groups_wind(dsc, Xs, float(dt2), n_ac, Fp, t2)
+        if pairs is None:
+            sol = ctx.nlp_solve_groups_wind(dsc, Xs, float(dt2), n_ac, Fp, t2)
+        else:
+            sol = ctx.nlp_solve_groups_pairs(dsc, Xs, float(dt2), n_ac, Fp, t2)
         pl.update(cost_fit=cost, cost=sol['cost'], Xs=Xs, W=Xs, feas=sol['feas'], status=sol['status'], iters=sol['iters'],
                   sweeps=sol['sweeps'], moved=sol['moved'], t_start=t2, field=Fp)
         kw['wind'] = F
         kw2 = dict(t_start=t2d)
+    elif pairs is not None:                                         # a cost with its own pairs: the collocation problem decides here too
+        Xs = Xs.contiguous().clone()
+        sol = ctx.nlp_solve_groups_pairs(dsc, Xs, float(dt2), n_ac)
+        pl.update(cost_fit=cost, cost=sol['cost'], Xs=Xs, W=Xs, feas=sol['feas'], status=sol['status'], iters=sol['iters'],
+                  sweeps=sol['sweeps'], moved=sol['moved'])
+    if pairs is not None:
+        pl['pairs'] = pairs
     x_ref2 = Xs[:, 0, :].t().contiguous(); y_ref2 = Xs[:, 1, :].t().contiguous()     # dev [K][N]
     ph2 = ctx.track_run(x_ref2, y_ref2, Xs1, float(dt2), record=record2, **kw, **kw2)
     out = dict(phase1=ph1, plan=pl, phase2=ph2, phase3=[])

@@ -11,6 +11,16 @@ import single_opt_planner as sop
 seed = None
 
 
+def scenario_pairs(scen, n):
+    """The aircraft pairs the scenario's cost keeps apart when it asks for anything but the reference's pair (0, 1)
+    (CostCollision(pairs=) / CostComposit(col_pairs=)) -- the rows then carry the partner sets and the collocation backend solves
+    them with d2d_nlp_solve_groups_pairs; None: the default pair, today's rows and entry points.  ValueError for malformed pairs."""
+    low = sop.lower_cost(scen.cost)
+    if np.isnan(low[5]) or n < 2:
+        return None
+    return sop.collision_pairs_of(low, n)
+
+
 def scenario_rows(scen, p0s, p1s, N, duration, obj_scale, wind):
     """d2dhip scenario rows (n_ac, SCEN_STRIDE) of one multi-aircraft scenario, its fit plan and whether the aircraft
     are coupled by collision rows -- the lowering shared by Planner._solve and full_sim's on-device phase chain."""
@@ -19,6 +29,7 @@ def scenario_rows(scen, p0s, p1s, N, duration, obj_scale, wind):
     coupled = not np.isnan(low[5]) and n >= 2
     if coupled and n > 8:
         raise NotImplementedError('collision coupling is built for groups of at most 8 aircraft')
+    pairs = sop.collision_pairs_of(low, n) if coupled else None
     s = obj_scale / N / n                        # src/d2d/multiopty_utils.py:62
     plan = sop.get_plan(N, duration, s, low[1], low[2])
     rows = np.stack([sop.scen_row(p0, p1, scen.vref, low if i == 0 else low[:4] + ((),) + low[5:], s,
@@ -28,12 +39,24 @@ def scenario_rows(scen, p0s, p1s, N, duration, obj_scale, wind):
     # (static obstacles act on aircraft 0 only, src/d2d/multiopty_utils.py:74)
     if low[4]:
         rows[:, d2dhip.SC_KOBS] *= n             # obstacle scale has no 1/n_ac (:91)
-    if coupled:
+    if coupled and pairs is None:
         # CostCollision acts on the pair (aircraft 0, aircraft 1) only (src/d2d/multiopty_utils.py:124-125);
         # scale obj_scale/N without 1/n_ac (:132)
         rows[:, d2dhip.SC_KCOL], rows[:, d2dhip.SC_RCOL], rows[:, d2dhip.SC_SCOL] = low[5], low[6], obj_scale / N
         rows[0, d2dhip.SC_PMASK], rows[1, d2dhip.SC_PMASK] = 0b10, 0b01
+    elif coupled:
+        # CostCollision(pairs=): every aircraft with a partner carries the collision columns and its symmetric partner set
+        for a, m in enumerate(d2mou.pair_masks(pairs, n)):
+            if m:
+                rows[a, d2dhip.SC_KCOL], rows[a, d2dhip.SC_RCOL], rows[a, d2dhip.SC_SCOL] = low[5], low[6], obj_scale / N
+                rows[a, d2dhip.SC_PMASK] = m
+        coupled = len(pairs) > 0
     return rows, plan, coupled
+
+
+def min_separation(X, Y, pairs):
+    """{(i, j): smallest node-wise distance of the pair}, X, Y (n, N) node positions."""
+    return {(i, j): float(np.hypot(X[i] - X[j], Y[i] - Y[j]).min()) for i, j in pairs}
 
 
 class Planner:
@@ -137,6 +160,8 @@ class Planner:
         vphi, vv = sop.bound_violation(Xs[:, 3], Xs[:, 4], self.scen.phi_constraint, self.scen.v_constraint)
         info = {'status': st.tolist(), 'iters': iters.cpu().numpy().tolist(), 'obj_val': float(cost.sum().item()),
                 'box_violation': viol, 'phi_violation': vphi, 'v_violation': vv}
+        if coupled:
+            info['min_separation'] = min_separation(Xs[:, 0], Xs[:, 1], scenario_pairs(self.scen, n) or [(0, 1)])
         return sol, info
 
     def run(self, initial_guess=None, tol=1e-8, max_iter=500):

@@ -25,7 +25,9 @@ The whole Problem is ONE launch (d2d_nlp_solve_groups): wavefront a of a workgro
 through the objective only -- CostCollision acts on the pair of aircraft 0 and 1, src/d2d/multiopty_utils.py:124-125 -- so the
 pair alternates on the device (each turn a full solve against the partner's frozen node positions) until neither moves by more than
 options['sweep_tol'] (1e-7 m) or options['max_sweeps'] (12): a fixed point of that alternation is a KKT point of the joint NLP.  A
-pair that has not settled is reported 'max_iter'."""
+pair that has not settled is reported 'max_iter'.  A cost that selects its own pairs (CostCollision(pairs=) / CostComposit(col_pairs=))
+is lowered to a partner set per aircraft and solved by d2d_nlp_solve_groups_pairs: every aircraft with a partner takes turns against
+all of them.  info['min_separation']: per coupled pair, the smallest node-wise distance of the returned plan."""
 import numpy as np
 
 import d2dhip
@@ -191,8 +193,20 @@ class Problem:
             rows.append(r)
         rows = np.stack(rows)
         coupled = multi and n >= 2 and not np.isnan(low[5]) and low[5] > 0
-        if coupled:
+        self._pairs = sop.collision_pairs_of(low, n) if coupled else None      # None: the reference's pair (0, 1)
+        if coupled and self._pairs is None:
             rows[:2, d2dhip.SC_KCOL], rows[:2, d2dhip.SC_RCOL], rows[:2, d2dhip.SC_SCOL] = low[5], low[6], self.planner.obj_scale / N
+        elif coupled:
+            # CostCollision(pairs=): every aircraft with a partner carries the collision columns and its symmetric partner set
+            # (d2d_nlp_solve_groups_pairs)
+            if n > 8:
+                raise NotImplementedError('collision coupling is built for groups of at most 8 aircraft')
+            import d2d.multiopty_utils as d2mou
+            for a, m in enumerate(d2mou.pair_masks(self._pairs, n)):
+                if m:
+                    rows[a, d2dhip.SC_KCOL], rows[a, d2dhip.SC_RCOL], rows[a, d2dhip.SC_SCOL] = low[5], low[6], self.planner.obj_scale / N
+                    rows[a, d2dhip.SC_PMASK] = m
+            coupled = len(self._pairs) > 0
         # (low[8]: CostBank(use_mean=False) travels as D2D_SC_BANKMAX -- obj_scale kbank max phi^2 with the maximiser frozen for the
         # length of a Newton step, csrc/nlp_kernels.hip nlp_assemble / oracle/nlp.py)
         return rows, coupled
@@ -236,8 +250,10 @@ class Problem:
             out = ctx.nlp_solve_wind(dsc, dW, self.time_step, self.field, t_start=self.t_start, bounds=bnd, **kw)
             sweeps, moved = 0, 0.0
         else:
-            out = ctx.nlp_solve_groups(dsc, dW, self.time_step, n, max_sweeps=int(self.options.get('max_sweeps', 12)),
-                                       tol=float(self.options.get('sweep_tol', 1e-7)), bounds=bnd, **kw)
+            # (a cost that selects its own pairs: the same alternation over every aircraft with a partner)
+            solve = ctx.nlp_solve_groups if self._pairs is None else ctx.nlp_solve_groups_pairs
+            out = solve(dsc, dW, self.time_step, n, max_sweeps=int(self.options.get('max_sweeps', 12)),
+                        tol=float(self.options.get('sweep_tol', 1e-7)), bounds=bnd, **kw)
             sweeps = int(out['sweeps'][0].item())
             moved = float(out['moved'][0].item())
         ctx.sync()
@@ -251,6 +267,9 @@ class Problem:
                 'iters': out['iters'].cpu().numpy().tolist(), 'sweeps': sweeps, 'moved': moved,
                 'obj_val': float(self.obj(sol)), 'status_msg': 'converged' if (st == 1).all() else 'max_iter',
                 'box_violation': 0.0, 'phi_violation': 0.0, 'v_violation': 0.0}       # hard bounds: an interior-point iterate never leaves its box
+        if coupled:                               # per coupled pair: the smallest node-wise distance of the returned plan
+            info['min_separation'] = {(i, j): float(np.hypot(Wh[i, 0] - Wh[j, 0], Wh[i, 1] - Wh[j, 1]).min())
+                                      for i, j in (self._pairs if self._pairs is not None else [(0, 1)])}
         return sol, info
 
     # ---- host objective ------------------------------------------------------------------------------------------------------

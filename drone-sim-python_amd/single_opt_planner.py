@@ -68,7 +68,9 @@ def fit_cost(cost):
 
 def lower_cost(cost):
     """Recognise the reference's cost plug-ins structurally -> (vsp, kv, kphi, kobs, obstacles, kcol, rcol,
-    okind, bankmax): okind = bit mask of the obstacles of CostObstacle kind 0, bankmax = CostBank max mode.
+    okind, bankmax[, pairs]): okind = bit mask of the obstacles of CostObstacle kind 0, bankmax = CostBank max mode.
+    A collision term that selects anything but the reference's pair (0, 1) appends its `pairs` argument as a tenth entry
+    (collision_pairs_of resolves it); the default keeps the nine entries.
     Anything else has no kernel and raises (there is no CPU solver to fall back to)."""
     nan = float('nan')
     if isinstance(cost, d2ou.CostAirVel):
@@ -85,7 +87,7 @@ def lower_cost(cost):
         obss = tuple((o.c[0], o.c[1], o.r) for o in cost.obss)
         return 0., 0., 0., 1., obss, nan, 0., sum(1 << i for i, o in enumerate(cost.obss) if o.kind == 0), 0
     if isinstance(cost, d2mou.CostCollision):                              # the collision term on its own
-        return 0., 0., 0., 0., (), 1., cost.r, 0, 0
+        return (0., 0., 0., 0., (), 1., cost.r, 0, 0) + (() if cost.pairs is None else (cost.pairs,))
     if isinstance(cost, d2ou.CostComposit):
         obss = [(o.c[0], o.c[1], o.r) for o in cost.cobs.obss] if hasattr(cost, 'cobs') else []
         okind = sum(1 << i for i, o in enumerate(cost.cobs.obss) if o.kind == 0) if obss else 0
@@ -98,8 +100,17 @@ def lower_cost(cost):
             obss = tuple((o[0], o[1], o[2]) for o in cost.obss)
             kobs = cost.kobs
             okind = ((1 << len(obss)) - 1) if cost.obs_kind == 0 else 0
-        return cost.vsp, cost.kvel, cost.kbank, kobs, obss, cost.kcol, cost.rcol, okind, 0
+        return (cost.vsp, cost.kvel, cost.kbank, kobs, obss, cost.kcol, cost.rcol, okind, 0) + (
+            () if getattr(cost, 'col_pairs', None) is None else (cost.col_pairs,))
     raise NotImplementedError(f'cost plug-in {type(cost).__name__} has no HIP lowering')
+
+
+def collision_pairs_of(lowered, n):
+    """The pairs a lowered cost couples among n aircraft, or None for the reference's pair (0, 1) (lower_cost's nine entries).
+    ValueError for malformed pairs (d2d.multiopty_utils.collision_pairs)."""
+    if len(lowered) <= 9:
+        return None
+    return d2mou.collision_pairs(lowered[9], n)
 
 
 def scen_row(p0, p1, vref, lowered, s, wind, phi_c, v_c, go_left=-1., x_c=None, y_c=None):

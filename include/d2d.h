@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 113
+#define D2D_VERSION 114
 
 /* error codes */
 #define D2D_OK 0
@@ -739,6 +739,28 @@ int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen,
 int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
                               double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
                               int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start);
+
+/* d2d_nlp_solve_groups / d2d_nlp_solve_groups_wind with collision avoidance on ANY set of aircraft pairs.  D2D_SC_PMASK of aircraft
+ * a's row is its partner set (bit j: aircraft j of the same scenario); an aircraft with a non-empty set carries D2D_SC_KCOL / RCOL /
+ * SCOL (KCOL = 0: it takes its turns without the term).  Block Gauss-Seidel as before: sweep 0 solves every aircraft uncoupled and
+ * concurrently; in sweeps 1.. the aircraft with a non-empty set take turns in index order, each turn a full solve from the
+ * aircraft's current nodes against the frozen node positions of ALL its partners (terms summed in ascending partner index); moved is
+ * the largest move of any turn of the sweep, and the loop ends at moved <= tol or max_sweeps.  An unsettled scenario reports
+ * D2D_ST_MAXITER on the aircraft that took turns.  A fixed point is a KKT point of the joint problem: the coupling is in the
+ * objective only.  With the masks 0b10, 0b01 of the pair (0, 1) the results are those of d2d_nlp_solve_groups[_wind] bit for bit.
+ * f and t_start both NULL: the rows' constant wind (d2d_nlp_solve_groups); both set: the field, node i of scenario r at
+ * t_start[r] + i h (d2d_nlp_solve_groups_wind, same validation); one of them NULL: D2D_EINVAL.
+ * Masks are checked on the device, per scenario, before its first solve (no host round trip: the rows may have been finished on
+ * the device): an entry that is not an integer in [0, 2^n_ac), a self bit, or a bit j that aircraft j's mask does not return
+ * (the term of a pair belongs to both aircraft's objectives or to neither) refuses ALL aircraft of that scenario at once --
+ * D2D_ST_NONFINITE, cost = feas = NaN, iters = 0, sweeps = 0, moved = 0, W untouched -- like an unusable row; the other scenarios
+ * of the launch are solved.  No mask indexes outside its scenario's W.
+ * Arguments and workspace size as d2d_nlp_solve_groups_wind; the last 2 * N doubles per scenario of work hold the x and y planes
+ * the aircraft of the last turn had before it.  tests/nlp_groups_pairs_ref.py is the CPU statement.  Asynchronous on the context's
+ * stream.  (version 114) */
+int d2d_nlp_solve_groups_pairs(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                               double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                               int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,12 @@ python tools/bench_nlp_wind.py groups [R]  the multi-aircraft problem (d2d_nlp_s
     the trap_4-like scenarios of tests/nlp_groups_wind_ref.py (4 aircraft, 61 nodes, the collision pair active) in the steady shear
     and the unsteady gust, against d2d_nlp_solve_groups on the same scenarios in the constant wind of the field's mean; then the
     wall time of the three-formation mission of tests/test_gpu_mission_wind.py (one pass of phase 3) with and without its field.  Median of 5 timed
-    launches after a warm-up, HIP events, one process."""
+    launches after a warm-up, HIP events, one process.
+python tools/bench_nlp_wind.py pairs [R]   collision avoidance on every pair (d2d_nlp_solve_groups_pairs): R (default 1024) perturbed copies
+    of four-aircraft scenarios in constant wind, (i) the default pair through d2d_nlp_solve_groups, three repeats of the whole
+    measurement (their spread is the noise band), (ii) the same rows with the masks of the pair (0, 1) through the new entry point,
+    (iii) all six pairs; on the side-by-side layouts of tests/nlp_groups_wind_ref.py and on the crossing layouts of
+    tests/nlp_groups_pairs_ref.py.  Median of 5 timed launches after a warm-up, HIP events, one process."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 'tests')):
@@ -74,7 +79,62 @@ def groups_leg(R):
                           'seconds_median': float(np.median(times[1:])), 'seconds_min': min(times[1:]), 'seconds_max': max(times[1:])}), flush=True)
 
 
+def pairs_leg(R):
+    import torch, d2dhip
+    import d2dhip as D
+    import nlp_groups_wind_ref as G
+    import nlp_groups_pairs_ref as P
+    ctx = d2dhip.Context(0)
+    rng = np.random.default_rng(7)
+    shift = np.repeat(rng.uniform(-3.0, 3.0, (R, 2)), G.N_AC, 0)              # a scenario moves as a whole: the gaps stay
+
+    def batch(base):
+        rows = np.concatenate([base[r % len(base)].copy() for r in range(R)])
+        rows[:, [D.SC_X0, D.SC_X1]] += shift[:, :1]; rows[:, [D.SC_Y0, D.SC_Y1]] += shift[:, 1:]
+        return rows
+
+    def timed(label, layout, rows, W0, pairs_entry, max_sweeps):
+        dsc = ctx.dev(rows)
+        times = []
+        for rep in range(6):                                 # the first launch is the warm-up
+            W = ctx.dev(np.ascontiguousarray(W0))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            out = (ctx.nlp_solve_groups_pairs if pairs_entry else ctx.nlp_solve_groups)(dsc, W, G.H, G.N_AC, max_sweeps=max_sweeps)
+            e1.record(); torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) * 1e-3)
+        med = float(np.median(times[1:]))
+        st = out['status'].cpu().numpy(); it = out['iters'].cpu().numpy(); sw = out['sweeps'].cpu().numpy()
+        print(json.dumps({'leg': 'pairs', 'what': label, 'layout': layout, 'R': R, 'n_ac': G.N_AC, 'nodes': G.N_NODES, 'max_sweeps': max_sweeps,
+                          'seconds_median': med, 'seconds_min': min(times[1:]), 'seconds_max': max(times[1:]), 'scenarios_per_s': R / med,
+                          'aircraft_problems_per_s': R * G.N_AC / med, 'converged_frac': float((st == 1).mean()),
+                          'mean_newton_steps': float(it.mean()), 'mean_sweeps': float(sw.mean()), 'min_sweeps': int(sw.min()),
+                          'max_sweeps_seen': int(sw.max())}), flush=True)
+        return med
+
+    wind = (3.0, 0.0)                                        # the planner's constant wind: 9 m/s over the ground at 12 m/s of airspeed
+    for layout, p01, pall, ms in (('side_by_side', [r.copy() for r in G.group_scenarios()], None, 12),
+                                  ('crossing', P.pair_scenarios([(0, 1)]), P.pair_scenarios('all'), P.MAX_SWEEPS)):
+        for r in p01:
+            r[:, D.SC_WX], r[:, D.SC_WY] = -wind[0], -wind[1]
+            r[0, D.SC_PMASK], r[1, D.SC_PMASK] = 0b10, 0b01          # (d2d_nlp_solve_groups does not read the column)
+        if pall is None:
+            pall = [P.pair_rows([tuple(q[D.SC_X0:D.SC_X0 + 3]) for q in r], [tuple(q[D.SC_X1:D.SC_X1 + 3]) for q in r], P.all_pairs(G.N_AC)) for r in p01]
+        for r in pall:
+            r[:, D.SC_WX], r[:, D.SC_WY] = -wind[0], -wind[1]
+        rows01, rows_all = batch(p01), batch(pall)
+        W0 = np.stack([w.T for w in G.guesses(rows01)])
+        base = [timed('(i) default pair, d2d_nlp_solve_groups, repeat %d' % k, layout, rows01, W0, False, ms) for k in range(3)]
+        same = timed('(ii) the same rows, d2d_nlp_solve_groups_pairs', layout, rows01, W0, True, ms)
+        allp = timed('(iii) all six pairs, d2d_nlp_solve_groups_pairs', layout, rows_all, W0, True, ms)
+        print(json.dumps({'leg': 'pairs', 'layout': layout, 'noise_band_of_i': (max(base) - min(base)) / float(np.median(base)),
+                          'ii_over_i': same / float(np.median(base)), 'iii_over_i': allp / float(np.median(base))}), flush=True)
+    ctx.close()
+
+
 def main():
+    if sys.argv[1:2] == ['pairs']:
+        return pairs_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024)
     if sys.argv[1:2] == ['groups']:
         return groups_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024)
     import torch, d2dhip
