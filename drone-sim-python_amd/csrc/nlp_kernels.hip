@@ -1332,6 +1332,17 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
 #ifndef NLP_WAVES_PER_SIMD
 #define NLP_WAVES_PER_SIMD 2       // (A/B: -DNLP_WAVES_PER_SIMD=1 gives the assembly 512 registers and no scratch)
 #endif
+#ifndef NLP_WIND_WAVES_PER_SIMD
+#define NLP_WIND_WAVES_PER_SIMD 2
+#endif
+
+// the next ticket of the hand-out queue: lane 0 draws it, the wavefront reads it
+__device__ __forceinline__ int nlp_next_ticket(int32_t *queue, int lane) {
+  int tn = 0;
+  if (lane == 0) tn = (int)gridDim.x + atomicAdd(queue, 1);
+  return __builtin_amdgcn_readfirstlane(tn);
+}
+
 // One wavefront per problem.  Node-parallel phases (merit, assembly, step statistics, update) run with lane = node; the two
 // block recursions are serial in the nodes and run wave-uniform.  Control flow is uniform: no lane waits for another problem.
 // Two waves per SIMD: the assembly spills for it (640-708 B / lane, once per Newton step; the serial recursions are separate functions
@@ -1342,6 +1353,10 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
 // a device counter, and the WORKSPACE BELONGS TO THE SLOT (work + blockIdx.x * WS_TOTAL * N), not to the problem: nothing in it
 // outlives a solve, and with one workspace per problem every solve streamed its 100+ kB through cold lines while the ones it
 // followed were written back -- slots keep the chip's working set at (resident waves) x (workspace) whatever the batch.
+// The hand-out loop stands here and in nlp_solve_wind_kernel, not in one `template <bool WIND>` body: built through such a
+// __forceinline__ body (tried with and without __restrict__ on its parameters, and with the ticket in the for-increment) this
+// kernel kept 255 VGPRs and 672 B / lane of scratch but its spills moved (SGPR 206 -> 204 .. 216, VGPR 122 -> 124) and 4300 - 5600 of
+// its 12 223 lines of ISA with them.  The benchmark times this kernel, so it keeps its code; only the ticket is shared.
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WAVES_PER_SIMD, NLP_WAVES_PER_SIMD)))
 nlp_solve_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, const double *partner, double *W,
                  double *work, double *mult, double *__restrict__ cost_out, double *__restrict__ feas_out,
@@ -1353,9 +1368,7 @@ nlp_solve_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restric
   for (int t = blockIdx.x; t < B;) {
     const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
     if ((unsigned)b >= (unsigned)B) {        // (an entry that is no problem index is skipped, not dereferenced)
-      int tn = 0;
-      if (lane == 0) tn = (int)gridDim.x + atomicAdd(queue, 1);
-      t = __builtin_amdgcn_readfirstlane(tn);
+      t = nlp_next_ticket(queue, lane);
       continue;
     }
     NlpOut out;
@@ -1369,18 +1382,13 @@ nlp_solve_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restric
       if (status_out) status_out[b] = out.status;
     }
     nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
-    int tn = 0;
-    if (lane == 0) tn = (int)gridDim.x + atomicAdd(queue, 1);
-    t = __builtin_amdgcn_readfirstlane(tn);
+    t = nlp_next_ticket(queue, lane);
   }
 }
 
 // d2d_nlp_solve_wind: nlp_solve_kernel's persistent hand-out around the WIND instantiation of the solve (no partner, no stamps).
 // The field is shared by the batch and travels as a kernel argument (scalar registers); its control points are a small table that
 // every wavefront reads and that stays in L2.
-#ifndef NLP_WIND_WAVES_PER_SIMD
-#define NLP_WIND_WAVES_PER_SIMD 2
-#endif
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
 nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
                       double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
@@ -1392,9 +1400,7 @@ nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__re
   for (int t = blockIdx.x; t < B;) {
     const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
     if ((unsigned)b >= (unsigned)B) {        // (an entry that is no problem index is skipped, not dereferenced)
-      int tn = 0;
-      if (lane == 0) tn = (int)gridDim.x + atomicAdd(queue, 1);
-      t = __builtin_amdgcn_readfirstlane(tn);
+      t = nlp_next_ticket(queue, lane);
       continue;
     }
     NlpOut out;
@@ -1408,188 +1414,78 @@ nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__re
       if (status_out) status_out[b] = out.status;
     }
     nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
-    int tn = 0;
-    if (lane == 0) tn = (int)gridDim.x + atomicAdd(queue, 1);
-    t = __builtin_amdgcn_readfirstlane(tn);
+    t = nlp_next_ticket(queue, lane);
   }
+}
+
+// A scenario of the group loop is refused: all its aircraft at once, before the workgroup's first barrier (the caller returns).
+__device__ __forceinline__ void nlp_groups_refuse(int b, int r, int wave, int lane, double *cost_out, double *feas_out,
+                                                  int32_t *iters_out, int32_t *status_out, int32_t *sweeps_out, double *moved_out) {
+  if (lane == 0) {
+    cost_out[b] = feas_out[b] = __builtin_nan("");
+    if (iters_out) iters_out[b] = 0;
+    if (status_out) status_out[b] = D2D_ST_NONFINITE;
+    if (wave == 0) {
+      if (sweeps_out) sweeps_out[r] = 0;
+      if (moved_out) moved_out[r] = 0.0;
+    }
+  }
+}
+
+// The group loop's report: per aircraft, and per scenario by its first wavefront.
+__device__ __forceinline__ void nlp_groups_report(int b, int r, int wave, int lane, const NlpOut &out, int iters_total, int sweep, double moved,
+                                                  double *cost_out, double *feas_out, int32_t *iters_out, int32_t *status_out,
+                                                  int32_t *sweeps_out, double *moved_out) {
+  if (lane == 0) {
+    cost_out[b] = out.cost;
+    feas_out[b] = out.feas;
+    if (iters_out) iters_out[b] = iters_total;
+    if (status_out) status_out[b] = out.status;
+    if (wave == 0) {
+      if (sweeps_out) sweeps_out[r] = sweep;
+      if (moved_out) moved_out[r] = moved;
+    }
+  }
+}
+
+// does aircraft a take turns in sweeps 1..?  Fixed pair: aircraft 0 and 1; PAIRS: the aircraft with a non-empty partner set (cset)
+template <bool PAIRS>
+__device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
+  if constexpr (PAIRS) return ((cset >> a) & 1u) != 0u;
+  else return a < 2;
 }
 
 // The reference's multi-aircraft Problem (src/multi_opt_planner.py:69-78,86) in ONE launch: a workgroup takes a scenario, wavefront
 // a its aircraft a.  The aircraft are coupled through the objective only -- CostCollision on the pair (0, 1), src/d2d/
 // multiopty_utils.py:120-153; every constraint is per aircraft -- so a fixed point of block Gauss-Seidel over the aircraft (each
-// block = the full collocation solve of one aircraft against its partner's frozen node positions) is a KKT point of the joint
-// problem.  Sweep 0 solves every aircraft uncoupled, concurrently; then aircraft 0 and 1 take turns (workgroup barriers between
-// the turns; the partner's positions are read from its W in global memory, which its wave does not touch meanwhile) until neither
-// moved by more than tol in a sweep, or max_sweeps.  No host round trips.  prev [R][2][N] scratch.
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_WAVES_PER_SIMD, NLP_WAVES_PER_SIMD)))
-nlp_groups_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
-                  double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
-                  int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
-                  double *__restrict__ moved_out) {
-  __shared__ double moved_s[2];
-  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
-  const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int b = r * n_ac + wave;
-  const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE;
-  double *Wb = W + (size_t)b * NLP_NV * N;
-  double *wsb = work + (size_t)b * WS_TOTAL * N;
-  double *mb = mult ? mult + (size_t)b * 3 * N : nullptr;
-  const bool coupled = n_ac >= 2 && scen[(size_t)(r * n_ac) * D2D_SCEN_STRIDE + D2D_SC_KCOL] > 0.0;       // wave-uniform for the whole group
-  NlpOut out;
-  int iters_total = 0;
-  double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
-  const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
-  nlp_solve_one(N, h, o, sc, nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd);
-  iters_total += out.iters;
-  if (threadIdx.x < 2) moved_s[threadIdx.x] = 0.0;
-  __threadfence_block();
-  __syncthreads();
-  int sweep = 0;
-  double moved = 0.0;
-  if (coupled) {
-    double *pv = prev + (size_t)r * 2 * N;
-    for (sweep = 1; sweep <= max_sweeps; ++sweep) {
-      for (int turn = 0; turn < 2; ++turn) {
-        if (wave == turn) {
-          const double *pw = W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;      // the partner's x and y planes
-          for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
-          nlp_solve_one(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd);
-          iters_total += out.iters;
-          double m = 0.0;
-          for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
-          m = wave_max(m);
-          if (lane == 0) moved_s[turn] = m;
-        }
-        __threadfence_block();
-        __syncthreads();
-      }
-      moved = fmax(moved_s[0], moved_s[1]);
-      __syncthreads();
-      if (moved <= tol) break;
-    }
-    if (sweep > max_sweeps) sweep = max_sweeps;
-    // not settled after the last sweep: the pair is reported as such (the inner solves each converged, the alternation did not)
-    if (moved > tol && wave < 2 && out.status == D2D_ST_CONVERGED) out.status = D2D_ST_MAXITER;
-  }
-  if (lane == 0) {
-    cost_out[b] = out.cost;
-    feas_out[b] = out.feas;
-    if (iters_out) iters_out[b] = iters_total;
-    if (status_out) status_out[b] = out.status;
-    if (wave == 0) {
-      if (sweeps_out) sweeps_out[r] = sweep;
-      if (moved_out) moved_out[r] = moved;
-    }
-  }
-}
-
-// d2d_nlp_solve_groups_wind: nlp_groups_kernel in a field (a copy, as the tracking loops in a field are: the constant-wind kernel
-// keeps its exact code; change the two together).  Every solve is the WIND instantiation -- the first one with a partner: the
-// collision terms live in the objective and do not meet the field's terms, which live in the equalities.  The field is shared by the
-// launch and travels as a kernel argument (scalar registers); the start time is the SCENARIO's (t_start [R], device memory: the
-// mission chain computes it on the device), wave-uniform.  A scenario whose start time is not finite is refused before its first
-// solve, all its aircraft at once (the whole workgroup leaves: no barrier is left waiting).
+// block = the full collocation solve of one aircraft against its partners' frozen node positions) is a KKT point of the joint
+// problem.  Sweep 0 solves every aircraft uncoupled, concurrently; then the coupled aircraft take turns in index order (workgroup
+// barriers between the turns; a partner's positions are read from its W in global memory, L2-resident, which its wave does not touch
+// meanwhile) until none moved by more than tol in a sweep, or max_sweeps.  No host round trips.  prev [R][2][N] scratch.
+// One body for the four kernels below, switched at compile time:
+// WIND: every solve is the WIND instantiation -- the collision terms live in the objective and do not meet the field's terms, which
+//   live in the equalities.  The field is shared by the launch and travels as a kernel argument (scalar registers); the start time is
+//   the SCENARIO's (t_start [R], device memory: the mission chain computes it on the device), wave-uniform.  A scenario whose start
+//   time is not finite is refused before its first solve.
+// PAIRS: any set of coupled pairs instead of the pair (0, 1) when the row's KCOL > 0.  D2D_SC_PMASK of aircraft a's row is its
+//   partner set, bit j = aircraft j of the same scenario; each turn solves against ALL partners, which nlp_exp_terms reads through a
+//   rolled loop over the set bits of the mask in a scalar register.  With the masks of the pair (0, 1) every solve, sum and barrier is
+//   that of the fixed pair (tests/test_gpu_collision_pairs.py: equal bit for bit).  The masks of a scenario are checked before its
+//   first solve, by every wavefront alike (scalar loads): an entry that is no integer in [0, 2^n_ac), a self bit or a bit j whose
+//   aircraft j does not name a back -- the term of a pair belongs to both objectives or to none -- refuses the whole scenario
+//   (D2D_ST_NONFINITE, cost = feas = NaN, sweeps = 0, W untouched), like a non-finite start time: no mask ever indexes outside the
+//   scenario's W.
+// The pointer parameters of the body and of its two helpers carry no __restrict__ (the kernels' do): with it the fixed-pair kernel
+// went from 256 VGPRs / 624 B of scratch to 255 / 608 and the field kernel from 752 B to 784.
 // Registers: 512 threads per workgroup are 8 wavefronts on 4 SIMDs, two per SIMD, so a wavefront gets at most 256 of the SIMD's 512
 // registers whatever amdgpu_waves_per_eu says -- the workgroup size binds, and (2, 2) states what the hardware does.
-#ifndef NLP_GROUPS_WIND_WAVES_PER_SIMD
-#define NLP_GROUPS_WIND_WAVES_PER_SIMD 2
-#endif
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
-nlp_groups_wind_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
-                       double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
-                       int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
-                       double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
-  __shared__ double moved_s[2];
-  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
-  const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int b = r * n_ac + wave;
-  const double t0 = nlp_first_lane(t_start[r]);
-  if (!(fabs(t0) <= 1.79e308)) {             // (uniform over the workgroup: before the first barrier)
-    if (lane == 0) {
-      cost_out[b] = feas_out[b] = __builtin_nan("");
-      if (iters_out) iters_out[b] = 0;
-      if (status_out) status_out[b] = D2D_ST_NONFINITE;
-      if (wave == 0) {
-        if (sweeps_out) sweeps_out[r] = 0;
-        if (moved_out) moved_out[r] = 0.0;
-      }
-    }
-    return;
-  }
-  const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE;
-  double *Wb = W + (size_t)b * NLP_NV * N;
-  double *wsb = work + (size_t)b * WS_TOTAL * N;
-  double *mb = mult ? mult + (size_t)b * 3 * N : nullptr;
-  const bool coupled = n_ac >= 2 && scen[(size_t)(r * n_ac) * D2D_SCEN_STRIDE + D2D_SC_KCOL] > 0.0;       // wave-uniform for the whole group
-  NlpOut out;
-  int iters_total = 0;
-  double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
-  const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
-  const NlpModel no_model{nullptr, nullptr, nullptr};
-  nlp_solve_one<false, true>(N, h, o, sc, nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, &wf, t0);
-  iters_total += out.iters;
-  if (threadIdx.x < 2) moved_s[threadIdx.x] = 0.0;
-  __threadfence_block();
-  __syncthreads();
-  int sweep = 0;
-  double moved = 0.0;
-  if (coupled) {
-    double *pv = prev + (size_t)r * 2 * N;
-    for (sweep = 1; sweep <= max_sweeps; ++sweep) {
-      for (int turn = 0; turn < 2; ++turn) {
-        if (wave == turn) {
-          const double *pw = W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;      // the partner's x and y planes
-          for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
-          nlp_solve_one<false, true>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, &wf, t0);
-          iters_total += out.iters;
-          double m = 0.0;
-          for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
-          m = wave_max(m);
-          if (lane == 0) moved_s[turn] = m;
-        }
-        __threadfence_block();
-        __syncthreads();
-      }
-      moved = fmax(moved_s[0], moved_s[1]);
-      __syncthreads();
-      if (moved <= tol) break;
-    }
-    if (sweep > max_sweeps) sweep = max_sweeps;
-    // not settled after the last sweep: the pair is reported as such (the inner solves each converged, the alternation did not)
-    if (moved > tol && wave < 2 && out.status == D2D_ST_CONVERGED) out.status = D2D_ST_MAXITER;
-  }
-  if (lane == 0) {
-    cost_out[b] = out.cost;
-    feas_out[b] = out.feas;
-    if (iters_out) iters_out[b] = iters_total;
-    if (status_out) status_out[b] = out.status;
-    if (wave == 0) {
-      if (sweeps_out) sweeps_out[r] = sweep;
-      if (moved_out) moved_out[r] = moved;
-    }
-  }
-}
-
-// d2d_nlp_solve_groups_pairs: the block Gauss-Seidel of nlp_groups_kernel / nlp_groups_wind_kernel over ANY set of coupled pairs (a
-// copy again: those two keep their exact code; WIND selects the instantiation of the solve -- the rows' constant wind or the field).
-// D2D_SC_PMASK of aircraft a's row is its partner set, bit j = aircraft j of the same scenario.  Sweep 0 solves every aircraft
-// uncoupled, concurrently; in sweeps 1.. the aircraft with a non-empty set take turns in index order (workgroup barriers between
-// the turns), each turn a full solve from the aircraft's current nodes against the frozen (x, y) planes of ALL its partners, which
-// nlp_exp_terms reads from their W in global memory (L2-resident: 2 x N doubles per partner, and no partner's wave writes meanwhile)
-// through a rolled loop over the set bits of the mask in a scalar register.  The coupling is in the objective only, so a fixed point
-// is a KKT point of the joint problem, as for one pair.  With the masks of the pair (0, 1) every solve, sum and barrier is that of
-// nlp_groups_kernel (tests/test_gpu_collision_pairs.py: equal bit for bit).
-// The masks of a scenario are checked before its first solve, by every wavefront alike (scalar loads): an entry that is no integer in
-// [0, 2^n_ac), a self bit or a bit j whose aircraft j does not name a back -- the term of a pair belongs to both objectives or to none
-// -- refuses the whole scenario at once (D2D_ST_NONFINITE, cost = feas = NaN, sweeps = 0, W untouched; the whole workgroup leaves
-// before the first barrier), like a non-finite start time: no mask ever indexes outside the scenario's W.
-template <bool WIND>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
-nlp_groups_pairs_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
-                        double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
-                        int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
-                        double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
-  __shared__ double moved_s[8];
+template <bool WIND, bool PAIRS>
+__device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h, const d2d_nlp_opts &o, int max_sweeps, double tol,
+                                                const double *scen, double *W, double *work, double *mult, double *prev,
+                                                double *cost_out, double *feas_out, int32_t *iters_out,
+                                                int32_t *status_out, int32_t *sweeps_out, double *moved_out,
+                                                const d2d_wind_field *wf, const double *t_start) {
+  __shared__ double moved_s[PAIRS ? 8 : 2];
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int b = r * n_ac + wave;
@@ -1599,60 +1495,59 @@ nlp_groups_pairs_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int ma
     t0 = nlp_first_lane(t_start[r]);
     bad = !(fabs(t0) <= 1.79e308);
   }
-  // the scenario's masks, 8 bits per aircraft; cset: the aircraft that take turns
-  unsigned long long masks = 0ull;
-  unsigned cset = 0u;
-  for (int a = 0; a < n_ac; ++a) {
-    const double pm = scen[(size_t)(r * n_ac + a) * D2D_SCEN_STRIDE + D2D_SC_PMASK];
-    if (!(pm >= 0.0 && pm < (double)(1u << n_ac)) || pm != floor(pm)) { bad = true; continue; }
-    const unsigned m = (unsigned)pm;
-    if ((m >> a) & 1u) bad = true;
-    masks |= (unsigned long long)m << (8 * a);
-    if (m != 0u) cset |= 1u << a;
-  }
-  for (int a = 0; a < n_ac; ++a)
-    for (int j = 0; j < n_ac; ++j)
-      if (((masks >> (8 * a + j)) & 1ull) != ((masks >> (8 * j + a)) & 1ull)) bad = true;
-  bad = __builtin_amdgcn_readfirstlane((int)bad) != 0;
-  if (bad) {                                 // (uniform over the workgroup: before the first barrier)
-    if (lane == 0) {
-      cost_out[b] = feas_out[b] = __builtin_nan("");
-      if (iters_out) iters_out[b] = 0;
-      if (status_out) status_out[b] = D2D_ST_NONFINITE;
-      if (wave == 0) {
-        if (sweeps_out) sweeps_out[r] = 0;
-        if (moved_out) moved_out[r] = 0.0;
-      }
+  unsigned cset = 0u, pmask = 0u;            // PAIRS: the aircraft that take turns; this aircraft's partner set
+  if constexpr (PAIRS) {
+    unsigned long long masks = 0ull;         // the scenario's masks, 8 bits per aircraft
+    for (int a = 0; a < n_ac; ++a) {
+      const double pm = scen[(size_t)(r * n_ac + a) * D2D_SCEN_STRIDE + D2D_SC_PMASK];
+      if (!(pm >= 0.0 && pm < (double)(1u << n_ac)) || pm != floor(pm)) { bad = true; continue; }
+      const unsigned m = (unsigned)pm;
+      if ((m >> a) & 1u) bad = true;
+      masks |= (unsigned long long)m << (8 * a);
+      if (m != 0u) cset |= 1u << a;
     }
+    for (int a = 0; a < n_ac; ++a)
+      for (int j = 0; j < n_ac; ++j)
+        if (((masks >> (8 * a + j)) & 1ull) != ((masks >> (8 * j + a)) & 1ull)) bad = true;
+    bad = __builtin_amdgcn_readfirstlane((int)bad) != 0;
+    cset = (unsigned)__builtin_amdgcn_readfirstlane((int)cset);
+    pmask = (unsigned)__builtin_amdgcn_readfirstlane((int)((masks >> (8 * wave)) & 0xffull));
+  }
+  if (bad) {                                 // (uniform over the workgroup: before the first barrier)
+    nlp_groups_refuse(b, r, wave, lane, cost_out, feas_out, iters_out, status_out, sweeps_out, moved_out);
     return;
   }
-  cset = (unsigned)__builtin_amdgcn_readfirstlane((int)cset);
-  const unsigned pmask = (unsigned)__builtin_amdgcn_readfirstlane((int)((masks >> (8 * wave)) & 0xffull));
   const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE;
   double *Wb = W + (size_t)b * NLP_NV * N;
   double *wsb = work + (size_t)b * WS_TOTAL * N;
   double *mb = mult ? mult + (size_t)b * 3 * N : nullptr;
-  const double *Wr = W + (size_t)r * n_ac * NLP_NV * N;        // the scenario's W: partner j's planes at j * 5 * N
+  const double *Wr = W + (size_t)r * n_ac * NLP_NV * N;        // the scenario's W: aircraft j's planes at j * 5 * N
+  bool coupled;                              // wave-uniform for the whole group
+  if constexpr (PAIRS) coupled = cset != 0u;
+  else coupled = n_ac >= 2 && scen[(size_t)(r * n_ac) * D2D_SCEN_STRIDE + D2D_SC_KCOL] > 0.0;
   NlpOut out;
   int iters_total = 0;
   double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
   const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
   const NlpModel no_model{nullptr, nullptr, nullptr};
-  nlp_solve_one<false, WIND, true>(N, h, o, sc, Wr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, &wf, t0, 0u);
+  nlp_solve_one<false, WIND, PAIRS>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, 0u);
   iters_total += out.iters;
-  if (threadIdx.x < 8) moved_s[threadIdx.x] = 0.0;
+  if (threadIdx.x < (PAIRS ? 8 : 2)) moved_s[threadIdx.x] = 0.0;
   __threadfence_block();
   __syncthreads();
   int sweep = 0;
   double moved = 0.0;
-  if (cset != 0u) {
+  if (coupled) {
     double *pv = prev + (size_t)r * 2 * N;
+    const int n_turns = PAIRS ? n_ac : 2;
     for (sweep = 1; sweep <= max_sweeps; ++sweep) {
-      for (int turn = 0; turn < n_ac; ++turn) {
-        if (!((cset >> turn) & 1u)) continue;
+      for (int turn = 0; turn < n_turns; ++turn) {
+        if (!nlp_takes_turns<PAIRS>(cset, turn)) continue;
         if (wave == turn) {
+          // fixed pair: the partner's x and y planes; PAIRS: the scenario's W and the set
+          const double *pw = PAIRS ? Wr : W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;
           for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
-          nlp_solve_one<false, WIND, true>(N, h, o, sc, Wr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, &wf, t0, pmask);
+          nlp_solve_one<false, WIND, PAIRS>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, pmask);
           iters_total += out.iters;
           double m = 0.0;
           for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
@@ -1662,25 +1557,54 @@ nlp_groups_pairs_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int ma
         __threadfence_block();
         __syncthreads();
       }
-      moved = 0.0;
-      for (int a = 0; a < n_ac; ++a) moved = fmax(moved, moved_s[a]);       // (the entries of aircraft outside cset stay 0)
+      if constexpr (PAIRS) {
+        moved = 0.0;
+        for (int a = 0; a < n_ac; ++a) moved = fmax(moved, moved_s[a]);     // (the entries of aircraft outside cset stay 0)
+      } else {
+        moved = fmax(moved_s[0], moved_s[1]);
+      }
       __syncthreads();
       if (moved <= tol) break;
     }
     if (sweep > max_sweeps) sweep = max_sweeps;
     // not settled after the last sweep: the coupled aircraft are reported as such (the inner solves each converged, the alternation did not)
-    if (moved > tol && ((cset >> wave) & 1u) && out.status == D2D_ST_CONVERGED) out.status = D2D_ST_MAXITER;
+    if (moved > tol && nlp_takes_turns<PAIRS>(cset, wave) && out.status == D2D_ST_CONVERGED) out.status = D2D_ST_MAXITER;
   }
-  if (lane == 0) {
-    cost_out[b] = out.cost;
-    feas_out[b] = out.feas;
-    if (iters_out) iters_out[b] = iters_total;
-    if (status_out) status_out[b] = out.status;
-    if (wave == 0) {
-      if (sweeps_out) sweeps_out[r] = sweep;
-      if (moved_out) moved_out[r] = moved;
-    }
-  }
+  nlp_groups_report(b, r, wave, lane, out, iters_total, sweep, moved, cost_out, feas_out, iters_out, status_out, sweeps_out, moved_out);
+}
+
+#ifndef NLP_GROUPS_WIND_WAVES_PER_SIMD
+#define NLP_GROUPS_WIND_WAVES_PER_SIMD 2
+#endif
+// d2d_nlp_solve_groups: the pair (0, 1), the rows' constant wind
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_WAVES_PER_SIMD, NLP_WAVES_PER_SIMD)))
+nlp_groups_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                  double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                  int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                  double *__restrict__ moved_out) {
+  nlp_groups_body<false, false>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
+                                sweeps_out, moved_out, nullptr, nullptr);
+}
+
+// d2d_nlp_solve_groups_wind: the pair (0, 1) in a field
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
+nlp_groups_wind_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                       double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                       int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                       double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
+  nlp_groups_body<true, false>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
+                               sweeps_out, moved_out, &wf, t_start);
+}
+
+// d2d_nlp_solve_groups_pairs: the pairs of the masks; WIND selects the rows' constant wind or the field
+template <bool WIND>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
+nlp_groups_pairs_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                        double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                        int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                        double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
+  nlp_groups_body<WIND, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
+                              sweeps_out, moved_out, &wf, t_start);
 }
 
 // d2d_nlp_solve_model: the collocation NLP under the quadratic objective model of a cost that only the host can evaluate (a user's
@@ -1710,6 +1634,42 @@ nlp_model_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restric
   }
 }
 
+// opts or the defaults, validated; who: the entry's name for the message
+static int nlp_options(const d2d_nlp_opts *opts, const char *who, d2d_nlp_opts *o) {
+  *o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
+  if (opts) *o = *opts;
+  D2D_REQUIRE(o->inner_max >= 1 && o->outer_max >= 1 && o->rho0 > 0 && o->mub0 > 0 && o->mub_min > 0, "%s: bad options", who);
+  return D2D_OK;
+}
+
+// the persistent launches' grid: one wavefront per wave slot of the chip (d2d_nlp_opts.slots > 0: the caller's count), or per problem
+static int nlp_handout_grid(int B, const d2d_nlp_opts &o, int waves_per_simd) {
+  static int n_cu = 0;
+  if (n_cu == 0) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256; }
+  int slots = n_cu * 4 * waves_per_simd;
+  if (o.slots > 0) slots = o.slots;
+  return B < slots ? B : (slots < 1 ? 1 : slots);
+}
+
+// the group loops' scratch for the positions before a turn: the tail of aircraft 0's workspace is not free, so it lives behind the workspaces
+static double *nlp_groups_prev(double *work, int R, int n_ac, int N) { return work + (size_t)R * n_ac * WS_TOTAL * N; }
+
+// what the three group entries require alike
+static int nlp_groups_check(const d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, int max_sweeps, double tol,
+                            const double *W, const double *work, const double *cost, const double *feas, const char *who) {
+  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "%s: null argument", who);
+  D2D_REQUIRE(R >= 1 && n_ac >= 1 && n_ac <= 8 && N >= 3 && h > 0, "%s: R >= 1, 1 <= n_ac <= 8, N >= 3, h > 0 required (R=%d n_ac=%d N=%d h=%g)", who, R, n_ac, N, h);
+  D2D_REQUIRE(max_sweeps >= 1 && tol >= 0, "%s: max_sweeps >= 1 and tol >= 0 required", who);
+  return D2D_OK;
+}
+
+// a group kernel's launch: a workgroup per scenario, a wavefront and an LDS block per aircraft
+template <typename Kernel, typename... Args>
+static void nlp_groups_launch(Kernel kernel, d2d_ctx *ctx, int R, int n_ac, Args... args) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
+  hipLaunchKernelGGL(kernel, dim3(R), dim3(64 * n_ac), (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double), ctx->stream, R, n_ac, args...);
+}
+
 extern "C" {
 
 int d2d_nlp_workspace_doubles(int N) { return N * WS_TOTAL; }
@@ -1718,9 +1678,8 @@ int d2d_nlp_solve_model(d2d_ctx *ctx, int B, int N, double h, const double *scen
                         double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status) {
   D2D_REQUIRE(ctx && scen && model && model->g && model->H && model->Wc && W && work && cost && feas, "d2d_nlp_solve_model: null argument");
   D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_model: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
-  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
-  if (opts) o = *opts;
-  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_model: bad options");
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_model", &o)) return rc;
   o.order = nullptr;                                       // (one wavefront per problem: no hand-out)
   hipLaunchKernelGGL(nlp_model_kernel, dim3(B), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, *model, W, work,
                      mult, cost, feas, iters, status);
@@ -1732,17 +1691,11 @@ int d2d_nlp_solve(d2d_ctx *ctx, int B, int N, double h, const double *scen, cons
                   const double *partner, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status) {
   D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve: null argument");
   D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
-  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
-  if (opts) o = *opts;
-  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve: bad options");
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve", &o)) return rc;
   unsigned long long *stamps = nullptr;
   if (getenv("D2D_NLP_STAMPS")) D2D_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&stamps), 16 * sizeof(unsigned long long)));
-  // one wavefront per wave slot (d2d_nlp_opts.slots > 0: the caller's count)
-  static int n_cu = 0;
-  if (n_cu == 0) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256; }
-  int slots = n_cu * 4 * NLP_WAVES_PER_SIMD;
-  if (o.slots > 0) slots = o.slots;
-  const int grid = B < slots ? B : (slots < 1 ? 1 : slots);
+  const int grid = nlp_handout_grid(B, o, NLP_WAVES_PER_SIMD);
   int32_t *queue = ctx->counter_dev + 2;
   D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
   hipLaunchKernelGGL(nlp_solve_kernel, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, partner, W, work, mult, cost, feas, iters,
@@ -1767,14 +1720,9 @@ int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen,
   D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_wind: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
   D2D_REQUIRE(fabs(t_start) <= 1.79e308, "d2d_nlp_solve_wind: t_start must be finite");
   if (int rc = check_wind(f, "d2d_nlp_solve_wind")) return rc;
-  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
-  if (opts) o = *opts;
-  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_wind: bad options");
-  static int n_cu = 0;
-  if (n_cu == 0) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256; }
-  int slots = n_cu * 4 * NLP_WIND_WAVES_PER_SIMD;
-  if (o.slots > 0) slots = o.slots;
-  const int grid = B < slots ? B : (slots < 1 ? 1 : slots);
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_wind", &o)) return rc;
+  const int grid = nlp_handout_grid(B, o, NLP_WIND_WAVES_PER_SIMD);
   int32_t *queue = ctx->counter_dev + 2;
   D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
   hipLaunchKernelGGL(nlp_solve_wind_kernel, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work, mult, cost,
@@ -1786,17 +1734,11 @@ int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen,
 int d2d_nlp_solve_groups(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
                          double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
                          int32_t *sweeps, double *moved) {
-  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_groups: null argument");
-  D2D_REQUIRE(R >= 1 && n_ac >= 1 && n_ac <= 8 && N >= 3 && h > 0, "d2d_nlp_solve_groups: R >= 1, 1 <= n_ac <= 8, N >= 3, h > 0 required (R=%d n_ac=%d N=%d h=%g)", R, n_ac, N, h);
-  D2D_REQUIRE(max_sweeps >= 1 && tol >= 0, "d2d_nlp_solve_groups: max_sweeps >= 1 and tol >= 0 required");
-  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
-  if (opts) o = *opts;
-  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_groups: bad options");
-  // scratch for the positions before a turn: the tail of aircraft 0's workspace is not free, so it lives behind the workspaces
-  double *prev = work + (size_t)R * n_ac * WS_TOTAL * N;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
-  hipLaunchKernelGGL(nlp_groups_kernel, dim3(R), dim3(64 * n_ac), (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double), ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev,
-                     cost, feas, iters, status, sweeps, moved);
+  if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups")) return rc;
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_groups", &o)) return rc;
+  nlp_groups_launch(nlp_groups_kernel, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, nlp_groups_prev(work, R, n_ac, N), cost, feas,
+                    iters, status, sweeps, moved);
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }
@@ -1804,18 +1746,13 @@ int d2d_nlp_solve_groups(d2d_ctx *ctx, int R, int n_ac, int N, double h, const d
 int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
                               double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
                               int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start) {
-  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_groups_wind: null argument");
-  D2D_REQUIRE(R >= 1 && n_ac >= 1 && n_ac <= 8 && N >= 3 && h > 0, "d2d_nlp_solve_groups_wind: R >= 1, 1 <= n_ac <= 8, N >= 3, h > 0 required (R=%d n_ac=%d N=%d h=%g)", R, n_ac, N, h);
-  D2D_REQUIRE(max_sweeps >= 1 && tol >= 0, "d2d_nlp_solve_groups_wind: max_sweeps >= 1 and tol >= 0 required");
+  if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_wind")) return rc;
   if (int rc = check_wind(f, "d2d_nlp_solve_groups_wind")) return rc;
   D2D_REQUIRE(t_start, "d2d_nlp_solve_groups_wind: null t_start (a device array [R]: one start time per scenario)");
-  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
-  if (opts) o = *opts;
-  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_groups_wind: bad options");
-  double *prev = work + (size_t)R * n_ac * WS_TOTAL * N;       // (behind the workspaces, as in d2d_nlp_solve_groups)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_wind_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
-  hipLaunchKernelGGL(nlp_groups_wind_kernel, dim3(R), dim3(64 * n_ac), (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double), ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
-                     prev, cost, feas, iters, status, sweeps, moved, *f, t_start);
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_wind", &o)) return rc;
+  nlp_groups_launch(nlp_groups_wind_kernel, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, nlp_groups_prev(work, R, n_ac, N), cost, feas,
+                    iters, status, sweeps, moved, *f, t_start);
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }
@@ -1823,26 +1760,18 @@ int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, co
 int d2d_nlp_solve_groups_pairs(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
                                double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
                                int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start) {
-  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_groups_pairs: null argument");
-  D2D_REQUIRE(R >= 1 && n_ac >= 1 && n_ac <= 8 && N >= 3 && h > 0, "d2d_nlp_solve_groups_pairs: R >= 1, 1 <= n_ac <= 8, N >= 3, h > 0 required (R=%d n_ac=%d N=%d h=%g)", R, n_ac, N, h);
-  D2D_REQUIRE(max_sweeps >= 1 && tol >= 0, "d2d_nlp_solve_groups_pairs: max_sweeps >= 1 and tol >= 0 required");
+  if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_pairs")) return rc;
   D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_groups_pairs: f and t_start go together (both NULL: the rows' constant wind)");
   if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_groups_pairs")) return rc; }
-  d2d_nlp_opts o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
-  if (opts) o = *opts;
-  D2D_REQUIRE(o.inner_max >= 1 && o.outer_max >= 1 && o.rho0 > 0 && o.mub0 > 0 && o.mub_min > 0, "d2d_nlp_solve_groups_pairs: bad options");
-  double *prev = work + (size_t)R * n_ac * WS_TOTAL * N;       // (behind the workspaces, as in d2d_nlp_solve_groups)
-  const size_t lds = (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double);
-  if (f) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_pairs_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
-    hipLaunchKernelGGL(nlp_groups_pairs_kernel<true>, dim3(R), dim3(64 * n_ac), lds, ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
-                       prev, cost, feas, iters, status, sweeps, moved, *f, t_start);
-  } else {
-    const d2d_wind_field none = {};
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nlp_groups_pairs_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
-    hipLaunchKernelGGL(nlp_groups_pairs_kernel<false>, dim3(R), dim3(64 * n_ac), lds, ctx->stream, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
-                       prev, cost, feas, iters, status, sweeps, moved, none, t_start);
-  }
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_pairs", &o)) return rc;
+  double *prev = nlp_groups_prev(work, R, n_ac, N);
+  if (f)
+    nlp_groups_launch(nlp_groups_pairs_kernel<true>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
+                      sweeps, moved, *f, t_start);
+  else
+    nlp_groups_launch(nlp_groups_pairs_kernel<false>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
+                      sweeps, moved, d2d_wind_field{}, t_start);
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }

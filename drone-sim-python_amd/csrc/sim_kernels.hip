@@ -409,14 +409,17 @@ dfff_kernel(d2d_track_params p, const double *__restrict__ X, const double *__re
   }
 }
 
-// (dfff_run_wind_kernel below is a copy of this kernel with the plant in a field: change the two together.)
 // run_simulation of src/05_test_simulation.py:21-34 with the legacy DFFFController (src/d2d/guidance.py:52-91):
 //   U[i-1] = ctl.get(X[i-1], t[i-1]);  X[i] = disc_dyn(X[i-1], U[i-1]) + perts[i];  U[T-1] = ctl.get(X[T-1], t[T-1])
 // Yref [n_rows][6][n] = the trajectory's flat outputs at the sample times (x, y, xd, yd, xdd, ydd).
-__global__ void __launch_bounds__(64)
-dfff_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref, const double *__restrict__ perts,
-                const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist,
-                double *__restrict__ Xr_hist, double *__restrict__ X_final) {
+// FIELD: the plant flies wf, step i from row i - 1 at t_start + (i - 1) dt, and the controller sees the field at (t_i, the position of
+// reference sample i), as DFFFController.get samples it (src/d2d/guidance.py:62-65); else both see the constant p.wx, p.wy.
+template <bool FIELD>
+__device__ __forceinline__ void
+dfff_run_body(const d2d_track_params &p, const GlMesh &mesh, const double *__restrict__ Yref, const double *__restrict__ perts,
+              const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist, double *__restrict__ Xr_hist,
+              double *__restrict__ X_final, const d2d_wind_field *wf = nullptr, double t_start = 0.0, int32_t *__restrict__ iter_max = nullptr) {
+  WindCtx wc = {wf, t_start, 0};
   const long n = p.n;
   long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
   const bool live = d < n;
@@ -430,7 +433,12 @@ dfff_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref
     double Y[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) Y[c] = Yref[(q * 6 + c) * n + d];
-    const DfffOut o = dfff_gain(s, Y, p);
+    d2d_track_params pq = p;
+    if constexpr (FIELD) {
+      const WindVec w = wind_at(*wf, t_start + q * p.dt, Y[0], Y[1]);
+      pq.wx = w.x; pq.wy = w.y;
+    }
+    const DfffOut o = dfff_gain(s, Y, pq);
     if (live) {
       if (U_hist) { U_hist[q * 2 * n + d] = o.U[0]; U_hist[q * 2 * n + n + d] = o.U[1]; }
       if (Xr_hist) {
@@ -439,7 +447,12 @@ dfff_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref
       }
     }
     if (i == p.n_rows) break;                         // the last row only gets its command (:33)
-    s = plant_step(s, o.U[0], o.U[1], p.wx, p.wy, mesh);
+    if constexpr (FIELD) {
+      wc.t = t_start + q * p.dt;
+      s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
+    } else {
+      s = plant_step(s, o.U[0], o.U[1], p.wx, p.wy, mesh);
+    }
     if (perts) {
       const double *pr = perts + (long)i * 5 * n + d;
       s.x += pr[0]; s.y += pr[n]; s.psi += pr[2 * n]; s.phi += pr[3 * n]; s.v += pr[4 * n];
@@ -452,6 +465,16 @@ dfff_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref
   if (live && X_final) {
     X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
   }
+  if constexpr (FIELD) {
+    if (iter_max) atomicMax(iter_max, wc.iters);
+  }
+}
+
+__global__ void __launch_bounds__(64)
+dfff_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref, const double *__restrict__ perts,
+                const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist,
+                double *__restrict__ Xr_hist, double *__restrict__ X_final) {
+  dfff_run_body<false>(p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final);
 }
 
 // numpy.gradient(f, edge_order=2) with unit spacing at row i of a [n_rows][n] plane
@@ -470,21 +493,25 @@ gradient_kernel(int T, int n, double inv_dt, const double *__restrict__ f, doubl
   out[(long)i * n + d] = grad2(f, i, T, n, d) * inv_dt;
 }
 
-// Tracking loop, src/11_full_sim_case1.py:272-290.  track_run_wind_kernel and track_run_wind_at_kernel below are copies of this kernel with the
-// plant in a field: change them together.
-__global__ void __launch_bounds__(64)
-track_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
-                 const double *__restrict__ y_ref, const double *__restrict__ xd,
-                 const double *__restrict__ yd, const double *__restrict__ xdd,
-                 const double *__restrict__ ydd, const double *__restrict__ X0,
-                 double *__restrict__ X_hist, double *__restrict__ U_hist,
-                 double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
-                 double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
-                 double *__restrict__ X_final) {
+// Tracking loop, src/11_full_sim_case1.py:272-290.
+// FIELD: the plant flies wf, step i from row i - 1 at t_start + (i - 1) dt; the controller keeps p.wx, p.wy, the constant of
+// DiffController(w) (src/11_full_sim_case1.py:241-291 hands w to the controller and WindField(w) to the plant separately).
+// T_AT: the start time is the drone's own, t_at [n] (the drones of the mission chain start phase 2 where their own formation ended
+// phase 1), else the scalar t_start; the time of a step is the same expression in both.
+template <bool FIELD, bool T_AT>
+__device__ __forceinline__ void
+track_run_body(const d2d_track_params &p, const GlMesh &mesh, const double *__restrict__ x_ref, const double *__restrict__ y_ref,
+               const double *__restrict__ xd, const double *__restrict__ yd, const double *__restrict__ xdd,
+               const double *__restrict__ ydd, const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist,
+               double *__restrict__ Xr_hist, double *__restrict__ dX_hist, double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
+               double *__restrict__ X_final, const d2d_wind_field *wf = nullptr, double t_start = 0.0,
+               const double *__restrict__ t_at = nullptr, int32_t *__restrict__ iter_max = nullptr) {
   const long n = p.n;
   long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
   const bool live = d < n;
   if (!live) d = n - 1;
+  if constexpr (T_AT) t_start = t_at[d];
+  WindCtx wc = {wf, t_start, 0};
   State5 s = {X0[d], X0[n + d], X0[2 * n + d], X0[3 * n + d], X0[4 * n + d]};
   if (live && X_hist) {
     X_hist[d] = s.x; X_hist[n + d] = s.y; X_hist[2 * n + d] = s.psi; X_hist[3 * n + d] = s.phi; X_hist[4 * n + d] = s.v;
@@ -493,7 +520,12 @@ track_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_r
     const long r = (long)i * n + d;
     double Y[8] = {x_ref[r], y_ref[r], xd[r], yd[r], xdd[r], ydd[r], 0.0, 0.0};   // Yddd = [0,0] (:279)
     const GainOut o = compute_gain(s, Y, p);
-    s = plant_step(s, o.U[0], o.U[1], p.wx, p.wy, mesh);
+    if constexpr (FIELD) {
+      wc.t = t_start + (i - 1) * p.dt;
+      s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
+    } else {
+      s = plant_step(s, o.U[0], o.U[1], p.wx, p.wy, mesh);
+    }
     if (live) {
       const long q = (long)(i - 1);
       if (U_hist) { U_hist[q * 2 * n + d] = o.U[0]; U_hist[q * 2 * n + n + d] = o.U[1]; }
@@ -516,6 +548,21 @@ track_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_r
   if (live && X_final) {
     X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
   }
+  if constexpr (FIELD) {
+    if (iter_max) atomicMax(iter_max, wc.iters);
+  }
+}
+
+__global__ void __launch_bounds__(64)
+track_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
+                 const double *__restrict__ y_ref, const double *__restrict__ xd,
+                 const double *__restrict__ yd, const double *__restrict__ xdd,
+                 const double *__restrict__ ydd, const double *__restrict__ X0,
+                 double *__restrict__ X_hist, double *__restrict__ U_hist,
+                 double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
+                 double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
+                 double *__restrict__ X_final) {
+  track_run_body<false, false>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final);
 }
 
 // ------------------------------------------------------------------------------------
@@ -743,9 +790,6 @@ gvf_run_wind_kernel(GVF_ARGS, d2d_wind_field wf, double t_start, int32_t *__rest
   gvf_run_body<0, false, true>(GVF_PASS, &wf, t_start, iter_max);
 }
 
-// track_run_kernel in a field (a copy rather than a shared template body: the constant-wind kernels keep their exact code).  The
-// plant flies wf, step i from row i - 1 at t_start + (i - 1) dt; the controller keeps p.wx, p.wy, the constant of DiffController(w)
-// (src/11_full_sim_case1.py:241-291 hands w to the controller and WindField(w) to the plant separately).
 __global__ void __launch_bounds__(64)
 track_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
                       const double *__restrict__ y_ref, const double *__restrict__ xd,
@@ -756,49 +800,11 @@ track_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict_
                       double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
                       double *__restrict__ X_final, d2d_wind_field wf, double t_start,
                       int32_t *__restrict__ iter_max) {
-  WindCtx wc = {&wf, t_start, 0};
-  const long n = p.n;
-  long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const bool live = d < n;
-  if (!live) d = n - 1;
-  State5 s = {X0[d], X0[n + d], X0[2 * n + d], X0[3 * n + d], X0[4 * n + d]};
-  if (live && X_hist) {
-    X_hist[d] = s.x; X_hist[n + d] = s.y; X_hist[2 * n + d] = s.psi; X_hist[3 * n + d] = s.phi; X_hist[4 * n + d] = s.v;
-  }
-  for (int i = 1; i < p.n_rows; ++i) {
-    const long r = (long)i * n + d;
-    double Y[8] = {x_ref[r], y_ref[r], xd[r], yd[r], xdd[r], ydd[r], 0.0, 0.0};   // Yddd = [0,0] (:279)
-    const GainOut o = compute_gain(s, Y, p);
-    wc.t = t_start + (i - 1) * p.dt;
-    s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
-    if (live) {
-      const long q = (long)(i - 1);
-      if (U_hist) { U_hist[q * 2 * n + d] = o.U[0]; U_hist[q * 2 * n + n + d] = o.U[1]; }
-      if (dX_hist) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) dX_hist[q * 5 * n + c * n + d] = o.dX[c];
-      }
-      if (Xr_hist) {
-        double *o5 = Xr_hist + q * 5 * n;
-        o5[d] = o.Xr.x; o5[n + d] = o.Xr.y; o5[2 * n + d] = o.Xr.psi; o5[3 * n + d] = o.Xr.phi; o5[4 * n + d] = o.Xr.v;
-      }
-      if (Yd_hist) { Yd_hist[q * 2 * n + d] = Y[2]; Yd_hist[q * 2 * n + n + d] = Y[3]; }
-      if (Ydd_hist) { Ydd_hist[q * 2 * n + d] = Y[4]; Ydd_hist[q * 2 * n + n + d] = Y[5]; }
-      if (X_hist) {
-        double *o5 = X_hist + (long)i * 5 * n;
-        o5[d] = s.x; o5[n + d] = s.y; o5[2 * n + d] = s.psi; o5[3 * n + d] = s.phi; o5[4 * n + d] = s.v;
-      }
-    }
-  }
-  if (live && X_final) {
-    X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
-  }
-  if (iter_max) atomicMax(iter_max, wc.iters);
+  track_run_body<true, false>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final,
+                              &wf, t_start, nullptr, iter_max);
 }
 
-// d2d_sim_track_run_wind_at: track_run_wind_kernel with a start time per drone, t_at [n] (a copy again: the scalar kernel keeps its
-// exact code; change the three together).  The drones of the mission chain start phase 2 where their own formation ended phase 1.
-// The time of a step is written as in the scalar kernel, t_start + (i - 1) dt.
+// d2d_sim_track_run_wind_at: a start time per drone
 __global__ void __launch_bounds__(64)
 track_run_wind_at_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
                       const double *__restrict__ y_ref, const double *__restrict__ xd,
@@ -809,95 +815,16 @@ track_run_wind_at_kernel(d2d_track_params p, GlMesh mesh, const double *__restri
                       double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
                       double *__restrict__ X_final, d2d_wind_field wf, const double *__restrict__ t_at,
                       int32_t *__restrict__ iter_max) {
-  const long n = p.n;
-  long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const bool live = d < n;
-  if (!live) d = n - 1;
-  const double t_start = t_at[d];
-  WindCtx wc = {&wf, t_start, 0};
-  State5 s = {X0[d], X0[n + d], X0[2 * n + d], X0[3 * n + d], X0[4 * n + d]};
-  if (live && X_hist) {
-    X_hist[d] = s.x; X_hist[n + d] = s.y; X_hist[2 * n + d] = s.psi; X_hist[3 * n + d] = s.phi; X_hist[4 * n + d] = s.v;
-  }
-  for (int i = 1; i < p.n_rows; ++i) {
-    const long r = (long)i * n + d;
-    double Y[8] = {x_ref[r], y_ref[r], xd[r], yd[r], xdd[r], ydd[r], 0.0, 0.0};   // Yddd = [0,0] (:279)
-    const GainOut o = compute_gain(s, Y, p);
-    wc.t = t_start + (i - 1) * p.dt;
-    s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
-    if (live) {
-      const long q = (long)(i - 1);
-      if (U_hist) { U_hist[q * 2 * n + d] = o.U[0]; U_hist[q * 2 * n + n + d] = o.U[1]; }
-      if (dX_hist) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) dX_hist[q * 5 * n + c * n + d] = o.dX[c];
-      }
-      if (Xr_hist) {
-        double *o5 = Xr_hist + q * 5 * n;
-        o5[d] = o.Xr.x; o5[n + d] = o.Xr.y; o5[2 * n + d] = o.Xr.psi; o5[3 * n + d] = o.Xr.phi; o5[4 * n + d] = o.Xr.v;
-      }
-      if (Yd_hist) { Yd_hist[q * 2 * n + d] = Y[2]; Yd_hist[q * 2 * n + n + d] = Y[3]; }
-      if (Ydd_hist) { Ydd_hist[q * 2 * n + d] = Y[4]; Ydd_hist[q * 2 * n + n + d] = Y[5]; }
-      if (X_hist) {
-        double *o5 = X_hist + (long)i * 5 * n;
-        o5[d] = s.x; o5[n + d] = s.y; o5[2 * n + d] = s.psi; o5[3 * n + d] = s.phi; o5[4 * n + d] = s.v;
-      }
-    }
-  }
-  if (live && X_final) {
-    X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
-  }
-  if (iter_max) atomicMax(iter_max, wc.iters);
+  track_run_body<true, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final,
+                             &wf, 0.0, t_at, iter_max);
 }
 
-// dfff_run_kernel in a field (a copy, as above): the plant flies wf, step i from row i - 1 at t_start + (i - 1) dt, and the controller
-// sees the field at (t_i, the position of reference sample i), as DFFFController.get samples it (src/d2d/guidance.py:62-65).
 __global__ void __launch_bounds__(64)
 dfff_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref, const double *__restrict__ perts,
                      const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist,
                      double *__restrict__ Xr_hist, double *__restrict__ X_final, d2d_wind_field wf, double t_start,
                      int32_t *__restrict__ iter_max) {
-  WindCtx wc = {&wf, t_start, 0};
-  const long n = p.n;
-  long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const bool live = d < n;
-  if (!live) d = n - 1;                               // (keeps the wave converged in care_sda's __all())
-  State5 s = {X0[d], X0[n + d], X0[2 * n + d], X0[3 * n + d], X0[4 * n + d]};
-  if (live && X_hist) {
-    X_hist[d] = s.x; X_hist[n + d] = s.y; X_hist[2 * n + d] = s.psi; X_hist[3 * n + d] = s.phi; X_hist[4 * n + d] = s.v;
-  }
-  for (int i = 1; i <= p.n_rows; ++i) {
-    const long q = i - 1;                             // the row the controller acts on
-    double Y[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) Y[c] = Yref[(q * 6 + c) * n + d];
-    d2d_track_params pq = p;
-    const WindVec w = wind_at(wf, t_start + q * p.dt, Y[0], Y[1]);
-    pq.wx = w.x; pq.wy = w.y;
-    const DfffOut o = dfff_gain(s, Y, pq);
-    if (live) {
-      if (U_hist) { U_hist[q * 2 * n + d] = o.U[0]; U_hist[q * 2 * n + n + d] = o.U[1]; }
-      if (Xr_hist) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) Xr_hist[(q * 5 + c) * n + d] = o.Xr[c];
-      }
-    }
-    if (i == p.n_rows) break;                         // the last row only gets its command (:33)
-    wc.t = t_start + q * p.dt;
-    s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
-    if (perts) {
-      const double *pr = perts + (long)i * 5 * n + d;
-      s.x += pr[0]; s.y += pr[n]; s.psi += pr[2 * n]; s.phi += pr[3 * n]; s.v += pr[4 * n];
-    }
-    if (live && X_hist) {
-      double *o5 = X_hist + (long)i * 5 * n;
-      o5[d] = s.x; o5[n + d] = s.y; o5[2 * n + d] = s.psi; o5[3 * n + d] = s.phi; o5[4 * n + d] = s.v;
-    }
-  }
-  if (live && X_final) {
-    X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
-  }
-  if (iter_max) atomicMax(iter_max, wc.iters);
+  dfff_run_body<true>(p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, &wf, t_start, iter_max);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1036,13 +963,13 @@ static int dfff_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double *
     if (int rc = check_wind(f, who)) return rc;
   }
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
+  const dim3 grid((p->n + 63) / 64), block(64);          // a wavefront per workgroup
   if (f) {
     if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(dfff_run_wind_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist,
-                       U_hist, Xr_hist, X_final, *f, t_start, iter_max);
+    hipLaunchKernelGGL(dfff_run_wind_kernel, grid, block, 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, *f,
+                       t_start, iter_max);
   } else {
-    hipLaunchKernelGGL(dfff_run_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist,
-                       U_hist, Xr_hist, X_final);
+    hipLaunchKernelGGL(dfff_run_kernel, grid, block, 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final);
   }
   D2D_LAUNCH_CHECK();
   return D2D_OK;
@@ -1083,17 +1010,18 @@ static int track_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double 
   hipLaunchKernelGGL(gradient_kernel, g, b, 0, ctx->stream, p->n_rows, p->n, inv_dt, yd, ydd);
   D2D_LAUNCH_CHECK();
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
+  const dim3 grid((p->n + 63) / 64), block(64);          // a wavefront per workgroup
   if (f) {
     if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
     if (t_at)
-      hipLaunchKernelGGL(track_run_wind_at_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
-                         yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_at, iter_max);
+      hipLaunchKernelGGL(track_run_wind_at_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist,
+                         Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_at, iter_max);
     else
-      hipLaunchKernelGGL(track_run_wind_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
-                         yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_start, iter_max);
+      hipLaunchKernelGGL(track_run_wind_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist,
+                         Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_start, iter_max);
   } else {
-    hipLaunchKernelGGL(track_run_kernel, dim3((p->n + 63) / 64), dim3(64), 0, ctx->stream, *p, mesh, x_ref, y_ref, xd,
-                       yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final);
+    hipLaunchKernelGGL(track_run_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist,
+                       dX_hist, Yd_hist, Ydd_hist, X_final);
   }
   D2D_LAUNCH_CHECK();
   D2D_CHECK_HIP(hipFreeAsync(deriv, ctx->stream));
