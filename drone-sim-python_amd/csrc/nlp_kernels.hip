@@ -14,6 +14,7 @@
 // one broadcast request for the serial recursions); control flow is uniform, so no problem waits for another one's line search.
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "fit_device.h"      // scenario row columns (D2D_SC_*), FIT_G, FIT_OBS_K
@@ -78,10 +79,20 @@ __device__ __forceinline__ void nlp_obs(const double *__restrict__ sc, int i, do
 // this aircraft's partners, bit j = aircraft j: a wave-uniform value (scalar register), walked bit by bit in a ROLLED loop -- one
 // partner's terms live at a time, whatever the count (an unrolled loop over seven partners would spill: the kernel already sits at
 // the register limit), and no lane diverges.  Ascending j: with the mask of one partner the sums are the frozen partner's above.
-template <bool PAIRS = false>
+// MOV (d2d_nlp_solve_moving, d2d_nlp_solve_groups_moving): mv holds the problem's moving discs -- centre planes ctr [n][2][N] that
+// nlp_mov_sample_kernel wrote ahead of the solve (disc m's x at node i: ctr[(2 m) * N + i], read like a partner's plane) and the table
+// disc [n][2] = (r, kind), wave-uniform.  Each disc adds the static disc's term of its kind with the node's own centre, in a rolled
+// loop like the partner set's, ascending m, after the static discs and before the partners.
+struct NlpMovSet {
+  const double *ctr;
+  const double *disc;
+  int n;
+};
+template <bool PAIRS = false, bool MOV = false>
 __device__ __forceinline__ void nlp_exp_terms(const NlpScen &s, const double *__restrict__ sc, const double *__restrict__ partner,
                                               long pidx, long pstride, double x, double y, double &obj, double &cost_ref,
-                                              double *gx, double *gy, double *dxx, double *dxy, double *dyy, unsigned pmask = 0u) {
+                                              double *gx, double *gy, double *dxx, double *dxy, double *dyy, unsigned pmask = 0u,
+                                              const NlpMovSet *mv = nullptr) {
   for (int i = 0; i < s.n_obs; ++i) {
     double cx, cy, r;
     nlp_obs(sc, i, cx, cy, r);
@@ -106,6 +117,35 @@ __device__ __forceinline__ void nlp_exp_terms(const NlpScen &s, const double *__
     if (gx) {
       *gx += -k2 * we * dx; *gy += -k2 * we * dy;
       *dxx += k2 * k2 * we * dx * dx; *dxy += k2 * k2 * we * dx * dy; *dyy += k2 * k2 * we * dy * dy;
+    }
+  }
+  if constexpr (MOV) {
+    const double *__restrict__ ctr = mv->ctr, *__restrict__ disc = mv->disc;
+#pragma clang loop unroll(disable)
+    for (int m = 0; m < mv->n; ++m) {
+      const double r = disc[2 * m];
+      if (!(r > 0.0)) continue;
+      const double dx = x - ctr[(long)(2 * m) * pstride + pidx], dy = y - ctr[(long)(2 * m + 1) * pstride + pidx];
+      double k2, w, e, f;
+      if (disc[2 * m + 1] == 0.0) {   // kind 0, as in the loop of the static discs
+        k2 = 1.0; w = s.wobs;
+        const double arg = r * r - (dx * dx + dy * dy);
+        e = exp(fmin(arg, 6.907755278982137));
+        f = arg > 6.907755278982137 ? 1e3 * (1.0 + arg - 6.907755278982137) : e;
+        cost_ref += w * e;
+      } else {                        // kind 1
+        k2 = (FIT_OBS_K / r) * (FIT_OBS_K / r);
+        e = exp(-(dx * dx + dy * dy) * k2);
+        cost_ref += s.wobs * e;
+        w = s.wobs / k2;
+        f = e;
+      }
+      const double we = w * e;
+      obj += w * f;
+      if (gx) {
+        *gx += -k2 * we * dx; *gy += -k2 * we * dy;
+        *dxx += k2 * k2 * we * dx * dx; *dxy += k2 * k2 * we * dx * dy; *dyy += k2 * k2 * we * dy * dy;
+      }
     }
   }
   if constexpr (PAIRS) {
@@ -171,6 +211,15 @@ struct NlpProb {
   const d2d_wind_field *wf;  // WIND instantiations (d2d_nlp_solve_wind): the field of the equalities, node i at t0 + i h; else null
   double t0;
 };
+// MOV instantiations: the problem with its moving discs (the others keep NlpProb as it is)
+struct NlpMovProb : NlpProb {
+  NlpMovSet mv;
+};
+template <bool MOV> using NlpProbT = std::conditional_t<MOV, NlpMovProb, NlpProb>;
+template <bool MOV> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const NlpProbT<MOV> &pb) {
+  if constexpr (MOV) return &pb.mv;
+  else return nullptr;
+}
 // Objective model of d2d_nlp_solve_model (user cost plug-ins, opty/direct_collocation.py): this problem's planes.  The objective of
 // that instantiation is  m(W) = sum_i g_i.d_i + 1/2 d_i^T H_i d_i,  d_i = W_i - Wc_i, on top of the structured terms (which the
 // host's row zeroes); H_i is held as its upper triangle, row by row (nlp_hidx).
@@ -236,8 +285,8 @@ __device__ __forceinline__ bool nlp_fixed(int i, int N, int c) { return c < 3 &&
 
 // Merit function of the inner problem at W + a*dw: objective + rho sum (c + mu)^2 - mub sum log(slacks); +inf outside the box.
 // Node-parallel (lane = node, chunks of 64) + wave reductions.  All results are wave-uniform.
-template <bool MODEL, bool WIND = false, bool PAIRS = false>
-__device__ double nlp_merit(const NlpProb &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false>
+__device__ double nlp_merit(const NlpProbT<MOV> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
                             double mub, double *cost_ref_out, double *feas_out, const NlpModel &md) {
   const int N = pb.N;
   double val = 0.0, bar = 0.0, cref = 0.0, feas = 0.0, phi2max = 0.0;
@@ -284,7 +333,7 @@ __device__ double nlp_merit(const NlpProb &pb, const NlpScen &s, const double *_
       }
       phi2max = fmax(phi2max, w[3] * w[3]);
       cref += obj;
-      nlp_exp_terms<PAIRS>(s, sc, pb.partner, i, N, w[0], w[1], obj, cref, nullptr, nullptr, nullptr, nullptr, nullptr, pb.pmask);
+      nlp_exp_terms<PAIRS, MOV>(s, sc, pb.partner, i, N, w[0], w[1], obj, cref, nullptr, nullptr, nullptr, nullptr, nullptr, pb.pmask, nlp_mov_set<MOV>(pb));
       val += obj;
       if (i >= 1) {
         double c3[3];
@@ -345,8 +394,8 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // WIND (d2d_nlp_solve_wind): the constraint that ends at node i reads the field at (t_i, x_i, y_i): with J = d(wx, wy)/d(x, y) there,
 // Ac gains J on its (x, y) columns and D the constraint curvature rho (c + mu)_0 Hess(wx) + rho (c + mu)_1 Hess(wy) on its (x, y)
 // block; node i+1's constraint sees node i through -1/h only, so the has_next terms and the structure of E do not change.
-template <bool MODEL, bool WIND = false, bool PAIRS = false>
-__device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false>
+__device__ double nlp_assemble(const NlpProbT<MOV> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
                                double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md) {
   const int N = pb.N;
   const double h = pb.h, ih = 1.0 / h;
@@ -429,7 +478,7 @@ __device__ double nlp_assemble(const NlpProb &pb, const NlpScen &s, const double
     }
     {
       double obj = 0.0, cref = 0.0;
-      nlp_exp_terms<PAIRS>(s, sc, pb.partner, i, N, wc[0], wc[1], obj, cref, &g[0], &g[1], &D[0][0], &D[0][1], &D[1][1], pb.pmask);
+      nlp_exp_terms<PAIRS, MOV>(s, sc, pb.partner, i, N, wc[0], wc[1], obj, cref, &g[0], &g[1], &D[0][0], &D[0][1], &D[1][1], pb.pmask, nlp_mov_set<MOV>(pb));
       D[1][0] = D[0][1];
     }
     double E[NLP_NV][3];                        // block (i, i-1): only the (x, y, psi) columns of node i-1 are non-zero
@@ -1146,11 +1195,13 @@ struct NlpOut { double cost, feas; int iters, status; };
 // MODEL: the objective is the quadratic model md (d2d_nlp_solve_model) on top of the row's structured terms; cost = its value.
 // WIND: the equalities read the field wf at node i's own (t_start + i h, x_i, y_i) instead of the row's constant (d2d_nlp_solve_wind).
 // PAIRS: partner is the scenario's W and pmask this aircraft's partner set (nlp_exp_terms); pmask = 0: no partner.
-template <bool MODEL = false, bool WIND = false, bool PAIRS = false>
+// MOV: mv the problem's moving discs (nlp_exp_terms), their centre planes sampled at this problem's node times.
+template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
                                               const double *__restrict__ bnd, const NlpModel &md = NlpModel{nullptr, nullptr, nullptr},
-                                              const d2d_wind_field *wf = nullptr, double t_start = 0.0, unsigned pmask = 0u) {
+                                              const d2d_wind_field *wf = nullptr, double t_start = 0.0, unsigned pmask = 0u,
+                                              const NlpMovSet *mv = nullptr) {
   // diagnostics (D2D_NLP_STAMPS): cycles per phase -- merit, assembly, factorisation, back substitution, ratio tests, update
   unsigned long long st_t = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define NLP_STAMP(k) if (st_on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t; st_t = t_; }
@@ -1158,7 +1209,8 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   if (st_on) st_t = __builtin_amdgcn_s_memtime();
   NlpScen s = nlp_load_scen(sc, o, bnd);
   if (sc[D2D_SC_BANKMAX] != 0.0) { s.sbank = s.skphi * (double)N; s.skphi = 0.0; }     // obj_scale * kbank (the row's S is obj_scale / N)
-  NlpProb pb;
+  NlpProbT<MOV> pb;
+  if constexpr (MOV) pb.mv = *mv;
   pb.N = N; pb.h = h;
   pb.W = Wb;
   pb.ws = wsb;
@@ -1228,7 +1280,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     const double tol_in = fmax(fmax(o.opt_tol, fmin(1e-1, 10.0 * mub)), D2D_NLP_GRAD_FLOOR * rho);
     // merit value of the current point for this (mub, rho, mu): one pass here, afterwards the accepted trial's value
     NLP_STAMP(7)
-    double phi0 = nlp_merit<MODEL, WIND, PAIRS>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    double phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1239,7 +1291,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       const int imax = s.sbank > 0.0 ? nlp_bank_argmax(pb, lane) : -1;
       for (int tr = 0; tr < 30; ++tr) {
         bool pd;
-        err = nlp_assemble<MODEL, WIND, PAIRS>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -1262,7 +1314,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         double a = amax, pt = 0.0;
         bool ok = false;
         for (int ls = 0; ls < 8; ++ls) {
-          pt = nlp_merit<MODEL, WIND, PAIRS>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
+          pt = nlp_merit<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
@@ -1280,7 +1332,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       }
       if (converged || !accepted) break;
     }
-    (void)nlp_merit<MODEL, WIND, PAIRS>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+    (void)nlp_merit<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -1319,7 +1371,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     feas_prev = feas;
     mub = fmax(o.mub_min, fmin(0.2 * mub, mub * sqrt(mub)));
   }
-  (void)nlp_merit<MODEL, WIND, PAIRS>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+  (void)nlp_merit<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -1418,6 +1470,93 @@ nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__re
   }
 }
 
+// d2d_mov_sample: the centres of the moving discs at the node times, ctr [G][n_mov][2][N].  A workgroup per (problem or scenario,
+// disc), lane = node; the track's knots are a table of at most D2D_MOV_MAX_KNOT rows that every lane walks (scalar loads).  The
+// centre is linear between the two knots that bracket t = t_start[g] + i h (one multiply-add, not accumulated) and held at the first
+// or last knot outside them; at a segment's end it is that knot exactly, so knots repeated behind the last one change nothing.
+// Tracks are not validated here (the solve kernels do that): whatever the knots hold, no index leaves the track.
+__global__ void __launch_bounds__(64)
+nlp_mov_sample_kernel(int N, double h, const double *__restrict__ t_start, d2d_moving_obstacles mv, double *__restrict__ ctr) {
+  const int g = blockIdx.x / mv.n_mov;
+  const double *__restrict__ kn = mv.knots + (size_t)blockIdx.x * mv.n_knot * 3;
+  double *__restrict__ out = ctr + (size_t)blockIdx.x * 2 * N;
+  const double t0 = t_start[g];
+  for (int i = threadIdx.x; i < N; i += 64) {
+    const double t = t0 + (double)i * h;
+    int k = 0;                               // the segment [knot k, knot k + 1] that holds t, the first or last one outside the knots
+    for (int q = 1; q < mv.n_knot - 1; ++q)
+      if (kn[3 * q] <= t) k = q;
+    const double ta = kn[3 * k], xa = kn[3 * k + 1], ya = kn[3 * k + 2], tb = kn[3 * k + 3], xb = kn[3 * k + 4], yb = kn[3 * k + 5];
+    const double u = fmax((t - ta) / (tb - ta), 0.0);
+    out[i] = u >= 1.0 ? xb : fma(u, xb - xa, xa);
+    out[N + i] = u >= 1.0 ? yb : fma(u, yb - ya, ya);
+  }
+}
+
+// The tracks of problem or scenario g, checked by every wavefront that solves against them before its first solve: a non-finite knot,
+// times that do not increase strictly, or a kind that is neither 0 nor 1.  Wave-uniform.
+__device__ __forceinline__ bool nlp_mov_bad(const d2d_moving_obstacles &mv, int g, int lane) {
+  int bad = 0;
+  const double *__restrict__ kn = mv.knots + (size_t)g * mv.n_mov * mv.n_knot * 3;
+  for (int e = lane; e < mv.n_mov * mv.n_knot; e += 64) {
+    const double t = kn[3 * e];
+    bad |= !(fabs(t) <= 1.79e308) || !(fabs(kn[3 * e + 1]) <= 1.79e308) || !(fabs(kn[3 * e + 2]) <= 1.79e308);
+    if (e % mv.n_knot != 0) bad |= !(t > kn[3 * (e - 1)]);
+  }
+  for (int m = lane; m < mv.n_mov; m += 64) {
+    const double kind = mv.disc[((size_t)g * mv.n_mov + m) * 2 + 1];
+    bad |= !(kind == 0.0 || kind == 1.0);
+  }
+  return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
+}
+
+// d2d_nlp_solve_moving: the persistent hand-out around the MOV instantiations of the solve -- the rows' constant wind or the field
+// (WIND), the start time per problem (t_start [B], device memory), the centre planes ctr [B][n_mov][2][N] sampled ahead of this launch.
+// A loop of its own, like nlp_solve_wind_kernel's (the comment above nlp_solve_kernel has the reason).  A problem whose start time is
+// not finite or whose tracks are unusable is refused before its solve: its W is not touched.
+template <bool WIND>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_moving_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                        double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                        int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
+                        d2d_moving_obstacles mv, const double *ctr) {
+  const int lane = threadIdx.x;
+  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
+  double *wsb = work + (size_t)blockIdx.x * WS_TOTAL * N;
+  const int32_t *__restrict__ order = o.order;
+  for (int t = blockIdx.x; t < B;) {
+    const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
+    if ((unsigned)b >= (unsigned)B) {        // (an entry that is no problem index is skipped, not dereferenced)
+      t = nlp_next_ticket(queue, lane);
+      continue;
+    }
+    NlpOut out;
+    double t0 = 0.0;
+    bool bad = false;
+    if (WIND || mv.n_mov > 0) {
+      t0 = nlp_first_lane(t_start[b]);
+      bad = !(fabs(t0) <= 1.79e308);
+    }
+    if (mv.n_mov > 0) bad = bad || nlp_mov_bad(mv, b, lane);
+    if (bad) {
+      out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
+    } else {
+      const NlpMovSet ms{ctr + (size_t)b * mv.n_mov * 2 * N, mv.disc + (size_t)b * mv.n_mov * 2, mv.n_mov};
+      nlp_solve_one<false, WIND, false, true>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + (size_t)b * NLP_NV * N, wsb,
+                                              mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds,
+                                              o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpModel{nullptr, nullptr, nullptr}, &wf, t0, 0u, &ms);
+    }
+    if (lane == 0) {
+      cost_out[b] = out.cost;
+      feas_out[b] = out.feas;
+      if (iters_out) iters_out[b] = out.iters;
+      if (status_out) status_out[b] = out.status;
+    }
+    nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
+    t = nlp_next_ticket(queue, lane);
+  }
+}
+
 // A scenario of the group loop is refused: all its aircraft at once, before the workgroup's first barrier (the caller returns).
 __device__ __forceinline__ void nlp_groups_refuse(int b, int r, int wave, int lane, double *cost_out, double *feas_out,
                                                   int32_t *iters_out, int32_t *status_out, int32_t *sweeps_out, double *moved_out) {
@@ -1475,16 +1614,20 @@ __device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
 //   aircraft j does not name a back -- the term of a pair belongs to both objectives or to none -- refuses the whole scenario
 //   (D2D_ST_NONFINITE, cost = feas = NaN, sweeps = 0, W untouched), like a non-finite start time: no mask ever indexes outside the
 //   scenario's W.
+// MOV (d2d_nlp_solve_groups_moving): every aircraft of scenario r solves around the scenario's moving discs, centre planes
+//   ctr [R][n_mov][2][N] sampled at t_start[r] + i h ahead of this launch.  The tracks are checked before the first solve, by every
+//   wavefront alike; an unusable track, or a start time that is not finite while discs move, refuses the scenario like a bad mask.
 // The pointer parameters of the body and of its two helpers carry no __restrict__ (the kernels' do): with it the fixed-pair kernel
 // went from 256 VGPRs / 624 B of scratch to 255 / 608 and the field kernel from 752 B to 784.
 // Registers: 512 threads per workgroup are 8 wavefronts on 4 SIMDs, two per SIMD, so a wavefront gets at most 256 of the SIMD's 512
 // registers whatever amdgpu_waves_per_eu says -- the workgroup size binds, and (2, 2) states what the hardware does.
-template <bool WIND, bool PAIRS>
+template <bool WIND, bool PAIRS, bool MOV = false>
 __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h, const d2d_nlp_opts &o, int max_sweeps, double tol,
                                                 const double *scen, double *W, double *work, double *mult, double *prev,
                                                 double *cost_out, double *feas_out, int32_t *iters_out,
                                                 int32_t *status_out, int32_t *sweeps_out, double *moved_out,
-                                                const d2d_wind_field *wf, const double *t_start) {
+                                                const d2d_wind_field *wf, const double *t_start,
+                                                const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr) {
   __shared__ double moved_s[PAIRS ? 8 : 2];
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1513,6 +1656,16 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
     cset = (unsigned)__builtin_amdgcn_readfirstlane((int)cset);
     pmask = (unsigned)__builtin_amdgcn_readfirstlane((int)((masks >> (8 * wave)) & 0xffull));
   }
+  [[maybe_unused]] NlpMovSet ms{nullptr, nullptr, 0};
+  const NlpMovSet *msp = nullptr;
+  if constexpr (MOV) {
+    if (mv->n_mov > 0) {
+      if constexpr (!WIND) bad = bad || !(fabs(nlp_first_lane(t_start[r])) <= 1.79e308);
+      bad = bad || nlp_mov_bad(*mv, r, lane);
+    }
+    ms = NlpMovSet{ctr + (size_t)r * mv->n_mov * 2 * N, mv->disc + (size_t)r * mv->n_mov * 2, mv->n_mov};
+    msp = &ms;
+  }
   if (bad) {                                 // (uniform over the workgroup: before the first barrier)
     nlp_groups_refuse(b, r, wave, lane, cost_out, feas_out, iters_out, status_out, sweeps_out, moved_out);
     return;
@@ -1530,7 +1683,7 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
   double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
   const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
   const NlpModel no_model{nullptr, nullptr, nullptr};
-  nlp_solve_one<false, WIND, PAIRS>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, 0u);
+  nlp_solve_one<false, WIND, PAIRS, MOV>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, 0u, msp);
   iters_total += out.iters;
   if (threadIdx.x < (PAIRS ? 8 : 2)) moved_s[threadIdx.x] = 0.0;
   __threadfence_block();
@@ -1547,7 +1700,7 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
           // fixed pair: the partner's x and y planes; PAIRS: the scenario's W and the set
           const double *pw = PAIRS ? Wr : W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;
           for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
-          nlp_solve_one<false, WIND, PAIRS>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, pmask);
+          nlp_solve_one<false, WIND, PAIRS, MOV>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, pmask, msp);
           iters_total += out.iters;
           double m = 0.0;
           for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
@@ -1605,6 +1758,18 @@ nlp_groups_pairs_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int ma
                         double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
   nlp_groups_body<WIND, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
                               sweeps_out, moved_out, &wf, t_start);
+}
+
+// d2d_nlp_solve_groups_moving: the pairs of the masks around the scenarios' moving discs; WIND as above
+template <bool WIND>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
+nlp_groups_moving_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                         double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                         int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                         double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start, d2d_moving_obstacles mv,
+                         const double *__restrict__ ctr) {
+  nlp_groups_body<WIND, true, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
+                                    sweeps_out, moved_out, &wf, t_start, &mv, ctr);
 }
 
 // d2d_nlp_solve_model: the collocation NLP under the quadratic objective model of a cost that only the host can evaluate (a user's
@@ -1668,6 +1833,23 @@ template <typename Kernel, typename... Args>
 static void nlp_groups_launch(Kernel kernel, d2d_ctx *ctx, int R, int n_ac, Args... args) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
   hipLaunchKernelGGL(kernel, dim3(R), dim3(64 * n_ac), (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double), ctx->stream, R, n_ac, args...);
+}
+
+// a d2d_moving_obstacles argument of an entry point (include/d2d.h: what makes one D2D_EINVAL); work: the centre planes
+static int check_moving(const d2d_moving_obstacles *mov, const double *work, const double *t_start, const char *who) {
+  D2D_REQUIRE(mov, "%s: null moving-obstacle table (n_mov = 0: nothing moves)", who);
+  D2D_REQUIRE(mov->n_mov >= 0 && mov->n_mov <= D2D_MAX_MOV, "%s: n_mov = %d outside 0 .. %d", who, mov->n_mov, D2D_MAX_MOV);
+  if (mov->n_mov == 0) return D2D_OK;
+  D2D_REQUIRE(mov->n_knot >= 2 && mov->n_knot <= D2D_MOV_MAX_KNOT, "%s: n_knot = %d outside 2 .. %d", who, mov->n_knot, D2D_MOV_MAX_KNOT);
+  D2D_REQUIRE(mov->knots && mov->disc, "%s: null knots or disc table with n_mov = %d", who, mov->n_mov);
+  D2D_REQUIRE(work, "%s: null array of centre planes with n_mov = %d", who, mov->n_mov);
+  D2D_REQUIRE(t_start, "%s: null t_start with n_mov = %d (a device array: the tracks' times are absolute)", who, mov->n_mov);
+  return D2D_OK;
+}
+
+// the sampler's launch on the context's stream: a workgroup per (problem or scenario, disc)
+static void nlp_mov_sample_launch(d2d_ctx *ctx, int G, int N, double h, const double *t_start, const d2d_moving_obstacles &mov, double *ctr) {
+  hipLaunchKernelGGL(nlp_mov_sample_kernel, dim3((unsigned)G * (unsigned)mov.n_mov), dim3(64), 0, ctx->stream, N, h, t_start, mov, ctr);
 }
 
 extern "C" {
@@ -1772,6 +1954,70 @@ int d2d_nlp_solve_groups_pairs(d2d_ctx *ctx, int R, int n_ac, int N, double h, c
   else
     nlp_groups_launch(nlp_groups_pairs_kernel<false>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
                       sweeps, moved, d2d_wind_field{}, t_start);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+int d2d_mov_sample(d2d_ctx *ctx, int G, int N, double h, const double *t_start, const d2d_moving_obstacles *mov, double *ctr) {
+  D2D_REQUIRE(ctx, "d2d_mov_sample: null argument");
+  D2D_REQUIRE(G >= 1 && N >= 1 && h > 0, "d2d_mov_sample: G >= 1, N >= 1, h > 0 required (G=%d N=%d h=%g)", G, N, h);
+  if (int rc = check_moving(mov, ctr, t_start, "d2d_mov_sample")) return rc;
+  if (mov->n_mov == 0) return D2D_OK;
+  nlp_mov_sample_launch(ctx, G, N, h, t_start, *mov, ctr);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+int d2d_nlp_solve_moving(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
+                         double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
+                         const double *t_start, const d2d_moving_obstacles *mov, double *mov_work) {
+  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_moving: null argument");
+  D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_moving: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
+  if (int rc = check_moving(mov, mov_work, t_start, "d2d_nlp_solve_moving")) return rc;
+  if (mov->n_mov == 0)
+    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_moving: without moving discs f and t_start go together (both NULL: the rows' constant wind)");
+  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_moving")) return rc; }
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_moving", &o)) return rc;
+  if (mov->n_mov > 0) {
+    nlp_mov_sample_launch(ctx, B, N, h, t_start, *mov, mov_work);
+    D2D_LAUNCH_CHECK();
+  }
+  const int grid = nlp_handout_grid(B, o, NLP_WIND_WAVES_PER_SIMD);
+  int32_t *queue = ctx->counter_dev + 2;
+  D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
+  if (f)
+    hipLaunchKernelGGL(nlp_solve_moving_kernel<true>, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work,
+                       mult, cost, feas, iters, status, queue, *f, t_start, *mov, mov_work);
+  else
+    hipLaunchKernelGGL(nlp_solve_moving_kernel<false>, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work,
+                       mult, cost, feas, iters, status, queue, d2d_wind_field{}, t_start, *mov, mov_work);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+int d2d_nlp_solve_groups_moving(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                                double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                                int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
+                                const d2d_moving_obstacles *mov, double *mov_work) {
+  if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_moving")) return rc;
+  if (int rc = check_moving(mov, mov_work, t_start, "d2d_nlp_solve_groups_moving")) return rc;
+  if (mov->n_mov == 0)
+    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_groups_moving: without moving discs f and t_start go together (both NULL: the rows' constant wind)");
+  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_groups_moving")) return rc; }
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_moving", &o)) return rc;
+  if (mov->n_mov > 0) {
+    nlp_mov_sample_launch(ctx, R, N, h, t_start, *mov, mov_work);
+    D2D_LAUNCH_CHECK();
+  }
+  double *prev = nlp_groups_prev(work, R, n_ac, N);
+  if (f)
+    nlp_groups_launch(nlp_groups_moving_kernel<true>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
+                      sweeps, moved, *f, t_start, *mov, (const double *)mov_work);
+  else
+    nlp_groups_launch(nlp_groups_moving_kernel<false>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
+                      sweeps, moved, d2d_wind_field{}, t_start, *mov, (const double *)mov_work);
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }

@@ -248,3 +248,77 @@ def triangle(p0, p1, va, duration, num_nodes, go_left=1.):
     h0, h1 = apex - p0, p1 - apex
     psis = np.hstack((np.arctan2(h0[1], h0[0]) * np.ones(n1), np.arctan2(h1[1], h1[0]) * np.ones(n2)))
     return pts[:, 0], pts[:, 1], psis, np.zeros(num_nodes), va * np.ones(num_nodes)
+
+
+class MovingObstacle:
+    """A CostObstacle disc whose centre is piecewise linear in time (include/d2d.h d2d_moving_obstacles): knot times t (n,), strictly
+    increasing, centres xy (n, 2), radius r, kind 0 / 1 as CostObstacle's.  Between two knots the centre is interpolated linearly;
+    before the first and after the last it is held.  Times are absolute, on the clock of the scenario's t0 and of a wind field.
+    Scenarios list them in `moving_obstacles`; the collocation backend plans around them with the cost's kobs as their weight."""
+
+    def __init__(self, t, xy, r, kind=1):
+        self.t = np.asarray(t, dtype=np.float64).reshape(-1)
+        self.xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+        self.r, self.kind = float(r), int(kind)
+        if len(self.t) < 2 or len(self.t) != len(self.xy):
+            raise ValueError('a moving obstacle needs at least two knots, one centre per knot time')
+        if not (np.isfinite(self.t).all() and np.isfinite(self.xy).all()):
+            raise ValueError('moving obstacle: knot times and centres must be finite')
+        if not (np.diff(self.t) > 0).all():
+            raise ValueError('moving obstacle: knot times must increase strictly')
+        if self.kind not in (0, 1):
+            raise ValueError('moving obstacle: kind is 0 or 1 (CostObstacle)')
+
+    @classmethod
+    def linear(cls, c0, v, r, t0=0., t1=60., kind=1):
+        """A disc at c0 at time t0 that moves with the constant velocity v until t1 (and stands still outside [t0, t1])."""
+        c0, v = np.asarray(c0, dtype=np.float64), np.asarray(v, dtype=np.float64)
+        return cls((t0, t1), (c0, c0 + v * (t1 - t0)), r, kind)
+
+    def at(self, t):
+        """Centres at the times t -> (..., 2): the numpy twin of the device sampler (csrc/nlp_kernels.hip nlp_mov_sample_kernel) --
+        the same segment, the same expression up to the device's fused multiply-add."""
+        return track_at(self.t, self.xy, t)
+
+    def padded(self, n_knot):
+        """(n_knot, 3) rows (t, x, y): the knots, then the last one repeated at strictly later times -- which changes no centre."""
+        n = len(self.t)
+        if n > n_knot:
+            raise ValueError(f'{n} knots do not fit {n_knot}')
+        out = np.empty((n_knot, 3))
+        out[:n, 0], out[:n, 1:] = self.t, self.xy
+        step = max(1.0, abs(self.t[-1]))          # (large enough to be a strict increase at any magnitude of the last time)
+        out[n:, 0] = self.t[-1] + step * np.arange(1, n_knot - n + 1)
+        out[n:, 1:] = self.xy[-1]
+        return out
+
+
+def track_at(tk, xy, t):
+    """Centre of a piecewise-linear track (knot times tk (n,), centres xy (n, 2)) at the times t: linear inside the segment that holds
+    t, the first or last knot outside the knots, and a segment's end knot exactly at its end."""
+    tk, xy, t = np.asarray(tk, dtype=np.float64), np.asarray(xy, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    k = np.clip(np.searchsorted(tk, t, side='right') - 1, 0, len(tk) - 2)
+    u = np.maximum((t - tk[k]) / (tk[k + 1] - tk[k]), 0.0)[..., None]
+    return np.where(u >= 1.0, xy[k + 1], xy[k] + u * (xy[k + 1] - xy[k]))
+
+
+def lower_moving(obstacles, n_knot=None):
+    """The tables of d2d_moving_obstacles for one problem or scenario: knots (n_mov, n_knot, 3) = (t, x, y) and disc (n_mov, 2) =
+    (r, kind).  n_knot: the call's knot count (default: the longest track's); shorter tracks are padded (MovingObstacle.padded).
+    NotImplementedError beyond d2dhip.MAX_MOV discs, ValueError beyond d2dhip.MOV_MAX_KNOT knots."""
+    import d2dhip
+    obstacles = list(obstacles)
+    if len(obstacles) > d2dhip.MAX_MOV:
+        raise NotImplementedError(f'at most {d2dhip.MAX_MOV} moving obstacles per problem in this build ({len(obstacles)} given)')
+    need = max([len(o.t) for o in obstacles], default=2)
+    n_knot = need if n_knot is None else int(n_knot)
+    if need > d2dhip.MOV_MAX_KNOT or n_knot > d2dhip.MOV_MAX_KNOT:
+        raise ValueError(f'at most {d2dhip.MOV_MAX_KNOT} knots per moving obstacle ({max(need, n_knot)} asked for)')
+    knots = np.stack([o.padded(n_knot) for o in obstacles]) if obstacles else np.zeros((0, n_knot, 3))
+    disc = np.array([(o.r, o.kind) for o in obstacles], dtype=np.float64).reshape(-1, 2)
+    return knots, disc
+
+
+def min_clearance(obstacles, t, x, y):
+    """Per moving obstacle: min_i |p_i - c(t_i)| - r over the nodes (t_i, x_i, y_i) of a plan."""
+    return [float((np.hypot(*(np.stack([x, y], -1) - o.at(t)).T)).min() - o.r) for o in obstacles]

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('D2D_LIB') or os.path.join(os.path.dirname(_HERE), 'li
 
 SCEN_STRIDE = 80
 MAX_OBS = 16
+MAX_MOV, MOV_MAX_KNOT = 8, 32          # include/d2d.h D2D_MAX_MOV / D2D_MOV_MAX_KNOT (tests compare)
 (SC_X0, SC_Y0, SC_PSI0, SC_X1, SC_Y1, SC_PSI1, SC_VREF, SC_VSP, SC_KV, SC_KPHI, SC_KOBS, SC_S,
  SC_WWP, SC_WX, SC_WY, SC_GOLEFT, SC_O0X, SC_O0Y, SC_O0R, SC_O1X, SC_O1Y, SC_O1R, SC_WBND,
  SC_PHIMAX, SC_VMIN, SC_VMAX, SC_KCOL, SC_RCOL, SC_SCOL, SC_PMASK, SC_OKIND, SC_BANKMAX, SC_OEXT) = range(33)
@@ -69,6 +70,11 @@ class NlpOpts(C.Structure):
 class NlpModel(C.Structure):
     """d2d_nlp_model: device pointers of the quadratic objective model (g [B][5][N], H [B][15][N] upper triangles, Wc [B][5][N])."""
     _fields_ = [('g', C.c_void_p), ('H', C.c_void_p), ('Wc', C.c_void_p)]
+
+
+class MovingObstaclesC(C.Structure):
+    """d2d_moving_obstacles (include/d2d.h): knots dev [G][n_mov][n_knot][3] = (t, x, y), disc dev [G][n_mov][2] = (r, kind)."""
+    _fields_ = [('n_mov', C.c_int32), ('n_knot', C.c_int32), ('knots', C.c_void_p), ('disc', C.c_void_p)]
 
 
 class FitOpts(C.Structure):
@@ -145,6 +151,11 @@ _SIGS = {
     'd2d_nlp_solve_groups_pairs': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
                                    + [C.POINTER(WindFieldC), _P]),
     'd2d_nlp_solve_model': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.POINTER(NlpModel)] + [_P] * 7),
+    'd2d_mov_sample': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(MovingObstaclesC), _P]),
+    'd2d_nlp_solve_moving': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
+                             + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P]),
+    'd2d_nlp_solve_groups_moving': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
+                                    + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P]),
     'd2d_fit_plan_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(_P)]),
     'd2d_fit_plan_create_ex': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(FitPlanOpts), C.POINTER(_P)]),
     'd2d_fit_opts_default': (C.c_int, [C.POINTER(FitOpts)]),
@@ -605,6 +616,93 @@ class Context:
                                                    None if f is None else C.byref(f), _ptr(t_start)))
         prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
         return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev)
+
+    def _moving_c(self, knots, disc, G):
+        """d2d_moving_obstacles over device tables: knots [G][n_mov][n_knot][3] and disc [G][n_mov][2], or (None, None): nothing moves.
+        Shapes only -- the ranges are the library's to check (D2D_EINVAL) and the tracks' contents the kernels'."""
+        torch = _torch()
+        if knots is None and disc is None:
+            return MovingObstaclesC(0, 0, None, None)
+        for t in (knots, disc):
+            assert t.is_contiguous() and t.dtype == torch.float64 and t.device.type == 'cuda'
+        assert knots.dim() == 4 and knots.shape[0] == G and knots.shape[3] == 3 and tuple(disc.shape) == (G, knots.shape[1], 2)
+        return MovingObstaclesC(int(knots.shape[1]), int(knots.shape[2]), knots.data_ptr(), disc.data_ptr())
+
+    def _t_start_dev(self, t_start, G, ref):
+        torch = _torch()
+        if t_start is not None and not torch.is_tensor(t_start):
+            t_start = torch.full((G,), float(t_start), dtype=torch.float64, device=self.device)
+        assert t_start is None or (t_start.is_contiguous() and tuple(t_start.shape) == (G,) and t_start.dtype == torch.float64 and t_start.device == ref.device)
+        return t_start
+
+    def mov_sample(self, knots, disc, t_start, N, h):
+        """The centres of moving discs at the node times (d2d_mov_sample): knots dev [G][n_mov][n_knot][3], disc dev [G][n_mov][2],
+        t_start dev [G] (or a float) -> ctr dev [G][n_mov][2][N], disc m of problem g at t_start[g] + i h."""
+        G = knots.shape[0]
+        m = self._moving_c(knots, disc, G)
+        t_start = self._t_start_dev(t_start, G, knots)
+        ctr = self.empty(G, m.n_mov, 2, int(N))
+        _check(self.lib.d2d_mov_sample(self.h, G, int(N), float(h), _ptr(t_start), C.byref(m), _ptr(ctr)))
+        return ctr
+
+    def nlp_solve_moving(self, scen, W, h, knots=None, disc=None, field=None, t_start=None, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9,
+                         opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None, slots=0,
+                         order=None):
+        """nlp_solve / nlp_solve_wind around moving discs (d2d_nlp_solve_moving): knots dev [B][n_mov][n_knot][3] = (t, x, y) and disc
+        dev [B][n_mov][2] = (r, kind) per problem (both None: nothing moves), field None: the rows' constant wind, t_start dev [B] or a
+        float: the problems' start times (required when discs move or with a field).  A problem with an unusable track or start time is
+        refused on the device: status ST_NONFINITE, cost = feas = NaN, its W untouched.  Returns nlp_solve's dict plus mov_work
+        [B][n_mov][2][N]: the discs' centres at the node times."""
+        torch = _torch()
+        B, _, N = W.shape
+        assert W.is_contiguous() and scen.shape[0] == B
+        m = self._moving_c(knots, disc, B)
+        t_start = self._t_start_dev(t_start, B, W)
+        work = self.empty(self.lib.d2d_nlp_workspace_doubles(N) * B)
+        mov_work = self.empty(B, m.n_mov, 2, N) if m.n_mov > 0 else None
+        cost, feas = self.empty(B), self.empty(B)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        mult = self.zeros(B, 3, N) if want_mult else None
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        assert order is None or (order.is_contiguous() and tuple(order.shape) == (B,) and order.dtype == torch.int32)
+        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, int(slots), None if bounds is None else bounds.data_ptr(),
+                    None if order is None else order.data_ptr())
+        f = None if field is None else _wind_c(self, field)
+        _check(self.lib.d2d_nlp_solve_moving(self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), _ptr(work), _ptr(mult), _ptr(cost),
+                                             _ptr(feas), _ptr(iters), _ptr(status), None if f is None else C.byref(f), _ptr(t_start),
+                                             C.byref(m), _ptr(mov_work)))
+        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work, mov_work=mov_work, t_start=t_start)
+        if want_mult:
+            out['mult'] = mult
+        return out
+
+    def nlp_solve_groups_moving(self, scen, W, h, n_ac, knots=None, disc=None, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0,
+                                mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0,
+                                bounds=None):
+        """nlp_solve_groups_pairs around moving discs (d2d_nlp_solve_groups_moving): knots dev [R][n_mov][n_knot][3] and disc dev
+        [R][n_mov][2] per SCENARIO -- all its aircraft see the same tracks -- and t_start dev [R] or a float (required when discs move
+        or with a field).  A scenario with an unusable track is refused like one with a malformed mask.  Returns
+        nlp_solve_groups_pairs's dict plus mov_work [R][n_mov][2][N]."""
+        torch = _torch()
+        B, _, N = W.shape
+        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
+        R = B // n_ac
+        m = self._moving_c(knots, disc, R)
+        t_start = self._t_start_dev(t_start, R, W)
+        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
+        mov_work = self.empty(R, m.n_mov, 2, N) if m.n_mov > 0 else None
+        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
+        f = None if field is None else _wind_c(self, field)
+        _check(self.lib.d2d_nlp_solve_groups_moving(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W),
+                                                    _ptr(work), None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps),
+                                                    _ptr(moved), None if f is None else C.byref(f), _ptr(t_start), C.byref(m), _ptr(mov_work)))
+        prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
+        return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev,
+                    mov_work=mov_work)
 
     def nlp_solve_model(self, scen, W, h, g, H, Wc, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
                         outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None):

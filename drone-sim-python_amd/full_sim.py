@@ -200,8 +200,21 @@ def _rows_select_pairs(scen_rows, n_ac):
     return bool((~np.isin(pm[:, 0], (0, 0b10))).any() or (~np.isin(pm[:, 1], (0, 0b01))).any() or (pm[:, 2:] != 0).any())
 
 
+def _moving_tables(ctx, moving, n_scen):
+    """Device tables (knots [n_scen][n_mov][n_knot][3], disc [n_scen][n_mov][2]) of `moving`: a list of d2d.opty_utils.MovingObstacle
+    that every scenario sees, or one such list per scenario (the same number of discs in each; an absent disc has r <= 0)."""
+    import d2d.opty_utils as d2ou
+    moving = list(moving)
+    per = [list(m) for m in moving] if moving and not isinstance(moving[0], d2ou.MovingObstacle) else [moving] * n_scen
+    if len(per) != n_scen or len({len(m) for m in per}) != 1:
+        raise ValueError(f'moving obstacles: one list for all scenarios or one list per scenario ({n_scen}) with the same number of discs')
+    n_knot = max(len(o.t) for m in per for o in m)
+    tabs = [d2ou.lower_moving(m, n_knot) for m in per]
+    return ctx.dev(np.stack([t[0] for t in tabs])), ctx.dev(np.stack([t[1] for t in tabs]))
+
+
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               **solve_kw):
+               moving=None, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -211,10 +224,15 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     planner's field, whose model adds it to the residual, so a plan for a plant that flies F takes -F -- with node i of scenario r at
     t_start[r] + i h (d2d_nlp_solve_groups_wind); t_start a float or a device tensor [B / n_ac]; the rows' wind columns are not read.
     Rows whose SC_PMASK name other partners than the pair (0, 1) (multi_opt_planner.scenario_rows for a cost with `pairs`) are solved
-    by d2d_nlp_solve_groups_pairs, with and without a field."""
+    by d2d_nlp_solve_groups_pairs, with and without a field.
+    moving (backend='nlp'): moving obstacles -- a list of d2d.opty_utils.MovingObstacle for all scenarios or one list per scenario --
+    that every aircraft plans around, node i of scenario r at t_start[r] + i h, with the rows' KOBS and S as their weight
+    (d2d_nlp_solve_groups_moving, with and without a field)."""
     import single_opt_planner as sop
     from d2d.wind import planner_wind
     fld = planner_wind(windfield)
+    if moving and backend != 'nlp':
+        raise NotImplementedError("the polynomial fit has no moving obstacles: plan_batch(backend='nlp', moving=...) plans around them")
     if fld is not None and backend != 'nlp':
         raise NotImplementedError("the polynomial fit has no wind field: plan_batch(backend='nlp', windfield=...) plans in one")
     ctx = d2dhip.default_context()
@@ -222,7 +240,10 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
         W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
         assert W.shape == (dsc.shape[0], 5, K) and h is not None
-        if _rows_select_pairs(scen_rows, int(n_ac)):        # partner sets other than the reference's pair (0, 1)
+        if moving:
+            knots, disc = _moving_tables(ctx, moving, dsc.shape[0] // int(n_ac))
+            out = ctx.nlp_solve_groups_moving(dsc, W, float(h), int(n_ac), knots, disc, fld, t_start, **solve_kw)
+        elif _rows_select_pairs(scen_rows, int(n_ac)):      # partner sets other than the reference's pair (0, 1)
             out = ctx.nlp_solve_groups_pairs(dsc, W, float(h), int(n_ac), fld, t_start, **solve_kw)
         elif fld is None:
             out = ctx.nlp_solve_groups(dsc, W, float(h), int(n_ac), **solve_kw)
@@ -238,7 +259,8 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
 
 
 def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_sim_end=200., w=(0., 0.), t_step=0.05,
-                          t_end_1=1000., X0=None, max_sweeps=250, record2=('X', 'U'), record3=('X', 'U'), windfield=None):
+                          t_end_1=1000., X0=None, max_sweeps=250, record2=('X', 'U'), record3=('X', 'U'), windfield=None,
+                          moving_obstacles=None):
     """The three phases of src/11_full_sim_case1.py main() (:406-478) for many independent formations, chained ON THE
     DEVICE: the circular-formation phase hands its final states to the planner as a device tensor, the planner's sampled
     plan is the tracking reference of phase 2 without leaving HBM, and phase 3 restarts from phase 2's final states.
@@ -266,7 +288,12 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     alive while the launches that read it are queued); plan['q'] is the fit's (the guess); the controllers keep the constant w.
     A scen.cost that selects its own collision pairs (CostComposit(col_pairs=...)): the fit couples those pairs (SC_PMASK) and the
     plan is the collocation problem over all of them (d2d_nlp_solve_groups_pairs), in -F or, without a field, in the rows' constant
-    wind; plan gains `pairs` and, without a field too, W, cost_fit, feas, status, iters, sweeps, moved."""
+    wind; plan gains `pairs` and, without a field too, W, cost_fit, feas, status, iters, sweeps, moved.
+    moving_obstacles: a list of d2d.opty_utils.MovingObstacle (or one list per formation) on the mission's clock.  Each formation's
+    transition is the collocation problem around them from that formation's own end-of-phase-1 time t2[r] (the device array above,
+    computed with or without a field), in -F or in the rows' constant wind (d2d_nlp_solve_groups_moving), from the fit's plan as the
+    guess; the weight is scen.cost's kobs.  plan gains the entries listed for a field, t_start included, and mov_work: the discs'
+    centres at the plan's nodes [n_form][n_mov][2][K]."""
     import multi_opt_planner as mop
     import d2d.opty_utils as d2ou
     F = plant_wind(windfield)
@@ -286,8 +313,10 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     rows[:, [d2dhip.SC_X1, d2dhip.SC_Y1, d2dhip.SC_PSI1]] = X2f.reshape(-1, 3)
     dsc = ctx.dev(rows)
     dsc[:, d2dhip.SC_X0], dsc[:, d2dhip.SC_Y0], dsc[:, d2dhip.SC_PSI0] = Xs1[0], Xs1[1], Xs1[2]
-    if F is not None:
+    moving = list(moving_obstacles or [])
+    if F is not None or moving:
         t2 = (torch.clamp(ph1['stop_row'], max=len(ph1['time'])) - 1).to(torch.float64) * float(t_step)      # dev [n_form]
+    if F is not None:
         t2d = t2.repeat_interleave(n_ac).contiguous()                                                       # dev [N]: per drone
         w0 = ctx.wind_sample(F, t2d, Xs1[:2].contiguous())         # (the rows store -w of the planner's wind: -(-F) = F)
         dsc[:, d2dhip.SC_WX], dsc[:, d2dhip.SC_WY] = w0[0], w0[1]
@@ -305,7 +334,18 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     kw = dict(w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v)
     kw2 = {}
     pairs = mop.scenario_pairs(scen, n_ac)                          # None: the reference's pair (0, 1), the chain as it was
-    if F is not None:                                               # the fit was the guess: the collocation problem in -F from t2
+    if moving:                                                      # the fit was the guess: the collocation problem around the discs from t2
+        Fp = None if F is None else F.negated()
+        Xs = Xs.contiguous().clone()
+        knots, disc = _moving_tables(ctx, moving, n_form)
+        sol = ctx.nlp_solve_groups_moving(dsc, Xs, float(dt2), n_ac, knots, disc, Fp, t2)
+        pl.update(cost_fit=cost, cost=sol['cost'], Xs=Xs, W=Xs, feas=sol['feas'], status=sol['status'], iters=sol['iters'],
+                  sweeps=sol['sweeps'], moved=sol['moved'], t_start=t2, mov_work=sol['mov_work'], moving=(knots, disc))
+        if F is not None:
+            pl['field'] = Fp
+            kw['wind'] = F
+            kw2 = dict(t_start=t2d)
+    elif F is not None:                                             # the fit was the guess: the collocation problem in -F from t2
         Fp = F.negated()
         Xs = Xs.contiguous().clone()
         if pairs is None:

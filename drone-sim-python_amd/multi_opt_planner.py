@@ -70,6 +70,7 @@ class Planner:
             raise NotImplementedError('the multi-aircraft planner takes a constant wind: a field that varies in space and time is planned '
                                       'one aircraft at a time (single_opt_planner.Planner, d2d_nlp_solve_wind); the joint problem and its '
                                       'CostCollision partner (d2d_nlp_solve_groups) have no field')
+        self.moving_obstacles = sop.check_moving(scen, self.backend)
         self.acs = d2mou.AircraftSet(n=len(scen.p0s))
         self.num_nodes, self.time_step, self.duration = d2ou.planner_timing(scen.t0, scen.t1, scen.hz)
         N, n = self.num_nodes, self.acs.nb_aicraft
@@ -83,7 +84,9 @@ class Planner:
         self._slice_v = [slice(o + i * N, o + (i + 1) * N, 1) for i in range(n)]
         # a cost plug-in without a lowering: the collocation problem with the host objective, unless the fit was asked for
         self._host_cost = self.backend != 'fit' and not sop.lowerable(scen.cost)
-        if initialize and (self.backend == 'nlp' or self._host_cost):
+        if self._host_cost and self.moving_obstacles:
+            raise NotImplementedError(sop.MOVING_HOST_COST)
+        if initialize and (self.backend == 'nlp' or self._host_cost or self.moving_obstacles):
             import itertools
             import opty.direct_collocation
 
@@ -170,9 +173,9 @@ class Planner:
         self.prob.add_option('tol', tol)
         self.prob.addOption('max_iter', max_iter)
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self.backend == 'nlp' or self._host_cost:
+        if self.backend == 'nlp' or self._host_cost or self.moving_obstacles:
             self.fit_q = self.fit_plan = self.fit_scen = self.fit_coefs = None
-            if self._host_cost:
+            if self._host_cost or self.moving_obstacles:
                 self.info['backend_used'] = 'nlp'
         else:
             sop.Planner._harden(self)      # backend='auto': a plan that overshoots a bound is re-planned by the collocation backend

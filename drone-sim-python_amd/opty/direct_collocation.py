@@ -27,7 +27,11 @@ pair alternates on the device (each turn a full solve against the partner's froz
 options['sweep_tol'] (1e-7 m) or options['max_sweeps'] (12): a fixed point of that alternation is a KKT point of the joint NLP.  A
 pair that has not settled is reported 'max_iter'.  A cost that selects its own pairs (CostCollision(pairs=) / CostComposit(col_pairs=))
 is lowered to a partner set per aircraft and solved by d2d_nlp_solve_groups_pairs: every aircraft with a partner takes turns against
-all of them.  info['min_separation']: per coupled pair, the smallest node-wise distance of the returned plan."""
+all of them.  info['min_separation']: per coupled pair, the smallest node-wise distance of the returned plan.
+Moving obstacles (the planner's `moving_obstacles`, d2d.opty_utils.MovingObstacle) are lowered to the side table of
+d2d_moving_obstacles and solved by d2d_nlp_solve_moving (one aircraft, with or without a field) or d2d_nlp_solve_groups_moving (all
+aircraft of the Problem see the same tracks), node i at t0 + i time_step; info['min_clearance']: per disc (per aircraft and disc for
+several aircraft) the smallest node-wise distance to the disc's rim."""
 import numpy as np
 
 import d2dhip
@@ -129,6 +133,7 @@ class Problem:
                 if planner is None and hasattr(o, 'num_nodes') and hasattr(o, 'obj_scale'):
                     planner = o
         self.cost, self.planner = cost, planner
+        self.moving = list(getattr(planner, 'moving_obstacles', None) or [])
         # a known plug-in behind a planner: its kernel ('lowered'); anything else: the host calls obj / obj_grad ('host')
         self.objective = 'host'
         if cost is not None and planner is not None:
@@ -213,6 +218,9 @@ class Problem:
 
     def solve(self, x0):
         if self.objective == 'host':
+            if self.moving:
+                import single_opt_planner as sop
+                raise NotImplementedError(sop.MOVING_HOST_COST)
             if self.field is not None:
                 raise NotImplementedError('a wind field that varies in space and time together with a host objective (a cost plug-in '
                                           'without a kernel, d2d_nlp_solve_model) is not supported: use one of the cost classes of '
@@ -246,7 +254,21 @@ class Problem:
         # alternates on the device (block Gauss-Seidel, d2d_nlp_solve_groups) until neither aircraft moves
         if not coupled:
             dsc[:, d2dhip.SC_KCOL] = 0.0
-        if self.field is not None:                # one aircraft in a field (the rows' NaN wind columns are not read)
+        multi = hasattr(self.planner, 'acs')
+        if self.moving:                           # the tracks travel beside the rows; node i at t_start + i time_step
+            import d2d.opty_utils as d2ou
+            knots, disc = d2ou.lower_moving(self.moving)
+            mv = dict(knots=ctx.dev(knots[None]), disc=ctx.dev(disc[None]), field=self.field, t_start=self.t_start, bounds=bnd, **kw)
+            if multi:
+                if coupled and self._pairs is None:       # the reference's pair (0, 1) as partner sets
+                    dsc[0, d2dhip.SC_PMASK], dsc[1, d2dhip.SC_PMASK] = 0b10, 0b01
+                out = ctx.nlp_solve_groups_moving(dsc, dW, self.time_step, n, max_sweeps=int(self.options.get('max_sweeps', 12)),
+                                                  tol=float(self.options.get('sweep_tol', 1e-7)), **mv)
+                sweeps, moved = int(out['sweeps'][0].item()), float(out['moved'][0].item())
+            else:
+                out = ctx.nlp_solve_moving(dsc, dW, self.time_step, **mv)
+                sweeps, moved = 0, 0.0
+        elif self.field is not None:              # one aircraft in a field (the rows' NaN wind columns are not read)
             out = ctx.nlp_solve_wind(dsc, dW, self.time_step, self.field, t_start=self.t_start, bounds=bnd, **kw)
             sweeps, moved = 0, 0.0
         else:
@@ -270,6 +292,12 @@ class Problem:
         if coupled:                               # per coupled pair: the smallest node-wise distance of the returned plan
             info['min_separation'] = {(i, j): float(np.hypot(Wh[i, 0] - Wh[j, 0], Wh[i, 1] - Wh[j, 1]).min())
                                       for i, j in (self._pairs if self._pairs is not None else [(0, 1)])}
+        if self.moving:                           # the device's cost carries the discs' terms; the plug-in's value does not
+            import d2d.opty_utils as d2ou
+            tn = self.t_start + np.arange(N) * self.time_step
+            mc = [d2ou.min_clearance(self.moving, tn, Wh[a, 0], Wh[a, 1]) for a in range(n)]
+            info['min_clearance'] = mc if multi else mc[0]
+            info['cost'] = float(out['cost'].sum().item())
         return sol, info
 
     # ---- host objective ------------------------------------------------------------------------------------------------------

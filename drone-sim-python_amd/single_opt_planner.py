@@ -25,6 +25,8 @@ seed = None
 #            calls its cost / cost_grad on the host (opty.direct_collocation, host objective): info['backend_used'] = 'nlp'.
 #            So does a wind that varies in space and time (exp.wind a d2d.wind.SplineWindField; d2d_nlp_solve_wind): the fit's speed
 #            and bank rows would depend on position through the field, and backend='fit' refuses it.
+#            So do moving obstacles (exp.moving_obstacles, a list of d2d.opty_utils.MovingObstacle; d2d_nlp_solve_moving): the fit's
+#            scenario row has no room for their tracks, and backend='fit' refuses them.
 BACKEND = 'auto'
 AUTO_TOL = 1e-6        # rad, m/s, m
 N_SEG = 6
@@ -45,6 +47,22 @@ def get_plan(K, duration, obj_scale_over_n, kv=5., kphi=1.):
     if key not in _plans:
         _plans[key] = d2dhip.FitPlan(ctx, N_SEG, K, duration, wref)
     return _plans[key]
+
+
+MOVING_HOST_COST = ('moving obstacles together with a host objective (a cost plug-in without a kernel, d2d_nlp_solve_model) are not '
+                    'supported: use one of the cost classes of d2d.opty_utils / d2d.multiopty_utils')
+
+
+def check_moving(exp, backend):
+    """The scenario's moving obstacles (exp.moving_obstacles, absent or empty: none) as a list, refused where they cannot be planned:
+    backend='fit', more discs than d2dhip.MAX_MOV, a track with more knots than d2dhip.MOV_MAX_KNOT."""
+    moving = list(getattr(exp, 'moving_obstacles', None) or [])
+    if moving and backend == 'fit':
+        raise NotImplementedError("backend='fit' cannot plan around moving obstacles: the fit's scenario row has no room for their "
+                                  "tracks and its kernels no registers for their terms.  backend='nlp' (or 'auto') solves the "
+                                  "collocation problem around them")
+    d2ou.lower_moving(moving)
+    return moving
 
 
 def lowerable(cost):
@@ -197,6 +215,7 @@ class Planner:
             raise NotImplementedError("backend='fit' cannot plan in a wind field that varies in space and time: the polynomial fit's "
                                       "speed and bank rows would depend on position through the field.  backend='nlp' (or 'auto') "
                                       "solves the collocation problem in the field")
+        self.moving_obstacles = check_moving(exp, self.backend)
         self.aircraft = d2ou.Aircraft()
         N = self.num_nodes
         self._slice_x, self._slice_y, self._slice_psi, self._slice_phi, self._slice_v = (
@@ -204,7 +223,9 @@ class Planner:
         self.obstacles = exp.obstacles
         # a cost plug-in without a lowering: the collocation problem with the host objective, unless the fit was asked for
         self._host_cost = self.backend != 'fit' and not lowerable(exp.cost)
-        if initialize and (self.backend == 'nlp' or self._host_cost or self.field is not None):
+        if self._host_cost and self.moving_obstacles:
+            raise NotImplementedError(MOVING_HOST_COST)
+        if initialize and (self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles):
             import opty.direct_collocation
             _g = self.aircraft
             t0, (x0, y0, psi0, phi0, v0) = exp.t0, exp.p0
@@ -302,7 +323,7 @@ class Planner:
         if initial_guess is None:
             initial_guess = self.get_initial_guess('tri')
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self._host_cost or self.field is not None:
+        if self._host_cost or self.field is not None or self.moving_obstacles:
             self.info['backend_used'] = 'nlp'
         elif self.backend != 'nlp':
             self._harden()

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 114
+#define D2D_VERSION 115
 
 /* error codes */
 #define D2D_OK 0
@@ -761,6 +761,55 @@ int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, co
 int d2d_nlp_solve_groups_pairs(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
                                double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
                                int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start);
+
+/* Moving obstacles of the collocation planner: CostObstacle discs whose centre is piecewise linear in time -- crossing traffic, a
+ * formation whose plan is committed, a no-fly disc that drifts.  A moving disc is a static disc of the row (D2D_SC_O0X ..) with the
+ * centre c(t_i) of the node's own time t_i = t_start + i h in place of (x, y): the same value, reference cost, gradient and
+ * Gauss-Newton block, weighted by the row's D2D_SC_KOBS and D2D_SC_S; its radius and kind are its own.  The tracks live in a side table
+ * (the scenario row is full): G = the number of problems (d2d_nlp_solve_moving) or of scenarios (d2d_nlp_solve_groups_moving: all
+ * aircraft of a scenario see the same tracks).  Centre at time t: linear between the two knots that bracket t, held at the first or
+ * last knot outside them.  Times are absolute, on the clock of t_start and of the wind field.  (version 115) */
+#define D2D_MAX_MOV 8            /* moving discs per problem / scenario */
+#define D2D_MOV_MAX_KNOT 32
+typedef struct {
+  int32_t n_mov;        /* 0 .. D2D_MAX_MOV */
+  int32_t n_knot;       /* 2 .. D2D_MOV_MAX_KNOT, the same for every track of the call */
+  const double *knots;  /* dev [G][n_mov][n_knot][3] = (t, x, y), t strictly increasing */
+  const double *disc;   /* dev [G][n_mov][2] = (r, kind); r <= 0: absent; kind 0 / 1: CostObstacle kind 0 / kind 1 (D2D_SC_OKIND) */
+} d2d_moving_obstacles;
+
+/* The centres of the moving discs at the node times: ctr dev [G][n_mov][2][N], disc m of problem g at node i = the track at
+ * t_start[g] + i h (one multiply-add, not accumulated); t_start dev [G].  This is the pass the two solve entries below run ahead of
+ * their solve; it is exported so that it can be tested on its own.  It does not validate the tracks (the solve kernels do).  mov NULL,
+ * n_mov or n_knot out of range, or a NULL table, ctr or t_start with n_mov > 0: D2D_EINVAL; n_mov = 0: nothing is written.
+ * Asynchronous on the context's stream. */
+int d2d_mov_sample(d2d_ctx *ctx, int G, int N, double h, const double *t_start, const d2d_moving_obstacles *mov, double *ctr);
+
+/* d2d_nlp_solve_wind around moving discs.  The arguments of d2d_nlp_solve_wind with three changes: t_start is a DEVICE array [B], one
+ * start time per problem; f may be NULL, meaning the rows' constant wind (D2D_SC_WX / D2D_SC_WY); mov are the tracks and mov_work
+ * B * n_mov * 2 * N doubles for the centre planes, which d2d_mov_sample's kernel fills on the context's stream ahead of the solve.
+ * The objective gains, per node and per disc with r > 0, the static disc's term of that disc's kind, summed in ascending disc index
+ * after the row's static discs.  t_start is required whenever n_mov > 0; with n_mov = 0, f and t_start go together (both NULL: the
+ * solve of d2d_nlp_solve, bit for bit; both set: that of d2d_nlp_solve_wind).  mov NULL, n_mov or n_knot out of range, or a NULL
+ * table or mov_work with n_mov > 0: D2D_EINVAL before anything is launched.
+ * The tracks are validated on the device, per problem, before its solve: a non-finite knot, knot times that do not increase strictly,
+ * a kind that is neither 0 nor 1 (absent discs included), or a start time that is not finite refuses THAT problem --
+ * D2D_ST_NONFINITE, cost = feas = NaN, iters = 0, its W untouched -- and the rest of the launch is solved.
+ * tests/nlp_moving_ref.py is the CPU statement.  Asynchronous on the context's stream. */
+int d2d_nlp_solve_moving(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
+                         double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
+                         const double *t_start, const d2d_moving_obstacles *mov, double *mov_work);
+
+/* d2d_nlp_solve_groups_pairs around moving discs: its arguments (masks in the rows, optional field), plus the tracks of each
+ * SCENARIO (G = R) and mov_work of R * n_mov * 2 * N doubles.  Every aircraft of scenario r adds the discs' terms at the node times
+ * t_start[r] + i h, in the uncoupled sweep and in every turn; the rules for f, t_start, mov and mov_work are those of
+ * d2d_nlp_solve_moving.  An unusable track, or a start time that is not finite, refuses all aircraft of that scenario exactly as a
+ * malformed mask does (sweeps = 0, moved = 0, W untouched).  With n_mov = 0, or every r <= 0, the results are those of
+ * d2d_nlp_solve_groups_pairs bit for bit.  Asynchronous on the context's stream. */
+int d2d_nlp_solve_groups_moving(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                                double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                                int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
+                                const d2d_moving_obstacles *mov, double *mov_work);
 
 #ifdef __cplusplus
 }

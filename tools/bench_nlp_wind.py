@@ -13,7 +13,12 @@ python tools/bench_nlp_wind.py pairs [R]   collision avoidance on every pair (d2
     of four-aircraft scenarios in constant wind, (i) the default pair through d2d_nlp_solve_groups, three repeats of the whole
     measurement (their spread is the noise band), (ii) the same rows with the masks of the pair (0, 1) through the new entry point,
     (iii) all six pairs; on the side-by-side layouts of tests/nlp_groups_wind_ref.py and on the crossing layouts of
-    tests/nlp_groups_pairs_ref.py.  Median of 5 timed launches after a warm-up, HIP events, one process."""
+    tests/nlp_groups_pairs_ref.py.  Median of 5 timed launches after a warm-up, HIP events, one process.
+python tools/bench_nlp_wind.py moving [B]  moving obstacles (d2d_nlp_solve_moving): B (default 4096) perturbed exp_14 at 121 nodes with 0,
+    1 and 4 moving discs against the SAME problems with the same number of static discs in the row through d2d_nlp_solve -- the
+    tracks stand still where the static discs are, so both entries solve the same problems and the ratio is the cost of the centre
+    planes and the rolled loop, not of the terms.  The two entries alternate, 1 warm-up + 5 timed launches each, HIP events, one
+    process; medians and the spread of each."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 'tests')):
@@ -132,7 +137,50 @@ def pairs_leg(R):
     ctx.close()
 
 
+def moving_leg(B):
+    import torch, d2dhip
+    import d2dhip as D
+    from d2dhip import synth
+    from d2d.opty_utils import MovingObstacle, lower_moving
+    ctx = d2dhip.Context(0)
+    rows0, W0, h = synth.nlp_problems(B)
+    rows0[:, D.SC_KOBS] = 1.0
+    mid = 0.5 * (rows0[:, [D.SC_X0, D.SC_Y0]] + rows0[:, [D.SC_X1, D.SC_Y1]])
+    offs = np.array([(4.0, -3.0), (-18.0, 14.0), (22.0, 10.0), (-6.0, -24.0)])      # disc centres relative to the middle of the leg
+    radius = 7.0
+    for n_disc in (0, 1, 4):
+        rows_s = rows0.copy()
+        for i in range(n_disc):
+            c = D.obs_col(i)
+            rows_s[:, c:c + 2] = mid + offs[i]; rows_s[:, c + 2] = radius
+        kn = dc = None
+        if n_disc:
+            tabs = [lower_moving([MovingObstacle((0.0, 12.0), (mid[b] + offs[i], mid[b] + offs[i]), radius) for i in range(n_disc)]) for b in range(B)]
+            kn, dc = ctx.dev(np.stack([t[0] for t in tabs])), ctx.dev(np.stack([t[1] for t in tabs]))
+        dsc_s, dsc_m, t0 = ctx.dev(rows_s), ctx.dev(rows0), ctx.dev(np.zeros(B))
+        times = {'static': [], 'moving': []}
+        outs = {}
+        for rep in range(6):                                 # the first launch of each is the warm-up; the entries alternate
+            for what in ('static', 'moving'):
+                W = ctx.dev(np.ascontiguousarray(W0))
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                outs[what] = ctx.nlp_solve(dsc_s, W, h) if what == 'static' else ctx.nlp_solve_moving(dsc_m, W, h, kn, dc, None, t0 if n_disc else None)
+                e1.record(); torch.cuda.synchronize()
+                times[what].append(e0.elapsed_time(e1) * 1e-3)
+        med = {k: float(np.median(v[1:])) for k, v in times.items()}
+        for what in ('static', 'moving'):
+            st = outs[what]['status'].cpu().numpy(); it = outs[what]['iters'].cpu().numpy()
+            print(json.dumps({'leg': 'moving', 'B': B, 'nodes': W0.shape[2], 'discs': n_disc, 'entry': what, 'seconds_median': med[what],
+                              'seconds_min': min(times[what][1:]), 'seconds_max': max(times[what][1:]), 'problems_per_s': B / med[what],
+                              'moving_over_static': med['moving'] / med['static'], 'converged_frac': float((st == 1).mean()),
+                              'mean_newton_steps': float(it.mean())}), flush=True)
+    ctx.close()
+
+
 def main():
+    if sys.argv[1:2] == ['moving']:
+        return moving_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['pairs']:
         return pairs_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024)
     if sys.argv[1:2] == ['groups']:
