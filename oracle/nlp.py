@@ -285,7 +285,7 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
     log barrier (parameter mub, duals zL / zU), both driven by ONE outer loop; the inner problem is solved by damped
     Newton steps on the block-tridiagonal system (Lagrangian Hessian + barrier diagonal), fraction-to-the-boundary
     rule and a backtracking line search on the barrier-AL merit function.
-    Returns W, info (cost, feas, outer, inner, status, mult)."""
+    Returns W, info (cost, feas, outer, inner, status, mult, path)."""
     fixed, hasL, hasU = _barrier_sets(pb)
     free = ~fixed
     W = np.asarray(W0, float).copy()
@@ -304,6 +304,7 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
     total_inner = 0
     status = 2
     n_stalled = 0
+    path = []                       # per accepted step: its length, the largest |dW| it made, eightfold raises of its damping, halvings of its length
     if pb.bank_max:                 # the value test of the max mode needs a window of its own length (include/d2d.h D2D_NLP_BANKMAX_BATCHES)
         inner_max, outer_max = BANKMAX_BATCHES * inner_max, (outer_max + BANKMAX_BATCHES - 1) // BANKMAX_BATCHES
     for outer in range(1, outer_max + 1):
@@ -329,14 +330,15 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
             if phi_first is None:
                 phi_first = phi_last = phi0
             accepted = False
+            raised = 0
             for _ in range(30):
                 try:
                     dw = _solve_block_tridiag(Dh, E, 0.5 * rhs, free, lam)
                 except np.linalg.LinAlgError:
-                    lam = min(lam * 8.0, LAM_MAX); continue
+                    lam = min(lam * 8.0, LAM_MAX); raised += 1; continue
                 dphi = -float(np.sum(rhs * dw))                  # directional derivative of the merit function (< 0: descent)
                 if not dphi < 0.0:
-                    lam = min(lam * 8.0, LAM_MAX); continue
+                    lam = min(lam * 8.0, LAM_MAX); raised += 1; continue
                 # fraction to the boundary
                 tau = max(0.99, 1.0 - mub)
                 with np.errstate(divide='ignore', invalid='ignore'):
@@ -359,6 +361,7 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
                         azL = np.where(hasL & (dzL < 0), -tau * zL / dzL, np.inf)
                         azU = np.where(hasU & (dzU < 0), -tau * zU / dzU, np.inf)
                     az = min(1.0, float(azL.min()), float(azU.min()))
+                    path.append((a, float(np.abs(Wt - W).max()), raised, _ls))
                     W = Wt
                     phi_last = pt
                     zL = zL + az * dzL; zU = zU + az * dzU
@@ -402,7 +405,7 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
         feas_prev = feas
         mub = max(MUB_MIN, min(0.2 * mub, mub ** 1.5))
     return W, dict(cost=cost(pb, W), feas=float(np.abs(constraints(pb, W)).max()), outer=outer, inner=total_inner, status=status,
-                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU)
+                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU, path=path)
 
 
 def _apply(D, E, s):

@@ -56,14 +56,14 @@ def solve_groups(pbs, W0s, inner, max_sweeps=12, tol=1e-7):
     return Ws, infos, sweep, moved
 
 
-def in_field(field, t_start):
+def in_field(field, t_start, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX):
     """inner solver of solve_groups: nlp_wind_ref.solve in `field`, node 0 at t_start."""
-    return lambda a, pb, W0: R.solve(R.FieldProblem(pb, field, t_start), W0)
+    return lambda a, pb, W0: R.solve(R.FieldProblem(pb, field, t_start), W0, inner_max=inner_max, outer_max=outer_max)
 
 
-def in_constant_wind():
+def in_constant_wind(inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX):
     """inner solver of solve_groups: oracle.nlp.solve in each Problem's own constant wind."""
-    return lambda a, pb, W0: nlp.solve(pb, W0)
+    return lambda a, pb, W0: nlp.solve(pb, W0, inner_max=inner_max, outer_max=outer_max)
 
 
 def group_rows(p0s, p1s, wind=(0.0, 0.0)):

@@ -65,15 +65,16 @@ def straight_guess(r, N=N_NODES):
     return W
 
 
-def solve(pb, W0, field=None, t_start=0.0):
-    """oracle.nlp.solve in pb's constant wind, or nlp_wind_ref.solve in `field` with node 0 at t_start."""
-    return nlp.solve(pb, W0) if field is None else R.solve(R.FieldProblem(pb, field, t_start), W0)
+def solve(pb, W0, field=None, t_start=0.0, **kw):
+    """oracle.nlp.solve in pb's constant wind, or nlp_wind_ref.solve in `field` with node 0 at t_start; kw goes to the solver."""
+    return nlp.solve(pb, W0, **kw) if field is None else R.solve(R.FieldProblem(pb, field, t_start), W0, **kw)
 
 
-def solve_groups(rows, moving, W0s, field=None, t_start=0.0, max_sweeps=P.MAX_SWEEPS, N=N_NODES, h=H):
-    """One scenario of len(rows) aircraft with the partner sets of the rows' SC_PMASK, every aircraft around the same moving discs."""
+def solve_groups(rows, moving, W0s, field=None, t_start=0.0, max_sweeps=P.MAX_SWEEPS, N=N_NODES, h=H, **kw):
+    """One scenario of len(rows) aircraft with the partner sets of the rows' SC_PMASK, every aircraft around the same moving discs;
+    kw (inner_max, outer_max) goes to every solve."""
     pbs = [with_moving(nlp.problem_from_row(r, N, h), moving, t_start) for r in rows]
-    inner = P.in_constant_wind() if field is None else P.in_field(field, t_start)
+    inner = P.in_constant_wind(**kw) if field is None else P.in_field(field, t_start, **kw)
     return P.solve_groups(pbs, W0s, inner, P.masks_of(rows), max_sweeps=max_sweeps)
 
 

@@ -13,7 +13,9 @@ F.derivatives: the numpy twin of the kernel's wind_eval2):
   kkt_residual       the multipliers act on (x, y) of their own node through (I/h + J)^T
 
 Everything that does not touch the wind is oracle/nlp.py's own code: the objective and its gradient, the banded solve, the barrier
-sets, the constants.  solve() below is oracle.nlp.solve line for line with these three functions in place of its own.
+sets, the constants.  solve() below is oracle.nlp.solve line for line with these three functions in place of its own; it reaches
+them through the problem object, so that another statement of the same solver (tests/nlp_model_ref.py) supplies its own without a
+copy of the loop.
 """
 import numpy as np
 
@@ -32,6 +34,20 @@ class FieldProblem:
     def jet(self, W):
         """w (2, N), J (2, 2, N), H (2, 3, N) of the field at the nodes."""
         return self.field.derivatives(self.t, W[:, 0], W[:, 1])
+
+    # what solve() asks of a problem object: the places that see the wind (below), and the value it reports.  Another statement of
+    # the same solver (tests/nlp_model_ref.py) is a class with these four methods and `pb`.
+    def constraints(self, W):
+        return constraints(self, W)
+
+    def normal_equations(self, W, mu, rho):
+        return _normal_equations(self, W, mu, rho)
+
+    def merit(self, W, mu, rho, mub, hasL, hasU):
+        return _merit(self, W, mu, rho, mub, hasL, hasU)
+
+    def cost(self, W):
+        return nlp.cost(self.pb, W)
 
 
 def constraints(fp, W):
@@ -108,7 +124,10 @@ def _merit(fp, W, mu, rho, mub, hasL, hasU):
 
 
 def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX, feas_tol=nlp.FEAS_TOL, opt_tol=nlp.OPT_TOL):
-    """oracle.nlp.solve in the field.  Returns W, info (cost, feas, outer, inner, status, rho, mult, zL, zU)."""
+    """oracle.nlp.solve in the field.  fp: a FieldProblem, or any object with `pb` and its four methods constraints,
+    normal_equations, merit and cost.  Returns W, info (cost, feas, outer, inner, status, rho, mult, zL, zU, path).  path holds, per
+    accepted Newton step, its length a, the largest |dW| it made, the number of times its damping was raised eightfold and the number
+    of halvings of its line search."""
     pb = fp.pb
     fixed, hasL, hasU = nlp._barrier_sets(pb)
     free = ~fixed
@@ -127,6 +146,7 @@ def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MA
     total_inner = 0
     status = 2
     n_stalled = 0
+    path = []
     if pb.bank_max:
         inner_max, outer_max = nlp.BANKMAX_BATCHES * inner_max, (outer_max + nlp.BANKMAX_BATCHES - 1) // nlp.BANKMAX_BATCHES
     for outer in range(1, outer_max + 1):
@@ -135,7 +155,7 @@ def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MA
         for it in range(inner_max):
             total_inner += 1
             sl = np.where(hasL, W - pb.lo, 1.0); su = np.where(hasU, pb.hi - W, 1.0)
-            g, D, E = _normal_equations(fp, W, mu, rho)
+            g, D, E = fp.normal_equations(W, mu, rho)
             stat = np.where(free, 2.0 * g - zL + zU, 0.0)
             comp = max(float(np.abs(np.where(hasL, zL * sl - mub, 0.0)).max()), float(np.abs(np.where(hasU, zU * su - mub, 0.0)).max()))
             err = max(float(np.abs(stat).max()), comp)
@@ -146,18 +166,19 @@ def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MA
             Dh = D.copy()
             idx = np.arange(NV)
             Dh[:, idx, idx] += 0.5 * sig
-            phi0 = _merit(fp, W, mu, rho, mub, hasL, hasU)
+            phi0 = fp.merit(W, mu, rho, mub, hasL, hasU)
             if phi_first is None:
                 phi_first = phi_last = phi0
             accepted = False
+            raised = 0
             for _ in range(30):
                 try:
                     dw = nlp._solve_block_tridiag(Dh, E, 0.5 * rhs, free, lam)
                 except np.linalg.LinAlgError:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); continue
+                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
                 dphi = -float(np.sum(rhs * dw))
                 if not dphi < 0.0:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); continue
+                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
                 tau = max(0.99, 1.0 - mub)
                 with np.errstate(divide='ignore', invalid='ignore'):
                     aL = np.where(hasL & (dw < 0), -tau * sl / dw, np.inf)
@@ -167,7 +188,7 @@ def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MA
                 ok = False
                 for _ls in range(8):
                     Wt = W + a * dw
-                    pt = _merit(fp, Wt, mu, rho, mub, hasL, hasU)
+                    pt = fp.merit(Wt, mu, rho, mub, hasL, hasU)
                     if np.isfinite(pt) and pt <= phi0 + 1e-4 * a * dphi:
                         ok = True
                         break
@@ -179,6 +200,7 @@ def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MA
                         azL = np.where(hasL & (dzL < 0), -tau * zL / dzL, np.inf)
                         azU = np.where(hasU & (dzU < 0), -tau * zU / dzU, np.inf)
                     az = min(1.0, float(azL.min()), float(azU.min()))
+                    path.append((a, float(np.abs(Wt - W).max()), raised, _ls))
                     W = Wt
                     phi_last = pt
                     zL = zL + az * dzL; zU = zU + az * dzU
@@ -191,7 +213,7 @@ def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MA
                 lam = min(lam * 4.0, nlp.LAM_MAX)
             if not accepted:
                 break
-        c = constraints(fp, W)
+        c = fp.constraints(W)
         feas = float(np.abs(c).max())
         if feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and err <= tol_in:
             status = 1
@@ -211,8 +233,8 @@ def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MA
             mu = mu / nlp.RHO_GROW; rho *= nlp.RHO_GROW
         feas_prev = feas
         mub = max(nlp.MUB_MIN, min(0.2 * mub, mub ** 1.5))
-    return W, dict(cost=nlp.cost(pb, W), feas=float(np.abs(constraints(fp, W)).max()), outer=outer, inner=total_inner, status=status,
-                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU)
+    return W, dict(cost=fp.cost(W), feas=float(np.abs(fp.constraints(W)).max()), outer=outer, inner=total_inner, status=status,
+                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU, path=path)
 
 
 def kkt_residual(fp, W, mult, zL=None, zU=None):

@@ -6,6 +6,7 @@
 import numpy as np
 import pytest
 
+from nlp_steps_ref import scenario_row as _row
 from oracle import nlp, costs as C
 
 pytestmark = pytest.mark.gpu
@@ -17,25 +18,6 @@ def ctx():
     c = d2dhip.Context(0)
     yield c
     c.close()
-
-
-def _row(pb, obstacles=(), kobs=0.0, okind=0):
-    """d2dhip scenario row of an oracle Problem."""
-    import d2dhip as D
-    r = np.zeros(D.SCEN_STRIDE)
-    r[D.SC_X0:D.SC_X0 + 3] = pb.p0; r[D.SC_X1:D.SC_X1 + 3] = pb.p1
-    r[D.SC_VSP], r[D.SC_KV], r[D.SC_KPHI], r[D.SC_S], r[D.SC_KOBS] = pb.vsp, pb.kv, pb.kphi, pb.s, kobs
-    r[D.SC_WX], r[D.SC_WY] = -pb.wind[0], -pb.wind[1]
-    r[D.SC_PHIMAX] = pb.hi[1, 3]; r[D.SC_VMIN], r[D.SC_VMAX] = pb.lo[1, 4], pb.hi[1, 4]
-    if np.isfinite(pb.lo[1, 0]):
-        r[D.SC_XMIN], r[D.SC_XMAX] = pb.lo[1, 0], pb.hi[1, 0]
-    if np.isfinite(pb.lo[1, 1]):
-        r[D.SC_YMIN], r[D.SC_YMAX] = pb.lo[1, 1], pb.hi[1, 1]
-    for i, o in enumerate(obstacles):
-        c = D.obs_col(i)
-        r[c:c + 3] = o
-    r[D.SC_OKIND] = okind
-    return r
 
 
 def _solve(ctx, pbs, W0s, rows, **kw):
