@@ -215,7 +215,14 @@ struct NlpProb {
 struct NlpMovProb : NlpProb {
   NlpMovSet mv;
 };
-template <bool MOV> using NlpProbT = std::conditional_t<MOV, NlpMovProb, NlpProb>;
+// VIA instantiations (d2d_nlp_solve_via, d2d_nlp_solve_groups_via): the problem with the fixed set of its nodes.  vm [N], bits 0..2 of
+// vm[i] = x, y, psi of node i are fixed variables: 7 at both ends (the end conditions), the pins of the via table in between.  The
+// start pass of nlp_solve_one writes the plane; every pass that asks nlp_fixed elsewhere reads vm[i] with the node's values.
+struct NlpViaProb : NlpMovProb {
+  const int32_t *vm;
+};
+template <bool MOV, bool VIA = false> using NlpProbT = std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>;
+template <bool VIA> using NlpProbV = std::conditional_t<VIA, NlpViaProb, NlpProb>;       // for the passes that read no disc
 template <bool MOV> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const NlpProbT<MOV> &pb) {
   if constexpr (MOV) return &pb.mv;
   else return nullptr;
@@ -282,11 +289,22 @@ __device__ __forceinline__ void nlp_constraint(const NlpScen &s, double h, const
 }
 
 __device__ __forceinline__ bool nlp_fixed(int i, int N, int c) { return c < 3 && (i == 0 || i == N - 1); }
+// VIA: the node's mask m = vm[i] answers instead (nlp_via_mask: 0 in the other instantiations, where it is not read)
+template <bool VIA>
+__device__ __forceinline__ bool nlp_fixed_at(int i, int N, int c, int m) {
+  if constexpr (VIA) return c < 3 && ((m >> c) & 1) != 0;
+  else return nlp_fixed(i, N, c);
+}
+template <bool VIA, typename PB>
+__device__ __forceinline__ int nlp_via_mask(const PB &pb, int i) {
+  if constexpr (VIA) return pb.vm[i];
+  else return 0;
+}
 
 // Merit function of the inner problem at W + a*dw: objective + rho sum (c + mu)^2 - mub sum log(slacks); +inf outside the box.
 // Node-parallel (lane = node, chunks of 64) + wave reductions.  All results are wave-uniform.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false>
-__device__ double nlp_merit(const NlpProbT<MOV> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false>
+__device__ double nlp_merit(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
                             double mub, double *cost_ref_out, double *feas_out, const NlpModel &md) {
   const int N = pb.N;
   double val = 0.0, bar = 0.0, cref = 0.0, feas = 0.0, phi2max = 0.0;
@@ -302,6 +320,7 @@ __device__ double nlp_merit(const NlpProbT<MOV> &pb, const NlpScen &s, const dou
       for (int c = 0; c < NLP_NV; ++c) { w[c] = NLP_W(c, i); dwl[c] = NLP_DW(c, i); }
 #pragma unroll
       for (int c = 0; c < 3; ++c) { wp[c] = NLP_W(c, im); dwp[c] = NLP_DW(c, im); muv[c] = NLP_MU(c, i); }
+      [[maybe_unused]] const int vmi = nlp_via_mask<VIA>(pb, i);
       if (a != 0.0) {
 #pragma unroll
         for (int c = 0; c < NLP_NV; ++c) w[c] += a * dwl[c];
@@ -312,7 +331,7 @@ __device__ double nlp_merit(const NlpProbT<MOV> &pb, const NlpScen &s, const dou
       double prod = 1.0;
 #pragma unroll
       for (int c = 0; c < NLP_NV; ++c) {
-        if (nlp_fixed(i, N, c)) continue;
+        if (nlp_fixed_at<VIA>(i, N, c, vmi)) continue;
         if (s.lo[c] > -1e299) { const double sl = w[c] - s.lo[c]; if (!(sl > 0.0)) outside = 1; prod *= (sl > 0.0 ? sl : 1.0); }
         if (s.hi[c] < 1e299) { const double su = s.hi[c] - w[c]; if (!(su > 0.0)) outside = 1; prod *= (su > 0.0 ? su : 1.0); }
       }
@@ -394,8 +413,10 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // WIND (d2d_nlp_solve_wind): the constraint that ends at node i reads the field at (t_i, x_i, y_i): with J = d(wx, wy)/d(x, y) there,
 // Ac gains J on its (x, y) columns and D the constraint curvature rho (c + mu)_0 Hess(wx) + rho (c + mu)_1 Hess(wy) on its (x, y)
 // block; node i+1's constraint sees node i through -1/h only, so the has_next terms and the structure of E do not change.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false>
-__device__ double nlp_assemble(const NlpProbT<MOV> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
+// VIA: the rows and columns of a pinned component are the identity with right-hand side 0, as at the ends, and the columns of E_i that
+// belong to pinned components of node i-1 are zero (at the ends: all of E_1) -- before the elimination, so Rt carries none of them.
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false>
+__device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
                                double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md) {
   const int N = pb.N;
   const double h = pb.h, ih = 1.0 / h;
@@ -422,6 +443,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV> &pb, const NlpScen &s, const 
     for (int c = 0; c < NLP_NV; ++c) { wc[c] = NLP_W(c, i); wn[c] = NLP_W(c, ip); zlv[c] = NLP_P(WS_ZL + c, i); zuv[c] = NLP_P(WS_ZU + c, i); }
 #pragma unroll
     for (int c = 0; c < 3; ++c) { wp[c] = NLP_W(c, im); mu_c[c] = NLP_MU(c, i); mu_n[c] = NLP_MU(c, ip); }
+    [[maybe_unused]] const int vmi = nlp_via_mask<VIA>(pb, i), vmp = nlp_via_mask<VIA>(pb, im);
     if (i < 1) { wp[0] = 0.0; wp[1] = 0.0; wp[2] = 0.0; }
     // WIND: the field at this node -- value, Jacobian, second derivatives in one pass -- for every live lane; the value at the
     // NEXT node, which cn needs, comes from the neighbouring lane (NLP_WIND_NEXT_SHUFFLE, the default) or from a second, value-only
@@ -536,7 +558,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV> &pb, const NlpScen &s, const 
     // barrier terms, stationarity / complementarity error, right-hand side
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) {
-      const bool fx = nlp_fixed(i, N, c);
+      const bool fx = nlp_fixed_at<VIA>(i, N, c, vmi);
       double sig = 0.0, r = -2.0 * g[c], st = 2.0 * g[c];
       if (!fx && s.lo[c] > -1e299) {
         const double sl = wc[c] - s.lo[c], z = zlv[c], isl = 1.0 / sl;
@@ -561,6 +583,15 @@ __device__ double nlp_assemble(const NlpProbT<MOV> &pb, const NlpScen &s, const 
         for (int k = 0; k < 3; ++k) E[c][k] = 0.0;
       }
     }
+    if constexpr (VIA) {                        // columns of E that belong to the fixed variables of node i-1 (node 0: E is zero)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        if ((vmp >> k) & 1) {
+#pragma unroll
+          for (int a = 0; a < NLP_NV; ++a) E[a][k] = 0.0;
+        }
+      }
+    } else
     if (i == 1) {                               // columns of E that belong to the fixed variables of node 0
 #pragma unroll
       for (int a = 0; a < NLP_NV; ++a) { E[a][0] = 0.0; E[a][1] = 0.0; E[a][2] = 0.0; }
@@ -1032,17 +1063,26 @@ __device__ __attribute__((noinline)) bool nlp_factor(double *sin_generic, double
 }
 
 // Serial recursion 2, from the middle outwards in both halves: ds_m = L_m^-T y_m;  ds_i = L_i^-T (y_i - Lon^T dn).
-__device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, double *mid_generic, double *ds_generic, int N) {
+// VIA: vm the fixed set of the nodes; a node's mask travels in the ring with its factor record, and the middle node can be pinned too.
+typedef __attribute__((address_space(1))) int32_t gint32;
+template <bool VIA = false>
+__device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, double *mid_generic, double *ds_generic, int N,
+                                                        const int32_t *vm_generic = nullptr) {
   const gdouble *sf = (const gdouble *)sf_generic;
+  [[maybe_unused]] const gint32 *vm = (const gint32 *)vm_generic;
   const gdouble *mid = (const gdouble *)mid_generic;
   gdouble *dsv = (gdouble *)ds_generic;
   const bool up = (threadIdx.x & 32) != 0;
   const int m = N >> 1, nlo = m, cnt = up ? N - 1 - m : m;
   auto node_of = [&](int k) { const int kk = k < cnt ? k : cnt - 1; return up ? m + 1 + kk : m - 1 - kk; };
-  auto load = [&](int k, NlpNodeIn &n) {
+  NlpNodeIn buf[4];
+  [[maybe_unused]] int mk[4] = {0, 0, 0, 0};
+  auto load = [&](int k, int slot) {                        // slot: the ring position, a compile-time value at every call
+    NlpNodeIn &n = buf[slot];
     const gdouble *p = sf + (long)node_of(k) * SF_N;
 #pragma unroll
     for (int q = 0; q < SF_N; ++q) n.v[q] = p[q];
+    if constexpr (VIA) mk[slot] = vm[node_of(k)];
   };
   auto subst = [&](const double *v, const double (&t)[3], double (&ds)[3]) {       // ds = L^-T t (v: the node's factor record)
 #pragma unroll
@@ -1053,8 +1093,7 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
       ds[a] = x * v[SF_L + a * (a + 1) / 2 + a];
     }
   };
-  NlpNodeIn buf[4];
-  load(0, buf[0]); load(1, buf[1]); load(2, buf[2]);
+  load(0, 0); load(1, 1); load(2, 2);
   double dn[3], Lon[3][3];
   {
     NlpNodeIn md;
@@ -1066,11 +1105,16 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
     for (int a = 0; a < 3; ++a)
 #pragma unroll
       for (int c = 0; c < 3; ++c) Lon[a][c] = pc[a * 3 + c];
+    [[maybe_unused]] int mm = 0;
+    if constexpr (VIA) mm = vm[m];
     __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0)
     double t[3] = {md.v[SF_Y], md.v[SF_Y + 1], md.v[SF_Y + 2]};
     subst(md.v, t, dn);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) dsv[(long)m * 3 + c] = dn[c];
+    for (int c = 0; c < 3; ++c) {
+      if constexpr (VIA) { if ((mm >> c) & 1) dn[c] = 0.0; }
+      dsv[(long)m * 3 + c] = dn[c];
+    }
   }
   __builtin_amdgcn_s_waitcnt(0x0F70);
   for (int k0 = 0; k0 < nlo; k0 += 4) {
@@ -1078,7 +1122,7 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
    for (int u = 0; u < 4; ++u) {
     const int k = k0 + u;
     if (k >= nlo) break;
-    load(k + 3, buf[(u + 3) & 3]);
+    load(k + 3, (u + 3) & 3);
     const NlpNodeIn &cur = buf[u];
     if (k < cnt) {
       const int i = up ? m + 1 + k : m - 1 - k;
@@ -1089,6 +1133,8 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
       const bool fx = i == 0 || i == N - 1;                 // end conditions: fixed variables
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
+        if constexpr (VIA) { if ((mk[u] >> c) & 1) ds[c] = 0.0; }
+        else
         if (fx) ds[c] = 0.0;
         dn[c] = ds[c];
         dsv[(long)i * 3 + c] = ds[c];
@@ -1105,7 +1151,8 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
 // Recovery of the eliminated (phi, v) steps + step statistics (node-parallel): d(phi, v)_i = LP^-T (tt - Qt ds_i - Rt ds_{i-1});
 // directional derivative of the merit function, largest primal step (fraction to the boundary) and the dual steps' largest
 // fraction.  Wave-uniform results.
-__device__ void nlp_recover_stats(const NlpProb &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
+template <bool VIA = false>
+__device__ void nlp_recover_stats(const NlpProbV<VIA> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
                                   double *amax_out, double *az_out) {
   const int N = pb.N;
   double dphi = 0.0, amax = 1.0, az = 1.0;
@@ -1125,6 +1172,7 @@ __device__ void nlp_recover_stats(const NlpProb &pb, const NlpScen &s, int lane,
     for (int k = 0; k < 3; ++k) ellp[k] = NLP_EL(EL_LP + k, i);
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) { wv[c] = NLP_W(c, i); rhv[c] = NLP_RHS(c, i); zlv[c] = NLP_P(WS_ZL + c, i); zuv[c] = NLP_P(WS_ZU + c, i); }
+    [[maybe_unused]] const int vmi = nlp_via_mask<VIA>(pb, i);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       z0 -= elq[k] * dwv[k] + elr[k] * dsp[k];
@@ -1137,7 +1185,7 @@ __device__ void nlp_recover_stats(const NlpProb &pb, const NlpScen &s, int lane,
       const double dw = dwv[c];
       NLP_DW(c, i) = dw;
       dphi -= rhv[c] * dw;
-      if (nlp_fixed(i, N, c)) continue;
+      if (nlp_fixed_at<VIA>(i, N, c, vmi)) continue;
       const double w = wv[c];
       if (s.lo[c] > -1e299) {
         const double sl = w - s.lo[c], z = zlv[c];
@@ -1157,7 +1205,8 @@ __device__ void nlp_recover_stats(const NlpProb &pb, const NlpScen &s, int lane,
 }
 
 // Take the step (node-parallel): W += a dw, duals += az dz (dz from the step's dw), duals kept near the central path.
-__device__ void nlp_apply(const NlpProb &pb, const NlpScen &s, int lane, double a, double az, double mub) {
+template <bool VIA = false>
+__device__ void nlp_apply(const NlpProbV<VIA> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
   const int N = pb.N;
   for (int i0 = 0; i0 < N; i0 += 64) {
     const int i = i0 + lane;
@@ -1166,9 +1215,10 @@ __device__ void nlp_apply(const NlpProb &pb, const NlpScen &s, int lane, double 
     double wv[NLP_NV], dwl[NLP_NV], zlv[NLP_NV], zuv[NLP_NV];
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) { wv[c] = NLP_W(c, i); dwl[c] = NLP_DW(c, i); zlv[c] = NLP_P(WS_ZL + c, i); zuv[c] = NLP_P(WS_ZU + c, i); }
+    [[maybe_unused]] const int vmi = nlp_via_mask<VIA>(pb, i);
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) {
-      if (nlp_fixed(i, N, c)) continue;
+      if (nlp_fixed_at<VIA>(i, N, c, vmi)) continue;
       const double w = wv[c], dw = dwl[c];
       const double wn = w + a * dw;
       NLP_W(c, i) = wn;
@@ -1190,18 +1240,57 @@ __device__ void nlp_apply(const NlpProb &pb, const NlpScen &s, int lane, double 
 
 struct NlpOut { double cost, feas; int iters, status; };
 
+// VIA: the pins of one problem -- pts [n][5] = (node, mask, x, y, psi) of d2d_via_points, a row with mask 0 absent -- and vm [N], the
+// plane of the nodes' fixed sets that the start pass fills from them.
+struct NlpViaSet {
+  const double *pts;
+  int32_t *vm;
+  int n;
+};
+// The pins of a problem, checked before its solve, one row per lane (n <= D2D_MAX_VIA): a mask that is no integer in 1 .. 7, a node
+// that is no integer in 1 .. N-2, a pinned value that is not finite or lies outside the problem's box (the row's, d2d_nlp_opts.bounds
+// for psi), or a (node, component) that an earlier row pins already.  Wave-uniform.
+__device__ __forceinline__ bool nlp_via_bad(const double *__restrict__ pts, int n, int N, const double *__restrict__ sc, const d2d_nlp_opts &o,
+                                            const double *__restrict__ bnd, int lane) {
+  const NlpScen s = nlp_load_scen(sc, o, bnd);
+  int bad = 0;
+  if (lane < n) {
+    const double fn = pts[5 * lane], fm = pts[5 * lane + 1];
+    if (fm != 0.0) {
+      if (!(fm >= 1.0 && fm <= 7.0) || fm != floor(fm) || !(fn >= 1.0 && fn <= (double)(N - 2)) || fn != floor(fn)) {
+        bad = 1;
+      } else {
+        const int m = (int)fm;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double v = pts[5 * lane + 2 + c];
+          if ((m >> c) & 1) bad |= !(fabs(v) <= 1.79e308) || v < s.lo[c] || v > s.hi[c];
+        }
+        for (int e = 0; e < lane; ++e) {
+          const double qm = pts[5 * e + 1];
+          if (pts[5 * e] == fn && qm >= 1.0 && qm <= 7.0 && ((int)qm & m) != 0) bad = 1;
+        }
+      }
+    }
+  }
+  return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
+}
+
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
 // MODEL: the objective is the quadratic model md (d2d_nlp_solve_model) on top of the row's structured terms; cost = its value.
 // WIND: the equalities read the field wf at node i's own (t_start + i h, x_i, y_i) instead of the row's constant (d2d_nlp_solve_wind).
 // PAIRS: partner is the scenario's W and pmask this aircraft's partner set (nlp_exp_terms); pmask = 0: no partner.
 // MOV: mv the problem's moving discs (nlp_exp_terms), their centre planes sampled at this problem's node times.
-template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false>
+// VIA: via the problem's pins, checked by the caller (nlp_via_bad): a pinned component starts at its value and stays there -- no duals,
+// no barrier, no step, an identity row in the Newton system -- exactly as x, y, psi of the two end nodes do.  The terms of the objective
+// still count at a pinned node.
+template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
                                               const double *__restrict__ bnd, const NlpModel &md = NlpModel{nullptr, nullptr, nullptr},
                                               const d2d_wind_field *wf = nullptr, double t_start = 0.0, unsigned pmask = 0u,
-                                              const NlpMovSet *mv = nullptr) {
+                                              const NlpMovSet *mv = nullptr, const NlpViaSet *via = nullptr) {
   // diagnostics (D2D_NLP_STAMPS): cycles per phase -- merit, assembly, factorisation, back substitution, ratio tests, update
   unsigned long long st_t = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define NLP_STAMP(k) if (st_on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t; st_t = t_; }
@@ -1209,8 +1298,9 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   if (st_on) st_t = __builtin_amdgcn_s_memtime();
   NlpScen s = nlp_load_scen(sc, o, bnd);
   if (sc[D2D_SC_BANKMAX] != 0.0) { s.sbank = s.skphi * (double)N; s.skphi = 0.0; }     // obj_scale * kbank (the row's S is obj_scale / N)
-  NlpProbT<MOV> pb;
+  NlpProbT<MOV, VIA> pb;
   if constexpr (MOV) pb.mv = *mv;
+  if constexpr (VIA) pb.vm = via->vm;
   pb.N = N; pb.h = h;
   pb.W = Wb;
   pb.ws = wsb;
@@ -1244,11 +1334,29 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   for (int i0 = 0; i0 < N; i0 += 64) {
     const int i = i0 + lane;
     if (i >= N) continue;
+    [[maybe_unused]] int vmi = 0;
+    [[maybe_unused]] double pin[3] = {0.0, 0.0, 0.0};
+    if constexpr (VIA) {                     // the node's fixed set and pinned values: the table's rows that name it (wave-uniform loads)
+      if (i == 0 || i == N - 1) vmi = 7;
+#pragma clang loop unroll(disable)
+      for (int e = 0; e < via->n; ++e) {
+        const double *__restrict__ p = via->pts + 5 * e;
+        const int m = (int)p[1];
+        if (m == 0 || (int)p[0] != i) continue;
+        vmi |= m;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          if ((m >> c) & 1) pin[c] = p[2 + c];
+      }
+      via->vm[i] = vmi;
+    }
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) {
       double w = NLP_W(c, i);
       double zl = 0.0, zu = 0.0;
-      if (nlp_fixed(i, N, c)) {
+      if (nlp_fixed_at<VIA>(i, N, c, vmi)) {
+        if constexpr (VIA) w = (i == 0) ? s.p0[c] : (i == N - 1 ? s.p1[c] : pin[c]);
+        else
         w = (i == 0) ? s.p0[c] : s.p1[c];
       } else {
         const bool hl = s.lo[c] > -1e299, hu = s.hi[c] < 1e299;
@@ -1280,7 +1388,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     const double tol_in = fmax(fmax(o.opt_tol, fmin(1e-1, 10.0 * mub)), D2D_NLP_GRAD_FLOOR * rho);
     // merit value of the current point for this (mub, rho, mu): one pass here, afterwards the accepted trial's value
     NLP_STAMP(7)
-    double phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    double phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1291,7 +1399,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       const int imax = s.sbank > 0.0 ? nlp_bank_argmax(pb, lane) : -1;
       for (int tr = 0; tr < 30; ++tr) {
         bool pd;
-        err = nlp_assemble<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -1302,26 +1410,28 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         NLP_STAMP(2)
         if (!pd) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
         nlp_phase_sync();
+        if constexpr (VIA) { if (o.serial) nlp_backsolve<true>(pb.ws + (size_t)WS_SF * N, pb.ws + (size_t)WS_UP * N, pb.ws + (size_t)WS_DS * N, N, pb.vm); }
+        else
         if (o.serial) nlp_backsolve(pb.ws + (size_t)WS_SF * N, pb.ws + (size_t)WS_UP * N, pb.ws + (size_t)WS_DS * N, N);
         nlp_phase_sync();
         NLP_STAMP(3)
         const double tau = fmax(0.99, 1.0 - mub);
         double dphi, amax, az;
-        nlp_recover_stats(pb, s, lane, mub, tau, &dphi, &amax, &az);
+        nlp_recover_stats<VIA>(pb, s, lane, mub, tau, &dphi, &amax, &az);
         nlp_phase_sync();
         NLP_STAMP(4)
         if (!(dphi < 0.0)) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
         double a = amax, pt = 0.0;
         bool ok = false;
         for (int ls = 0; ls < 8; ++ls) {
-          pt = nlp_merit<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
+          pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
         NLP_STAMP(0)
         if (ok) {
           phi0 = pt;
-          nlp_apply(pb, s, lane, a, az, mub);
+          nlp_apply<VIA>(pb, s, lane, a, az, mub);
           nlp_phase_sync();
           NLP_STAMP(5)
           if (a == amax) lam = fmax(lam / 3.0, D2D_LM_LAMBDA_MIN);
@@ -1332,7 +1442,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       }
       if (converged || !accepted) break;
     }
-    (void)nlp_merit<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -1371,7 +1481,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     feas_prev = feas;
     mub = fmax(o.mub_min, fmin(0.2 * mub, mub * sqrt(mub)));
   }
-  (void)nlp_merit<MODEL, WIND, PAIRS, MOV>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+  (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -1557,6 +1667,54 @@ nlp_solve_moving_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__
   }
 }
 
+// d2d_nlp_solve_via: nlp_solve_moving_kernel's hand-out around the VIA instantiations -- the problem's pins via.pts [B][n_via][5] and
+// the plane of its nodes' fixed sets vwork [B][N].  Unusable pins refuse the problem like an unusable track.  mv.n_mov = 0: nothing moves.
+template <bool WIND>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_via_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                     double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                     int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
+                     d2d_moving_obstacles mv, const double *ctr, d2d_via_points via, int32_t *vwork) {
+  const int lane = threadIdx.x;
+  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
+  double *wsb = work + (size_t)blockIdx.x * WS_TOTAL * N;
+  const int32_t *__restrict__ order = o.order;
+  for (int t = blockIdx.x; t < B;) {
+    const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
+    if ((unsigned)b >= (unsigned)B) {        // (an entry that is no problem index is skipped, not dereferenced)
+      t = nlp_next_ticket(queue, lane);
+      continue;
+    }
+    NlpOut out;
+    double t0 = 0.0;
+    bool bad = false;
+    if (WIND || mv.n_mov > 0) {
+      t0 = nlp_first_lane(t_start[b]);
+      bad = !(fabs(t0) <= 1.79e308);
+    }
+    if (mv.n_mov > 0) bad = bad || nlp_mov_bad(mv, b, lane);
+    const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE, *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
+    const NlpViaSet vs{via.pts + (size_t)b * via.n_via * 5, vwork + (size_t)b * N, via.n_via};
+    bad = bad || nlp_via_bad(vs.pts, vs.n, N, sc, o, bnd, lane);
+    if (bad) {
+      out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
+    } else {
+      const NlpMovSet ms{ctr + (size_t)b * mv.n_mov * 2 * N, mv.disc + (size_t)b * mv.n_mov * 2, mv.n_mov};
+      nlp_solve_one<false, WIND, false, true, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb,
+                                                    mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds, bnd,
+                                                    NlpModel{nullptr, nullptr, nullptr}, &wf, t0, 0u, &ms, &vs);
+    }
+    if (lane == 0) {
+      cost_out[b] = out.cost;
+      feas_out[b] = out.feas;
+      if (iters_out) iters_out[b] = out.iters;
+      if (status_out) status_out[b] = out.status;
+    }
+    nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
+    t = nlp_next_ticket(queue, lane);
+  }
+}
+
 // A scenario of the group loop is refused: all its aircraft at once, before the workgroup's first barrier (the caller returns).
 __device__ __forceinline__ void nlp_groups_refuse(int b, int r, int wave, int lane, double *cost_out, double *feas_out,
                                                   int32_t *iters_out, int32_t *status_out, int32_t *sweeps_out, double *moved_out) {
@@ -1617,17 +1775,21 @@ __device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
 // MOV (d2d_nlp_solve_groups_moving): every aircraft of scenario r solves around the scenario's moving discs, centre planes
 //   ctr [R][n_mov][2][N] sampled at t_start[r] + i h ahead of this launch.  The tracks are checked before the first solve, by every
 //   wavefront alike; an unusable track, or a start time that is not finite while discs move, refuses the scenario like a bad mask.
+// VIA (d2d_nlp_solve_groups_via): every AIRCRAFT has its own pins, via->pts [R n_ac][n_via][5], and its own plane vwork [R n_ac][N].  The
+//   pins of all aircraft of the scenario are checked before the first solve, by every wavefront alike: one unusable row refuses the
+//   scenario, as a bad mask does.  The partners' terms still count at a pinned node.
 // The pointer parameters of the body and of its two helpers carry no __restrict__ (the kernels' do): with it the fixed-pair kernel
 // went from 256 VGPRs / 624 B of scratch to 255 / 608 and the field kernel from 752 B to 784.
 // Registers: 512 threads per workgroup are 8 wavefronts on 4 SIMDs, two per SIMD, so a wavefront gets at most 256 of the SIMD's 512
 // registers whatever amdgpu_waves_per_eu says -- the workgroup size binds, and (2, 2) states what the hardware does.
-template <bool WIND, bool PAIRS, bool MOV = false>
+template <bool WIND, bool PAIRS, bool MOV = false, bool VIA = false>
 __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h, const d2d_nlp_opts &o, int max_sweeps, double tol,
                                                 const double *scen, double *W, double *work, double *mult, double *prev,
                                                 double *cost_out, double *feas_out, int32_t *iters_out,
                                                 int32_t *status_out, int32_t *sweeps_out, double *moved_out,
                                                 const d2d_wind_field *wf, const double *t_start,
-                                                const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr) {
+                                                const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr,
+                                                const d2d_via_points *via = nullptr, int32_t *vwork = nullptr) {
   __shared__ double moved_s[PAIRS ? 8 : 2];
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1666,6 +1828,16 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
     ms = NlpMovSet{ctr + (size_t)r * mv->n_mov * 2 * N, mv->disc + (size_t)r * mv->n_mov * 2, mv->n_mov};
     msp = &ms;
   }
+  [[maybe_unused]] NlpViaSet vs{nullptr, nullptr, 0};
+  const NlpViaSet *vsp = nullptr;
+  if constexpr (VIA) {
+    for (int a = 0; a < n_ac; ++a) {
+      const size_t ba = (size_t)r * n_ac + a;
+      bad = bad || nlp_via_bad(via->pts + ba * via->n_via * 5, via->n_via, N, scen + ba * D2D_SCEN_STRIDE, o, o.bounds ? o.bounds + ba * 4 : nullptr, lane);
+    }
+    vs = NlpViaSet{via->pts + (size_t)b * via->n_via * 5, vwork + (size_t)b * N, via->n_via};
+    vsp = &vs;
+  }
   if (bad) {                                 // (uniform over the workgroup: before the first barrier)
     nlp_groups_refuse(b, r, wave, lane, cost_out, feas_out, iters_out, status_out, sweeps_out, moved_out);
     return;
@@ -1683,6 +1855,8 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
   double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
   const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
   const NlpModel no_model{nullptr, nullptr, nullptr};
+  if constexpr (VIA) nlp_solve_one<false, WIND, PAIRS, MOV, true>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, 0u, msp, vsp);
+  else
   nlp_solve_one<false, WIND, PAIRS, MOV>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, 0u, msp);
   iters_total += out.iters;
   if (threadIdx.x < (PAIRS ? 8 : 2)) moved_s[threadIdx.x] = 0.0;
@@ -1700,6 +1874,8 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
           // fixed pair: the partner's x and y planes; PAIRS: the scenario's W and the set
           const double *pw = PAIRS ? Wr : W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;
           for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
+          if constexpr (VIA) nlp_solve_one<false, WIND, PAIRS, MOV, true>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, pmask, msp, vsp);
+          else
           nlp_solve_one<false, WIND, PAIRS, MOV>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, pmask, msp);
           iters_total += out.iters;
           double m = 0.0;
@@ -1770,6 +1946,18 @@ nlp_groups_moving_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int m
                          const double *__restrict__ ctr) {
   nlp_groups_body<WIND, true, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
                                     sweeps_out, moved_out, &wf, t_start, &mv, ctr);
+}
+
+// d2d_nlp_solve_groups_via: the pairs of the masks around the scenarios' moving discs, through every aircraft's own pins; WIND as above
+template <bool WIND>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
+nlp_groups_via_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                      double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                      int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                      double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start, d2d_moving_obstacles mv,
+                      const double *__restrict__ ctr, d2d_via_points via, int32_t *vwork) {
+  nlp_groups_body<WIND, true, true, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
+                                          sweeps_out, moved_out, &wf, t_start, &mv, ctr, &via, vwork);
 }
 
 // d2d_nlp_solve_model: the collocation NLP under the quadratic objective model of a cost that only the host can evaluate (a user's
@@ -1844,6 +2032,16 @@ static int check_moving(const d2d_moving_obstacles *mov, const double *work, con
   D2D_REQUIRE(mov->knots && mov->disc, "%s: null knots or disc table with n_mov = %d", who, mov->n_mov);
   D2D_REQUIRE(work, "%s: null array of centre planes with n_mov = %d", who, mov->n_mov);
   D2D_REQUIRE(t_start, "%s: null t_start with n_mov = %d (a device array: the tracks' times are absolute)", who, mov->n_mov);
+  return D2D_OK;
+}
+
+// a d2d_via_points argument of an entry point (include/d2d.h: what makes one D2D_EINVAL); work: the planes of the fixed sets
+static int check_via(const d2d_via_points *via, const int32_t *work, const char *who) {
+  D2D_REQUIRE(via, "%s: null via-point table (n_via = 0: no pins)", who);
+  D2D_REQUIRE(via->n_via >= 0 && via->n_via <= D2D_MAX_VIA, "%s: n_via = %d outside 0 .. %d", who, via->n_via, D2D_MAX_VIA);
+  if (via->n_via == 0) return D2D_OK;
+  D2D_REQUIRE(via->pts, "%s: null table with n_via = %d", who, via->n_via);
+  D2D_REQUIRE(work, "%s: null via_work with n_via = %d", who, via->n_via);
   return D2D_OK;
 }
 
@@ -2018,6 +2216,71 @@ int d2d_nlp_solve_groups_moving(d2d_ctx *ctx, int R, int n_ac, int N, double h, 
   else
     nlp_groups_launch(nlp_groups_moving_kernel<false>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
                       sweeps, moved, d2d_wind_field{}, t_start, *mov, (const double *)mov_work);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+int d2d_nlp_solve_via(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
+                      double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
+                      const double *t_start, const d2d_moving_obstacles *mov, double *mov_work, const d2d_via_points *via, int32_t *via_work) {
+  const d2d_moving_obstacles none{0, 0, nullptr, nullptr};
+  if (!mov) mov = &none;
+  if (int rc = check_via(via, via_work, "d2d_nlp_solve_via")) return rc;
+  if (via->n_via == 0)                                     // no pins: the solve of d2d_nlp_solve_moving, its kernels and its checks
+    return d2d_nlp_solve_moving(ctx, B, N, h, scen, opts, W, work, mult, cost, feas, iters, status, f, t_start, mov, mov_work);
+  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_via: null argument");
+  D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_via: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
+  if (int rc = check_moving(mov, mov_work, t_start, "d2d_nlp_solve_via")) return rc;
+  if (mov->n_mov == 0)
+    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_via: without moving discs f and t_start go together (both NULL: the rows' constant wind)");
+  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_via")) return rc; }
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_via", &o)) return rc;
+  if (mov->n_mov > 0) {
+    nlp_mov_sample_launch(ctx, B, N, h, t_start, *mov, mov_work);
+    D2D_LAUNCH_CHECK();
+  }
+  const int grid = nlp_handout_grid(B, o, NLP_WIND_WAVES_PER_SIMD);
+  int32_t *queue = ctx->counter_dev + 2;
+  D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
+  if (f)
+    hipLaunchKernelGGL(nlp_solve_via_kernel<true>, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work,
+                       mult, cost, feas, iters, status, queue, *f, t_start, *mov, (const double *)mov_work, *via, via_work);
+  else
+    hipLaunchKernelGGL(nlp_solve_via_kernel<false>, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work,
+                       mult, cost, feas, iters, status, queue, d2d_wind_field{}, t_start, *mov, (const double *)mov_work, *via, via_work);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+int d2d_nlp_solve_groups_via(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                             double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                             int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
+                             const d2d_moving_obstacles *mov, double *mov_work, const d2d_via_points *via, int32_t *via_work) {
+  const d2d_moving_obstacles none{0, 0, nullptr, nullptr};
+  if (!mov) mov = &none;
+  if (int rc = check_via(via, via_work, "d2d_nlp_solve_groups_via")) return rc;
+  if (via->n_via == 0)                                     // no pins: the solve of d2d_nlp_solve_groups_moving, its kernels and its checks
+    return d2d_nlp_solve_groups_moving(ctx, R, n_ac, N, h, scen, opts, max_sweeps, tol, W, work, mult, cost, feas, iters, status, sweeps, moved, f,
+                                       t_start, mov, mov_work);
+  if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_via")) return rc;
+  if (int rc = check_moving(mov, mov_work, t_start, "d2d_nlp_solve_groups_via")) return rc;
+  if (mov->n_mov == 0)
+    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_groups_via: without moving discs f and t_start go together (both NULL: the rows' constant wind)");
+  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_groups_via")) return rc; }
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_via", &o)) return rc;
+  if (mov->n_mov > 0) {
+    nlp_mov_sample_launch(ctx, R, N, h, t_start, *mov, mov_work);
+    D2D_LAUNCH_CHECK();
+  }
+  double *prev = nlp_groups_prev(work, R, n_ac, N);
+  if (f)
+    nlp_groups_launch(nlp_groups_via_kernel<true>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
+                      sweeps, moved, *f, t_start, *mov, (const double *)mov_work, *via, via_work);
+  else
+    nlp_groups_launch(nlp_groups_via_kernel<false>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
+                      sweeps, moved, d2d_wind_field{}, t_start, *mov, (const double *)mov_work, *via, via_work);
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }

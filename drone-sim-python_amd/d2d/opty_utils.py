@@ -322,3 +322,89 @@ def lower_moving(obstacles, n_knot=None):
 def min_clearance(obstacles, t, x, y):
     """Per moving obstacle: min_i |p_i - c(t_i)| - r over the nodes (t_i, x_i, y_i) of a plan."""
     return [float((np.hypot(*(np.stack([x, y], -1) - o.at(t)).T)).min() - o.r) for o in obstacles]
+
+
+class Waypoint:
+    """A timed waypoint of the collocation planner (include/d2d.h d2d_via_points): at time t -- absolute, on the clock of the scenario's
+    t0 -- the given ones of x, y, psi hold exactly; None leaves a component free.  The time must be that of an interior node of the
+    plan (lower_waypoints).  Scenarios list them in `waypoints`: one list for single_opt_planner, one list per aircraft for
+    multi_opt_planner."""
+
+    def __init__(self, t, x=None, y=None, psi=None):
+        self.t = float(t)
+        self.x, self.y, self.psi = (None if v is None else float(v) for v in (x, y, psi))
+        if self.x is None and self.y is None and self.psi is None:
+            raise ValueError('a waypoint pins at least one of x, y, psi')
+        if not np.isfinite([self.t] + [v for v in (self.x, self.y, self.psi) if v is not None]).all():
+            raise ValueError('waypoint: time and pinned values must be finite')
+
+    @property
+    def mask(self):
+        """bit 0 / 1 / 2: x / y / psi is pinned"""
+        return (self.x is not None) * 1 + (self.y is not None) * 2 + (self.psi is not None) * 4
+
+    def __repr__(self):
+        return f'Waypoint(t={self.t}, x={self.x}, y={self.y}, psi={self.psi})'
+
+
+def waypoint_node(t, t_start, h, N):
+    """The node of the time t on the grid t_start + k h, k = 0 .. N-1.  ValueError (naming the two nearest node times) when t is on
+    no node, and when it is on the first or last one: those carry the end conditions."""
+    k = int(round((t - t_start) / h))
+    if abs(t - (t_start + k * h)) > 1e-9 * max(1.0, abs(t)):
+        k0 = int(np.floor((t - t_start) / h))
+        raise ValueError(f'waypoint time {t} is not a node time: the nearest nodes are at {t_start + k0 * h} and {t_start + (k0 + 1) * h} '
+                         f'(t0 = {t_start}, time step {h})')
+    if k <= 0 or k >= N - 1:
+        if k == 0 or k == N - 1:
+            raise ValueError(f'waypoint time {t} is the {"first" if k == 0 else "last"} node: x, y, psi there are the end conditions (p0 / p1)')
+        raise ValueError(f'waypoint time {t} lies outside the plan [{t_start}, {t_start + (N - 1) * h}]')
+    return k
+
+
+def lower_waypoints(waypoints, t_start, h, N, n_via=None):
+    """The table of d2d_via_points for one problem: (n_via, 5) rows (node, mask, x, y, psi), a free component 0.  n_via: the call's row
+    count (default: the list's length); shorter lists are padded with rows of mask 0, which the kernels skip.  ValueError for a time
+    that is no interior node (waypoint_node), a (node, component) pinned twice, or more than d2dhip.MAX_VIA rows."""
+    import d2dhip
+    waypoints = list(waypoints or [])
+    n_via = len(waypoints) if n_via is None else int(n_via)
+    if len(waypoints) > d2dhip.MAX_VIA or n_via > d2dhip.MAX_VIA:
+        raise ValueError(f'at most {d2dhip.MAX_VIA} waypoints per problem ({max(len(waypoints), n_via)} asked for)')
+    if len(waypoints) > n_via:
+        raise ValueError(f'{len(waypoints)} waypoints do not fit {n_via} rows')
+    out = np.zeros((n_via, 5))
+    seen = {}
+    for e, w in enumerate(waypoints):
+        k = waypoint_node(w.t, t_start, h, N)
+        if seen.get(k, 0) & w.mask:
+            raise ValueError(f'two waypoints pin the same component at time {w.t} (node {k})')
+        seen[k] = seen.get(k, 0) | w.mask
+        out[e] = (k, w.mask, w.x or 0.0, w.y or 0.0, w.psi or 0.0)
+    return out
+
+
+def via_guess(p0, p1, waypoints, t_start, h, N, vref):
+    """Piecewise-linear guess through p0, the waypoints that pin both x and y (in time order) and p1 -> x, y, psi, phi, v: positions
+    linear in time on every leg, psi along the leg, phi = 0, v = vref."""
+    pts = [(0, float(p0[0]), float(p0[1]))]
+    for w in sorted(waypoints or [], key=lambda w: w.t):
+        if w.x is not None and w.y is not None:
+            pts.append((waypoint_node(w.t, t_start, h, N), w.x, w.y))
+    pts.append((N - 1, float(p1[0]), float(p1[1])))
+    kk, xx, yy = (np.array(v, dtype=np.float64) for v in zip(*pts))
+    i = np.arange(N, dtype=np.float64)
+    x, y = np.interp(i, kk, xx), np.interp(i, kk, yy)
+    leg = np.clip(np.searchsorted(kk, i, side='right') - 1, 0, len(kk) - 2)
+    psi = np.arctan2(yy[leg + 1] - yy[leg], xx[leg + 1] - xx[leg])
+    return x, y, psi, np.zeros(N), vref * np.ones(N)
+
+
+def waypoint_error(table, W):
+    """Largest |plan - pin| over the rows of a d2d_via_points table (n_via, 5) and a plan W (5, N)."""
+    err = 0.0
+    for node, mask, *val in np.asarray(table, dtype=np.float64):
+        for c in range(3):
+            if (int(mask) >> c) & 1:
+                err = max(err, abs(float(W[c][int(node)]) - val[c]))
+    return err

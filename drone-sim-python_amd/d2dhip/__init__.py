@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('D2D_LIB') or os.path.join(os.path.dirname(_HERE), 'li
 SCEN_STRIDE = 80
 MAX_OBS = 16
 MAX_MOV, MOV_MAX_KNOT = 8, 32          # include/d2d.h D2D_MAX_MOV / D2D_MOV_MAX_KNOT (tests compare)
+MAX_VIA = 16                           # include/d2d.h D2D_MAX_VIA
 (SC_X0, SC_Y0, SC_PSI0, SC_X1, SC_Y1, SC_PSI1, SC_VREF, SC_VSP, SC_KV, SC_KPHI, SC_KOBS, SC_S,
  SC_WWP, SC_WX, SC_WY, SC_GOLEFT, SC_O0X, SC_O0Y, SC_O0R, SC_O1X, SC_O1Y, SC_O1R, SC_WBND,
  SC_PHIMAX, SC_VMIN, SC_VMAX, SC_KCOL, SC_RCOL, SC_SCOL, SC_PMASK, SC_OKIND, SC_BANKMAX, SC_OEXT) = range(33)
@@ -75,6 +76,11 @@ class NlpModel(C.Structure):
 class MovingObstaclesC(C.Structure):
     """d2d_moving_obstacles (include/d2d.h): knots dev [G][n_mov][n_knot][3] = (t, x, y), disc dev [G][n_mov][2] = (r, kind)."""
     _fields_ = [('n_mov', C.c_int32), ('n_knot', C.c_int32), ('knots', C.c_void_p), ('disc', C.c_void_p)]
+
+
+class ViaPointsC(C.Structure):
+    """d2d_via_points (include/d2d.h): pts dev [G][n_via][5] = (node, mask, x, y, psi); mask bits 0..2 = x, y, psi pinned, 0 = absent."""
+    _fields_ = [('n_via', C.c_int32), ('pts', C.c_void_p)]
 
 
 class FitOpts(C.Structure):
@@ -156,6 +162,10 @@ _SIGS = {
                              + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P]),
     'd2d_nlp_solve_groups_moving': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
                                     + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P]),
+    'd2d_nlp_solve_via': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
+                          + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, C.POINTER(ViaPointsC), _P]),
+    'd2d_nlp_solve_groups_via': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
+                                 + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, C.POINTER(ViaPointsC), _P]),
     'd2d_fit_plan_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(_P)]),
     'd2d_fit_plan_create_ex': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(FitPlanOpts), C.POINTER(_P)]),
     'd2d_fit_opts_default': (C.c_int, [C.POINTER(FitOpts)]),
@@ -703,6 +713,84 @@ class Context:
         prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
         return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev,
                     mov_work=mov_work)
+
+    def _via_c(self, via, G):
+        """d2d_via_points over a device table [G][n_via][5] = (node, mask, x, y, psi), or None: no pins.  Shapes only -- the range of
+        n_via is the library's to check (D2D_EINVAL) and the rows' contents the kernels'."""
+        torch = _torch()
+        if via is None:
+            return ViaPointsC(0, None)
+        assert via.is_contiguous() and via.dtype == torch.float64 and via.device.type == 'cuda'
+        assert via.dim() == 3 and via.shape[0] == G and via.shape[2] == 5
+        return ViaPointsC(int(via.shape[1]), via.data_ptr())
+
+    def nlp_solve_via(self, scen, W, h, via, knots=None, disc=None, field=None, t_start=None, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9,
+                      opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None, slots=0,
+                      order=None):
+        """nlp_solve_moving through timed waypoints (d2d_nlp_solve_via): via dev [B][n_via][5] = (node, mask, x, y, psi) per problem,
+        mask bits 0..2 = x, y, psi of that node pinned, a row of mask 0 absent (None: no pins); the other arguments as nlp_solve_moving.
+        A problem with an unusable row (node outside 1 .. N-2, mask outside 0 .. 7, a non-finite or out-of-box value, a component pinned
+        twice) is refused on the device: status ST_NONFINITE, cost = feas = NaN, its W untouched.  The pinned components of the returned
+        W hold their values exactly.  Returns nlp_solve_moving's dict plus via_work int32 [B][N]: the fixed set of every node."""
+        torch = _torch()
+        B, _, N = W.shape
+        assert W.is_contiguous() and scen.shape[0] == B
+        m = self._moving_c(knots, disc, B)
+        v = self._via_c(via, B)
+        t_start = self._t_start_dev(t_start, B, W)
+        work = self.empty(self.lib.d2d_nlp_workspace_doubles(N) * B)
+        mov_work = self.empty(B, m.n_mov, 2, N) if m.n_mov > 0 else None
+        via_work = torch.zeros(B, N, dtype=torch.int32, device=self.device) if v.n_via > 0 else None
+        cost, feas = self.empty(B), self.empty(B)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        mult = self.zeros(B, 3, N) if want_mult else None
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        assert order is None or (order.is_contiguous() and tuple(order.shape) == (B,) and order.dtype == torch.int32)
+        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, int(slots), None if bounds is None else bounds.data_ptr(),
+                    None if order is None else order.data_ptr())
+        f = None if field is None else _wind_c(self, field)
+        _check(self.lib.d2d_nlp_solve_via(self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), _ptr(work), _ptr(mult), _ptr(cost),
+                                          _ptr(feas), _ptr(iters), _ptr(status), None if f is None else C.byref(f), _ptr(t_start),
+                                          C.byref(m), _ptr(mov_work), C.byref(v), _ptr(via_work)))
+        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work, mov_work=mov_work, t_start=t_start, via_work=via_work)
+        if want_mult:
+            out['mult'] = mult
+        return out
+
+    def nlp_solve_groups_via(self, scen, W, h, n_ac, via, knots=None, disc=None, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0,
+                             mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0,
+                             bounds=None, want_mult=False):
+        """nlp_solve_groups_moving through timed waypoints (d2d_nlp_solve_groups_via): via dev [R*n_ac][n_via][5], every AIRCRAFT its own
+        rows (None: no pins); knots / disc per scenario as before.  An unusable row of any aircraft refuses its whole scenario, like a
+        malformed mask.  Returns nlp_solve_groups_moving's dict plus via_work int32 [R*n_ac][N] and, with want_mult, mult [R*n_ac][3][N]:
+        the scaled multiplier estimates of every aircraft's last solve."""
+        torch = _torch()
+        B, _, N = W.shape
+        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
+        R = B // n_ac
+        m = self._moving_c(knots, disc, R)
+        v = self._via_c(via, B)
+        t_start = self._t_start_dev(t_start, R, W)
+        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
+        mov_work = self.empty(R, m.n_mov, 2, N) if m.n_mov > 0 else None
+        via_work = torch.zeros(B, N, dtype=torch.int32, device=self.device) if v.n_via > 0 else None
+        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
+        mult = self.zeros(B, 3, N) if want_mult else None
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
+        f = None if field is None else _wind_c(self, field)
+        _check(self.lib.d2d_nlp_solve_groups_via(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W),
+                                                 _ptr(work), _ptr(mult), _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps),
+                                                 _ptr(moved), None if f is None else C.byref(f), _ptr(t_start), C.byref(m), _ptr(mov_work),
+                                                 C.byref(v), _ptr(via_work)))
+        prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
+        out = dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev,
+                   mov_work=mov_work, via_work=via_work)
+        if want_mult:
+            out['mult'] = mult
+        return out
 
     def nlp_solve_model(self, scen, W, h, g, H, Wc, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
                         outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None):

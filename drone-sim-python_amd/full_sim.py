@@ -213,8 +213,34 @@ def _moving_tables(ctx, moving, n_scen):
     return ctx.dev(np.stack([t[0] for t in tabs])), ctx.dev(np.stack([t[1] for t in tabs]))
 
 
+def _plan_batch_via(ctx, scen_rows, dsc, W, N, h, n_ac, fld, t_start, moving, via, solve_kw):
+    """plan_batch's path through timed waypoints: the table of every problem on its scenario's clock, then d2d_nlp_solve_groups_via."""
+    import d2d.opty_utils as d2ou
+    B = dsc.shape[0]
+    R = B // n_ac
+    via = [list(v or []) for v in via]
+    if len(via) != B:
+        raise ValueError(f'via: one waypoint list per problem ({B})')
+    ts = t_start.cpu().numpy() if hasattr(t_start, 'cpu') else np.full(R, 0.0 if t_start is None else float(t_start))
+    n_via = max(1, max(len(v) for v in via))
+    table = np.stack([d2ou.lower_waypoints(v, float(ts[b // n_ac]), h, N, n_via) for b, v in enumerate(via)])
+    if n_ac >= 2 and not _rows_select_pairs(scen_rows, n_ac):       # the reference's pair (0, 1) as partner sets
+        on = (dsc[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc[1::n_ac, d2dhip.SC_KCOL] > 0)
+        dsc[0::n_ac, d2dhip.SC_PMASK] = on * 2.0
+        dsc[1::n_ac, d2dhip.SC_PMASK] = on * 1.0
+    knots, disc = _moving_tables(ctx, moving, R) if moving else (None, None)
+    if fld is None and not moving:
+        t_start = None
+    dvia = ctx.dev(table)
+    out = ctx.nlp_solve_groups_via(dsc, W, h, n_ac, dvia, knots, disc, fld, t_start, **solve_kw)
+    ctx.sync()
+    Wh = W.cpu().numpy()
+    out.update(via=dvia, waypoint_error=max(d2ou.waypoint_error(table[b], Wh[b]) for b in range(B)))
+    return out
+
+
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               moving=None, **solve_kw):
+               moving=None, via=None, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -227,12 +253,19 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     by d2d_nlp_solve_groups_pairs, with and without a field.
     moving (backend='nlp'): moving obstacles -- a list of d2d.opty_utils.MovingObstacle for all scenarios or one list per scenario --
     that every aircraft plans around, node i of scenario r at t_start[r] + i h, with the rows' KOBS and S as their weight
-    (d2d_nlp_solve_groups_moving, with and without a field)."""
+    (d2d_nlp_solve_groups_moving, with and without a field).
+    via (backend='nlp'): timed waypoints -- one list of d2d.opty_utils.Waypoint per PROBLEM (row of scen_rows; an empty list: no pin) --
+    on the clock of t_start, held exactly (d2d_nlp_solve_groups_via, with and without a field or moving obstacles); the result carries
+    via (the device table) and waypoint_error, the largest |plan - pin|: 0.0.  Like moving=, via= goes through the group entry
+    for every n_ac: with n_ac = 1 that is one workgroup with one wavefront per problem, each with its own workspace, not the persistent
+    hand-out of d2d_nlp_solve_via -- for large batches of single aircraft call Context.nlp_solve_via (the difference is not measured)."""
     import single_opt_planner as sop
     from d2d.wind import planner_wind
     fld = planner_wind(windfield)
     if moving and backend != 'nlp':
         raise NotImplementedError("the polynomial fit has no moving obstacles: plan_batch(backend='nlp', moving=...) plans around them")
+    if via is not None and backend != 'nlp':
+        raise NotImplementedError("the polynomial fit has no timed waypoints: plan_batch(backend='nlp', via=...) plans through them")
     if fld is not None and backend != 'nlp':
         raise NotImplementedError("the polynomial fit has no wind field: plan_batch(backend='nlp', windfield=...) plans in one")
     ctx = d2dhip.default_context()
@@ -240,7 +273,9 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
         W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
         assert W.shape == (dsc.shape[0], 5, K) and h is not None
-        if moving:
+        if via is not None:
+            out = _plan_batch_via(ctx, scen_rows, dsc, W, K, float(h), int(n_ac), fld, t_start, moving, via, solve_kw)
+        elif moving:
             knots, disc = _moving_tables(ctx, moving, dsc.shape[0] // int(n_ac))
             out = ctx.nlp_solve_groups_moving(dsc, W, float(h), int(n_ac), knots, disc, fld, t_start, **solve_kw)
         elif _rows_select_pairs(scen_rows, int(n_ac)):      # partner sets other than the reference's pair (0, 1)

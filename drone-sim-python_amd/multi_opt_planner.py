@@ -71,6 +71,8 @@ class Planner:
                                       'one aircraft at a time (single_opt_planner.Planner, d2d_nlp_solve_wind); the joint problem and its '
                                       'CostCollision partner (d2d_nlp_solve_groups) have no field')
         self.moving_obstacles = sop.check_moving(scen, self.backend)
+        self.waypoints = sop.check_waypoints(scen, self.backend, len(scen.p0s))       # one list per aircraft
+        self._has_via = any(self.waypoints)
         self.acs = d2mou.AircraftSet(n=len(scen.p0s))
         self.num_nodes, self.time_step, self.duration = d2ou.planner_timing(scen.t0, scen.t1, scen.hz)
         N, n = self.num_nodes, self.acs.nb_aicraft
@@ -86,13 +88,16 @@ class Planner:
         self._host_cost = self.backend != 'fit' and not sop.lowerable(scen.cost)
         if self._host_cost and self.moving_obstacles:
             raise NotImplementedError(sop.MOVING_HOST_COST)
-        if initialize and (self.backend == 'nlp' or self._host_cost or self.moving_obstacles):
+        if self._host_cost and self._has_via:
+            raise NotImplementedError(sop.VIA_HOST_COST)
+        if initialize and (self.backend == 'nlp' or self._host_cost or self.moving_obstacles or self._has_via):
             import itertools
             import opty.direct_collocation
 
             def ic(_ac, _p, _t): return (_ac._sx(_t) - _p[0], _ac._sy(_t) - _p[1], _ac._spsi(_t) - _p[2])
             cons = [ic(_ac, _p, scen.t0) for _ac, _p in zip(self.acs.aircraft, scen.p0s)]
             cons += [ic(_ac, _p, scen.t1) for _ac, _p in zip(self.acs.aircraft, scen.p1s)]
+            cons += [sop.waypoint_constraints(_ac, _w) for _ac, _w in zip(self.acs.aircraft, self.waypoints)]
             self._instance_constraints = tuple(itertools.chain(*cons))
             self._bounds = {}
             for _ac in self.acs.aircraft:
@@ -124,6 +129,12 @@ class Planner:
                 g[self._slice_psi[i]] = rng.uniform(-np.pi, np.pi, N)
                 g[self._slice_phi[i]] = rng.uniform(self.scen.phi_constraint[0], self.scen.phi_constraint[1], N)
                 g[self._slice_v[i]] = rng.uniform(self.scen.v_constraint[0], self.scen.v_constraint[1], N)
+        elif what == 'via':
+            self.initial_guesses = [d2ou.via_guess(p0, p1, w, self.scen.t0, self.time_step, N, self.scen.vref)
+                                    for p0, p1, w in zip(self.scen.p0s, self.scen.p1s, self.waypoints)]
+            for i, ig in enumerate(self.initial_guesses):
+                (g[self._slice_x[i]], g[self._slice_y[i]], g[self._slice_psi[i]], g[self._slice_phi[i]],
+                 g[self._slice_v[i]]) = ig
         else:
             self.initial_guesses = [d2ou.triangle(np.array(p0)[:2], np.array(p1)[:2], self.scen.vref, self.duration, N, go_left=-1.)
                                     for p0, p1 in zip(self.scen.p0s, self.scen.p1s)]
@@ -169,13 +180,13 @@ class Planner:
 
     def run(self, initial_guess=None, tol=1e-8, max_iter=500):
         if initial_guess is None:
-            initial_guess = self.get_initial_guess('tri')
+            initial_guess = self.get_initial_guess('via' if self._has_via else 'tri')
         self.prob.add_option('tol', tol)
         self.prob.addOption('max_iter', max_iter)
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self.backend == 'nlp' or self._host_cost or self.moving_obstacles:
+        if self.backend == 'nlp' or self._host_cost or self.moving_obstacles or self._has_via:
             self.fit_q = self.fit_plan = self.fit_scen = self.fit_coefs = None
-            if self._host_cost or self.moving_obstacles:
+            if self._host_cost or self.moving_obstacles or self._has_via:
                 self.info['backend_used'] = 'nlp'
         else:
             sop.Planner._harden(self)      # backend='auto': a plan that overshoots a bound is re-planned by the collocation backend

@@ -10,7 +10,9 @@ What is interpreted instead of compiled:
   * eom / state_symbols  -- the fixed kinematic model of d2d.opty_utils.Aircraft.get_eom (an `Eom`: wind, g, aircraft count).  A wind
                             that varies in space and time (eom.field, a d2d.wind.SplineWindField: what its sample_sym put into the
                             equations) is solved by d2d_nlp_solve_wind: one aircraft, lowered objective; node i at t0 + i time_step;
-  * instance_constraints -- `x(t) - value` objects: the end conditions of every aircraft;
+  * instance_constraints -- `x(t) - value` objects: at the smallest and the largest time the end conditions of every aircraft (x, y, psi
+                            each); at any time in between a timed waypoint of that aircraft (Problem.waypoints, d2d.opty_utils.Waypoint),
+                            which must lie on a node and is held exactly (d2d_nlp_solve_via / d2d_nlp_solve_groups_via);
   * bounds               -- {phi(t): (lo, hi), v(t): ..., x(t): ..., y(t): ..., psi(t): ...}: HARD boxes (primal-dual barrier); the phi
                             interval need not be symmetric (d2d_nlp_opts.bounds carries it and the psi box to the kernel);
   * obj / obj_grad       -- the reference passes closures over a cost plug-in and the planner
@@ -146,19 +148,32 @@ class Problem:
         # end conditions per aircraft from the instance constraints: names x<i>, y<i>, psi<i>
         ids = [str(s.sym.name)[1:] for s in state_symbols[0::3]]
         t_all = sorted({c.t for c in instance_constraints})
-        if len(t_all) != 2:
-            raise NotImplementedError('instance constraints at exactly two times (t0 and t1) are supported')
+        if len(t_all) < 2:
+            raise NotImplementedError('instance constraints at two times at least (t0 and t1: the end conditions) are required')
         self.t_start = float(t_all[0])                  # node i is at t_start + i time_step (what a field is sampled at)
         self.p0s = np.zeros((self.n_aircraft, 3)); self.p1s = np.zeros((self.n_aircraft, 3))
         seen = set()
+        pins = [{} for _ in range(self.n_aircraft)]     # per aircraft: time -> {component name: value}
         for c in instance_constraints:
             for k, nm in enumerate(('x', 'y', 'psi')):
                 for a, i in enumerate(ids):
                     if c.name == nm + i:
-                        (self.p0s if c.t == t_all[0] else self.p1s)[a, k] = c.value
-                        seen.add((a, k, c.t == t_all[0]))
+                        if c.t in (t_all[0], t_all[-1]):
+                            (self.p0s if c.t == t_all[0] else self.p1s)[a, k] = c.value
+                            seen.add((a, k, c.t == t_all[0]))
+                        elif nm in pins[a].setdefault(float(c.t), {}):
+                            raise ValueError(f'{c.name} is fixed twice at t = {c.t}')
+                        else:
+                            pins[a][float(c.t)][nm] = float(c.value)
         if len(seen) != 6 * self.n_aircraft:
             raise NotImplementedError('every aircraft needs x, y, psi fixed at t0 and t1 (src/single_opt_planner.py:46-49)')
+        # every other time: pins of that aircraft, which must lie on interior nodes (ValueError otherwise)
+        import d2d.opty_utils as d2ou
+        self.waypoints = [[d2ou.Waypoint(t, **pa[t]) for t in sorted(pa)] for pa in pins]
+        self.via = None                                 # (n_aircraft, n_via, 5): the table of d2d_via_points
+        if any(self.waypoints):
+            n_via = max(len(w) for w in self.waypoints)
+            self.via = np.stack([d2ou.lower_waypoints(w, self.t_start, self.time_step, self.num_nodes, n_via) for w in self.waypoints])
         # bounds per aircraft
         self.bounds = [{} for _ in range(self.n_aircraft)]
         for key, (lo, hi) in (bounds or {}).items():
@@ -221,6 +236,9 @@ class Problem:
             if self.moving:
                 import single_opt_planner as sop
                 raise NotImplementedError(sop.MOVING_HOST_COST)
+            if self.via is not None:
+                import single_opt_planner as sop
+                raise NotImplementedError(sop.VIA_HOST_COST)
             if self.field is not None:
                 raise NotImplementedError('a wind field that varies in space and time together with a host objective (a cost plug-in '
                                           'without a kernel, d2d_nlp_solve_model) is not supported: use one of the cost classes of '
@@ -255,11 +273,22 @@ class Problem:
         if not coupled:
             dsc[:, d2dhip.SC_KCOL] = 0.0
         multi = hasattr(self.planner, 'acs')
-        if self.moving:                           # the tracks travel beside the rows; node i at t_start + i time_step
+        if self.moving or self.via is not None:   # the tracks and the pins travel beside the rows; node i at t_start + i time_step
             import d2d.opty_utils as d2ou
-            knots, disc = d2ou.lower_moving(self.moving)
-            mv = dict(knots=ctx.dev(knots[None]), disc=ctx.dev(disc[None]), field=self.field, t_start=self.t_start, bounds=bnd, **kw)
-            if multi:
+            mv = dict(field=self.field, t_start=self.t_start if (self.moving or self.field is not None) else None, bounds=bnd, **kw)
+            if self.moving:
+                knots, disc = d2ou.lower_moving(self.moving)
+                mv.update(knots=ctx.dev(knots[None]), disc=ctx.dev(disc[None]))
+            if self.via is not None and multi:
+                if coupled and self._pairs is None:       # the reference's pair (0, 1) as partner sets
+                    dsc[0, d2dhip.SC_PMASK], dsc[1, d2dhip.SC_PMASK] = 0b10, 0b01
+                out = ctx.nlp_solve_groups_via(dsc, dW, self.time_step, n, ctx.dev(self.via), max_sweeps=int(self.options.get('max_sweeps', 12)),
+                                               tol=float(self.options.get('sweep_tol', 1e-7)), **mv)
+                sweeps, moved = int(out['sweeps'][0].item()), float(out['moved'][0].item())
+            elif self.via is not None:
+                out = ctx.nlp_solve_via(dsc, dW, self.time_step, ctx.dev(self.via), **mv)
+                sweeps, moved = 0, 0.0
+            elif multi:
                 if coupled and self._pairs is None:       # the reference's pair (0, 1) as partner sets
                     dsc[0, d2dhip.SC_PMASK], dsc[1, d2dhip.SC_PMASK] = 0b10, 0b01
                 out = ctx.nlp_solve_groups_moving(dsc, dW, self.time_step, n, max_sweeps=int(self.options.get('max_sweeps', 12)),
@@ -298,6 +327,9 @@ class Problem:
             mc = [d2ou.min_clearance(self.moving, tn, Wh[a, 0], Wh[a, 1]) for a in range(n)]
             info['min_clearance'] = mc if multi else mc[0]
             info['cost'] = float(out['cost'].sum().item())
+        if self.via is not None:                  # 0.0 by construction: a pinned component never leaves its value
+            import d2d.opty_utils as d2ou
+            info['waypoint_error'] = max(d2ou.waypoint_error(self.via[a], Wh[a]) for a in range(n))
         return sol, info
 
     # ---- host objective ------------------------------------------------------------------------------------------------------

@@ -27,6 +27,8 @@ seed = None
 #            and bank rows would depend on position through the field, and backend='fit' refuses it.
 #            So do moving obstacles (exp.moving_obstacles, a list of d2d.opty_utils.MovingObstacle; d2d_nlp_solve_moving): the fit's
 #            scenario row has no room for their tracks, and backend='fit' refuses them.
+#            So do timed waypoints (exp.waypoints, a list of d2d.opty_utils.Waypoint; d2d_nlp_solve_via): the fit has no interior
+#            conditions, and backend='fit' refuses them.
 BACKEND = 'auto'
 AUTO_TOL = 1e-6        # rad, m/s, m
 N_SEG = 6
@@ -51,6 +53,43 @@ def get_plan(K, duration, obj_scale_over_n, kv=5., kphi=1.):
 
 MOVING_HOST_COST = ('moving obstacles together with a host objective (a cost plug-in without a kernel, d2d_nlp_solve_model) are not '
                     'supported: use one of the cost classes of d2d.opty_utils / d2d.multiopty_utils')
+
+
+VIA_HOST_COST = ('timed waypoints together with a host objective (a cost plug-in without a kernel, d2d_nlp_solve_model) are not '
+                 'supported: use one of the cost classes of d2d.opty_utils / d2d.multiopty_utils')
+
+
+def check_waypoints(exp, backend, n_ac=None):
+    """The scenario's timed waypoints (exp.waypoints, absent or empty: none), refused where they cannot be planned: backend='fit'.
+    n_ac None: one list of d2d.opty_utils.Waypoint (single_opt_planner); else one list per aircraft (multi_opt_planner) -> a list of
+    n_ac lists."""
+    wps = getattr(exp, 'waypoints', None) or []
+    if n_ac is None:
+        wps = list(wps)
+        if any(not isinstance(w, d2ou.Waypoint) for w in wps):
+            raise ValueError('waypoints: a list of d2d.opty_utils.Waypoint')
+        has = bool(wps)
+    else:
+        if any(isinstance(w, d2ou.Waypoint) for w in wps):
+            raise ValueError(f'waypoints: one list of d2d.opty_utils.Waypoint per aircraft ({n_ac})')
+        wps = [list(w or []) for w in wps] or [[] for _ in range(n_ac)]
+        if len(wps) != n_ac or any(not isinstance(w, d2ou.Waypoint) for ws in wps for w in ws):
+            raise ValueError(f'waypoints: one list of d2d.opty_utils.Waypoint per aircraft ({n_ac})')
+        has = any(wps)
+    if has and backend == 'fit':
+        raise NotImplementedError("backend='fit' cannot plan through timed waypoints: the polynomial fit has no interior conditions.  "
+                                  "backend='nlp' (or 'auto') solves the collocation problem through them")
+    return wps if has else ([] if n_ac is None else [[] for _ in range(n_ac)])
+
+
+def waypoint_constraints(ac, waypoints):
+    """The instance constraints of one aircraft's waypoints: `x(t) - value` for every pinned component."""
+    out = ()
+    for w in waypoints:
+        for sym, v in ((ac._sx, w.x), (ac._sy, w.y), (ac._spsi, w.psi)):
+            if v is not None:
+                out += (sym(w.t) - v,)
+    return out
 
 
 def check_moving(exp, backend):
@@ -216,6 +255,7 @@ class Planner:
                                       "speed and bank rows would depend on position through the field.  backend='nlp' (or 'auto') "
                                       "solves the collocation problem in the field")
         self.moving_obstacles = check_moving(exp, self.backend)
+        self.waypoints = check_waypoints(exp, self.backend)
         self.aircraft = d2ou.Aircraft()
         N = self.num_nodes
         self._slice_x, self._slice_y, self._slice_psi, self._slice_phi, self._slice_v = (
@@ -225,13 +265,16 @@ class Planner:
         self._host_cost = self.backend != 'fit' and not lowerable(exp.cost)
         if self._host_cost and self.moving_obstacles:
             raise NotImplementedError(MOVING_HOST_COST)
-        if initialize and (self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles):
+        if self._host_cost and self.waypoints:
+            raise NotImplementedError(VIA_HOST_COST)
+        if initialize and (self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints):
             import opty.direct_collocation
             _g = self.aircraft
             t0, (x0, y0, psi0, phi0, v0) = exp.t0, exp.p0
             self._instance_constraints = (_g._sx(t0) - x0, _g._sy(t0) - y0, _g._spsi(t0) - psi0)
             t1, (x1, y1, psi1, phi1, v1) = exp.t1, exp.p1
             self._instance_constraints += (_g._sx(t1) - x1, _g._sy(t1) - y1, _g._spsi(t1) - psi1)
+            self._instance_constraints += waypoint_constraints(_g, self.waypoints)
             self._bounds = {_g._sphi(_g._st): exp.phi_constraint, _g._sv(_g._st): exp.v_constraint}
             if exp.x_constraint is not None:
                 self._bounds[_g._sx(_g._st)] = exp.x_constraint
@@ -287,6 +330,9 @@ class Planner:
             g[self._slice_x] = rng.uniform(cx[0], cx[1], N)
             g[self._slice_y] = rng.uniform(cy[0], cy[1], N)
             g[self._slice_psi] = rng.uniform(-np.pi, np.pi, N)
+        elif kind == 'via':
+            g[self._slice_x], g[self._slice_y], g[self._slice_psi], g[self._slice_phi], g[self._slice_v] = d2ou.via_guess(
+                self.exp.p0, self.exp.p1, self.waypoints, self.exp.t0, self.time_step, N, self.exp.vref)
         elif kind == 'tri':
             x, y, psi, phi, v = d2ou.triangle(self.exp.p0[:2], self.exp.p1[:2], self.exp.vref, self.duration, N, go_left=-1.)
             g[self._slice_x], g[self._slice_y], g[self._slice_psi], g[self._slice_phi], g[self._slice_v] = x, y, psi, phi, v
@@ -321,9 +367,9 @@ class Planner:
 
     def run(self, initial_guess=None):
         if initial_guess is None:
-            initial_guess = self.get_initial_guess('tri')
+            initial_guess = self.get_initial_guess('via' if self.waypoints else 'tri')
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self._host_cost or self.field is not None or self.moving_obstacles:
+        if self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints:
             self.info['backend_used'] = 'nlp'
         elif self.backend != 'nlp':
             self._harden()

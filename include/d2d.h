@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 115
+#define D2D_VERSION 116
 
 /* error codes */
 #define D2D_OK 0
@@ -810,6 +810,41 @@ int d2d_nlp_solve_groups_moving(d2d_ctx *ctx, int R, int n_ac, int N, double h, 
                                 double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
                                 int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
                                 const d2d_moving_obstacles *mov, double *mov_work);
+
+/* Timed waypoints of the collocation planner: components of x, y, psi of INTERIOR nodes held at given values -- a point to fly
+ * through at a given time, a gate, a heading at a hand-over.  A pinned component is a fixed variable exactly as x, y, psi of the two end
+ * nodes are: it starts at its value and keeps it (the returned W holds the value bit for bit), has no bound duals and no barrier
+ * term, takes no step (an identity row and column in the Newton system, in both factorisations), and is left out of the KKT error and
+ * the ratio tests.  The objective's terms -- discs, moving discs, partners -- still count at a pinned node.  The pins live in a side
+ * table, one list per problem, padded to a common length with rows of mask 0.  (version 116) */
+#define D2D_MAX_VIA 16           /* rows per problem */
+typedef struct {
+  int32_t n_via;        /* 0 .. D2D_MAX_VIA */
+  const double *pts;    /* dev [G][n_via][5] = (node, mask, x, y, psi); mask bit 0 / 1 / 2: x / y / psi is pinned; mask 0: the row is absent */
+} d2d_via_points;
+
+/* d2d_nlp_solve_moving through pins: its arguments, with mov NULL allowed (nothing moves), plus the pins of each problem (G = B) and
+ * via_work, B * N int32 for the planes of the nodes' fixed sets.  via NULL, n_via out of range, or a NULL table or via_work with
+ * n_via > 0: D2D_EINVAL before anything is launched; the other rules are those of d2d_nlp_solve_moving.  With n_via = 0 the call IS
+ * d2d_nlp_solve_moving; with every mask 0 its results are bit for bit the same.
+ * The pins are validated on the device, per problem, before its solve.  A row with a mask that is no integer in 1 .. 7 (0: absent), a
+ * node that is no integer in 1 .. N-2, a pinned value that is not finite or lies outside the problem's box (D2D_SC_XMIN .. YMAX, the
+ * psi interval of d2d_nlp_opts.bounds), or a (node, component) that another row pins too refuses THAT problem -- D2D_ST_NONFINITE,
+ * cost = feas = NaN, iters = 0, its W untouched -- and the rest of the launch is solved.  The values of components outside a row's
+ * mask are not read.  tests/nlp_via_ref.py states the solve on the CPU.  Asynchronous on the context's stream. */
+int d2d_nlp_solve_via(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
+                      double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
+                      const double *t_start, const d2d_moving_obstacles *mov, double *mov_work, const d2d_via_points *via, int32_t *via_work);
+
+/* d2d_nlp_solve_groups_moving through pins: its arguments, with mov NULL allowed, plus the pins of each AIRCRAFT (G = R * n_ac, the
+ * aircraft of a scenario consecutive) and via_work of R * n_ac * N int32.  The rules for via and via_work are those of
+ * d2d_nlp_solve_via; an unusable row of any aircraft refuses all aircraft of its scenario exactly as a malformed mask does (sweeps = 0,
+ * moved = 0, W untouched).  With n_via = 0 the call IS d2d_nlp_solve_groups_moving; with every mask 0 its results are bit for bit the
+ * same.  Asynchronous on the context's stream. */
+int d2d_nlp_solve_groups_via(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                             double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                             int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
+                             const d2d_moving_obstacles *mov, double *mov_work, const d2d_via_points *via, int32_t *via_work);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,11 @@ python tools/bench_nlp_wind.py moving [B]  moving obstacles (d2d_nlp_solve_movin
     1 and 4 moving discs against the SAME problems with the same number of static discs in the row through d2d_nlp_solve -- the
     tracks stand still where the static discs are, so both entries solve the same problems and the ratio is the cost of the centre
     planes and the rolled loop, not of the terms.  The two entries alternate, 1 warm-up + 5 timed launches each, HIP events, one
-    process; medians and the spread of each."""
+    process; medians and the spread of each.
+python tools/bench_nlp_wind.py via [B]     timed waypoints (d2d_nlp_solve_via): B (default 4096) perturbed exp_14 at 121 nodes, each with one
+    (x, y) pin at node 60 on the middle of its leg moved 5 m sideways, from the piecewise-linear guess through the pin, against the
+    tool's own unpinned constant-wind figure (d2d_nlp_solve, the same rows from their own guess) in the same run.  The two entries
+    alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians and the spread of each."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 'tests')):
@@ -178,7 +182,45 @@ def moving_leg(B):
     ctx.close()
 
 
+def via_leg(B):
+    import torch, d2dhip
+    import d2dhip as D
+    from d2dhip import synth
+    from d2d.opty_utils import Waypoint, lower_waypoints, via_guess
+    ctx = d2dhip.Context(0)
+    rows, W0, h = synth.nlp_problems(B)
+    N, node = W0.shape[2], 60
+    p0, p1 = rows[:, D.SC_X0:D.SC_X0 + 3], rows[:, D.SC_X1:D.SC_X1 + 3]
+    d = p1[:, :2] - p0[:, :2]
+    d /= np.hypot(d[:, 0], d[:, 1])[:, None]
+    pin = p0[:, :2] + (p1[:, :2] - p0[:, :2]) * node / (N - 1) + 5.0 * np.stack([-d[:, 1], d[:, 0]], 1)
+    wps = [[Waypoint(node * h, pin[b, 0], pin[b, 1])] for b in range(B)]
+    via = ctx.dev(np.stack([lower_waypoints(w, 0.0, h, N) for w in wps]))
+    Wv = np.stack([np.stack(via_guess(p0[b], p1[b], wps[b], 0.0, h, N, rows[b, D.SC_VSP])) for b in range(B)])
+    dsc = ctx.dev(rows)
+    times = {'unpinned': [], 'via': []}
+    outs = {}
+    for rep in range(6):                                     # the first launch of each is the warm-up; the entries alternate
+        for what in ('unpinned', 'via'):
+            W = ctx.dev(np.ascontiguousarray(W0 if what == 'unpinned' else Wv))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            outs[what] = ctx.nlp_solve(dsc, W, h) if what == 'unpinned' else ctx.nlp_solve_via(dsc, W, h, via)
+            e1.record(); torch.cuda.synchronize()
+            times[what].append(e0.elapsed_time(e1) * 1e-3)
+    med = {k: float(np.median(v[1:])) for k, v in times.items()}
+    for what in ('unpinned', 'via'):
+        st = outs[what]['status'].cpu().numpy(); it = outs[what]['iters'].cpu().numpy()
+        print(json.dumps({'leg': 'via', 'B': B, 'nodes': N, 'entry': what, 'seconds_median': med[what], 'seconds_min': min(times[what][1:]),
+                          'seconds_max': max(times[what][1:]), 'problems_per_s': B / med[what], 'via_over_unpinned': med['via'] / med['unpinned'],
+                          'converged_frac': float((st == 1).mean()), 'mean_newton_steps': float(it.mean()), 'max_newton_steps': int(it.max())}),
+              flush=True)
+    ctx.close()
+
+
 def main():
+    if sys.argv[1:2] == ['via']:
+        return via_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['moving']:
         return moving_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['pairs']:
