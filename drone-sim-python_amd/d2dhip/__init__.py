@@ -83,6 +83,22 @@ class ViaPointsC(C.Structure):
     _fields_ = [('n_via', C.c_int32), ('pts', C.c_void_p)]
 
 
+class AuditParams(C.Structure):
+    """d2d_audit_params (include/d2d.h)."""
+    _fields_ = [('n_form', C.c_int32), ('n_ac', C.c_int32), ('n_rows', C.c_int32), ('rows_per_block', C.c_int32), ('n_stat', C.c_int32),
+                ('reserved', C.c_int32), ('dt_row', C.c_double), ('d_safe', C.c_double), ('err_tol', C.c_double)]
+
+
+AUDIT_OUT = ('sep_dist', 'sep_partner', 'sep_time', 'sep_count', 'stat_clear', 'stat_time', 'stat_count', 'mov_clear', 'mov_time', 'mov_count',
+             'err_max', 'err_time', 'err_count', 'phi_max', 'v_min', 'v_max', 'status')
+AUDIT_NONFINITE, AUDIT_BAD_TSTART, AUDIT_BAD_TRACK = 1, 2, 4     # include/d2d.h D2D_AUDIT_*: the bits of a refused formation's status
+
+
+class AuditOut(C.Structure):
+    """d2d_audit_out (include/d2d.h): device addresses of the outputs, None for one that is not wanted."""
+    _fields_ = [(k, C.c_void_p) for k in AUDIT_OUT]
+
+
 class FitOpts(C.Structure):
     _fields_ = [('max_iter', C.c_int32), ('check_every', C.c_int32), ('ftol', C.c_double),
                 ('gtol', C.c_double), ('xtol', C.c_double), ('so_lambda', C.c_double),
@@ -166,6 +182,8 @@ _SIGS = {
                           + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, C.POINTER(ViaPointsC), _P]),
     'd2d_nlp_solve_groups_via': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
                                  + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, C.POINTER(ViaPointsC), _P]),
+    'd2d_flight_audit_workspace': (C.c_int64, [C.POINTER(AuditParams), C.c_int]),
+    'd2d_flight_audit': (C.c_int, [_P, C.POINTER(AuditParams)] + [_P] * 6 + [C.POINTER(MovingObstaclesC), _P, _P, C.POINTER(AuditOut)]),
     'd2d_fit_plan_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(_P)]),
     'd2d_fit_plan_create_ex': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(FitPlanOpts), C.POINTER(_P)]),
     'd2d_fit_opts_default': (C.c_int, [C.POINTER(FitOpts)]),
@@ -815,6 +833,61 @@ class Context:
         out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work)
         if want_mult:
             out['mult'] = mult
+        return out
+
+    def flight_audit(self, X_hist, n_ac, dt_row, rows=None, t_start=None, x_ref=None, y_ref=None, static=None, knots=None, disc=None,
+                     d_safe=0.0, err_tol=float('inf'), rows_per_block=0, layout='hist', outputs=None):
+        """Audit a state history that is on the device (d2d_flight_audit): X_hist dev [n_rows][5][N], N = n_form * n_ac, row i of
+        formation f at t_start[f] + i dt_row (t_start dev [n_form], a float or None: 0).  layout='plan': X_hist is a collocation plan
+        W [N][5][K], transposed here to [K][5][N].  rows dev int32 [n_form]: the valid rows (None: all).  x_ref, y_ref dev [n_rows][N]:
+        the tracked reference (both or neither).  static dev [n_form][n_stat][3] = (x, y, r): static discs; knots, disc: the tables of
+        Context.mov_sample with G = n_form (t_start is then required).  Returns a dict of device tensors, per drone [N]: sep_dist,
+        sep_partner, sep_time, sep_count (rows closer than d_safe); stat_* / mov_* [n_disc][N]: clear, time, count; err_max, err_time,
+        err_count (rows above err_tol); phi_max, v_min, v_max; status int32 [n_form] (0, or the AUDIT_* bits of a refused formation:
+        its floating outputs are NaN, its counts -1); mov_work [n_form][n_mov][2][n_rows]: the moving centres at the rows.  The result
+        does not depend on rows_per_block (0: the library's choice), bit for bit.  outputs: the groups to compute, of 'sep', 'env'
+        (phi_max, v_min, v_max), 'err', 'stat', 'mov' (None: every group the inputs allow); only the planes they need are read."""
+        torch = _torch()
+        if layout == 'plan':
+            X_hist = X_hist.permute(2, 1, 0).contiguous()
+        elif layout != 'hist':
+            raise ValueError(f"layout={layout!r}: 'hist' ([n_rows][5][N]) or 'plan' ([N][5][K])")
+        assert X_hist.dim() == 3 and X_hist.shape[1] == 5 and X_hist.is_contiguous() and X_hist.dtype == torch.float64 and X_hist.device.type == 'cuda'
+        n_rows, _, N = X_hist.shape
+        n_ac = int(n_ac)
+        n_form = N // n_ac if n_ac >= 1 else 0
+        assert n_ac < 1 or N == n_form * n_ac
+        for t in (x_ref, y_ref):
+            assert t is None or (t.is_contiguous() and tuple(t.shape) == (n_rows, N) and t.dtype == torch.float64 and t.device == X_hist.device)
+        assert rows is None or (rows.is_contiguous() and tuple(rows.shape) == (n_form,) and rows.dtype == torch.int32 and rows.device == X_hist.device)
+        assert static is None or (static.is_contiguous() and static.dim() == 3 and static.shape[0] == n_form and static.shape[2] == 3
+                                  and static.dtype == torch.float64 and static.device == X_hist.device)
+        n_stat = 0 if static is None else int(static.shape[1])
+        m = self._moving_c(knots, disc, n_form)
+        t_start = self._t_start_dev(t_start, n_form, X_hist)
+        p = AuditParams(n_form, n_ac, n_rows, int(rows_per_block), n_stat, 0, float(dt_row), float(d_safe), float(err_tol))
+        nbytes = self.lib.d2d_flight_audit_workspace(C.byref(p), m.n_mov)
+        if nbytes < 0:
+            _check(int(nbytes))
+        work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
+        mov_work = self.empty(n_form, m.n_mov, 2, n_rows) if m.n_mov > 0 else None
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=self.device)     # noqa: E731
+        out = dict(sep_dist=self.empty(N), sep_partner=i32(N), sep_time=self.empty(N), sep_count=i32(N), phi_max=self.empty(N),
+                   v_min=self.empty(N), v_max=self.empty(N), status=i32(n_form))
+        if n_stat > 0:
+            out.update(stat_clear=self.empty(n_stat, N), stat_time=self.empty(n_stat, N), stat_count=i32(n_stat, N))
+        if m.n_mov > 0:
+            out.update(mov_clear=self.empty(m.n_mov, N), mov_time=self.empty(m.n_mov, N), mov_count=i32(m.n_mov, N))
+        if x_ref is not None and y_ref is not None:
+            out.update(err_max=self.empty(N), err_time=self.empty(N), err_count=i32(N))
+        if outputs is not None:
+            keep = {'sep': 'sep_', 'env': ('phi_', 'v_'), 'err': 'err_', 'stat': 'stat_', 'mov': 'mov_'}
+            pre = tuple(x for g in outputs for x in np.atleast_1d(keep[g]))
+            out = {k: v for k, v in out.items() if k == 'status' or k.startswith(pre)}
+        o = AuditOut(**{k: v.data_ptr() for k, v in out.items()})
+        _check(self.lib.d2d_flight_audit(self.h, C.byref(p), _ptr(X_hist), _ptr(rows), _ptr(t_start), _ptr(x_ref), _ptr(y_ref), _ptr(static),
+                                         C.byref(m), _ptr(mov_work), _ptr(work), C.byref(o)))
+        out['mov_work'] = mov_work                    # (work is released here: the context's stream is torch's, whose allocator orders its reuse)
         return out
 
     def track_run(self, x_ref, y_ref, X0, dt, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), out=None, wind=None, t_start=0.0, **kw):

@@ -42,14 +42,32 @@ def hold_steps(t_opt_comp, t_step):
     return k
 
 
+def _audit_kw(ctx, audit, n_form, what):
+    """The flight_audit arguments of an `audit=` value: True, or a dict of d_safe (m; rows closer than it are counted), err_tol (m) and
+    static (discs (n_stat, 3) = (x, y, r) for every formation, or (n_form, n_stat, 3)); `what`: further keys this caller accepts."""
+    audit = {} if audit is True else dict(audit)
+    unknown = set(audit) - {'d_safe', 'err_tol', 'static'} - set(what)
+    if unknown:
+        raise ValueError(f'audit: unknown keys {sorted(unknown)}')
+    kw = dict(d_safe=float(audit.get('d_safe', 0.0)), err_tol=float(audit.get('err_tol', np.inf)))
+    if audit.get('static') is not None:
+        st = np.asarray(audit['static'], dtype=np.float64)
+        kw['static'] = ctx.dev(np.ascontiguousarray(np.broadcast_to(st, (n_form,) + st.shape[-2:])))
+    return kw
+
+
 def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, t_end=1000, X0=None,
                                tau_phi=None, rec_stride=1, record=('X', 'U', 'Rr', 'eth'), W=(0., 0.), etheta_tol_deg=None,
-                               t_opt_comp=0.0, windfield=None):
+                               t_opt_comp=0.0, windfield=None, audit=None):
     """Many formations at once.  c (n_form, n_ac, 2) centres; r scalar or (n_form, n_ac); X0
     (n_form, n_ac, 5) or None (every aircraft starts at the reference's X1); X0f (n_form, n_ac, >=3)
     or None.  etheta_tol_deg: stop by the phase-error rule of cases 2 / 3 instead of the state rule (after t_opt_comp more seconds on
     which it holds).  windfield: a SplineWindField the plant flies instead of W (row i at t_start + i t_step; the GVF law never reads
-    the wind).  Returns the raw device dictionary of d2dhip.Context.gvf_run plus `time`."""
+    the wind).  Returns the raw device dictionary of d2dhip.Context.gvf_run plus `time`.
+    audit: True or a dict (d_safe, err_tol, static: _audit_kw) -- out['audit'] is Context.flight_audit of the recorded history: every
+    formation's rows up to its stop row (derived on the device), dt_row = t_step rec_stride; needs 'X' in record."""
+    if audit is not None and 'X' not in record:
+        raise ValueError("audit needs the state history: 'X' must be in record")
     fld = plant_wind(windfield)
     ctx = d2dhip.default_context()
     c = np.asarray(c, dtype=np.float64).reshape(-1, n_ac, 2)
@@ -67,6 +85,11 @@ def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, 
                       stop_hold=hold_steps(t_opt_comp, t_step) if etheta_tol_deg is not None else 0,
                       **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
     out['time'] = time
+    if audit is not None:
+        torch = d2dhip._torch()
+        kw = _audit_kw(ctx, audit, n_form, ())
+        rows = ((torch.clamp(out['stop_row'], max=len(time)) + (rec_stride - 1)) // rec_stride).to(torch.int32)
+        out['audit'] = ctx.flight_audit(out['X'], n_ac, t_step * rec_stride, rows=rows, t_start=float(time[0]), **kw)
     return out
 
 
@@ -168,17 +191,26 @@ def ExtendTraj_symm(n_ac, x_ref, y_ref, psi_ref, time):
     return time, np.append(x_ref, xs, axis=0), np.append(y_ref, ys, axis=0), np.append(psi_ref, ys, axis=0)
 
 
-def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), windfield=None):
+def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), windfield=None, audit=None):
     """x_ref, y_ref (T, n) for n independent drones; X0s (n, 5).  Device dictionary out.  windfield: a SplineWindField the plant
-    flies (row i at time[i]); the controller keeps w, as DiffController(w) does (src/11_full_sim_case1.py:241-291)."""
+    flies (row i at time[i]); the controller keeps w, as DiffController(w) does (src/11_full_sim_case1.py:241-291).
+    audit: True or a dict (d_safe, err_tol, static: _audit_kw; n_ac: consecutive drones that form a formation, default 1 -- the
+    drones are independent) -- out['audit'] is Context.flight_audit of the flown history against x_ref, y_ref; needs 'X' in record."""
+    if audit is not None and 'X' not in record:
+        raise ValueError("audit needs the state history: 'X' must be in record")
     fld = plant_wind(windfield)
     ctx = d2dhip.default_context()
     ac = ddyn.Aircraft()
     dt = time[1] - time[0]
-    return ctx.track_run(ctx.dev(np.ascontiguousarray(x_ref, dtype=np.float64)), ctx.dev(np.ascontiguousarray(y_ref, dtype=np.float64)),
-                         ctx.dev(_planes(np.asarray(X0s, dtype=np.float64))), float(dt), record=record,
-                         w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v,
-                         **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
+    xr, yr = ctx.dev(np.ascontiguousarray(x_ref, dtype=np.float64)), ctx.dev(np.ascontiguousarray(y_ref, dtype=np.float64))
+    out = ctx.track_run(xr, yr, ctx.dev(_planes(np.asarray(X0s, dtype=np.float64))), float(dt), record=record,
+                        w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v,
+                        **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
+    if audit is not None:
+        n_ac = 1 if audit is True else int(audit.get('n_ac', 1))
+        kw = _audit_kw(ctx, audit, xr.shape[1] // n_ac, ('n_ac',))
+        out['audit'] = ctx.flight_audit(out['X'], n_ac, float(dt), t_start=float(time[0]), x_ref=xr, y_ref=yr, **kw)
+    return out
 
 
 def implement_controller(n_ac, time, x_ref, y_ref, v, w, X0s):
@@ -295,7 +327,7 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
 
 def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_sim_end=200., w=(0., 0.), t_step=0.05,
                           t_end_1=1000., X0=None, max_sweeps=250, record2=('X', 'U'), record3=('X', 'U'), windfield=None,
-                          moving_obstacles=None):
+                          moving_obstacles=None, audit=None):
     """The three phases of src/11_full_sim_case1.py main() (:406-478) for many independent formations, chained ON THE
     DEVICE: the circular-formation phase hands its final states to the planner as a device tensor, the planner's sampled
     plan is the tracking reference of phase 2 without leaving HBM, and phase 3 restarts from phase 2's final states.
@@ -328,8 +360,15 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     transition is the collocation problem around them from that formation's own end-of-phase-1 time t2[r] (the device array above,
     computed with or without a field), in -F or in the rows' constant wind (d2d_nlp_solve_groups_moving), from the fit's plan as the
     guess; the weight is scen.cost's kobs.  plan gains the entries listed for a field, t_start included, and mov_work: the discs'
-    centres at the plan's nodes [n_form][n_mov][2][K]."""
+    centres at the plan's nodes [n_form][n_mov][2][K].
+    audit: None (nothing is launched, the result is what it was), True or a dict (d_safe, err_tol, static: _audit_kw).  out['audit']
+    then holds Context.flight_audit dictionaries of what was planned and what was flown: plan (the plan Xs as a history with
+    dt_row = dt2), phase2 (the flown X against the plan's x, y) and phase3 (a list, one per repetition, against the phase-3
+    reference) -- on the chain's clock where it has one (a field or moving discs: t_start = t2, repetition k of phase 3 from
+    t2 + dur2 + k time_3[-1]) and around the chain's moving discs.  'X' must be in record2 / record3."""
     import multi_opt_planner as mop
+    if audit is not None and ('X' not in record2 or (ref3 is not None and 'X' not in record3)):
+        raise ValueError("audit needs the flown histories: 'X' must be in record2 and record3")
     import d2d.opty_utils as d2ou
     F = plant_wind(windfield)
     ctx = d2dhip.default_context()
@@ -401,6 +440,13 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     x_ref2 = Xs[:, 0, :].t().contiguous(); y_ref2 = Xs[:, 1, :].t().contiguous()     # dev [K][N]
     ph2 = ctx.track_run(x_ref2, y_ref2, Xs1, float(dt2), record=record2, **kw, **kw2)
     out = dict(phase1=ph1, plan=pl, phase2=ph2, phase3=[])
+    if audit is not None:
+        akw = _audit_kw(ctx, audit, n_form, ())
+        if moving:
+            akw.update(knots=pl['moving'][0], disc=pl['moving'][1])
+        t2a = t2 if (F is not None or moving) else None
+        out['audit'] = dict(plan=ctx.flight_audit(Xs, n_ac, float(dt2), t_start=t2a, layout='plan', **akw),
+                            phase2=ctx.flight_audit(ph2['X'], n_ac, float(dt2), t_start=t2a, x_ref=x_ref2, y_ref=y_ref2, **akw), phase3=[])
     # ---- phase 3: the periodic formation-flight reference, restarted from the last state until t_sim_end (:466-474) ----
     if ref3 is not None:
         time_3, x3, y3 = ref3
@@ -417,6 +463,10 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
                 kw2 = dict(t_start=t2d + (float(dur2) + k * float(time_3[-1])))
             ph3 = ctx.track_run(x3, y3, X_last, dt3, record=record3, **kw, **kw2)
             out['phase3'].append(ph3)
+            if audit is not None:
+                t3 = float(dur2) + k * float(time_3[-1])
+                out['audit']['phase3'].append(ctx.flight_audit(ph3['X'], n_ac, dt3, t_start=t3 if t2a is None else t2a + t3, x_ref=x3,
+                                                               y_ref=y3, **akw))
             X_last = ph3['X_final']
             t_final += float(time_3[-1])
             k += 1

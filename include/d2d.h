@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 116
+#define D2D_VERSION 117
 
 /* error codes */
 #define D2D_OK 0
@@ -845,6 +845,72 @@ int d2d_nlp_solve_groups_via(d2d_ctx *ctx, int R, int n_ac, int N, double h, con
                              double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
                              int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
                              const d2d_moving_obstacles *mov, double *mov_work, const d2d_via_points *via, int32_t *via_work);
+
+/* Flight audit: what a flown or planned state history kept of the planners' promises, in one streaming pass over a history that is
+ * already on the device.  Per aircraft: the closest approach to the other aircraft of its formation, the clearance from static and
+ * from moving discs, the tracking error against the reference it followed, the bank and airspeed envelope.  (version 117)
+ * History: X_hist dev [n_rows][5][N], plane-major, planes x, y, psi, phi, v, N = n_form * n_ac, drone d = formation d / n_ac, aircraft
+ * d % n_ac -- the layout d2d_sim_gvf_run*, d2d_sim_track_run* and d2d_sim_dfff_run* write (a plan [N][5][K] is transposed by the
+ * caller).  Only the planes the requested outputs need are read; psi never is.  Row i of formation f is at t_start[f] + i dt_row
+ * (t_start dev [n_form], NULL: 0; dt_row = the step times the history's rec_stride).  rows dev int32 [n_form] (NULL: n_rows) is the
+ * number of valid rows of each formation, clamped to 0 .. n_rows: a row at an index >= rows[f] is never read.
+ * Between two rows every position is linear in s in [0, 1].  For a relative position p(s) = p0 + s d the closest approach is at
+ * s* = clamp(-(p0 . d) / (d . d), 0, 1) (0 when d . d = 0), its distance |p0 + s* d| -- at s* = 0 and s* = 1 the row's own p0 and p1,
+ * exactly -- and its time t_start[f] + (i + s*) dt_row.  Minima and maxima are taken over the squared distances and the square root
+ * is drawn once, at the end; the counts compare squared distances with d_safe^2, r^2 and err_tol^2.  One valid row: the row is the
+ * answer.  No valid row, no partner (n_ac = 1) or an absent disc (r <= 0), "nothing seen": minima +inf, maxima -inf, times NaN,
+ * partner -1, counts 0.  Ties: the earliest time wins, among partners at the same time the smallest index.
+ * Outputs (d2d_audit_out; any pointer may be NULL: neither computed nor stored), per drone [N] unless noted:
+ *   sep_dist, sep_partner, sep_time   the smallest distance over all segments to any other aircraft of the formation, that partner's
+ *                                     index in the formation, the time;  sep_count: the valid rows at which the nearest partner is
+ *                                     closer than d_safe (d_safe <= 0: no count, 0)
+ *   stat_clear, stat_time, stat_count [n_stat][N]: distance to the centre minus r of static disc k, its minimum over the segments, the
+ *                                     time, the valid rows with clearance < 0.  stat dev [n_form][n_stat][3] = (x, y, r), r <= 0: absent
+ *   mov_clear, mov_time, mov_count    [n_mov][N]: the same for the moving discs of mov (G = n_form).  Their centres at the row times are
+ *                                     d2d_mov_sample's (its kernel fills mov_work, n_form * n_mov * 2 * n_rows doubles, on the context's
+ *                                     stream ahead of the audit) and a centre is LINEAR BETWEEN ROWS: a track's knot that falls inside a
+ *                                     step is cut.  The disc's kind is not used
+ *   err_max, err_time, err_count      against x_ref, y_ref dev [n_rows][N] (row i pairs with sample i, as in d2d_sim_track_run): the largest
+ *                                     |(x, y) - (x_ref, y_ref)| over the valid ROWS (not between them), its time, the rows above err_tol
+ *   phi_max, v_min, v_max             max |phi|, min v, max v over the valid rows
+ *   status                            int32 [n_form]: 0, or the D2D_AUDIT_* bits of a refusal
+ * Refusals, per formation: a non-finite value in a plane, reference or disc row that the call reads for the valid rows of any of its
+ * aircraft (D2D_AUDIT_NONFINITE), a t_start that is not finite (D2D_AUDIT_BAD_TSTART), with n_mov > 0 a track that d2d_nlp_solve_moving
+ * would refuse (D2D_AUDIT_BAD_TRACK) -- every floating output of its aircraft NaN, every count and partner -1; the other formations are
+ * audited.
+ * The rows are cut into blocks of rows_per_block (0: the library's choice) whose partial results a second kernel folds; the block
+ * length only schedules the work: every output is bit-identical for every block length and on every call.  work: device memory of
+ * d2d_flight_audit_workspace(p, n_mov) bytes (a negative value: D2D_EINVAL), 16-byte aligned, that the call overwrites.
+ * D2D_EINVAL before anything is launched: NULL ctx, p, X_hist, work or out; n_form < 1; n_ac outside 1 .. 64; n_rows < 1; dt_row not
+ * > 0; n_stat outside 0 .. D2D_MAX_OBS or n_mov outside 0 .. D2D_MAX_MOV (mov NULL: 0), n_knot out of range; a NULL stat, knots, disc
+ * or mov_work with a non-zero count; one of x_ref, y_ref without the other, or a tracking-error output without them; n_mov > 0 without
+ * t_start; rows_per_block < 0; err_tol < 0 or NaN.  tests/flight_audit_ref.py is the CPU statement.  Asynchronous on the context's
+ * stream. */
+#define D2D_AUDIT_NONFINITE 1
+#define D2D_AUDIT_BAD_TSTART 2
+#define D2D_AUDIT_BAD_TRACK 4
+typedef struct {
+  int32_t n_form, n_ac;       /* n_ac 1 .. 64 */
+  int32_t n_rows;             /* rows of X_hist, x_ref, y_ref and mov_work */
+  int32_t rows_per_block;     /* 0: the library's choice */
+  int32_t n_stat;             /* 0 .. D2D_MAX_OBS */
+  int32_t reserved;
+  double dt_row;
+  double d_safe;              /* <= 0: no count */
+  double err_tol;             /* +inf: no count */
+} d2d_audit_params;
+typedef struct {
+  double *sep_dist; int32_t *sep_partner; double *sep_time; int32_t *sep_count;
+  double *stat_clear; double *stat_time; int32_t *stat_count;
+  double *mov_clear; double *mov_time; int32_t *mov_count;
+  double *err_max; double *err_time; int32_t *err_count;
+  double *phi_max; double *v_min; double *v_max;
+  int32_t *status;
+} d2d_audit_out;
+int64_t d2d_flight_audit_workspace(const d2d_audit_params *p, int n_mov);
+int d2d_flight_audit(d2d_ctx *ctx, const d2d_audit_params *p, const double *X_hist, const int32_t *rows, const double *t_start,
+                     const double *x_ref, const double *y_ref, const double *stat, const d2d_moving_obstacles *mov, double *mov_work,
+                     void *work, const d2d_audit_out *out);
 
 #ifdef __cplusplus
 }
