@@ -1276,6 +1276,17 @@ __device__ __forceinline__ bool nlp_via_bad(const double *__restrict__ pts, int 
   return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
 }
 
+// The optional inputs of nlp_solve_one in one aggregate, so that one call expression serves every instantiation: each reads the
+// members of its own template arguments and ignores the others (NlpExtra{}: none).
+struct NlpExtra {
+  NlpModel md;               // MODEL
+  const d2d_wind_field *wf;  // WIND: the field and the problem's start time
+  double t_start;
+  unsigned pmask;            // PAIRS
+  const NlpMovSet *mv;       // MOV
+  const NlpViaSet *via;      // VIA
+};
+
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
 // MODEL: the objective is the quadratic model md (d2d_nlp_solve_model) on top of the row's structured terms; cost = its value.
@@ -1288,9 +1299,9 @@ __device__ __forceinline__ bool nlp_via_bad(const double *__restrict__ pts, int 
 template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
-                                              const double *__restrict__ bnd, const NlpModel &md = NlpModel{nullptr, nullptr, nullptr},
-                                              const d2d_wind_field *wf = nullptr, double t_start = 0.0, unsigned pmask = 0u,
-                                              const NlpMovSet *mv = nullptr, const NlpViaSet *via = nullptr) {
+                                              const double *__restrict__ bnd, const NlpExtra &ex = NlpExtra{}) {
+  const NlpModel md = ex.md;
+  [[maybe_unused]] const NlpViaSet *via = ex.via;
   // diagnostics (D2D_NLP_STAMPS): cycles per phase -- merit, assembly, factorisation, back substitution, ratio tests, update
   unsigned long long st_t = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define NLP_STAMP(k) if (st_on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t; st_t = t_; }
@@ -1299,16 +1310,16 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   NlpScen s = nlp_load_scen(sc, o, bnd);
   if (sc[D2D_SC_BANKMAX] != 0.0) { s.sbank = s.skphi * (double)N; s.skphi = 0.0; }     // obj_scale * kbank (the row's S is obj_scale / N)
   NlpProbT<MOV, VIA> pb;
-  if constexpr (MOV) pb.mv = *mv;
+  if constexpr (MOV) pb.mv = *ex.mv;
   if constexpr (VIA) pb.vm = via->vm;
   pb.N = N; pb.h = h;
   pb.W = Wb;
   pb.ws = wsb;
   pb.mu = multb ? multb : pb.ws + (size_t)WS_MU * N;
   pb.partner = partner;
-  pb.pmask = pmask;
+  pb.pmask = ex.pmask;
   pb.lds = ldsw;
-  pb.wf = wf; pb.t0 = t_start;
+  pb.wf = ex.wf; pb.t0 = ex.t_start;
   // (a row whose bounds are unset or inverted would give a zero-width box, infinite duals and NaN pivots for
   // outer_max x 30 assemblies -- refuse it at once)
   {
@@ -1515,10 +1526,10 @@ __device__ __forceinline__ int nlp_next_ticket(int32_t *queue, int lane) {
 // a device counter, and the WORKSPACE BELONGS TO THE SLOT (work + blockIdx.x * WS_TOTAL * N), not to the problem: nothing in it
 // outlives a solve, and with one workspace per problem every solve streamed its 100+ kB through cold lines while the ones it
 // followed were written back -- slots keep the chip's working set at (resident waves) x (workspace) whatever the batch.
-// The hand-out loop stands here and in nlp_solve_wind_kernel, not in one `template <bool WIND>` body: built through such a
-// __forceinline__ body (tried with and without __restrict__ on its parameters, and with the ticket in the for-increment) this
+// The hand-out loop stands here once more, not in nlp_handout_body, which the wind and via kernels share: built through
+// such a __forceinline__ body (tried with and without __restrict__ on its parameters, and with the ticket in the for-increment) this
 // kernel kept 255 VGPRs and 672 B / lane of scratch but its spills moved (SGPR 206 -> 204 .. 216, VGPR 122 -> 124) and 4300 - 5600 of
-// its 12 223 lines of ISA with them.  The benchmark times this kernel, so it keeps its code (DESIGN 5.11); only the ticket is shared.
+// its 12 223 lines of ISA with them.  The benchmark times this kernel, so it keeps its code (DESIGN 5.16); only the ticket is shared.
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WAVES_PER_SIMD, NLP_WAVES_PER_SIMD)))
 nlp_solve_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, const double *partner, double *W,
                  double *work, double *mult, double *__restrict__ cost_out, double *__restrict__ feas_out,
@@ -1537,38 +1548,6 @@ nlp_solve_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restric
     nlp_solve_one(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, partner ? partner + (size_t)b * 2 * N : nullptr, W + (size_t)b * NLP_NV * N,
                   wsb, mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, b == 0 ? stamps : nullptr, nlp_lds,
                   o.bounds ? o.bounds + (size_t)b * 4 : nullptr);
-    if (lane == 0) {
-      cost_out[b] = out.cost;
-      feas_out[b] = out.feas;
-      if (iters_out) iters_out[b] = out.iters;
-      if (status_out) status_out[b] = out.status;
-    }
-    nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
-    t = nlp_next_ticket(queue, lane);
-  }
-}
-
-// d2d_nlp_solve_wind: nlp_solve_kernel's persistent hand-out around the WIND instantiation of the solve (no partner, no stamps).
-// The field is shared by the batch and travels as a kernel argument (scalar registers); its control points are a small table that
-// every wavefront reads and that stays in L2.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
-nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
-                      double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
-                      int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, double t_start) {
-  const int lane = threadIdx.x;
-  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
-  double *wsb = work + (size_t)blockIdx.x * WS_TOTAL * N;
-  const int32_t *__restrict__ order = o.order;
-  for (int t = blockIdx.x; t < B;) {
-    const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
-    if ((unsigned)b >= (unsigned)B) {        // (an entry that is no problem index is skipped, not dereferenced)
-      t = nlp_next_ticket(queue, lane);
-      continue;
-    }
-    NlpOut out;
-    nlp_solve_one<false, true>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + (size_t)b * NLP_NV * N, wsb,
-                               mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds,
-                               o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpModel{nullptr, nullptr, nullptr}, &wf, t_start);
     if (lane == 0) {
       cost_out[b] = out.cost;
       feas_out[b] = out.feas;
@@ -1620,10 +1599,87 @@ __device__ __forceinline__ bool nlp_mov_bad(const d2d_moving_obstacles &mv, int 
   return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
 }
 
-// d2d_nlp_solve_moving: the persistent hand-out around the MOV instantiations of the solve -- the rows' constant wind or the field
-// (WIND), the start time per problem (t_start [B], device memory), the centre planes ctr [B][n_mov][2][N] sampled ahead of this launch.
-// A loop of its own, like nlp_solve_wind_kernel's (the comment above nlp_solve_kernel has the reason).  A problem whose start time is
-// not finite or whose tracks are unusable is refused before its solve: its W is not touched.
+// The hand-out loop's report of one problem: the single-problem twin of nlp_groups_report.
+__device__ __forceinline__ void nlp_report(int b, int lane, const NlpOut &out, double *cost_out, double *feas_out, int32_t *iters_out,
+                                           int32_t *status_out) {
+  if (lane == 0) {
+    cost_out[b] = out.cost;
+    feas_out[b] = out.feas;
+    if (iters_out) iters_out[b] = out.iters;
+    if (status_out) status_out[b] = out.status;
+  }
+}
+
+// nlp_solve_kernel's persistent hand-out around the WIND, MOV and VIA instantiations of the solve (no partner, no stamps): one body
+// for nlp_solve_wind_kernel and the two nlp_solve_via_kernel below, switched at compile time.  The field is shared by the batch and travels as a kernel argument (scalar
+// registers); its control points are a small table that every wavefront reads and that stays in L2.
+// T_AT: the start time is the problem's own, t_at [B] (device memory), read when the equalities or a track need it and checked: a
+//   problem whose start time is not finite is refused before its solve.  Else it is the scalar t_start of d2d_nlp_solve_wind, which
+//   the host has checked.
+// MOV: the centre planes ctr [B][n_mov][2][N] were sampled ahead of this launch; a problem whose tracks are unusable is refused.
+// VIA: the problem's pins via->pts [B][n_via][5] and the plane of its nodes' fixed sets vwork [B][N]; unusable pins refuse the problem
+//   like an unusable track.  mv->n_mov = 0: nothing moves.
+// A refused problem's W is not touched.  The pointer parameters carry no __restrict__ (the kernels' do), as in nlp_groups_body.
+template <bool WIND, bool MOV, bool VIA, bool T_AT>
+__device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d2d_nlp_opts &o, const double *scen, double *W, double *work,
+                                                 double *mult, double *cost_out, double *feas_out, int32_t *iters_out, int32_t *status_out,
+                                                 int32_t *queue, const d2d_wind_field *wf, double t_start, const double *t_at = nullptr,
+                                                 const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr,
+                                                 const d2d_via_points *via = nullptr, int32_t *vwork = nullptr) {
+  const int lane = threadIdx.x;
+  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
+  double *wsb = work + (size_t)blockIdx.x * WS_TOTAL * N;
+  const int32_t *__restrict__ order = o.order;
+  for (int t = blockIdx.x; t < B;) {
+    const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
+    if ((unsigned)b >= (unsigned)B) {        // (an entry that is no problem index is skipped, not dereferenced)
+      t = nlp_next_ticket(queue, lane);
+      continue;
+    }
+    NlpOut out;
+    double t0 = t_start;
+    bool bad = false;
+    if constexpr (T_AT) {
+      t0 = 0.0;
+      if (WIND || mv->n_mov > 0) {
+        t0 = nlp_first_lane(t_at[b]);
+        bad = !(fabs(t0) <= 1.79e308);
+      }
+    }
+    [[maybe_unused]] NlpMovSet ms{nullptr, nullptr, 0};
+    if constexpr (MOV) {
+      if (mv->n_mov > 0) bad = bad || nlp_mov_bad(*mv, b, lane);
+      ms = NlpMovSet{ctr + (size_t)b * mv->n_mov * 2 * N, mv->disc + (size_t)b * mv->n_mov * 2, mv->n_mov};
+    }
+    const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE, *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
+    [[maybe_unused]] NlpViaSet vs{nullptr, nullptr, 0};
+    if constexpr (VIA) {
+      vs = NlpViaSet{via->pts + (size_t)b * via->n_via * 5, vwork + (size_t)b * N, via->n_via};
+      bad = bad || nlp_via_bad(vs.pts, vs.n, N, sc, o, bnd, lane);
+    }
+    if (bad) {
+      out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
+    } else {
+      nlp_solve_one<false, WIND, false, MOV, VIA>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
+                                                  lane, out, nullptr, nlp_lds, bnd, NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, &ms, &vs});
+    }
+    nlp_report(b, lane, out, cost_out, feas_out, iters_out, status_out);
+    nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
+    t = nlp_next_ticket(queue, lane);
+  }
+}
+
+// d2d_nlp_solve_wind: the field and one start time for the batch, a host scalar
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                      double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                      int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, double t_start) {
+  nlp_handout_body<true, false, false, false>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, t_start);
+}
+
+// d2d_nlp_solve_moving: around the problems' moving discs -- the rows' constant wind or the field (WIND), the start time per problem.
+// nlp_handout_body<WIND, true, false, true> written out: through the body the constant-wind instantiation took 256 VGPRs for its 255
+// (DESIGN 5.16), so this kernel keeps its loop and shares the ticket, the track check and the report.
 template <bool WIND>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
 nlp_solve_moving_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
@@ -1654,65 +1710,23 @@ nlp_solve_moving_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__
       const NlpMovSet ms{ctr + (size_t)b * mv.n_mov * 2 * N, mv.disc + (size_t)b * mv.n_mov * 2, mv.n_mov};
       nlp_solve_one<false, WIND, false, true>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + (size_t)b * NLP_NV * N, wsb,
                                               mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds,
-                                              o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpModel{nullptr, nullptr, nullptr}, &wf, t0, 0u, &ms);
+                                              o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpExtra{{nullptr, nullptr, nullptr}, &wf, t0, 0u, &ms, nullptr});
     }
-    if (lane == 0) {
-      cost_out[b] = out.cost;
-      feas_out[b] = out.feas;
-      if (iters_out) iters_out[b] = out.iters;
-      if (status_out) status_out[b] = out.status;
-    }
+    nlp_report(b, lane, out, cost_out, feas_out, iters_out, status_out);
     nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
     t = nlp_next_ticket(queue, lane);
   }
 }
 
-// d2d_nlp_solve_via: nlp_solve_moving_kernel's hand-out around the VIA instantiations -- the problem's pins via.pts [B][n_via][5] and
-// the plane of its nodes' fixed sets vwork [B][N].  Unusable pins refuse the problem like an unusable track.  mv.n_mov = 0: nothing moves.
+// d2d_nlp_solve_via: nlp_solve_moving_kernel through every problem's own pins
 template <bool WIND>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
 nlp_solve_via_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
                      double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
                      int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
                      d2d_moving_obstacles mv, const double *ctr, d2d_via_points via, int32_t *vwork) {
-  const int lane = threadIdx.x;
-  extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
-  double *wsb = work + (size_t)blockIdx.x * WS_TOTAL * N;
-  const int32_t *__restrict__ order = o.order;
-  for (int t = blockIdx.x; t < B;) {
-    const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
-    if ((unsigned)b >= (unsigned)B) {        // (an entry that is no problem index is skipped, not dereferenced)
-      t = nlp_next_ticket(queue, lane);
-      continue;
-    }
-    NlpOut out;
-    double t0 = 0.0;
-    bool bad = false;
-    if (WIND || mv.n_mov > 0) {
-      t0 = nlp_first_lane(t_start[b]);
-      bad = !(fabs(t0) <= 1.79e308);
-    }
-    if (mv.n_mov > 0) bad = bad || nlp_mov_bad(mv, b, lane);
-    const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE, *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
-    const NlpViaSet vs{via.pts + (size_t)b * via.n_via * 5, vwork + (size_t)b * N, via.n_via};
-    bad = bad || nlp_via_bad(vs.pts, vs.n, N, sc, o, bnd, lane);
-    if (bad) {
-      out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
-    } else {
-      const NlpMovSet ms{ctr + (size_t)b * mv.n_mov * 2 * N, mv.disc + (size_t)b * mv.n_mov * 2, mv.n_mov};
-      nlp_solve_one<false, WIND, false, true, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb,
-                                                    mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds, bnd,
-                                                    NlpModel{nullptr, nullptr, nullptr}, &wf, t0, 0u, &ms, &vs);
-    }
-    if (lane == 0) {
-      cost_out[b] = out.cost;
-      feas_out[b] = out.feas;
-      if (iters_out) iters_out[b] = out.iters;
-      if (status_out) status_out[b] = out.status;
-    }
-    nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
-    t = nlp_next_ticket(queue, lane);
-  }
+  nlp_handout_body<WIND, true, true, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, 0.0, t_start,
+                                           &mv, ctr, &via, vwork);
 }
 
 // A scenario of the group loop is refused: all its aircraft at once, before the workgroup's first barrier (the caller returns).
@@ -1854,10 +1868,9 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
   int iters_total = 0;
   double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
   const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
-  const NlpModel no_model{nullptr, nullptr, nullptr};
-  if constexpr (VIA) nlp_solve_one<false, WIND, PAIRS, MOV, true>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, 0u, msp, vsp);
-  else
-  nlp_solve_one<false, WIND, PAIRS, MOV>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, 0u, msp);
+  NlpExtra ex{{nullptr, nullptr, nullptr}, wf, t0, 0u, msp, vsp};      // sweep 0: no partner
+  nlp_solve_one<false, WIND, PAIRS, MOV, VIA>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
+  ex.pmask = pmask;
   iters_total += out.iters;
   if (threadIdx.x < (PAIRS ? 8 : 2)) moved_s[threadIdx.x] = 0.0;
   __threadfence_block();
@@ -1874,9 +1887,7 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
           // fixed pair: the partner's x and y planes; PAIRS: the scenario's W and the set
           const double *pw = PAIRS ? Wr : W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;
           for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
-          if constexpr (VIA) nlp_solve_one<false, WIND, PAIRS, MOV, true>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, pmask, msp, vsp);
-          else
-          nlp_solve_one<false, WIND, PAIRS, MOV>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, no_model, wf, t0, pmask, msp);
+          nlp_solve_one<false, WIND, PAIRS, MOV, VIA>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
           iters_total += out.iters;
           double m = 0.0;
           for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
@@ -1978,7 +1989,7 @@ nlp_model_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restric
   const NlpModel md{m.g + pl * NLP_NV, m.H + pl * 15, m.Wc + pl * NLP_NV};
   NlpOut out;
   nlp_solve_one<true>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + pl * NLP_NV, work + pl * WS_TOTAL, mult ? mult + pl * 3 : nullptr,
-                      lane, out, nullptr, nlp_lds, o.bounds ? o.bounds + (size_t)b * 4 : nullptr, md);
+                      lane, out, nullptr, nlp_lds, o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpExtra{md});
   if (lane == 0) {
     cost_out[b] = out.cost;
     feas_out[b] = out.feas;
@@ -2004,10 +2015,47 @@ static int nlp_handout_grid(int B, const d2d_nlp_opts &o, int waves_per_simd) {
   return B < slots ? B : (slots < 1 ? 1 : slots);
 }
 
+// what the single-problem entries require alike
+static int nlp_single_check(const d2d_ctx *ctx, int B, int N, double h, const double *scen, const double *W, const double *work,
+                            const double *cost, const double *feas, const char *who) {
+  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "%s: null argument", who);
+  D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "%s: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", who, B, N, h);
+  return D2D_OK;
+}
+
+// the optional field of an entry: f and t_start go together -- when discs move (mov: the entry's table, null if it takes none) the
+// start times are there already (check_moving) and the field alone is optional
+static int nlp_field_check(const d2d_wind_field *f, const double *t_start, const d2d_moving_obstacles *mov, const char *who) {
+  if (!mov)
+    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "%s: f and t_start go together (both NULL: the rows' constant wind)", who);
+  else if (mov->n_mov == 0)
+    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "%s: without moving discs f and t_start go together (both NULL: the rows' constant wind)", who);
+  return f ? check_wind(f, who) : D2D_OK;
+}
+
+// f or no f: launch(WIND as a std::bool_constant, the field's kernel argument), so that an entry names its kernel template once
+template <typename Launch>
+static int nlp_with_field(const d2d_wind_field *f, Launch launch) {
+  return f ? launch(std::true_type{}, *f) : launch(std::false_type{}, d2d_wind_field{});
+}
+
+// a hand-out kernel's launch: the grid, the queue's reset, a wavefront and an LDS block per slot; tail: what follows the queue
+template <typename Kernel, typename... Tail>
+static int nlp_handout_launch(Kernel kernel, d2d_ctx *ctx, int B, int N, double h, const d2d_nlp_opts &o, const double *scen, double *W,
+                              double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, Tail... tail) {
+  const int grid = nlp_handout_grid(B, o, NLP_WIND_WAVES_PER_SIMD);
+  int32_t *queue = ctx->counter_dev + 2;
+  D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work, mult, cost, feas, iters,
+                     status, queue, tail...);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
 // the group loops' scratch for the positions before a turn: the tail of aircraft 0's workspace is not free, so it lives behind the workspaces
 static double *nlp_groups_prev(double *work, int R, int n_ac, int N) { return work + (size_t)R * n_ac * WS_TOTAL * N; }
 
-// what the three group entries require alike
+// what the group entries require alike
 static int nlp_groups_check(const d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, int max_sweeps, double tol,
                             const double *W, const double *work, const double *cost, const double *feas, const char *who) {
   D2D_REQUIRE(ctx && scen && W && work && cost && feas, "%s: null argument", who);
@@ -2018,9 +2066,11 @@ static int nlp_groups_check(const d2d_ctx *ctx, int R, int n_ac, int N, double h
 
 // a group kernel's launch: a workgroup per scenario, a wavefront and an LDS block per aircraft
 template <typename Kernel, typename... Args>
-static void nlp_groups_launch(Kernel kernel, d2d_ctx *ctx, int R, int n_ac, Args... args) {
+static int nlp_groups_launch(Kernel kernel, d2d_ctx *ctx, int R, int n_ac, Args... args) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NLP_LDS_DOUBLES * (int)sizeof(double));
   hipLaunchKernelGGL(kernel, dim3(R), dim3(64 * n_ac), (size_t)n_ac * NLP_LDS_DOUBLES * sizeof(double), ctx->stream, R, n_ac, args...);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
 }
 
 // a d2d_moving_obstacles argument of an entry point (include/d2d.h: what makes one D2D_EINVAL); work: the centre planes
@@ -2045,9 +2095,22 @@ static int check_via(const d2d_via_points *via, const int32_t *work, const char 
   return D2D_OK;
 }
 
-// the sampler's launch on the context's stream: a workgroup per (problem or scenario, disc)
-static void nlp_mov_sample_launch(d2d_ctx *ctx, int G, int N, double h, const double *t_start, const d2d_moving_obstacles &mov, double *ctr) {
+// the sampler's launch on the context's stream, if anything moves: a workgroup per (problem or scenario, disc)
+static int nlp_mov_sample_launch(d2d_ctx *ctx, int G, int N, double h, const double *t_start, const d2d_moving_obstacles &mov, double *ctr) {
+  if (mov.n_mov == 0) return D2D_OK;
   hipLaunchKernelGGL(nlp_mov_sample_kernel, dim3((unsigned)G * (unsigned)mov.n_mov), dim3(64), 0, ctx->stream, N, h, t_start, mov, ctr);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
+}
+
+// what the moving and via entries of either launch shape do between their argument check and their launch: the tracks, the optional
+// field, the options, the sampler
+static int nlp_moving_prologue(d2d_ctx *ctx, int G, int N, double h, const d2d_nlp_opts *opts, const d2d_wind_field *f, const double *t_start,
+                               const d2d_moving_obstacles *mov, double *mov_work, const char *who, d2d_nlp_opts *o) {
+  if (int rc = check_moving(mov, mov_work, t_start, who)) return rc;
+  if (int rc = nlp_field_check(f, t_start, mov, who)) return rc;
+  if (int rc = nlp_options(opts, who, o)) return rc;
+  return nlp_mov_sample_launch(ctx, G, N, h, t_start, *mov, mov_work);
 }
 
 extern "C" {
@@ -2096,19 +2159,12 @@ int d2d_nlp_solve(d2d_ctx *ctx, int B, int N, double h, const double *scen, cons
 
 int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
                        double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f, double t_start) {
-  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_wind: null argument");
-  D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_wind: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
+  if (int rc = nlp_single_check(ctx, B, N, h, scen, W, work, cost, feas, "d2d_nlp_solve_wind")) return rc;
   D2D_REQUIRE(fabs(t_start) <= 1.79e308, "d2d_nlp_solve_wind: t_start must be finite");
   if (int rc = check_wind(f, "d2d_nlp_solve_wind")) return rc;
   d2d_nlp_opts o;
   if (int rc = nlp_options(opts, "d2d_nlp_solve_wind", &o)) return rc;
-  const int grid = nlp_handout_grid(B, o, NLP_WIND_WAVES_PER_SIMD);
-  int32_t *queue = ctx->counter_dev + 2;
-  D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
-  hipLaunchKernelGGL(nlp_solve_wind_kernel, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work, mult, cost,
-                     feas, iters, status, queue, *f, t_start);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  return nlp_handout_launch(nlp_solve_wind_kernel, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status, *f, t_start);
 }
 
 int d2d_nlp_solve_groups(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
@@ -2117,10 +2173,8 @@ int d2d_nlp_solve_groups(d2d_ctx *ctx, int R, int n_ac, int N, double h, const d
   if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups")) return rc;
   d2d_nlp_opts o;
   if (int rc = nlp_options(opts, "d2d_nlp_solve_groups", &o)) return rc;
-  nlp_groups_launch(nlp_groups_kernel, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, nlp_groups_prev(work, R, n_ac, N), cost, feas,
-                    iters, status, sweeps, moved);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  return nlp_groups_launch(nlp_groups_kernel, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, nlp_groups_prev(work, R, n_ac, N), cost,
+                           feas, iters, status, sweeps, moved);
 }
 
 int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
@@ -2131,67 +2185,40 @@ int d2d_nlp_solve_groups_wind(d2d_ctx *ctx, int R, int n_ac, int N, double h, co
   D2D_REQUIRE(t_start, "d2d_nlp_solve_groups_wind: null t_start (a device array [R]: one start time per scenario)");
   d2d_nlp_opts o;
   if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_wind", &o)) return rc;
-  nlp_groups_launch(nlp_groups_wind_kernel, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, nlp_groups_prev(work, R, n_ac, N), cost, feas,
-                    iters, status, sweeps, moved, *f, t_start);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  return nlp_groups_launch(nlp_groups_wind_kernel, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, nlp_groups_prev(work, R, n_ac, N),
+                           cost, feas, iters, status, sweeps, moved, *f, t_start);
 }
 
 int d2d_nlp_solve_groups_pairs(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
                                double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
                                int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start) {
   if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_pairs")) return rc;
-  D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_groups_pairs: f and t_start go together (both NULL: the rows' constant wind)");
-  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_groups_pairs")) return rc; }
+  if (int rc = nlp_field_check(f, t_start, nullptr, "d2d_nlp_solve_groups_pairs")) return rc;
   d2d_nlp_opts o;
   if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_pairs", &o)) return rc;
-  double *prev = nlp_groups_prev(work, R, n_ac, N);
-  if (f)
-    nlp_groups_launch(nlp_groups_pairs_kernel<true>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
-                      sweeps, moved, *f, t_start);
-  else
-    nlp_groups_launch(nlp_groups_pairs_kernel<false>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
-                      sweeps, moved, d2d_wind_field{}, t_start);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_groups_launch(nlp_groups_pairs_kernel<decltype(wind)::value>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
+                             nlp_groups_prev(work, R, n_ac, N), cost, feas, iters, status, sweeps, moved, wf, t_start);
+  });
 }
 
 int d2d_mov_sample(d2d_ctx *ctx, int G, int N, double h, const double *t_start, const d2d_moving_obstacles *mov, double *ctr) {
   D2D_REQUIRE(ctx, "d2d_mov_sample: null argument");
   D2D_REQUIRE(G >= 1 && N >= 1 && h > 0, "d2d_mov_sample: G >= 1, N >= 1, h > 0 required (G=%d N=%d h=%g)", G, N, h);
   if (int rc = check_moving(mov, ctr, t_start, "d2d_mov_sample")) return rc;
-  if (mov->n_mov == 0) return D2D_OK;
-  nlp_mov_sample_launch(ctx, G, N, h, t_start, *mov, ctr);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  return nlp_mov_sample_launch(ctx, G, N, h, t_start, *mov, ctr);
 }
 
 int d2d_nlp_solve_moving(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
                          double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
                          const double *t_start, const d2d_moving_obstacles *mov, double *mov_work) {
-  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_moving: null argument");
-  D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_moving: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
-  if (int rc = check_moving(mov, mov_work, t_start, "d2d_nlp_solve_moving")) return rc;
-  if (mov->n_mov == 0)
-    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_moving: without moving discs f and t_start go together (both NULL: the rows' constant wind)");
-  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_moving")) return rc; }
+  if (int rc = nlp_single_check(ctx, B, N, h, scen, W, work, cost, feas, "d2d_nlp_solve_moving")) return rc;
   d2d_nlp_opts o;
-  if (int rc = nlp_options(opts, "d2d_nlp_solve_moving", &o)) return rc;
-  if (mov->n_mov > 0) {
-    nlp_mov_sample_launch(ctx, B, N, h, t_start, *mov, mov_work);
-    D2D_LAUNCH_CHECK();
-  }
-  const int grid = nlp_handout_grid(B, o, NLP_WIND_WAVES_PER_SIMD);
-  int32_t *queue = ctx->counter_dev + 2;
-  D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
-  if (f)
-    hipLaunchKernelGGL(nlp_solve_moving_kernel<true>, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work,
-                       mult, cost, feas, iters, status, queue, *f, t_start, *mov, mov_work);
-  else
-    hipLaunchKernelGGL(nlp_solve_moving_kernel<false>, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work,
-                       mult, cost, feas, iters, status, queue, d2d_wind_field{}, t_start, *mov, mov_work);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  if (int rc = nlp_moving_prologue(ctx, B, N, h, opts, f, t_start, mov, mov_work, "d2d_nlp_solve_moving", &o)) return rc;
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_handout_launch(nlp_solve_moving_kernel<decltype(wind)::value>, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status, wf,
+                              t_start, *mov, (const double *)mov_work);
+  });
 }
 
 int d2d_nlp_solve_groups_moving(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
@@ -2199,25 +2226,13 @@ int d2d_nlp_solve_groups_moving(d2d_ctx *ctx, int R, int n_ac, int N, double h, 
                                 int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
                                 const d2d_moving_obstacles *mov, double *mov_work) {
   if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_moving")) return rc;
-  if (int rc = check_moving(mov, mov_work, t_start, "d2d_nlp_solve_groups_moving")) return rc;
-  if (mov->n_mov == 0)
-    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_groups_moving: without moving discs f and t_start go together (both NULL: the rows' constant wind)");
-  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_groups_moving")) return rc; }
   d2d_nlp_opts o;
-  if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_moving", &o)) return rc;
-  if (mov->n_mov > 0) {
-    nlp_mov_sample_launch(ctx, R, N, h, t_start, *mov, mov_work);
-    D2D_LAUNCH_CHECK();
-  }
-  double *prev = nlp_groups_prev(work, R, n_ac, N);
-  if (f)
-    nlp_groups_launch(nlp_groups_moving_kernel<true>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
-                      sweeps, moved, *f, t_start, *mov, (const double *)mov_work);
-  else
-    nlp_groups_launch(nlp_groups_moving_kernel<false>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
-                      sweeps, moved, d2d_wind_field{}, t_start, *mov, (const double *)mov_work);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  if (int rc = nlp_moving_prologue(ctx, R, N, h, opts, f, t_start, mov, mov_work, "d2d_nlp_solve_groups_moving", &o)) return rc;
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_groups_launch(nlp_groups_moving_kernel<decltype(wind)::value>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
+                             nlp_groups_prev(work, R, n_ac, N), cost, feas, iters, status, sweeps, moved, wf, t_start, *mov,
+                             (const double *)mov_work);
+  });
 }
 
 int d2d_nlp_solve_via(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
@@ -2228,29 +2243,13 @@ int d2d_nlp_solve_via(d2d_ctx *ctx, int B, int N, double h, const double *scen, 
   if (int rc = check_via(via, via_work, "d2d_nlp_solve_via")) return rc;
   if (via->n_via == 0)                                     // no pins: the solve of d2d_nlp_solve_moving, its kernels and its checks
     return d2d_nlp_solve_moving(ctx, B, N, h, scen, opts, W, work, mult, cost, feas, iters, status, f, t_start, mov, mov_work);
-  D2D_REQUIRE(ctx && scen && W && work && cost && feas, "d2d_nlp_solve_via: null argument");
-  D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve_via: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
-  if (int rc = check_moving(mov, mov_work, t_start, "d2d_nlp_solve_via")) return rc;
-  if (mov->n_mov == 0)
-    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_via: without moving discs f and t_start go together (both NULL: the rows' constant wind)");
-  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_via")) return rc; }
+  if (int rc = nlp_single_check(ctx, B, N, h, scen, W, work, cost, feas, "d2d_nlp_solve_via")) return rc;
   d2d_nlp_opts o;
-  if (int rc = nlp_options(opts, "d2d_nlp_solve_via", &o)) return rc;
-  if (mov->n_mov > 0) {
-    nlp_mov_sample_launch(ctx, B, N, h, t_start, *mov, mov_work);
-    D2D_LAUNCH_CHECK();
-  }
-  const int grid = nlp_handout_grid(B, o, NLP_WIND_WAVES_PER_SIMD);
-  int32_t *queue = ctx->counter_dev + 2;
-  D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
-  if (f)
-    hipLaunchKernelGGL(nlp_solve_via_kernel<true>, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work,
-                       mult, cost, feas, iters, status, queue, *f, t_start, *mov, (const double *)mov_work, *via, via_work);
-  else
-    hipLaunchKernelGGL(nlp_solve_via_kernel<false>, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, W, work,
-                       mult, cost, feas, iters, status, queue, d2d_wind_field{}, t_start, *mov, (const double *)mov_work, *via, via_work);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  if (int rc = nlp_moving_prologue(ctx, B, N, h, opts, f, t_start, mov, mov_work, "d2d_nlp_solve_via", &o)) return rc;
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_handout_launch(nlp_solve_via_kernel<decltype(wind)::value>, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status, wf,
+                              t_start, *mov, (const double *)mov_work, *via, via_work);
+  });
 }
 
 int d2d_nlp_solve_groups_via(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
@@ -2264,25 +2263,13 @@ int d2d_nlp_solve_groups_via(d2d_ctx *ctx, int R, int n_ac, int N, double h, con
     return d2d_nlp_solve_groups_moving(ctx, R, n_ac, N, h, scen, opts, max_sweeps, tol, W, work, mult, cost, feas, iters, status, sweeps, moved, f,
                                        t_start, mov, mov_work);
   if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_via")) return rc;
-  if (int rc = check_moving(mov, mov_work, t_start, "d2d_nlp_solve_groups_via")) return rc;
-  if (mov->n_mov == 0)
-    D2D_REQUIRE((f == nullptr) == (t_start == nullptr), "d2d_nlp_solve_groups_via: without moving discs f and t_start go together (both NULL: the rows' constant wind)");
-  if (f) { if (int rc = check_wind(f, "d2d_nlp_solve_groups_via")) return rc; }
   d2d_nlp_opts o;
-  if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_via", &o)) return rc;
-  if (mov->n_mov > 0) {
-    nlp_mov_sample_launch(ctx, R, N, h, t_start, *mov, mov_work);
-    D2D_LAUNCH_CHECK();
-  }
-  double *prev = nlp_groups_prev(work, R, n_ac, N);
-  if (f)
-    nlp_groups_launch(nlp_groups_via_kernel<true>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
-                      sweeps, moved, *f, t_start, *mov, (const double *)mov_work, *via, via_work);
-  else
-    nlp_groups_launch(nlp_groups_via_kernel<false>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost, feas, iters, status,
-                      sweeps, moved, d2d_wind_field{}, t_start, *mov, (const double *)mov_work, *via, via_work);
-  D2D_LAUNCH_CHECK();
-  return D2D_OK;
+  if (int rc = nlp_moving_prologue(ctx, R, N, h, opts, f, t_start, mov, mov_work, "d2d_nlp_solve_groups_via", &o)) return rc;
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_groups_launch(nlp_groups_via_kernel<decltype(wind)::value>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
+                             nlp_groups_prev(work, R, n_ac, N), cost, feas, iters, status, sweeps, moved, wf, t_start, *mov,
+                             (const double *)mov_work, *via, via_work);
+  });
 }
 
 }  // extern "C"

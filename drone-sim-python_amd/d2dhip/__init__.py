@@ -245,6 +245,9 @@ def _torch():
     return torch
 
 
+_ABSENT = object()      # an optional input that an entry point does not take (None is a value: no field, nothing moves, no pins)
+
+
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -519,72 +522,83 @@ class Context:
             _check(self.lib.d2d_sim_dfff_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
 
+    def _nlp_core(self, entry, scen, W, h, opts, bounds, n_ac=None, sweeps=None, want_mult=False, slots=0, order=None, mid=(),
+                  field=_ABSENT, t_start=None, t_scalar=False, moving=_ABSENT, via=_ABSENT):
+        """What the nlp_solve* methods share: the shape checks, the workspace and the outputs, d2d_nlp_opts from opts = (rho0, mub0,
+        mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), the call of `entry` and the result.  n_ac: a group entry (sweeps =
+        (max_sweeps, tol)), R = B / n_ac scenarios with one start time and one set of tracks each; else B problems.  mid: arguments
+        between W and work.  field, moving = (knots, disc), via: the optional inputs in the entries' order, _ABSENT where the entry takes
+        none (it takes t_start with the field: a device array, or with t_scalar a float); each adds its entries to the result."""
+        torch = _torch()
+        B, _, N = W.shape
+        groups = n_ac is not None
+        assert W.is_contiguous() and scen.shape[0] == B and (not groups or B % n_ac == 0)
+        G = B // n_ac if groups else B
+        ws = self.lib.d2d_nlp_workspace_doubles(N)
+        m = None if moving is _ABSENT else self._moving_c(*moving, G)
+        v = None if via is _ABSENT else self._via_c(via, B)
+        if field is not _ABSENT and not t_scalar:
+            t_start = self._t_start_dev(t_start, G, W)
+        work = self.empty((ws * n_ac + 2 * N) * G if groups else ws * B)
+        cost, feas = self.empty(B), self.empty(B)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
+        mult = self.zeros(B, 3, N) if want_mult else None
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        assert order is None or (order.is_contiguous() and tuple(order.shape) == (B,) and order.dtype == torch.int32)
+        o = NlpOpts(*opts, int(slots), None if bounds is None else bounds.data_ptr(), None if order is None else order.data_ptr())
+        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work)
+        args = [_ptr(work), _ptr(mult), _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status)]
+        if groups:
+            out['sweeps'], out['moved'] = torch.empty(G, dtype=torch.int32, device=self.device), self.empty(G)
+            args = [self.h, G, n_ac, N, float(h), _ptr(scen), C.byref(o), int(sweeps[0]), float(sweeps[1]), _ptr(W)] + args + [_ptr(out['sweeps']), _ptr(out['moved'])]
+        else:
+            args = [self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), *mid] + args
+        if field is not _ABSENT:
+            f = None if field is None else _wind_c(self, field)
+            args += [None if f is None else C.byref(f), float(t_start) if t_scalar else _ptr(t_start)]
+            if not t_scalar:
+                out['t_start'] = t_start
+            if groups:
+                # prev [R][2][N]: the kernel's scratch behind the workspaces; it is left holding the x, y planes aircraft 1 had BEFORE its
+                # last turn, i.e. the frozen partner that aircraft 0's last solve (and its reported cost) saw
+                out['prev'] = work[ws * n_ac * G:].view(G, 2, N)
+        if m is not None:
+            out['mov_work'] = self.empty(G, m.n_mov, 2, N) if m.n_mov > 0 else None
+            args += [C.byref(m), _ptr(out['mov_work'])]
+        if v is not None:
+            out['via_work'] = torch.zeros(B, N, dtype=torch.int32, device=self.device) if v.n_via > 0 else None
+            args += [C.byref(v), _ptr(out['via_work'])]
+        _check(entry(*args))
+        if want_mult:
+            out['mult'] = mult
+        return out
+
     def nlp_solve(self, scen, W, h, partner=None, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
                   outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None, slots=0, order=None):
         """Direct-collocation NLP in node variables (d2d_nlp_solve): scen dev [B][SCEN_STRIDE], W dev [B][5][N] in/out (initial
         guess -> solution), partner dev [B][2][N] or None, bounds dev [B][4] = (phi_lo, phi_hi, psi_lo, psi_hi) or None (d2d_nlp_opts.bounds),
         order dev int32 [B]: the hand-out order of the persistent launch (a permutation; d2d_nlp_opts.order) or None.
         Returns dict(cost, feas, iters, status[, mult [B][3][N]]) of device tensors."""
-        torch = _torch()
         B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B and (partner is None or (partner.is_contiguous() and partner.shape == (B, 2, N)))
-        work = self.empty(self.lib.d2d_nlp_workspace_doubles(N) * B)
-        cost, feas = self.empty(B), self.empty(B)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        mult = self.zeros(B, 3, N) if want_mult else None
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == _torch().float64)
-        assert order is None or (order.is_contiguous() and tuple(order.shape) == (B,) and order.dtype == torch.int32)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, int(slots), None if bounds is None else bounds.data_ptr(),
-                    None if order is None else order.data_ptr())
-        _check(self.lib.d2d_nlp_solve(self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), _ptr(partner), _ptr(work), _ptr(mult),
-                                      _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status)))
-        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work)
-        if want_mult:
-            out['mult'] = mult
-        return out
+        assert partner is None or (partner.is_contiguous() and partner.shape == (B, 2, N))
+        return self._nlp_core(self.lib.d2d_nlp_solve, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
+                              want_mult=want_mult, slots=slots, order=order, mid=(_ptr(partner),))
 
     def nlp_solve_wind(self, scen, W, h, field, t_start=0.0, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7,
                        inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None, slots=0, order=None):
         """nlp_solve with the wind of the equalities read from `field` (a d2d.wind.SplineWindField or a WindFieldC) at every node's own
         (t_start + i h, x_i, y_i) instead of the rows' constant (d2d_nlp_solve_wind; no partner).  The model ADDS the field to its
         residual: a plan for a plant that flies F is solved in -F.  Returns dict(cost, feas, iters, status[, mult]) of device tensors."""
-        torch = _torch()
-        B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B
-        work = self.empty(self.lib.d2d_nlp_workspace_doubles(N) * B)
-        cost, feas = self.empty(B), self.empty(B)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        mult = self.zeros(B, 3, N) if want_mult else None
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
-        assert order is None or (order.is_contiguous() and tuple(order.shape) == (B,) and order.dtype == torch.int32)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, int(slots), None if bounds is None else bounds.data_ptr(),
-                    None if order is None else order.data_ptr())
-        f = None if field is None else _wind_c(self, field)
-        _check(self.lib.d2d_nlp_solve_wind(self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), _ptr(work), _ptr(mult), _ptr(cost),
-                                           _ptr(feas), _ptr(iters), _ptr(status), None if f is None else C.byref(f), float(t_start)))
-        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work)
-        if want_mult:
-            out['mult'] = mult
-        return out
+        return self._nlp_core(self.lib.d2d_nlp_solve_wind, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
+                              want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, t_scalar=True)
 
     def nlp_solve_groups(self, scen, W, h, n_ac, max_sweeps=12, tol=1e-7, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7,
                          inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0, bounds=None):
         """The reference's multi-aircraft Problem for R scenarios in one launch (d2d_nlp_solve_groups): scen dev [R*n_ac][SCEN_STRIDE],
         W dev [R*n_ac][5][N] in/out, the aircraft of a scenario consecutive; CostCollision couples aircraft 0 and 1 (rows' KCOL > 0).
         Returns dict(cost, feas, iters, status per aircraft; sweeps, moved per scenario) of device tensors."""
-        torch = _torch()
-        B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
-        R = B // n_ac
-        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
-        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == _torch().float64)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
-        _check(self.lib.d2d_nlp_solve_groups(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W), _ptr(work),
-                                             None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps), _ptr(moved)))
-        return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work)
+        return self._nlp_core(self.lib.d2d_nlp_solve_groups, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
+                              n_ac=n_ac, sweeps=(max_sweeps, tol))
 
     def nlp_solve_groups_wind(self, scen, W, h, n_ac, field, t_start, max_sweeps=12, tol=1e-7, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9,
                               opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0, bounds=None):
@@ -593,27 +607,8 @@ class Context:
         one start time per scenario (a float is spread over the scenarios).  The model ADDS the field to its residual: a plan for a
         plant that flies F is solved in -F.  Returns nlp_solve_groups's dict plus t_start and prev [R][2][N] (coupled scenarios: the
         positions of aircraft 1 before its last turn -- the partner the reported cost of aircraft 0 was evaluated against)."""
-        torch = _torch()
-        B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
-        R = B // n_ac
-        if t_start is not None and not torch.is_tensor(t_start):
-            t_start = torch.full((R,), float(t_start), dtype=torch.float64, device=self.device)
-        assert t_start is None or (t_start.is_contiguous() and tuple(t_start.shape) == (R,) and t_start.dtype == torch.float64 and t_start.device == W.device)
-        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
-        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
-        f = None if field is None else _wind_c(self, field)
-        _check(self.lib.d2d_nlp_solve_groups_wind(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W),
-                                                  _ptr(work), None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps), _ptr(moved),
-                                                  None if f is None else C.byref(f), _ptr(t_start)))
-        # prev [R][2][N]: the kernel's scratch behind the workspaces; it is left holding the x, y planes aircraft 1 had BEFORE its last
-        # turn, i.e. the frozen partner that aircraft 0's last solve (and its reported cost) saw
-        prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
-        return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev)
+        return self._nlp_core(self.lib.d2d_nlp_solve_groups_wind, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial),
+                              bounds, n_ac=n_ac, sweeps=(max_sweeps, tol), field=field, t_start=t_start)
 
     def nlp_solve_groups_pairs(self, scen, W, h, n_ac, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0, mub0=0.1, mub_min=1e-9,
                                feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0, bounds=None):
@@ -622,28 +617,12 @@ class Context:
         the frozen positions of all of them.  field None: the rows' constant wind (t_start is not read); else as nlp_solve_groups_wind.
         A scenario with a malformed mask (no integer in [0, 2^n_ac), a self bit, a bit its partner does not return) is refused on the
         device: status ST_NONFINITE, cost = feas = NaN, sweeps 0, its W untouched.  Returns nlp_solve_groups_wind's dict."""
-        torch = _torch()
-        B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
-        R = B // n_ac
         if field is None:
             t_start = None
-        else:
-            if not torch.is_tensor(t_start):
-                t_start = torch.full((R,), float(0.0 if t_start is None else t_start), dtype=torch.float64, device=self.device)
-            assert t_start.is_contiguous() and tuple(t_start.shape) == (R,) and t_start.dtype == torch.float64 and t_start.device == W.device
-        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
-        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
-        f = None if field is None else _wind_c(self, field)
-        _check(self.lib.d2d_nlp_solve_groups_pairs(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W),
-                                                   _ptr(work), None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps), _ptr(moved),
-                                                   None if f is None else C.byref(f), _ptr(t_start)))
-        prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
-        return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev)
+        elif t_start is None:
+            t_start = 0.0
+        return self._nlp_core(self.lib.d2d_nlp_solve_groups_pairs, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial),
+                              bounds, n_ac=n_ac, sweeps=(max_sweeps, tol), field=field, t_start=t_start)
 
     def _moving_c(self, knots, disc, G):
         """d2d_moving_obstacles over device tables: knots [G][n_mov][n_knot][3] and disc [G][n_mov][2], or (None, None): nothing moves.
@@ -681,28 +660,8 @@ class Context:
         float: the problems' start times (required when discs move or with a field).  A problem with an unusable track or start time is
         refused on the device: status ST_NONFINITE, cost = feas = NaN, its W untouched.  Returns nlp_solve's dict plus mov_work
         [B][n_mov][2][N]: the discs' centres at the node times."""
-        torch = _torch()
-        B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B
-        m = self._moving_c(knots, disc, B)
-        t_start = self._t_start_dev(t_start, B, W)
-        work = self.empty(self.lib.d2d_nlp_workspace_doubles(N) * B)
-        mov_work = self.empty(B, m.n_mov, 2, N) if m.n_mov > 0 else None
-        cost, feas = self.empty(B), self.empty(B)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        mult = self.zeros(B, 3, N) if want_mult else None
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
-        assert order is None or (order.is_contiguous() and tuple(order.shape) == (B,) and order.dtype == torch.int32)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, int(slots), None if bounds is None else bounds.data_ptr(),
-                    None if order is None else order.data_ptr())
-        f = None if field is None else _wind_c(self, field)
-        _check(self.lib.d2d_nlp_solve_moving(self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), _ptr(work), _ptr(mult), _ptr(cost),
-                                             _ptr(feas), _ptr(iters), _ptr(status), None if f is None else C.byref(f), _ptr(t_start),
-                                             C.byref(m), _ptr(mov_work)))
-        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work, mov_work=mov_work, t_start=t_start)
-        if want_mult:
-            out['mult'] = mult
-        return out
+        return self._nlp_core(self.lib.d2d_nlp_solve_moving, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
+                              want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, moving=(knots, disc))
 
     def nlp_solve_groups_moving(self, scen, W, h, n_ac, knots=None, disc=None, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0,
                                 mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0,
@@ -711,26 +670,8 @@ class Context:
         [R][n_mov][2] per SCENARIO -- all its aircraft see the same tracks -- and t_start dev [R] or a float (required when discs move
         or with a field).  A scenario with an unusable track is refused like one with a malformed mask.  Returns
         nlp_solve_groups_pairs's dict plus mov_work [R][n_mov][2][N]."""
-        torch = _torch()
-        B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
-        R = B // n_ac
-        m = self._moving_c(knots, disc, R)
-        t_start = self._t_start_dev(t_start, R, W)
-        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
-        mov_work = self.empty(R, m.n_mov, 2, N) if m.n_mov > 0 else None
-        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
-        f = None if field is None else _wind_c(self, field)
-        _check(self.lib.d2d_nlp_solve_groups_moving(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W),
-                                                    _ptr(work), None, _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps),
-                                                    _ptr(moved), None if f is None else C.byref(f), _ptr(t_start), C.byref(m), _ptr(mov_work)))
-        prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
-        return dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev,
-                    mov_work=mov_work)
+        return self._nlp_core(self.lib.d2d_nlp_solve_groups_moving, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial),
+                              bounds, n_ac=n_ac, sweeps=(max_sweeps, tol), field=field, t_start=t_start, moving=(knots, disc))
 
     def _via_c(self, via, G):
         """d2d_via_points over a device table [G][n_via][5] = (node, mask, x, y, psi), or None: no pins.  Shapes only -- the range of
@@ -750,30 +691,8 @@ class Context:
         A problem with an unusable row (node outside 1 .. N-2, mask outside 0 .. 7, a non-finite or out-of-box value, a component pinned
         twice) is refused on the device: status ST_NONFINITE, cost = feas = NaN, its W untouched.  The pinned components of the returned
         W hold their values exactly.  Returns nlp_solve_moving's dict plus via_work int32 [B][N]: the fixed set of every node."""
-        torch = _torch()
-        B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B
-        m = self._moving_c(knots, disc, B)
-        v = self._via_c(via, B)
-        t_start = self._t_start_dev(t_start, B, W)
-        work = self.empty(self.lib.d2d_nlp_workspace_doubles(N) * B)
-        mov_work = self.empty(B, m.n_mov, 2, N) if m.n_mov > 0 else None
-        via_work = torch.zeros(B, N, dtype=torch.int32, device=self.device) if v.n_via > 0 else None
-        cost, feas = self.empty(B), self.empty(B)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        mult = self.zeros(B, 3, N) if want_mult else None
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
-        assert order is None or (order.is_contiguous() and tuple(order.shape) == (B,) and order.dtype == torch.int32)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, int(slots), None if bounds is None else bounds.data_ptr(),
-                    None if order is None else order.data_ptr())
-        f = None if field is None else _wind_c(self, field)
-        _check(self.lib.d2d_nlp_solve_via(self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), _ptr(work), _ptr(mult), _ptr(cost),
-                                          _ptr(feas), _ptr(iters), _ptr(status), None if f is None else C.byref(f), _ptr(t_start),
-                                          C.byref(m), _ptr(mov_work), C.byref(v), _ptr(via_work)))
-        out = dict(cost=cost, feas=feas, iters=iters, status=status, work=work, mov_work=mov_work, t_start=t_start, via_work=via_work)
-        if want_mult:
-            out['mult'] = mult
-        return out
+        return self._nlp_core(self.lib.d2d_nlp_solve_via, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
+                              want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, moving=(knots, disc), via=via)
 
     def nlp_solve_groups_via(self, scen, W, h, n_ac, via, knots=None, disc=None, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0,
                              mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0,
@@ -782,33 +701,9 @@ class Context:
         rows (None: no pins); knots / disc per scenario as before.  An unusable row of any aircraft refuses its whole scenario, like a
         malformed mask.  Returns nlp_solve_groups_moving's dict plus via_work int32 [R*n_ac][N] and, with want_mult, mult [R*n_ac][3][N]:
         the scaled multiplier estimates of every aircraft's last solve."""
-        torch = _torch()
-        B, _, N = W.shape
-        assert W.is_contiguous() and scen.shape[0] == B and B % n_ac == 0
-        R = B // n_ac
-        m = self._moving_c(knots, disc, R)
-        v = self._via_c(via, B)
-        t_start = self._t_start_dev(t_start, R, W)
-        work = self.empty((self.lib.d2d_nlp_workspace_doubles(N) * n_ac + 2 * N) * R)
-        mov_work = self.empty(R, m.n_mov, 2, N) if m.n_mov > 0 else None
-        via_work = torch.zeros(B, N, dtype=torch.int32, device=self.device) if v.n_via > 0 else None
-        cost, feas, moved = self.empty(B), self.empty(B), self.empty(R)
-        iters = torch.empty(B, dtype=torch.int32, device=self.device); status = torch.empty(B, dtype=torch.int32, device=self.device)
-        sweeps = torch.empty(R, dtype=torch.int32, device=self.device)
-        mult = self.zeros(B, 3, N) if want_mult else None
-        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
-        o = NlpOpts(rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial, 0, None if bounds is None else bounds.data_ptr(), None)
-        f = None if field is None else _wind_c(self, field)
-        _check(self.lib.d2d_nlp_solve_groups_via(self.h, R, n_ac, N, float(h), _ptr(scen), C.byref(o), int(max_sweeps), float(tol), _ptr(W),
-                                                 _ptr(work), _ptr(mult), _ptr(cost), _ptr(feas), _ptr(iters), _ptr(status), _ptr(sweeps),
-                                                 _ptr(moved), None if f is None else C.byref(f), _ptr(t_start), C.byref(m), _ptr(mov_work),
-                                                 C.byref(v), _ptr(via_work)))
-        prev = work[self.lib.d2d_nlp_workspace_doubles(N) * n_ac * R:].view(R, 2, N)
-        out = dict(cost=cost, feas=feas, iters=iters, status=status, sweeps=sweeps, moved=moved, work=work, t_start=t_start, prev=prev,
-                   mov_work=mov_work, via_work=via_work)
-        if want_mult:
-            out['mult'] = mult
-        return out
+        return self._nlp_core(self.lib.d2d_nlp_solve_groups_via, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial),
+                              bounds, n_ac=n_ac, sweeps=(max_sweeps, tol), want_mult=want_mult, field=field, t_start=t_start, moving=(knots, disc),
+                              via=via)
 
     def nlp_solve_model(self, scen, W, h, g, H, Wc, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
                         outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None):

@@ -212,6 +212,50 @@ def test_batches_and_repeats_are_bitwise(ctx, fields):
 
 
 @pytest.mark.parametrize('wind', ['const', 'gust'])
+def test_fewer_slots_than_problems_and_the_order_only_schedule(ctx, fields, wind):
+    """5b. The hand-out loop of the moving kernels: six problems of 41 nodes by the catalogue's rule (4 s legs: 48 m in still air, 32 m
+    in the gust), problem 3's track with times that do not increase.  (a) index order, default slots; (b) two slots and the reversed
+    order: a slot takes a third ticket, the refused problem lies between two solved ones -- W, cost, feas, iters, status equal (a)
+    bitwise; (c) two slots and the order with problem 1's entry replaced by an index outside [0, B): the others equal (a) bitwise,
+    problem 1 keeps its guess (its outputs are not written: compared only where defined).  The refused problem: ST_NONFINITE, NaN cost,
+    W bitwise its guess, in every run."""
+    import torch
+    import d2dhip as D
+    n, B, BAD, DROP = 41, 6, 3, 1
+    leg, t0, F = (48.0, 0.0, None) if wind == 'const' else (32.0, M.GUST_T_START, fields['gust'])
+    kinds, names = (1, 1, 1, 0, 0, 0), ('crossing', 'headon', 'two') * 2
+    rows = np.stack([M.row(k, p1=(leg, 0.0, 0.0), N=n) for k in kinds])
+    mv = [M.catalogue(k, t0, leg)[nm] + ([MovingObstacle.linear((0, 0), (0, 0), -1.0)] if nm != 'two' else []) for k, nm in zip(kinds, names)]
+    kn, dc = M.tables(mv)
+    kn[BAD, 0, 1, 0] = kn[BAD, 0, 0, 0]
+    W0 = np.stack([M.straight_guess(r, n).T for r in rows])
+    dsc, dkn, ddc, dts = ctx.dev(rows), ctx.dev(kn), ctx.dev(dc), ctx.dev(t0 + 0.25 * np.arange(B))
+
+    def run(**kw):
+        W = ctx.dev(W0.copy())
+        out = ctx.nlp_solve_moving(dsc, W, H, dkn, ddc, F, dts, **kw)
+        ctx.sync()
+        return W.cpu().numpy(), _np(out)
+
+    def order(perm):
+        return torch.from_numpy(np.asarray(perm, dtype=np.int32)).to(ctx.device)
+
+    rev = np.arange(B)[::-1].copy()
+    dropped = rev.copy(); dropped[rev == DROP] = B
+    Wa, oa = run()
+    Wb, ob = run(slots=2, order=order(rev))
+    Wc, oc = run(slots=2, order=order(dropped))
+    print(f'{wind}: status {oa["status"]}, steps {oa["iters"]}')
+    assert (np.delete(oa['status'], BAD) != D.ST_NONFINITE).all()
+    assert Wb.tobytes() == Wa.tobytes() and all(ob[k].tobytes() == oa[k].tobytes() for k in OUT)
+    keep = np.arange(B) != DROP
+    assert Wc[keep].tobytes() == Wa[keep].tobytes() and all(oc[k][keep].tobytes() == oa[k][keep].tobytes() for k in OUT)
+    assert np.array_equal(Wc[DROP], W0[DROP])
+    for W, out in ((Wa, oa), (Wb, ob), (Wc, oc)):
+        assert out['status'][BAD] == D.ST_NONFINITE and np.isnan(out['cost'][BAD]) and np.array_equal(W[BAD], W0[BAD])
+
+
+@pytest.mark.parametrize('wind', ['const', 'gust'])
 def test_groups_against_the_cpu_statement(ctx, fields, wind):
     """6. Two four-aircraft crossings, all six pairs coupled, one moving disc through each, one launch: statuses and sweep counts
     equal the statement's, every aircraft within the family tolerances."""

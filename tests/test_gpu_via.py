@@ -241,6 +241,52 @@ def test_batch_equals_each_problem_alone_and_repeats(ctx):
         assert np.array_equal(W1[0], W[b]) and all(o1[k][0] == out[k][b] for k in ('cost', 'feas', 'iters', 'status')), b
 
 
+@pytest.mark.parametrize('wind', ['const', 'gust'])
+def test_fewer_slots_than_problems_and_the_order_only_schedule(ctx, fields, wind):
+    """6b. The hand-out loop of the via kernels: six problems of 41 nodes, the catalogue's pins moved to a 4 s leg (48 m in still air,
+    32 m in the gust: point, heading, yonly, a pin on node 0, psionly, last), so problem 3 is unusable.  (a) index order, default
+    slots; (b) two slots and the reversed order: a slot takes a third ticket, the refused problem lies between two solved ones -- W,
+    cost, feas, iters, status equal (a) bitwise; (c) two slots and the order with problem 1's entry replaced by an index outside
+    [0, B): the others equal (a) bitwise, problem 1 keeps its guess (its outputs are not written: compared only where defined).  The
+    refused problem: ST_NONFINITE, NaN cost, W bitwise its guess, in every run."""
+    import torch
+    import d2dhip as D
+    n, B, BAD, DROP = 41, 6, 3, 1
+    OUT = ('cost', 'feas', 'iters', 'status')
+    leg, t0, F, dy = (48.0, 0.0, None, 5.0) if wind == 'const' else (32.0, V.GUST_T_START, fields['gust'], 3.0)
+    r = M.row(1, p1=(leg, 0.0, 0.0), N=n, kobs=0.0)
+    mid, step = (n - 1) // 2, leg / (n - 1)
+    tabs = [V.rows_of((mid, {0: leg / 2, 1: dy})), V.rows_of((mid, {0: leg / 2, 1: dy, 2: 0.0})), V.rows_of((mid, {1: 0.6 * dy})),
+            V.rows_of((0, {0: 0.0, 1: 0.0})), V.rows_of((mid, {2: 0.2})), V.rows_of((n - 2, {0: leg - step, 1: 0.0}))]
+    rows = np.stack([r] * B)
+    W0 = np.stack([(V.guess(r, tab, n) if b != BAD else M.straight_guess(r, n)).T for b, tab in enumerate(tabs)])
+    dsc, dvia = ctx.dev(rows), ctx.dev(np.ascontiguousarray(V.tables(tabs)))
+    dts = None if F is None else ctx.dev(t0 + 0.25 * np.arange(B))
+
+    def run(**kw):
+        W = ctx.dev(W0.copy())
+        out = ctx.nlp_solve_via(dsc, W, H, dvia, None, None, F, dts, **kw)
+        ctx.sync()
+        return W.cpu().numpy(), _np(out)
+
+    def order(perm):
+        return torch.from_numpy(np.asarray(perm, dtype=np.int32)).to(ctx.device)
+
+    rev = np.arange(B)[::-1].copy()
+    dropped = rev.copy(); dropped[rev == DROP] = -1
+    Wa, oa = run()
+    Wb, ob = run(slots=2, order=order(rev))
+    Wc, oc = run(slots=2, order=order(dropped))
+    print(f'{wind}: status {oa["status"]}, steps {oa["iters"]}')
+    assert (np.delete(oa['status'], BAD) != D.ST_NONFINITE).all()
+    assert Wb.tobytes() == Wa.tobytes() and all(ob[k].tobytes() == oa[k].tobytes() for k in OUT)
+    keep = np.arange(B) != DROP
+    assert Wc[keep].tobytes() == Wa[keep].tobytes() and all(oc[k][keep].tobytes() == oa[k][keep].tobytes() for k in OUT)
+    assert np.array_equal(Wc[DROP], W0[DROP])
+    for W, out in ((Wa, oa), (Wb, ob), (Wc, oc)):
+        assert out['status'][BAD] == D.ST_NONFINITE and np.isnan(out['cost'][BAD]) and np.array_equal(W[BAD], W0[BAD])
+
+
 def test_a_pin_on_the_unpinned_plan_changes_nothing(ctx):
     """6. Pinning node 30 where the unpinned solve passes gives that plan again, to the statement's tolerances."""
     r = M.row(1, p1=(M.LEG, 0.0, 0.0))
