@@ -245,6 +245,9 @@ __device__ __forceinline__ void knot_mfma_so(const KnotGeom &kg, const unsigned 
   const int m = 4 * (c >> 3) + (c & 3);
   const bool ay = ((c >> 2) & 1) != 0, row_y = (rho & 1) != 0, row_2 = rho >= 2;
   const int tab = hb32_off + 4 * m * 4;
+  // the lane's axis picks the (x | y) half of the row record and the x | y word of the position record: by ADDRESS, formed once per
+  // evaluation (one 8-byte and one 4-byte read per sample), not by selects on a quad and a pair per sample -- the same words
+  const int reco = cf_off + rho * 16 + (ay ? 8 : 0), rpo = cfp_off + (rho & 1) * 8 + (ay ? 4 : 0);
 #pragma unroll
   for (int s = 0; s < D2D_FIT_MAX_S; ++s) {
 #pragma unroll
@@ -254,19 +257,19 @@ __device__ __forceinline__ void knot_mfma_so(const KnotGeom &kg, const unsigned 
     LAUNDER_S(k1); LAUNDER_S(k);
     if (k < k1) {
       f32x4 hb = lds_get<f32x4>(lds + tab + k * 128);                      // d0, d1, d2, -
-      f32x4 rec = lds_get<f32x4>(lds + cf_off + (k * 4 + rho) * 16);
-      float2 rp = lds_get<float2>(lds + cfp_off + (k * 2 + (rho & 1)) * 8);
+      float2 rec = lds_get<float2>(lds + reco + k * 64);
+      float rp = lds_get<float>(lds + rpo + k * 16);
       for (; k < k1; ++k) {
         const int kn = k + 1 < k1 ? k + 1 : k;                             // the next sample's records: requested before this one's k-steps
         const f32x4 hbn = lds_get<f32x4>(lds + tab + kn * 128);
-        const f32x4 recn = lds_get<f32x4>(lds + cf_off + (kn * 4 + rho) * 16);
-        const float2 rpn = lds_get<float2>(lds + cfp_off + (kn * 2 + (rho & 1)) * 8);
+        const float2 recn = lds_get<float2>(lds + reco + kn * 64);
+        const float rpn = lds_get<float>(lds + rpo + kn * 16);
         const float h0 = hb.x, h1 = hb.y, h2 = hb.z;
-        const float cx = ay ? rec.z : rec.x, cy = ay ? rec.w : rec.y;
+        const float cx = rec.x, cy = rec.y;
         const float vb = fmaf(cy, h2, cx * h1);
         const float va = (row_y == ay) ? (row_2 ? h2 : h1) : 0.f;
         acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(va, vb, acc[s], 0, 0, 0);
-        const float vbp = row_2 ? 0.f : (ay ? rp.y : rp.x) * h0;
+        const float vbp = row_2 ? 0.f : rp * h0;
         const float vap = (!row_2 && row_y == ay) ? h0 : 0.f;
         acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(vap, vbp, acc[s], 0, 0, 0);
         hb = hbn; rec = recn; rp = rpn;
@@ -369,6 +372,14 @@ struct KnotMetric {
 }  // namespace
 // (the factorisation may leave out the tiles a half-bandwidth <= 15 keeps zero: fit_phases.h damped_solve)
 template <> struct nd_is_banded<KnotMetric> { static constexpr bool value = true; };
+// (... and, inside a block column, the chunk that panel 3 never meets.  The free entries lie 4 / 8 / 8 / 8 / 8 / 8 / 4 -- knot 0 ->
+// rows 0 .. 3, knot j = 1 .. 5 -> rows 8 j - 4 .. 8 j + 3, knot 6 -> rows 44 .. 47 -- so a panel of four never straddles a knot, and
+// panel 3 of the block columns (rows 12 .. 15, 28 .. 31, 44 .. 47: the first half of the knots 2, 4, 6) faces in chunk 0 (columns
+// 0 .. 3, 16 .. 19, 32 .. 35) the knots 0, 2 (second half), 4 (second half) -- the knot BEFORE its neighbour: H_u + lam Mu is block
+// tridiagonal in the knots, those 4 x 4 blocks are zero in the matrix and in the factor.  A property of S = 6 -- of KN_N = 48 with
+// this numbering -- not of K; tests/test_knot_band_cpu.py states it on the oracle.)
+static_assert(KN_N == 48 && D2D_FIT_MAX_S == 6, "nd_panel3_chunk0_zero<KnotMetric> rests on the 4 / 8 x 5 / 4 layout of the 48 free entries");
+template <> struct nd_panel3_chunk0_zero<KnotMetric> { static constexpr bool value = true; };
 namespace {
 
 // SEG9: no segment holds more than nine samples (K <= 54 at S = 6: the bench's K = 50) -- the MFMA pass keeps 27 operands, not 33

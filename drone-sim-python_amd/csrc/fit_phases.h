@@ -617,12 +617,18 @@ __device__ __forceinline__ float lanes_above(float v, int j, unsigned long long 
 }
 
 template <class M> struct nd_is_banded { static constexpr bool value = false; };
+// A banded Metric may say more: `panel3_chunk0_zero` -- in EVERY block column of 16 the rows of panel 3 (16 I + 12 .. + 15) have
+// no entries in the columns of chunk 0 (16 I .. + 3), in the matrix and therefore in its factor.  That is a statement about how the
+// blocks of the band sit on the grid of four: the panel's dot products then leave that chunk out (8 packed FMAs and 4 broadcast
+// reads per block column that only add +-0 to an accumulator that starts at +0: the same bits).
+template <class M> struct nd_panel3_chunk0_zero { static constexpr bool value = false; };
 
 // Metric (fit_knot.hip: the solve in knot coordinates, where lmder's norm is ||s||_M and the damping is lam M): an object with
 //   apply(delta) -> (M delta)[lane]      dxnorm = sqrt(delta^T M delta), isq = || L^-1 (M delta / dxnorm) ||^2
 //   prepare(lane); damp(j0), scale -> M[lane][j0 .. j0+3] and lam: scale * damp is added to the lane's matrix row where the panel of columns
 //                      j0 .. j0+3 reads it (scale = 0 on the lanes that are not rows of the system: lane N carries the right-hand side)
-// The default (int) is the Euclidean norm with the damping on the pivots.
+// The default (int) is the Euclidean norm with the damping on the pivots.  Under a Metric ALL the damping is the metric's: `lam` and
+// `unit` are not used (the knot kernel passes lam = 0), nothing is added to the pivots.
 template <int N, bool MP = false, bool FULL = false, class Metric = int>
 __device__ __forceinline__ bool damped_solve(const f32x2 (&hrow)[N / 2], double lam, bool act, int lane,
                                              float *Lm, float &dgi, float &delta, unsigned long long *tt = nullptr,
@@ -653,8 +659,13 @@ __device__ __forceinline__ bool damped_solve(const f32x2 (&hrow)[N / 2], double 
   float *wrow = Lm + (lane <= N ? lane : N + 1) * LS;  // lanes > N write a dummy row
   float *dinv = Lm + (N + 2) * LS;                     // [N] reciprocal diagonal
   float *damp = Lm + (N + 3) * LS;                     // [N] damping of the pivots
-  damp[lane < N ? lane : N] = dadd;
-  wave_lds_sync();
+  // (a Metric damps through its rows -- damp() / scale -- and is called with lam = 0: the pivots get nothing added, the damp row
+  // is neither written nor read.  x + 0.f == x for every x but -0.f, and a pivot of +-0 fails the factorisation either way.)
+  constexpr bool PIVOT_DAMP = __is_same(Metric, int);
+  if constexpr (PIVOT_DAMP) {
+    damp[lane < N ? lane : N] = dadd;
+    wave_lds_sync();
+  }
   const int m16 = lane & 15, g4 = lane >> 4;           // tile coordinates of this lane (MFMA operand and accumulator layouts)
   // the tiles of the block columns to come: T[I'][J] = rows of block J (J == NBK: the block of the right-hand side, row N),
   // columns of block I'; lane (m, g) holds rows 4 g + r, column m
@@ -689,11 +700,13 @@ __device__ __forceinline__ bool damped_solve(const f32x2 (&hrow)[N / 2], double 
       for (int sp = 0; sp < 4; ++sp) dv[sp] = lds_get<f32x4>(own + 4 * sp);
     }
     f32x4 ring[3][4];                  // chunk kq (columns c0 + 4 kq .. + 3) of rows j0 .. j0+3
+    constexpr bool SKIP30 = nd_is_banded<Metric>::value && nd_panel3_chunk0_zero<Metric>::value;      // panel 3 has no chunk 0
 #pragma unroll
     for (int sp = 0; sp < 4; ++sp) {
       const int j0 = c0 + 4 * sp;
       __builtin_amdgcn_sched_barrier(0);
-      const f32x4 dq = lds_get<f32x4>(damp + j0);
+      f32x4 dq = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (PIVOT_DAMP) dq = lds_get<f32x4>(damp + j0);
       f32x4 mq = f32x4{0.f, 0.f, 0.f, 0.f};             // (requested here, with the panel's other reads: used after the dot products)
       if constexpr (!__is_same(Metric, int)) mq = metric.damp(j0);
       // the newest chunk (published by the panel before); the older ones were requested before that panel's diagonal block
@@ -705,7 +718,7 @@ __device__ __forceinline__ bool damped_solve(const f32x2 (&hrow)[N / 2], double 
 #pragma unroll
       for (int c = 0; c < 4; ++c) acc[c] = f32x2{0.f, 0.f};
 #pragma unroll
-      for (int kq = 0; kq < sp; ++kq) {
+      for (int kq = (SKIP30 && sp == 3) ? 1 : 0; kq < sp; ++kq) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const f32x4 l = ring[kq][c];
@@ -721,19 +734,32 @@ __device__ __forceinline__ bool damped_solve(const f32x2 (&hrow)[N / 2], double 
       // the older chunks of the next panel (rows j0+4 .., columns c0 .. j0-1): under the diagonal block's dependent chain
       if (sp < 3) {
 #pragma unroll
-        for (int kq = 0; kq < sp; ++kq)
+        for (int kq = (SKIP30 && sp == 2) ? 1 : 0; kq < sp; ++kq)
 #pragma unroll
           for (int c = 0; c < 4; ++c) ring[kq][c] = lds_get<f32x4>(Lm + (j0 + 4 + c) * LS + c0 + 4 * kq);
       }
       __builtin_amdgcn_sched_barrier(0);
       float s[4];
+      if constexpr (!__is_same(Metric, int) && FULL) {
+        // (the same operations on the pairs the operands already sit in -- hrow[] pairs, halves of the quads: v_pk_fma_f32 and
+        // v_pk_add_f32 round like their scalar forms)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float a = HEL(j0 + c);
-        if constexpr (!__is_same(Metric, int)) a = fmaf(metric.scale, mq[c], a);
-        if (!FULL) a = live ? a : 0.f;
-        if (I > 0) a -= dv[sp][c];
-        s[c] = sp > 0 ? a - (acc[c].x + acc[c].y) : a;
+        for (int h = 0; h < 2; ++h) {
+          f32x2 a = hrow[(j0 >> 1) + h];
+          a = __builtin_elementwise_fma(f32x2{metric.scale, metric.scale}, f32x2{mq[2 * h], mq[2 * h + 1]}, a);
+          if (I > 0) a -= f32x2{dv[sp][2 * h], dv[sp][2 * h + 1]};
+          s[2 * h] = sp > 0 ? a.x - (acc[2 * h].x + acc[2 * h].y) : a.x;
+          s[2 * h + 1] = sp > 0 ? a.y - (acc[2 * h + 1].x + acc[2 * h + 1].y) : a.y;
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          float a = HEL(j0 + c);
+          if constexpr (!__is_same(Metric, int)) a = fmaf(metric.scale, mq[c], a);
+          if (!FULL) a = live ? a : 0.f;
+          if (I > 0) a -= dv[sp][c];
+          s[c] = sp > 0 ? a - (acc[c].x + acc[c].y) : a;
+        }
       }
       // 4x4 diagonal block across lanes j0 .. j0+3; l[c] = L[lane][j0+c] (valid on the lanes below the pivot)
       float l[4], inv[4];
@@ -744,7 +770,8 @@ __device__ __forceinline__ bool damped_solve(const f32x2 (&hrow)[N / 2], double 
       // every broadcast on the dependent chain: readlane, add, rsq, mul, readlane, fma per column
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const float piv = lane_value(s[c], j0 + c) + dq[c];
+        float piv = lane_value(s[c], j0 + c);
+        if constexpr (PIVOT_DAMP) piv += dq[c];
         inv[c] = __builtin_amdgcn_rsqf(piv);
         l[c] = s[c] * inv[c];
 #pragma unroll

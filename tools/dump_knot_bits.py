@@ -1,0 +1,89 @@
+"""The knot kernel's results on a fixed set of small fit families, bit for bit: tests/golden/knot_parent_bits.npz.
+
+    python tools/dump_knot_bits.py [OUT.npz]          (D2D_LIB=<library> selects the build, as for every A/B run)
+
+The fixture was written ONCE, with the build of the commit BEFORE the round-7 pass over the solver loop, and is what
+tests/test_gpu_knot_bits.py compares every later build with: a change of csrc/fit_knot.hip or of damped_solve that is meant to remove
+work only must leave every array below np.array_equal.  A change that is MEANT to alter a rounding re-writes the fixture with this
+tool and says so.
+
+Families (max_iter = 150 everywhere; name -> what it reaches):
+  bench     192 bench scenarios, K = 50          the SEG9 instantiation: Gauss-Newton steps inside and outside the region, lmpar, the finish
+  k40, k64  64 each of the other-K scenarios     K = 64 is the generic (non-SEG9) instantiation
+  so0       64 bench scenarios, so_lambda = 0    the option's Gauss-Newton setting (the MINPACK path's finish is second-order whatever it says)
+  bankmax   64 CostBank-max scenarios            the piecewise-smooth cost: rejected trials, long finishes
+  resume    64 bench scenarios, 7 trials a launch every fit goes through the resume path (lm[] state, the kept knot vector)
+Per family: cost, q (float64), iters, status (int32) and stats (float64[3]: max |J^T r| over the family, fits not converged, evaluations
+-- d2d_fit_solve's stats[1 .. 3]; stats[0], the cost sum, is accumulated with atomics in an order that is not fixed, and `cost` holds
+its terms).  The per-fit count of factorisations, lm[7], stays inside the plan -- no entry point of the library returns it -- so the
+evaluation count and the trial counts of `iters` are what pins the path a fit took."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [p for p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd')) if p not in sys.path]
+
+import numpy as np  # noqa: E402
+
+MAX_ITER = 150
+FAMILIES = ('bench', 'k40', 'k64', 'so0', 'bankmax', 'resume')
+FIELDS = ('cost', 'q', 'iters', 'status', 'stats')
+
+
+def scenarios(name):
+    """(K, duration, wref, scenarios) of a family"""
+    import bench
+    from d2dhip import synth
+    if name in ('k40', 'k64'):
+        K2 = int(name[1:])
+        dur = synth.planner_timing(0, (K2 - 1) / 10.0, 10)[2]
+        return K2, dur, synth.default_wref(0.1, K2), synth.synth_scenarios(64, seed=5, obj_scale=0.1, K=K2, dist_range=(30. * dur / 4.9, 55. * dur / 4.9))
+    dur, wref = bench._plan_consts()
+    sc = bench.bench_scenarios(4096)
+    if name == 'bankmax':
+        return bench.K, dur, wref, synth.variant_scenarios('bankmax', 64, K=bench.K)
+    return bench.K, dur, wref, {'bench': sc[:192], 'so0': sc[192:256], 'resume': sc[256:320]}[name]
+
+
+def run(ctx, name):
+    """One family through the knot kernel -> {field: numpy array}"""
+    import d2dhip
+    K2, dur, wref, sc = scenarios(name)
+    dsc = ctx.dev(sc)
+    plan = d2dhip.FitPlan(ctx, 6, K2, dur, wref, kernel='knot')
+    try:
+        assert plan.kernel == 'knot'
+        q = plan.init(dsc)
+        if name == 'resume':
+            plan.begin(len(sc))
+            for _ in range(MAX_ITER):
+                if plan.iterate(dsc, q, 7, max_iter=MAX_ITER) == 0:
+                    break
+            cost, iters, status, stats = plan.finish(dsc, q)
+        else:
+            kw = {'so_lambda': 0.0} if name == 'so0' else {}
+            cost, iters, status, stats = plan.solve(dsc, q, max_iter=MAX_ITER, **kw)
+        return {'cost': cost.cpu().numpy().astype(np.float64), 'q': q.cpu().numpy().astype(np.float64),
+                'iters': iters.cpu().numpy().astype(np.int32), 'status': status.cpu().numpy().astype(np.int32),
+                'stats': np.asarray(stats, dtype=np.float64)[1:4].copy()}
+    finally:
+        plan.close()
+
+
+def main():
+    import d2dhip
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'tests', 'golden', 'knot_parent_bits.npz')
+    ctx = d2dhip.Context(0)
+    arrays = {}
+    for name in FAMILIES:
+        r = run(ctx, name)
+        arrays.update({f'{name}_{k}': v for k, v in r.items()})
+        print(name, 'fits', len(r['cost']), 'iters', int(r['iters'].min()), int(r['iters'].max()), 'status', np.bincount(r['status']).tolist(),
+              'evaluations', int(r['stats'][2]), flush=True)
+    ctx.close()
+    np.savez_compressed(out, **arrays)
+    print('wrote', out, os.path.getsize(out), 'bytes')
+
+
+if __name__ == '__main__':
+    main()
