@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "sim_device.h"
+#include "gust_device.h"
 
 static GlMesh make_mesh(double dt, double tau_phi, double tau_v) {
   // oracle/sim.py gl_mesh: geometric panels resolve the phi boundary layer (tau_phi << dt)
@@ -85,7 +86,10 @@ __device__ __forceinline__ int member_get_i(int v) {
 // (s_mov_b32: a scalar instruction costs a lone wave the same issue slot as an fp64 FMA; 263 per step against 802 vector ones).
 // WIND (the general kernel only): the plant flies the field wf, step i starting at t_start + (i - 1) dt; the guidance law sees no wind
 // (GVFcontroller stores it and never reads it).  iter_max: the largest fixed-point sweep count (include/d2d.h D2D_WIND_*).
-template <int NAC, bool VCONST, bool WIND = false>
+// GUST (the general kernel only): step i flies the wind plus the lane's gust g_{i-1} (gust_device.h; the law sees none of it) and
+// the gust is advanced after the step -- of a running formation only: a frozen one keeps looping with its block and its gust stays
+// where its last executed step left it.
+template <int NAC, bool VCONST, bool WIND = false, bool GUST = false>
 __device__ __forceinline__ void
 gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double *__restrict__ X0,
              const double *__restrict__ centres, const double *__restrict__ radius,
@@ -93,8 +97,10 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
              double *__restrict__ X_hist, double *__restrict__ U_hist,
              double *__restrict__ Rr_hist, double *__restrict__ eth_hist,
              double *__restrict__ X_final, int32_t *__restrict__ stop_row, int32_t *__restrict__ conv_row,
-             const d2d_wind_field *wf = nullptr, double t_start = 0.0, int32_t *__restrict__ iter_max = nullptr) {
+             const d2d_wind_field *wf = nullptr, double t_start = 0.0, int32_t *__restrict__ iter_max = nullptr,
+             const d2d_gust *gp = nullptr) {
   static_assert(!WIND || NAC == 0, "wind runs take the general kernel");
+  static_assert(!GUST || NAC == 0, "gust runs take the general kernel");
   extern __shared__ double lds[];
   constexpr bool QUAD = NAC != 0;
   double *sh_theta = lds;
@@ -122,6 +128,13 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
     if (X_hist) {
       X_hist[d] = s.x; X_hist[N + d] = s.y; X_hist[2 * N + d] = s.psi; X_hist[3 * N + d] = s.phi;
       X_hist[4 * N + d] = s.v;
+    }
+  }
+  GustState gst = {};
+  if constexpr (GUST) {
+    if (live) {
+      gst = gust_begin(*gp, d, N);
+      gust_store_row(*gp, gst, 0, d, N);
     }
   }
   __syncthreads();
@@ -262,13 +275,23 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
     const double phi_c = gvf_bank_cmd(s, sin_psi, cos_psi, cx, cy, Rr, p.ke, p.kd, nullptr, nullptr, &tan_c);
     double sn_n = sin_psi, cs_n = cos_psi;
     State5 sn;
-    if constexpr (WIND) {
+    if constexpr (GUST) {
+      const Normal2 gv = gust_value(*gp, gst);
+      if constexpr (WIND) {
+        wc.t = t_start + (i - 1) * p.dt;
+        wc.gx = gv.x; wc.gy = gv.y;
+        sn = plant_step<true, true, true>(s, phi_c, p.v_c, 0.0, 0.0, mesh, sn_n, cs_n, tan_c, &ga6, &gb6, fast6, &wc);
+      } else {
+        sn = plant_step<true>(s, phi_c, p.v_c, p.wx + gv.x, p.wy + gv.y, mesh, sn_n, cs_n, tan_c, &ga6, &gb6, fast6);
+      }
+    } else if constexpr (WIND) {
       wc.t = t_start + (i - 1) * p.dt;
       sn = plant_step<true, true>(s, phi_c, p.v_c, 0.0, 0.0, mesh, sn_n, cs_n, tan_c, &ga6, &gb6, fast6, &wc);
     } else {
       sn = plant_step<true>(s, phi_c, p.v_c, p.wx, p.wy, mesh, sn_n, cs_n, tan_c, &ga6, &gb6, fast6);
     }
     if (run) {
+      if constexpr (GUST) gust_advance(*gp, gst, i);
       if (U_hist && ph_prev == 0) {
         const long r = (long)row_prev * 2 * N;
         U_hist[r + d] = phi_c; U_hist[r + N + d] = p.v_c;
@@ -281,6 +304,7 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
         }
         if (Rr_hist) Rr_hist[(long)row * N + d] = Rr;
         if (eth_hist && a < nm) eth_hist[(long)row * p.n_form * nm + (long)f * nm + a] = e * (180.0 / D2D_PI);
+        if constexpr (GUST) gust_store_row(*gp, gst, row, d, N);
       }
       s = sn;
       sin_psi = sn_n; cos_psi = cs_n;
@@ -333,6 +357,7 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
     X_final[4 * N + d] = s.v;
     if (a == 0 && stop_row) stop_row[f] = (p.use_stop == 2 && prev_all_ok && my_stop == p.n_rows) ? p.n_rows : my_stop;
     if (a == 0 && conv_row) conv_row[f] = first_true;
+    if constexpr (GUST) gust_store_state(*gp, gst, d, N);
   }
   if constexpr (WIND) {
     if (iter_max) atomicMax(iter_max, wc.iters);
@@ -346,6 +371,10 @@ gvf_run_body(const d2d_gvf_params &p, const GlMesh &mesh, int fpb, const double 
 #define GVF_PASS p, mesh, fpb, X0, centres, radius, Bz, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row
 // any formation size (LDS exchange); two waves per SIMD for 131 072 drones and more
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) gvf_run_kernel(GVF_ARGS) { gvf_run_body<0, false>(GVF_PASS); }
+// ... in constant wind plus gusts (d2d_sim_gvf_run_gust without a field: every formation size)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) gvf_run_gust_kernel(GVF_ARGS, d2d_gust gust) {
+  gvf_run_body<0, false, false, true>(GVF_PASS, nullptr, 0.0, nullptr, &gust);
+}
 // quad-aligned formations (1, 2, 4 aircraft), one wavefront per block; ..._wide: the launch puts at most one wave on a SIMD
 // (<= 1024 blocks: BASELINE configs[4], 65 536 drones), which then has the whole register file -- no scratch
 template <int NAC>
@@ -498,14 +527,15 @@ gradient_kernel(int T, int n, double inv_dt, const double *__restrict__ f, doubl
 // DiffController(w) (src/11_full_sim_case1.py:241-291 hands w to the controller and WindField(w) to the plant separately).
 // T_AT: the start time is the drone's own, t_at [n] (the drones of the mission chain start phase 2 where their own formation ended
 // phase 1), else the scalar t_start; the time of a step is the same expression in both.
-template <bool FIELD, bool T_AT>
+// GUST: step i flies the wind plus the drone's gust g_{i-1} (gust_device.h); the controller sees none of it.
+template <bool FIELD, bool T_AT, bool GUST = false>
 __device__ __forceinline__ void
 track_run_body(const d2d_track_params &p, const GlMesh &mesh, const double *__restrict__ x_ref, const double *__restrict__ y_ref,
                const double *__restrict__ xd, const double *__restrict__ yd, const double *__restrict__ xdd,
                const double *__restrict__ ydd, const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist,
                double *__restrict__ Xr_hist, double *__restrict__ dX_hist, double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
                double *__restrict__ X_final, const d2d_wind_field *wf = nullptr, double t_start = 0.0,
-               const double *__restrict__ t_at = nullptr, int32_t *__restrict__ iter_max = nullptr) {
+               const double *__restrict__ t_at = nullptr, int32_t *__restrict__ iter_max = nullptr, const d2d_gust *gp = nullptr) {
   const long n = p.n;
   long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
   const bool live = d < n;
@@ -516,11 +546,27 @@ track_run_body(const d2d_track_params &p, const GlMesh &mesh, const double *__re
   if (live && X_hist) {
     X_hist[d] = s.x; X_hist[n + d] = s.y; X_hist[2 * n + d] = s.psi; X_hist[3 * n + d] = s.phi; X_hist[4 * n + d] = s.v;
   }
+  GustState gst = {};
+  if constexpr (GUST) {
+    gst = gust_begin(*gp, d, n);
+    if (live) gust_store_row(*gp, gst, 0, d, n);
+  }
   for (int i = 1; i < p.n_rows; ++i) {
     const long r = (long)i * n + d;
     double Y[8] = {x_ref[r], y_ref[r], xd[r], yd[r], xdd[r], ydd[r], 0.0, 0.0};   // Yddd = [0,0] (:279)
     const GainOut o = compute_gain(s, Y, p);
-    if constexpr (FIELD) {
+    if constexpr (GUST) {
+      const Normal2 gv = gust_value(*gp, gst);
+      if constexpr (FIELD) {
+        wc.t = t_start + (i - 1) * p.dt;
+        wc.gx = gv.x; wc.gy = gv.y;
+        s = plant_step_wind<true>(s, o.U[0], o.U[1], mesh, wc);
+      } else {
+        s = plant_step(s, o.U[0], o.U[1], p.wx + gv.x, p.wy + gv.y, mesh);
+      }
+      gust_advance(*gp, gst, i);
+      if (live) gust_store_row(*gp, gst, i, d, n);
+    } else if constexpr (FIELD) {
       wc.t = t_start + (i - 1) * p.dt;
       s = plant_step_wind(s, o.U[0], o.U[1], mesh, wc);
     } else {
@@ -547,6 +593,9 @@ track_run_body(const d2d_track_params &p, const GlMesh &mesh, const double *__re
   }
   if (live && X_final) {
     X_final[d] = s.x; X_final[n + d] = s.y; X_final[2 * n + d] = s.psi; X_final[3 * n + d] = s.phi; X_final[4 * n + d] = s.v;
+  }
+  if constexpr (GUST) {
+    if (live) gust_store_state(*gp, gst, d, n);
   }
   if constexpr (FIELD) {
     if (iter_max) atomicMax(iter_max, wc.iters);
@@ -790,6 +839,11 @@ gvf_run_wind_kernel(GVF_ARGS, d2d_wind_field wf, double t_start, int32_t *__rest
   gvf_run_body<0, false, true>(GVF_PASS, &wf, t_start, iter_max);
 }
 
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+gvf_run_wind_gust_kernel(GVF_ARGS, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max, d2d_gust gust) {
+  gvf_run_body<0, false, true, true>(GVF_PASS, &wf, t_start, iter_max, &gust);
+}
+
 __global__ void __launch_bounds__(64)
 track_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
                       const double *__restrict__ y_ref, const double *__restrict__ xd,
@@ -817,6 +871,56 @@ track_run_wind_at_kernel(d2d_track_params p, GlMesh mesh, const double *__restri
                       int32_t *__restrict__ iter_max) {
   track_run_body<true, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final,
                              &wf, 0.0, t_at, iter_max);
+}
+
+// the gust twins of the three tracking kernels (d2d_sim_track_run_gust: no field, a field, a field and a start time per drone)
+__global__ void __launch_bounds__(64)
+track_run_gust_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
+                      const double *__restrict__ y_ref, const double *__restrict__ xd,
+                      const double *__restrict__ yd, const double *__restrict__ xdd,
+                      const double *__restrict__ ydd, const double *__restrict__ X0,
+                      double *__restrict__ X_hist, double *__restrict__ U_hist,
+                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
+                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
+                      double *__restrict__ X_final, d2d_gust gust) {
+  track_run_body<false, false, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, nullptr, 0.0, nullptr, nullptr, &gust);
+}
+
+__global__ void __launch_bounds__(64)
+track_run_wind_gust_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
+                      const double *__restrict__ y_ref, const double *__restrict__ xd,
+                      const double *__restrict__ yd, const double *__restrict__ xdd,
+                      const double *__restrict__ ydd, const double *__restrict__ X0,
+                      double *__restrict__ X_hist, double *__restrict__ U_hist,
+                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
+                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
+                      double *__restrict__ X_final, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max, d2d_gust gust) {
+  track_run_body<true, false, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, &wf, t_start, nullptr, iter_max, &gust);
+}
+
+__global__ void __launch_bounds__(64)
+track_run_wind_at_gust_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
+                      const double *__restrict__ y_ref, const double *__restrict__ xd,
+                      const double *__restrict__ yd, const double *__restrict__ xdd,
+                      const double *__restrict__ ydd, const double *__restrict__ X0,
+                      double *__restrict__ X_hist, double *__restrict__ U_hist,
+                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
+                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
+                      double *__restrict__ X_final, d2d_wind_field wf, const double *__restrict__ t_at, int32_t *__restrict__ iter_max, d2d_gust gust) {
+  track_run_body<true, true, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, &wf, 0.0, t_at, iter_max, &gust);
+}
+
+// d2d_gust_sample: the process alone, one lane per drone -- the statements of the loops in the same order
+__global__ void __launch_bounds__(256) gust_sample_kernel(long N, int n_rows, d2d_gust gust) {
+  const long d = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (d >= N) return;
+  GustState gst = gust_begin(gust, d, N);
+  gust_store_row(gust, gst, 0, d, N);
+  for (int i = 1; i < n_rows; ++i) {
+    gust_advance(gust, gst, i);
+    gust_store_row(gust, gst, i, d, N);
+  }
+  gust_store_state(gust, gst, d, N);
 }
 
 __global__ void __launch_bounds__(64)
@@ -863,11 +967,28 @@ int d2d_step_wind(d2d_ctx *ctx, int n, const double *X, const double *U, double 
   return D2D_OK;
 }
 
-// f == NULL: the constant-wind loop of d2d_sim_gvf_run; else its wind twin (always the general kernel)
+// a d2d_gust argument of an entry point (include/d2d.h: what makes one D2D_EINVAL); N drones, steps 0 .. n_rows - 1
+static int check_gust(const d2d_gust *g, long N, long n_rows, const char *who) {
+  D2D_REQUIRE(g, "%s: null gust", who);
+  D2D_REQUIRE(std::isfinite(g->sigma) && g->sigma >= 0 && std::isfinite(g->s) && g->s >= 0, "%s: gust sigma, s must be finite and >= 0", who);
+  D2D_REQUIRE(g->a >= 0 && g->a < 1, "%s: gust a=%g not in [0, 1)", who, g->a);
+  D2D_REQUIRE(std::isfinite(g->w_own) && std::isfinite(g->w_form) && g->w_own >= 0 && g->w_form >= 0 &&
+                  std::fabs(g->w_own * g->w_own + g->w_form * g->w_form - 1.0) <= 1e-12,
+              "%s: gust weights w_own=%g, w_form=%g must be >= 0 with squares that sum to 1", who, g->w_own, g->w_form);
+  D2D_REQUIRE(g->n_ac >= 1 && N % g->n_ac == 0, "%s: gust n_ac=%d must be >= 1 and divide the %ld drones", who, g->n_ac, N);
+  D2D_REQUIRE(g->stream_base >= 0 && g->stream_base % g->n_ac == 0, "%s: gust stream_base=%lld must be >= 0 and a multiple of n_ac", who,
+              (long long)g->stream_base);
+  D2D_REQUIRE(g->phase >= 0 && g->step_base >= 0 && g->step_base + n_rows <= 0xffffffffLL,
+              "%s: gust phase, step_base must be >= 0 and step_base + n_rows fit the 32-bit step word", who);
+  return D2D_OK;
+}
+
+// f == NULL: the constant-wind loop of d2d_sim_gvf_run; else its wind twin (always the general kernel).  gust (with gusty): the
+// gust twin of either, always the general kernel too.
 static int gvf_run_impl(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
                         const double *Bmat, const double *z_des, const double *X0f, double *X_hist, double *U_hist, double *Rr_hist,
                         double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const d2d_wind_field *f,
-                        double t_start, int32_t *iter_max, const char *who) {
+                        double t_start, int32_t *iter_max, const char *who, bool gusty = false, const d2d_gust *gust = nullptr) {
   D2D_REQUIRE(ctx && p && X0 && centres && radius && X_final, "%s: null argument", who);
   D2D_REQUIRE(p->use_stop >= 0 && p->use_stop <= 2 && p->stop_hold >= 0, "%s: use_stop in 0..2, stop_hold >= 0", who);
   D2D_REQUIRE(p->n_ac >= 1 && p->n_ac <= 64, "%s: n_ac=%d not in 1..64", who, p->n_ac);
@@ -878,6 +999,9 @@ static int gvf_run_impl(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
   D2D_REQUIRE(p->dt > 0 && p->tau_phi > 0 && p->tau_v > 0, "%s: dt, tau_phi, tau_v must be > 0", who);
   if (f) {
     if (int rc = check_wind(f, who)) return rc;
+  }
+  if (gusty) {
+    if (int rc = check_gust(gust, (long)p->n_form * p->n_ac, p->n_rows, who)) return rc;
   }
   const int n_ac = p->n_ac, nm = n_ac - 1;
   const size_t nb = (size_t)n_ac * nm + nm;
@@ -891,7 +1015,16 @@ static int gvf_run_impl(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
 #define GVF_LAUNCH(KERNEL)                                                                                             \
   hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius, ctx->Bmat_dev, \
                      X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row)
-  if (f) {
+  if (gusty) {
+    if (f) {
+      if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
+      hipLaunchKernelGGL(gvf_run_wind_gust_kernel, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius,
+                         ctx->Bmat_dev, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row, *f, t_start, iter_max, *gust);
+    } else {
+      hipLaunchKernelGGL(gvf_run_gust_kernel, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius,
+                         ctx->Bmat_dev, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row, *gust);
+    }
+  } else if (f) {
     if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
     hipLaunchKernelGGL(gvf_run_wind_kernel, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius,
                        ctx->Bmat_dev, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row, *f, t_start, iter_max);
@@ -927,6 +1060,24 @@ int d2d_sim_gvf_run_wind(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0
   D2D_REQUIRE(f, "d2d_sim_gvf_run_wind: null wind field");
   return gvf_run_impl(ctx, p, X0, centres, radius, Bmat, z_des, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row,
                       f, t_start, iter_max, "d2d_sim_gvf_run_wind");
+}
+
+int d2d_sim_gvf_run_gust(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
+                         const double *Bmat, const double *z_des, const double *X0f, double *X_hist, double *U_hist, double *Rr_hist,
+                         double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const d2d_wind_field *f,
+                         double t_start, int32_t *iter_max, const d2d_gust *gust) {
+  return gvf_run_impl(ctx, p, X0, centres, radius, Bmat, z_des, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row,
+                      f, t_start, iter_max, "d2d_sim_gvf_run_gust", true, gust);
+}
+
+int d2d_gust_sample(d2d_ctx *ctx, int64_t N, int n_rows, const d2d_gust *gust) {
+  D2D_REQUIRE(ctx, "d2d_gust_sample: null argument");
+  D2D_REQUIRE(N >= 1 && n_rows >= 1, "d2d_gust_sample: N, n_rows must be >= 1");
+  if (int rc = check_gust(gust, (long)N, n_rows, "d2d_gust_sample")) return rc;
+  D2D_REQUIRE(gust->state_out || gust->g_hist, "d2d_gust_sample: state_out and g_hist are both NULL: nothing to write");
+  hipLaunchKernelGGL(gust_sample_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, (long)N, n_rows, *gust);
+  D2D_LAUNCH_CHECK();
+  return D2D_OK;
 }
 
 static int check_track(const d2d_track_params *p, const char *who) {
@@ -990,12 +1141,15 @@ int d2d_sim_dfff_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double 
 static int track_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
                           double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
                           double *X_final, const d2d_wind_field *f, double t_start, int32_t *iter_max, const char *who,
-                          const double *t_at = nullptr) {
+                          const double *t_at = nullptr, bool gusty = false, const d2d_gust *gust = nullptr) {
   D2D_REQUIRE(ctx && p && x_ref && y_ref && X0, "%s: null argument", who);
   if (int rc = check_track(p, who)) return rc;
   D2D_REQUIRE(p->n_rows >= 3, "%s: n_rows must be >= 3 (second-order edge differences)", who);
   if (f) {
     if (int rc = check_wind(f, who)) return rc;
+  }
+  if (gusty) {
+    if (int rc = check_gust(gust, p->n, p->n_rows, who)) return rc;
   }
   const size_t plane = (size_t)p->n_rows * p->n * sizeof(double);
   double *deriv = nullptr;
@@ -1011,7 +1165,18 @@ static int track_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double 
   D2D_LAUNCH_CHECK();
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
   const dim3 grid((p->n + 63) / 64), block(64);          // a wavefront per workgroup
-  if (f) {
+  if (gusty) {
+    if (f && iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
+    if (f && t_at)
+      hipLaunchKernelGGL(track_run_wind_at_gust_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist,
+                         U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_at, iter_max, *gust);
+    else if (f)
+      hipLaunchKernelGGL(track_run_wind_gust_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist,
+                         U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, 0.0, iter_max, *gust);
+    else
+      hipLaunchKernelGGL(track_run_gust_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist,
+                         Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *gust);
+  } else if (f) {
     if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
     if (t_at)
       hipLaunchKernelGGL(track_run_wind_at_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist,
@@ -1051,6 +1216,13 @@ int d2d_sim_track_run_wind_at(d2d_ctx *ctx, const d2d_track_params *p, const dou
   D2D_REQUIRE(t_start, "d2d_sim_track_run_wind_at: null t_start (a device array [n]: one start time per drone)");
   return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, f, 0.0, iter_max,
                         "d2d_sim_track_run_wind_at", t_start);
+}
+
+int d2d_sim_track_run_gust(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
+                           double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
+                           double *X_final, const d2d_wind_field *f, const double *t_start, int32_t *iter_max, const d2d_gust *gust) {
+  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, f, 0.0, iter_max,
+                        "d2d_sim_track_run_gust", t_start, true, gust);
 }
 
 int d2d_traj_sample(d2d_ctx *ctx, int n, int T, double t_start, double dt, const double *desc, double *Yref) {

@@ -13,6 +13,7 @@ cubic B-spline (C2: the Gauss panels of the plant step keep their order):
                                                       constraint Jacobian and curvature; sim_device.h wind_eval2 in numpy)
   SplineWindField.sample_num / sample_sym / -field    the planner's wind protocol (src/d2d/opty_utils.py:16-29) and the field with the
                                                       opposite sign (the planner's model has the wind with the opposite sign to the plant)
+  GustModel(sigma, tau | L, V, seed, form_corr)       a stochastic gust on top of either wind, drawn inside the device loops
 
 Outside the spline's box every coordinate is clamped: the field is held at its boundary value, continuous but only C0 there.
 """
@@ -250,6 +251,57 @@ class SplineWindField:
             hit = (cp, f)
             self._dev[ctx] = hit
         return hit[1]
+
+
+class GustModel:
+    """A stochastic gust of the plant (include/d2d.h d2d_gust): per aircraft and axis a first-order Gauss-Markov process of standard
+    deviation sigma (m/s) and correlation time tau (s) -- or tau = L / V, the first-order Dryden form with length scale L (m) at
+    airspeed V (m/s) -- of which the fraction form_corr in [0, 1) of the variance is shared by the aircraft of a formation.  It
+    holds parameters only: the device loops draw the numbers (Philox4x32-10 on (seed, drone, phase, step)), and the controllers never
+    see the gust.  Pass it as gust= to full_sim's batched loops or to Context.gvf_run / track_run / gust_sample."""
+
+    def __init__(self, sigma, tau=None, L=None, V=None, seed=0, form_corr=0.0):
+        if (tau is None) == (L is None and V is None) or (tau is None and (L is None or V is None)):
+            raise ValueError('give the correlation time as tau, or as the pair L, V (tau = L / V)')
+        if tau is None:
+            if not (np.isfinite(L) and np.isfinite(V) and L > 0 and V > 0):
+                raise ValueError(f'L={L!r}, V={V!r}: both must be finite and > 0')
+            tau = float(L) / float(V)
+        if not (np.isfinite(sigma) and sigma >= 0):
+            raise ValueError(f'sigma={sigma!r} must be finite and >= 0')
+        if not (np.isfinite(tau) and tau > 0):
+            raise ValueError(f'tau={tau!r} must be finite and > 0')
+        if not (np.isfinite(form_corr) and 0.0 <= form_corr < 1.0):
+            raise ValueError(f'form_corr={form_corr!r} must be in [0, 1)')
+        if int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f'seed={seed!r} must be an integer in [0, 2^64)')
+        self.sigma, self.tau, self.seed, self.form_corr = float(sigma), float(tau), int(seed), float(form_corr)
+
+    def numbers(self, dt):
+        """The numbers the process runs on for a step dt, computed once in fp64: dict(seed, a = exp(-dt / tau),
+        s = sigma sqrt(1 - a^2), sigma, w_own = sqrt(1 - c), w_form = sqrt(c))."""
+        if not (np.isfinite(dt) and dt > 0):
+            raise ValueError(f'dt={dt!r} must be finite and > 0')
+        a = float(np.exp(-float(dt) / self.tau))
+        return dict(seed=self.seed, a=a, s=self.sigma * float(np.sqrt(1.0 - a * a)), sigma=self.sigma,
+                    w_own=float(np.sqrt(1.0 - self.form_corr)), w_form=float(np.sqrt(self.form_corr)))
+
+    def lower(self, dt, n_ac, phase=0, stream_base=0, step_base=0):
+        """d2dhip.GustC for a loop of step dt over formations of n_ac aircraft: phase separates the loops of one mission, stream_base
+        is the global index of the call's first drone (a multiple of n_ac: a shard's first drone), step_base the steps a continued
+        series has already made.  The state and history pointers are the caller's to fill."""
+        if int(n_ac) < 1 or int(phase) < 0 or int(stream_base) < 0 or int(stream_base) % int(n_ac) or int(step_base) < 0:
+            raise ValueError(f'n_ac={n_ac} >= 1, phase={phase} >= 0, step_base={step_base} >= 0 and stream_base={stream_base} a multiple of n_ac >= 0')
+        k = self.numbers(dt)
+        return d2dhip.GustC(k['seed'], int(stream_base), int(phase), int(n_ac), int(step_base), k['a'], k['s'], k['sigma'], k['w_own'],
+                            k['w_form'], None, None, None)
+
+
+def plant_gust(gust):
+    """A gust= argument of a device loop: None, or a GustModel (anything else cannot be drawn on the device)."""
+    if gust is None or isinstance(gust, GustModel):
+        return gust
+    raise TypeError(f'{type(gust).__name__} is not a gust model: build one with d2d.wind.GustModel(sigma, tau=...)')
 
 
 def _is_constant_class(cls):

@@ -62,6 +62,13 @@ class WindFieldC(C.Structure):
 WIND_TOL, WIND_MAX_ITERS = 1e-13, 8          # include/d2d.h D2D_WIND_*
 
 
+class GustC(C.Structure):
+    """d2d_gust (include/d2d.h): a stochastic gust of the plant; state_in, state_out, g_hist are device addresses or None."""
+    _fields_ = [('seed', C.c_uint64), ('stream_base', C.c_int64), ('phase', C.c_int32), ('n_ac', C.c_int32), ('step_base', C.c_int64),
+                ('a', C.c_double), ('s', C.c_double), ('sigma', C.c_double), ('w_own', C.c_double), ('w_form', C.c_double),
+                ('state_in', C.c_void_p), ('state_out', C.c_void_p), ('g_hist', C.c_void_p)]
+
+
 class NlpOpts(C.Structure):
     _fields_ = [('rho0', C.c_double), ('mub0', C.c_double), ('mub_min', C.c_double), ('feas_tol', C.c_double),
                 ('opt_tol', C.c_double), ('inner_max', C.c_int32), ('outer_max', C.c_int32), ('serial', C.c_int32), ('slots', C.c_int32),
@@ -158,6 +165,9 @@ _SIGS = {
     'd2d_sim_track_run_wind': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 10 + [C.POINTER(WindFieldC), C.c_double, _P]),
     'd2d_sim_dfff_run_wind': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 7 + [C.POINTER(WindFieldC), C.c_double, _P]),
     'd2d_sim_track_run_wind_at': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 10 + [C.POINTER(WindFieldC), _P, _P]),
+    'd2d_gust_sample': (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(GustC)]),
+    'd2d_sim_gvf_run_gust': (C.c_int, [_P, C.POINTER(GvfParams)] + [_P] * 13 + [C.POINTER(WindFieldC), C.c_double, _P, C.POINTER(GustC)]),
+    'd2d_sim_track_run_gust': (C.c_int, [_P, C.POINTER(TrackParams)] + [_P] * 10 + [C.POINTER(WindFieldC), _P, _P, C.POINTER(GustC)]),
     'd2d_traj_sample': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P]),
     'd2d_dcf_eval': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_double, _P, _P, _P, _P]),
     'd2d_gvf_eval': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, C.c_double, _P]),
@@ -383,16 +393,43 @@ class Context:
         torch = _torch()
         return torch.zeros(1, dtype=torch.int32, device=self.device)
 
+    def _gust_c(self, gust, dt, n_ac, N, phase, state, stream_base=0, step_base=0):
+        """The d2d_gust of `gust` -- a GustC (a COPY of it, state_in included: the caller's struct is not written; its state_out and
+        g_hist are replaced by the method's own outputs) or a model with lower(dt, n_ac, phase, stream_base) (d2d.wind.GustModel) --
+        for N drones, from `state` (dev [4][N] or None: the stationary start)."""
+        if isinstance(gust, GustC):
+            return GustC.from_buffer_copy(gust)
+        if not hasattr(gust, 'lower'):
+            raise TypeError(f'{type(gust).__name__} is not a gust model: build one with d2d.wind.GustModel')
+        assert state is None or (state.is_contiguous() and tuple(state.shape) == (4, N) and state.dtype == _torch().float64 and state.device.type == 'cuda')
+        g = gust.lower(float(dt), int(n_ac), int(phase), int(stream_base), int(step_base))
+        g.state_in = None if state is None else state.data_ptr()
+        return g
+
+    def gust_sample(self, gust, N, n_rows, dt, n_ac=1, phase=0, state=None, stream_base=0, step_base=0, record=True):
+        """The gust process alone (d2d_gust_sample): gust a d2d.wind.GustModel, N drones in formations of n_ac, rows 0 .. n_rows - 1
+        at spacing dt.  state dev [4][N]: the state of row 0 (None: the stationary start); stream_base: the global index of drone 0;
+        step_base: the steps a continued series has already made.  Returns dict(g dev [n_rows][2][N] (record), gust_state dev [4][N])."""
+        g = self._gust_c(gust, dt, n_ac, N, phase, state, stream_base, step_base)
+        out = dict(g=self.empty(n_rows, 2, N) if record else None, gust_state=self.empty(4, N))
+        g.state_out, g.g_hist = out['gust_state'].data_ptr(), None if out['g'] is None else out['g'].data_ptr()
+        _check(self.lib.d2d_gust_sample(self.h, int(N), int(n_rows), C.byref(g)))
+        return out
+
     def gvf_run(self, X0, centres, radius, n_ac, n_rows, dt, v_c, ke=4e-4, kd=25.0, kr=20.0,
                 B=None, z_des=None, tau_phi=0.01, tau_v=1.0, W=(0.0, 0.0), X0f=None,
                 stop_tol=(3.0, 3.0, np.deg2rad(0.5)), rec_stride=1, record=('X', 'U', 'Rr', 'eth'), out=None,
-                etheta_tol_deg=None, stop_hold=0, wind=None, t_start=0.0):
+                etheta_tol_deg=None, stop_hold=0, wind=None, t_start=0.0, gust=None, gust_state=None, gust_phase=0, gust_stream_base=0):
         """Circular-formation phase for N = n_form*n_ac drones.  X0 dev [5][N], centres dev
         [2][N], radius dev [N].  Returns dict of device tensors (plane-major).  out: the dictionary of an earlier
         call with the same shapes and `record` -- its buffers are written again instead of allocating new ones
         (without the stop rule every recorded row is rewritten; with it, rows behind the stop row keep their old
         content).  wind: a field the plant flies instead of W (d2d_sim_gvf_run_wind; row i at t_start + i dt); out['iter_max'] then
-        holds the largest fixed-point sweep count."""
+        holds the largest fixed-point sweep count.  gust: a d2d.wind.GustModel the plant flies on top of W or the field
+        (d2d_sim_gvf_run_gust, the general kernel for every n_ac; gust_state dev [4][N]: the state of row 0, None: the stationary
+        start; gust_phase: the loop's phase word; gust_stream_base: the global index of drone 0); out['gust_state'] dev [4][N] is the
+        state after each formation's last executed step and, with 'g' in record, out['g'] dev [n_rec][2][N] the gust of every kept
+        row.  gust None: nothing new is launched."""
         torch = _torch()
         N = X0.shape[1]
         assert N % n_ac == 0
@@ -424,7 +461,18 @@ class Context:
         args = (self.h, C.byref(p), _ptr(X0), _ptr(centres), _ptr(radius), _hptr(B), _hptr(z_des), _ptr(X0f if use_stop == 1 else None),
                 _ptr(out['X']), _ptr(out['U']), _ptr(out['Rr']), _ptr(out['eth']), _ptr(out['X_final']), _ptr(out['stop_row']),
                 _ptr(out.get('conv_row')))
-        if wind is None:
+        if gust is not None:
+            g = self._gust_c(gust, dt, n_ac, N, gust_phase, gust_state, gust_stream_base)
+            if out.get('gust_state') is None:
+                out['gust_state'] = self.empty(4, N)
+            if 'g' in record and out.get('g') is None:
+                out['g'] = self.zeros(n_rec, 2, N)
+            g.state_out, g.g_hist = out['gust_state'].data_ptr(), None if out.get('g') is None else out['g'].data_ptr()
+            f = None if wind is None else _wind_c(self, wind)
+            if f is not None:
+                out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
+            _check(self.lib.d2d_sim_gvf_run_gust(*args, None if f is None else C.byref(f), float(t_start), _ptr(out.get('iter_max')), C.byref(g)))
+        elif wind is None:
             _check(self.lib.d2d_sim_gvf_run(*args))
         else:
             f = _wind_c(self, wind)
@@ -785,11 +833,15 @@ class Context:
         out['mov_work'] = mov_work                    # (work is released here: the context's stream is torch's, whose allocator orders its reuse)
         return out
 
-    def track_run(self, x_ref, y_ref, X0, dt, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), out=None, wind=None, t_start=0.0, **kw):
+    def track_run(self, x_ref, y_ref, X0, dt, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), out=None, wind=None, t_start=0.0, gust=None,
+                  gust_state=None, gust_phase=0, gust_n_ac=1, gust_stream_base=0, **kw):
         """x_ref, y_ref dev [T][n]; X0 dev [5][n] -> dict of device histories (out: reuse the buffers of an earlier
         call with the same shapes and `record`).  wind: a field the plant flies (d2d_sim_track_run_wind; the controller keeps the
         constant w of kw; row i at t_start + i dt); out['iter_max']: the largest fixed-point sweep count.  t_start: a float, or a
-        device float64 tensor [n] with every drone's own start time (d2d_sim_track_run_wind_at)."""
+        device float64 tensor [n] with every drone's own start time (d2d_sim_track_run_wind_at).  gust: a d2d.wind.GustModel the plant
+        flies on top of w or the field (d2d_sim_track_run_gust; gust_state dev [4][n] or None, gust_phase, gust_stream_base as in gvf_run;
+        gust_n_ac: consecutive drones that share the formation part); out['gust_state'] dev [4][n] and, with 'g' in record, out['g']
+        dev [T][2][n].  gust None: nothing new is launched."""
         T, n = x_ref.shape
         p = self.track_params(n, T, dt, **kw)
         if out is None:
@@ -800,7 +852,26 @@ class Context:
             assert out['X_final'].shape == (5, n) and all(out[k] is None or out[k].shape[0] == T for k in ('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'))
         args = (self.h, C.byref(p), _ptr(x_ref), _ptr(y_ref), _ptr(X0), _ptr(out['X']), _ptr(out['U']), _ptr(out['Xr']), _ptr(out['dX']),
                 _ptr(out['Yd']), _ptr(out['Ydd']), _ptr(out['X_final']))
-        if wind is None:
+        if gust is not None:
+            g = self._gust_c(gust, dt, gust_n_ac, n, gust_phase, gust_state, gust_stream_base)
+            if out.get('gust_state') is None:
+                out['gust_state'] = self.empty(4, n)
+            if 'g' in record and out.get('g') is None:
+                out['g'] = self.zeros(T, 2, n)
+            g.state_out, g.g_hist = out['gust_state'].data_ptr(), None if out.get('g') is None else out['g'].data_ptr()
+            f = None if wind is None else _wind_c(self, wind)
+            t_at = None
+            if f is None:
+                assert not hasattr(t_start, 'data_ptr'), 'per-drone start times (a tensor) need a wind field: without one the time is not read'
+            else:
+                out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
+                if hasattr(t_start, 'data_ptr'):
+                    t_at = t_start
+                    assert t_at.is_contiguous() and tuple(t_at.shape) == (n,) and t_at.dtype == _torch().float64 and t_at.device == x_ref.device
+                elif float(t_start) != 0.0:                     # (the entry point takes the start times per drone, or none: all 0)
+                    t_at = _torch().full((n,), float(t_start), dtype=_torch().float64, device=self.device)
+            _check(self.lib.d2d_sim_track_run_gust(*args, None if f is None else C.byref(f), _ptr(t_at), _ptr(out.get('iter_max')), C.byref(g)))
+        elif wind is None:
             assert not hasattr(t_start, 'data_ptr'), 'per-drone start times (a tensor) need a wind field: without one the time is not read'
             _check(self.lib.d2d_sim_track_run(*args))
         else:

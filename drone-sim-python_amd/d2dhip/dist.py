@@ -13,6 +13,13 @@ def shard_bounds(total, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def gust_stream_base(total_form, rank, world, n_ac):
+    """The gust stream_base of this rank's shard of total_form formations of n_ac aircraft (shard_bounds over the formations): the
+    global index of its first drone.  A drone's gust is a function of (seed, global drone index, phase, step) alone, so the shards
+    of a study fly the gusts the unsharded batch would, bit for bit (include/d2d.h d2d_gust)."""
+    return shard_bounds(total_form, rank, world)[0] * int(n_ac)
+
+
 class StatsReducer:
     """The convergence exchange.  `device` is where the backend wants its buffers (cuda:<local_rank> for nccl / RCCL, cpu for
     gloo).  Everything is allocated once: a pinned host staging tensor, the device send buffer and the gathered [world, 3]

@@ -10,12 +10,14 @@ GPU, plus batched variants over many independent formations.
 Wind: the constant WindField classes take the constant-wind loops as before; a d2d.wind.SplineWindField (windfield=) is flown by
 the plant at each aircraft's own position and time (the reference's WindField.sample plug-point); any other field with its own
 sample() raises NotImplementedError (d2d.wind.plant_wind) instead of being frozen at one sample.
+Gusts: gust= (a d2d.wind.GustModel) adds a stochastic gust per aircraft, drawn inside the device loops, to whichever wind the plant
+flies; the controllers never see it.  The planners take none: a gust is a property of the plant, not of a plan.
 """
 import numpy as np
 
 import d2dhip
 import d2d.dynamic as ddyn
-from d2d.wind import plant_wind
+from d2d.wind import plant_gust, plant_wind
 
 KE, KD, KR = 0.0004, 25, 20            # src/11_full_sim_case1.py:108-110
 X1_START = np.array([20, 30, -np.pi / 2, 0, 10])     # :113
@@ -58,17 +60,21 @@ def _audit_kw(ctx, audit, n_form, what):
 
 def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, t_end=1000, X0=None,
                                tau_phi=None, rec_stride=1, record=('X', 'U', 'Rr', 'eth'), W=(0., 0.), etheta_tol_deg=None,
-                               t_opt_comp=0.0, windfield=None, audit=None):
+                               t_opt_comp=0.0, windfield=None, audit=None, gust=None, gust_state=None, gust_phase=0, gust_stream_base=0):
     """Many formations at once.  c (n_form, n_ac, 2) centres; r scalar or (n_form, n_ac); X0
     (n_form, n_ac, 5) or None (every aircraft starts at the reference's X1); X0f (n_form, n_ac, >=3)
     or None.  etheta_tol_deg: stop by the phase-error rule of cases 2 / 3 instead of the state rule (after t_opt_comp more seconds on
     which it holds).  windfield: a SplineWindField the plant flies instead of W (row i at t_start + i t_step; the GVF law never reads
     the wind).  Returns the raw device dictionary of d2dhip.Context.gvf_run plus `time`.
     audit: True or a dict (d_safe, err_tol, static: _audit_kw) -- out['audit'] is Context.flight_audit of the recorded history: every
-    formation's rows up to its stop row (derived on the device), dt_row = t_step rec_stride; needs 'X' in record."""
+    formation's rows up to its stop row (derived on the device), dt_row = t_step rec_stride; needs 'X' in record.
+    gust: a d2d.wind.GustModel flown on top of W or the field (the law sees none of it); gust_state dev [4][N] or None (the stationary
+    start), gust_phase: the loop's phase word, gust_stream_base: the global index of the first drone (a shard of a larger batch).
+    out['gust_state'] dev [4][N]: the state after each formation's last executed step; with 'g' in record out['g'] dev [n_rec][2][N]."""
     if audit is not None and 'X' not in record:
         raise ValueError("audit needs the state history: 'X' must be in record")
     fld = plant_wind(windfield)
+    gkw = {} if plant_gust(gust) is None else dict(gust=gust, gust_state=gust_state, gust_phase=gust_phase, gust_stream_base=gust_stream_base)
     ctx = d2dhip.default_context()
     c = np.asarray(c, dtype=np.float64).reshape(-1, n_ac, 2)
     n_form = c.shape[0]
@@ -83,7 +89,7 @@ def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, 
                       tau_phi=ac.tau_phi if tau_phi is None else tau_phi, tau_v=ac.tau_v, W=W, X0f=x0f,
                       rec_stride=rec_stride, record=record, etheta_tol_deg=etheta_tol_deg,
                       stop_hold=hold_steps(t_opt_comp, t_step) if etheta_tol_deg is not None else 0,
-                      **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
+                      **({} if fld is None else dict(wind=fld, t_start=float(time[0]))), **gkw)
     out['time'] = time
     if audit is not None:
         torch = d2dhip._torch()
@@ -191,21 +197,27 @@ def ExtendTraj_symm(n_ac, x_ref, y_ref, psi_ref, time):
     return time, np.append(x_ref, xs, axis=0), np.append(y_ref, ys, axis=0), np.append(psi_ref, ys, axis=0)
 
 
-def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), windfield=None, audit=None):
+def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), windfield=None, audit=None,
+                               gust=None, gust_state=None, gust_phase=0, gust_n_ac=1, gust_stream_base=0):
     """x_ref, y_ref (T, n) for n independent drones; X0s (n, 5).  Device dictionary out.  windfield: a SplineWindField the plant
     flies (row i at time[i]); the controller keeps w, as DiffController(w) does (src/11_full_sim_case1.py:241-291).
     audit: True or a dict (d_safe, err_tol, static: _audit_kw; n_ac: consecutive drones that form a formation, default 1 -- the
-    drones are independent) -- out['audit'] is Context.flight_audit of the flown history against x_ref, y_ref; needs 'X' in record."""
+    drones are independent) -- out['audit'] is Context.flight_audit of the flown history against x_ref, y_ref; needs 'X' in record.
+    gust: a d2d.wind.GustModel flown on top of w or the field (the controller sees none of it); gust_state, gust_phase,
+    gust_stream_base as in CircularFormationGVF_batch, gust_n_ac: consecutive drones that share the formation part of the gust.
+    out['gust_state'] dev [4][n]; with 'g' in record out['g'] dev [T][2][n]."""
     if audit is not None and 'X' not in record:
         raise ValueError("audit needs the state history: 'X' must be in record")
     fld = plant_wind(windfield)
+    gkw = {} if plant_gust(gust) is None else dict(gust=gust, gust_state=gust_state, gust_phase=gust_phase, gust_n_ac=gust_n_ac,
+                                                   gust_stream_base=gust_stream_base)
     ctx = d2dhip.default_context()
     ac = ddyn.Aircraft()
     dt = time[1] - time[0]
     xr, yr = ctx.dev(np.ascontiguousarray(x_ref, dtype=np.float64)), ctx.dev(np.ascontiguousarray(y_ref, dtype=np.float64))
     out = ctx.track_run(xr, yr, ctx.dev(_planes(np.asarray(X0s, dtype=np.float64))), float(dt), record=record,
                         w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v,
-                        **({} if fld is None else dict(wind=fld, t_start=float(time[0]))))
+                        **({} if fld is None else dict(wind=fld, t_start=float(time[0]))), **gkw)
     if audit is not None:
         n_ac = 1 if audit is True else int(audit.get('n_ac', 1))
         kw = _audit_kw(ctx, audit, xr.shape[1] // n_ac, ('n_ac',))
@@ -272,7 +284,7 @@ def _plan_batch_via(ctx, scen_rows, dsc, W, N, h, n_ac, fld, t_start, moving, vi
 
 
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               moving=None, via=None, **solve_kw):
+               moving=None, via=None, gust=None, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -293,6 +305,9 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     hand-out of d2d_nlp_solve_via -- for large batches of single aircraft call Context.nlp_solve_via (the difference is not measured)."""
     import single_opt_planner as sop
     from d2d.wind import planner_wind
+    if gust is not None:
+        raise ValueError('a gust is a property of the plant, not of a plan: the planners take none (fly the plan through it with '
+                         'implement_controller_batch(gust=...) or full_sim_phases_batch(gust=...))')
     fld = planner_wind(windfield)
     if moving and backend != 'nlp':
         raise NotImplementedError("the polynomial fit has no moving obstacles: plan_batch(backend='nlp', moving=...) plans around them")
@@ -327,7 +342,7 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
 
 def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_sim_end=200., w=(0., 0.), t_step=0.05,
                           t_end_1=1000., X0=None, max_sweeps=250, record2=('X', 'U'), record3=('X', 'U'), windfield=None,
-                          moving_obstacles=None, audit=None):
+                          moving_obstacles=None, audit=None, gust=None, gust_stream_base=0):
     """The three phases of src/11_full_sim_case1.py main() (:406-478) for many independent formations, chained ON THE
     DEVICE: the circular-formation phase hands its final states to the planner as a device tensor, the planner's sampled
     plan is the tracking reference of phase 2 without leaving HBM, and phase 3 restarts from phase 2's final states.
@@ -365,19 +380,32 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     then holds Context.flight_audit dictionaries of what was planned and what was flown: plan (the plan Xs as a history with
     dt_row = dt2), phase2 (the flown X against the plan's x, y) and phase3 (a list, one per repetition, against the phase-3
     reference) -- on the chain's clock where it has one (a field or moving discs: t_start = t2, repetition k of phase 3 from
-    t2 + dur2 + k time_3[-1]) and around the chain's moving discs.  'X' must be in record2 / record3."""
+    t2 + dur2 + k time_3[-1]) and around the chain's moving discs.  'X' must be in record2 / record3.
+    gust: None (nothing new is launched, the result is what it was) or a d2d.wind.GustModel the PLANT flies through all three phases
+    on top of w or F -- an unmeasured disturbance: neither the controllers nor the plan see it.  Every loop counts its steps from 1
+    under its own phase word (phase 1: 0, phase 2: 1, repetition k of phase 3: 2 + k) and hands its gust state to the next on the
+    device (phase*['gust_state'] dev [4][N]; 'g' in record2 / record3 keeps the flown gusts); gust_stream_base: the global index of the
+    first drone when the formations are a shard of a larger study."""
     import multi_opt_planner as mop
     if audit is not None and ('X' not in record2 or (ref3 is not None and 'X' not in record3)):
         raise ValueError("audit needs the flown histories: 'X' must be in record2 and record3")
     import d2d.opty_utils as d2ou
     F = plant_wind(windfield)
+    gust = plant_gust(gust)
+
+    def gk(phase, state, track=False):
+        """the gust arguments of the loop with this phase word (track: of Context.track_run, which is told the formation size)"""
+        if gust is None:
+            return {}
+        return dict(gust=gust, gust_state=state, gust_phase=phase, gust_stream_base=gust_stream_base, **(dict(gust_n_ac=n_ac) if track else {}))
+
     ctx = d2dhip.default_context()
     torch = d2dhip._torch()
     c = np.asarray(c, dtype=np.float64).reshape(-1, n_ac, 2)
     n_form = c.shape[0]
     X1f = np.broadcast_to(np.asarray(X1_f, dtype=np.float64).reshape(-1, n_ac, np.shape(X1_f)[-1])[:, :, :3], (n_form, n_ac, 3))
     X2f = np.broadcast_to(np.asarray(X2_f, dtype=np.float64).reshape(-1, n_ac, np.shape(X2_f)[-1])[:, :, :3], (n_form, n_ac, 3))
-    ph1 = CircularFormationGVF_batch(c, r, v, n_ac, X0f=X1f, t_step=t_step, t_end=t_end_1, X0=X0, record=(), windfield=F)
+    ph1 = CircularFormationGVF_batch(c, r, v, n_ac, X0f=X1f, t_step=t_step, t_end=t_end_1, X0=X0, record=(), windfield=F, **gk(0, None))
     Xs1 = ph1['X_final']                                            # dev [5][N]: state at each formation's stop row
     # ---- phase 2: plan from where phase 1 ended (scenario rows finished on the device) ----
     scen.t1 = t_opt
@@ -438,7 +466,9 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     if pairs is not None:
         pl['pairs'] = pairs
     x_ref2 = Xs[:, 0, :].t().contiguous(); y_ref2 = Xs[:, 1, :].t().contiguous()     # dev [K][N]
-    ph2 = ctx.track_run(x_ref2, y_ref2, Xs1, float(dt2), record=record2, **kw, **kw2)
+    gs = ph1.get('gust_state')
+    ph2 = ctx.track_run(x_ref2, y_ref2, Xs1, float(dt2), record=record2, **kw, **kw2, **gk(1, gs, track=True))
+    gs = ph2.get('gust_state')
     out = dict(phase1=ph1, plan=pl, phase2=ph2, phase3=[])
     if audit is not None:
         akw = _audit_kw(ctx, audit, n_form, ())
@@ -461,7 +491,8 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
         while t_final <= t_sim_end:
             if F is not None:
                 kw2 = dict(t_start=t2d + (float(dur2) + k * float(time_3[-1])))
-            ph3 = ctx.track_run(x3, y3, X_last, dt3, record=record3, **kw, **kw2)
+            ph3 = ctx.track_run(x3, y3, X_last, dt3, record=record3, **kw, **kw2, **gk(2 + k, gs, track=True))
+            gs = ph3.get('gust_state')
             out['phase3'].append(ph3)
             if audit is not None:
                 t3 = float(dur2) + k * float(time_3[-1])

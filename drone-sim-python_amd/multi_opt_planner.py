@@ -60,7 +60,10 @@ def min_separation(X, Y, pairs):
 
 
 class Planner:
-    def __init__(self, scen, initialize=True, backend=None):
+    def __init__(self, scen, initialize=True, backend=None, gust=None):
+        if gust is not None:
+            raise ValueError('a gust is a property of the plant, not of a plan: the planner takes none (fly the plan through it with '
+                             'full_sim.implement_controller_batch(gust=...))')
         self.scen = scen
         self.backend = backend or sop.BACKEND            # 'fit' | 'nlp' (single_opt_planner.BACKEND)
         self.obj_scale = scen.obj_scale

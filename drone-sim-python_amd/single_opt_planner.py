@@ -242,7 +242,10 @@ class _FitProblem:
 
 
 class Planner:
-    def __init__(self, exp, initialize=True, backend=None):
+    def __init__(self, exp, initialize=True, backend=None, gust=None):
+        if gust is not None:
+            raise ValueError('a gust is a property of the plant, not of a plan: the planner takes none (fly the plan through it with '
+                             'full_sim.implement_controller_batch(gust=...))')
         self.exp = exp
         self.backend = backend or BACKEND
         self.obj_scale = exp.obj_scale

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 117
+#define D2D_VERSION 118
 
 /* error codes */
 #define D2D_OK 0
@@ -271,6 +271,66 @@ int d2d_sim_dfff_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double 
 int d2d_sim_track_run_wind_at(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
                               double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
                               double *X_final, const d2d_wind_field *f, const double *t_start, int32_t *iter_max);
+
+/* Stochastic gusts: an unmeasured disturbance of the plant inside the time loops (version 118).  Each drone d flies, on top of the
+ * constant wind or the field, the gust g = w_own o(d) + w_form h(formation of d): o is the drone's own process, h one process per
+ * formation of n_ac consecutive drones (aircraft 50 m apart do not see independent air), w_own = sqrt(1 - c), w_form = sqrt(c) for a
+ * formation correlation c in [0, 1).  The controllers never see it (the reference hands w to DiffController and WindField(w) to the
+ * plant separately, src/11_full_sim_case1.py:241-291).
+ *   Random numbers  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl increments 0x9E3779B9, 0xBB67AE85, ten rounds), one call
+ *                   per process and step: counter = (step_base + step, stream & 0xffffffff, stream >> 32, sub), key = (seed &
+ *                   0xffffffff, seed >> 32), sub = 2 phase + part (part 0: the drone's own process, 1: the formation's);
+ *                   u1 = ((r0 >> 5) 2^26 + (r1 >> 6) + 0.5) 2^-53, u2 the same from r2, r3; (xi_x, xi_y) = sqrt(-2 ln u1) (cos, sin)(2 pi u2).
+ *                   The own process of drone d draws on stream stream_base + d, the shared one on (stream_base + d) / n_ac: a gust is
+ *                   a function of (seed, stream, phase, step) alone, bit for bit, whatever the batch, the block layout or the shard
+ *                   (a shard passes the global index of its first drone as stream_base).
+ *   Process         first-order Gauss-Markov per component, discretised exactly: o_i = a o_{i-1} + s xi_i, a = exp(-dt / tau),
+ *                   s = sigma sqrt(1 - a^2), both computed by the host in fp64 (tau = L / V: the first-order Dryden form).  With
+ *                   w_form = 0 the shared call is not made and the shared planes keep what they started with (0 without state_in).
+ *   Time            a zero-order hold like the inputs: step i, from row i - 1 to row i, flies w + g_{i-1}; after the step the state
+ *                   advances with the draw at counter step_base + i.  Every loop counts its steps from 1; `phase` separates the loops
+ *                   of one mission (full_sim: phase 1 -> 0, phase 2 -> 1, repetition k of phase 3 -> 2 + k) and the state is handed
+ *                   from loop to loop on the device.  step_base (0 in the loops of a mission) lets one series be CONTINUED under the
+ *                   same phase word: a call from state_out with step_base advanced by the steps already made reproduces the rows
+ *                   of one long call bit for bit.
+ *   State           gs dev [4][N]: own x, own y, shared x, shared y (the shared planes replicated per aircraft).  state_in NULL: the
+ *                   stationary start o_0 = sigma xi(step_base); given: o_0 is read from it and that draw is not made.  state_out (or
+ *                   NULL): gs after the last EXECUTED step -- of a formation that stopped with stop_row = m, after step m - 1.
+ *   g_hist          dev [n_rec][2][N] or NULL: row q holds g_q, the gust flown during step q + 1, on the rows X_hist keeps.
+ * D2D_EINVAL before anything is launched: gust NULL; sigma or s negative or not finite; a outside [0, 1); a weight that is negative or
+ * not finite, or w_own^2 + w_form^2 further than 1e-12 from 1; n_ac < 1, N % n_ac, stream_base % n_ac, stream_base < 0; phase or
+ * step_base < 0, step_base + n_rows beyond the 32-bit step word.  n_ac is the gust's own (the tracking loop has none); in the
+ * formation loop pass p->n_ac.  (phase is a non-negative int32, so sub = 2 phase + part < 2^32 never wraps: no two phases share
+ * a word.)  A non-finite state_in entry is not detected, exactly as a non-finite X0 is not: it propagates as NaN into that drone's
+ * gust, history and final state (shared planes: the caller keeps them equal within a formation). */
+typedef struct {
+  uint64_t seed;
+  int64_t stream_base;     /* stream of drone 0 of this call: >= 0, a multiple of n_ac */
+  int32_t phase;           /* >= 0: the loop of the mission */
+  int32_t n_ac;            /* aircraft per formation: consecutive drones that share h */
+  int64_t step_base;       /* added to the step counter; 0 unless a series is continued */
+  double a, s, sigma;      /* exp(-dt / tau), sigma sqrt(1 - a^2), sigma (m/s) */
+  double w_own, w_form;    /* sqrt(1 - c), sqrt(c) */
+  const double *state_in;  /* dev [4][N] or NULL */
+  double *state_out;       /* dev [4][N] or NULL */
+  double *g_hist;          /* dev [n_rec][2][N] or NULL */
+} d2d_gust;
+
+/* The process alone, without a loop: rows 0 .. n_rows - 1 of g_hist [n_rows][2][N] and state_out after step n_rows - 1 -- the
+ * statements of the time loops in the same order, so a loop's g equals this series bit for bit.  state_out and g_hist both NULL:
+ * D2D_EINVAL. */
+int d2d_gust_sample(d2d_ctx *ctx, int64_t N, int n_rows, const d2d_gust *gust);
+/* d2d_sim_gvf_run / d2d_sim_gvf_run_wind through gusts: f NULL means the constant p->wx, p->wy (t_start, iter_max are then not used).
+ * Every formation size takes the general (LDS-exchange) kernel.  A frozen formation does not advance its gust. */
+int d2d_sim_gvf_run_gust(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
+                         const double *Bmat, const double *z_des, const double *X0f, double *X_hist, double *U_hist, double *Rr_hist,
+                         double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const d2d_wind_field *f,
+                         double t_start, int32_t *iter_max, const d2d_gust *gust);
+/* d2d_sim_track_run / _wind / _wind_at through gusts: f NULL means the constant p->wx, p->wy for the plant too; t_start dev [n] or
+ * NULL (0 for every drone; not read without a field).  g_hist has n_rows rows. */
+int d2d_sim_track_run_gust(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
+                           double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
+                           double *X_final, const d2d_wind_field *f, const double *t_start, int32_t *iter_max, const d2d_gust *gust);
 
 /* Single batched evaluations behind the reference's per-call helper methods (the time
  * loops above fuse them; these exist so that host code written against the reference's
