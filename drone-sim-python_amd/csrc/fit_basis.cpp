@@ -86,29 +86,58 @@ bool invert(Dense &A) {
 
 }  // namespace
 
+// segment lookup of the K samples (CompositeTraj.get, src/d2d/trajectory.py:202-208)
+void fit_basis_sample_segments(int S, int K, double duration, std::vector<int> &seg, std::vector<double> &tau) {
+  const double T = duration / S;
+  seg.assign(K, 0);
+  tau.assign(K, 0.0);
+  std::vector<double> ends(S);
+  double acc = 0;
+  for (int s = 0; s < S; ++s) { acc += T; ends[s] = acc; }
+  for (int k = 0; k < K; ++k) {
+    // numpy.linspace(0, duration, K): start + k*step, last sample forced to `duration`
+    const double step = duration / (K - 1);
+    const double t = (k == K - 1) ? duration : k * step;
+    int s = S - 1;
+    for (int j = 0; j < S; ++j)
+      if (ends[j] > t) { s = j; break; }
+    seg[k] = s;
+    tau[k] = t - s * T;
+  }
+}
+
+// first sample of every segment of the knot-space statement, k0[S .. D2D_FIT_MAX_S] = K (an empty segment: an empty range)
+void fit_knot_first_samples(const std::vector<int> &seg, int S, int *k0) {
+  const int K = (int)seg.size();
+  for (int s = 0; s <= D2D_FIT_MAX_S; ++s) k0[s] = K;
+  for (int k = K - 1; k >= 0; --k) k0[seg[k]] = k;
+  for (int s = S - 1; s >= 0; --s) {
+    bool any = false;
+    for (int k = 0; k < K && !any; ++k) any = seg[k] == s;
+    if (!any) k0[s] = k0[s + 1];
+  }
+}
+
+// shortest and longest segment of such a plan (either pointer may be NULL)
+void fit_knot_seg_range(const int *k0, int S, int *smin, int *smax) {
+  int lo = S > 0 ? k0[1] - k0[0] : 0, hi = lo;
+  for (int s = 1; s < S; ++s) {
+    const int n = k0[s + 1] - k0[s];
+    lo = n < lo ? n : lo;
+    hi = n > hi ? n : hi;
+  }
+  if (smin) *smin = lo;
+  if (smax) *smax = hi;
+}
+
 int fit_basis_build(d2d_fit_plan *pl) {
   const int S = pl->S, K = pl->K, nz = 8 * S, nk = 4 * (S + 1), nq = 4 * S;
   const double T = pl->duration / S;
   pl->T = T;
   pl->nq = nq;
-  // --- segment lookup of the K samples (CompositeTraj.get, src/d2d/trajectory.py:202-208)
-  std::vector<int> seg(K);
-  std::vector<double> tau(K);
-  {
-    std::vector<double> ends(S);
-    double acc = 0;
-    for (int s = 0; s < S; ++s) { acc += T; ends[s] = acc; }
-    for (int k = 0; k < K; ++k) {
-      // numpy.linspace(0, duration, K): start + k*step, last sample forced to `duration`
-      const double step = pl->duration / (K - 1);
-      const double t = (k == K - 1) ? pl->duration : k * step;
-      int s = S - 1;
-      for (int j = 0; j < S; ++j)
-        if (ends[j] > t) { s = j; break; }
-      seg[k] = s;
-      tau[k] = t - s * T;
-    }
-  }
+  std::vector<int> seg;
+  std::vector<double> tau;
+  fit_basis_sample_segments(S, K, pl->duration, seg, tau);
   pl->seg = seg;
   pl->tau = tau;
   // --- Phi_d (K x 8S), d = 0..2
@@ -343,10 +372,7 @@ int fit_basis_knots(d2d_fit_plan *pl) {
         kn.Hb32[(size_t)k * 32 + 4 * m + d] = fixed ? 0.f : (float)v;
       }
   }
-  for (int s = 0; s <= S; ++s) kn.k0[s] = s < S ? pl->seg_k0[s] : K;
-  for (int s = 0; s < S; ++s)
-    if (pl->seg_Ks[s] == 0) kn.k0[s] = s + 1 < S ? pl->seg_k0[s + 1] : K;     // (an empty segment: empty range)
-  for (int s = S + 1; s <= D2D_FIT_MAX_S; ++s) kn.k0[s] = K;
+  fit_knot_first_samples(pl->seg, S, kn.k0);
   // waypoint rows' constant J^T J: per segment sum_k Hb0_k^T Hb0_k on the (x, x) and (y, y) columns, in the MFMA accumulator layout
   kn.Wseg.assign((size_t)S * 4 * 64, 0.f);
   for (int s = 0; s < S; ++s)

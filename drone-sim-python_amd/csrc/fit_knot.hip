@@ -28,6 +28,8 @@
 #define KN_US 10                // doubles per sample of the u records [axis][4] (80 B)
 #define KN_GTOL_SCALE 0.1        // the finish's gradient test in the metric's diagonal scaling: a tenth of gtol (oracle/fit_knot.py GTOL_SCALE)
 #define KN_SEG_MAX 11            // samples of one segment at K <= 64, S = 6
+#define KN_FUSED_DEPTH 6         // k-steps between the fetch of an MFMA operand and its use in knot_eval_fused
+#define KN_SEG_FLOOR 8           // the instantiated floor on a plan's shortest segment (template parameter SEGMIN)
 #define KN_IMG_LS (KN_N + 4)    // row stride of the dense image (fit_phases.h CHOL_LS)
 
 namespace {
@@ -235,6 +237,124 @@ __device__ __forceinline__ void knot_mfma(const KnotGeom &kg, const unsigned cha
   }
 }
 
+// ---- phases 2 + 3 in one pass, for a plan whose segments all hold at least SEGMIN samples (SEGMIN > 0: fit_knot_launch) -------------
+// v_mfma_f32_16x16x4_f32 holds the matrix pipe for 32 cycles and the pass is nothing but 50 of them: J^T r -- which needs only the
+// u records the pass reads too -- is issued in that shadow.  The SAME operations as knot_phase2 and knot_mfma<SEGMAX>, per lane in
+// the same order (every sum keeps its order); what the floor buys is the form:
+//   * k-step i < SEGMIN of a segment is unconditional and its index unclamped: one base address per segment and table, immediate
+//     offsets, no branch between the MFMAs; only the steps SEGMIN <= i < SEGMAX keep their predicate;
+//   * a sample i < SEGMIN of phase 2 is read unmasked.  A lane's half is either empty (the outer knots, the lanes without an entry)
+//     or holds n >= SEGMIN samples: a lane of an empty half reads the samples 0 .. of the table and its sums are put back to what
+//     they were at the SEGMIN-th sample; its masked FMAs fma(0, 0, a) -- the knot_phase2 loop runs SLOTS = 3 ceil(smax / 3)
+//     samples, SEGMIN is no multiple of three, so there is one -- follow as they do there;
+//   * half `h` of phase 2 goes, sample by sample, between the k-steps of the segments 3 h .. 3 h + 2.
+template <int SEGMAX, int SEGMIN>
+__device__ __forceinline__ double knot_eval_fused(const KnotGeom &kg, const unsigned char *lds, const double *Hb64, const double *us,
+                                                  int kb, int km, int ke, int a, int kd, bool live, int hb32_off, int cf_off,
+                                                  const float *Wseg, float ww, int lane, f32x4 (&acc)[D2D_FIT_MAX_S]) {
+  typedef double __attribute__((ext_vector_type(2), may_alias)) f64x2a;
+  constexpr int SLOTS = (SEGMAX + 2) / 3 * 3;
+  static_assert(SEGMIN > 0 && SEGMIN <= SEGMAX && SEGMIN % 3 != 0, "a masked sample follows the floor in every half");
+  static_assert(D2D_FIT_MAX_S == 6, "two halves of three segments");
+  LAUNDER(lane);
+  LAUNDER(kb);
+  const int c = lane & 15, r = lane >> 4;
+  const int m = 4 * (c >> 3) + (c & 3), ax = (c >> 2) & 1;
+  const int tab = hb32_off + (4 * m + (r < 2 ? 1 : 0)) * 4;
+  const int cfo = cf_off + r * 16 + ax * 8;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int s0 = 3 * half;
+    // phase 2: this half's range, the lane's two base addresses
+    const int k0 = half ? km : kb, k1 = half ? ke : km;
+    const int n = live ? k1 - k0 : 0;
+    const bool some = n > 0;
+    const int k0r = some ? k0 : 0;
+    const double *hb = Hb64 + (size_t)k0r * KN_HB_STRIDE + 4 * ((half ? 0 : 4) + kd);
+    const double *uk = us + k0r * KN_US + 4 * a;
+    const double b0 = a0, b1 = a1, b2 = a2;
+    // phase 3: the accumulators' start values, and the operands of the first two rows of k-steps (a row: one k-step of each of the
+    // three segments); the pass below fetches the operands of k-step q + 6 behind k-step q -- two 8-byte reads, 192 cycles of
+    // the matrix pipe ahead of their use -- and forms the operand of k-step q + 1 there
+    constexpr int NQ = 3 * SEGMIN, TAIL = SEGMAX - SEGMIN, DEPTH = KN_FUSED_DEPTH;
+    static_assert(SEGMIN >= 4, "the operand pipeline is two rows deep");
+    const unsigned char *tp[3], *cp[3];
+    float2 rt[DEPTH], rc[DEPTH], rtt[3][TAIL > 0 ? TAIL : 1], rct[3][TAIL > 0 ? TAIL : 1];
+    float vq[2], vt[3][TAIL > 0 ? TAIL : 1];
+    int ns[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int s = s0 + j;
+      int sb = kg.k0[s];
+      ns[j] = kg.k0[s + 1] - kg.k0[s];
+      LAUNDER_S(sb); LAUNDER_S(ns[j]);
+      tp[j] = lds + tab + sb * 128; cp[j] = lds + cfo + sb * 64;
+#pragma unroll
+      for (int i = 0; i < DEPTH / 3; ++i) { rt[3 * i + j] = lds_get<float2>(tp[j] + i * 128); rc[3 * i + j] = lds_get<float2>(cp[j] + i * 64); }
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) acc[s][rr] = ww * Wseg[(s * 4 + rr) * 64 + lane];
+    }
+    vq[0] = fmaf(rc[0].y, rt[0].y, rc[0].x * rt[0].x);
+    __builtin_amdgcn_sched_barrier(0);
+    // the k-steps, round-robin over the three accumulators; sample w of phase 2 rides on the unconditional ones: its four reads
+    // behind k-step STEP w, its three FMAs behind k-step STEP w + LAG (LAG k-steps = 96 cycles of the matrix pipe: the reads are
+    // back).  The order is held (sched_barrier): left to itself the scheduler takes every read of the half to the front of the pass
+    // and spills them.
+    constexpr int LAG = 3, STEP = (NQ - 1 - LAG) / (SLOTS - 1), NBUF = LAG / (STEP > 0 ? STEP : 1) + 1;
+    static_assert(STEP >= 1, "every sample of the half finds its two k-steps");
+    f64x2a h01[NBUF], u01[NBUF];
+    double h2[NBUF], u2[NBUF];
+    auto p2_read = [&](int idx, int i) {
+      if (idx < SEGMIN) {
+        h01[i] = *reinterpret_cast<const f64x2a *>(hb + idx * KN_HB_STRIDE); u01[i] = *reinterpret_cast<const f64x2a *>(uk + idx * KN_US);
+        h2[i] = hb[idx * KN_HB_STRIDE + 2]; u2[i] = uk[idx * KN_US + 2];
+      } else {                                            // past the floor: the sample of a longer segment, zeros elsewhere
+        const bool in = idx < n;
+        const int o = in ? idx : 0;
+        const f64x2a hr = *reinterpret_cast<const f64x2a *>(hb + o * KN_HB_STRIDE), ur = *reinterpret_cast<const f64x2a *>(uk + o * KN_US);
+        const double h2r = hb[o * KN_HB_STRIDE + 2], u2r = uk[o * KN_US + 2];
+        h01[i] = in ? hr : f64x2a{0.0, 0.0}; u01[i] = in ? ur : f64x2a{0.0, 0.0};
+        h2[i] = in ? h2r : 0.0; u2[i] = in ? u2r : 0.0;
+      }
+    };
+    auto p2_fma = [&](int idx, int i) {
+      if (idx == SEGMIN) { a0 = some ? a0 : b0; a1 = some ? a1 : b1; a2 = some ? a2 : b2; }
+      a0 = fma(h01[i].x, u01[i].x, a0);
+      a1 = fma(h01[i].y, u01[i].y, a1);
+      a2 = fma(h2[i], u2[i], a2);
+      LAUNDER(a0); LAUNDER(a1); LAUNDER(a2);              // (held here: the sums are sunk below the predicated k-steps otherwise)
+    };
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int i = q / 3, j = q % 3;
+      acc[s0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vq[q & 1], vq[q & 1], acc[s0 + j], 0, 0, 0);
+      if (q + DEPTH < NQ) {
+        rt[q % DEPTH] = lds_get<float2>(tp[j] + (i + DEPTH / 3) * 128); rc[q % DEPTH] = lds_get<float2>(cp[j] + (i + DEPTH / 3) * 64);
+      } else if (q + 6 < NQ + 3 && q + 6 >= NQ) {                        // the predicated k-steps of this segment: clamped past its end
+#pragma unroll
+        for (int t = 0; t < TAIL; ++t) {
+          const int kk = SEGMIN + t < ns[j] ? SEGMIN + t : ns[j] - 1;
+          rtt[j][t] = lds_get<float2>(tp[j] + kk * 128); rct[j][t] = lds_get<float2>(cp[j] + kk * 64);
+        }
+      } else if (q + 3 >= NQ) {
+#pragma unroll
+        for (int t = 0; t < TAIL; ++t) vt[j][t] = fmaf(rct[j][t].y, rtt[j][t].y, rct[j][t].x * rtt[j][t].x);
+      }
+      if (q % STEP == 0 && q / STEP < SLOTS) p2_read(q / STEP, (q / STEP) % NBUF);
+      if (q >= LAG && (q - LAG) % STEP == 0 && (q - LAG) / STEP < SLOTS) p2_fma((q - LAG) / STEP, ((q - LAG) / STEP) % NBUF);
+      if (q + 1 < NQ) vq[(q + 1) & 1] = fmaf(rc[(q + 1) % DEPTH].y, rt[(q + 1) % DEPTH].y, rc[(q + 1) % DEPTH].x * rt[(q + 1) % DEPTH].x);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int t = 0; t < TAIL; ++t)
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if (SEGMIN + t < ns[j]) acc[s0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[j][t], vt[j][t], acc[s0 + j], 0, 0, 0);
+  }
+  return (a0 + a1) + a2;
+}
+
 // second-order mode: B_s = sum_k G_k^T M_k G_k (fit_phases.h jtj_mfma_so): per sample one velocity k-step (A = the plain rows a, b,
 // c, d = G1 on x, G1 on y, G2 on x, G2 on y; B = the M_vel-weighted rows from the block records) and one position k-step (rows
 // x, y; rows 2, 3 zero)
@@ -383,7 +503,9 @@ template <> struct nd_panel3_chunk0_zero<KnotMetric> { static constexpr bool val
 namespace {
 
 // SEG9: no segment holds more than nine samples (K <= 54 at S = 6: the bench's K = 50) -- the MFMA pass keeps 27 operands, not 33
-template <bool STAMPS, bool SEG9>
+// SEGMIN: a floor on the samples of EVERY segment of the plan (0: none known -- the generic code): phases 2 and 3 of a first-order
+// evaluation run as one pass (knot_eval_fused)
+template <bool STAMPS, bool SEG9, int SEGMIN>
 __global__ void __launch_bounds__(64 * KN_WPB_MAX)
 fit_lm_knot_kernel(int B, KnotGeom kg, KnotLds L, d2d_fit_opts opts, int iter_cap, KnotDev T, const double *__restrict__ pk,
                    const double *__restrict__ prep, double *q_io, double *cost_io, double *g_io, double *lm, int32_t *flags,
@@ -591,14 +713,20 @@ fit_lm_knot_kernel(int B, KnotGeom kg, KnotLds L, d2d_fit_opts opts, int iter_ca
           if (fresh) {
             int p2_kb, p2_km, p2_ke;
             p2_ranges(p2_kb, p2_km, p2_ke);
-            gi = knot_phase2(kg, Hb64, us, p2_kb, p2_km, p2_ke, ea, ekd, act, lane);
-            KN_STAMP(2)
-            fresh = false;
-            if (status != D2D_ST_RUNNING) break;
             f32x4 acc[D2D_FIT_MAX_S];
             const float ww = (float)(sp[PR_WWP] * sp[PR_WWP]);
             const int wbase = L.wave0 + wave * L.wave_stride;
+            // with a floor on the segments a first-order evaluation forms J^T r inside the MFMA pass (knot_eval_fused); the
+            // stand-alone phase 2 stays for second-order mode and for the fit that leaves here, whose accumulators nobody reads
+            const bool fused = SEGMIN > 0 && !so_rows && status == D2D_ST_RUNNING;
+            if (!fused) gi = knot_phase2(kg, Hb64, us, p2_kb, p2_km, p2_ke, ea, ekd, act, lane);
+            KN_STAMP(2)
+            fresh = false;
+            if (status != D2D_ST_RUNNING) break;
             if (so_rows) knot_mfma_so(kg, lds, L.Hb32, wbase + L.cf, wbase + L.cfp, Wseg, ww, lane, acc);
+            else if constexpr (SEGMIN > 0)
+              gi = knot_eval_fused<(SEG9 ? 9 : KN_SEG_MAX), SEGMIN>(kg, lds, Hb64, us, p2_kb, p2_km, p2_ke, ea, ekd, act, L.Hb32, wbase + L.cf,
+                                                                    Wseg, ww, lane, acc);
             else if (SEG9) knot_mfma<9>(kg, lds, L.Hb32, wbase + L.cf, Wseg, ww, lane, acc);
             else knot_mfma<KN_SEG_MAX>(kg, lds, L.Hb32, wbase + L.cf, Wseg, ww, lane, acc);
             nev += so_rows ? 3 : 2;
@@ -940,10 +1068,11 @@ int fit_knot_plan_init(d2d_fit_plan *pl) {
   if (!rc) rc = upload(&kn.d_Pu, kn.Pu);
   if (!rc) rc = upload(&kn.d_msc, kn.msc);
   if (rc) return rc;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fit_lm_knot_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, KN_LDS_BYTES);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fit_lm_knot_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, KN_LDS_BYTES);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fit_lm_knot_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, KN_LDS_BYTES);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fit_lm_knot_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, KN_LDS_BYTES);
+#define KN_ATTR(ST, S9, SM) \
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fit_lm_knot_kernel<ST, S9, SM>), hipFuncAttributeMaxDynamicSharedMemorySize, KN_LDS_BYTES)
+  KN_ATTR(false, false, 0); KN_ATTR(true, false, 0); KN_ATTR(false, true, 0); KN_ATTR(true, true, 0);
+  KN_ATTR(false, false, KN_SEG_FLOOR); KN_ATTR(true, false, KN_SEG_FLOOR); KN_ATTR(false, true, KN_SEG_FLOOR); KN_ATTR(true, true, KN_SEG_FLOOR);
+#undef KN_ATTR
   kn.wpb = wpb;
   return D2D_OK;
 }
@@ -969,13 +1098,30 @@ int fit_knot_ensure(d2d_fit_plan *pl, int cap_B) {
   return D2D_OK;
 }
 
+// the floor on a plan's shortest segment that its launches are compiled with (0: the generic instantiation)
+static int knot_seg_floor(int S, int smin) { return S == D2D_FIT_MAX_S && smin >= KN_SEG_FLOOR ? KN_SEG_FLOOR : 0; }
+
+int d2d_fit_knot_segments(int S, int K, double duration, int32_t *k0, int32_t *seg_min, int32_t *seg_max, int32_t *seg_floor) {
+  if (S < 1 || S > D2D_FIT_MAX_S || K < 2 || !(duration > 0.0)) { d2d_set_error("d2d_fit_knot_segments: S in 1 .. %d, K >= 2, duration > 0", D2D_FIT_MAX_S); return D2D_EINVAL; }
+  std::vector<int> seg;
+  std::vector<double> tau;
+  fit_basis_sample_segments(S, K, duration, seg, tau);
+  int first[D2D_FIT_MAX_S + 2] = {0}, smin = 0, smax = 0;
+  fit_knot_first_samples(seg, S, first);
+  fit_knot_seg_range(first, S, &smin, &smax);
+  if (k0) for (int s = 0; s <= S; ++s) k0[s] = first[s];
+  if (seg_min) *seg_min = smin;
+  if (seg_max) *seg_max = smax;
+  if (seg_floor) *seg_floor = knot_seg_floor(S, smin);
+  return D2D_OK;
+}
+
 int fit_knot_launch(d2d_ctx *ctx, d2d_fit_plan *pl, int B, double *q, const d2d_fit_opts &o, int iter_cap, const int32_t *order, int prio_at) {
   auto &kn = pl->kn;
   KnotGeom kg;
   kg.K = pl->K; kg.S = pl->S; kg.smax = 0;
   for (int s = 0; s <= D2D_FIT_MAX_S + 1; ++s) kg.k0[s] = kn.k0[s < D2D_FIT_MAX_S + 2 ? s : D2D_FIT_MAX_S + 1];
-  for (int j = 0; j < pl->S; ++j)
-    if (kn.k0[j + 1] - kn.k0[j] > kg.smax) kg.smax = kn.k0[j + 1] - kn.k0[j];
+  fit_knot_seg_range(kn.k0, pl->S, nullptr, &kg.smax);
   const KnotLds L = knot_lds_layout(pl->K, kn.wpb);
   KnotDev T{kn.d_Hb64, kn.d_Bq, kn.d_BiT, kn.d_Binv, kn.d_Minv, kn.d_Pu, kn.d_msc, kn.d_Hb32, kn.d_Wseg, kn.d_Md32, kn.d_Mrow32, kn.d_Mi32};
   static const bool want_stamps = getenv("D2D_LM_STAMPS") != nullptr || getenv("D2D_KNOT_DEBUG") != nullptr;     // (the dump lives in the stamped build)
@@ -985,12 +1131,24 @@ int fit_knot_launch(d2d_ctx *ctx, d2d_fit_plan *pl, int B, double *q, const d2d_
   int32_t *queue = ctx->counter_dev + 8;
   float *dbg = nullptr;                  // development: D2D_KNOT_DEBUG=<file> dumps the first evaluation (H_u rows, g_u, u) of every fit
   if (getenv("D2D_KNOT_DEBUG")) D2D_CHECK_HIP(hipMalloc(&dbg, (size_t)B * (KN_N * KN_N + 4 * KN_N) * sizeof(float)));
-#define KN_LAUNCH(ST, S9)                                                                                                                  \
-  hipLaunchKernelGGL((fit_lm_knot_kernel<ST, S9>), dim3(blocks), dim3(64 * kn.wpb), L.total, ctx->stream, B, kg, L, o, iter_cap, T, pl->d_pk, \
+#define KN_LAUNCH(ST, S9, SM)                                                                                                                  \
+  hipLaunchKernelGGL((fit_lm_knot_kernel<ST, S9, SM>), dim3(blocks), dim3(64 * kn.wpb), L.total, ctx->stream, B, kg, L, o, iter_cap, T, pl->d_pk, \
                      pl->d_prep, q, pl->d_cost, pl->d_g, pl->d_lm, pl->d_flags, queue, order, prio_at, kn.d_u, stamps, dbg)
-  const bool seg9 = kg.smax <= 9;
-  if (want_stamps) { if (seg9) KN_LAUNCH(true, true); else KN_LAUNCH(true, false); }
-  else { if (seg9) KN_LAUNCH(false, true); else KN_LAUNCH(false, false); }
+#define KN_LAUNCH_SEG(ST)                                                                     \
+  do {                                                                                        \
+    if (floor8) { if (seg9) KN_LAUNCH(ST, true, KN_SEG_FLOOR); else KN_LAUNCH(ST, false, KN_SEG_FLOOR); } \
+    else { if (seg9) KN_LAUNCH(ST, true, 0); else KN_LAUNCH(ST, false, 0); }                  \
+  } while (0)
+  // the instantiation with the floor serves every plan whose shortest segment reaches it (K >= 48 at S = 6: the bench's K = 50 has
+  // segments of 8 and 9); the generic one every other geometry, and any plan under D2D_FIT_ABLATE & 64 (diagnostics: the two
+  // must agree bit for bit, tests/test_gpu_knot_segmin.py)
+  const char *ablate = getenv("D2D_FIT_ABLATE");      // (read at every launch: the test runs both instantiations in one process)
+  const bool force_generic = ablate != nullptr && (atoi(ablate) & 64) != 0;
+  int smin = 0, smax = 0;
+  fit_knot_seg_range(kn.k0, pl->S, &smin, &smax);
+  const bool seg9 = smax <= 9, floor8 = knot_seg_floor(pl->S, smin) == KN_SEG_FLOOR && !force_generic;
+  if (want_stamps) KN_LAUNCH_SEG(true); else KN_LAUNCH_SEG(false);
+#undef KN_LAUNCH_SEG
 #undef KN_LAUNCH
   D2D_LAUNCH_CHECK();
   if (dbg) {

@@ -99,6 +99,9 @@ struct d2d_fit_plan {
 };
 
 int fit_basis_build(d2d_fit_plan *pl);   // fills the host vectors
+void fit_basis_sample_segments(int S, int K, double duration, std::vector<int> &seg, std::vector<double> &tau);   // segment and local time of every sample
+void fit_knot_first_samples(const std::vector<int> &seg, int S, int *k0);   // KnotTables::k0 from it
+void fit_knot_seg_range(const int *k0, int S, int *smin, int *smax);        // shortest / longest segment
 int fit_basis_segments(d2d_fit_plan *pl);   // ... of the segment formulation (after fit_basis_build)
 int fit_basis_knots(d2d_fit_plan *pl);      // ... of the knot-space statement (after fit_basis_segments)
 // fit_knot.hip: the persistent LM kernel in knot coordinates (S = 6, K <= 64, default solver)

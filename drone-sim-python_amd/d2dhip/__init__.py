@@ -200,6 +200,7 @@ _SIGS = {
     'd2d_fit_plan_destroy': (C.c_int, [_P]),
     'd2d_fit_plan_get': (C.c_int, [_P] * 6),
     'd2d_fit_plan_kernel': (C.c_int, [_P]),
+    'd2d_fit_knot_segments': (C.c_int, [C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),
     'd2d_fit_init': (C.c_int, [_P, _P, C.c_int, _P, _P]),
     'd2d_fit_project': (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     'd2d_fit_eval': (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),
@@ -246,6 +247,16 @@ def load():
 def _check(rc):
     if rc != 0:
         raise D2DError(f'libd2dhip error {rc}: {load().d2d_last_error().decode()}')
+
+
+def knot_segments(S, K, duration):
+    """(host, no GPU) sample geometry of a knot-coordinate plan: (k0 [S+1], seg_min, seg_max, seg_floor) -- d2d_fit_knot_segments."""
+    import numpy as np
+    k0 = np.zeros(S + 1, dtype=np.int32)
+    out = (C.c_int32 * 3)()
+    p = [C.cast(C.byref(out, 4 * i), C.c_void_p) for i in range(3)]
+    _check(load().d2d_fit_knot_segments(S, K, float(duration), _hptr(k0), *p))
+    return k0, int(out[0]), int(out[1]), int(out[2])
 
 
 def _torch():

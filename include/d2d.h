@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 118
+#define D2D_VERSION 119
 
 /* error codes */
 #define D2D_OK 0
@@ -528,6 +528,11 @@ int d2d_fit_plan_destroy(d2d_fit_plan *plan);
  * d2d_fit_plan_opts.kernel = D2D_FIT_KERNEL_FUSED at plan creation keeps the q kernel for the default solver too. */
 enum { D2D_FIT_KERNEL_SPLIT = 0, D2D_FIT_KERNEL_FUSED = 1, D2D_FIT_KERNEL_LONG = 2, D2D_FIT_KERNEL_KNOT = 3 };
 int d2d_fit_plan_kernel(const d2d_fit_plan *plan);
+/* The sample geometry of a knot-coordinate plan (version 119; a host function: no context, no GPU).  k0 [S+1]: the first sample of
+ * every segment, k0[S] = K; seg_min / seg_max: samples of its shortest / longest segment; seg_floor: the compile-time floor on the
+ * shortest segment that the plan's launches of fit_lm_knot_kernel are instantiated with (csrc/fit_knot.hip: the evaluation's
+ * J^T r and J^T J run as one straight-line pass then), 0 for the generic instantiation.  Any pointer may be NULL. */
+int d2d_fit_knot_segments(int S, int K, double duration, int32_t *k0, int32_t *seg_min, int32_t *seg_max, int32_t *seg_floor);
 
 /* Copy the basis to host buffers (any may be NULL): G [3][K][nq], Gp [3][K][4],
  * Z [8S][nq], Zp [8S][4], Pinit [nq][K]. */

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""(CPU) Static instruction census of fit_lm_knot_kernel<false, true> -- the headline's instantiation -- as hipcc compiles
+"""(CPU) Static instruction census of the headline's instantiation of fit_lm_knot_kernel -- <false, true, 8> (no stamps, SEG9, the
+floor of eight samples a segment; <false, true> before round 8) -- as hipcc compiles
 csrc/fit_knot.hip for gfx950 with the Makefile's flags: the whole kernel and the straight-line block that is one factorisation of
 damped_solve (the basic block that holds its 16 MFMAs and its reciprocal roots), by class; registers / scratch / occupancy of all four
-instantiations.  The per-item table of DESIGN 5.3c (round 7) is this tool's output, commit by commit.
+instantiations; and (round 8) the evaluation's k-steps: every cluster of twenty or more accumulating MFMAs outside the factorisation,
+with the instructions between its first and last v_mfma and the branches among them.  The per-item tables of DESIGN 5.3c (rounds 7
+and 8) are this tool's output, commit by commit.
 
     python tools/knot_count.py [file.s]        (an assembly file already made with --cuda-device-only -S is read instead of compiling)"""
 import os
@@ -45,8 +48,9 @@ def main():
                                   cwd=os.path.join(ROOT, 'drone-sim-python_amd', 'csrc'))
             asm = open(out).read()
     body, on = [], False
+    head = r'^_Z\w*fit_lm_knot_kernelILb0ELb1ELi8E\w*:' if 'fit_lm_knot_kernelILb0ELb1ELi8E' in asm else r'^_Z\w*fit_lm_knot_kernelILb0ELb1E\w*:'
     for ln in asm.splitlines():
-        if re.match(r'^_Z\w*fit_lm_knot_kernelILb0ELb1E\w*:', ln):
+        if re.match(head, ln):
             on = True
             continue
         if on and ln.startswith('.Lfunc_end'):
@@ -59,14 +63,37 @@ def main():
             blocks.append([])
         blocks[-1].append(ln)
     fact = max((b for b in blocks if any('v_mfma_f32_16x16x4' in x for x in b) and any('v_rsq_f32' in x for x in b)), key=len)
-    print('fit_lm_knot_kernel<false, true>')
+    print('fit_lm_knot_kernel<false, true, 8>' if 'Li8E' in head else 'fit_lm_knot_kernel<false, true>')
     print('  whole kernel  ', census(body))
     print('  factorisation ', census(fact))
+    # the evaluation's k-steps: accumulating MFMAs (a register block as C) outside the factorisation blocks, clustered by position
+    infact = {id(b) for b in blocks if any('v_rsq_f32' in x for x in b)}
+    pos, n = [], 0
+    for b in blocks:
+        for ln in b:
+            if 'v_mfma_f32_16x16x4' in ln and id(b) not in infact and not ln.rstrip().endswith(', 0'):
+                pos.append(n)
+            n += 1
+    flat = [ln for b in blocks for ln in b]
+    clusters = [[]]
+    for q in pos:
+        if clusters[-1] and q - clusters[-1][-1] > 150:
+            clusters.append([])
+        clusters[-1].append(q)
+    for cl in clusters:
+        if len(cl) >= 20:
+            span = flat[cl[0]:cl[-1] + 1]
+            c = census(span)
+            br = sum(1 for x in span if x.strip().startswith(('s_cbranch', 's_branch')))
+            print(f'  evaluation     {len(cl)} v_mfma: {c["all"]} instructions from the first to the last, {br} branches, '
+                  f'{sum(1 for x in span if x.startswith(".LBB"))} labels; valu {c["valu"]} lds {c["lds"]} salu {c["salu"]} s_nop {c["s_nop"]}')
     res = re.findall(r'^; (NumVgprs|ScratchSize|Occupancy): (\d+)', asm, re.M)
-    names = re.findall(r'^\s+\.name:\s+\S*fit_lm_knot_kernelILb(\d)ELb(\d)E', asm, re.M)
-    for i, (st, s9) in enumerate(names):
+    names = re.findall(r'^\s+\.name:\s+\S*fit_lm_knot_kernelILb(\d)ELb(\d)E(?:Li(\d+)E)?', asm, re.M)
+    sizes = re.findall(r'^; codeLenInByte = (\d+)', asm, re.M)
+    for i, (st, s9, sm) in enumerate(names):
         r = dict(res[3 * i:3 * i + 3])
-        print(f'  <STAMPS={st}, SEG9={s9}>: {r.get("NumVgprs")} VGPRs, scratch {r.get("ScratchSize")}, occupancy {r.get("Occupancy")}')
+        print(f'  <STAMPS={st}, SEG9={s9}' + (f', SEGMIN={sm}' if sm else '') + f'>: {r.get("NumVgprs")} VGPRs, scratch {r.get("ScratchSize")}, '
+              f'occupancy {r.get("Occupancy")}' + (f', {sizes[i]} bytes' if len(sizes) == len(names) else ''))
 
 
 if __name__ == '__main__':
