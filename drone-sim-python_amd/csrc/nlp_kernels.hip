@@ -198,6 +198,17 @@ enum {
   SIN_D = 0, SIN_E = 6, SIN_T = 15, SIN_N = 18,
   SF_L = 0, SF_LO = 6, SF_Y = 15, SF_N = 18
 };
+// FREE instantiations (d2d_nlp_solve_free) keep the planes above and add, behind them, what the border column b of the Newton system
+// needs: b itself, its (phi, v) part after the local elimination, the solution y = A^-1 b, and a second set of reduced-node records
+// and reduced steps for the second pass of the cyclic reduction (which overwrites its records).
+enum {
+  WSF_B = WS_TOTAL,                      // border column b (5 planes)
+  WSF_TB = WSF_B + 5,                    // LP^-1 b_pv (2 planes): the twin of EL_T
+  WSF_Y = WSF_TB + 2,                    // y = A^-1 b (5 planes)
+  WSF_SIN2 = WSF_Y + 5,                  // reduced node [N][18] with b's reduced right-hand side in the place of t'
+  WSF_DS2 = WSF_SIN2 + SIN_N,            // reduced y [N][3]
+  WSF_TOTAL = WSF_DS2 + 3
+};
 
 struct NlpProb {
   int N;
@@ -221,7 +232,18 @@ struct NlpMovProb : NlpProb {
 struct NlpViaProb : NlpMovProb {
   const int32_t *vm;
 };
-template <bool MOV, bool VIA = false> using NlpProbT = std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>;
+// FREE instantiations (d2d_nlp_solve_free): the problem with its free time step.  The solver's unknown is u = 1 / h, in which every
+// equality is linear; h above is kept equal to 1 / u.  Wave-uniform values: u in (ulo, uhi) = (1 / h_hi, 1 / h_lo), its two bound
+// duals, and kd = k_dur (N - 1), the weight of the duration term kd / u of the objective.
+struct NlpFreeProb : NlpProb {
+  double u, ulo, uhi, zul, zuu, kd;
+};
+// what nlp_assemble hands back for the row of u: rho sum (c + mu) . dc/du and rho sum |dc/du|^2 over the equalities
+struct NlpFreeRow {
+  double gu, dd;
+};
+template <bool MOV, bool VIA = false, bool FREE = false>
+using NlpProbT = std::conditional_t<FREE, NlpFreeProb, std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>>;
 template <bool VIA> using NlpProbV = std::conditional_t<VIA, NlpViaProb, NlpProb>;       // for the passes that read no disc
 template <bool MOV> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const NlpProbT<MOV> &pb) {
   if constexpr (MOV) return &pb.mv;
@@ -303,10 +325,13 @@ __device__ __forceinline__ int nlp_via_mask(const PB &pb, int i) {
 
 // Merit function of the inner problem at W + a*dw: objective + rho sum (c + mu)^2 - mub sum log(slacks); +inf outside the box.
 // Node-parallel (lane = node, chunks of 64) + wave reductions.  All results are wave-uniform.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false>
-__device__ double nlp_merit(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
-                            double mub, double *cost_ref_out, double *feas_out, const NlpModel &md) {
+// FREE: ut is the trial value of u = 1 / h (u + a du): the equalities are read at 1 / ut, and the duration term kd / ut, the barrier of
+// u's box and the value +inf outside it join the sums (cost_ref_out: the reference's cost() + k_dur (N - 1) h).
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false>
+__device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
+                            double mub, double *cost_ref_out, double *feas_out, const NlpModel &md, [[maybe_unused]] double ut = 0.0) {
   const int N = pb.N;
+  [[maybe_unused]] const double ht = FREE ? 1.0 / ut : 0.0;
   double val = 0.0, bar = 0.0, cref = 0.0, feas = 0.0, phi2max = 0.0;
   int outside = 0;
   for (int i0 = 0; i0 < N; i0 += 64) {
@@ -356,6 +381,8 @@ __device__ double nlp_merit(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, cons
       val += obj;
       if (i >= 1) {
         double c3[3];
+        if constexpr (FREE) nlp_constraint(s, ht, wp, w, c3);
+        else
         nlp_constraint<WIND>(s, pb.h, wp, w, c3, pb.wf, NLP_T(i));
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -371,6 +398,12 @@ __device__ double nlp_merit(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, cons
   if (s.sbank > 0.0) {                       // CostBank max mode (src/d2d/opty_utils.py:68-82): obj_scale * kbank * max_i phi_i^2
     const double bk = s.sbank * wave_max(phi2max);
     val += bk; cref += bk;
+  }
+  if constexpr (FREE) {
+    const double dur = pb.kd / ut, sl = ut - pb.ulo, su = pb.uhi - ut;
+    val += dur; cref += dur;
+    if (!(sl > 0.0) || !(su > 0.0)) outside = 1;
+    else bar += log(sl * su);
   }
   if (cost_ref_out) *cost_ref_out = cref;
   if (feas_out) *feas_out = wave_max(feas);
@@ -415,25 +448,35 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // block; node i+1's constraint sees node i through -1/h only, so the has_next terms and the structure of E do not change.
 // VIA: the rows and columns of a pinned component are the identity with right-hand side 0, as at the ends, and the columns of E_i that
 // belong to pinned components of node i-1 are zero (at the ends: all of E_1) -- before the elimination, so Rt carries none of them.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false>
-__device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
-                               double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md) {
+// FREE: the border column b of the Newton system, bordered by the row of u = 1 / h (c = (s_i - s_{i-1}) u - f(s_i): dc/du = the node
+// difference dl, cross curvature +1 on the node's own (x, y, psi) and -1 on its predecessor's):
+//   b_i = rho Ac^T dl_i + rho (c + mu)_i  on node i  [own equality]   - rho u dl_{i+1} - rho (c + mu)_{i+1}  on (x, y, psi)_i  [next one]
+// b goes through the same elimination of (phi, v) as the right-hand side (ttb, its hand-over, its reduced part, which lands in the
+// t' slots of a second set of records for the second pass of the cyclic reduction); fr_out: the sums of the row of u.  rec_lds is
+// false for this instantiation: both passes load their records from the workspace.
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false>
+__device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
+                               double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md, [[maybe_unused]] NlpFreeRow *fr_out = nullptr) {
   const int N = pb.N;
   const double h = pb.h, ih = 1.0 / h;
   double err = 0.0;
   int bad = 0;
+  constexpr int UPN = FREE ? 12 : 9;          // doubles a node hands to the node before it (FREE: + Rt^T ttb)
+  [[maybe_unused]] double gu = 0.0, dd = 0.0;
   // The chunks of 64 nodes are visited from the LAST to the first: node i needs what node i+1 hands to it (the hand-over of the
   // elimination, below), and for the last lane of a chunk that is the first node of the chunk visited before.
-  double *lds_up = pb.lds + NLP_LDS_UP, *lds_rec = pb.lds + NLP_LDS_REC;
+  double *lds_up = pb.lds + NLP_LDS_UP, *lds_rec = pb.lds + (FREE ? 65 * UPN : NLP_LDS_REC);
   [[maybe_unused]] double wnx_first = 0.0, wny_first = 0.0;      // WIND: the field at the first node of the chunk visited before (lane 63's next node)
   for (int i0 = ((N - 1) / 64) * 64; i0 >= 0; i0 -= 64) {
     const int i = i0 + lane;
     const bool live = i < N;
-    double sinv[SIN_N], upv[9];
+    double sinv[SIN_N], upv[UPN];
+    [[maybe_unused]] double tbv[3] = {0.0, 0.0, 0.0};      // FREE: b's reduced right-hand side
     [[maybe_unused]] WindJet wj;                     // WIND: the field at this lane's node
     if (live) {
     const bool has_next = i + 1 < N;
     double rhsv[NLP_NV];
+    [[maybe_unused]] double bv[NLP_NV] = {0, 0, 0, 0, 0};
     double wp[3] = {0, 0, 0}, wc[NLP_NV], wn[NLP_NV] = {0, 0, 0, 0, 1};
     double cc[3] = {0, 0, 0}, cn[3] = {0, 0, 0};     // (c + mu) of the constraint that ends at this node / at the next one
     // (all loads of the node up front, neighbours from clamped indices: see nlp_merit)
@@ -535,6 +578,13 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
 #pragma unroll
         for (int k = 0; k < 3; ++k) E[a][k] = -rho * Ac[k][a] * ih;
       }
+      if constexpr (FREE) {
+        const double dl[3] = {wc[0] - wp[0], wc[1] - wp[1], wc[2] - wp[2]};
+#pragma unroll
+        for (int a = 0; a < NLP_NV; ++a) bv[a] += rho * (Ac[0][a] * dl[0] + Ac[1][a] * dl[1] + Ac[2][a] * dl[2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { bv[k] += rho * cc[k]; gu += cc[k] * dl[k]; dd += dl[k] * dl[k]; }
+      }
       // + rho (c + mu) Hessian(c): the constraint curvature of the Lagrangian
       const double m0 = rho * cc[0], m1 = rho * cc[1], m2 = rho * cc[2];
       D[2][2] += m0 * vi * cp + m1 * vi * sp;
@@ -554,6 +604,10 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
     if (has_next) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) { D[k][k] += rho * ih * ih; g[k] += -rho * cn[k] * ih; }
+      if constexpr (FREE) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) bv[k] += -rho * ih * (wn[k] - wc[k]) - rho * cn[k];
+      }
     }
     // barrier terms, stationarity / complementarity error, right-hand side
 #pragma unroll
@@ -573,6 +627,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
       if (!fx) err = fmax(err, fabs(st));
       rhsv[c] = fx ? 0.0 : r;
       NLP_RHS(c, i) = rhsv[c];
+      if constexpr (FREE) { if (fx) bv[c] = 0.0; NLP_P(WSF_B + c, i) = bv[c]; }
       D[c][c] += 0.5 * sig;
       if (!fx) D[c][c] += lam * fmax(fabs(D[c][c]), 1e-12);
       if (fx) {
@@ -618,6 +673,12 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
       for (int k = 0; k < 3; ++k) { NLP_EL(EL_Q + j * 3 + k, i) = Qt[j][k]; NLP_EL(EL_R + j * 3 + k, i) = Rt[j][k]; }
       NLP_EL(EL_T + j, i) = tt[j];
     }
+    [[maybe_unused]] double ttb[2] = {0.0, 0.0};
+    if constexpr (FREE) {                       // the border through the same elimination: ttb = LP^-1 b_pv
+      ttb[0] = bv[3] * i00;
+      ttb[1] = (bv[4] - l10 * ttb[0]) * i11;
+      NLP_P(WSF_TB + 0, i) = ttb[0]; NLP_P(WSF_TB + 1, i) = ttb[1];
+    }
     // what node i-1 gets from this node's elimination, and this node's own part of the reduced node
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -630,6 +691,10 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
 #pragma unroll
       for (int k = 0; k < 3; ++k) sinv[SIN_E + a * 3 + k] = E[a][k] - (Qt[0][a] * Rt[0][k] + Qt[1][a] * Rt[1][k]);
       sinv[SIN_T + a] = 0.5 * rhsv[a] - (Qt[0][a] * tt[0] + Qt[1][a] * tt[1]);
+      if constexpr (FREE) {
+        upv[9 + a] = Rt[0][a] * ttb[0] + Rt[1][a] * ttb[1];
+        tbv[a] = bv[a] - (Qt[0][a] * ttb[0] + Qt[1][a] * ttb[1]);
+      }
     }
     }
 #if NLP_WIND_NEXT_SHUFFLE
@@ -642,15 +707,25 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
     // full 512-byte rows: 8-byte stores at a stride of 144 bytes reached the memory as partial sectors (WRITE_SIZE 1.6 x algorithmic)
     if (live) {
 #pragma unroll
-      for (int k = 0; k < 9; ++k) lds_up[lane * 9 + k] = upv[k];
+      for (int k = 0; k < UPN; ++k) lds_up[lane * UPN + k] = upv[k];
     }
     nlp_phase_sync();
     if (live && i + 1 < N) {
-      const double *nb = lds_up + (lane + 1) * 9;           // lane 63: row 64 = node i0 + 64, left there by the chunk visited before
+      const double *nb = lds_up + (lane + 1) * UPN;         // lane 63: row 64 = node i0 + 64, left there by the chunk visited before
 #pragma unroll
       for (int k = 0; k < 6; ++k) sinv[SIN_D + k] -= nb[UP_RR + k];
 #pragma unroll
       for (int a = 0; a < 3; ++a) sinv[SIN_T + a] -= nb[UP_RT + a];
+      if constexpr (FREE) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) tbv[a] -= nb[9 + a];
+      }
+    }
+    if constexpr (FREE) {
+      if (live) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) pb.ws[(size_t)WSF_SIN2 * N + (size_t)i * SIN_N + SIN_T + a] = tbv[a];
+      }
     }
     if (rec_lds) {
       // The cyclic reduction that follows works in this wave's LDS block on records [node][NLP_BCR_STRIDE] (N <= NLP_BCR_LDS_NODES):
@@ -660,7 +735,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
       nlp_phase_sync();
       if (lane == 0 && i0 > 0) {                            // this chunk's first node for the chunk below
 #pragma unroll
-        for (int k = 0; k < 9; ++k) lds_up[64 * 9 + k] = upv[k];
+        for (int k = 0; k < UPN; ++k) lds_up[64 * UPN + k] = upv[k];
       }
       if (live) {
 #pragma unroll
@@ -676,8 +751,18 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
     nlp_phase_sync();
     if (lane == 0) {                                        // this chunk's first node for the chunk below
 #pragma unroll
-      for (int k = 0; k < 9; ++k) lds_up[64 * 9 + k] = upv[k];
+      for (int k = 0; k < UPN; ++k) lds_up[64 * UPN + k] = upv[k];
     }
+    if constexpr (FREE) {                                   // D' and E' also into the second set of records (its t' slots: above)
+      const int cnt = (N - i0 < 64 ? N - i0 : 64) * SIN_N;
+      double *dst = pb.ws + (size_t)WS_SIN * N + (size_t)i0 * SIN_N, *dst2 = pb.ws + (size_t)WSF_SIN2 * N + (size_t)i0 * SIN_N;
+      for (int e = lane; e < cnt; e += 64) {
+        const int node = e / SIN_N, k = e - node * SIN_N;
+        const double v = lds_rec[node * NLP_REC_STRIDE + k];
+        dst[e] = v;
+        if (k < SIN_T) dst2[e] = v;
+      }
+    } else
     {
       const int cnt = (N - i0 < 64 ? N - i0 : 64) * SIN_N;
       double *dst = pb.ws + (size_t)WS_SIN * N + (size_t)i0 * SIN_N;
@@ -689,6 +774,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA> &pb, const NlpScen &s, c
     nlp_phase_sync();
   }
   *pd_out = __builtin_amdgcn_ballot_w64(bad != 0) == 0ull;
+  if constexpr (FREE) { fr_out->gu = rho * wave_sum(gu); fr_out->dd = rho * wave_sum(dd); }
   return wave_max(err);
 }
 
@@ -1204,6 +1290,97 @@ __device__ void nlp_recover_stats(const NlpProbV<VIA> &pb, const NlpScen &s, int
   *dphi_out = wave_sum(dphi); *amax_out = wave_min(amax); *az_out = wave_min(az);
 }
 
+// FREE: nlp_recover_stats for the bordered system  [A b; b^T d] (dW, du) = (r, r_u) / 2  by the Schur complement on d.  The two
+// passes of the cyclic reduction left the reduced parts of x0 = A^-1 r / 2 (WS_DS) and y = A^-1 b (WSF_DS2); the first pass here
+// recovers (phi, v) of both, node-parallel, keeps x0 in the step's planes and y in its own, and sums b.x0 and b.y; then
+//   du = (r_u / 2 - b.x0) / (d - b.y),   dW = x0 - y du
+// and the second pass is nlp_recover_stats' own: directional derivative and the two ratio tests, with u and its duals included.
+// false: d - b.y is not positive -- the bordered matrix is not positive definite (the caller raises the damping).
+__device__ bool nlp_recover_free(const NlpFreeProb &pb, const NlpScen &s, int lane, double mub, double tau, double ru, double d,
+                                 double *dphi_out, double *amax_out, double *az_out, double *du_out) {
+  const int N = pb.N;
+  double bx = 0.0, by = 0.0;
+  for (int i0 = 0; i0 < N; i0 += 64) {
+    const int i = i0 + lane;
+    if (i >= N) continue;
+    const int im = i >= 1 ? i - 1 : 0;
+    double xv[NLP_NV], yv[NLP_NV], xp[3], yp[3], bvv[NLP_NV], elq[6], elr[6], ellp[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      xv[c] = NLP_DS(c, i); xp[c] = NLP_DS(c, im);
+      yv[c] = pb.ws[(size_t)WSF_DS2 * N + i * 3 + c]; yp[c] = pb.ws[(size_t)WSF_DS2 * N + im * 3 + c];
+    }
+    if (i < 1) { xp[0] = 0.0; xp[1] = 0.0; xp[2] = 0.0; yp[0] = 0.0; yp[1] = 0.0; yp[2] = 0.0; }
+    double z0 = NLP_EL(EL_T + 0, i), z1 = NLP_EL(EL_T + 1, i), q0 = NLP_P(WSF_TB + 0, i), q1 = NLP_P(WSF_TB + 1, i);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { elq[k] = NLP_EL(EL_Q + k, i); elr[k] = NLP_EL(EL_R + k, i); }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ellp[k] = NLP_EL(EL_LP + k, i);
+#pragma unroll
+    for (int c = 0; c < NLP_NV; ++c) bvv[c] = NLP_P(WSF_B + c, i);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      z0 -= elq[k] * xv[k] + elr[k] * xp[k];
+      z1 -= elq[3 + k] * xv[k] + elr[3 + k] * xp[k];
+      q0 -= elq[k] * yv[k] + elr[k] * yp[k];
+      q1 -= elq[3 + k] * yv[k] + elr[3 + k] * yp[k];
+    }
+    xv[4] = z1 * ellp[2]; xv[3] = (z0 - ellp[1] * xv[4]) * ellp[0];
+    yv[4] = q1 * ellp[2]; yv[3] = (q0 - ellp[1] * yv[4]) * ellp[0];
+#pragma unroll
+    for (int c = 0; c < NLP_NV; ++c) {
+      NLP_DW(c, i) = xv[c]; NLP_P(WSF_Y + c, i) = yv[c];
+      bx += bvv[c] * xv[c]; by += bvv[c] * yv[c];
+    }
+  }
+  bx = wave_sum(bx); by = wave_sum(by);
+  const double sch = d - by;
+  if (!(sch > 0.0)) return false;
+  const double du = (0.5 * ru - bx) / sch;
+  double dphi = 0.0, amax = 1.0, az = 1.0;
+  for (int i0 = 0; i0 < N; i0 += 64) {
+    const int i = i0 + lane;
+    if (i >= N) continue;
+    double xv[NLP_NV], yv[NLP_NV], wv[NLP_NV], rhv[NLP_NV], zlv[NLP_NV], zuv[NLP_NV];
+#pragma unroll
+    for (int c = 0; c < NLP_NV; ++c) {
+      xv[c] = NLP_DW(c, i); yv[c] = NLP_P(WSF_Y + c, i);        // (this lane's own stores of the pass above)
+      wv[c] = NLP_W(c, i); rhv[c] = NLP_RHS(c, i); zlv[c] = NLP_P(WS_ZL + c, i); zuv[c] = NLP_P(WS_ZU + c, i);
+    }
+#pragma unroll
+    for (int c = 0; c < NLP_NV; ++c) {
+      const double dw = xv[c] - yv[c] * du;
+      NLP_DW(c, i) = dw;
+      dphi -= rhv[c] * dw;
+      if (nlp_fixed(i, N, c)) continue;
+      const double w = wv[c];
+      if (s.lo[c] > -1e299) {
+        const double sl = w - s.lo[c], z = zlv[c];
+        if (-dw * amax > tau * sl) amax = -tau * sl / dw;
+        const double dz = (mub - z * dw) / sl - z;
+        if (-dz * az > tau * z) az = -tau * z / dz;
+      }
+      if (s.hi[c] < 1e299) {
+        const double su = s.hi[c] - w, z = zuv[c];
+        if (dw * amax > tau * su) amax = tau * su / dw;
+        const double dz = (mub + z * dw) / su - z;
+        if (-dz * az > tau * z) az = -tau * z / dz;
+      }
+    }
+  }
+  dphi = wave_sum(dphi) - ru * du; amax = wave_min(amax); az = wave_min(az);
+  {
+    const double sl = pb.u - pb.ulo, su = pb.uhi - pb.u;
+    if (-du * amax > tau * sl) amax = -tau * sl / du;
+    if (du * amax > tau * su) amax = tau * su / du;
+    const double dzl = (mub - pb.zul * du) / sl - pb.zul, dzu = (mub + pb.zuu * du) / su - pb.zuu;
+    if (-dzl * az > tau * pb.zul) az = -tau * pb.zul / dzl;
+    if (-dzu * az > tau * pb.zuu) az = -tau * pb.zuu / dzu;
+  }
+  *dphi_out = dphi; *amax_out = amax; *az_out = az; *du_out = du;
+  return true;
+}
+
 // Take the step (node-parallel): W += a dw, duals += az dz (dz from the step's dw), duals kept near the central path.
 template <bool VIA = false>
 __device__ void nlp_apply(const NlpProbV<VIA> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
@@ -1285,6 +1462,8 @@ struct NlpExtra {
   unsigned pmask;            // PAIRS
   const NlpMovSet *mv;       // MOV
   const NlpViaSet *via;      // VIA
+  const double *free_row;    // FREE: (h_lo, h_hi, k_dur, h_start; 0 = the launch's h) of the problem, and where its solved h goes
+  double *h_out;
 };
 
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
@@ -1296,7 +1475,11 @@ struct NlpExtra {
 // VIA: via the problem's pins, checked by the caller (nlp_via_bad): a pinned component starts at its value and stays there -- no duals,
 // no barrier, no step, an identity row in the Newton system -- exactly as x, y, psi of the two end nodes do.  The terms of the objective
 // still count at a pinned node.
-template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false>
+// FREE (d2d_nlp_solve_free): h is the problem's own unknown in the box of ex.free_row, started from the row's value or from the
+// launch's h; the Newton system is bordered by the row of u = 1 / h (nlp_assemble, nlp_recover_free), every pass reads the
+// equalities at the current u, the line search at the trial one, and cost carries the duration term.  An unusable row of the box
+// refuses the problem like an unusable scenario row; *ex.h_out gets the solved h (NaN for a refused problem).
+template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
                                               const double *__restrict__ bnd, const NlpExtra &ex = NlpExtra{}) {
@@ -1309,7 +1492,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   if (st_on) st_t = __builtin_amdgcn_s_memtime();
   NlpScen s = nlp_load_scen(sc, o, bnd);
   if (sc[D2D_SC_BANKMAX] != 0.0) { s.sbank = s.skphi * (double)N; s.skphi = 0.0; }     // obj_scale * kbank (the row's S is obj_scale / N)
-  NlpProbT<MOV, VIA> pb;
+  NlpProbT<MOV, VIA, FREE> pb;
   if constexpr (MOV) pb.mv = *ex.mv;
   if constexpr (VIA) pb.vm = via->vm;
   pb.N = N; pb.h = h;
@@ -1334,6 +1517,11 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         for (int k = 0; k < 15; ++k) nf |= !(fabs(md.H[k * N + i]) <= 1.79e308);
       }
       bad = bad || __builtin_amdgcn_ballot_w64(nf != 0) != 0ull;
+    }
+    if constexpr (FREE) {             // the box of h: 0 < h_lo < h_hi, k_dur >= 0, a start that is 0 (the launch's h) or finite
+      const double hl = ex.free_row[0], hh = ex.free_row[1], kd = ex.free_row[2], hs = ex.free_row[3];
+      bad = bad || !(hl > 0.0) || !(hl < hh) || !(hh <= 1.79e308) || !(kd >= 0.0) || !(kd <= 1.79e308) || !(fabs(hs) <= 1.79e308);
+      if (lane == 0) *ex.h_out = __builtin_nan("");
     }
     if (bad) {
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
@@ -1385,8 +1573,18 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
 #pragma unroll
     for (int k = 0; k < 3; ++k) NLP_MU(k, i) = 0.0;
   }
+  [[maybe_unused]] double du = 0.0;
+  if constexpr (FREE) {                      // u = 1 / h pushed strictly inside its box like a node variable, its duals on the central path
+    const double hs = ex.free_row[3] != 0.0 ? ex.free_row[3] : h;
+    pb.ulo = 1.0 / ex.free_row[1]; pb.uhi = 1.0 / ex.free_row[0]; pb.kd = ex.free_row[2] * (double)(N - 1);
+    double u = 1.0 / hs;
+    const double kap = fmin(1e-2 * fmax(1.0, fabs(u)), 1e-2 * (pb.uhi - pb.ulo));
+    u = fmin(fmax(u, pb.ulo + kap), pb.uhi - kap);
+    pb.u = u; pb.h = 1.0 / u;
+    pb.zul = mub / (u - pb.ulo); pb.zuu = mub / (pb.uhi - u);
+  }
   nlp_phase_sync();
-  const bool rec_lds = !o.serial && N <= NLP_BCR_LDS_NODES;       // the reduced records go from the assembly to the cyclic reduction through the LDS
+  const bool rec_lds = !FREE && !o.serial && N <= NLP_BCR_LDS_NODES;       // the reduced records go from the assembly to the cyclic reduction through the LDS
   double rho = o.rho0, lam = D2D_LM_LAMBDA0, feas_prev = INFINITY;
   int total_inner = 0, status = D2D_ST_MAXITER;
   double err = 0.0, cost_ref = 0.0, feas = 0.0;
@@ -1399,7 +1597,10 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     const double tol_in = fmax(fmax(o.opt_tol, fmin(1e-1, 10.0 * mub)), D2D_NLP_GRAD_FLOOR * rho);
     // merit value of the current point for this (mub, rho, mu): one pass here, afterwards the accepted trial's value
     NLP_STAMP(7)
-    double phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    double phi0;
+    if constexpr (FREE) phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md, pb.u);
+    else
+    phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1410,10 +1611,29 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       const int imax = s.sbank > 0.0 ? nlp_bank_argmax(pb, lane) : -1;
       for (int tr = 0; tr < 30; ++tr) {
         bool pd;
+        [[maybe_unused]] double ru = 0.0, dfull = 0.0;
+        if constexpr (FREE) {
+          NlpFreeRow fr;
+          err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, rho, mub, lam, &pd, imax, false, md, &fr);
+          // the row of u: half gradient, KKT error, right-hand side, damped half curvature
+          const double u = pb.u, sl = u - pb.ulo, su = pb.uhi - u;
+          const double g_u = -0.5 * pb.kd / (u * u) + fr.gu;
+          err = fmax(fmax(err, fabs(2.0 * g_u - pb.zul + pb.zuu)), fmax(fabs(pb.zul * sl - mub), fabs(pb.zuu * su - mub)));
+          ru = -(2.0 * g_u - mub / sl + mub / su);
+          const double d0 = pb.kd / (u * u * u) + fr.dd + 0.5 * (pb.zul / sl + pb.zuu / su);
+          dfull = d0 + lam * fmax(fabs(d0), 1e-12);
+        } else
         err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
+        if constexpr (FREE) {                // two passes of the cyclic reduction: right-hand side, then border (each loads its own records)
+          if (pd) pd = nlp_bcr(pb.ws + (size_t)WS_SIN * N, pb.ws + (size_t)WS_SF * N, pb.ws + (size_t)WS_DS * N, pb.lds, N, false);
+          if (pd) {
+            nlp_phase_sync();
+            pd = nlp_bcr(pb.ws + (size_t)WSF_SIN2 * N, pb.ws + (size_t)WS_SF * N, pb.ws + (size_t)WSF_DS2 * N, pb.lds, N, false);
+          }
+        } else
         if (pd) {
           if (o.serial) pd = nlp_factor(pb.ws + (size_t)WS_SIN * N, pb.ws + (size_t)WS_SF * N, pb.ws + (size_t)WS_UP * N, N);   // (UP is free by now)
           else pd = nlp_bcr(pb.ws + (size_t)WS_SIN * N, pb.ws + (size_t)WS_SF * N, pb.ws + (size_t)WS_DS * N, pb.lds, N, rec_lds);
@@ -1428,13 +1648,22 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         NLP_STAMP(3)
         const double tau = fmax(0.99, 1.0 - mub);
         double dphi, amax, az;
+        if constexpr (FREE) {
+          const bool spd = nlp_recover_free(pb, s, lane, mub, tau, ru, dfull, &dphi, &amax, &az, &du);
+          nlp_phase_sync();
+          NLP_STAMP(4)
+          if (!spd) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
+        } else {
         nlp_recover_stats<VIA>(pb, s, lane, mub, tau, &dphi, &amax, &az);
         nlp_phase_sync();
         NLP_STAMP(4)
+        }
         if (!(dphi < 0.0)) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
         double a = amax, pt = 0.0;
         bool ok = false;
         for (int ls = 0; ls < 8; ++ls) {
+          if constexpr (FREE) pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md, pb.u + a * du);
+          else
           pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
@@ -1443,6 +1672,13 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         if (ok) {
           phi0 = pt;
           nlp_apply<VIA>(pb, s, lane, a, az, mub);
+          if constexpr (FREE) {              // u and its duals move like a node variable (nlp_apply)
+            const double u = pb.u, un = u + a * du, sl = u - pb.ulo, su = pb.uhi - u;
+            const double ml = mub / (un - pb.ulo), mh = mub / (pb.uhi - un);
+            pb.zul = fmin(fmax(pb.zul + az * ((mub - pb.zul * du) / sl - pb.zul), 1e-10 * ml), 1e10 * ml);
+            pb.zuu = fmin(fmax(pb.zuu + az * ((mub + pb.zuu * du) / su - pb.zuu), 1e-10 * mh), 1e10 * mh);
+            pb.u = un; pb.h = 1.0 / un;
+          }
           nlp_phase_sync();
           NLP_STAMP(5)
           if (a == amax) lam = fmax(lam / 3.0, D2D_LM_LAMBDA_MIN);
@@ -1453,6 +1689,8 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       }
       if (converged || !accepted) break;
     }
+    if constexpr (FREE) (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
+    else
     (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
@@ -1480,6 +1718,8 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       for (int c = 0; c < 3; ++c) wp[c] = NLP_W(c, i - 1);
 #pragma unroll
       for (int c = 0; c < NLP_NV; ++c) w[c] = NLP_W(c, i);
+      if constexpr (FREE) nlp_constraint(s, pb.h, wp, w, c3);
+      else
       nlp_constraint<WIND>(s, h, wp, w, c3, pb.wf, NLP_T(i));
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -1492,6 +1732,10 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     feas_prev = feas;
     mub = fmax(o.mub_min, fmin(0.2 * mub, mub * sqrt(mub)));
   }
+  if constexpr (FREE) {
+    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
+    if (lane == 0) *ex.h_out = pb.h;
+  } else
   (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
@@ -1620,15 +1864,19 @@ __device__ __forceinline__ void nlp_report(int b, int lane, const NlpOut &out, d
 // VIA: the problem's pins via->pts [B][n_via][5] and the plane of its nodes' fixed sets vwork [B][N]; unusable pins refuse the problem
 //   like an unusable track.  mv->n_mov = 0: nothing moves.
 // A refused problem's W is not touched.  The pointer parameters carry no __restrict__ (the kernels' do), as in nlp_groups_body.
-template <bool WIND, bool MOV, bool VIA, bool T_AT>
+// FREE (nlp_solve_free_kernel): the problems' boxes of the time step free_rows [B][4] and their solved steps h_out [B]; the slot's
+// workspace has the planes of the border behind the others (WSF_TOTAL).
+template <bool WIND, bool MOV, bool VIA, bool T_AT, bool FREE = false>
 __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d2d_nlp_opts &o, const double *scen, double *W, double *work,
                                                  double *mult, double *cost_out, double *feas_out, int32_t *iters_out, int32_t *status_out,
                                                  int32_t *queue, const d2d_wind_field *wf, double t_start, const double *t_at = nullptr,
                                                  const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr,
-                                                 const d2d_via_points *via = nullptr, int32_t *vwork = nullptr) {
+                                                 const d2d_via_points *via = nullptr, int32_t *vwork = nullptr,
+                                                 const double *free_rows = nullptr, double *h_out = nullptr,
+                                                 [[maybe_unused]] unsigned long long *stamps = nullptr) {
   const int lane = threadIdx.x;
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
-  double *wsb = work + (size_t)blockIdx.x * WS_TOTAL * N;
+  double *wsb = work + (size_t)blockIdx.x * (FREE ? WSF_TOTAL : WS_TOTAL) * N;
   const int32_t *__restrict__ order = o.order;
   for (int t = blockIdx.x; t < B;) {
     const int b = order ? __builtin_amdgcn_readfirstlane(order[t]) : t;
@@ -1659,6 +1907,10 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
     }
     if (bad) {
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
+    } else if constexpr (FREE) {
+      nlp_solve_one<false, false, false, false, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
+                                                             lane, out, b == 0 ? stamps : nullptr, nlp_lds, bnd,
+                                                             NlpExtra{{nullptr, nullptr, nullptr}, nullptr, 0.0, 0u, nullptr, nullptr, free_rows + (size_t)b * 4, h_out + b});
     } else {
       nlp_solve_one<false, WIND, false, MOV, VIA>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
                                                   lane, out, nullptr, nlp_lds, bnd, NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, &ms, &vs});
@@ -1675,6 +1927,16 @@ nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__re
                       double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
                       int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, double t_start) {
   nlp_handout_body<true, false, false, false>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, t_start);
+}
+
+// d2d_nlp_solve_free: every problem with its own free time step (constant wind, static discs, no partner)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_free_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                      double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                      int32_t *__restrict__ status_out, int32_t *queue, const double *__restrict__ free_rows, double *__restrict__ h_out,
+                      unsigned long long *stamps) {
+  nlp_handout_body<false, false, false, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, nullptr, 0.0,
+                                                     nullptr, nullptr, nullptr, nullptr, nullptr, free_rows, h_out, stamps);
 }
 
 // d2d_nlp_solve_moving: around the problems' moving discs -- the rows' constant wind or the field (WIND), the start time per problem.
@@ -1998,6 +2260,25 @@ nlp_model_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restric
   }
 }
 
+// D2D_NLP_STAMPS (diagnostics): the buffer of problem 0's cycle stamps, or null; nlp_stamps_report prints and frees it (synchronous)
+static int nlp_stamps_alloc(unsigned long long **stamps) {
+  *stamps = nullptr;
+  if (getenv("D2D_NLP_STAMPS")) D2D_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(stamps), 16 * sizeof(unsigned long long)));
+  return D2D_OK;
+}
+static int nlp_stamps_report(d2d_ctx *ctx, unsigned long long *stamps) {
+  if (!stamps) return D2D_OK;
+  unsigned long long hs[9];
+  D2D_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  D2D_CHECK_HIP(hipMemcpy(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost));
+  D2D_CHECK_HIP(hipFree(stamps));
+  static const char *nm[8] = {"merit", "assemble", "factor", "backsolve", "recover+ratio tests", "update", "eliminate", "other"};
+  fprintf(stderr, "[nlp] problem 0: %llu Newton steps; shader clocks per phase:", hs[8]);
+  for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %llu", nm[k], hs[k]);
+  fprintf(stderr, "\n");
+  return D2D_OK;
+}
+
 // opts or the defaults, validated; who: the entry's name for the message
 static int nlp_options(const d2d_nlp_opts *opts, const char *who, d2d_nlp_opts *o) {
   *o = {D2D_NLP_RHO0, D2D_NLP_MUB0, D2D_NLP_MUB_MIN, 1e-9, 1e-7, 60, 40, 0, 0, nullptr, nullptr};
@@ -2136,25 +2417,15 @@ int d2d_nlp_solve(d2d_ctx *ctx, int B, int N, double h, const double *scen, cons
   D2D_REQUIRE(B >= 1 && N >= 3 && h > 0, "d2d_nlp_solve: B >= 1, N >= 3, h > 0 required (B=%d N=%d h=%g)", B, N, h);
   d2d_nlp_opts o;
   if (int rc = nlp_options(opts, "d2d_nlp_solve", &o)) return rc;
-  unsigned long long *stamps = nullptr;
-  if (getenv("D2D_NLP_STAMPS")) D2D_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&stamps), 16 * sizeof(unsigned long long)));
+  unsigned long long *stamps;
+  if (int rc = nlp_stamps_alloc(&stamps)) return rc;
   const int grid = nlp_handout_grid(B, o, NLP_WAVES_PER_SIMD);
   int32_t *queue = ctx->counter_dev + 2;
   D2D_CHECK_HIP(hipMemsetAsync(queue, 0, sizeof(int32_t), ctx->stream));
   hipLaunchKernelGGL(nlp_solve_kernel, dim3(grid), dim3(64), NLP_LDS_DOUBLES * sizeof(double), ctx->stream, B, N, h, o, scen, partner, W, work, mult, cost, feas, iters,
                      status, stamps, queue);
   D2D_LAUNCH_CHECK();
-  if (stamps) {                                            // diagnostics: synchronous
-    unsigned long long hs[9];
-    D2D_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    D2D_CHECK_HIP(hipMemcpy(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost));
-    D2D_CHECK_HIP(hipFree(stamps));
-    static const char *nm[8] = {"merit", "assemble", "factor", "backsolve", "recover+ratio tests", "update", "eliminate", "other"};
-    fprintf(stderr, "[nlp] problem 0: %llu Newton steps; shader clocks per phase:", hs[8]);
-    for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %llu", nm[k], hs[k]);
-    fprintf(stderr, "\n");
-  }
-  return D2D_OK;
+  return nlp_stamps_report(ctx, stamps);                   // diagnostics: synchronous
 }
 
 int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
@@ -2165,6 +2436,22 @@ int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen,
   d2d_nlp_opts o;
   if (int rc = nlp_options(opts, "d2d_nlp_solve_wind", &o)) return rc;
   return nlp_handout_launch(nlp_solve_wind_kernel, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status, *f, t_start);
+}
+
+int d2d_nlp_free_workspace_doubles(int N) { return N * WSF_TOTAL; }
+
+int d2d_nlp_solve_free(d2d_ctx *ctx, int B, int N, double h0, const double *scen, const d2d_nlp_opts *opts, const double *free_rows,
+                       double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, double *h_out) {
+  if (int rc = nlp_single_check(ctx, B, N, h0, scen, W, work, cost, feas, "d2d_nlp_solve_free")) return rc;
+  D2D_REQUIRE(free_rows && h_out, "d2d_nlp_solve_free: null free_rows or h_out");
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_free", &o)) return rc;
+  D2D_REQUIRE(o.serial == 0, "d2d_nlp_solve_free: opts->serial = 1 (the twisted recursion) is not available with a free time step");
+  unsigned long long *stamps;
+  if (int rc = nlp_stamps_alloc(&stamps)) return rc;
+  if (int rc = nlp_handout_launch(nlp_solve_free_kernel, ctx, B, N, h0, o, scen, W, work, mult, cost, feas, iters, status, free_rows, h_out, stamps))
+    return rc;
+  return nlp_stamps_report(ctx, stamps);                   // (factor: both passes of the cyclic reduction)
 }
 
 int d2d_nlp_solve_groups(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,

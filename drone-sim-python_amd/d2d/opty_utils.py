@@ -168,6 +168,26 @@ class CostInput:
         return g * (_p.obj_scale / _p.num_nodes)
 
 
+class CostDuration:
+    """k * duration of the plan, for a Problem whose node interval is free (opty's variable duration: the interval is the LAST
+    entry of the free vector, duration = (num_nodes - 1) * interval).  cost_grad is zero on the node variables and k (num_nodes - 1)
+    on the interval entry.  On a free vector without that entry (a fixed interval) the value is k * the planner's duration and the
+    gradient is zero."""
+
+    def __init__(self, k=1.):
+        self.k = k
+
+    def cost(self, free, _p):
+        n = _p.num_nodes
+        return self.k * (n - 1) * (free[-1] if len(free) == 5 * n + 1 else _p.time_step)
+
+    def cost_grad(self, free, _p):
+        g = np.zeros_like(free)
+        if len(free) == 5 * _p.num_nodes + 1:
+            g[-1] = self.k * (_p.num_nodes - 1)
+        return g
+
+
 def _obstacle_field(dx, dy, r, kind, k):
     if kind == 0:
         return np.clip(np.exp(r ** 2 - (dx ** 2 + dy ** 2)), 0., 1e3)
@@ -211,10 +231,13 @@ class CostObstacles:
 
 class CostComposit:
     """kobs * obstacles + kvel * air speed + kbank * bank (src/d2d/opty_utils.py:147-165);
-    obss=None leaves the obstacle term out, as the reference's try/except does."""
+    obss=None leaves the obstacle term out, as the reference's try/except does.  kdur (not in the reference): + kdur * duration, for a
+    Problem whose node interval is free (CostDuration); without it the class is the reference's."""
 
-    def __init__(self, obss, vsp=10., kobs=1., kvel=1., kbank=1., obs_kind=0):
+    def __init__(self, obss, vsp=10., kobs=1., kvel=1., kbank=1., obs_kind=0, kdur=None):
         self.kobs, self.kvel, self.kbank = kobs, kvel, kbank
+        if kdur is not None:
+            self.kdur, self.cdur = float(kdur), CostDuration(1.)
         if obss is not None:
             self.cobs = CostObstacles(obss, obs_kind)
         self.cvel = CostAirVel(vsp)
@@ -224,6 +247,8 @@ class CostComposit:
         t = [(self.kvel, self.cvel), (self.kbank, self.cbank)]
         if hasattr(self, 'cobs'):
             t.insert(0, (self.kobs, self.cobs))
+        if hasattr(self, 'cdur'):
+            t.append((self.kdur, self.cdur))
         return t
 
     def cost(self, free, _p):

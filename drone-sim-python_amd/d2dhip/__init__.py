@@ -177,6 +177,8 @@ _SIGS = {
     'd2d_nlp_workspace_doubles': (C.c_int, [C.c_int]),
     'd2d_nlp_solve': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 8),
     'd2d_nlp_solve_wind': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7 + [C.POINTER(WindFieldC), C.c_double]),
+    'd2d_nlp_free_workspace_doubles': (C.c_int, [C.c_int]),
+    'd2d_nlp_solve_free': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 9),
     'd2d_nlp_solve_groups': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9),
     'd2d_nlp_solve_groups_wind': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
                                   + [C.POINTER(WindFieldC), _P]),
@@ -582,18 +584,20 @@ class Context:
         return out
 
     def _nlp_core(self, entry, scen, W, h, opts, bounds, n_ac=None, sweeps=None, want_mult=False, slots=0, order=None, mid=(),
-                  field=_ABSENT, t_start=None, t_scalar=False, moving=_ABSENT, via=_ABSENT):
+                  field=_ABSENT, t_start=None, t_scalar=False, moving=_ABSENT, via=_ABSENT, free_rows=None):
         """What the nlp_solve* methods share: the shape checks, the workspace and the outputs, d2d_nlp_opts from opts = (rho0, mub0,
         mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), the call of `entry` and the result.  n_ac: a group entry (sweeps =
         (max_sweeps, tol)), R = B / n_ac scenarios with one start time and one set of tracks each; else B problems.  mid: arguments
         between W and work.  field, moving = (knots, disc), via: the optional inputs in the entries' order, _ABSENT where the entry takes
-        none (it takes t_start with the field: a device array, or with t_scalar a float); each adds its entries to the result."""
+        none (it takes t_start with the field: a device array, or with t_scalar a float); each adds its entries to the result.
+        free_rows: the entry is d2d_nlp_solve_free -- the rows go in front of W, the solved steps `h` [B] behind status, and the
+        workspace is the larger one."""
         torch = _torch()
         B, _, N = W.shape
         groups = n_ac is not None
         assert W.is_contiguous() and scen.shape[0] == B and (not groups or B % n_ac == 0)
         G = B // n_ac if groups else B
-        ws = self.lib.d2d_nlp_workspace_doubles(N)
+        ws = self.lib.d2d_nlp_workspace_doubles(N) if free_rows is None else self.lib.d2d_nlp_free_workspace_doubles(N)
         m = None if moving is _ABSENT else self._moving_c(*moving, G)
         v = None if via is _ABSENT else self._via_c(via, B)
         if field is not _ABSENT and not t_scalar:
@@ -610,6 +614,10 @@ class Context:
         if groups:
             out['sweeps'], out['moved'] = torch.empty(G, dtype=torch.int32, device=self.device), self.empty(G)
             args = [self.h, G, n_ac, N, float(h), _ptr(scen), C.byref(o), int(sweeps[0]), float(sweeps[1]), _ptr(W)] + args + [_ptr(out['sweeps']), _ptr(out['moved'])]
+        elif free_rows is not None:
+            assert free_rows.is_contiguous() and tuple(free_rows.shape) == (B, 4) and free_rows.dtype == torch.float64
+            out['h'] = self.empty(B)
+            args = [self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(free_rows), _ptr(W)] + args + [_ptr(out['h'])]
         else:
             args = [self.h, B, N, float(h), _ptr(scen), C.byref(o), _ptr(W), *mid] + args
         if field is not _ABSENT:
@@ -642,6 +650,15 @@ class Context:
         assert partner is None or (partner.is_contiguous() and partner.shape == (B, 2, N))
         return self._nlp_core(self.lib.d2d_nlp_solve, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
                               want_mult=want_mult, slots=slots, order=order, mid=(_ptr(partner),))
+
+    def nlp_solve_free(self, scen, W, h, free_rows, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
+                       outer_max=NLP_OUTER_MAX, want_mult=False, bounds=None, slots=0, order=None):
+        """nlp_solve with every problem's time step free (d2d_nlp_solve_free; opty's variable-duration Problem): free_rows dev [B][4] =
+        (h_lo, h_hi, k_dur, h_start; 0 = h), the hard box of the step, the weight of the duration (N - 1) h in the objective and the
+        start step.  No partner; the rows' constant wind.  Returns nlp_solve's dict plus h (device [B]: the solved steps; NaN for a
+        refused problem); cost includes k_dur (N - 1) h."""
+        return self._nlp_core(self.lib.d2d_nlp_solve_free, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, 0), bounds,
+                              want_mult=want_mult, slots=slots, order=order, free_rows=free_rows)
 
     def nlp_solve_wind(self, scen, W, h, field, t_start=0.0, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7,
                        inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None, slots=0, order=None):

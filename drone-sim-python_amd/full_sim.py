@@ -163,7 +163,8 @@ def trajectory_gen_multi(p, delta):
 
 def trajectory_optimization_single(scen, delta, backend=None):
     """src/12_full_sim_case3.py:184-193 without the plots: one single-aircraft plan (scen.p0 injected by the caller, :456-460),
-    duplicated with an offset for the wingman."""
+    duplicated with an offset for the wingman.  A scenario with t1_free is planned with its duration free (single_opt_planner): both
+    aircraft then share the solved clock p.sol_time, p.time_step, p.duration."""
     import single_opt_planner as sop
     p = sop.Planner(scen, backend=backend)
     p.configure(tol=1e-5, max_iter=1500)
@@ -284,7 +285,7 @@ def _plan_batch_via(ctx, scen_rows, dsc, W, N, h, n_ac, fld, t_start, moving, vi
 
 
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               moving=None, via=None, gust=None, **solve_kw):
+               moving=None, via=None, gust=None, free_time=None, kdur=0.0, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -302,7 +303,10 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     on the clock of t_start, held exactly (d2d_nlp_solve_groups_via, with and without a field or moving obstacles); the result carries
     via (the device table) and waypoint_error, the largest |plan - pin|: 0.0.  Like moving=, via= goes through the group entry
     for every n_ac: with n_ac = 1 that is one workgroup with one wavefront per problem, each with its own workspace, not the persistent
-    hand-out of d2d_nlp_solve_via -- for large batches of single aircraft call Context.nlp_solve_via (the difference is not measured)."""
+    hand-out of d2d_nlp_solve_via -- for large batches of single aircraft call Context.nlp_solve_via (the difference is not measured).
+    free_time (backend='nlp', n_ac = 1): (h_lo, h_hi) for all problems or an array (B, 2) -- every problem's time step is an unknown in
+    that box, started from h, with kdur (a number or (B,)) the weight of the duration (K - 1) h in its objective (d2d_nlp_solve_free);
+    the result carries h, the solved steps (device [B]).  Not combined with n_ac > 1, windfield, moving or via: raised by name."""
     import single_opt_planner as sop
     from d2d.wind import planner_wind
     if gust is not None:
@@ -315,12 +319,27 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
         raise NotImplementedError("the polynomial fit has no timed waypoints: plan_batch(backend='nlp', via=...) plans through them")
     if fld is not None and backend != 'nlp':
         raise NotImplementedError("the polynomial fit has no wind field: plan_batch(backend='nlp', windfield=...) plans in one")
+    if free_time is not None:
+        if backend != 'nlp':
+            raise NotImplementedError("the polynomial fit has no free time step: plan_batch(backend='nlp', free_time=...) plans with one")
+        if int(n_ac) != 1:
+            raise NotImplementedError('free_time with n_ac > 1: the aircraft of a scenario share one time step, which the block '
+                                      'Gauss-Seidel over the aircraft cannot hold; plan them one at a time')
+        if fld is not None or moving or via is not None:
+            raise NotImplementedError('free_time together with windfield, moving or via is not supported: node times move with the step')
     ctx = d2dhip.default_context()
     if backend == 'nlp':
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
         W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
         assert W.shape == (dsc.shape[0], 5, K) and h is not None
-        if via is not None:
+        if free_time is not None:
+            B = dsc.shape[0]
+            fr = np.zeros((B, 4))
+            fr[:, :2] = np.broadcast_to(np.asarray(free_time, dtype=np.float64), (B, 2))
+            fr[:, 2] = np.broadcast_to(np.asarray(kdur, dtype=np.float64), (B,))
+            out = ctx.nlp_solve_free(dsc, W, float(h), ctx.dev(fr), **solve_kw)
+            out['free_rows'] = fr
+        elif via is not None:
             out = _plan_batch_via(ctx, scen_rows, dsc, W, K, float(h), int(n_ac), fld, t_start, moving, via, solve_kw)
         elif moving:
             knots, disc = _moving_tables(ctx, moving, dsc.shape[0] // int(n_ac))

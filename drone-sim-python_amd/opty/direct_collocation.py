@@ -33,7 +33,13 @@ all of them.  info['min_separation']: per coupled pair, the smallest node-wise d
 Moving obstacles (the planner's `moving_obstacles`, d2d.opty_utils.MovingObstacle) are lowered to the side table of
 d2d_moving_obstacles and solved by d2d_nlp_solve_moving (one aircraft, with or without a field) or d2d_nlp_solve_groups_moving (all
 aircraft of the Problem see the same tracks), node i at t0 + i time_step; info['min_clearance']: per disc (per aircraft and disc for
-several aircraft) the smallest node-wise distance to the disc's rim."""
+several aircraft) the smallest node-wise distance to the disc's rim.
+A VARIABLE DURATION, as upstream opty spells it: `time_step` a symbol (a sympy Symbol, or any object with a `name` that is no number)
+instead of a float.  The interval is then the LAST entry of the free vector (num_free = 5 N + 1), may carry a bound in `bounds`
+({h_sym: (lo, hi)}; without one: (h / 4, 4 h) of the start value x0[-1]), and is solved with the node values by d2d_nlp_solve_free; a
+duration term of the cost (d2d.opty_utils.CostDuration, CostComposit(kdur=)) is its weight.  One aircraft, the constant wind, static
+obstacles and a lowered objective: with timed waypoints, moving obstacles, a wind field, the host objective or several aircraft the
+constructor raises NotImplementedError naming the combination.  info carries time_step and duration."""
 import numpy as np
 
 import d2dhip
@@ -115,9 +121,11 @@ class Problem:
     def __init__(self, obj, obj_grad, eom, state_symbols, num_nodes, time_step, known_parameter_map=None,
                  instance_constraints=(), bounds=None, parallel=False, cost=None, planner=None):
         self.obj, self.obj_grad = obj, obj_grad
-        self.num_nodes, self.time_step = int(num_nodes), float(time_step)
+        # a symbol for the interval: variable duration (the interval is the last free entry); a number: the fixed step
+        self.free_step = time_step if (hasattr(time_step, 'name') and not isinstance(time_step, (int, float, np.number))) else None
+        self.num_nodes, self.time_step = int(num_nodes), (float('nan') if self.free_step is not None else float(time_step))
         self.n_aircraft = len(state_symbols) // 3
-        self.num_free = 5 * self.num_nodes * self.n_aircraft
+        self.num_free = 5 * self.num_nodes * self.n_aircraft + (1 if self.free_step is not None else 0)
         self.options = {'tol': 1e-8, 'max_iter': 3000}
         self.wind = tuple(getattr(eom, 'wind', (0., 0.)))
         self.field = getattr(eom, 'field', None)
@@ -171,12 +179,21 @@ class Problem:
         import d2d.opty_utils as d2ou
         self.waypoints = [[d2ou.Waypoint(t, **pa[t]) for t in sorted(pa)] for pa in pins]
         self.via = None                                 # (n_aircraft, n_via, 5): the table of d2d_via_points
+        if any(self.waypoints) and self.free_step is not None:
+            raise NotImplementedError(f'a variable duration (time_step = {self.free_step}) together with instance_constraints at interior '
+                                      'times (a timed waypoint changes node with the step) is not supported')
         if any(self.waypoints):
             n_via = max(len(w) for w in self.waypoints)
             self.via = np.stack([d2ou.lower_waypoints(w, self.t_start, self.time_step, self.num_nodes, n_via) for w in self.waypoints])
         # bounds per aircraft
         self.bounds = [{} for _ in range(self.n_aircraft)]
+        self.step_bounds = None                        # (lo, hi) of a free interval, or None: (h / 4, 4 h) of the start value
         for key, (lo, hi) in (bounds or {}).items():
+            if self.free_step is not None and (key is self.free_step or (not hasattr(key, 'sym') and key == self.free_step)):
+                self.step_bounds = (float(lo), float(hi))
+                if not 0.0 < self.step_bounds[0] < self.step_bounds[1]:
+                    raise ValueError(f'bounds of the time step {key}: 0 < lo < hi required, got {self.step_bounds}')
+                continue
             for nm in ('phi', 'psi', 'v', 'x', 'y'):
                 for a, i in enumerate(ids):
                     if key.sym.name == nm + i:
@@ -184,6 +201,13 @@ class Problem:
         for bd in self.bounds:
             if 'phi' not in bd or 'v' not in bd:
                 raise NotImplementedError('phi and v bounds are required (the model divides by v)')
+        if self.free_step is not None:                  # what a free interval is not combined with (d2d_nlp_solve_free)
+            what = ('more than one aircraft (they share one interval: the joint system is not built)' if self.n_aircraft != 1 else
+                    'moving obstacles (their node times move with the step)' if self.moving else
+                    'a wind field that varies in space and time (its time derivative enters the border)' if self.field is not None else
+                    'the host objective (a cost plug-in without a kernel)' if self.objective == 'host' else None)
+            if what:
+                raise NotImplementedError(f'a variable duration (time_step = {self.free_step}) together with {what} is not supported')
 
     def addOption(self, k, v):
         self.options[k] = v
@@ -253,6 +277,8 @@ class Problem:
         W = np.stack([np.stack([get(sl._slice_x, a), get(sl._slice_y, a), get(sl._slice_psi, a), get(sl._slice_phi, a),
                                 get(sl._slice_v, a)], 0) for a in range(n)], 0)                       # (n, 5, N)
         rows, coupled = self._rows()
+        if self.free_step is not None:
+            return self._solve_free(ctx, x0, W, rows)
         # IPOPT's max_iter counts Newton steps; here they are grouped as outer (multiplier / barrier updates) x inner (<= D2D_NLP_INNER_MAX):
         # between 720 and 3600 steps in all, as in rounds 2-3 (12 .. 60 batches of 60)
         _im = d2dhip.NLP_INNER_MAX
@@ -331,6 +357,41 @@ class Problem:
             import d2d.opty_utils as d2ou
             info['waypoint_error'] = max(d2ou.waypoint_error(self.via[a], Wh[a]) for a in range(n))
         return sol, info
+
+    def _solve_free(self, ctx, x0, W, rows):
+        """The variable-duration Problem: one aircraft, the interval x0[-1] free in its bound (d2d_nlp_solve_free)."""
+        import single_opt_planner as sop
+        N = self.num_nodes
+        h0 = float(x0[-1])
+        if not (np.isfinite(h0) and h0 > 0.0):
+            raise ValueError(f'the start value of the time step (the last entry of x0) must be positive and finite, got {h0}')
+        lo, hi = self.step_bounds if self.step_bounds is not None else (h0 / 4.0, 4.0 * h0)
+        _im = d2dhip.NLP_INNER_MAX
+        tol = float(self.options.get('tol', 1e-8))
+        kw = dict(inner_max=_im, outer_max=int(min(max(self.options.get('max_iter', 3000) // _im, 720 // _im), 3600 // _im)),
+                  opt_tol=min(tol, 1e-7), feas_tol=min(1e-2 * tol, 1e-9))
+        bd = self.bounds[0]
+        bnd = None
+        if 'psi' in bd or abs(bd['phi'][0] + bd['phi'][1]) > 1e-12:
+            bnd = ctx.dev(np.array([[bd['phi'][0], bd['phi'][1]] + list(bd.get('psi', (0.0, 0.0)))], dtype=np.float64))
+        dsc = ctx.dev(rows)
+        dsc[:, d2dhip.SC_KCOL] = 0.0
+        dW = ctx.dev(np.ascontiguousarray(W))
+        self.free_rows = np.array([[lo, hi, sop.duration_weight(sop.lower_cost(self.cost)), h0]])
+        out = ctx.nlp_solve_free(dsc, dW, h0, ctx.dev(self.free_rows), bounds=bnd, **kw)
+        ctx.sync()
+        Wh = dW.cpu().numpy()
+        h = float(out['h'][0].item())
+        sl = self.planner
+        sol = np.zeros(self.num_free)
+        for c, s in enumerate((sl._slice_x, sl._slice_y, sl._slice_psi, sl._slice_phi, sl._slice_v)):
+            sol[s] = Wh[0, c]
+        sol[-1] = h
+        st = int(out['status'][0].item())
+        return sol, {'status': st, 'feas': float(out['feas'][0].item()), 'iters': out['iters'].cpu().numpy().tolist(), 'sweeps': 0,
+                     'moved': 0.0, 'obj_val': float(self.obj(sol)), 'cost': float(out['cost'][0].item()),
+                     'status_msg': STATUS_MSG.get(st, 'max_iter'), 'time_step': h, 'duration': h * (N - 1),
+                     'box_violation': 0.0, 'phi_violation': 0.0, 'v_violation': 0.0}
 
     # ---- host objective ------------------------------------------------------------------------------------------------------
     def _host_rows(self):

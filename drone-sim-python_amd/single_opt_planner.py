@@ -123,13 +123,50 @@ def fit_cost(cost):
                                   "cost_grad on the host") from None
 
 
+class Lowered(tuple):
+    """lower_cost's tuple of a cost with a duration term: the same nine entries, and the weight of the duration as the attribute
+    `kdur` (duration_weight reads it; a plain tuple has none: 0)."""
+    kdur = 0.0
+
+    def __new__(cls, entries, kdur):
+        self = super().__new__(cls, entries)
+        self.kdur = float(kdur)
+        return self
+
+
+def duration_weight(lowered):
+    """k of the term k * duration of a lowered cost (CostDuration, CostComposit(kdur=)); 0 for every other cost."""
+    return float(getattr(lowered, 'kdur', 0.0))
+
+
+FREE_TIME_FIT = ("backend='fit' cannot plan with a free duration (t1_free): the polynomial fit's basis is built for one duration.  "
+                 "backend='nlp' (or 'auto') solves the collocation problem with the time step as an unknown")
+
+
+def check_free_time(exp, backend):
+    """The scenario's optional t1_free = (t1_lo, t1_hi) in seconds -> None or the pair, refused where it cannot be planned."""
+    tf = getattr(exp, 't1_free', None)
+    if tf is None:
+        return None
+    lo, hi = (float(v) for v in tf)
+    if not (np.isfinite(lo) and np.isfinite(hi)) or not lo > exp.t0 or not lo < hi:
+        raise ValueError(f't1_free = ({lo}, {hi}): t0 < t1_lo < t1_hi required (t0 = {exp.t0})')
+    if backend == 'fit':
+        raise NotImplementedError(FREE_TIME_FIT)
+    return lo, hi
+
+
 def lower_cost(cost):
     """Recognise the reference's cost plug-ins structurally -> (vsp, kv, kphi, kobs, obstacles, kcol, rcol,
     okind, bankmax[, pairs]): okind = bit mask of the obstacles of CostObstacle kind 0, bankmax = CostBank max mode.
     A collision term that selects anything but the reference's pair (0, 1) appends its `pairs` argument as a tenth entry
     (collision_pairs_of resolves it); the default keeps the nine entries.
+    A cost with a duration term (CostDuration, CostComposit(kdur=)) returns the same entries as a Lowered, whose attribute kdur is
+    the weight (duration_weight); every other cost returns the plain tuple it always did.
     Anything else has no kernel and raises (there is no CPU solver to fall back to)."""
     nan = float('nan')
+    if isinstance(cost, d2ou.CostDuration):
+        return Lowered((0., 0., 0., 0., (), nan, 0., 0, 0), cost.k)
     if isinstance(cost, d2ou.CostAirVel):
         return cost.vsp, 1., 0., 0., (), nan, 0., 0, 0
     if isinstance(cost, d2ou.CostBank):
@@ -148,7 +185,8 @@ def lower_cost(cost):
     if isinstance(cost, d2ou.CostComposit):
         obss = [(o.c[0], o.c[1], o.r) for o in cost.cobs.obss] if hasattr(cost, 'cobs') else []
         okind = sum(1 << i for i, o in enumerate(cost.cobs.obss) if o.kind == 0) if obss else 0
-        return cost.cvel.vsp, cost.kvel, cost.kbank, cost.kobs, tuple(obss), nan, 0., okind, 0 if cost.cbank.use_mean else 1
+        low = cost.cvel.vsp, cost.kvel, cost.kbank, cost.kobs, tuple(obss), nan, 0., okind, 0 if cost.cbank.use_mean else 1
+        return Lowered(low, cost.kdur) if hasattr(cost, 'cdur') else low
     if isinstance(cost, d2mou.CostComposit):
         obss = ()
         kobs = 0.
@@ -259,6 +297,9 @@ class Planner:
                                       "solves the collocation problem in the field")
         self.moving_obstacles = check_moving(exp, self.backend)
         self.waypoints = check_waypoints(exp, self.backend)
+        # an optional free duration (exp.t1_free = (t1_lo, t1_hi), seconds): the node count stays that of t1 and hz, the time step is
+        # an unknown of the collocation problem in [(t1_lo - t0) / (N - 1), (t1_hi - t0) / (N - 1)] (d2d_nlp_solve_free)
+        self.t1_free = check_free_time(exp, self.backend)
         self.aircraft = d2ou.Aircraft()
         N = self.num_nodes
         self._slice_x, self._slice_y, self._slice_psi, self._slice_phi, self._slice_v = (
@@ -270,7 +311,8 @@ class Planner:
             raise NotImplementedError(MOVING_HOST_COST)
         if self._host_cost and self.waypoints:
             raise NotImplementedError(VIA_HOST_COST)
-        if initialize and (self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints):
+        if initialize and (self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints
+                           or self.t1_free is not None):
             import opty.direct_collocation
             _g = self.aircraft
             t0, (x0, y0, psi0, phi0, v0) = exp.t0, exp.p0
@@ -284,9 +326,13 @@ class Planner:
             if exp.y_constraint is not None:
                 self._bounds[_g._sy(_g._st)] = exp.y_constraint
             obj = exp.cost
+            step = self.time_step
+            if self.t1_free is not None:           # the interval as a symbol with its bound: opty's variable duration
+                step = d2ou._Sym('h')
+                self._bounds[step] = tuple((t - exp.t0) / (self.num_nodes - 1) for t in self.t1_free)
             self.prob = opty.direct_collocation.Problem(lambda _free: obj.cost(_free, self),
                                                         lambda _free: obj.cost_grad(_free, self),
-                                                        _g.get_eom(self.wind), _g._state_symbols, self.num_nodes, self.time_step,
+                                                        _g.get_eom(self.wind), _g._state_symbols, self.num_nodes, step,
                                                         known_parameter_map={}, instance_constraints=self._instance_constraints,
                                                         bounds=self._bounds, parallel=False)
         elif initialize:
@@ -326,6 +372,8 @@ class Planner:
         """Node-vector guess [x, y, psi, phi, v] (src/single_opt_planner.py:79-115)."""
         g = np.zeros(self.prob.num_free)
         N = self.num_nodes
+        if self.t1_free is not None:               # the interval is the last entry: the scenario's own step is its start
+            g[-1] = self.time_step
         if kind == 'rnd':
             rng = np.random.default_rng(seed)
             cx = self.exp.x_constraint or [-100, 100]
@@ -372,7 +420,11 @@ class Planner:
         if initial_guess is None:
             initial_guess = self.get_initial_guess('via' if self.waypoints else 'tri')
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints:
+        if self.t1_free is not None:               # the plan's clock follows the solved interval
+            self.time_step = float(self.solution[-1])
+            self.duration = self.time_step * (self.num_nodes - 1)
+            self.info['backend_used'] = 'nlp'
+        elif self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints:
             self.info['backend_used'] = 'nlp'
         elif self.backend != 'nlp':
             self._harden()
@@ -385,8 +437,9 @@ class Planner:
 
     def save_solution(self, filename):
         wind = np.array([self.wind.sample_num(t, x, y) for t, x, y in zip(self.sol_time, self.sol_x, self.sol_y)])
+        extra = {} if self.t1_free is None else dict(time_step=self.time_step, duration=self.duration)
         np.savez(filename, sol_time=self.sol_time, sol_x=self.sol_x, sol_y=self.sol_y, sol_psi=self.sol_psi,
-                 sol_phi=self.sol_phi, sol_v=self.sol_v, wind=wind)
+                 sol_phi=self.sol_phi, sol_v=self.sol_v, wind=wind, **extra)
         print('saved {}'.format(filename))
 
     def load_solution(self, filename):

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 119
+#define D2D_VERSION 120
 
 /* error codes */
 #define D2D_OK 0
@@ -787,6 +787,34 @@ int d2d_nlp_solve_model(d2d_ctx *ctx, int B, int N, double h, const double *scen
 int d2d_nlp_solve_wind(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W,
                        double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
                        const d2d_wind_field *f, double t_start);
+
+/* d2d_nlp_solve with a FREE time step: the solve behind `opty.direct_collocation.Problem(..., node_time_interval=<sympy Symbol>,
+ * bounds={h: (lo, hi), ...})` (variable duration: the interval is the last entry of opty's free vector and may carry a bound).  The
+ * node count N stays fixed; every problem's interval h is one more unknown, shared by all its equalities
+ *   (x_i - x_{i-1})/h - v_i cos psi_i + wx = 0, ... (the rows' constant wind),
+ * inside the HARD box h_lo < h < h_hi (same primal-dual log barrier as the node variables, two duals of its own), with the objective
+ *   the row's structured cost + k_dur (N - 1) h,   k_dur >= 0  (0: the duration is whatever lets v sit at VSP).
+ * The solver's variable is u = 1 / h, in which the equalities are linear (dc/du = the node difference, d2c/du2 = 0, cross curvature
+ * +-1).  The Newton system is the block-tridiagonal matrix A of d2d_nlp_solve BORDERED by one column: b = rho J^T dc/du + rho (c + mu)
+ * d2c/(du dw) on a node's five variables and its predecessor's (x, y, psi), and the scalar d = rho |dc/du|^2 + k_dur (N - 1) / u^3 + the
+ * barrier diagonal of u, damped like A's diagonal (d += lambda max(|d|, 1e-12)).  It is solved by the Schur complement on d,
+ *   x0 = A^-1 r / 2,  y = A^-1 b,  du = (r_u / 2 - b.x0) / (d - b.y),  dW = x0 - y du,
+ * b passing through the same per-node elimination of (phi, v) as the right-hand side and through a second pass of the block cyclic
+ * reduction; d - b.y <= 0 (the bordered matrix is not positive definite) raises the damping like a failed pivot.  The line search
+ * reads the equalities at the trial step, the ratio tests and the KKT error include u.  opts->serial = 1 is not available:
+ * D2D_EINVAL.  opts->order, slots, bounds and the tolerances as d2d_nlp_solve; no partner, no field, nothing moves, no pins.
+ * free_rows dev [B][4] = (h_lo, h_hi, k_dur, h_start); h_start = 0: the start interval is h0, else h_start; either is pushed strictly
+ * inside the box.  A problem with h_lo <= 0, h_lo >= h_hi, k_dur < 0, a non-finite entry, or an unusable scenario row is refused on
+ * the device at once: D2D_ST_NONFINITE, cost = feas = h_out = NaN, iters = 0, its W untouched; the rest of the launch is solved.
+ * h_out dev [B]: the solved interval (strictly inside its box).  cost: the reference's cost() + k_dur (N - 1) h_out; feas: the largest
+ * collocation residual at h_out; status D2D_ST_CONVERGED / D2D_ST_MAXITER / D2D_ST_STALLED as d2d_nlp_solve.
+ * work dev double[d2d_nlp_free_workspace_doubles(N) * B].  tests/nlp_free_ref.py is the CPU statement.  Asynchronous on the context's
+ * stream.  (version 120) */
+int d2d_nlp_free_workspace_doubles(int N);
+int d2d_nlp_solve_free(d2d_ctx *ctx, int B, int N, double h0, const double *scen, const d2d_nlp_opts *opts,
+                       const double *free_rows /* dev [B][4] = (h_lo, h_hi, k_dur, h_start; 0 = h0) */,
+                       double *W, double *work, double *mult, double *cost, double *feas,
+                       int32_t *iters, int32_t *status, double *h_out /* dev [B] */);
 
 /* d2d_nlp_solve_groups in a wind field: the multi-aircraft Problem of R scenarios whose equalities are those of d2d_nlp_solve_wind,
  *   .. + wx(t_i, x_i, y_i) = 0,  .. + wy(t_i, x_i, y_i) = 0,   t_i = t_start[r] + i h  (one multiply-add, not accumulated),

@@ -22,7 +22,11 @@ python tools/bench_nlp_wind.py moving [B]  moving obstacles (d2d_nlp_solve_movin
 python tools/bench_nlp_wind.py via [B]     timed waypoints (d2d_nlp_solve_via): B (default 4096) perturbed exp_14 at 121 nodes, each with one
     (x, y) pin at node 60 on the middle of its leg moved 5 m sideways, from the piecewise-linear guess through the pin, against the
     tool's own unpinned constant-wind figure (d2d_nlp_solve, the same rows from their own guess) in the same run.  The two entries
-    alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians and the spread of each."""
+    alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians and the spread of each.
+python tools/bench_nlp_wind.py free [B]    a free time step (d2d_nlp_solve_free): B (default 4096) perturbed exp_14 at 121 nodes, once with
+    the step fixed (d2d_nlp_solve) and once with h free in [h / 2, 2 h] (k_dur = 0: the duration is whatever lets v sit at VSP), the
+    same rows from the same guess.  The two entries alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians,
+    the spread of each, the share CONVERGED of both and what the freed step does to the problems the fixed one leaves STALLED."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 'tests')):
@@ -218,7 +222,44 @@ def via_leg(B):
     ctx.close()
 
 
+def free_leg(B):
+    import torch, d2dhip
+    from d2dhip import synth
+    ctx = d2dhip.Context(0)
+    rows, W0, h = synth.nlp_problems(B)
+    dsc = ctx.dev(rows)
+    fr = ctx.dev(np.tile([0.5 * h, 2.0 * h, 0.0, 0.0], (B, 1)))
+    times = {'fixed': [], 'free': []}
+    outs = {}
+    for rep in range(6):                                     # the first launch of each is the warm-up; the entries alternate
+        for what in ('fixed', 'free'):
+            W = ctx.dev(np.ascontiguousarray(W0))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            outs[what] = ctx.nlp_solve(dsc, W, h) if what == 'fixed' else ctx.nlp_solve_free(dsc, W, h, fr)
+            e1.record(); torch.cuda.synchronize()
+            times[what].append(e0.elapsed_time(e1) * 1e-3)
+    med = {k: float(np.median(v[1:])) for k, v in times.items()}
+    st = {k: outs[k]['status'].cpu().numpy() for k in outs}
+    for what in ('fixed', 'free'):
+        it = outs[what]['iters'].cpu().numpy()
+        rec = {'leg': 'free', 'B': B, 'nodes': W0.shape[2], 'entry': what, 'seconds_median': med[what], 'seconds_min': min(times[what][1:]),
+               'seconds_max': max(times[what][1:]), 'problems_per_s': B / med[what], 'free_over_fixed': med['free'] / med['fixed'],
+               'converged_frac': float((st[what] == 1).mean()), 'stalled_frac': float((st[what] == 4).mean()),
+               'mean_newton_steps': float(it.mean()), 'max_newton_steps': int(it.max())}
+        if what == 'free':
+            hh = outs['free']['h'].cpu().numpy()
+            ok = st['free'] == 1
+            rec.update(fixed_not_converged=int((st['fixed'] != 1).sum()), of_those_free_converged=int((ok & (st['fixed'] != 1)).sum()),
+                       fixed_converged_free_not=int((~ok & (st['fixed'] == 1)).sum()),
+                       duration_min_mean_max=[float(v) * (W0.shape[2] - 1) for v in (hh[ok].min(), hh[ok].mean(), hh[ok].max())] if ok.any() else None)
+        print(json.dumps(rec), flush=True)
+    ctx.close()
+
+
 def main():
+    if sys.argv[1:2] == ['free']:
+        return free_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['via']:
         return via_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['moving']:

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """The collocation backend over the reference's single-aircraft scenario catalogue (d2d.optyplan_scenarios.scens, every case):
-status, Newton steps, cost, feasibility -- a robustness survey of d2d_nlp_solve.  python tools/nlp_catalogue.py"""
+status, Newton steps, cost, feasibility -- a robustness survey of d2d_nlp_solve.  python tools/nlp_catalogue.py
+--free-time: every case with its duration freed to [t / 2, 2 t] (t = t1 - t0; the scenario protocol's t1_free, d2d_nlp_solve_free):
+status, duration and cost per case.  Cases that a free step is not combined with (a wind field, moving obstacles, waypoints, a host
+cost) report the refusal."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd')):
@@ -9,6 +12,7 @@ import numpy as np
 
 
 def main():
+    free = '--free-time' in sys.argv[1:]
     import d2d.optyplan_scenarios as sc
     import single_opt_planner as sop
     # the reference's sweeps mutate exp_0 (exp_0_1: t1, exp_0_2: wind, exp_6: p0 / p1) and every exp_0-based scenario sees it:
@@ -20,12 +24,19 @@ def main():
         for case in range(s.ncases):
             s.set_case(case)
             try:
-                p = sop.Planner(s, initialize=True, backend='nlp')
+                exp = s
+                if free:                                # the case as it stands, with t1 free in [t0 + t / 2, t0 + 2 t]
+                    t = s.t1 - s.t0
+                    exp = type(s.__name__ + '_free', (s,), {'t1_free': (s.t0 + 0.5 * t, s.t0 + 2.0 * t)})
+                p = sop.Planner(exp, initialize=True, backend='nlp')
                 t0 = time.perf_counter()
                 p.run(p.get_initial_guess(getattr(s, 'initial_guess', 'tri')))
                 dt = time.perf_counter() - t0
-                print(json.dumps({'scen': s.name, 'case': case, 'nodes': p.num_nodes, 'status': p.info['status'], 'iters': p.info['iters'],
-                                  'cost': p.info['obj_val'], 'feas': p.info['feas'], 'seconds': round(dt, 3)}), flush=True)
+                rec = {'scen': s.name, 'case': case, 'nodes': p.num_nodes, 'status': p.info['status'], 'iters': p.info['iters'],
+                       'cost': p.info['obj_val'], 'feas': p.info['feas'], 'seconds': round(dt, 3)}
+                if free:
+                    rec.update(duration=p.duration, asked=s.t1 - s.t0)
+                print(json.dumps(rec), flush=True)
             except Exception as e:                      # noqa: BLE001 -- a survey: report and go on
                 print(json.dumps({'scen': s.name, 'case': case, 'error': f'{type(e).__name__}: {e}'[:200]}), flush=True)
 
