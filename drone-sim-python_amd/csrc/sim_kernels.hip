@@ -499,12 +499,11 @@ dfff_run_body(const d2d_track_params &p, const GlMesh &mesh, const double *__res
   }
 }
 
-__global__ void __launch_bounds__(64)
-dfff_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref, const double *__restrict__ perts,
-                const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist,
-                double *__restrict__ Xr_hist, double *__restrict__ X_final) {
-  dfff_run_body<false>(p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final);
-}
+#define DFFF_ARGS d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref, const double *__restrict__ perts,                     \
+                  const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist, double *__restrict__ Xr_hist, \
+                  double *__restrict__ X_final
+#define DFFF_PASS p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final
+__global__ void __launch_bounds__(64) dfff_run_kernel(DFFF_ARGS) { dfff_run_body<false>(DFFF_PASS); }
 
 // numpy.gradient(f, edge_order=2) with unit spacing at row i of a [n_rows][n] plane
 __device__ __forceinline__ double grad2(const double *__restrict__ f, int i, int T, long n, long d) {
@@ -602,17 +601,13 @@ track_run_body(const d2d_track_params &p, const GlMesh &mesh, const double *__re
   }
 }
 
-__global__ void __launch_bounds__(64)
-track_run_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
-                 const double *__restrict__ y_ref, const double *__restrict__ xd,
-                 const double *__restrict__ yd, const double *__restrict__ xdd,
-                 const double *__restrict__ ydd, const double *__restrict__ X0,
-                 double *__restrict__ X_hist, double *__restrict__ U_hist,
-                 double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
-                 double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
-                 double *__restrict__ X_final) {
-  track_run_body<false, false>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final);
-}
+#define TRACK_ARGS d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref, const double *__restrict__ y_ref,                    \
+                   const double *__restrict__ xd, const double *__restrict__ yd, const double *__restrict__ xdd,                        \
+                   const double *__restrict__ ydd, const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist, \
+                   double *__restrict__ Xr_hist, double *__restrict__ dX_hist, double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist, \
+                   double *__restrict__ X_final
+#define TRACK_PASS p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final
+__global__ void __launch_bounds__(64) track_run_kernel(TRACK_ARGS) { track_run_body<false, false>(TRACK_PASS); }
 
 // ------------------------------------------------------------------------------------
 // Single-evaluation entry points behind the reference's per-call helper methods.
@@ -838,76 +833,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 gvf_run_wind_kernel(GVF_ARGS, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max) {
   gvf_run_body<0, false, true>(GVF_PASS, &wf, t_start, iter_max);
 }
-
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 gvf_run_wind_gust_kernel(GVF_ARGS, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max, d2d_gust gust) {
   gvf_run_body<0, false, true, true>(GVF_PASS, &wf, t_start, iter_max, &gust);
 }
 
-__global__ void __launch_bounds__(64)
-track_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
-                      const double *__restrict__ y_ref, const double *__restrict__ xd,
-                      const double *__restrict__ yd, const double *__restrict__ xdd,
-                      const double *__restrict__ ydd, const double *__restrict__ X0,
-                      double *__restrict__ X_hist, double *__restrict__ U_hist,
-                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
-                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
-                      double *__restrict__ X_final, d2d_wind_field wf, double t_start,
-                      int32_t *__restrict__ iter_max) {
-  track_run_body<true, false>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final,
-                              &wf, t_start, nullptr, iter_max);
+__global__ void __launch_bounds__(64) track_run_wind_kernel(TRACK_ARGS, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max) {
+  track_run_body<true, false>(TRACK_PASS, &wf, t_start, nullptr, iter_max);
 }
-
 // d2d_sim_track_run_wind_at: a start time per drone
 __global__ void __launch_bounds__(64)
-track_run_wind_at_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
-                      const double *__restrict__ y_ref, const double *__restrict__ xd,
-                      const double *__restrict__ yd, const double *__restrict__ xdd,
-                      const double *__restrict__ ydd, const double *__restrict__ X0,
-                      double *__restrict__ X_hist, double *__restrict__ U_hist,
-                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
-                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
-                      double *__restrict__ X_final, d2d_wind_field wf, const double *__restrict__ t_at,
-                      int32_t *__restrict__ iter_max) {
-  track_run_body<true, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final,
-                             &wf, 0.0, t_at, iter_max);
+track_run_wind_at_kernel(TRACK_ARGS, d2d_wind_field wf, const double *__restrict__ t_at, int32_t *__restrict__ iter_max) {
+  track_run_body<true, true>(TRACK_PASS, &wf, 0.0, t_at, iter_max);
 }
-
-// the gust twins of the three tracking kernels (d2d_sim_track_run_gust: no field, a field, a field and a start time per drone)
-__global__ void __launch_bounds__(64)
-track_run_gust_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
-                      const double *__restrict__ y_ref, const double *__restrict__ xd,
-                      const double *__restrict__ yd, const double *__restrict__ xdd,
-                      const double *__restrict__ ydd, const double *__restrict__ X0,
-                      double *__restrict__ X_hist, double *__restrict__ U_hist,
-                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
-                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
-                      double *__restrict__ X_final, d2d_gust gust) {
-  track_run_body<false, false, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, nullptr, 0.0, nullptr, nullptr, &gust);
+// the gust twins of the three (d2d_sim_track_run_gust: no field, a field, a field and a start time per drone)
+__global__ void __launch_bounds__(64) track_run_gust_kernel(TRACK_ARGS, d2d_gust gust) {
+  track_run_body<false, false, true>(TRACK_PASS, nullptr, 0.0, nullptr, nullptr, &gust);
 }
-
 __global__ void __launch_bounds__(64)
-track_run_wind_gust_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
-                      const double *__restrict__ y_ref, const double *__restrict__ xd,
-                      const double *__restrict__ yd, const double *__restrict__ xdd,
-                      const double *__restrict__ ydd, const double *__restrict__ X0,
-                      double *__restrict__ X_hist, double *__restrict__ U_hist,
-                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
-                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
-                      double *__restrict__ X_final, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max, d2d_gust gust) {
-  track_run_body<true, false, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, &wf, t_start, nullptr, iter_max, &gust);
+track_run_wind_gust_kernel(TRACK_ARGS, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max, d2d_gust gust) {
+  track_run_body<true, false, true>(TRACK_PASS, &wf, t_start, nullptr, iter_max, &gust);
 }
-
 __global__ void __launch_bounds__(64)
-track_run_wind_at_gust_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ x_ref,
-                      const double *__restrict__ y_ref, const double *__restrict__ xd,
-                      const double *__restrict__ yd, const double *__restrict__ xdd,
-                      const double *__restrict__ ydd, const double *__restrict__ X0,
-                      double *__restrict__ X_hist, double *__restrict__ U_hist,
-                      double *__restrict__ Xr_hist, double *__restrict__ dX_hist,
-                      double *__restrict__ Yd_hist, double *__restrict__ Ydd_hist,
-                      double *__restrict__ X_final, d2d_wind_field wf, const double *__restrict__ t_at, int32_t *__restrict__ iter_max, d2d_gust gust) {
-  track_run_body<true, true, true>(p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, &wf, 0.0, t_at, iter_max, &gust);
+track_run_wind_at_gust_kernel(TRACK_ARGS, d2d_wind_field wf, const double *__restrict__ t_at, int32_t *__restrict__ iter_max, d2d_gust gust) {
+  track_run_body<true, true, true>(TRACK_PASS, &wf, 0.0, t_at, iter_max, &gust);
 }
 
 // d2d_gust_sample: the process alone, one lane per drone -- the statements of the loops in the same order
@@ -923,12 +872,8 @@ __global__ void __launch_bounds__(256) gust_sample_kernel(long N, int n_rows, d2
   gust_store_state(gust, gst, d, N);
 }
 
-__global__ void __launch_bounds__(64)
-dfff_run_wind_kernel(d2d_track_params p, GlMesh mesh, const double *__restrict__ Yref, const double *__restrict__ perts,
-                     const double *__restrict__ X0, double *__restrict__ X_hist, double *__restrict__ U_hist,
-                     double *__restrict__ Xr_hist, double *__restrict__ X_final, d2d_wind_field wf, double t_start,
-                     int32_t *__restrict__ iter_max) {
-  dfff_run_body<true>(p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, &wf, t_start, iter_max);
+__global__ void __launch_bounds__(64) dfff_run_wind_kernel(DFFF_ARGS, d2d_wind_field wf, double t_start, int32_t *__restrict__ iter_max) {
+  dfff_run_body<true>(DFFF_PASS, &wf, t_start, iter_max);
 }
 
 // ------------------------------------------------------------------------------------
@@ -983,12 +928,32 @@ static int check_gust(const d2d_gust *g, long N, long n_rows, const char *who) {
   return D2D_OK;
 }
 
-// f == NULL: the constant-wind loop of d2d_sim_gvf_run; else its wind twin (always the general kernel).  gust (with gusty): the
-// gust twin of either, always the general kernel too.
+// The optional inputs of a time loop (NlpExtra of nlp_kernels.hip is the model); LoopExtra{}: none, the constant-wind loop.
+struct LoopExtra {
+  const d2d_wind_field *f = nullptr;   // the field the plant flies, from the scalar start time ...
+  double t_start = 0.0;
+  const double *t_at = nullptr;        // ... or from every drone's own (device [n]: the tracking loop)
+  int32_t *iter_max = nullptr;         // device: receives the largest fixed-point sweep count of a field run
+  bool gusty = false;                  // the gust twin (its gust must not be null)
+  const d2d_gust *gust = nullptr;
+};
+
+static int check_extra(const LoopExtra &ex, long N, long n_rows, const char *who) {
+  if (ex.f) {
+    if (int rc = check_wind(ex.f, who)) return rc;
+  }
+  if (ex.gusty) {
+    if (int rc = check_gust(ex.gust, N, n_rows, who)) return rc;
+  }
+  return D2D_OK;
+}
+
+// ex.f == NULL: the constant-wind loop of d2d_sim_gvf_run; else its wind twin (always the general kernel).  ex.gusty: the gust twin
+// of either, always the general kernel too.
 static int gvf_run_impl(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
                         const double *Bmat, const double *z_des, const double *X0f, double *X_hist, double *U_hist, double *Rr_hist,
-                        double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const d2d_wind_field *f,
-                        double t_start, int32_t *iter_max, const char *who, bool gusty = false, const d2d_gust *gust = nullptr) {
+                        double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const char *who,
+                        const LoopExtra &ex = LoopExtra{}) {
   D2D_REQUIRE(ctx && p && X0 && centres && radius && X_final, "%s: null argument", who);
   D2D_REQUIRE(p->use_stop >= 0 && p->use_stop <= 2 && p->stop_hold >= 0, "%s: use_stop in 0..2, stop_hold >= 0", who);
   D2D_REQUIRE(p->n_ac >= 1 && p->n_ac <= 64, "%s: n_ac=%d not in 1..64", who, p->n_ac);
@@ -997,12 +962,7 @@ static int gvf_run_impl(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
   D2D_REQUIRE(p->use_stop != 1 || X0f, "%s: use_stop = 1 needs X0f", who);
   D2D_REQUIRE(p->use_stop != 2 || p->n_ac >= 2, "%s: the phase-error rule needs at least two aircraft", who);
   D2D_REQUIRE(p->dt > 0 && p->tau_phi > 0 && p->tau_v > 0, "%s: dt, tau_phi, tau_v must be > 0", who);
-  if (f) {
-    if (int rc = check_wind(f, who)) return rc;
-  }
-  if (gusty) {
-    if (int rc = check_gust(gust, (long)p->n_form * p->n_ac, p->n_rows, who)) return rc;
-  }
+  if (int rc = check_extra(ex, (long)p->n_form * p->n_ac, p->n_rows, who)) return rc;
   const int n_ac = p->n_ac, nm = n_ac - 1;
   const size_t nb = (size_t)n_ac * nm + nm;
   if (int rc = upload_Bz(ctx, n_ac, Bmat, z_des)) return rc;
@@ -1012,22 +972,17 @@ static int gvf_run_impl(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
   const int blocks = (p->n_form + fpb - 1) / fpb;
   const size_t lds = (512 + 128 + nb + 8) * sizeof(double);
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
-#define GVF_LAUNCH(KERNEL)                                                                                             \
+  const d2d_wind_field *f = ex.f;
+#define GVF_LAUNCH(KERNEL, ...)                                                                                                \
   hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius, ctx->Bmat_dev, \
-                     X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row)
-  if (gusty) {
-    if (f) {
-      if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
-      hipLaunchKernelGGL(gvf_run_wind_gust_kernel, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius,
-                         ctx->Bmat_dev, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row, *f, t_start, iter_max, *gust);
-    } else {
-      hipLaunchKernelGGL(gvf_run_gust_kernel, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius,
-                         ctx->Bmat_dev, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row, *gust);
-    }
+                     X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row, ##__VA_ARGS__)
+  if (f && ex.iter_max) D2D_CHECK_HIP(hipMemsetAsync(ex.iter_max, 0, sizeof(int32_t), ctx->stream));
+  if (ex.gusty && f) {
+    GVF_LAUNCH(gvf_run_wind_gust_kernel, *f, ex.t_start, ex.iter_max, *ex.gust);
+  } else if (ex.gusty) {
+    GVF_LAUNCH(gvf_run_gust_kernel, *ex.gust);
   } else if (f) {
-    if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(gvf_run_wind_kernel, dim3(blocks), dim3(threads), lds, ctx->stream, *p, mesh, fpb, X0, centres, radius,
-                       ctx->Bmat_dev, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row, *f, t_start, iter_max);
+    GVF_LAUNCH(gvf_run_wind_kernel, *f, ex.t_start, ex.iter_max);
   } else if (n_ac == 1 || n_ac == 2 || n_ac == 4) {
     // formations inside a DPP quad: no LDS exchange, no barrier in the step; a launch of at most one wave per SIMD gets the
     // instantiation that may use the whole register file
@@ -1050,7 +1005,7 @@ int d2d_sim_gvf_run(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0,
                     const double *z_des, const double *X0f, double *X_hist, double *U_hist,
                     double *Rr_hist, double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row) {
   return gvf_run_impl(ctx, p, X0, centres, radius, Bmat, z_des, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row,
-                      nullptr, 0.0, nullptr, "d2d_sim_gvf_run");
+                      "d2d_sim_gvf_run");
 }
 
 int d2d_sim_gvf_run_wind(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
@@ -1059,7 +1014,7 @@ int d2d_sim_gvf_run_wind(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0
                          double t_start, int32_t *iter_max) {
   D2D_REQUIRE(f, "d2d_sim_gvf_run_wind: null wind field");
   return gvf_run_impl(ctx, p, X0, centres, radius, Bmat, z_des, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row,
-                      f, t_start, iter_max, "d2d_sim_gvf_run_wind");
+                      "d2d_sim_gvf_run_wind", LoopExtra{f, t_start, nullptr, iter_max});
 }
 
 int d2d_sim_gvf_run_gust(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0, const double *centres, const double *radius,
@@ -1067,7 +1022,7 @@ int d2d_sim_gvf_run_gust(d2d_ctx *ctx, const d2d_gvf_params *p, const double *X0
                          double *eth_hist, double *X_final, int32_t *stop_row, int32_t *conv_row, const d2d_wind_field *f,
                          double t_start, int32_t *iter_max, const d2d_gust *gust) {
   return gvf_run_impl(ctx, p, X0, centres, radius, Bmat, z_des, X0f, X_hist, U_hist, Rr_hist, eth_hist, X_final, stop_row, conv_row,
-                      f, t_start, iter_max, "d2d_sim_gvf_run_gust", true, gust);
+                      "d2d_sim_gvf_run_gust", LoopExtra{f, t_start, nullptr, iter_max, true, gust});
 }
 
 int d2d_gust_sample(d2d_ctx *ctx, int64_t N, int n_rows, const d2d_gust *gust) {
@@ -1106,51 +1061,43 @@ int d2d_dfff_eval(d2d_ctx *ctx, const d2d_track_params *p, const double *X, cons
 }
 
 static int dfff_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts, const double *X0,
-                         double *X_hist, double *U_hist, double *Xr_hist, double *X_final, const d2d_wind_field *f, double t_start,
-                         int32_t *iter_max, const char *who) {
+                         double *X_hist, double *U_hist, double *Xr_hist, double *X_final, const char *who,
+                         const LoopExtra &ex = LoopExtra{}) {
   D2D_REQUIRE(ctx && p && Yref && X0, "%s: null argument", who);
   if (int rc = check_track(p, who)) return rc;
-  if (f) {
-    if (int rc = check_wind(f, who)) return rc;
-  }
+  if (int rc = check_extra(ex, p->n, p->n_rows, who)) return rc;
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
   const dim3 grid((p->n + 63) / 64), block(64);          // a wavefront per workgroup
-  if (f) {
-    if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(dfff_run_wind_kernel, grid, block, 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, *f,
-                       t_start, iter_max);
-  } else {
-    hipLaunchKernelGGL(dfff_run_kernel, grid, block, 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final);
-  }
+#define DFFF_LAUNCH(KERNEL, ...)                                                                                              \
+  hipLaunchKernelGGL(KERNEL, grid, block, 0, ctx->stream, *p, mesh, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, ##__VA_ARGS__)
+  if (ex.f && ex.iter_max) D2D_CHECK_HIP(hipMemsetAsync(ex.iter_max, 0, sizeof(int32_t), ctx->stream));
+  if (ex.f) DFFF_LAUNCH(dfff_run_wind_kernel, *ex.f, ex.t_start, ex.iter_max);
+  else DFFF_LAUNCH(dfff_run_kernel);
+#undef DFFF_LAUNCH
   D2D_LAUNCH_CHECK();
   return D2D_OK;
 }
 
 int d2d_sim_dfff_run(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts,
                      const double *X0, double *X_hist, double *U_hist, double *Xr_hist, double *X_final) {
-  return dfff_run_impl(ctx, p, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, nullptr, 0.0, nullptr, "d2d_sim_dfff_run");
+  return dfff_run_impl(ctx, p, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, "d2d_sim_dfff_run");
 }
 
 int d2d_sim_dfff_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double *Yref, const double *perts, const double *X0,
                           double *X_hist, double *U_hist, double *Xr_hist, double *X_final, const d2d_wind_field *f, double t_start,
                           int32_t *iter_max) {
   D2D_REQUIRE(f, "d2d_sim_dfff_run_wind: null wind field");
-  return dfff_run_impl(ctx, p, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, f, t_start, iter_max, "d2d_sim_dfff_run_wind");
+  return dfff_run_impl(ctx, p, Yref, perts, X0, X_hist, U_hist, Xr_hist, X_final, "d2d_sim_dfff_run_wind",
+                       LoopExtra{f, t_start, nullptr, iter_max});
 }
 
 static int track_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
                           double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
-                          double *X_final, const d2d_wind_field *f, double t_start, int32_t *iter_max, const char *who,
-                          const double *t_at = nullptr, bool gusty = false, const d2d_gust *gust = nullptr) {
+                          double *X_final, const char *who, const LoopExtra &ex = LoopExtra{}) {
   D2D_REQUIRE(ctx && p && x_ref && y_ref && X0, "%s: null argument", who);
   if (int rc = check_track(p, who)) return rc;
   D2D_REQUIRE(p->n_rows >= 3, "%s: n_rows must be >= 3 (second-order edge differences)", who);
-  if (f) {
-    if (int rc = check_wind(f, who)) return rc;
-  }
-  if (gusty) {
-    if (int rc = check_gust(gust, p->n, p->n_rows, who)) return rc;
-  }
+  if (int rc = check_extra(ex, p->n, p->n_rows, who)) return rc;
   const size_t plane = (size_t)p->n_rows * p->n * sizeof(double);
   double *deriv = nullptr;
   D2D_CHECK_HIP(hipMallocAsync(reinterpret_cast<void **>(&deriv), 4 * plane, ctx->stream));
@@ -1165,29 +1112,22 @@ static int track_run_impl(d2d_ctx *ctx, const d2d_track_params *p, const double 
   D2D_LAUNCH_CHECK();
   const GlMesh mesh = make_mesh(p->dt, p->tau_phi, p->tau_v);
   const dim3 grid((p->n + 63) / 64), block(64);          // a wavefront per workgroup
-  if (gusty) {
-    if (f && iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
-    if (f && t_at)
-      hipLaunchKernelGGL(track_run_wind_at_gust_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist,
-                         U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_at, iter_max, *gust);
-    else if (f)
-      hipLaunchKernelGGL(track_run_wind_gust_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist,
-                         U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, 0.0, iter_max, *gust);
-    else
-      hipLaunchKernelGGL(track_run_gust_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist,
-                         Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *gust);
+  const d2d_wind_field *f = ex.f;
+#define TRACK_LAUNCH(KERNEL, ...)                                                                                               \
+  hipLaunchKernelGGL(KERNEL, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist, \
+                     dX_hist, Yd_hist, Ydd_hist, X_final, ##__VA_ARGS__)
+  if (f && ex.iter_max) D2D_CHECK_HIP(hipMemsetAsync(ex.iter_max, 0, sizeof(int32_t), ctx->stream));
+  if (ex.gusty) {
+    if (f && ex.t_at) TRACK_LAUNCH(track_run_wind_at_gust_kernel, *f, ex.t_at, ex.iter_max, *ex.gust);
+    else if (f) TRACK_LAUNCH(track_run_wind_gust_kernel, *f, ex.t_start, ex.iter_max, *ex.gust);
+    else TRACK_LAUNCH(track_run_gust_kernel, *ex.gust);
   } else if (f) {
-    if (iter_max) D2D_CHECK_HIP(hipMemsetAsync(iter_max, 0, sizeof(int32_t), ctx->stream));
-    if (t_at)
-      hipLaunchKernelGGL(track_run_wind_at_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist,
-                         Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_at, iter_max);
-    else
-      hipLaunchKernelGGL(track_run_wind_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist,
-                         Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, *f, t_start, iter_max);
+    if (ex.t_at) TRACK_LAUNCH(track_run_wind_at_kernel, *f, ex.t_at, ex.iter_max);
+    else TRACK_LAUNCH(track_run_wind_kernel, *f, ex.t_start, ex.iter_max);
   } else {
-    hipLaunchKernelGGL(track_run_kernel, grid, block, 0, ctx->stream, *p, mesh, x_ref, y_ref, xd, yd, xdd, ydd, X0, X_hist, U_hist, Xr_hist,
-                       dX_hist, Yd_hist, Ydd_hist, X_final);
+    TRACK_LAUNCH(track_run_kernel);
   }
+#undef TRACK_LAUNCH
   D2D_LAUNCH_CHECK();
   D2D_CHECK_HIP(hipFreeAsync(deriv, ctx->stream));
   return D2D_OK;
@@ -1197,16 +1137,15 @@ int d2d_sim_track_run(d2d_ctx *ctx, const d2d_track_params *p, const double *x_r
                       const double *y_ref, const double *X0, double *X_hist, double *U_hist,
                       double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
                       double *X_final) {
-  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, nullptr, 0.0, nullptr,
-                        "d2d_sim_track_run");
+  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, "d2d_sim_track_run");
 }
 
 int d2d_sim_track_run_wind(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
                            double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
                            double *X_final, const d2d_wind_field *f, double t_start, int32_t *iter_max) {
   D2D_REQUIRE(f, "d2d_sim_track_run_wind: null wind field");
-  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, f, t_start, iter_max,
-                        "d2d_sim_track_run_wind");
+  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, "d2d_sim_track_run_wind",
+                        LoopExtra{f, t_start, nullptr, iter_max});
 }
 
 int d2d_sim_track_run_wind_at(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
@@ -1214,15 +1153,15 @@ int d2d_sim_track_run_wind_at(d2d_ctx *ctx, const d2d_track_params *p, const dou
                               double *X_final, const d2d_wind_field *f, const double *t_start, int32_t *iter_max) {
   D2D_REQUIRE(f, "d2d_sim_track_run_wind_at: null wind field");
   D2D_REQUIRE(t_start, "d2d_sim_track_run_wind_at: null t_start (a device array [n]: one start time per drone)");
-  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, f, 0.0, iter_max,
-                        "d2d_sim_track_run_wind_at", t_start);
+  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, "d2d_sim_track_run_wind_at",
+                        LoopExtra{f, 0.0, t_start, iter_max});
 }
 
 int d2d_sim_track_run_gust(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref, const double *X0,
                            double *X_hist, double *U_hist, double *Xr_hist, double *dX_hist, double *Yd_hist, double *Ydd_hist,
                            double *X_final, const d2d_wind_field *f, const double *t_start, int32_t *iter_max, const d2d_gust *gust) {
-  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, f, 0.0, iter_max,
-                        "d2d_sim_track_run_gust", t_start, true, gust);
+  return track_run_impl(ctx, p, x_ref, y_ref, X0, X_hist, U_hist, Xr_hist, dX_hist, Yd_hist, Ydd_hist, X_final, "d2d_sim_track_run_gust",
+                        LoopExtra{f, 0.0, t_start, iter_max, true, gust});
 }
 
 int d2d_traj_sample(d2d_ctx *ctx, int n, int T, double t_start, double dt, const double *desc, double *Yref) {

@@ -136,6 +136,15 @@ def pair_masks(pairs, n):
     return masks
 
 
+def default_pair_masks(dsc, n_ac, on):
+    """The reference's pair (0, 1) as partner sets, for the entries that read them (d2d_nlp_solve_groups_moving / _via): D2D_SC_PMASK
+    of the scenario rows dsc [R * n_ac][SCEN_STRIDE] (in place) becomes 0b10 on aircraft 0 and 0b01 on aircraft 1 of every scenario
+    where `on` holds (True, or a boolean tensor [R]) and 0 where it does not."""
+    from d2dhip import SC_PMASK
+    dsc[0::n_ac, SC_PMASK] = on * 2.0
+    dsc[1::n_ac, SC_PMASK] = on * 1.0
+
+
 class CostCollision:
     """Gaussian proximity penalty between aircraft 0 and 1 (src/d2d/multiopty_utils.py:120-153).  pairs: None -- that pair, as in
     the reference; 'all' -- every unordered pair of the planner's aircraft; an iterable of (i, j) -- those pairs.  The same term

@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from .plan import nlp_plan       # noqa: F401  (the planners' choice among the nlp_solve* methods of a Context)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('D2D_LIB') or os.path.join(os.path.dirname(_HERE), 'lib', 'libd2dhip.so')   # D2D_LIB: A/B builds
 
@@ -402,10 +404,6 @@ class Context:
         _check(self.lib.d2d_step_wind(self.h, n, _ptr(X), _ptr(U), float(t), C.byref(f), tau_phi, tau_v, dt, _ptr(out), _ptr(iter_max)))
         return out
 
-    def _iter_max(self):
-        torch = _torch()
-        return torch.zeros(1, dtype=torch.int32, device=self.device)
-
     def _gust_c(self, gust, dt, n_ac, N, phase, state, stream_base=0, step_base=0):
         """The d2d_gust of `gust` -- a GustC (a COPY of it, state_in included: the caller's struct is not written; its state_out and
         g_hist are replaced by the method's own outputs) or a model with lower(dt, n_ac, phase, stream_base) (d2d.wind.GustModel) --
@@ -418,6 +416,27 @@ class Context:
         g = gust.lower(float(dt), int(n_ac), int(phase), int(stream_base), int(step_base))
         g.state_in = None if state is None else state.data_ptr()
         return g
+
+    def _plant_extras(self, out, N, n_rec, record, wind, gust=None, gust_kw=(), t_start=None):
+        """The plant's optional inputs as gvf_run, track_run and dfff_run share them -> (f, t_at, g), each None when absent.  g: the GustC
+        of `gust` (_gust_c with gust_kw = (dt, n_ac, phase, state, stream_base)) writing out['gust_state'] [4][N] and, with 'g' in record,
+        out['g'] [n_rec][2][N]; f: the WindFieldC of `wind`, with out['iter_max']; both outputs are made unless `out` brought them.
+        t_at: track_run's t_start when it is a device tensor [N], one start time per drone (that needs a field); None for a float."""
+        g = None
+        if gust is not None:
+            g = self._gust_c(gust, *gust_kw[:2], N, *gust_kw[2:])
+            if out.get('gust_state') is None:
+                out['gust_state'] = self.empty(4, N)
+            if 'g' in record and out.get('g') is None:
+                out['g'] = self.zeros(n_rec, 2, N)
+            g.state_out, g.g_hist = out['gust_state'].data_ptr(), None if out.get('g') is None else out['g'].data_ptr()
+        f = None if wind is None else _wind_c(self, wind)
+        if f is not None and out.get('iter_max') is None:
+            out['iter_max'] = self.zeros(1, dtype=_torch().int32)
+        t_at = t_start if hasattr(t_start, 'data_ptr') else None
+        assert t_at is None or f is not None, 'per-drone start times (a tensor) need a wind field: without one the time is not read'
+        assert t_at is None or (t_at.is_contiguous() and tuple(t_at.shape) == (N,) and t_at.dtype == _torch().float64 and t_at.device == self.device)
+        return f, t_at, g
 
     def gust_sample(self, gust, N, n_rows, dt, n_ac=1, phase=0, state=None, stream_base=0, step_base=0, record=True):
         """The gust process alone (d2d_gust_sample): gust a d2d.wind.GustModel, N drones in formations of n_ac, rows 0 .. n_rows - 1
@@ -474,22 +493,12 @@ class Context:
         args = (self.h, C.byref(p), _ptr(X0), _ptr(centres), _ptr(radius), _hptr(B), _hptr(z_des), _ptr(X0f if use_stop == 1 else None),
                 _ptr(out['X']), _ptr(out['U']), _ptr(out['Rr']), _ptr(out['eth']), _ptr(out['X_final']), _ptr(out['stop_row']),
                 _ptr(out.get('conv_row')))
-        if gust is not None:
-            g = self._gust_c(gust, dt, n_ac, N, gust_phase, gust_state, gust_stream_base)
-            if out.get('gust_state') is None:
-                out['gust_state'] = self.empty(4, N)
-            if 'g' in record and out.get('g') is None:
-                out['g'] = self.zeros(n_rec, 2, N)
-            g.state_out, g.g_hist = out['gust_state'].data_ptr(), None if out.get('g') is None else out['g'].data_ptr()
-            f = None if wind is None else _wind_c(self, wind)
-            if f is not None:
-                out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
+        f, _, g = self._plant_extras(out, N, n_rec, record, wind, gust, (dt, n_ac, gust_phase, gust_state, gust_stream_base))
+        if g is not None:
             _check(self.lib.d2d_sim_gvf_run_gust(*args, None if f is None else C.byref(f), float(t_start), _ptr(out.get('iter_max')), C.byref(g)))
-        elif wind is None:
+        elif f is None:
             _check(self.lib.d2d_sim_gvf_run(*args))
         else:
-            f = _wind_c(self, wind)
-            out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
             _check(self.lib.d2d_sim_gvf_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
 
@@ -575,11 +584,10 @@ class Context:
             out = {k: (self.zeros(T, c, n) if k in record else None) for k, c in (('X', 5), ('U', 2), ('Xr', 5))}
             out['X_final'] = self.empty(5, n)
         args = (self.h, C.byref(p), _ptr(Yref), _ptr(perts), _ptr(X0), _ptr(out['X']), _ptr(out['U']), _ptr(out['Xr']), _ptr(out['X_final']))
-        if wind is None:
+        f, _, _ = self._plant_extras(out, n, T, record, wind)
+        if f is None:
             _check(self.lib.d2d_sim_dfff_run(*args))
         else:
-            f = _wind_c(self, wind)
-            out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
             _check(self.lib.d2d_sim_dfff_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
 
@@ -880,36 +888,17 @@ class Context:
             assert out['X_final'].shape == (5, n) and all(out[k] is None or out[k].shape[0] == T for k in ('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'))
         args = (self.h, C.byref(p), _ptr(x_ref), _ptr(y_ref), _ptr(X0), _ptr(out['X']), _ptr(out['U']), _ptr(out['Xr']), _ptr(out['dX']),
                 _ptr(out['Yd']), _ptr(out['Ydd']), _ptr(out['X_final']))
-        if gust is not None:
-            g = self._gust_c(gust, dt, gust_n_ac, n, gust_phase, gust_state, gust_stream_base)
-            if out.get('gust_state') is None:
-                out['gust_state'] = self.empty(4, n)
-            if 'g' in record and out.get('g') is None:
-                out['g'] = self.zeros(T, 2, n)
-            g.state_out, g.g_hist = out['gust_state'].data_ptr(), None if out.get('g') is None else out['g'].data_ptr()
-            f = None if wind is None else _wind_c(self, wind)
-            t_at = None
-            if f is None:
-                assert not hasattr(t_start, 'data_ptr'), 'per-drone start times (a tensor) need a wind field: without one the time is not read'
-            else:
-                out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
-                if hasattr(t_start, 'data_ptr'):
-                    t_at = t_start
-                    assert t_at.is_contiguous() and tuple(t_at.shape) == (n,) and t_at.dtype == _torch().float64 and t_at.device == x_ref.device
-                elif float(t_start) != 0.0:                     # (the entry point takes the start times per drone, or none: all 0)
-                    t_at = _torch().full((n,), float(t_start), dtype=_torch().float64, device=self.device)
+        f, t_at, g = self._plant_extras(out, n, T, record, wind, gust, (dt, gust_n_ac, gust_phase, gust_state, gust_stream_base), t_start)
+        if g is not None:
+            if f is not None and t_at is None and float(t_start) != 0.0:     # (the entry point takes the start times per drone, or none: all 0)
+                t_at = _torch().full((n,), float(t_start), dtype=_torch().float64, device=self.device)
             _check(self.lib.d2d_sim_track_run_gust(*args, None if f is None else C.byref(f), _ptr(t_at), _ptr(out.get('iter_max')), C.byref(g)))
-        elif wind is None:
-            assert not hasattr(t_start, 'data_ptr'), 'per-drone start times (a tensor) need a wind field: without one the time is not read'
+        elif f is None:
             _check(self.lib.d2d_sim_track_run(*args))
+        elif t_at is not None:
+            _check(self.lib.d2d_sim_track_run_wind_at(*args, C.byref(f), _ptr(t_at), _ptr(out['iter_max'])))
         else:
-            f = _wind_c(self, wind)
-            out['iter_max'] = out.get('iter_max') if out.get('iter_max') is not None else self._iter_max()
-            if hasattr(t_start, 'data_ptr'):
-                assert t_start.is_contiguous() and tuple(t_start.shape) == (n,) and t_start.dtype == _torch().float64 and t_start.device == x_ref.device
-                _check(self.lib.d2d_sim_track_run_wind_at(*args, C.byref(f), _ptr(t_start), _ptr(out['iter_max'])))
-            else:
-                _check(self.lib.d2d_sim_track_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
+            _check(self.lib.d2d_sim_track_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
 
 

@@ -1,0 +1,27 @@
+"""Which collocation entry a planner calls: policy above the binding, no ctypes (d2dhip.nlp_plan)."""
+
+
+def nlp_plan(ctx, scen, W, h, *, n_ac=None, field=None, t_start=None, knots=None, disc=None, via=None, free_rows=None, pairs=False, **opts):
+    """The planners' one rule for choosing among the nlp_solve* methods of `ctx` (a Context, or any object that has them) -- the first
+    optional input that is given names the entry, which also takes the inputs below it in its column (free_rows: none):
+      n_ac given, R scenarios of n_ac aircraft:  via -> _groups_via, knots -> _groups_moving, pairs -> _groups_pairs, field -> _groups_wind,
+                                                 none -> nlp_solve_groups;
+      n_ac None, B problems handed out:          free_rows -> _free, via -> _via, knots -> _moving, field -> _wind, none -> nlp_solve.
+    opts: the entry's own keywords (solver options, bounds, max_sweeps ...).  Returns the entry's dictionary plus `entry`, its name.
+    (nlp_solve_model is not chosen here: its objective model is another problem, not an optional input of a plan -- DESIGN.md 5.16.)"""
+    wind = dict(field=field, t_start=t_start)
+    mov = dict(knots=knots, disc=disc, **wind)
+    if n_ac is not None:
+        entry, kw = (('nlp_solve_groups_via', dict(via=via, **mov)) if via is not None else
+                     ('nlp_solve_groups_moving', mov) if knots is not None else
+                     ('nlp_solve_groups_pairs', wind) if pairs else
+                     ('nlp_solve_groups_wind', wind) if field is not None else ('nlp_solve_groups', {}))
+        kw['n_ac'] = n_ac
+    else:
+        entry, kw = (('nlp_solve_free', dict(free_rows=free_rows)) if free_rows is not None else
+                     ('nlp_solve_via', dict(via=via, **mov)) if via is not None else
+                     ('nlp_solve_moving', mov) if knots is not None else
+                     ('nlp_solve_wind', dict(field=field, t_start=0.0 if t_start is None else t_start)) if field is not None else ('nlp_solve', {}))
+    out = getattr(ctx, entry)(scen, W, h, **kw, **opts)
+    out['entry'] = entry
+    return out

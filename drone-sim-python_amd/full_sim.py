@@ -17,6 +17,7 @@ import numpy as np
 
 import d2dhip
 import d2d.dynamic as ddyn
+import d2d.multiopty_utils as d2mou
 from d2d.wind import plant_gust, plant_wind
 
 KE, KD, KR = 0.0004, 25, 20            # src/11_full_sim_case1.py:108-110
@@ -258,30 +259,16 @@ def _moving_tables(ctx, moving, n_scen):
     return ctx.dev(np.stack([t[0] for t in tabs])), ctx.dev(np.stack([t[1] for t in tabs]))
 
 
-def _plan_batch_via(ctx, scen_rows, dsc, W, N, h, n_ac, fld, t_start, moving, via, solve_kw):
-    """plan_batch's path through timed waypoints: the table of every problem on its scenario's clock, then d2d_nlp_solve_groups_via."""
+def _via_table(dsc, n_ac, N, h, t_start, via):
+    """plan_batch's timed waypoints: the table (B, n_via, 5) of every problem on its scenario's clock."""
     import d2d.opty_utils as d2ou
     B = dsc.shape[0]
-    R = B // n_ac
     via = [list(v or []) for v in via]
     if len(via) != B:
         raise ValueError(f'via: one waypoint list per problem ({B})')
-    ts = t_start.cpu().numpy() if hasattr(t_start, 'cpu') else np.full(R, 0.0 if t_start is None else float(t_start))
+    ts = t_start.cpu().numpy() if hasattr(t_start, 'cpu') else np.full(B // n_ac, 0.0 if t_start is None else float(t_start))
     n_via = max(1, max(len(v) for v in via))
-    table = np.stack([d2ou.lower_waypoints(v, float(ts[b // n_ac]), h, N, n_via) for b, v in enumerate(via)])
-    if n_ac >= 2 and not _rows_select_pairs(scen_rows, n_ac):       # the reference's pair (0, 1) as partner sets
-        on = (dsc[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc[1::n_ac, d2dhip.SC_KCOL] > 0)
-        dsc[0::n_ac, d2dhip.SC_PMASK] = on * 2.0
-        dsc[1::n_ac, d2dhip.SC_PMASK] = on * 1.0
-    knots, disc = _moving_tables(ctx, moving, R) if moving else (None, None)
-    if fld is None and not moving:
-        t_start = None
-    dvia = ctx.dev(table)
-    out = ctx.nlp_solve_groups_via(dsc, W, h, n_ac, dvia, knots, disc, fld, t_start, **solve_kw)
-    ctx.sync()
-    Wh = W.cpu().numpy()
-    out.update(via=dvia, waypoint_error=max(d2ou.waypoint_error(table[b], Wh[b]) for b in range(B)))
-    return out
+    return np.stack([d2ou.lower_waypoints(v, float(ts[b // n_ac]), h, N, n_via) for b, v in enumerate(via)])
 
 
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
@@ -332,24 +319,32 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
         W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
         assert W.shape == (dsc.shape[0], 5, K) and h is not None
+        h, n_ac = float(h), int(n_ac)
         if free_time is not None:
             B = dsc.shape[0]
             fr = np.zeros((B, 4))
             fr[:, :2] = np.broadcast_to(np.asarray(free_time, dtype=np.float64), (B, 2))
             fr[:, 2] = np.broadcast_to(np.asarray(kdur, dtype=np.float64), (B,))
-            out = ctx.nlp_solve_free(dsc, W, float(h), ctx.dev(fr), **solve_kw)
+            out = d2dhip.nlp_plan(ctx, dsc, W, h, free_rows=ctx.dev(fr), **solve_kw)
             out['free_rows'] = fr
-        elif via is not None:
-            out = _plan_batch_via(ctx, scen_rows, dsc, W, K, float(h), int(n_ac), fld, t_start, moving, via, solve_kw)
-        elif moving:
-            knots, disc = _moving_tables(ctx, moving, dsc.shape[0] // int(n_ac))
-            out = ctx.nlp_solve_groups_moving(dsc, W, float(h), int(n_ac), knots, disc, fld, t_start, **solve_kw)
-        elif _rows_select_pairs(scen_rows, int(n_ac)):      # partner sets other than the reference's pair (0, 1)
-            out = ctx.nlp_solve_groups_pairs(dsc, W, float(h), int(n_ac), fld, t_start, **solve_kw)
-        elif fld is None:
-            out = ctx.nlp_solve_groups(dsc, W, float(h), int(n_ac), **solve_kw)
-        else:
-            out = ctx.nlp_solve_groups_wind(dsc, W, float(h), int(n_ac), fld, t_start, **solve_kw)
+        else:                                               # always the group entries (the docstring's note on via= with n_ac = 1)
+            pairs = _rows_select_pairs(scen_rows, n_ac)         # partner sets other than the reference's pair (0, 1)
+            ex = {}
+            if via is not None:
+                table = _via_table(dsc, n_ac, K, h, t_start, via)
+                if n_ac >= 2 and not pairs:                     # the reference's pair (0, 1) as partner sets
+                    d2mou.default_pair_masks(dsc, n_ac, (dsc[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc[1::n_ac, d2dhip.SC_KCOL] > 0))
+                if fld is None and not moving:
+                    t_start = None
+                ex['via'] = ctx.dev(table)
+            if moving:
+                ex['knots'], ex['disc'] = _moving_tables(ctx, moving, dsc.shape[0] // n_ac)
+            out = d2dhip.nlp_plan(ctx, dsc, W, h, n_ac=n_ac, field=fld, t_start=t_start, pairs=pairs, **ex, **solve_kw)
+            if via is not None:
+                import d2d.opty_utils as d2ou
+                ctx.sync()
+                Wh = W.cpu().numpy()
+                out.update(via=ex['via'], waypoint_error=max(d2ou.waypoint_error(table[b], Wh[b]) for b in range(len(Wh))))
         out.update(W=W, scen=dsc)
         return out
     plan = sop.get_plan(K, duration, obj_scale_over_n)
@@ -455,33 +450,23 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     kw = dict(w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v)
     kw2 = {}
     pairs = mop.scenario_pairs(scen, n_ac)                          # None: the reference's pair (0, 1), the chain as it was
-    if moving:                                                      # the fit was the guess: the collocation problem around the discs from t2
+    if moving or F is not None or pairs is not None:
+        # the fit was the guess, the collocation problem decides: around the discs from t2, in -F from t2, over a cost's own pairs
         Fp = None if F is None else F.negated()
         Xs = Xs.contiguous().clone()
-        knots, disc = _moving_tables(ctx, moving, n_form)
-        sol = ctx.nlp_solve_groups_moving(dsc, Xs, float(dt2), n_ac, knots, disc, Fp, t2)
+        knots, disc = _moving_tables(ctx, moving, n_form) if moving else (None, None)
+        sol = d2dhip.nlp_plan(ctx, dsc, Xs, float(dt2), n_ac=n_ac, knots=knots, disc=disc, field=Fp, t_start=t2 if (moving or F is not None) else None,
+                              pairs=pairs is not None)
         pl.update(cost_fit=cost, cost=sol['cost'], Xs=Xs, W=Xs, feas=sol['feas'], status=sol['status'], iters=sol['iters'],
-                  sweeps=sol['sweeps'], moved=sol['moved'], t_start=t2, mov_work=sol['mov_work'], moving=(knots, disc))
+                  sweeps=sol['sweeps'], moved=sol['moved'])
+        if moving or F is not None:
+            pl['t_start'] = t2
+        if moving:
+            pl.update(mov_work=sol['mov_work'], moving=(knots, disc))
         if F is not None:
             pl['field'] = Fp
             kw['wind'] = F
             kw2 = dict(t_start=t2d)
-    elif F is not None:                                             # the fit was the guess: the collocation problem in -F from t2
-        Fp = F.negated()
-        Xs = Xs.contiguous().clone()
-        if pairs is None:
-            sol = ctx.nlp_solve_groups_wind(dsc, Xs, float(dt2), n_ac, Fp, t2)
-        else:
-            sol = ctx.nlp_solve_groups_pairs(dsc, Xs, float(dt2), n_ac, Fp, t2)
-        pl.update(cost_fit=cost, cost=sol['cost'], Xs=Xs, W=Xs, feas=sol['feas'], status=sol['status'], iters=sol['iters'],
-                  sweeps=sol['sweeps'], moved=sol['moved'], t_start=t2, field=Fp)
-        kw['wind'] = F
-        kw2 = dict(t_start=t2d)
-    elif pairs is not None:                                         # a cost with its own pairs: the collocation problem decides here too
-        Xs = Xs.contiguous().clone()
-        sol = ctx.nlp_solve_groups_pairs(dsc, Xs, float(dt2), n_ac)
-        pl.update(cost_fit=cost, cost=sol['cost'], Xs=Xs, W=Xs, feas=sol['feas'], status=sol['status'], iters=sol['iters'],
-                  sweeps=sol['sweeps'], moved=sol['moved'])
     if pairs is not None:
         pl['pairs'] = pairs
     x_ref2 = Xs[:, 0, :].t().contiguous(); y_ref2 = Xs[:, 1, :].t().contiguous()     # dev [K][N]

@@ -255,6 +255,24 @@ class Problem:
         # length of a Newton step, csrc/nlp_kernels.hip nlp_assemble / oracle/nlp.py)
         return rows, coupled
 
+    def _solver_kw(self):
+        """The solver options of every path, from IPOPT's.  Its max_iter counts Newton steps; here they are grouped as outer (multiplier /
+        barrier updates) x inner (<= D2D_NLP_INNER_MAX): between 720 and 3600 steps in all, as in rounds 2-3 (12 .. 60 batches of 60).
+        Its `tol` (the reference sets 1e-5 .. 1e-8) bounds its scaled KKT error.  This backend's own tolerances -- barrier KKT error of the
+        last inner problem 1e-7, collocation residual 1e-9 -- are at least as tight as every value the reference uses, so a looser `tol`
+        changes nothing; a tighter one tightens them with it."""
+        _im = d2dhip.NLP_INNER_MAX
+        tol = float(self.options.get('tol', 1e-8))
+        return dict(inner_max=_im, outer_max=int(min(max(self.options.get('max_iter', 3000) // _im, 720 // _im), 3600 // _im)),
+                    opt_tol=min(tol, 1e-7), feas_tol=min(1e-2 * tol, 1e-9))
+
+    def _bounds_table(self):
+        """(n_aircraft, 4) = (phi_lo, phi_hi, psi_lo, psi_hi): an asymmetric phi interval / a box on psi travel beside the rows
+        (d2d_nlp_opts.bounds; lo >= hi: not set).  None when no aircraft has either."""
+        if not any('psi' in bd or abs(bd['phi'][0] + bd['phi'][1]) > 1e-12 for bd in self.bounds):
+            return None
+        return np.array([[bd['phi'][0], bd['phi'][1]] + list(bd.get('psi', (0.0, 0.0))) for bd in self.bounds], dtype=np.float64)
+
     def solve(self, x0):
         if self.objective == 'host':
             if self.moving:
@@ -279,60 +297,35 @@ class Problem:
         rows, coupled = self._rows()
         if self.free_step is not None:
             return self._solve_free(ctx, x0, W, rows)
-        # IPOPT's max_iter counts Newton steps; here they are grouped as outer (multiplier / barrier updates) x inner (<= D2D_NLP_INNER_MAX):
-        # between 720 and 3600 steps in all, as in rounds 2-3 (12 .. 60 batches of 60)
-        _im = d2dhip.NLP_INNER_MAX
-        kw = dict(inner_max=_im, outer_max=int(min(max(self.options.get('max_iter', 3000) // _im, 720 // _im), 3600 // _im)))
-        # IPOPT's `tol` (the reference sets 1e-5 .. 1e-8) bounds its scaled KKT error.  This backend's own tolerances -- barrier KKT
-        # error of the last inner problem 1e-7, collocation residual 1e-9 -- are at least as tight as every value the reference
-        # uses, so a looser `tol` changes nothing; a tighter one tightens them with it.
-        tol = float(self.options.get('tol', 1e-8))
-        kw.update(opt_tol=min(tol, 1e-7), feas_tol=min(1e-2 * tol, 1e-9))
+        kw = self._solver_kw()
+        bnd = self._bounds_table()
+        kw['bounds'] = None if bnd is None else ctx.dev(bnd)
         dsc = ctx.dev(rows)
         dW = ctx.dev(np.ascontiguousarray(W))
-        # an asymmetric phi interval / a box on psi travel beside the rows (d2d_nlp_opts.bounds; lo >= hi: not set)
-        bnd = None
-        if any('psi' in bd or abs(bd['phi'][0] + bd['phi'][1]) > 1e-12 for bd in self.bounds):
-            bnd = ctx.dev(np.array([[bd['phi'][0], bd['phi'][1]] + list(bd.get('psi', (0.0, 0.0))) for bd in self.bounds], dtype=np.float64))
-        # one launch for the whole Problem: wavefront a of a workgroup solves aircraft a; the pair coupled by CostCollision
-        # alternates on the device (block Gauss-Seidel, d2d_nlp_solve_groups) until neither aircraft moves
         if not coupled:
             dsc[:, d2dhip.SC_KCOL] = 0.0
         multi = hasattr(self.planner, 'acs')
-        if self.moving or self.via is not None:   # the tracks and the pins travel beside the rows; node i at t_start + i time_step
+        tabled = bool(self.moving) or self.via is not None   # tracks and pins travel beside the rows; node i at t_start + i time_step
+        # A lone aircraft with pins, discs or a field takes the hand-out entries (in a field the rows' NaN wind columns are not read).
+        # Everything else is ONE launch of a group entry: wavefront a of a workgroup solves aircraft a; the aircraft coupled by
+        # CostCollision alternate on the device (block Gauss-Seidel) until none moves -- the pair (0, 1), or with a cost that selects
+        # its own pairs every aircraft with a partner.
+        group = multi if tabled else self.field is None
+        ex = dict(field=self.field, t_start=self.t_start if (self.moving or self.field is not None) else None)
+        if self.moving:
             import d2d.opty_utils as d2ou
-            mv = dict(field=self.field, t_start=self.t_start if (self.moving or self.field is not None) else None, bounds=bnd, **kw)
-            if self.moving:
-                knots, disc = d2ou.lower_moving(self.moving)
-                mv.update(knots=ctx.dev(knots[None]), disc=ctx.dev(disc[None]))
-            if self.via is not None and multi:
-                if coupled and self._pairs is None:       # the reference's pair (0, 1) as partner sets
-                    dsc[0, d2dhip.SC_PMASK], dsc[1, d2dhip.SC_PMASK] = 0b10, 0b01
-                out = ctx.nlp_solve_groups_via(dsc, dW, self.time_step, n, ctx.dev(self.via), max_sweeps=int(self.options.get('max_sweeps', 12)),
-                                               tol=float(self.options.get('sweep_tol', 1e-7)), **mv)
-                sweeps, moved = int(out['sweeps'][0].item()), float(out['moved'][0].item())
-            elif self.via is not None:
-                out = ctx.nlp_solve_via(dsc, dW, self.time_step, ctx.dev(self.via), **mv)
-                sweeps, moved = 0, 0.0
-            elif multi:
-                if coupled and self._pairs is None:       # the reference's pair (0, 1) as partner sets
-                    dsc[0, d2dhip.SC_PMASK], dsc[1, d2dhip.SC_PMASK] = 0b10, 0b01
-                out = ctx.nlp_solve_groups_moving(dsc, dW, self.time_step, n, max_sweeps=int(self.options.get('max_sweeps', 12)),
-                                                  tol=float(self.options.get('sweep_tol', 1e-7)), **mv)
-                sweeps, moved = int(out['sweeps'][0].item()), float(out['moved'][0].item())
-            else:
-                out = ctx.nlp_solve_moving(dsc, dW, self.time_step, **mv)
-                sweeps, moved = 0, 0.0
-        elif self.field is not None:              # one aircraft in a field (the rows' NaN wind columns are not read)
-            out = ctx.nlp_solve_wind(dsc, dW, self.time_step, self.field, t_start=self.t_start, bounds=bnd, **kw)
-            sweeps, moved = 0, 0.0
-        else:
-            # (a cost that selects its own pairs: the same alternation over every aircraft with a partner)
-            solve = ctx.nlp_solve_groups if self._pairs is None else ctx.nlp_solve_groups_pairs
-            out = solve(dsc, dW, self.time_step, n, max_sweeps=int(self.options.get('max_sweeps', 12)),
-                        tol=float(self.options.get('sweep_tol', 1e-7)), bounds=bnd, **kw)
-            sweeps = int(out['sweeps'][0].item())
-            moved = float(out['moved'][0].item())
+            knots, disc = d2ou.lower_moving(self.moving)
+            ex.update(knots=ctx.dev(knots[None]), disc=ctx.dev(disc[None]))
+        if self.via is not None:
+            ex['via'] = ctx.dev(self.via)
+        if group:
+            if tabled and coupled and self._pairs is None:       # (these entries read the partner sets: the pair (0, 1) as such)
+                import d2d.multiopty_utils as d2mou
+                d2mou.default_pair_masks(dsc, n, True)
+            ex.update(n_ac=n, pairs=self._pairs is not None, max_sweeps=int(self.options.get('max_sweeps', 12)),
+                      tol=float(self.options.get('sweep_tol', 1e-7)))
+        out = d2dhip.nlp_plan(ctx, dsc, dW, self.time_step, **ex, **kw)
+        sweeps, moved = (int(out['sweeps'][0].item()), float(out['moved'][0].item())) if group else (0, 0.0)
         ctx.sync()
         Wh = dW.cpu().numpy()
         sol = np.zeros(self.num_free)
@@ -366,19 +359,12 @@ class Problem:
         if not (np.isfinite(h0) and h0 > 0.0):
             raise ValueError(f'the start value of the time step (the last entry of x0) must be positive and finite, got {h0}')
         lo, hi = self.step_bounds if self.step_bounds is not None else (h0 / 4.0, 4.0 * h0)
-        _im = d2dhip.NLP_INNER_MAX
-        tol = float(self.options.get('tol', 1e-8))
-        kw = dict(inner_max=_im, outer_max=int(min(max(self.options.get('max_iter', 3000) // _im, 720 // _im), 3600 // _im)),
-                  opt_tol=min(tol, 1e-7), feas_tol=min(1e-2 * tol, 1e-9))
-        bd = self.bounds[0]
-        bnd = None
-        if 'psi' in bd or abs(bd['phi'][0] + bd['phi'][1]) > 1e-12:
-            bnd = ctx.dev(np.array([[bd['phi'][0], bd['phi'][1]] + list(bd.get('psi', (0.0, 0.0)))], dtype=np.float64))
+        bnd = self._bounds_table()
         dsc = ctx.dev(rows)
         dsc[:, d2dhip.SC_KCOL] = 0.0
         dW = ctx.dev(np.ascontiguousarray(W))
         self.free_rows = np.array([[lo, hi, sop.duration_weight(sop.lower_cost(self.cost)), h0]])
-        out = ctx.nlp_solve_free(dsc, dW, h0, ctx.dev(self.free_rows), bounds=bnd, **kw)
+        out = d2dhip.nlp_plan(ctx, dsc, dW, h0, free_rows=ctx.dev(self.free_rows), bounds=None if bnd is None else ctx.dev(bnd), **self._solver_kw())
         ctx.sync()
         Wh = dW.cpu().numpy()
         h = float(out['h'][0].item())
@@ -400,10 +386,7 @@ class Problem:
         low = (0., 0., 0., 0., (), float('nan'), 0., 0, 0)
         rows = np.stack([sop.scen_row(tuple(self.p0s[a]) + (0., 0.), tuple(self.p1s[a]) + (0., 0.), 0., low, 1.0, self.wind,
                                       bd['phi'], bd['v'], x_c=bd.get('x'), y_c=bd.get('y')) for a, bd in enumerate(self.bounds)])
-        bnd = None
-        if any('psi' in bd or abs(bd['phi'][0] + bd['phi'][1]) > 1e-12 for bd in self.bounds):
-            bnd = np.array([[bd['phi'][0], bd['phi'][1]] + list(bd.get('psi', (0.0, 0.0))) for bd in self.bounds], dtype=np.float64)
-        return rows, bnd
+        return rows, self._bounds_table()
 
     def _solve_host(self, x0):
         """A sequence of quadratic models of the user's objective over the exact feasible set (the collocation equalities, end
@@ -424,10 +407,7 @@ class Problem:
         rows, bnd = self._host_rows()
         dsc = ctx.dev(rows)
         dbnd = None if bnd is None else ctx.dev(bnd)
-        _im = d2dhip.NLP_INNER_MAX
-        tol = float(self.options.get('tol', 1e-8))
-        kw = dict(inner_max=_im, outer_max=int(min(max(self.options.get('max_iter', 3000) // _im, 720 // _im), 3600 // _im)),
-                  opt_tol=min(tol, 1e-7), feas_tol=min(1e-2 * tol, 1e-9), bounds=dbnd)
+        kw = dict(self._solver_kw(), bounds=dbnd)
         outer_cap = int(self.options.get('outer_max', min(max(int(self.options.get('max_iter', 3000)) // 20, 8), 100)))
         calls = {'cost': 0, 'grad': 0}
 
