@@ -242,10 +242,23 @@ struct NlpFreeProb : NlpProb {
 struct NlpFreeRow {
   double gu, dd;
 };
-template <bool MOV, bool VIA = false, bool FREE = false>
-using NlpProbT = std::conditional_t<FREE, NlpFreeProb, std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>>;
-template <bool VIA> using NlpProbV = std::conditional_t<VIA, NlpViaProb, NlpProb>;       // for the passes that read no disc
-template <bool MOV> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const NlpProbT<MOV> &pb) {
+// KEEP instantiations (d2d_nlp_solve_keepout): the problem with its hard keep-out discs.  discs [n][3] = (cx, cy, R), wave-uniform, a row
+// with R <= 0 absent; z [n][N] the duals of  g_im = |p_i - c_m|^2 - R_m^2 > 0  (disc m's plane: z[m * N + i], lane = node), 0 at the two end
+// nodes and for absent discs.  Every pass walks the discs in a ROLLED loop, ascending m, like the moving discs of nlp_exp_terms.
+struct NlpKeepSet {
+  const double *discs;
+  double *z;
+  int n;
+};
+struct NlpKeepProb : NlpProb {
+  NlpKeepSet keep;
+};
+template <bool MOV, bool VIA = false, bool FREE = false, bool KEEP = false>
+using NlpProbT = std::conditional_t<KEEP, NlpKeepProb,
+                                    std::conditional_t<FREE, NlpFreeProb, std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>>>;
+template <bool VIA, bool KEEP = false>
+using NlpProbV = std::conditional_t<KEEP, NlpKeepProb, std::conditional_t<VIA, NlpViaProb, NlpProb>>;       // for the passes that read no soft disc
+template <bool MOV, typename PB> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const PB &pb) {
   if constexpr (MOV) return &pb.mv;
   else return nullptr;
 }
@@ -327,8 +340,9 @@ __device__ __forceinline__ int nlp_via_mask(const PB &pb, int i) {
 // Node-parallel (lane = node, chunks of 64) + wave reductions.  All results are wave-uniform.
 // FREE: ut is the trial value of u = 1 / h (u + a du): the equalities are read at 1 / ut, and the duration term kd / ut, the barrier of
 // u's box and the value +inf outside it join the sums (cost_ref_out: the reference's cost() + k_dur (N - 1) h).
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false>
-__device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
+// KEEP: - mub log g of every (interior node, disc) joins the barrier (one more log per node, of the product), +inf when a g <= 0.
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false>
+__device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
                             double mub, double *cost_ref_out, double *feas_out, const NlpModel &md, [[maybe_unused]] double ut = 0.0) {
   const int N = pb.N;
   [[maybe_unused]] const double ht = FREE ? 1.0 / ut : 0.0;
@@ -361,6 +375,22 @@ __device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE> &pb, const NlpScen &s
         if (s.hi[c] < 1e299) { const double su = s.hi[c] - w[c]; if (!(su > 0.0)) outside = 1; prod *= (su > 0.0 ? su : 1.0); }
       }
       bar += log(prod);               // one log per node: at most ten slacks in [1e-12, 1e3], their product stays in range
+      if constexpr (KEEP) {
+        if (i >= 1 && i < N - 1) {
+          const double *__restrict__ dk = pb.keep.discs;
+          double pk = 1.0;            // at most D2D_MAX_KEEP values g in [1e-12, 1e8]: in range too
+#pragma clang loop unroll(disable)
+          for (int m = 0; m < pb.keep.n; ++m) {
+            const double R = dk[3 * m + 2];
+            if (!(R > 0.0)) continue;
+            const double dx = w[0] - dk[3 * m], dy = w[1] - dk[3 * m + 1];
+            const double gk = dx * dx + dy * dy - R * R;
+            if (!(gk > 0.0)) outside = 1;
+            pk *= (gk > 0.0 ? gk : 1.0);
+          }
+          bar += log(pk);
+        }
+      }
       const double dv = w[4] - s.vsp;
       double obj = s.skv * dv * dv + s.skphi * w[3] * w[3];
       if constexpr (MODEL) {          // g.d + 1/2 d^T H d
@@ -454,8 +484,12 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // b goes through the same elimination of (phi, v) as the right-hand side (ttb, its hand-over, its reduced part, which lands in the
 // t' slots of a second set of records for the second pass of the cyclic reduction); fr_out: the sums of the row of u.  rec_lds is
 // false for this instantiation: both passes load their records from the workspace.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false>
-__device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
+// KEEP: disc m at an interior node i, d = p_i - c_m, g = |d|^2 - R^2, dual z: the stationarity rows of (x, y) gain - z 2d, the right-hand
+// side + (mub / g) 2d, the (x, y) corner of D (half convention)  2 (z / g) d d^T - z I  -- the - z I is the constraint's own, negative,
+// curvature: a corner that it makes indefinite fails a pivot of the reduced system and the caller raises the damping -- and the KKT
+// error |z g - mub|.  Nothing else of the pass changes.
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false>
+__device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
                                double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md, [[maybe_unused]] NlpFreeRow *fr_out = nullptr) {
   const int N = pb.N;
   const double h = pb.h, ih = 1.0 / h;
@@ -519,6 +553,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE> &pb, const NlpScen
       wn[0] = 0.0; wn[1] = 0.0; wn[2] = 0.0; wn[3] = 0.0; wn[4] = 1.0;
     }
     double g[NLP_NV] = {0, 0, 0, 0, 0};
+    [[maybe_unused]] double kst[2] = {0.0, 0.0}, krh[2] = {0.0, 0.0};      // KEEP: sum z 2d and sum (mub / g) 2d over the discs
     double D[NLP_NV][NLP_NV];
 #pragma unroll
     for (int a = 0; a < NLP_NV; ++a)
@@ -544,6 +579,22 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE> &pb, const NlpScen
     {
       double obj = 0.0, cref = 0.0;
       nlp_exp_terms<PAIRS, MOV>(s, sc, pb.partner, i, N, wc[0], wc[1], obj, cref, &g[0], &g[1], &D[0][0], &D[0][1], &D[1][1], pb.pmask, nlp_mov_set<MOV>(pb));
+      if constexpr (KEEP) {
+        if (i >= 1 && i < N - 1) {
+          const double *__restrict__ dk = pb.keep.discs;
+#pragma clang loop unroll(disable)
+          for (int m = 0; m < pb.keep.n; ++m) {
+            const double R = dk[3 * m + 2];
+            if (!(R > 0.0)) continue;
+            const double dx = wc[0] - dk[3 * m], dy = wc[1] - dk[3 * m + 1];
+            const double gk = dx * dx + dy * dy - R * R, z = pb.keep.z[(size_t)m * N + i], ig = 1.0 / gk, zg = z * ig, mg = mub * ig;
+            kst[0] += 2.0 * z * dx; kst[1] += 2.0 * z * dy;
+            krh[0] += 2.0 * mg * dx; krh[1] += 2.0 * mg * dy;
+            D[0][0] += 2.0 * zg * dx * dx - z; D[0][1] += 2.0 * zg * dx * dy; D[1][1] += 2.0 * zg * dy * dy - z;
+            err = fmax(err, fabs(z * gk - mub));
+          }
+        }
+      }
       D[1][0] = D[0][1];
     }
     double E[NLP_NV][3];                        // block (i, i-1): only the (x, y, psi) columns of node i-1 are non-zero
@@ -623,6 +674,9 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE> &pb, const NlpScen
         const double su = s.hi[c] - wc[c], z = zuv[c], isu = 1.0 / su;
         sig += z * isu; r -= mub * isu; st += z;
         err = fmax(err, fabs(z * su - mub));
+      }
+      if constexpr (KEEP) {
+        if (c < 2 && !fx) { r += krh[c]; st -= kst[c]; }
       }
       if (!fx) err = fmax(err, fabs(st));
       rhsv[c] = fx ? 0.0 : r;
@@ -1237,8 +1291,12 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
 // Recovery of the eliminated (phi, v) steps + step statistics (node-parallel): d(phi, v)_i = LP^-T (tt - Qt ds_i - Rt ds_{i-1});
 // directional derivative of the merit function, largest primal step (fraction to the boundary) and the dual steps' largest
 // fraction.  Wave-uniform results.
-template <bool VIA = false>
-__device__ void nlp_recover_stats(const NlpProbV<VIA> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
+// KEEP: g is quadratic in the step, g(a) = g + 2 a d.s + a^2 |s|^2 with s the step of (x, y): the fraction-to-the-boundary rule
+// g(a) >= (1 - tau) g is the smaller positive root of  |s|^2 a^2 + 2 (d.s) a + tau g = 0  (none when d.s >= 0 or the discriminant is not
+// positive), in the form tau g / (sqrt(disc) - d.s) that does not cancel; the dual's step is dz = mub / g - z - (z / g) 2 d.s.  The
+// directional derivative needs nothing: the right-hand side carries the discs' terms.
+template <bool VIA = false, bool KEEP = false>
+__device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
                                   double *amax_out, double *az_out) {
   const int N = pb.N;
   double dphi = 0.0, amax = 1.0, az = 1.0;
@@ -1284,6 +1342,26 @@ __device__ void nlp_recover_stats(const NlpProbV<VIA> &pb, const NlpScen &s, int
         if (dw * amax > tau * su) amax = tau * su / dw;
         const double dz = (mub + z * dw) / su - z;
         if (-dz * az > tau * z) az = -tau * z / dz;
+      }
+    }
+    if constexpr (KEEP) {
+      if (i >= 1 && i < N - 1) {
+        const double *__restrict__ dk = pb.keep.discs;
+        const double aa = dwv[0] * dwv[0] + dwv[1] * dwv[1];
+#pragma clang loop unroll(disable)
+        for (int m = 0; m < pb.keep.n; ++m) {
+          const double R = dk[3 * m + 2];
+          if (!(R > 0.0)) continue;
+          const double dx = wv[0] - dk[3 * m], dy = wv[1] - dk[3 * m + 1];
+          const double gk = dx * dx + dy * dy - R * R, z = pb.keep.z[(size_t)m * N + i];
+          const double bh = dx * dwv[0] + dy * dwv[1];
+          if (bh < 0.0) {
+            const double cq = tau * gk, disc = bh * bh - aa * cq;
+            if (disc > 0.0) amax = fmin(amax, cq / (sqrt(disc) - bh));
+          }
+          const double dz = (mub - 2.0 * z * bh) / gk - z;
+          if (-dz * az > tau * z) az = -tau * z / dz;
+        }
       }
     }
   }
@@ -1382,8 +1460,9 @@ __device__ bool nlp_recover_free(const NlpFreeProb &pb, const NlpScen &s, int la
 }
 
 // Take the step (node-parallel): W += a dw, duals += az dz (dz from the step's dw), duals kept near the central path.
-template <bool VIA = false>
-__device__ void nlp_apply(const NlpProbV<VIA> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
+// KEEP: the discs' duals move and are clipped like the box duals, with g at the new point.
+template <bool VIA = false, bool KEEP = false>
+__device__ void nlp_apply(const NlpProbV<VIA, KEEP> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
   const int N = pb.N;
   for (int i0 = 0; i0 < N; i0 += 64) {
     const int i = i0 + lane;
@@ -1410,6 +1489,23 @@ __device__ void nlp_apply(const NlpProbV<VIA> &pb, const NlpScen &s, int lane, d
         double zn = z + az * ((mub + z * dw) / su - z);
         zn = fmin(fmax(zn, 1e-10 * mn), 1e10 * mn);
         NLP_P(WS_ZU + c, i) = zn;
+      }
+    }
+    if constexpr (KEEP) {
+      if (i >= 1 && i < N - 1) {
+        const double *__restrict__ dk = pb.keep.discs;
+        const double xn = wv[0] + a * dwl[0], yn = wv[1] + a * dwl[1];
+#pragma clang loop unroll(disable)
+        for (int m = 0; m < pb.keep.n; ++m) {
+          const double R = dk[3 * m + 2];
+          if (!(R > 0.0)) continue;
+          const double dx = wv[0] - dk[3 * m], dy = wv[1] - dk[3 * m + 1], ex = xn - dk[3 * m], ey = yn - dk[3 * m + 1];
+          const double gk = dx * dx + dy * dy - R * R, gn = ex * ex + ey * ey - R * R, z = pb.keep.z[(size_t)m * N + i];
+          const double bh = dx * dwl[0] + dy * dwl[1], mn = mub / gn;
+          double zn = z + az * ((mub - 2.0 * z * bh) / gk - z);
+          zn = fmin(fmax(zn, 1e-10 * mn), 1e10 * mn);
+          pb.keep.z[(size_t)m * N + i] = zn;
+        }
       }
     }
   }
@@ -1464,7 +1560,71 @@ struct NlpExtra {
   const NlpViaSet *via;      // VIA
   const double *free_row;    // FREE: (h_lo, h_hi, k_dur, h_start; 0 = the launch's h) of the problem, and where its solved h goes
   double *h_out;
+  const NlpKeepSet *keep;    // KEEP
 };
+
+// KEEP: the start of a free node's position.  The box push of the start pass, then every disc in index order, twice (a push out of one
+// disc into its neighbour is undone by the second pass): a node with g <= kappa = (1.01^2 - 1) R^2, i.e. closer to the centre than
+// 1.01 R, moves radially to |d| = 1.01 R -- along (nx, ny), the left normal of the leg p0 -> p1, where the radial direction is
+// degenerate (|d| < 1e-12 R).  The caller re-applies the box push (nlp_box_push), as the start pass does for every variable.
+__device__ __forceinline__ double nlp_box_push(double w, double lo, double hi) {
+  const bool hl = lo > -1e299, hu = hi < 1e299;
+  const double width = (hl && hu) ? hi - lo : 1e300;
+  const double kap = fmin(1e-2 * fmax(1.0, fabs(w)), 1e-2 * width);
+  if (hl) w = fmax(w, lo + kap);
+  if (hu) w = fmin(w, hi - kap);
+  return w;
+}
+__device__ __forceinline__ void nlp_keep_start(const NlpScen &s, const NlpKeepSet &k, double &x, double &y) {
+  x = nlp_box_push(x, s.lo[0], s.hi[0]); y = nlp_box_push(y, s.lo[1], s.hi[1]);
+  const double lx = s.p1[0] - s.p0[0], ly = s.p1[1] - s.p0[1], ll = sqrt(lx * lx + ly * ly);
+  const double nx = ll > 0.0 ? -ly / ll : 0.0, ny = ll > 0.0 ? lx / ll : 1.0;
+  const double *__restrict__ dk = k.discs;
+#pragma clang loop unroll(disable)
+  for (int q = 0; q < 2 * k.n; ++q) {
+    const int m = q < k.n ? q : q - k.n;
+    const double R = dk[3 * m + 2];
+    if (!(R > 0.0)) continue;
+    const double cx = dk[3 * m], cy = dk[3 * m + 1], Rt = R * (1.0 + 1e-2);
+    const double dx = x - cx, dy = y - cy, d2 = dx * dx + dy * dy;
+    if (d2 - R * R <= Rt * Rt - R * R) {
+      const double dn = sqrt(d2);
+      const bool deg = dn < 1e-12 * R;
+      const double ux = deg ? nx : dx / dn, uy = deg ? ny : dy / dn;
+      x = cx + Rt * ux; y = cy + Rt * uy;
+    }
+  }
+}
+// KEEP: what refuses a problem before its first store (wave-uniform): a disc with a non-finite entry, an end pose on or inside a disc,
+// or a free node that the start rule leaves on or inside one (discs that cover the box, overlapping discs that leave no room).
+__device__ __forceinline__ bool nlp_keep_bad(const NlpScen &s, const NlpKeepSet &k, const double *__restrict__ Wb, int N, int lane) {
+  int bad = 0;
+  const double *__restrict__ dk = k.discs;
+#pragma clang loop unroll(disable)
+  for (int m = 0; m < k.n; ++m) {
+    const double cx = dk[3 * m], cy = dk[3 * m + 1], R = dk[3 * m + 2];
+    bad |= !(fabs(cx) <= 1.79e308) || !(fabs(cy) <= 1.79e308) || !(fabs(R) <= 1.79e308);
+    if (!(R > 0.0)) continue;
+    const double ax = s.p0[0] - cx, ay = s.p0[1] - cy, bx = s.p1[0] - cx, by = s.p1[1] - cy;
+    bad |= !(ax * ax + ay * ay - R * R > 0.0) || !(bx * bx + by * by - R * R > 0.0);
+  }
+  if (bad) return true;                      // (wave-uniform so far: the discs' table is)
+  for (int i0 = 0; i0 < N; i0 += 64) {
+    const int i = i0 + lane;
+    if (i < 1 || i >= N - 1) continue;
+    double x = Wb[i], y = Wb[N + i];
+    nlp_keep_start(s, k, x, y);
+    x = nlp_box_push(x, s.lo[0], s.hi[0]); y = nlp_box_push(y, s.lo[1], s.hi[1]);
+#pragma clang loop unroll(disable)
+    for (int m = 0; m < k.n; ++m) {
+      const double R = dk[3 * m + 2];
+      if (!(R > 0.0)) continue;
+      const double dx = x - dk[3 * m], dy = y - dk[3 * m + 1];
+      bad |= !(dx * dx + dy * dy - R * R > 0.0);
+    }
+  }
+  return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
+}
 
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
@@ -1479,7 +1639,10 @@ struct NlpExtra {
 // launch's h; the Newton system is bordered by the row of u = 1 / h (nlp_assemble, nlp_recover_free), every pass reads the
 // equalities at the current u, the line search at the trial one, and cost carries the duration term.  An unusable row of the box
 // refuses the problem like an unusable scenario row; *ex.h_out gets the solved h (NaN for a refused problem).
-template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false>
+// KEEP (d2d_nlp_solve_keepout): ex.keep the problem's hard discs and the planes of their duals; g > 0 is held at every interior node by
+// the same primal-dual barrier as the box (nlp_merit, nlp_assemble, nlp_recover_stats, nlp_apply), the start is moved out of the discs
+// (nlp_keep_start) and unusable discs refuse the problem (nlp_keep_bad).  cost does not see the discs.
+template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
                                               const double *__restrict__ bnd, const NlpExtra &ex = NlpExtra{}) {
@@ -1492,7 +1655,8 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   if (st_on) st_t = __builtin_amdgcn_s_memtime();
   NlpScen s = nlp_load_scen(sc, o, bnd);
   if (sc[D2D_SC_BANKMAX] != 0.0) { s.sbank = s.skphi * (double)N; s.skphi = 0.0; }     // obj_scale * kbank (the row's S is obj_scale / N)
-  NlpProbT<MOV, VIA, FREE> pb;
+  NlpProbT<MOV, VIA, FREE, KEEP> pb;
+  if constexpr (KEEP) pb.keep = *ex.keep;
   if constexpr (MOV) pb.mv = *ex.mv;
   if constexpr (VIA) pb.vm = via->vm;
   pb.N = N; pb.h = h;
@@ -1523,6 +1687,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       bad = bad || !(hl > 0.0) || !(hl < hh) || !(hh <= 1.79e308) || !(kd >= 0.0) || !(kd <= 1.79e308) || !(fabs(hs) <= 1.79e308);
       if (lane == 0) *ex.h_out = __builtin_nan("");
     }
+    if constexpr (KEEP) bad = bad || nlp_keep_bad(s, pb.keep, Wb, N, lane);
     if (bad) {
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
       return;
@@ -1549,9 +1714,15 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       }
       via->vm[i] = vmi;
     }
+    [[maybe_unused]] double kxy[2] = {0.0, 0.0};
+    if constexpr (KEEP) {
+      kxy[0] = NLP_W(0, i); kxy[1] = NLP_W(1, i);
+      nlp_keep_start(s, pb.keep, kxy[0], kxy[1]);
+    }
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) {
       double w = NLP_W(c, i);
+      if constexpr (KEEP) { if (c < 2) w = kxy[c]; }
       double zl = 0.0, zu = 0.0;
       if (nlp_fixed_at<VIA>(i, N, c, vmi)) {
         if constexpr (VIA) w = (i == 0) ? s.p0[c] : (i == N - 1 ? s.p1[c] : pin[c]);
@@ -1567,8 +1738,17 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         if (hu) zu = mub / (s.hi[c] - w);
       }
       NLP_W(c, i) = w;
+      if constexpr (KEEP) { if (c < 2) kxy[c] = w; }
       NLP_P(WS_ZL + c, i) = zl; NLP_P(WS_ZU + c, i) = zu;
       NLP_DW(c, i) = 0.0;
+    }
+    if constexpr (KEEP) {                    // the discs' duals on the central path; 0 at the end nodes and for absent discs
+      const double *__restrict__ dk = pb.keep.discs;
+#pragma clang loop unroll(disable)
+      for (int m = 0; m < pb.keep.n; ++m) {
+        const double R = dk[3 * m + 2], dx = kxy[0] - dk[3 * m], dy = kxy[1] - dk[3 * m + 1];
+        pb.keep.z[(size_t)m * N + i] = (R > 0.0 && i >= 1 && i < N - 1) ? mub / (dx * dx + dy * dy - R * R) : 0.0;
+      }
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) NLP_MU(k, i) = 0.0;
@@ -1600,7 +1780,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     double phi0;
     if constexpr (FREE) phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md, pb.u);
     else
-    phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1623,7 +1803,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
           const double d0 = pb.kd / (u * u * u) + fr.dd + 0.5 * (pb.zul / sl + pb.zuu / su);
           dfull = d0 + lam * fmax(fabs(d0), 1e-12);
         } else
-        err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -1654,7 +1834,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
           NLP_STAMP(4)
           if (!spd) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
         } else {
-        nlp_recover_stats<VIA>(pb, s, lane, mub, tau, &dphi, &amax, &az);
+        nlp_recover_stats<VIA, KEEP>(pb, s, lane, mub, tau, &dphi, &amax, &az);
         nlp_phase_sync();
         NLP_STAMP(4)
         }
@@ -1664,14 +1844,14 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         for (int ls = 0; ls < 8; ++ls) {
           if constexpr (FREE) pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md, pb.u + a * du);
           else
-          pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
+          pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
         NLP_STAMP(0)
         if (ok) {
           phi0 = pt;
-          nlp_apply<VIA>(pb, s, lane, a, az, mub);
+          nlp_apply<VIA, KEEP>(pb, s, lane, a, az, mub);
           if constexpr (FREE) {              // u and its duals move like a node variable (nlp_apply)
             const double u = pb.u, un = u + a * du, sl = u - pb.ulo, su = pb.uhi - u;
             const double ml = mub / (un - pb.ulo), mh = mub / (pb.uhi - un);
@@ -1691,7 +1871,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     }
     if constexpr (FREE) (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
     else
-    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -1736,7 +1916,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
     if (lane == 0) *ex.h_out = pb.h;
   } else
-  (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+  (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -1866,14 +2046,17 @@ __device__ __forceinline__ void nlp_report(int b, int lane, const NlpOut &out, d
 // A refused problem's W is not touched.  The pointer parameters carry no __restrict__ (the kernels' do), as in nlp_groups_body.
 // FREE (nlp_solve_free_kernel): the problems' boxes of the time step free_rows [B][4] and their solved steps h_out [B]; the slot's
 // workspace has the planes of the border behind the others (WSF_TOTAL).
-template <bool WIND, bool MOV, bool VIA, bool T_AT, bool FREE = false>
+// KEEP (nlp_solve_keepout_kernel): the problems' hard discs keep->discs [B][n_keep][3] and the planes of their duals kwork [B][n_keep][N]
+// (the problem's, not the slot's: they are a result).
+template <bool WIND, bool MOV, bool VIA, bool T_AT, bool FREE = false, bool KEEP = false>
 __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d2d_nlp_opts &o, const double *scen, double *W, double *work,
                                                  double *mult, double *cost_out, double *feas_out, int32_t *iters_out, int32_t *status_out,
                                                  int32_t *queue, const d2d_wind_field *wf, double t_start, const double *t_at = nullptr,
                                                  const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr,
                                                  const d2d_via_points *via = nullptr, int32_t *vwork = nullptr,
                                                  const double *free_rows = nullptr, double *h_out = nullptr,
-                                                 [[maybe_unused]] unsigned long long *stamps = nullptr) {
+                                                 [[maybe_unused]] unsigned long long *stamps = nullptr,
+                                                 [[maybe_unused]] const d2d_keep_out *keep = nullptr, [[maybe_unused]] double *kwork = nullptr) {
   const int lane = threadIdx.x;
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   double *wsb = work + (size_t)blockIdx.x * (FREE ? WSF_TOTAL : WS_TOTAL) * N;
@@ -1889,7 +2072,7 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
     bool bad = false;
     if constexpr (T_AT) {
       t0 = 0.0;
-      if (WIND || mv->n_mov > 0) {
+      if (WIND || (MOV && mv->n_mov > 0)) {
         t0 = nlp_first_lane(t_at[b]);
         bad = !(fabs(t0) <= 1.79e308);
       }
@@ -1911,6 +2094,11 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
       nlp_solve_one<false, false, false, false, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
                                                              lane, out, b == 0 ? stamps : nullptr, nlp_lds, bnd,
                                                              NlpExtra{{nullptr, nullptr, nullptr}, nullptr, 0.0, 0u, nullptr, nullptr, free_rows + (size_t)b * 4, h_out + b});
+    } else if constexpr (KEEP) {
+      const NlpKeepSet ks{keep->discs + (size_t)b * keep->n_keep * 3, kwork + (size_t)b * keep->n_keep * N, keep->n_keep};
+      nlp_solve_one<false, WIND, false, false, false, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
+                                                                   lane, out, nullptr, nlp_lds, bnd,
+                                                                   NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, nullptr, nullptr, nullptr, nullptr, &ks});
     } else {
       nlp_solve_one<false, WIND, false, MOV, VIA>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
                                                   lane, out, nullptr, nlp_lds, bnd, NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, &ms, &vs});
@@ -1937,6 +2125,17 @@ nlp_solve_free_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__re
                       unsigned long long *stamps) {
   nlp_handout_body<false, false, false, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, nullptr, 0.0,
                                                      nullptr, nullptr, nullptr, nullptr, nullptr, free_rows, h_out, stamps);
+}
+
+// d2d_nlp_solve_keepout: outside every problem's hard discs -- the rows' constant wind or the field (WIND), the start time per problem
+template <bool WIND>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_keepout_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                         double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                         int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
+                         d2d_keep_out keep, double *kwork) {
+  nlp_handout_body<WIND, false, false, true, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, 0.0,
+                                                          t_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &keep, kwork);
 }
 
 // d2d_nlp_solve_moving: around the problems' moving discs -- the rows' constant wind or the field (WIND), the start time per problem.
@@ -2505,6 +2704,26 @@ int d2d_nlp_solve_moving(d2d_ctx *ctx, int B, int N, double h, const double *sce
   return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
     return nlp_handout_launch(nlp_solve_moving_kernel<decltype(wind)::value>, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status, wf,
                               t_start, *mov, (const double *)mov_work);
+  });
+}
+
+int d2d_nlp_solve_keepout(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
+                          double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
+                          const double *t_start, const d2d_keep_out *keep, double *kwork) {
+  D2D_REQUIRE(keep, "d2d_nlp_solve_keepout: null keep-out table (n_keep = 0: no discs)");
+  D2D_REQUIRE(keep->n_keep >= 0 && keep->n_keep <= D2D_MAX_KEEP, "d2d_nlp_solve_keepout: n_keep = %d outside 0 .. %d", keep->n_keep, D2D_MAX_KEEP);
+  if (keep->n_keep == 0) {                                 // no discs: the solve of d2d_nlp_solve_moving with nothing moving, its kernels and its checks
+    const d2d_moving_obstacles none{0, 0, nullptr, nullptr};
+    return d2d_nlp_solve_moving(ctx, B, N, h, scen, opts, W, work, mult, cost, feas, iters, status, f, t_start, &none, nullptr);
+  }
+  if (int rc = nlp_single_check(ctx, B, N, h, scen, W, work, cost, feas, "d2d_nlp_solve_keepout")) return rc;
+  D2D_REQUIRE(keep->discs && kwork, "d2d_nlp_solve_keepout: null discs or kwork with n_keep = %d", keep->n_keep);
+  if (int rc = nlp_field_check(f, t_start, nullptr, "d2d_nlp_solve_keepout")) return rc;
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_keepout", &o)) return rc;
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_handout_launch(nlp_solve_keepout_kernel<decltype(wind)::value>, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status, wf,
+                              t_start, *keep, kwork);
   });
 }
 

@@ -349,6 +349,51 @@ def min_clearance(obstacles, t, x, y):
     return [float((np.hypot(*(np.stack([x, y], -1) - o.at(t)).T)).min() - o.r) for o in obstacles]
 
 
+class KeepOut:
+    """A HARD keep-out disc of the collocation planner (include/d2d.h d2d_keep_out): no point of the plan's polyline comes closer
+    than `margin` to the disc of radius r round c.  Scenarios list them in `keep_out`; unlike a CostObstacle this is a constraint the
+    plan holds, not a price it pays.  The solver holds |p_i - c|^2 >= R^2 at the nodes; lowered() inflates R for the chords between them,
+    for nodes at most v_max h apart.  The planners pass the upper AIRSPEED bound as v_max, and the spacing is h times the GROUND speed:
+    where a tail wind or a field of speed w can carry the aircraft faster than that bound, the polyline's margin is only guaranteed
+    for the smaller value sqrt(R^2 - ((v_max + w) h / 2)^2) - r -- ask for a `margin` larger by the difference (w h / 2 is enough once r + margin >= v_max h / 2)."""
+
+    def __init__(self, c, r, margin=0.0):
+        self.c = (float(c[0]), float(c[1]))
+        self.r, self.margin = float(r), float(margin)
+        if not (np.isfinite(self.c).all() and np.isfinite(self.r) and np.isfinite(self.margin)) or not self.r > 0.0 or not self.margin >= 0.0:
+            raise ValueError(f'KeepOut: a finite centre, r > 0 and margin >= 0 are required, got c = {self.c}, r = {self.r}, margin = {self.margin}')
+
+    def lowered(self, v_max, h):
+        """(cx, cy, R) of the node constraint: two nodes on the circle R at the largest spacing v_max h have their chord pass the centre
+        at sqrt(R^2 - (v_max h / 2)^2) = r + margin.  v_max: the largest speed over the ground, which the planners take to be the upper
+        airspeed bound (the class docstring says what a tail wind asks for)."""
+        return self.c[0], self.c[1], float(np.sqrt((self.r + self.margin) ** 2 + (0.5 * v_max * h) ** 2))
+
+    def __repr__(self):
+        return f'KeepOut(c={self.c}, r={self.r}, margin={self.margin})'
+
+
+def lower_keep_out(keep_out, v_max, h):
+    """The rows (n, 3) = (cx, cy, R) of d2d_keep_out for one problem.  NotImplementedError beyond d2dhip.MAX_KEEP discs."""
+    import d2dhip
+    keep_out = list(keep_out)
+    if len(keep_out) > d2dhip.MAX_KEEP:
+        raise NotImplementedError(f'at most {d2dhip.MAX_KEEP} keep-out discs per problem in this build ({len(keep_out)} given)')
+    return np.array([k.lowered(v_max, h) for k in keep_out], dtype=np.float64).reshape(-1, 3)
+
+
+def keep_out_clearance(keep_out, x, y):
+    """Per keep-out disc: the smallest |p - c| - r over the POLYLINE through the plan's nodes (x_i, y_i)."""
+    p = np.stack([np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)], -1)
+    a, ab = p[:-1], p[1:] - p[:-1]
+    out = []
+    for k in keep_out:
+        c = np.asarray(k.c)
+        t = np.clip(np.sum((c - a) * ab, 1) / np.maximum(np.sum(ab * ab, 1), 1e-300), 0.0, 1.0)
+        out.append(float(np.hypot(*(a + t[:, None] * ab - c).T).min() - k.r))
+    return out
+
+
 class Waypoint:
     """A timed waypoint of the collocation planner (include/d2d.h d2d_via_points): at time t -- absolute, on the clock of the scenario's
     t0 -- the given ones of x, y, psi hold exactly; None leaves a component free.  The time must be that of an interior node of the

@@ -18,6 +18,7 @@ SCEN_STRIDE = 80
 MAX_OBS = 16
 MAX_MOV, MOV_MAX_KNOT = 8, 32          # include/d2d.h D2D_MAX_MOV / D2D_MOV_MAX_KNOT (tests compare)
 MAX_VIA = 16                           # include/d2d.h D2D_MAX_VIA
+MAX_KEEP = 8                           # include/d2d.h D2D_MAX_KEEP
 (SC_X0, SC_Y0, SC_PSI0, SC_X1, SC_Y1, SC_PSI1, SC_VREF, SC_VSP, SC_KV, SC_KPHI, SC_KOBS, SC_S,
  SC_WWP, SC_WX, SC_WY, SC_GOLEFT, SC_O0X, SC_O0Y, SC_O0R, SC_O1X, SC_O1Y, SC_O1R, SC_WBND,
  SC_PHIMAX, SC_VMIN, SC_VMAX, SC_KCOL, SC_RCOL, SC_SCOL, SC_PMASK, SC_OKIND, SC_BANKMAX, SC_OEXT) = range(33)
@@ -90,6 +91,11 @@ class MovingObstaclesC(C.Structure):
 class ViaPointsC(C.Structure):
     """d2d_via_points (include/d2d.h): pts dev [G][n_via][5] = (node, mask, x, y, psi); mask bits 0..2 = x, y, psi pinned, 0 = absent."""
     _fields_ = [('n_via', C.c_int32), ('pts', C.c_void_p)]
+
+
+class KeepOutC(C.Structure):
+    """d2d_keep_out (include/d2d.h): discs dev [B][n_keep][3] = (cx, cy, R), a row with R <= 0 absent."""
+    _fields_ = [('n_keep', C.c_int32), ('pad', C.c_int32), ('discs', C.c_void_p)]
 
 
 class AuditParams(C.Structure):
@@ -192,6 +198,8 @@ _SIGS = {
                              + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P]),
     'd2d_nlp_solve_groups_moving': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
                                     + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P]),
+    'd2d_nlp_solve_keepout': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
+                              + [C.POINTER(WindFieldC), _P, C.POINTER(KeepOutC), _P]),
     'd2d_nlp_solve_via': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
                           + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, C.POINTER(ViaPointsC), _P]),
     'd2d_nlp_solve_groups_via': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
@@ -592,14 +600,15 @@ class Context:
         return out
 
     def _nlp_core(self, entry, scen, W, h, opts, bounds, n_ac=None, sweeps=None, want_mult=False, slots=0, order=None, mid=(),
-                  field=_ABSENT, t_start=None, t_scalar=False, moving=_ABSENT, via=_ABSENT, free_rows=None):
+                  field=_ABSENT, t_start=None, t_scalar=False, moving=_ABSENT, via=_ABSENT, free_rows=None, keep=_ABSENT):
         """What the nlp_solve* methods share: the shape checks, the workspace and the outputs, d2d_nlp_opts from opts = (rho0, mub0,
         mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), the call of `entry` and the result.  n_ac: a group entry (sweeps =
         (max_sweeps, tol)), R = B / n_ac scenarios with one start time and one set of tracks each; else B problems.  mid: arguments
         between W and work.  field, moving = (knots, disc), via: the optional inputs in the entries' order, _ABSENT where the entry takes
         none (it takes t_start with the field: a device array, or with t_scalar a float); each adds its entries to the result.
         free_rows: the entry is d2d_nlp_solve_free -- the rows go in front of W, the solved steps `h` [B] behind status, and the
-        workspace is the larger one."""
+        workspace is the larger one.  keep: the entry is d2d_nlp_solve_keepout -- discs dev [B][n_keep][3] or None (no discs) behind the
+        field; the result carries keep_mult [B][n_keep][N], the discs' duals."""
         torch = _torch()
         B, _, N = W.shape
         groups = n_ac is not None
@@ -643,6 +652,11 @@ class Context:
         if v is not None:
             out['via_work'] = torch.zeros(B, N, dtype=torch.int32, device=self.device) if v.n_via > 0 else None
             args += [C.byref(v), _ptr(out['via_work'])]
+        if keep is not _ABSENT:
+            assert keep is None or (keep.is_contiguous() and keep.dtype == torch.float64 and keep.dim() == 3 and keep.shape[0] == B and keep.shape[2] == 3)
+            k = KeepOutC(0 if keep is None else int(keep.shape[1]), 0, None if keep is None else keep.data_ptr())
+            out['keep_mult'] = self.zeros(B, k.n_keep, N) if k.n_keep > 0 else None
+            args += [C.byref(k), _ptr(out['keep_mult'])]
         _check(entry(*args))
         if want_mult:
             out['mult'] = mult
@@ -756,6 +770,20 @@ class Context:
         nlp_solve_groups_pairs's dict plus mov_work [R][n_mov][2][N]."""
         return self._nlp_core(self.lib.d2d_nlp_solve_groups_moving, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial),
                               bounds, n_ac=n_ac, sweeps=(max_sweeps, tol), field=field, t_start=t_start, moving=(knots, disc))
+
+    def nlp_solve_keepout(self, scen, W, h, discs, field=None, t_start=None, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7,
+                          inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None, slots=0, order=None):
+        """nlp_solve / nlp_solve_wind outside HARD keep-out discs (d2d_nlp_solve_keepout): discs dev [B][n_keep][3] = (cx, cy, R) per
+        problem (R <= 0: absent; None: no discs), every interior node held at |p - c|^2 - R^2 > 0 by the solver's barrier.  field None: the
+        rows' constant wind (t_start is not read); else t_start dev [B] or a float.  A problem with a non-finite disc, an end pose on or
+        inside a disc, or no start outside its discs is refused on the device: status ST_NONFINITE, cost = feas = NaN, its W untouched.
+        Returns nlp_solve's dict plus keep_mult [B][n_keep][N]: the multipliers of the disc constraints."""
+        if field is None:
+            t_start = None
+        elif t_start is None:
+            t_start = 0.0
+        return self._nlp_core(self.lib.d2d_nlp_solve_keepout, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
+                              want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, keep=discs)
 
     def _via_c(self, via, G):
         """d2d_via_points over a device table [G][n_via][5] = (node, mask, x, y, psi), or None: no pins.  Shapes only -- the range of

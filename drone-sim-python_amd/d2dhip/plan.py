@@ -1,15 +1,25 @@
 """Which collocation entry a planner calls: policy above the binding, no ctypes (d2dhip.nlp_plan)."""
 
 
-def nlp_plan(ctx, scen, W, h, *, n_ac=None, field=None, t_start=None, knots=None, disc=None, via=None, free_rows=None, pairs=False, **opts):
+def nlp_plan(ctx, scen, W, h, *, n_ac=None, field=None, t_start=None, knots=None, disc=None, via=None, free_rows=None, pairs=False, keep=None,
+             **opts):
     """The planners' one rule for choosing among the nlp_solve* methods of `ctx` (a Context, or any object that has them) -- the first
     optional input that is given names the entry, which also takes the inputs below it in its column (free_rows: none):
       n_ac given, R scenarios of n_ac aircraft:  via -> _groups_via, knots -> _groups_moving, pairs -> _groups_pairs, field -> _groups_wind,
                                                  none -> nlp_solve_groups;
       n_ac None, B problems handed out:          free_rows -> _free, via -> _via, knots -> _moving, field -> _wind, none -> nlp_solve.
+    keep given (n_ac None, no free_rows, via or knots -- each pair refused by name): nlp_solve_keepout with field and t_start.
     opts: the entry's own keywords (solver options, bounds, max_sweeps ...).  Returns the entry's dictionary plus `entry`, its name.
     (nlp_solve_model is not chosen here: its objective model is another problem, not an optional input of a plan -- DESIGN.md 5.16.)"""
     wind = dict(field=field, t_start=t_start)
+    if keep is not None:
+        # hard keep-out discs (dev [B][n_keep][3]): nlp_solve_keepout, with the field and the start times; alone among the optional inputs
+        for name, given in (('n_ac', n_ac is not None), ('free_rows', free_rows is not None), ('via', via is not None), ('knots', knots is not None)):
+            if given:
+                raise NotImplementedError(f'keep together with {name}: hard keep-out discs are for one aircraft on static discs with a fixed step')
+        out = ctx.nlp_solve_keepout(scen, W, h, keep, **wind, **opts)
+        out['entry'] = 'nlp_solve_keepout'
+        return out
     mov = dict(knots=knots, disc=disc, **wind)
     if n_ac is not None:
         entry, kw = (('nlp_solve_groups_via', dict(via=via, **mov)) if via is not None else

@@ -272,7 +272,7 @@ def _via_table(dsc, n_ac, N, h, t_start, via):
 
 
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               moving=None, via=None, gust=None, free_time=None, kdur=0.0, **solve_kw):
+               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -293,7 +293,11 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     hand-out of d2d_nlp_solve_via -- for large batches of single aircraft call Context.nlp_solve_via (the difference is not measured).
     free_time (backend='nlp', n_ac = 1): (h_lo, h_hi) for all problems or an array (B, 2) -- every problem's time step is an unknown in
     that box, started from h, with kdur (a number or (B,)) the weight of the duration (K - 1) h in its objective (d2d_nlp_solve_free);
-    the result carries h, the solved steps (device [B]).  Not combined with n_ac > 1, windfield, moving or via: raised by name."""
+    the result carries h, the solved steps (device [B]).  Not combined with n_ac > 1, windfield, moving or via: raised by name.
+    keep_out (backend='nlp', n_ac = 1): hard keep-out discs -- an array (B, n, 3) of (cx, cy, R), the node constraint as the kernel reads
+    it, or a list of d2d.opty_utils.KeepOut for all problems, lowered with each row's VMAX and h (d2d_nlp_solve_keepout, with and
+    without a field); the result carries keep_mult (device [B][n][K]) and keep (the lowered table, a host array (B, n, 3)).  Not combined with n_ac > 1, moving,
+    via or free_time: raised by name."""
     import single_opt_planner as sop
     from d2d.wind import planner_wind
     if gust is not None:
@@ -314,13 +318,32 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
                                       'Gauss-Seidel over the aircraft cannot hold; plan them one at a time')
         if fld is not None or moving or via is not None:
             raise NotImplementedError('free_time together with windfield, moving or via is not supported: node times move with the step')
+    if keep_out is not None:
+        if backend != 'nlp':
+            raise NotImplementedError("the polynomial fit has no hard keep-out discs: plan_batch(backend='nlp', keep_out=...) holds them")
+        for name, given in (('n_ac > 1', int(n_ac) != 1), ('moving', bool(moving)), ('via', via is not None), ('free_time', free_time is not None)):
+            if given:
+                raise NotImplementedError(f'keep_out with {name} is not supported: hard discs are held for one aircraft on static discs, '
+                                          'without pins, with a fixed step')
     ctx = d2dhip.default_context()
     if backend == 'nlp':
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
         W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
         assert W.shape == (dsc.shape[0], 5, K) and h is not None
         h, n_ac = float(h), int(n_ac)
-        if free_time is not None:
+        if keep_out is not None:
+            B = dsc.shape[0]
+            if len(keep_out) and hasattr(keep_out[0], 'lowered'):
+                import d2d.opty_utils as d2ou
+                rows = np.asarray(scen_rows, dtype=np.float64)
+                keep = np.stack([d2ou.lower_keep_out(keep_out, rows[b, d2dhip.SC_VMAX], h) for b in range(B)])
+            else:
+                keep = np.ascontiguousarray(keep_out, dtype=np.float64)
+                if keep.ndim != 3 or keep.shape[0] != B or keep.shape[2] != 3:
+                    raise ValueError(f'keep_out: an array (B, n, 3) of (cx, cy, R) or a list of KeepOut is required, got shape {keep.shape}')
+            out = d2dhip.nlp_plan(ctx, dsc, W, h, keep=ctx.dev(keep), field=fld, t_start=t_start if fld is not None else None, **solve_kw)
+            out['keep'] = keep
+        elif free_time is not None:
             B = dsc.shape[0]
             fr = np.zeros((B, 4))
             fr[:, :2] = np.broadcast_to(np.asarray(free_time, dtype=np.float64), (B, 2))
@@ -403,6 +426,9 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     import multi_opt_planner as mop
     if audit is not None and ('X' not in record2 or (ref3 is not None and 'X' not in record3)):
         raise ValueError("audit needs the flown histories: 'X' must be in record2 and record3")
+    if getattr(scen, 'keep_out', None):
+        raise NotImplementedError('the mission chain has no hard keep-out discs (scen.keep_out): its transit is the multi-aircraft fit; plan '
+                                  'one aircraft with single_opt_planner.Planner (d2d_nlp_solve_keepout)')
     import d2d.opty_utils as d2ou
     F = plant_wind(windfield)
     gust = plant_gust(gust)

@@ -73,6 +73,9 @@ class Planner:
             raise NotImplementedError('the multi-aircraft planner takes a constant wind: a field that varies in space and time is planned '
                                       'one aircraft at a time (single_opt_planner.Planner, d2d_nlp_solve_wind); the joint problem and its '
                                       'CostCollision partner (d2d_nlp_solve_groups) have no field')
+        if getattr(scen, 'keep_out', None):
+            raise NotImplementedError('the multi-aircraft planner has no hard keep-out discs (keep_out): they are held for one aircraft at a '
+                                      'time (single_opt_planner.Planner, d2d_nlp_solve_keepout)')
         self.moving_obstacles = sop.check_moving(scen, self.backend)
         self.waypoints = sop.check_waypoints(scen, self.backend, len(scen.p0s))       # one list per aircraft
         self._has_via = any(self.waypoints)

@@ -119,7 +119,7 @@ def _closure_objects(fn):
 
 class Problem:
     def __init__(self, obj, obj_grad, eom, state_symbols, num_nodes, time_step, known_parameter_map=None,
-                 instance_constraints=(), bounds=None, parallel=False, cost=None, planner=None):
+                 instance_constraints=(), bounds=None, parallel=False, cost=None, planner=None, keep_out=None):
         self.obj, self.obj_grad = obj, obj_grad
         # a symbol for the interval: variable duration (the interval is the last free entry); a number: the fixed step
         self.free_step = time_step if (hasattr(time_step, 'name') and not isinstance(time_step, (int, float, np.number))) else None
@@ -201,6 +201,18 @@ class Problem:
         for bd in self.bounds:
             if 'phi' not in bd or 'v' not in bd:
                 raise NotImplementedError('phi and v bounds are required (the model divides by v)')
+        # hard keep-out discs (d2d.opty_utils.KeepOut): true inequalities of the NLP, held at the nodes (d2d_nlp_solve_keepout)
+        self.keep_out = list(keep_out or [])
+        if self.keep_out:
+            what = ('more than one aircraft' if self.n_aircraft != 1 else
+                    'moving obstacles' if self.moving else
+                    'instance_constraints at interior times (waypoints)' if self.via is not None else
+                    f'a variable duration (time_step = {self.free_step})' if self.free_step is not None else
+                    'the host objective (a cost plug-in without a kernel)' if self.objective == 'host' else None)
+            if what:
+                raise NotImplementedError(f'keep_out together with {what} is not supported')
+            import d2d.opty_utils as d2ou
+            self.keep_rows = d2ou.lower_keep_out(self.keep_out, self.bounds[0]['v'][1], self.time_step)
         if self.free_step is not None:                  # what a free interval is not combined with (d2d_nlp_solve_free)
             what = ('more than one aircraft (they share one interval: the joint system is not built)' if self.n_aircraft != 1 else
                     'moving obstacles (their node times move with the step)' if self.moving else
@@ -310,8 +322,10 @@ class Problem:
         # Everything else is ONE launch of a group entry: wavefront a of a workgroup solves aircraft a; the aircraft coupled by
         # CostCollision alternate on the device (block Gauss-Seidel) until none moves -- the pair (0, 1), or with a cost that selects
         # its own pairs every aircraft with a partner.
-        group = multi if tabled else self.field is None
+        group = False if self.keep_out else multi if tabled else self.field is None
         ex = dict(field=self.field, t_start=self.t_start if (self.moving or self.field is not None) else None)
+        if self.keep_out:
+            ex['keep'] = ctx.dev(self.keep_rows[None])
         if self.moving:
             import d2d.opty_utils as d2ou
             knots, disc = d2ou.lower_moving(self.moving)
@@ -346,6 +360,9 @@ class Problem:
             mc = [d2ou.min_clearance(self.moving, tn, Wh[a, 0], Wh[a, 1]) for a in range(n)]
             info['min_clearance'] = mc if multi else mc[0]
             info['cost'] = float(out['cost'].sum().item())
+        if self.keep_out:                         # per disc: the polyline's clearance from the user's disc (>= its margin)
+            import d2d.opty_utils as d2ou
+            info['keep_out_clearance'] = d2ou.keep_out_clearance(self.keep_out, Wh[0, 0], Wh[0, 1])
         if self.via is not None:                  # 0.0 by construction: a pinned component never leaves its value
             import d2d.opty_utils as d2ou
             info['waypoint_error'] = max(d2ou.waypoint_error(self.via[a], Wh[a]) for a in range(n))

@@ -104,6 +104,24 @@ def check_moving(exp, backend):
     return moving
 
 
+def check_keep_out(exp, backend, moving=(), waypoints=(), t1_free=None):
+    """The scenario's hard keep-out discs (exp.keep_out, a list of d2d.opty_utils.KeepOut; absent or empty: none) as a list, refused where
+    they cannot be planned: backend='fit', more than d2dhip.MAX_KEEP, or together with moving obstacles, waypoints or t1_free."""
+    keep = list(getattr(exp, 'keep_out', None) or [])
+    if not keep:
+        return keep
+    if backend == 'fit':
+        raise NotImplementedError("backend='fit' cannot hold a keep-out disc (keep_out): the polynomial fit has soft rows only.  "
+                                  "backend='nlp' (or 'auto') solves the collocation problem with the discs as hard constraints")
+    for name, given in (('moving obstacles (moving_obstacles)', bool(moving)), ('waypoints', bool(waypoints)), ('a free duration (t1_free)', t1_free is not None)):
+        if given:
+            raise NotImplementedError(f'keep_out together with {name} is not supported: hard discs are planned on static discs, '
+                                      'without pins, with a fixed step (d2d_nlp_solve_keepout)')
+    if len(keep) > d2dhip.MAX_KEEP:
+        raise NotImplementedError(f'at most {d2dhip.MAX_KEEP} keep-out discs per problem in this build ({len(keep)} given)')
+    return keep
+
+
 def lowerable(cost):
     """True if lower_cost knows the plug-in (the fit and the lowered collocation kernel can express it)."""
     try:
@@ -139,6 +157,8 @@ def duration_weight(lowered):
     return float(getattr(lowered, 'kdur', 0.0))
 
 
+KEEP_HOST_COST = ('keep_out together with a host objective (a cost plug-in without a kernel, d2d_nlp_solve_model) is not supported: '
+                  'use one of the cost classes of d2d.opty_utils')
 FREE_TIME_FIT = ("backend='fit' cannot plan with a free duration (t1_free): the polynomial fit's basis is built for one duration.  "
                  "backend='nlp' (or 'auto') solves the collocation problem with the time step as an unknown")
 
@@ -300,6 +320,8 @@ class Planner:
         # an optional free duration (exp.t1_free = (t1_lo, t1_hi), seconds): the node count stays that of t1 and hz, the time step is
         # an unknown of the collocation problem in [(t1_lo - t0) / (N - 1), (t1_hi - t0) / (N - 1)] (d2d_nlp_solve_free)
         self.t1_free = check_free_time(exp, self.backend)
+        # optional hard keep-out discs (exp.keep_out): held by the collocation backend (d2d_nlp_solve_keepout), to which 'auto' goes straight
+        self.keep_out = check_keep_out(exp, self.backend, self.moving_obstacles, self.waypoints, self.t1_free)
         self.aircraft = d2ou.Aircraft()
         N = self.num_nodes
         self._slice_x, self._slice_y, self._slice_psi, self._slice_phi, self._slice_v = (
@@ -311,7 +333,9 @@ class Planner:
             raise NotImplementedError(MOVING_HOST_COST)
         if self._host_cost and self.waypoints:
             raise NotImplementedError(VIA_HOST_COST)
-        if initialize and (self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints
+        if self._host_cost and self.keep_out:
+            raise NotImplementedError(KEEP_HOST_COST)
+        if initialize and (self.keep_out or self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints
                            or self.t1_free is not None):
             import opty.direct_collocation
             _g = self.aircraft
@@ -334,7 +358,8 @@ class Planner:
                                                         lambda _free: obj.cost_grad(_free, self),
                                                         _g.get_eom(self.wind), _g._state_symbols, self.num_nodes, step,
                                                         known_parameter_map={}, instance_constraints=self._instance_constraints,
-                                                        bounds=self._bounds, parallel=False)
+                                                        bounds=self._bounds, parallel=False,
+                                                        **(dict(keep_out=self.keep_out) if self.keep_out else {}))
         elif initialize:
             self.prob = _FitProblem(self, 1)
 
@@ -424,7 +449,7 @@ class Planner:
             self.time_step = float(self.solution[-1])
             self.duration = self.time_step * (self.num_nodes - 1)
             self.info['backend_used'] = 'nlp'
-        elif self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints:
+        elif self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints or self.keep_out:
             self.info['backend_used'] = 'nlp'
         elif self.backend != 'nlp':
             self._harden()

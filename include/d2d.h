@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 120
+#define D2D_VERSION 121
 
 /* error codes */
 #define D2D_OK 0
@@ -815,6 +815,35 @@ int d2d_nlp_solve_free(d2d_ctx *ctx, int B, int N, double h0, const double *scen
                        const double *free_rows /* dev [B][4] = (h_lo, h_hi, k_dur, h_start; 0 = h0) */,
                        double *W, double *work, double *mult, double *cost, double *feas,
                        int32_t *iters, int32_t *status, double *h_out /* dev [B] */);
+
+/* d2d_nlp_solve / d2d_nlp_solve_wind OUTSIDE hard keep-out discs.  For problem b, interior node i (x and y free: 1 .. N-2) and disc
+ * m = (cx, cy, R) of keep->discs [B][n_keep][3]:   g_im = (x_i - cx)^2 + (y_i - cy)^2 - R^2 > 0,   a true inequality of the NLP, held by
+ * the same primal-dual log barrier as the box (a dual z_im > 0 per (node, disc), started at mub / g); a row with R <= 0 is absent.
+ * With d = (x_i - cx, y_i - cy) and the step s of (x_i, y_i): the merit gains - mub log g (+inf when a g <= 0), the stationarity rows
+ * of (x_i, y_i) - z 2d, the right-hand side + (mub / g) 2d, the KKT error |z g - mub|, and the (x, y) corner of the node's diagonal
+ * block the full Hessian (z / g)(2d)(2d)^T - 2 z I -- the second term is the constraint's own, negative, curvature (the feasible set is
+ * the OUTSIDE of a disc): a block that it leaves indefinite fails a pivot, the damping is raised eightfold and the system assembled
+ * again.  dz = mub / g - z - (z / g) 2 d.s, ratio test and clip to [mub / (1e10 g), 1e10 mub / g] as for the box duals.  The primal
+ * fraction-to-the-boundary rule is exact: the smaller positive root a of  g + 2 a d.s + a^2 |s|^2 = (1 - tau) g.
+ * Start: after the box push a free node closer than 1.01 R to a centre is moved radially to 1.01 R (along the left normal of the leg
+ * p0 -> p1 where |d| < 1e-12 R), discs in index order, two passes, then the box push again.
+ * Refused on the device before the problem's first store (D2D_ST_NONFINITE, cost = feas = NaN, iters = 0, W untouched; the rest of the
+ * launch is solved): a non-finite entry of a disc, an end pose on or inside a disc, a free node still on or inside a disc after the
+ * start rule.  cost is the reference's cost(): the discs add nothing.  The constraint is held AT THE NODES; between two nodes at spacing
+ * s the polyline can cut a chord of depth R - sqrt(R^2 - (s/2)^2): the caller inflates R for that (single_opt_planner does).
+ * f NULL: the rows' constant wind, and t_start is not read; else t_start dev [B], as d2d_nlp_solve_moving.  f and t_start go together.
+ * kwork dev [B][n_keep][N]: the duals z, written by the solve; afterwards the multipliers of the disc constraints (0 at the end nodes and
+ * for absent discs).  work dev double[d2d_nlp_workspace_doubles(N) * B].  n_keep = 0: the solve of d2d_nlp_solve / d2d_nlp_solve_wind
+ * (kwork may be NULL).  n_keep > D2D_MAX_KEEP or keep NULL: D2D_EINVAL.  opts, W, mult, iters, status as d2d_nlp_solve.
+ * tests/nlp_keepout_ref.py is the CPU statement.  Asynchronous on the context's stream.  (version 121) */
+#define D2D_MAX_KEEP 8
+typedef struct {
+  int32_t n_keep, pad;  /* 0 .. D2D_MAX_KEEP */
+  const double *discs;  /* dev [B][n_keep][3] = (cx, cy, R) */
+} d2d_keep_out;
+int d2d_nlp_solve_keepout(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W,
+                          double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
+                          const d2d_wind_field *field, const double *t_start, const d2d_keep_out *keep, double *kwork);
 
 /* d2d_nlp_solve_groups in a wind field: the multi-aircraft Problem of R scenarios whose equalities are those of d2d_nlp_solve_wind,
  *   .. + wx(t_i, x_i, y_i) = 0,  .. + wy(t_i, x_i, y_i) = 0,   t_i = t_start[r] + i h  (one multiply-add, not accumulated),

@@ -26,7 +26,12 @@ python tools/bench_nlp_wind.py via [B]     timed waypoints (d2d_nlp_solve_via): 
 python tools/bench_nlp_wind.py free [B]    a free time step (d2d_nlp_solve_free): B (default 4096) perturbed exp_14 at 121 nodes, once with
     the step fixed (d2d_nlp_solve) and once with h free in [h / 2, 2 h] (k_dur = 0: the duration is whatever lets v sit at VSP), the
     same rows from the same guess.  The two entries alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians,
-    the spread of each, the share CONVERGED of both and what the freed step does to the problems the fixed one leaves STALLED."""
+    the spread of each, the share CONVERGED of both and what the freed step does to the problems the fixed one leaves STALLED.
+python tools/bench_nlp_wind.py keepout [B] hard keep-out discs (d2d_nlp_solve_keepout): B (default 4096) perturbed exp_14 at 121 nodes, each
+    with one disc of 15 m whose centre lies on the middle of its leg moved 3 m sideways (node radius: KeepOut.lowered with the row's
+    VMAX and h, no margin), against the same rows without a disc through d2d_nlp_solve, from the same guess.  The two entries
+    alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians, the spread of each, statuses, mean and longest
+    step counts, and the smallest g / R^2 of the converged plans."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 'tests')):
@@ -257,7 +262,49 @@ def free_leg(B):
     ctx.close()
 
 
+def keepout_leg(B):
+    import torch, d2dhip
+    import d2dhip as D
+    from d2dhip import synth
+    from d2d.opty_utils import KeepOut
+    ctx = d2dhip.Context(0)
+    rows, W0, h = synth.nlp_problems(B)
+    N = W0.shape[2]
+    p0, p1 = rows[:, D.SC_X0:D.SC_X0 + 2], rows[:, D.SC_X1:D.SC_X1 + 2]
+    d = p1 - p0
+    d /= np.hypot(d[:, 0], d[:, 1])[:, None]
+    c = 0.5 * (p0 + p1) + 3.0 * np.stack([-d[:, 1], d[:, 0]], 1)
+    discs = np.array([[KeepOut(c[b], 15.0).lowered(rows[b, D.SC_VMAX], h)] for b in range(B)])
+    dsc, dk = ctx.dev(rows), ctx.dev(discs)
+    times = {'plain': [], 'keepout': []}
+    outs, Ws = {}, {}
+    for rep in range(6):                                     # the first launch of each is the warm-up; the entries alternate
+        for what in ('plain', 'keepout'):
+            W = ctx.dev(np.ascontiguousarray(W0))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            outs[what] = ctx.nlp_solve(dsc, W, h) if what == 'plain' else ctx.nlp_solve_keepout(dsc, W, h, dk)
+            e1.record(); torch.cuda.synchronize()
+            times[what].append(e0.elapsed_time(e1) * 1e-3)
+            Ws[what] = W
+    med = {k: float(np.median(v[1:])) for k, v in times.items()}
+    for what in ('plain', 'keepout'):
+        st = outs[what]['status'].cpu().numpy(); it = outs[what]['iters'].cpu().numpy()
+        Wh = Ws[what].cpu().numpy()
+        g = ((Wh[:, 0, 1:-1] - discs[:, 0, 0:1]) ** 2 + (Wh[:, 1, 1:-1] - discs[:, 0, 1:2]) ** 2) / discs[:, 0, 2:3] ** 2 - 1.0
+        ok = st == 1
+        print(json.dumps({'leg': 'keepout', 'B': B, 'nodes': N, 'entry': what, 'seconds_median': med[what], 'seconds_min': min(times[what][1:]),
+                          'seconds_max': max(times[what][1:]), 'problems_per_s': B / med[what], 'keepout_over_plain': med['keepout'] / med['plain'],
+                          'status_counts': {int(k): int((st == k).sum()) for k in np.unique(st)}, 'mean_newton_steps': float(it.mean()),
+                          'max_newton_steps': int(it.max()), 'mean_newton_steps_converged': float(it[ok].mean()) if ok.any() else None,
+                          'min_g_over_R2_converged': float(g[ok].min()) if ok.any() else None,
+                          'plans_inside_the_disc': int((g[ok].min(axis=1) < 0).sum()) if ok.any() else None}), flush=True)
+    ctx.close()
+
+
 def main():
+    if sys.argv[1:2] == ['keepout']:
+        return keepout_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['free']:
         return free_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['via']:

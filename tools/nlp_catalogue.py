@@ -3,7 +3,10 @@
 status, Newton steps, cost, feasibility -- a robustness survey of d2d_nlp_solve.  python tools/nlp_catalogue.py
 --free-time: every case with its duration freed to [t / 2, 2 t] (t = t1 - t0; the scenario protocol's t1_free, d2d_nlp_solve_free):
 status, duration and cost per case.  Cases that a free step is not combined with (a wind field, moving obstacles, waypoints, a host
-cost) report the refusal."""
+cost) report the refusal.
+--keep-out: every case with its soft discs (the cost's static obstacles) turned into hard ones (the scenario protocol's keep_out,
+d2d_nlp_solve_keepout; no margin): status, cost and the polyline's clearance per disc.  Cases without a disc, and those a hard disc is not
+combined with, say so."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd')):
@@ -13,6 +16,7 @@ import numpy as np
 
 def main():
     free = '--free-time' in sys.argv[1:]
+    hard = '--keep-out' in sys.argv[1:]
     import d2d.optyplan_scenarios as sc
     import single_opt_planner as sop
     # the reference's sweeps mutate exp_0 (exp_0_1: t1, exp_0_2: wind, exp_6: p0 / p1) and every exp_0-based scenario sees it:
@@ -28,6 +32,13 @@ def main():
                 if free:                                # the case as it stands, with t1 free in [t0 + t / 2, t0 + 2 t]
                     t = s.t1 - s.t0
                     exp = type(s.__name__ + '_free', (s,), {'t1_free': (s.t0 + 0.5 * t, s.t0 + 2.0 * t)})
+                if hard:                                # the cost's own discs, held instead of priced (they stay in the cost as well)
+                    from d2d.opty_utils import KeepOut
+                    obss = sop.lower_cost(s.cost)[4]
+                    if not obss:
+                        print(json.dumps({'scen': s.name, 'case': case, 'keep_out': 'no disc in this case'}), flush=True)
+                        continue
+                    exp = type(s.__name__ + '_hard', (s,), {'keep_out': [KeepOut(o[:2], o[2]) for o in obss]})
                 p = sop.Planner(exp, initialize=True, backend='nlp')
                 t0 = time.perf_counter()
                 p.run(p.get_initial_guess(getattr(s, 'initial_guess', 'tri')))
@@ -36,6 +47,8 @@ def main():
                        'cost': p.info['obj_val'], 'feas': p.info['feas'], 'seconds': round(dt, 3)}
                 if free:
                     rec.update(duration=p.duration, asked=s.t1 - s.t0)
+                if hard:
+                    rec.update(discs=len(exp.keep_out), keep_out_clearance=p.info.get('keep_out_clearance'))
                 print(json.dumps(rec), flush=True)
             except Exception as e:                      # noqa: BLE001 -- a survey: report and go on
                 print(json.dumps({'scen': s.name, 'case': case, 'error': f'{type(e).__name__}: {e}'[:200]}), flush=True)
