@@ -58,7 +58,7 @@ KnotLds knot_lds_layout(int K, int wpb) {
   L.Hb64 = o; o = align16(o + K * KN_HB_STRIDE * 8);
   L.Hb32 = o; o = align16(o + K * 32 * 4);
   L.Wseg = o; o = align16(o + D2D_FIT_MAX_S * 4 * 64 * 4);
-  L.Md32 = o; o = align16(o + KN_N * KN_N * 4);
+  L.Md32 = o; o = align16(o + (KN_N + 1) * KN_N * 4);   // + one row of +0.f behind the table (KnotMetric::prepare)
   L.Mi32 = o; o = align16(o + KN_NE * 28 * 4);
   L.Mr32 = o; o = align16(o + KN_NE * 12 * 4);
   L.Msc = o; o = align16(o + 64 * 8);
@@ -479,13 +479,17 @@ struct KnotMetric {
     return act ? r : 0.f;
   }
   int row_off;                  // byte offset of this lane's row of the dense metric: formed by prepare() inside the solve, dead outside it
-  __device__ __forceinline__ void prepare(int l) { row_off = md32_off + (l < KN_N ? l : 0) * (KN_N * 4); }
+  // prepare() READS lam: the caller sets lam (and scale) before it enters damped_solve, which calls prepare() first.  A lane with
+  // lam == 0 -- the right-hand side's lane and those above it always, every lane in a Gauss-Newton solve -- is pointed at row KN_N
+  // of the staged table, 48 x +0.f that the kernel writes behind the metric's own rows, so that damp() is one unconditional read
+  // per panel instead of a select under the exec mask.  Every operand of fma(scale, damp, a) is then the value it was with the
+  // select -- +0.f where the select gave +0.f, M[lane][j0 ..] elsewhere -- and identical bits follow from that alone.
+  __device__ __forceinline__ void prepare(int l) { row_off = md32_off + ((l < KN_N && lam != 0.f) ? l : KN_N) * (KN_N * 4); }
   __device__ __forceinline__ f32x4 damp(int j0) const {
 #ifdef KN_ABL_DAMP
     return f32x4{lam, lam, lam, lam};
 #endif
-    const float *mdrow = reinterpret_cast<const float *>(lds + row_off);
-    return lam != 0.f ? lds_get<f32x4>(mdrow + j0) : f32x4{0.f, 0.f, 0.f, 0.f};     // (unscaled: damped_solve multiplies by `scale`)
+    return lds_get<f32x4>(reinterpret_cast<const float *>(lds + row_off) + j0);     // (unscaled: damped_solve multiplies by `scale`)
   }
 };
 
@@ -529,6 +533,8 @@ fit_lm_knot_kernel(int B, KnotGeom kg, KnotLds L, d2d_fit_opts opts, int iter_ca
   stage(lds + L.Mi32, T.Mi32, KN_NE * 28 * 4);
   stage(lds + L.Mr32, T.Mrow32, KN_NE * 12 * 4);
   stage(lds + L.Msc, T.msc, KN_NE * 8);
+  // row KN_N of the staged metric: +0.f throughout -- what damp() hands to the lanes that get no damping (KnotMetric::prepare)
+  for (int i = threadIdx.x; i < N; i += blockDim.x) reinterpret_cast<float *>(lds + L.Md32)[N * N + i] = 0.f;
   __syncthreads();
   const double *Hb64 = reinterpret_cast<const double *>(lds + L.Hb64);
   const float *Wseg = reinterpret_cast<const float *>(lds + L.Wseg);
@@ -775,6 +781,7 @@ fit_lm_knot_kernel(int B, KnotGeom kg, KnotLds L, d2d_fit_opts opts, int iter_ca
           double dxn = 0.0, t2 = 0.0;
           float dls, dgi;
           // the damped matrix H_u + lam Mu: the metric's row is added where the factorisation reads the lane's row (damped_solve)
+          // (lam is set BEFORE the call: damped_solve begins with metric.prepare(), which picks the lane's row by it)
           metric.lam = lane < N ? (float)solve_lam : 0.f; metric.scale = metric.lam;
           ok = uniform_i(damped_solve<N, true, true>(hrow, 0.0, act, lane, big, dgi, dls, nullptr, true, isq_mode, V_mp_delta, &dxn, &t2,
                                                      hdiag, true, metric) ? 1 : 0) != 0;

@@ -849,8 +849,36 @@ __device__ __forceinline__ bool damped_solve(const f32x2 (&hrow)[N / 2], double 
   // the lane's column of the factor, in blocks of 16 rows, each block requested one block AHEAD of the dependent chain that uses it
   // (two blocks in flight at the start; 32 registers): left to the scheduler the reads were issued two at a time inside the chain,
   // each pair behind a full LDS wait -- 23 exposed LDS latencies on a chain of 47 readlane + fma steps
-  {
-    constexpr int NBS = N / 16;
+  constexpr int NBS = N / 16;
+  if constexpr (!__is_same(Metric, int)) {
+    // (under a Metric -- the knot kernel -- the column is held as the pairs of rows in which ds_read2_b32 delivers them, so that the
+    // scaling by -1 / L[lane][lane] is one v_pk_mul_f32 per pair -- the same product, rounded the same way, as the scalar multiply
+    // it replaces -- with no move to form a pair: rows 16 bk + 2 p, + 1; in block 0, whose row 0 no lane needs, rows 2 p + 1,
+    // 2 p + 2 -- the last pair's second half, row 16, is read and scaled for nothing and never used.  The q-coordinate kernels keep
+    // the scalar form below: packed, their N = 16 and N = 32 instantiations grew.)
+#define CM_ROW(bk, p) ((bk) > 0 ? 16 * (bk) + 2 * (p) : 2 * (p) + 1)
+    f32x2 cm[2][8];
+    const f32x2 ninv = f32x2{-myinv, -myinv};
+#pragma unroll
+    for (int p = 0; p < 8; ++p) cm[(NBS - 1) & 1][p] = f32x2{col[CM_ROW(NBS - 1, p) * LS], col[(CM_ROW(NBS - 1, p) + 1) * LS]};
+#pragma unroll
+    for (int bk = NBS - 1; bk >= 0; --bk) {
+      if (bk > 0) {
+#pragma unroll
+        for (int p = 0; p < 8; ++p) cm[(bk - 1) & 1][p] = f32x2{col[CM_ROW(bk - 1, p) * LS], col[(CM_ROW(bk - 1, p) + 1) * LS]};
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int p = 0; p < 8; ++p) cm[bk & 1][p] *= ninv;
+#pragma unroll
+      for (int r = 15; r >= 0; --r)
+        if (16 * bk + r >= 1) {                            // L[i][lane] = 0 for i <= lane
+          const int e = bk > 0 ? r : r - 1;                // position of row 16 bk + r among the block's pairs
+          dl = fmaf((e & 1) ? cm[bk & 1][e >> 1].y : cm[bk & 1][e >> 1].x, lane_value(dl, 16 * bk + r), dl);
+        }
+    }
+#undef CM_ROW
+  } else {
     float cm[2][16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) cm[(NBS - 1) & 1][r] = col[(16 * (NBS - 1) + r) * LS];

@@ -16,7 +16,21 @@ Families (max_iter = 150 everywhere; name -> what it reaches):
 Per family: cost, q (float64), iters, status (int32) and stats (float64[3]: max |J^T r| over the family, fits not converged, evaluations
 -- d2d_fit_solve's stats[1 .. 3]; stats[0], the cost sum, is accumulated with atomics in an order that is not fixed, and `cost` holds
 its terms).  The per-fit count of factorisations, lm[7], stays inside the plan -- no entry point of the library returns it -- so the
-evaluation count and the trial counts of `iters` are what pins the path a fit took."""
+evaluation count and the trial counts of `iters` are what pins the path a fit took.
+
+    python tools/dump_knot_bits.py --r9 [OUT.npz]     tests/golden/knot_r9_parent_bits.npz (tests/test_gpu_knot_metric_row.py)
+
+A second, smaller fixture, written ONCE with the build of the commit before round 9 (the metric's zero row, the packed
+column scaling of the back substitution).  32 fits a case, max_iter = 40: at that size every fit starts at once, so the hand-out
+order plays no part, and within the first trial of every fit both kinds of solve occur, Gauss-Newton (no damping on any lane) and
+damped.  The scenario families are those of tests/test_gpu_knot_segmin.py:
+  k23, k48, k50, k55, k64   the generic instantiation, every segment at the floor, the bench's K, the first K past SEG9, the longest
+  so0, bankmax              K = 50 with so_lambda = 0, and in CostBank's max mode
+and the three other kernels that share damped_solve (they pin its back substitution outside the knot kernel):
+  fused    K = 50 with d2d_fit_plan_opts.kernel = FUSED (fit_lm_kernel)
+  long     K = 121 (fit_lm_long_kernel)
+  groups   2 aircraft x 16 replicas through solve_groups (fit_groups_kernel); iters = sweeps of every replica, status = the call's
+Per case: cost, q (float64), iters, status (int32)."""
 import os
 import sys
 
@@ -70,8 +84,72 @@ def run(ctx, name):
         plan.close()
 
 
+R9_B, R9_MAX_ITER = 32, 40
+R9_KNOT = ('k23', 'k48', 'k50', 'k55', 'k64', 'so0', 'bankmax')
+R9_SHARED = ('fused', 'long', 'groups')
+R9_CASES = R9_KNOT + R9_SHARED
+R9_FIELDS = ('cost', 'q', 'iters', 'status')
+R9_GROUP_AC = 2
+
+
+def r9_scenarios(name):
+    """(K, duration, wref, scenarios [R9_B]) of a case of the round-9 fixture"""
+    import bench
+    from d2dhip import synth
+    if name == 'groups':
+        dur, _ = bench._plan_consts()
+        s = 1.0 / bench.K
+        sc = synth.circle_group_scenarios(R9_GROUP_AC, R9_B // R9_GROUP_AC, dur, bench.K, seed=R9_GROUP_AC, sigma=2.0, obj_scale=1.0)
+        return bench.K, dur, (0.02 ** 2, s * 5.0 / 8, s / 8 / synth.G_ACC ** 2), sc.reshape(R9_B, -1)
+    if name in ('k50', 'so0', 'bankmax', 'fused'):
+        dur, wref = bench._plan_consts()
+        sc = synth.variant_scenarios('bankmax', R9_B, K=bench.K) if name == 'bankmax' else bench.bench_scenarios(4096)[:R9_B]
+        return bench.K, dur, wref, sc
+    K2 = 121 if name == 'long' else int(name[1:])
+    dur = synth.planner_timing(0, (K2 - 1) / 10.0, 10)[2]
+    return K2, dur, synth.default_wref(0.1, K2), synth.synth_scenarios(R9_B, seed=5, obj_scale=0.1, K=K2, dist_range=(30. * dur / 4.9, 55. * dur / 4.9))
+
+
+def r9_run(ctx, name):
+    """One case of the round-9 fixture -> {field: numpy array}"""
+    import d2dhip
+    K2, dur, wref, sc = r9_scenarios(name)
+    dsc = ctx.dev(sc)
+    kernel = {'fused': 'fused', 'long': 'auto', 'groups': 'auto'}.get(name, 'knot')
+    plan = d2dhip.FitPlan(ctx, 6, K2, dur, wref, kernel=kernel)
+    try:
+        assert plan.kernel == {'fused': 'fused', 'long': 'long'}.get(name, 'knot'), (name, plan.kernel)
+        q = plan.init(dsc)
+        if name == 'groups':
+            R = R9_B // R9_GROUP_AC
+            cost, sweeps, _ = plan.solve_groups(dsc, q, R9_GROUP_AC, max_sweeps=80, inner_iters=8, tol=1e-12)
+            iters, status = plan.group_report(R)[0].astype(np.int32), np.asarray([sweeps], dtype=np.int32)
+        else:
+            kw = {'so_lambda': 0.0} if name == 'so0' else {}
+            cost, iters, status, _ = plan.solve(dsc, q, max_iter=R9_MAX_ITER, **kw)
+            iters, status = iters.cpu().numpy().astype(np.int32), status.cpu().numpy().astype(np.int32)
+        return {'cost': cost.cpu().numpy().astype(np.float64), 'q': q.cpu().numpy().astype(np.float64), 'iters': iters, 'status': status}
+    finally:
+        plan.close()
+
+
+def main_r9(out):
+    import d2dhip
+    ctx = d2dhip.Context(0)
+    arrays = {}
+    for name in R9_CASES:
+        r = r9_run(ctx, name)
+        arrays.update({f'{name}_{k}': v for k, v in r.items()})
+        print(name, 'fits', len(r['cost']), 'iters', int(r['iters'].min()), int(r['iters'].max()), 'status', np.bincount(r['status']).tolist(), flush=True)
+    ctx.close()
+    np.savez_compressed(out, **arrays)
+    print('wrote', out, os.path.getsize(out), 'bytes')
+
+
 def main():
     import d2dhip
+    if len(sys.argv) > 1 and sys.argv[1] == '--r9':
+        return main_r9(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, 'tests', 'golden', 'knot_r9_parent_bits.npz'))
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'tests', 'golden', 'knot_parent_bits.npz')
     ctx = d2dhip.Context(0)
     arrays = {}

@@ -4,8 +4,9 @@ floor of eight samples a segment; <false, true> before round 8) -- as hipcc comp
 csrc/fit_knot.hip for gfx950 with the Makefile's flags: the whole kernel and the straight-line block that is one factorisation of
 damped_solve (the basic block that holds its 16 MFMAs and its reciprocal roots), by class; registers / scratch / occupancy of all four
 instantiations; and (round 8) the evaluation's k-steps: every cluster of twenty or more accumulating MFMAs outside the factorisation,
-with the instructions between its first and last v_mfma and the branches among them.  The per-item tables of DESIGN 5.3c (rounds 7
-and 8) are this tool's output, commit by commit.
+with the instructions between its first and last v_mfma and the branches among them; and (round 9) the block of the isq forward
+substitution, the one with the most v_readlane outside the factorisation's.  The per-item tables of DESIGN 5.3c (rounds 7 to 9) are
+this tool's output, commit by commit.
 
     python tools/knot_count.py [file.s]        (an assembly file already made with --cuda-device-only -S is read instead of compiling)"""
 import os
@@ -66,6 +67,10 @@ def main():
     print('fit_lm_knot_kernel<false, true, 8>' if 'Li8E' in head else 'fit_lm_knot_kernel<false, true>')
     print('  whole kernel  ', census(body))
     print('  factorisation ', census(fact))
+    # (round 9) the forward substitution of isq -- lmpar's || L^-1 (M delta / dxnorm) ||^2: the block with the most v_readlane outside
+    # the factorisation's
+    isq = max((b for b in blocks if b is not fact), key=lambda b: sum('v_readlane' in x for x in b))
+    print('  isq           ', census(isq))
     # the evaluation's k-steps: accumulating MFMAs (a register block as C) outside the factorisation blocks, clustered by position
     infact = {id(b) for b in blocks if any('v_rsq_f32' in x for x in b)}
     pos, n = [], 0
