@@ -4,7 +4,9 @@
 // paths.  The GPU side cannot be sanitised on this pool; kernels are checked by the parity tests.
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 
 #include "fit_plan.h"
@@ -74,12 +76,26 @@ static int check_plan(int S, int K, double duration) {
   for (double v : pl.Zl) zlmax = std::fmax(zlmax, std::fabs(v));
   std::printf("  segments: |Psi Zl - G| = %.2e of %.2e, |Zl| <= %.2f, %d lanes, %d chunks\n", wseg, gmax, zlmax, lanes, pl.seg_nchunk);
   if (!(wseg < 1e-9 * gmax) || lanes > 64 || covered != K || zlbig || !(zlmax < 50.0)) return 1;
+  // the knot-space tables of the shapes the knot kernel takes (fit_knot.hip fit_knot_plan_init): fit_basis_knots itself refuses a
+  // fp32 Hermite table whose pad words are not +0.f -- restated here on what it returned, and that words 0 .. 2 are not all zero
+  if (S == 6 && nq == 24 && K <= 64) {
+    if (int rc3 = fit_basis_knots(&pl)) { std::printf("  knots: rc=%d (%s)\n", rc3, g_err.c_str()); return rc3; }
+    int pads = 0, filled = 0;
+    for (size_t i = 0; i < pl.kn.Hb32.size(); ++i) {
+      uint32_t bits;
+      std::memcpy(&bits, &pl.kn.Hb32[i], sizeof(bits));
+      if (i % 4 == 3) pads += bits != 0u;
+      else filled += bits != 0u;
+    }
+    std::printf("  knots: fp32 Hermite table of %zu words, %d filled, %d pad words not +0.f\n", pl.kn.Hb32.size(), filled, pads);
+    if ((int)pl.kn.Hb32.size() != K * 32 || pads != 0 || filled == 0) return 1;
+  }
   return worst < 1e-6 ? 0 : 1;
 }
 
 int main() {
   int bad = 0;
-  const int shapes[][2] = {{6, 50}, {6, 61}, {6, 121}, {6, 151}, {6, 501}, {3, 20}, {1, 8}, {4, 31}};
+  const int shapes[][2] = {{6, 50}, {6, 48}, {6, 64}, {6, 61}, {6, 121}, {6, 151}, {6, 501}, {3, 20}, {1, 8}, {4, 31}};
   for (auto &sh : shapes) bad += check_plan(sh[0], sh[1], 0.1 * (sh[1] - 1)) != 0;
   // failure path: too few samples for the unknowns -> a clean error code, no out-of-bounds access
   d2d_fit_plan pl;

@@ -7,6 +7,7 @@
 // end conditions; the other 4S knot values per axis are the free unknowns, whitened by the
 // Cholesky factor of Nfree^T Mref Nfree.
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 
 #include "fit_plan.h"
@@ -371,6 +372,13 @@ int fit_basis_knots(d2d_fit_plan *pl) {
         const bool fixed = (s == 0 && m < 2) || (s == S - 1 && m >= 4 && m < 6);
         kn.Hb32[(size_t)k * 32 + 4 * m + d] = fixed ? 0.f : (float)v;
       }
+  }
+  // the pad word: word 3 of every (sample, m) quad stays the +0.f the table was assigned.  fit_knot.hip knot_mfma_so_floor reads
+  // it as an MFMA operand wherever the rolled pass selects 0.f, so a table that fails this is refused, bit for bit (-0.f included)
+  for (size_t i = 3; i < kn.Hb32.size(); i += 4) {
+    uint32_t bits;
+    std::memcpy(&bits, &kn.Hb32[i], sizeof(bits));
+    if (bits != 0u) { d2d_set_error("fit_basis_knots: pad word %zu of the fp32 Hermite table is not +0.f", i); return D2D_EINVAL; }
   }
   fit_knot_first_samples(pl->seg, S, kn.k0);
   // waypoint rows' constant J^T J: per segment sum_k Hb0_k^T Hb0_k on the (x, x) and (y, y) columns, in the MFMA accumulator layout

@@ -237,24 +237,76 @@ __device__ __forceinline__ void knot_mfma(const KnotGeom &kg, const unsigned cha
   }
 }
 
+// ---- J^T r (phase 2) riding on the unconditional k-steps of an MFMA pass of NQ k-steps a half (knot_eval_fused, knot_mfma_so_floor) -----
+// The SAME operations as knot_phase2, per lane in the same order.  Sample w of the lane's half is read behind k-step STEP w (its four
+// reads) and summed behind k-step STEP w + LAG (its three FMAs; LAG k-steps = 96 cycles of the matrix pipe: the reads are back).
+// A sample i < SEGMIN is read unmasked.  A lane's half is either empty (the outer knots, the lanes without an entry) or holds
+// n >= SEGMIN samples: a lane of an empty half reads the samples 0 .. of the table and its sums are put back to what they were at
+// the SEGMIN-th sample; its masked FMAs fma(0, 0, a) -- the knot_phase2 loop runs SLOTS = 3 ceil(smax / 3) samples, SEGMIN is no
+// multiple of three, so there is one -- follow as they do there.
+template <int SEGMAX, int SEGMIN, int NQ>
+struct KnotP2Rider {
+  typedef double __attribute__((ext_vector_type(2), may_alias)) f64x2a;
+  static constexpr int SLOTS = (SEGMAX + 2) / 3 * 3;
+  static constexpr int LAG = 3, STEP = (NQ - 1 - LAG) / (SLOTS - 1), NBUF = LAG / (STEP > 0 ? STEP : 1) + 1;
+  static_assert(SEGMIN > 0 && SEGMIN <= SEGMAX && SEGMIN % 3 != 0, "a masked sample follows the floor in every half");
+  static_assert(STEP >= 1, "every sample of the half finds its two k-steps");
+  const double *hb, *uk;
+  int n;
+  bool some;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, b0, b1, b2;
+  f64x2a h01[NBUF], u01[NBUF];
+  double h2[NBUF], u2[NBUF];
+  // this half's range of the lane's entry (knot_phase2's kb / km / ke), the lane's two base addresses
+  __device__ __forceinline__ void begin(int half, const double *Hb64, const double *us, int kb, int km, int ke, int a, int kd, bool live) {
+    const int k0 = half ? km : kb, k1 = half ? ke : km;
+    n = live ? k1 - k0 : 0;
+    some = n > 0;
+    const int k0r = some ? k0 : 0;
+    hb = Hb64 + (size_t)k0r * KN_HB_STRIDE + 4 * ((half ? 0 : 4) + kd);
+    uk = us + k0r * KN_US + 4 * a;
+    b0 = a0; b1 = a1; b2 = a2;
+  }
+  __device__ __forceinline__ void read(int idx, int i) {
+    if (idx < SEGMIN) {
+      h01[i] = *reinterpret_cast<const f64x2a *>(hb + idx * KN_HB_STRIDE); u01[i] = *reinterpret_cast<const f64x2a *>(uk + idx * KN_US);
+      h2[i] = hb[idx * KN_HB_STRIDE + 2]; u2[i] = uk[idx * KN_US + 2];
+    } else {                                            // past the floor: the sample of a longer segment, zeros elsewhere
+      const bool in = idx < n;
+      const int o = in ? idx : 0;
+      const f64x2a hr = *reinterpret_cast<const f64x2a *>(hb + o * KN_HB_STRIDE), ur = *reinterpret_cast<const f64x2a *>(uk + o * KN_US);
+      const double h2r = hb[o * KN_HB_STRIDE + 2], u2r = uk[o * KN_US + 2];
+      h01[i] = in ? hr : f64x2a{0.0, 0.0}; u01[i] = in ? ur : f64x2a{0.0, 0.0};
+      h2[i] = in ? h2r : 0.0; u2[i] = in ? u2r : 0.0;
+    }
+  }
+  __device__ __forceinline__ void fma3(int idx, int i) {
+    if (idx == SEGMIN) { a0 = some ? a0 : b0; a1 = some ? a1 : b1; a2 = some ? a2 : b2; }
+    a0 = fma(h01[i].x, u01[i].x, a0);
+    a1 = fma(h01[i].y, u01[i].y, a1);
+    a2 = fma(h2[i], u2[i], a2);
+    LAUNDER(a0); LAUNDER(a1); LAUNDER(a2);              // (held here: the sums are sunk below the predicated k-steps otherwise)
+  }
+  // behind k-step q of the half
+  __device__ __forceinline__ void step(int q) {
+    if (q % STEP == 0 && q / STEP < SLOTS) read(q / STEP, (q / STEP) % NBUF);
+    if (q >= LAG && (q - LAG) % STEP == 0 && (q - LAG) / STEP < SLOTS) fma3((q - LAG) / STEP, ((q - LAG) / STEP) % NBUF);
+  }
+  __device__ __forceinline__ double sum() const { return (a0 + a1) + a2; }
+};
+
 // ---- phases 2 + 3 in one pass, for a plan whose segments all hold at least SEGMIN samples (SEGMIN > 0: fit_knot_launch) -------------
 // v_mfma_f32_16x16x4_f32 holds the matrix pipe for 32 cycles and the pass is nothing but 50 of them: J^T r -- which needs only the
 // u records the pass reads too -- is issued in that shadow.  The SAME operations as knot_phase2 and knot_mfma<SEGMAX>, per lane in
 // the same order (every sum keeps its order); what the floor buys is the form:
 //   * k-step i < SEGMIN of a segment is unconditional and its index unclamped: one base address per segment and table, immediate
 //     offsets, no branch between the MFMAs; only the steps SEGMIN <= i < SEGMAX keep their predicate;
-//   * a sample i < SEGMIN of phase 2 is read unmasked.  A lane's half is either empty (the outer knots, the lanes without an entry)
-//     or holds n >= SEGMIN samples: a lane of an empty half reads the samples 0 .. of the table and its sums are put back to what
-//     they were at the SEGMIN-th sample; its masked FMAs fma(0, 0, a) -- the knot_phase2 loop runs SLOTS = 3 ceil(smax / 3)
-//     samples, SEGMIN is no multiple of three, so there is one -- follow as they do there;
+//   * phase 2 is KnotP2Rider above: a sample i < SEGMIN is read unmasked;
 //   * half `h` of phase 2 goes, sample by sample, between the k-steps of the segments 3 h .. 3 h + 2.
 template <int SEGMAX, int SEGMIN>
 __device__ __forceinline__ double knot_eval_fused(const KnotGeom &kg, const unsigned char *lds, const double *Hb64, const double *us,
                                                   int kb, int km, int ke, int a, int kd, bool live, int hb32_off, int cf_off,
                                                   const float *Wseg, float ww, int lane, f32x4 (&acc)[D2D_FIT_MAX_S]) {
-  typedef double __attribute__((ext_vector_type(2), may_alias)) f64x2a;
-  constexpr int SLOTS = (SEGMAX + 2) / 3 * 3;
-  static_assert(SEGMIN > 0 && SEGMIN <= SEGMAX && SEGMIN % 3 != 0, "a masked sample follows the floor in every half");
   static_assert(D2D_FIT_MAX_S == 6, "two halves of three segments");
   LAUNDER(lane);
   LAUNDER(kb);
@@ -262,18 +314,11 @@ __device__ __forceinline__ double knot_eval_fused(const KnotGeom &kg, const unsi
   const int m = 4 * (c >> 3) + (c & 3), ax = (c >> 2) & 1;
   const int tab = hb32_off + (4 * m + (r < 2 ? 1 : 0)) * 4;
   const int cfo = cf_off + r * 16 + ax * 8;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  KnotP2Rider<SEGMAX, SEGMIN, 3 * SEGMIN> p2;
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     const int s0 = 3 * half;
-    // phase 2: this half's range, the lane's two base addresses
-    const int k0 = half ? km : kb, k1 = half ? ke : km;
-    const int n = live ? k1 - k0 : 0;
-    const bool some = n > 0;
-    const int k0r = some ? k0 : 0;
-    const double *hb = Hb64 + (size_t)k0r * KN_HB_STRIDE + 4 * ((half ? 0 : 4) + kd);
-    const double *uk = us + k0r * KN_US + 4 * a;
-    const double b0 = a0, b1 = a1, b2 = a2;
+    p2.begin(half, Hb64, us, kb, km, ke, a, kd, live);
     // phase 3: the accumulators' start values, and the operands of the first two rows of k-steps (a row: one k-step of each of the
     // three segments); the pass below fetches the operands of k-step q + 6 behind k-step q -- two 8-byte reads, 192 cycles of
     // the matrix pipe ahead of their use -- and forms the operand of k-step q + 1 there
@@ -297,34 +342,8 @@ __device__ __forceinline__ double knot_eval_fused(const KnotGeom &kg, const unsi
     }
     vq[0] = fmaf(rc[0].y, rt[0].y, rc[0].x * rt[0].x);
     __builtin_amdgcn_sched_barrier(0);
-    // the k-steps, round-robin over the three accumulators; sample w of phase 2 rides on the unconditional ones: its four reads
-    // behind k-step STEP w, its three FMAs behind k-step STEP w + LAG (LAG k-steps = 96 cycles of the matrix pipe: the reads are
-    // back).  The order is held (sched_barrier): left to itself the scheduler takes every read of the half to the front of the pass
-    // and spills them.
-    constexpr int LAG = 3, STEP = (NQ - 1 - LAG) / (SLOTS - 1), NBUF = LAG / (STEP > 0 ? STEP : 1) + 1;
-    static_assert(STEP >= 1, "every sample of the half finds its two k-steps");
-    f64x2a h01[NBUF], u01[NBUF];
-    double h2[NBUF], u2[NBUF];
-    auto p2_read = [&](int idx, int i) {
-      if (idx < SEGMIN) {
-        h01[i] = *reinterpret_cast<const f64x2a *>(hb + idx * KN_HB_STRIDE); u01[i] = *reinterpret_cast<const f64x2a *>(uk + idx * KN_US);
-        h2[i] = hb[idx * KN_HB_STRIDE + 2]; u2[i] = uk[idx * KN_US + 2];
-      } else {                                            // past the floor: the sample of a longer segment, zeros elsewhere
-        const bool in = idx < n;
-        const int o = in ? idx : 0;
-        const f64x2a hr = *reinterpret_cast<const f64x2a *>(hb + o * KN_HB_STRIDE), ur = *reinterpret_cast<const f64x2a *>(uk + o * KN_US);
-        const double h2r = hb[o * KN_HB_STRIDE + 2], u2r = uk[o * KN_US + 2];
-        h01[i] = in ? hr : f64x2a{0.0, 0.0}; u01[i] = in ? ur : f64x2a{0.0, 0.0};
-        h2[i] = in ? h2r : 0.0; u2[i] = in ? u2r : 0.0;
-      }
-    };
-    auto p2_fma = [&](int idx, int i) {
-      if (idx == SEGMIN) { a0 = some ? a0 : b0; a1 = some ? a1 : b1; a2 = some ? a2 : b2; }
-      a0 = fma(h01[i].x, u01[i].x, a0);
-      a1 = fma(h01[i].y, u01[i].y, a1);
-      a2 = fma(h2[i], u2[i], a2);
-      LAUNDER(a0); LAUNDER(a1); LAUNDER(a2);              // (held here: the sums are sunk below the predicated k-steps otherwise)
-    };
+    // the k-steps, round-robin over the three accumulators; phase 2 rides on the unconditional ones (KnotP2Rider).  The order is
+    // held (sched_barrier): left to itself the scheduler takes every read of the half to the front of the pass and spills them.
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int i = q / 3, j = q % 3;
@@ -341,8 +360,7 @@ __device__ __forceinline__ double knot_eval_fused(const KnotGeom &kg, const unsi
 #pragma unroll
         for (int t = 0; t < TAIL; ++t) vt[j][t] = fmaf(rct[j][t].y, rtt[j][t].y, rct[j][t].x * rtt[j][t].x);
       }
-      if (q % STEP == 0 && q / STEP < SLOTS) p2_read(q / STEP, (q / STEP) % NBUF);
-      if (q >= LAG && (q - LAG) % STEP == 0 && (q - LAG) / STEP < SLOTS) p2_fma((q - LAG) / STEP, ((q - LAG) / STEP) % NBUF);
+      p2.step(q);
       if (q + 1 < NQ) vq[(q + 1) & 1] = fmaf(rc[(q + 1) % DEPTH].y, rt[(q + 1) % DEPTH].y, rc[(q + 1) % DEPTH].x * rt[(q + 1) % DEPTH].x);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -352,7 +370,7 @@ __device__ __forceinline__ double knot_eval_fused(const KnotGeom &kg, const unsi
       for (int j = 0; j < 3; ++j)
         if (SEGMIN + t < ns[j]) acc[s0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[j][t], vt[j][t], acc[s0 + j], 0, 0, 0);
   }
-  return (a0 + a1) + a2;
+  return p2.sum();
 }
 
 // second-order mode: B_s = sum_k G_k^T M_k G_k (fit_phases.h jtj_mfma_so): per sample one velocity k-step (A = the plain rows a, b,
@@ -396,6 +414,114 @@ __device__ __forceinline__ void knot_mfma_so(const KnotGeom &kg, const unsigned 
       }
     }
   }
+}
+
+// ... the same pass for a plan whose segments all hold at least SEGMIN samples, built like knot_eval_fused: the SAME operations as
+// knot_mfma_so, per accumulator in the same order (sample by sample, the velocity k-step, then the position k-step), so every sum
+// keeps its order and every operand its bits; what the floor buys is the form:
+//   * three segments at a time, their k-steps round-robin over the three accumulators -- a row of three velocity k-steps, then the
+//     row of the same samples' position k-steps -- so that no MFMA waits for the one before it;
+//   * k-steps of the samples i < SEGMIN are unconditional and their indices unclamped: base addresses once per segment, immediate
+//     offsets, no branch between the MFMAs; only the samples SEGMIN <= i < SEGMAX keep their predicate and clamped reads;
+//   * the A operands by ADDRESS.  va is h1, h2 or 0 and vap is h0 or 0 by conditions that are constant per lane, and word 3 of every
+//     (sample, m) quad of the fp32 Hermite table is +0.f -- fit_basis_knots fills words 0 .. 2 of a table assigned 0.f and REFUSES a
+//     table whose pad words are not +0.f bit for bit (fit_basis.cpp: "pad word").  A lane forms once per evaluation the byte offset
+//     of its word (4 | 8 | 12 for va, 0 | 12 for vap) and reads the operand itself: the value the select gave, the sign of its zero
+//     included.  (vbp keeps its select: rp * h0 is -0.f for a negative h0 whatever word stands in for rp.)
+//   * the words of k-step q + KN_FUSED_DEPTH are requested behind k-step q and the operands of k-step q + 1 formed there; the order is
+//     held (sched_barrier), as in knot_eval_fused;
+//   * RIDER: J^T r rides on the unconditional k-steps (KnotP2Rider, by the rule of knot_eval_fused: there are twice as many k-steps
+//     a sample here) and is returned; without it the caller runs knot_phase2 first and the return value is not used.
+template <int SEGMAX, int SEGMIN, bool RIDER>
+__device__ __forceinline__ double knot_mfma_so_floor(const KnotGeom &kg, const unsigned char *lds, const double *Hb64, const double *us,
+                                                     int kb, int km, int ke, int a, int kd, bool live, int hb32_off, int cf_off,
+                                                     int cfp_off, const float *Wseg, float ww, int lane, f32x4 (&acc)[D2D_FIT_MAX_S]) {
+  static_assert(SEGMIN >= 2 && SEGMIN <= SEGMAX, "the operand pipeline is one row of k-steps deep");
+  static_assert(D2D_FIT_MAX_S == 6 && KN_FUSED_DEPTH == 6, "two halves of three segments; a k-step's words are fetched one row of the half ahead");
+  typedef float __attribute__((ext_vector_type(3))) f32x3;
+  LAUNDER(lane);
+  LAUNDER(kb);
+  const int c = lane & 15, rho = lane >> 4;
+  const int m = 4 * (c >> 3) + (c & 3);
+  const bool ay = ((c >> 2) & 1) != 0, row_y = (rho & 1) != 0, row_2 = rho >= 2;
+  const bool own = row_y == ay;
+  const int tab = hb32_off + 4 * m * 4;
+  // (the pad word of the quad -- byte 12 -- where knot_mfma_so selects 0.f: the check named above makes it +0.f)
+  const int tab_a = tab + (own ? (row_2 ? 8 : 4) : 12), tab_p = tab + (own && !row_2 ? 0 : 12);
+  const int reco = cf_off + rho * 16 + (ay ? 8 : 0), rpo = cfp_off + (rho & 1) * 8 + (ay ? 4 : 0);
+  constexpr int NQ = 6 * SEGMIN, TAIL = SEGMAX - SEGMIN, NT = TAIL > 0 ? TAIL : 1;
+  KnotP2Rider<SEGMAX, SEGMIN, NQ> p2;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int s0 = 3 * half;
+    if constexpr (RIDER) p2.begin(half, Hb64, us, kb, km, ke, a, kd, live);
+    const unsigned char *th[3], *ta[3], *tp[3], *cp[3], *pp[3];
+    f32x3 rh[3];                         // velocity k-step of segment j: the quad d0, d1, d2, - (d0 is kept for the position k-step)
+    float2 rc[3];                        // ... the row record's (x | y) half
+    float ra[3], rh0[3], rp[3], rap[3];  // ... its A word; position k-step: the position record's word, its A word
+    f32x3 rht[3][NT];
+    float2 rct[3][NT];
+    float rat[3][NT], rpt[3][NT], rapt[3][NT];
+    float va[2], vb[2], vat[3][NT], vbt[3][NT], vapt[3][NT], vbpt[3][NT];
+    int ns[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int s = s0 + j;
+      int sb = kg.k0[s];
+      ns[j] = kg.k0[s + 1] - kg.k0[s];
+      LAUNDER_S(sb); LAUNDER_S(ns[j]);
+      th[j] = lds + tab + sb * 128; ta[j] = lds + tab_a + sb * 128; tp[j] = lds + tab_p + sb * 128;
+      cp[j] = lds + reco + sb * 64; pp[j] = lds + rpo + sb * 16;
+      rh[j] = lds_get<f32x3>(th[j]); rc[j] = lds_get<float2>(cp[j]); ra[j] = lds_get<float>(ta[j]);
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) acc[s][rr] = ww * Wseg[(s * 4 + rr) * 64 + lane];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { rp[j] = lds_get<float>(pp[j]); rap[j] = lds_get<float>(tp[j]); }
+    va[0] = ra[0]; vb[0] = fmaf(rc[0].y, rh[0].z, rc[0].x * rh[0].y); rh0[0] = rh[0].x;
+    __builtin_amdgcn_sched_barrier(0);
+    auto form = [&](int q) {             // the operands of k-step q from the words fetched for it
+      const int t = (q / 3) & 1, j = q % 3;
+      if (t == 0) { va[q & 1] = ra[j]; vb[q & 1] = fmaf(rc[j].y, rh[j].z, rc[j].x * rh[j].y); rh0[j] = rh[j].x; }
+      else { va[q & 1] = rap[j]; vb[q & 1] = row_2 ? 0.f : rp[j] * rh0[j]; }
+    };
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int i = q / 6, t = (q / 3) & 1, j = q % 3;
+      acc[s0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[q & 1], vb[q & 1], acc[s0 + j], 0, 0, 0);
+      if (q + 6 < NQ) {                  // the same k-step of the next sample of this segment
+        if (t == 0) { rh[j] = lds_get<f32x3>(th[j] + (i + 1) * 128); rc[j] = lds_get<float2>(cp[j] + (i + 1) * 64); ra[j] = lds_get<float>(ta[j] + (i + 1) * 128); }
+        else { rp[j] = lds_get<float>(pp[j] + (i + 1) * 16); rap[j] = lds_get<float>(tp[j] + (i + 1) * 128); }
+      } else {                           // the predicated samples of this segment: clamped past its end
+#pragma unroll
+        for (int tt = 0; tt < TAIL; ++tt) {
+          const int kk = SEGMIN + tt < ns[j] ? SEGMIN + tt : ns[j] - 1;
+          if (t == 0) { rht[j][tt] = lds_get<f32x3>(th[j] + kk * 128); rct[j][tt] = lds_get<float2>(cp[j] + kk * 64); rat[j][tt] = lds_get<float>(ta[j] + kk * 128); }
+          else { rpt[j][tt] = lds_get<float>(pp[j] + kk * 16); rapt[j][tt] = lds_get<float>(tp[j] + kk * 128); }
+        }
+        if (t == 1) {
+#pragma unroll
+          for (int tt = 0; tt < TAIL; ++tt) { vat[j][tt] = rat[j][tt]; vbt[j][tt] = fmaf(rct[j][tt].y, rht[j][tt].z, rct[j][tt].x * rht[j][tt].y); }
+        }
+      }
+      if constexpr (RIDER) p2.step(q);
+      if (q + 1 < NQ) form(q + 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int tt = 0; tt < TAIL; ++tt)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { vapt[j][tt] = rapt[j][tt]; vbpt[j][tt] = row_2 ? 0.f : rpt[j][tt] * rht[j][tt].x; }
+#pragma unroll
+    for (int tt = 0; tt < TAIL; ++tt)
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if (SEGMIN + tt < ns[j]) {
+          acc[s0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vat[j][tt], vbt[j][tt], acc[s0 + j], 0, 0, 0);
+          acc[s0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vapt[j][tt], vbpt[j][tt], acc[s0 + j], 0, 0, 0);
+        }
+  }
+  return RIDER ? p2.sum() : 0.0;
 }
 
 // ---- the segment blocks -> the dense image of J_u^T J_u over the 48 free entries (fit_phases.h tiles_to_image's layout) ---------------
@@ -508,7 +634,7 @@ namespace {
 
 // SEG9: no segment holds more than nine samples (K <= 54 at S = 6: the bench's K = 50) -- the MFMA pass keeps 27 operands, not 33
 // SEGMIN: a floor on the samples of EVERY segment of the plan (0: none known -- the generic code): phases 2 and 3 of a first-order
-// evaluation run as one pass (knot_eval_fused)
+// evaluation run as one pass (knot_eval_fused), and a second-order evaluation runs its pass in a straight line (knot_mfma_so_floor)
 template <bool STAMPS, bool SEG9, int SEGMIN>
 __global__ void __launch_bounds__(64 * KN_WPB_MAX)
 fit_lm_knot_kernel(int B, KnotGeom kg, KnotLds L, d2d_fit_opts opts, int iter_cap, KnotDev T, const double *__restrict__ pk,
@@ -526,6 +652,9 @@ fit_lm_knot_kernel(int B, KnotGeom kg, KnotLds L, d2d_fit_opts opts, int iter_ca
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int N = KN_N;
+  // J^T r inside the second-order pass too: where no segment holds more than nine samples.  The instantiation of the longer
+  // segments (K = 55 .. 64) keeps the stand-alone phase 2 there: with the rider its code outgrows the 64 kB instruction cache
+  constexpr bool SO_RIDER = SEGMIN > 0 && SEG9;
   stage(lds + L.Hb64, T.Hb64, kg.K * KN_HB_STRIDE * 8);
   stage(lds + L.Hb32, T.Hb32, kg.K * 32 * 4);
   stage(lds + L.Wseg, T.Wseg, D2D_FIT_MAX_S * 4 * 64 * 4);
@@ -722,15 +851,21 @@ fit_lm_knot_kernel(int B, KnotGeom kg, KnotLds L, d2d_fit_opts opts, int iter_ca
             f32x4 acc[D2D_FIT_MAX_S];
             const float ww = (float)(sp[PR_WWP] * sp[PR_WWP]);
             const int wbase = L.wave0 + wave * L.wave_stride;
-            // with a floor on the segments a first-order evaluation forms J^T r inside the MFMA pass (knot_eval_fused); the
-            // stand-alone phase 2 stays for second-order mode and for the fit that leaves here, whose accumulators nobody reads
-            const bool fused = SEGMIN > 0 && !so_rows && status == D2D_ST_RUNNING;
+            // with a floor on the segments an evaluation forms J^T r inside its MFMA pass (knot_eval_fused, knot_mfma_so_floor); the
+            // stand-alone phase 2 stays for the fit that leaves here, whose accumulators nobody reads, and for the second-order
+            // evaluations of the instantiation whose pass carries no rider (SO_RIDER)
+            const bool fused = SEGMIN > 0 && (!so_rows || SO_RIDER) && status == D2D_ST_RUNNING;
             if (!fused) gi = knot_phase2(kg, Hb64, us, p2_kb, p2_km, p2_ke, ea, ekd, act, lane);
             KN_STAMP(2)
             fresh = false;
             if (status != D2D_ST_RUNNING) break;
-            if (so_rows) knot_mfma_so(kg, lds, L.Hb32, wbase + L.cf, wbase + L.cfp, Wseg, ww, lane, acc);
-            else if constexpr (SEGMIN > 0)
+            if (so_rows) {
+              if constexpr (SEGMIN > 0) {
+                const double g2 = knot_mfma_so_floor<(SEG9 ? 9 : KN_SEG_MAX), SEGMIN, SO_RIDER>(kg, lds, Hb64, us, p2_kb, p2_km, p2_ke, ea, ekd, act, L.Hb32,
+                                                                                                  wbase + L.cf, wbase + L.cfp, Wseg, ww, lane, acc);
+                if (SO_RIDER) gi = g2;
+              } else knot_mfma_so(kg, lds, L.Hb32, wbase + L.cf, wbase + L.cfp, Wseg, ww, lane, acc);
+            } else if constexpr (SEGMIN > 0)
               gi = knot_eval_fused<(SEG9 ? 9 : KN_SEG_MAX), SEGMIN>(kg, lds, Hb64, us, p2_kb, p2_km, p2_ke, ea, ekd, act, L.Hb32, wbase + L.cf,
                                                                     Wseg, ww, lane, acc);
             else if (SEG9) knot_mfma<9>(kg, lds, L.Hb32, wbase + L.cf, Wseg, ww, lane, acc);

@@ -30,7 +30,18 @@ and the three other kernels that share damped_solve (they pin its back substitut
   fused    K = 50 with d2d_fit_plan_opts.kernel = FUSED (fit_lm_kernel)
   long     K = 121 (fit_lm_long_kernel)
   groups   2 aircraft x 16 replicas through solve_groups (fit_groups_kernel); iters = sweeps of every replica, status = the call's
-Per case: cost, q (float64), iters, status (int32)."""
+Per case: cost, q (float64), iters, status (int32).
+
+    python tools/dump_knot_bits.py --r10 [OUT.npz]    tests/golden/knot_r10_parent_bits.npz (tests/test_gpu_knot_so_pass.py)
+
+A third fixture, written ONCE with the build of the commit before round 10 (the second-order pass under the segment
+floor).  32 fits a case, max_iter = 150, every case on the knot kernel:
+  k48, k50, k54, k55, k64   every segment at the floor (no predicated k-step), the bench's K, either side of SEG9, the longest segments
+  bankmax, so0              K = 50 in CostBank's max mode (long finishes, rejected trials), and with so_lambda = 0
+  resume                    K = 50 in launches of 7 trials: a fit resumed inside the finish enters through the second-order pass
+Per case: cost, q (float64), iters, status (int32), evals (float64[1], d2d_fit_solve's stats[3]) and slice (int32[1]): the fits are
+rows slice .. slice + 32 of the family's 128, the first such slice on which the evaluation count differs from that of the same
+solve with mp_finish = 0 -- a case that never leaves lmder reaches no second-order evaluation and would test nothing."""
 import os
 import sys
 
@@ -146,8 +157,79 @@ def main_r9(out):
     print('wrote', out, os.path.getsize(out), 'bytes')
 
 
+R10_B, R10_POOL = 32, 128
+R10_CASES = ('k48', 'k50', 'k54', 'k55', 'k64', 'bankmax', 'so0', 'resume')
+R10_FIELDS = ('cost', 'q', 'iters', 'status', 'evals', 'slice')
+
+
+def r10_scenarios(name, first):
+    """(K, duration, wref, scenarios [R10_B]) of a case of the round-10 fixture: rows first .. first + R10_B of its family's R10_POOL"""
+    import bench
+    from d2dhip import synth
+    if name[0] == 'k' and name != 'k50':
+        K2 = int(name[1:])
+        dur = synth.planner_timing(0, (K2 - 1) / 10.0, 10)[2]
+        wref = synth.default_wref(0.1, K2)
+        sc = synth.synth_scenarios(R10_POOL, seed=5, obj_scale=0.1, K=K2, dist_range=(30. * dur / 4.9, 55. * dur / 4.9))
+    else:
+        K2 = bench.K
+        dur, wref = bench._plan_consts()
+        if name == 'bankmax':
+            sc = synth.variant_scenarios('bankmax', R10_POOL, K=K2)
+        else:
+            base = {'k50': 0, 'so0': 256, 'resume': 512}[name]
+            sc = bench.bench_scenarios(4096)[base:base + R10_POOL]
+    return K2, dur, wref, sc[first:first + R10_B]
+
+
+def r10_run(ctx, name, first, **mode_kw):
+    """One case of the round-10 fixture -> {field: numpy array}; mode_kw: options of the solve (mp_finish = 0: lmder alone)"""
+    import d2dhip
+    K2, dur, wref, sc = r10_scenarios(name, first)
+    dsc = ctx.dev(sc)
+    plan = d2dhip.FitPlan(ctx, 6, K2, dur, wref, kernel='knot')
+    try:
+        assert plan.kernel == 'knot'
+        q = plan.init(dsc)
+        kw = dict(mode_kw, so_lambda=0.0) if name == 'so0' else mode_kw
+        if name == 'resume':
+            plan.begin(len(sc))
+            for _ in range(MAX_ITER):
+                if plan.iterate(dsc, q, 7, max_iter=MAX_ITER, **kw) == 0:
+                    break
+            cost, iters, status, stats = plan.finish(dsc, q)
+        else:
+            cost, iters, status, stats = plan.solve(dsc, q, max_iter=MAX_ITER, **kw)
+        return {'cost': cost.cpu().numpy().astype(np.float64), 'q': q.cpu().numpy().astype(np.float64),
+                'iters': iters.cpu().numpy().astype(np.int32), 'status': status.cpu().numpy().astype(np.int32),
+                'evals': np.asarray(stats, dtype=np.float64)[3:4].copy(), 'slice': np.asarray([first], dtype=np.int32)}
+    finally:
+        plan.close()
+
+
+def main_r10(out):
+    import d2dhip
+    ctx = d2dhip.Context(0)
+    arrays = {}
+    for name in R10_CASES:
+        for first in range(0, R10_POOL, R10_B):
+            r, lmder = r10_run(ctx, name, first), r10_run(ctx, name, first, mp_finish=0)
+            if r['evals'][0] != lmder['evals'][0]:
+                break
+        else:
+            raise SystemExit(f'{name}: no slice of the family reaches a second-order evaluation')
+        arrays.update({f'{name}_{k}': v for k, v in r.items()})
+        print(name, 'slice', first, 'iters', int(r['iters'].min()), int(r['iters'].max()), 'status', np.bincount(r['status']).tolist(),
+              'evaluations', int(r['evals'][0]), 'with mp_finish = 0', int(lmder['evals'][0]), flush=True)
+    ctx.close()
+    np.savez_compressed(out, **arrays)
+    print('wrote', out, os.path.getsize(out), 'bytes')
+
+
 def main():
     import d2dhip
+    if len(sys.argv) > 1 and sys.argv[1] == '--r10':
+        return main_r10(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, 'tests', 'golden', 'knot_r10_parent_bits.npz'))
     if len(sys.argv) > 1 and sys.argv[1] == '--r9':
         return main_r9(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, 'tests', 'golden', 'knot_r9_parent_bits.npz'))
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'tests', 'golden', 'knot_parent_bits.npz')

@@ -5,8 +5,9 @@ csrc/fit_knot.hip for gfx950 with the Makefile's flags: the whole kernel and the
 damped_solve (the basic block that holds its 16 MFMAs and its reciprocal roots), by class; registers / scratch / occupancy of all four
 instantiations; and (round 8) the evaluation's k-steps: every cluster of twenty or more accumulating MFMAs outside the factorisation,
 with the instructions between its first and last v_mfma and the branches among them; and (round 9) the block of the isq forward
-substitution, the one with the most v_readlane outside the factorisation's.  The per-item tables of DESIGN 5.3c (rounds 7 to 9) are
-this tool's output, commit by commit.
+substitution, the one with the most v_readlane outside the factorisation's; and (round 10) the second-order evaluation's k-steps on a
+line of their own, told from the first-order cluster by their A and B operand registers differing, beside the figure of the rolled
+pass they replace.  The per-item tables of DESIGN 5.3c (rounds 7 to 10) are this tool's output, commit by commit.
 
     python tools/knot_count.py [file.s]        (an assembly file already made with --cuda-device-only -S is read instead of compiling)"""
 import os
@@ -71,27 +72,34 @@ def main():
     # the factorisation's
     isq = max((b for b in blocks if b is not fact), key=lambda b: sum('v_readlane' in x for x in b))
     print('  isq           ', census(isq))
-    # the evaluation's k-steps: accumulating MFMAs (a register block as C) outside the factorisation blocks, clustered by position
+    # the evaluation's k-steps: accumulating MFMAs (a register block as C) outside the factorisation blocks, clustered by position.
+    # A first-order k-step multiplies the rows by themselves (A and B are one register); a second-order k-step (round 10) has a
+    # plain A operand and a weighted B operand: the two kinds are clustered apart and printed on lines of their own
     infact = {id(b) for b in blocks if any('v_rsq_f32' in x for x in b)}
-    pos, n = [], 0
+    pos, n = {'evaluation': [], 'second-order': []}, 0
     for b in blocks:
         for ln in b:
             if 'v_mfma_f32_16x16x4' in ln and id(b) not in infact and not ln.rstrip().endswith(', 0'):
-                pos.append(n)
+                ops = [o.strip() for o in ln.split(None, 1)[1].split(',')]
+                pos['evaluation' if ops[1] == ops[2] else 'second-order'].append(n)
             n += 1
     flat = [ln for b in blocks for ln in b]
-    clusters = [[]]
-    for q in pos:
-        if clusters[-1] and q - clusters[-1][-1] > 150:
-            clusters.append([])
-        clusters[-1].append(q)
-    for cl in clusters:
-        if len(cl) >= 20:
+    for kind, pp in pos.items():
+        clusters = [[]]
+        for q in pp:
+            if clusters[-1] and q - clusters[-1][-1] > 150:
+                clusters.append([])
+            clusters[-1].append(q)
+        big = [cl for cl in clusters if len(cl) >= 20]
+        for cl in big:
             span = flat[cl[0]:cl[-1] + 1]
             c = census(span)
             br = sum(1 for x in span if x.strip().startswith(('s_cbranch', 's_branch')))
-            print(f'  evaluation     {len(cl)} v_mfma: {c["all"]} instructions from the first to the last, {br} branches, '
+            print(f'  {kind:<14} {len(cl)} v_mfma: {c["all"]} instructions from the first to the last, {br} branches, '
                   f'{sum(1 for x in span if x.startswith(".LBB"))} labels; valu {c["valu"]} lds {c["lds"]} salu {c["salu"]} s_nop {c["s_nop"]}')
+        if kind == 'second-order':
+            print('  second-order   ' + ('(' if big else 'no straight-line pass; ') + 'before round 10: one rolled loop a segment, 24 instructions a sample -- 2 v_mfma, '
+                  '11 valu, 3 lds, 8 salu and s_nop -- so 1200 at K = 50' + (')' if big else ''))
     res = re.findall(r'^; (NumVgprs|ScratchSize|Occupancy): (\d+)', asm, re.M)
     names = re.findall(r'^\s+\.name:\s+\S*fit_lm_knot_kernelILb(\d)ELb(\d)E(?:Li(\d+)E)?', asm, re.M)
     sizes = re.findall(r'^; codeLenInByte = (\d+)', asm, re.M)
