@@ -14,6 +14,8 @@ cubic B-spline (C2: the Gauss panels of the plant step keep their order):
   SplineWindField.sample_num / sample_sym / -field    the planner's wind protocol (src/d2d/opty_utils.py:16-29) and the field with the
                                                       opposite sign (the planner's model has the wind with the opposite sign to the plant)
   GustModel(sigma, tau | L, V, seed, form_corr)       a stochastic gust on top of either wind, drawn inside the device loops
+  WindEstimator(x, y, t, lam, mu, w_max, prior).fit   the field fitted to a flown state history on the device (d2d_wind_fit): every
+                                                      aircraft is a moving anemometer; WindEstimate is what it returns
 
 Outside the spline's box every coordinate is clamped: the field is held at its boundary value, continuous but only C0 there.
 """
@@ -302,6 +304,123 @@ def plant_gust(gust):
     if gust is None or isinstance(gust, GustModel):
         return gust
     raise TypeError(f'{type(gust).__name__} is not a gust model: build one with d2d.wind.GustModel(sigma, tau=...)')
+
+
+class WindEstimate:
+    """What WindEstimator.fit returns: the fitted control points on the device with the estimator's geometry.  cp dev
+    [nt][2][ny][nx]; support dev [nt ny nx] (diag A^T A: how much data backs each control point); stats dev [8]
+    (d2dhip.WINDFIT_STATS).  Nothing here visits the host until field(), stats_host() or rms is asked for."""
+
+    def __init__(self, ctx, res, geom):
+        self.ctx, self.cp, self.support, self.stats = ctx, res['cp'], res.get('support'), res.get('stats')
+        self._field, self._geom, self._neg = res['field'], geom, None
+
+    def device_field(self, ctx=None):
+        """d2dhip.WindFieldC on the fitted control points (this object keeps them alive)."""
+        assert ctx is None or ctx is self.ctx, 'the estimate lives on the context that fitted it'
+        return self._field
+
+    def negated_device_field(self, ctx=None):
+        """A WindEstimate-like field object of -F, negated on the device (the planner's model adds its wind to the residual: a plan
+        for a plant that flies F is planned in -F); device_field(ctx) of the result is its WindFieldC."""
+        assert ctx is None or ctx is self.ctx, 'the estimate lives on the context that fitted it'
+        if self._neg is None:
+            cp = (-self.cp).contiguous()
+            f = self._field
+            self._neg = WindEstimate(self.ctx, dict(cp=cp, support=self.support, stats=self.stats,
+                                                    field=d2dhip.WindFieldC(f.nt, f.ny, f.nx, 0, f.t0, f.ht, f.x0, f.hx, f.y0, f.hy, cp.data_ptr())),
+                                     self._geom)
+        return self._neg
+
+    def field(self):
+        """The estimate as a host SplineWindField (synchronises): for Planner(exp) users and for plotting."""
+        g = self._geom
+        return SplineWindField(self.cp.cpu().numpy(), g['x0'], g['hx'], g['y0'], g['hy'], g['t0'], g['ht'])
+
+    def stats_host(self):
+        """dict of the eight numbers of stats (synchronises)."""
+        return dict(zip(d2dhip.WINDFIT_STATS, (float(v) for v in self.stats.cpu().numpy())))
+
+    @property
+    def rms(self):
+        """(rms_x, rms_y) of the fit's residual over the used samples, m/s: about the gust level (synchronises)."""
+        s = self.stats_host()
+        n = max(s['used'], 1.0)
+        return float(np.sqrt(s['rss_x'] / n)), float(np.sqrt(s['rss_y'] / n))
+
+
+class WindEstimator:
+    """Fits a SplineWindField to flown state histories on the device (include/d2d.h d2d_wind_fit).  x, y (and t, None: steady) are
+    uniform KNOT grids: the estimate lives on [x[0], x[-1]] x [y[0], y[-1]] (x [t[0], t[-1]]) with len + 2 control points per axis,
+    and samples outside that box are rejected.  lam: the weight of the second differences of the control points, one number or
+    (lam_x, lam_y, lam_t); mu > 0: the pull towards the prior, which decides the cells no aircraft visited; w_max: measurements above
+    it are rejected; prior: a constant (wx, wy) or a SplineWindField on the same grid (None: no wind); rec_stride: the stride at which
+    full_sim's loops keep the history they hand to fit (dt_row = t_step rec_stride; the trapezoid error grows with its square)."""
+
+    def __init__(self, x, y, t=None, lam=1e-2, mu=1e-6, w_max=50.0, prior=None, rec_stride=1, cg_tol=1e-10, cg_max=2000):
+        self.x0, self.hx = _grid(x, 'x'); self.y0, self.hy = _grid(y, 'y')
+        self.nx, self.ny = len(np.ravel(x)) + 2, len(np.ravel(y)) + 2
+        self.t0, self.ht, self.nt = 0.0, 1.0, 1
+        if t is not None:
+            self.t0, self.ht = _grid(t, 't')
+            self.nt = len(np.ravel(t)) + 2
+        if self.nt * self.ny * self.nx > d2dhip.WINDFIT_MAX_CP:
+            raise ValueError(f'x, y, t: {self.nt} x {self.ny} x {self.nx} control points, at most {d2dhip.WINDFIT_MAX_CP}')
+        lam3 = (float(lam),) * 3 if np.ndim(lam) == 0 else tuple(float(v) for v in lam)
+        if len(lam3) != 3 or not all(np.isfinite(v) and v >= 0 for v in lam3):
+            raise ValueError(f'lam={lam!r}: one number or (lam_x, lam_y, lam_t), finite and >= 0')
+        if not (np.isfinite(mu) and mu > 0):
+            raise ValueError(f'mu={mu!r} must be finite and > 0 (it decides the cells no aircraft visited)')
+        if not (np.isfinite(w_max) and w_max > 0):
+            raise ValueError(f'w_max={w_max!r} must be finite and > 0')
+        if int(rec_stride) != rec_stride or int(rec_stride) < 1:
+            raise ValueError(f'rec_stride={rec_stride!r} must be an integer >= 1')
+        if not (0 < cg_tol < 1) or int(cg_max) < 1:
+            raise ValueError(f'cg_tol={cg_tol!r} in (0, 1) and cg_max={cg_max!r} >= 1 required')
+        shape = (self.nt, 2, self.ny, self.nx)
+        if prior is None:
+            self.prior = None
+        elif isinstance(prior, SplineWindField):
+            same = prior.cp.shape == shape and np.allclose([prior.x0, prior.hx, prior.y0, prior.hy], [self.x0, self.hx, self.y0, self.hy]) \
+                and (self.nt == 1 or np.allclose([prior.t0, prior.ht], [self.t0, self.ht]))
+            if not same:
+                raise ValueError('prior: a SplineWindField prior must live on the estimator\'s own grid')
+            self.prior = np.array(prior.cp)
+        else:
+            pr = np.asarray(prior, dtype=np.float64).reshape(-1)
+            if pr.shape != (2,) or not np.isfinite(pr).all():
+                raise ValueError(f'prior={prior!r}: a constant (wx, wy) or a SplineWindField on the same grid')
+            self.prior = np.ascontiguousarray(np.broadcast_to(pr[None, :, None, None], shape))
+        self.lam, self.mu, self.w_max, self.rec_stride = lam3, float(mu), float(w_max), int(rec_stride)
+        self.cg_tol, self.cg_max = float(cg_tol), int(cg_max)
+        self._dev = weakref.WeakKeyDictionary()                                 # Context -> device prior
+
+    def geometry(self):
+        """The d2d_wind_field geometry of the estimate (SplineWindField's convention: n knots, n + 2 control points, first knot x[0])."""
+        return dict(nt=self.nt, ny=self.ny, nx=self.nx, t0=self.t0, ht=self.ht, x0=self.x0, hx=self.hx, y0=self.y0, hy=self.hy)
+
+    def device_field(self, ctx):
+        """The geometry as a d2dhip.WindFieldC without control points (what Context.wind_fit takes as its grid)."""
+        g = self.geometry()
+        return d2dhip.WindFieldC(g['nt'], g['ny'], g['nx'], 0, g['t0'], g['ht'], g['x0'], g['hx'], g['y0'], g['hy'], None)
+
+    def fit(self, ctx, X_hist, n_ac, dt_row, rows=None, t_start=None, outputs=None):
+        """X_hist dev [n_rows][5][N] (rows dev int32 [n_form], t_start dev [n_form] or a float as in Context.flight_audit) -> WindEstimate."""
+        prior = None
+        if self.prior is not None:
+            prior = self._dev.get(ctx)
+            if prior is None:
+                prior = self._dev[ctx] = ctx.dev(self.prior)
+        res = ctx.wind_fit(X_hist, n_ac, dt_row, self, rows=rows, t_start=t_start, prior=prior, w_max=self.w_max, lam=self.lam, mu=self.mu,
+                           cg_tol=self.cg_tol, cg_max=self.cg_max, outputs=outputs)
+        return WindEstimate(ctx, res, self.geometry())
+
+
+def wind_estimator(wind_estimate):
+    """A wind_estimate= argument: None, or a WindEstimator."""
+    if wind_estimate is None or isinstance(wind_estimate, WindEstimator):
+        return wind_estimate
+    raise TypeError(f'{type(wind_estimate).__name__} is not a wind estimator: build one with d2d.wind.WindEstimator(x, y, t)')
 
 
 def _is_constant_class(cls):

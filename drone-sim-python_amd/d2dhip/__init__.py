@@ -114,6 +114,22 @@ class AuditOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in AUDIT_OUT]
 
 
+WINDFIT_MAX_CP, WINDFIT_CHUNK = 4096, 64     # include/d2d.h D2D_WINDFIT_*
+WINDFIT_STATS = ('used', 'nonfinite', 'outside', 'over', 'rss_x', 'rss_y', 'cg_iters', 'cg_resid')   # the eight numbers of stats
+
+
+class WindFitParams(C.Structure):
+    """d2d_windfit_params (include/d2d.h)."""
+    _fields_ = [('n_form', C.c_int32), ('n_ac', C.c_int32), ('n_rows', C.c_int32), ('cg_max', C.c_int32), ('waves', C.c_int32),
+                ('reserved', C.c_int32), ('dt_row', C.c_double), ('w_max', C.c_double), ('lam_x', C.c_double), ('lam_y', C.c_double),
+                ('lam_t', C.c_double), ('mu', C.c_double), ('cg_tol', C.c_double)]
+
+
+class WindFitOut(C.Structure):
+    """d2d_windfit_out (include/d2d.h): device addresses of the optional outputs, None for one that is not wanted."""
+    _fields_ = [(k, C.c_void_p) for k in ('support', 'stats', 'H_out', 'b_out')]
+
+
 class FitOpts(C.Structure):
     _fields_ = [('max_iter', C.c_int32), ('check_every', C.c_int32), ('ftol', C.c_double),
                 ('gtol', C.c_double), ('xtol', C.c_double), ('so_lambda', C.c_double),
@@ -234,6 +250,8 @@ _SIGS = {
     'd2d_fit_profile_read': (C.c_int, [_P, _P]),
     'd2d_fit_coeffs': (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     'd2d_fit_sample': (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P]),
+    'd2d_wind_fit_workspace': (C.c_int64, [C.POINTER(WindFitParams), C.POINTER(WindFieldC)]),
+    'd2d_wind_fit': (C.c_int, [_P, C.POINTER(WindFitParams), _P, _P, _P, C.POINTER(WindFieldC), _P, _P, C.POINTER(WindFitOut)]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -896,6 +914,51 @@ class Context:
                                          C.byref(m), _ptr(mov_work), _ptr(work), C.byref(o)))
         out['mov_work'] = mov_work                    # (work is released here: the context's stream is torch's, whose allocator orders its reuse)
         return out
+
+    def wind_fit(self, X_hist, n_ac, dt_row, grid, rows=None, t_start=None, prior=None, w_max=50.0, lam=(1e-2, 1e-2, 1e-2), mu=1e-6,
+                 cg_tol=1e-10, cg_max=2000, outputs=None, waves=0):
+        """Fit a wind field to a state history that is on the device (d2d_wind_fit): X_hist dev [n_rows][5][N], N = n_form * n_ac, row i
+        of formation f at t_start[f] + i dt_row (t_start dev [n_form], a float or None: 0); rows dev int32 [n_form]: the valid rows
+        (None: all).  grid: a WindFieldC or an object with device_field(ctx) whose geometry (nt, ny, nx, knots) the estimate takes;
+        its control points are not read.  prior: dev [nt][2][ny][nx] the estimate is pulled towards with weight mu (None: 0).  lam =
+        (lam_x, lam_y, lam_t) or one number: the weights of the second differences.  outputs: of 'support', 'stats', 'H', 'b' (None:
+        support and stats).  waves: wavefronts of the accumulation launch (0: the library's choice; the bits do not depend on it).
+        Returns dict(cp dev [nt][2][ny][nx], field: a WindFieldC on cp, support dev [nt ny nx], stats dev [8] (WINDFIT_STATS),
+        H dev [nt ny nx][49 or 343], b dev [2][nt ny nx])."""
+        torch = _torch()
+        assert X_hist.dim() == 3 and X_hist.shape[1] == 5 and X_hist.is_contiguous() and X_hist.dtype == torch.float64 and X_hist.device.type == 'cuda'
+        n_rows, _, N = X_hist.shape
+        n_ac = int(n_ac)
+        n_form = N // n_ac if n_ac >= 1 else 0
+        assert n_ac < 1 or N == n_form * n_ac
+        assert rows is None or (rows.is_contiguous() and tuple(rows.shape) == (n_form,) and rows.dtype == torch.int32 and rows.device == X_hist.device)
+        t_start = self._t_start_dev(t_start, n_form, X_hist)
+        g0 = _wind_c(self, grid)
+        nt, ny, nx = int(g0.nt), int(g0.ny), int(g0.nx)
+        shape = (max(nt, 0), 2, max(ny, 0), max(nx, 0))
+        assert prior is None or (prior.is_contiguous() and tuple(prior.shape) == shape and prior.dtype == torch.float64 and prior.device == X_hist.device)
+        g = WindFieldC(nt, ny, nx, 0, g0.t0, g0.ht, g0.x0, g0.hx, g0.y0, g0.hy, None if prior is None else prior.data_ptr())
+        lam = (float(lam),) * 3 if np.ndim(lam) == 0 else tuple(float(v) for v in lam)
+        p = WindFitParams(n_form, n_ac, n_rows, int(cg_max), int(waves), 0, float(dt_row), float(w_max), lam[0], lam[1], lam[2], float(mu),
+                          float(cg_tol))
+        nbytes = self.lib.d2d_wind_fit_workspace(C.byref(p), C.byref(g))
+        if nbytes < 0:
+            _check(int(nbytes))
+        ncp = nt * ny * nx
+        work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
+        cp = self.empty(*shape)
+        want = ('support', 'stats') if outputs is None else tuple(outputs)
+        unknown = set(want) - {'support', 'stats', 'H', 'b'}
+        if unknown:
+            raise ValueError(f'outputs: unknown names {sorted(unknown)}')
+        out = dict(support=self.empty(ncp) if 'support' in want else None, stats=self.zeros(8) if 'stats' in want else None,
+                   H=self.empty(ncp, 49 if nt == 1 else 343) if 'H' in want else None, b=self.empty(2, ncp) if 'b' in want else None)
+        o = WindFitOut(_ptr(out['support']), _ptr(out['stats']), _ptr(out['H']), _ptr(out['b']))
+        _check(self.lib.d2d_wind_fit(self.h, C.byref(p), _ptr(X_hist), _ptr(rows), _ptr(t_start), C.byref(g), _ptr(cp), _ptr(work), C.byref(o)))
+        out = {k: v for k, v in out.items() if v is not None}
+        out['cp'] = cp
+        out['field'] = WindFieldC(nt, ny, nx, 0, g0.t0, g0.ht, g0.x0, g0.hx, g0.y0, g0.hy, cp.data_ptr())
+        return out                                    # (work is released here: the context's stream is torch's, whose allocator orders its reuse)
 
     def track_run(self, x_ref, y_ref, X0, dt, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), out=None, wind=None, t_start=0.0, gust=None,
                   gust_state=None, gust_phase=0, gust_n_ac=1, gust_stream_base=0, **kw):

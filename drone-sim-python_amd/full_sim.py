@@ -18,7 +18,7 @@ import numpy as np
 import d2dhip
 import d2d.dynamic as ddyn
 import d2d.multiopty_utils as d2mou
-from d2d.wind import plant_gust, plant_wind
+from d2d.wind import plant_gust, plant_wind, wind_estimator
 
 KE, KD, KR = 0.0004, 25, 20            # src/11_full_sim_case1.py:108-110
 X1_START = np.array([20, 30, -np.pi / 2, 0, 10])     # :113
@@ -61,7 +61,8 @@ def _audit_kw(ctx, audit, n_form, what):
 
 def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, t_end=1000, X0=None,
                                tau_phi=None, rec_stride=1, record=('X', 'U', 'Rr', 'eth'), W=(0., 0.), etheta_tol_deg=None,
-                               t_opt_comp=0.0, windfield=None, audit=None, gust=None, gust_state=None, gust_phase=0, gust_stream_base=0):
+                               t_opt_comp=0.0, windfield=None, audit=None, gust=None, gust_state=None, gust_phase=0, gust_stream_base=0,
+                               wind_estimate=None):
     """Many formations at once.  c (n_form, n_ac, 2) centres; r scalar or (n_form, n_ac); X0
     (n_form, n_ac, 5) or None (every aircraft starts at the reference's X1); X0f (n_form, n_ac, >=3)
     or None.  etheta_tol_deg: stop by the phase-error rule of cases 2 / 3 instead of the state rule (after t_opt_comp more seconds on
@@ -71,9 +72,14 @@ def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, 
     formation's rows up to its stop row (derived on the device), dt_row = t_step rec_stride; needs 'X' in record.
     gust: a d2d.wind.GustModel flown on top of W or the field (the law sees none of it); gust_state dev [4][N] or None (the stationary
     start), gust_phase: the loop's phase word, gust_stream_base: the global index of the first drone (a shard of a larger batch).
-    out['gust_state'] dev [4][N]: the state after each formation's last executed step; with 'g' in record out['g'] dev [n_rec][2][N]."""
+    out['gust_state'] dev [4][N]: the state after each formation's last executed step; with 'g' in record out['g'] dev [n_rec][2][N].
+    wind_estimate: a d2d.wind.WindEstimator -- out['wind_estimate'] is the WindEstimate fitted to the flight just made (d2d_wind_fit on
+    the recorded history: every formation's rows up to its stop row, dt_row = t_step rec_stride); needs 'X' in record."""
     if audit is not None and 'X' not in record:
         raise ValueError("audit needs the state history: 'X' must be in record")
+    est = wind_estimator(wind_estimate)
+    if est is not None and 'X' not in record:
+        raise ValueError("wind_estimate needs the state history: 'X' must be in record")
     fld = plant_wind(windfield)
     gkw = {} if plant_gust(gust) is None else dict(gust=gust, gust_state=gust_state, gust_phase=gust_phase, gust_stream_base=gust_stream_base)
     ctx = d2dhip.default_context()
@@ -92,11 +98,14 @@ def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, 
                       stop_hold=hold_steps(t_opt_comp, t_step) if etheta_tol_deg is not None else 0,
                       **({} if fld is None else dict(wind=fld, t_start=float(time[0]))), **gkw)
     out['time'] = time
-    if audit is not None:
+    if audit is not None or est is not None:
         torch = d2dhip._torch()
-        kw = _audit_kw(ctx, audit, n_form, ())
         rows = ((torch.clamp(out['stop_row'], max=len(time)) + (rec_stride - 1)) // rec_stride).to(torch.int32)
+    if audit is not None:
+        kw = _audit_kw(ctx, audit, n_form, ())
         out['audit'] = ctx.flight_audit(out['X'], n_ac, t_step * rec_stride, rows=rows, t_start=float(time[0]), **kw)
+    if est is not None:
+        out['wind_estimate'] = est.fit(ctx, out['X'], n_ac, t_step * rec_stride, rows=rows, t_start=float(time[0]))
     return out
 
 
@@ -200,16 +209,21 @@ def ExtendTraj_symm(n_ac, x_ref, y_ref, psi_ref, time):
 
 
 def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr', 'dX', 'Yd', 'Ydd'), windfield=None, audit=None,
-                               gust=None, gust_state=None, gust_phase=0, gust_n_ac=1, gust_stream_base=0):
+                               gust=None, gust_state=None, gust_phase=0, gust_n_ac=1, gust_stream_base=0, wind_estimate=None):
     """x_ref, y_ref (T, n) for n independent drones; X0s (n, 5).  Device dictionary out.  windfield: a SplineWindField the plant
     flies (row i at time[i]); the controller keeps w, as DiffController(w) does (src/11_full_sim_case1.py:241-291).
     audit: True or a dict (d_safe, err_tol, static: _audit_kw; n_ac: consecutive drones that form a formation, default 1 -- the
     drones are independent) -- out['audit'] is Context.flight_audit of the flown history against x_ref, y_ref; needs 'X' in record.
     gust: a d2d.wind.GustModel flown on top of w or the field (the controller sees none of it); gust_state, gust_phase,
     gust_stream_base as in CircularFormationGVF_batch, gust_n_ac: consecutive drones that share the formation part of the gust.
-    out['gust_state'] dev [4][n]; with 'g' in record out['g'] dev [T][2][n]."""
+    out['gust_state'] dev [4][n]; with 'g' in record out['g'] dev [T][2][n].
+    wind_estimate: a d2d.wind.WindEstimator -- out['wind_estimate'] is the WindEstimate fitted to the flown history (every drone its
+    own formation, row i at time[i]); needs 'X' in record."""
     if audit is not None and 'X' not in record:
         raise ValueError("audit needs the state history: 'X' must be in record")
+    est = wind_estimator(wind_estimate)
+    if est is not None and 'X' not in record:
+        raise ValueError("wind_estimate needs the state history: 'X' must be in record")
     fld = plant_wind(windfield)
     gkw = {} if plant_gust(gust) is None else dict(gust=gust, gust_state=gust_state, gust_phase=gust_phase, gust_n_ac=gust_n_ac,
                                                    gust_stream_base=gust_stream_base)
@@ -224,6 +238,8 @@ def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr
         n_ac = 1 if audit is True else int(audit.get('n_ac', 1))
         kw = _audit_kw(ctx, audit, xr.shape[1] // n_ac, ('n_ac',))
         out['audit'] = ctx.flight_audit(out['X'], n_ac, float(dt), t_start=float(time[0]), x_ref=xr, y_ref=yr, **kw)
+    if est is not None:
+        out['wind_estimate'] = est.fit(ctx, out['X'], 1, float(dt), t_start=float(time[0]))
     return out
 
 
@@ -379,7 +395,7 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
 
 def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_sim_end=200., w=(0., 0.), t_step=0.05,
                           t_end_1=1000., X0=None, max_sweeps=250, record2=('X', 'U'), record3=('X', 'U'), windfield=None,
-                          moving_obstacles=None, audit=None, gust=None, gust_stream_base=0):
+                          moving_obstacles=None, audit=None, gust=None, gust_stream_base=0, wind_estimate=None):
     """The three phases of src/11_full_sim_case1.py main() (:406-478) for many independent formations, chained ON THE
     DEVICE: the circular-formation phase hands its final states to the planner as a device tensor, the planner's sampled
     plan is the tracking reference of phase 2 without leaving HBM, and phase 3 restarts from phase 2's final states.
@@ -422,7 +438,13 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     on top of w or F -- an unmeasured disturbance: neither the controllers nor the plan see it.  Every loop counts its steps from 1
     under its own phase word (phase 1: 0, phase 2: 1, repetition k of phase 3: 2 + k) and hands its gust state to the next on the
     device (phase*['gust_state'] dev [4][N]; 'g' in record2 / record3 keeps the flown gusts); gust_stream_base: the global index of the
-    first drone when the formations are a shard of a larger study."""
+    first drone when the formations are a shard of a larger study.
+    wind_estimate: None (every path above, bit for bit) or a d2d.wind.WindEstimator -- the planner is no longer handed the truth.  Phase 1
+    keeps its state history on the device at the estimator's rec_stride, the field F^ is fitted to it (d2d_wind_fit, rows = the
+    formations' stop rows) and the transition is planned in -F^ instead of -F (d2d_nlp_solve_groups_wind, or with moving_obstacles that
+    path's field form), the fit's rows taking F^ at each aircraft's start; phases 2 and 3 fly the true windfield (or the constant w).
+    No state visits the host between the phases.  out['wind_fit']: dict(estimate: the WindEstimate, stats dev [8], support dev,
+    rms = (rms_x, rms_y), read when every launch is queued); plan['field'] is -F^."""
     import multi_opt_planner as mop
     if audit is not None and ('X' not in record2 or (ref3 is not None and 'X' not in record3)):
         raise ValueError("audit needs the flown histories: 'X' must be in record2 and record3")
@@ -432,6 +454,7 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     import d2d.opty_utils as d2ou
     F = plant_wind(windfield)
     gust = plant_gust(gust)
+    est = wind_estimator(wind_estimate)
 
     def gk(phase, state, track=False):
         """the gust arguments of the loop with this phase word (track: of Context.track_run, which is told the formation size)"""
@@ -445,7 +468,9 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     n_form = c.shape[0]
     X1f = np.broadcast_to(np.asarray(X1_f, dtype=np.float64).reshape(-1, n_ac, np.shape(X1_f)[-1])[:, :, :3], (n_form, n_ac, 3))
     X2f = np.broadcast_to(np.asarray(X2_f, dtype=np.float64).reshape(-1, n_ac, np.shape(X2_f)[-1])[:, :, :3], (n_form, n_ac, 3))
-    ph1 = CircularFormationGVF_batch(c, r, v, n_ac, X0f=X1f, t_step=t_step, t_end=t_end_1, X0=X0, record=(), windfield=F, **gk(0, None))
+    ph1 = CircularFormationGVF_batch(c, r, v, n_ac, X0f=X1f, t_step=t_step, t_end=t_end_1, X0=X0, windfield=F, **gk(0, None),
+                                     **(dict(record=()) if est is None else dict(record=('X',), rec_stride=est.rec_stride, wind_estimate=est)))
+    known = F if est is None else ph1['wind_estimate']            # what the planner knows of the field the plant flies
     Xs1 = ph1['X_final']                                            # dev [5][N]: state at each formation's stop row
     # ---- phase 2: plan from where phase 1 ended (scenario rows finished on the device) ----
     scen.t1 = t_opt
@@ -456,11 +481,11 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     dsc = ctx.dev(rows)
     dsc[:, d2dhip.SC_X0], dsc[:, d2dhip.SC_Y0], dsc[:, d2dhip.SC_PSI0] = Xs1[0], Xs1[1], Xs1[2]
     moving = list(moving_obstacles or [])
-    if F is not None or moving:
+    if known is not None or moving:
         t2 = (torch.clamp(ph1['stop_row'], max=len(ph1['time'])) - 1).to(torch.float64) * float(t_step)      # dev [n_form]
-    if F is not None:
+    if known is not None:
         t2d = t2.repeat_interleave(n_ac).contiguous()                                                       # dev [N]: per drone
-        w0 = ctx.wind_sample(F, t2d, Xs1[:2].contiguous())         # (the rows store -w of the planner's wind: -(-F) = F)
+        w0 = ctx.wind_sample(known, t2d, Xs1[:2].contiguous())         # (the rows store -w of the planner's wind: -(-F) = F)
         dsc[:, d2dhip.SC_WX], dsc[:, d2dhip.SC_WY] = w0[0], w0[1]
     q = plan.init(dsc)
     if coupled:
@@ -476,21 +501,22 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     kw = dict(w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v)
     kw2 = {}
     pairs = mop.scenario_pairs(scen, n_ac)                          # None: the reference's pair (0, 1), the chain as it was
-    if moving or F is not None or pairs is not None:
+    if moving or known is not None or pairs is not None:
         # the fit was the guess, the collocation problem decides: around the discs from t2, in -F from t2, over a cost's own pairs
-        Fp = None if F is None else F.negated()
+        Fp = None if known is None else (F.negated() if est is None else known.negated_device_field(ctx))
         Xs = Xs.contiguous().clone()
         knots, disc = _moving_tables(ctx, moving, n_form) if moving else (None, None)
-        sol = d2dhip.nlp_plan(ctx, dsc, Xs, float(dt2), n_ac=n_ac, knots=knots, disc=disc, field=Fp, t_start=t2 if (moving or F is not None) else None,
+        sol = d2dhip.nlp_plan(ctx, dsc, Xs, float(dt2), n_ac=n_ac, knots=knots, disc=disc, field=Fp, t_start=t2 if (moving or known is not None) else None,
                               pairs=pairs is not None)
         pl.update(cost_fit=cost, cost=sol['cost'], Xs=Xs, W=Xs, feas=sol['feas'], status=sol['status'], iters=sol['iters'],
                   sweeps=sol['sweeps'], moved=sol['moved'])
-        if moving or F is not None:
+        if moving or known is not None:
             pl['t_start'] = t2
         if moving:
             pl.update(mov_work=sol['mov_work'], moving=(knots, disc))
-        if F is not None:
+        if known is not None:
             pl['field'] = Fp
+        if F is not None:
             kw['wind'] = F
             kw2 = dict(t_start=t2d)
     if pairs is not None:
@@ -531,6 +557,8 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
             X_last = ph3['X_final']
             t_final += float(time_3[-1])
             k += 1
+    if est is not None:
+        out['wind_fit'] = dict(estimate=known, stats=known.stats, support=known.support, rms=known.rms)
     return out
 
 

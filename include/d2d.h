@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 121
+#define D2D_VERSION 122
 
 /* error codes */
 #define D2D_OK 0
@@ -1033,6 +1033,76 @@ int64_t d2d_flight_audit_workspace(const d2d_audit_params *p, int n_mov);
 int d2d_flight_audit(d2d_ctx *ctx, const d2d_audit_params *p, const double *X_hist, const int32_t *rows, const double *t_start,
                      const double *x_ref, const double *y_ref, const double *stat, const d2d_moving_obstacles *mov, double *mov_work,
                      void *work, const d2d_audit_out *out);
+
+/* ---- Wind-field estimation from flown histories (version 122) ---------------------------------------------------------------------
+ * Every aircraft of a history is a moving anemometer: ground velocity minus air velocity is the wind at its own position and time.
+ * d2d_wind_fit fits the control points of a d2d_wind_field (geometry given by the caller) to a history that is on the device.
+ * tests/wind_fit_ref.py is the CPU statement (numpy / scipy.sparse), including the fixed-point rule below, bit for bit.
+ *
+ * Input.  X_hist dev [n_rows][5][N] (planes x, y, psi, phi, v; N = n_form * n_ac), rows dev int32 [n_form] (NULL: n_rows; clamped to
+ * 0 .. n_rows; a row at an index >= rows[f] is never read), t_start dev [n_form] (NULL: 0), dt_row: as in d2d_flight_audit.
+ * Measurement.  Two consecutive valid rows i, i + 1 of one drone give one sample (trapezoid rule):
+ *   value     m = (p[i+1] - p[i]) / dt_row - 1/2 (v[i] u(psi[i]) + v[i+1] u(psi[i+1])),  u = (cos, sin)
+ *   position  1/2 (p[i] + p[i+1]),   time  t_start[f] + (i + 1/2) dt_row.
+ * Its error is O(dt_row^2), about dt_row^2 / 12 * v * psidot^2.  psi enters through cos and sin only (its wrap is harmless); both are
+ * computed by one fixed sequence of IEEE operations (Cody-Waite reduction by pi/2 in three parts, the fdlibm kernel polynomials,
+ * no fused multiply-add; within 2 ulp for |psi| <= 1e6) that the CPU statement repeats, so that m is the same bits on both sides.
+ * Rejection, counted by reason, in this order: (1) one of the ten numbers of the two rows (or, with nt > 1, the sample time) is not
+ * finite; (2) the midpoint is outside the grid's box [x0, x0 + (nx - 3) hx] x [y0, y0 + (ny - 3) hy] (x [t0, t0 + (nt - 3) ht] when
+ * nt > 1) -- rejected, not clamped: clamping would bias the boundary control points; (3) |m_x| or |m_y| > w_max.
+ * Unknowns.  c [nt ny nx] per component, nt ny nx <= D2D_WINDFIT_MAX_CP; wx and wy share the design matrix (two right-hand sides).
+ * Design row.  The 16 (nt = 1: by[a] bx[b]) or 64 (bt[c] (by[a] bx[b])) tensor-product weights of the sample's cell, with the axis
+ * weights of d2d_wind_field (segment i = min(floor(s), n - 4), r = s - i, B_k(r)), evaluated without fused multiply-add.
+ * Objective.  sum_s |A_s c - m_s|^2 + lam_x sum (d2_x c)^2 + lam_y sum (d2_y c)^2 + lam_t sum (d2_t c)^2 + mu sum (c - c_prior)^2,
+ * d2 the second difference of the control points along an axis (interior points only), c_prior = grid->cp (NULL: 0).  mu > 0 is
+ * required: a cell that no aircraft visited is otherwise undetermined.
+ * Normal matrix.  H = A^T A is stored by stencil: H_out dev [nt ny nx][S], S = 49 (nt = 1) or 343, entry
+ * [p][((dt + 3) 7 + (dy + 3)) 7 + (dx + 3)] (steady: [(dy + 3) 7 + (dx + 3)]) couples p and the point at offset (dt, dy, dx); entries
+ * whose partner is outside the grid are 0.  b_out dev [2][nt ny nx] = A^T m.
+ * Fixed point, and why every output is independent of the order of the work.  Every product w_i w_j of a sample (in [0, 1]) is
+ * rounded to a multiple of 2^-32 (round to nearest even) and every w_i m / W, W = w_max rounded up to a power of two, likewise; the
+ * sums are integers: exact in fp64 registers for up to 2^20 samples, then added to the 64-bit stencil storage with integer
+ * atomics.  Integer addition is associative and commutative, so H_out, b_out, support, the counts and with them cp_out are bit-identical from call to call, under
+ * any permutation of the formations (rows and t_start permuted alike) and for every launch geometry (p->waves): where a wavefront
+ * hands its sums over (when its cell changes, at the end of its share) schedules the work and nothing else.  Quantisation: at most
+ * 2^-33 per sample and entry of H, 2^-33 W per sample and entry of b.  (n_rows - 1) N < 2^31 keeps every sum below 2^63: beyond,
+ * D2D_EINVAL.  H and b of several ranks add exactly in this form.
+ * The work is cut into units of D2D_WINDFIT_CHUNK consecutive samples of one drone (one wavefront-load); a wavefront walks its units
+ * in time order.  The workspace does not grow with the number of samples.
+ * Solve.  (H + penalties + mu I) c = A^T m + mu c_prior for both components by Jacobi-preconditioned conjugate gradients in fp64, one
+ * workgroup, every reduction in a fixed order, from c = c_prior, until |r| <= cg_tol |rhs| per component or cg_max iterations.
+ * Outputs.  cp_out dev [nt][2][ny][nx]: with the caller's geometry a d2d_wind_field, no host visit.  d2d_windfit_out (any NULL):
+ *   support dev [nt ny nx]   diag A^T A: how much data backs each control point
+ *   stats   dev double [8]   samples used; rejected as non-finite, outside the box, above w_max; residual sum of squares of the fitted
+ *                            field over the used samples, x and y (a second streaming pass whose partials are folded in a fixed order;
+ *                            the RMS residual is about the gust level); CG iterations; largest relative CG residual reached
+ *   H_out, b_out             as above
+ * A formation with fewer than two valid rows contributes nothing; with no sample at all the answer is the prior (not an error).
+ * work: device memory of d2d_wind_fit_workspace(p, grid) bytes (negative: D2D_EINVAL), 16-byte aligned, overwritten.
+ * D2D_EINVAL before anything is launched: NULL ctx, p, X_hist, grid, cp_out or work; a geometry d2d_wind_sample refuses (grid->cp may
+ * be NULL here); nt ny nx > D2D_WINDFIT_MAX_CP; n_rows < 2, n_form < 1, n_ac outside 1 .. 64; dt_row, w_max or mu not > 0 or not
+ * finite; a negative or non-finite lam_*; cg_tol not in (0, 1); cg_max < 1; waves < 0; (n_rows - 1) N >= 2^31.  Asynchronous on the
+ * context's stream. */
+#define D2D_WINDFIT_MAX_CP 4096
+#define D2D_WINDFIT_CHUNK 64
+typedef struct {
+  int32_t n_form, n_ac;       /* n_ac 1 .. 64 */
+  int32_t n_rows;             /* rows of X_hist (>= 2) */
+  int32_t cg_max;             /* >= 1 */
+  int32_t waves;              /* wavefronts of the accumulation launch, 0: the library's choice (schedules only: same bits) */
+  int32_t reserved;
+  double dt_row;
+  double w_max;               /* a sample with a component above it is rejected */
+  double lam_x, lam_y, lam_t; /* >= 0 (lam_t is not read when nt = 1) */
+  double mu;                  /* > 0 */
+  double cg_tol;              /* in (0, 1) */
+} d2d_windfit_params;
+typedef struct {
+  double *support, *stats, *H_out, *b_out;
+} d2d_windfit_out;
+int64_t d2d_wind_fit_workspace(const d2d_windfit_params *p, const d2d_wind_field *grid);
+int d2d_wind_fit(d2d_ctx *ctx, const d2d_windfit_params *p, const double *X_hist, const int32_t *rows, const double *t_start,
+                 const d2d_wind_field *grid, double *cp_out, void *work, const d2d_windfit_out *out);
 
 #ifdef __cplusplus
 }
