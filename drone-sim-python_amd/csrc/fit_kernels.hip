@@ -1038,8 +1038,13 @@ fit_groups_kernel(int R, int n_ac, int nds, FitGeom g, FusedLds L, d2d_fit_opts 
       }
       return F;
     };
+    // A group is refused whole when the first evaluation of any of its aircraft is not finite (a NaN or inf in its row -- its
+    // partners then read NaN positions --, a cost that overflows): one cost-only pass over the group before the first sweep, so
+    // that no aircraft has moved by then.  Every q row of the group keeps the caller's bits, the group reports 0 sweeps and a NaN
+    // move, its aircraft D2D_ST_NONFINITE with the costs of that evaluation.
+    const bool refused = !(fabs(joint_merit(q_io, n)) <= 1.79e308);
     double moved_prev = 1e300;
-    for (sweep = 1; sweep <= max_sweeps; ++sweep) {
+    for (sweep = 1; sweep <= (refused ? 0 : max_sweeps); ++sweep) {
       moved = 0.0;
       if (sweep == prio_at) __builtin_amdgcn_s_setprio(2);      // a scenario that is still sweeping decides when the launch ends
       for (int a = 0; a < n_ac; ++a) {
@@ -1183,6 +1188,7 @@ fit_groups_kernel(int R, int n_ac, int nds, FitGeom g, FusedLds L, d2d_fit_opts 
       moved_prev = moved;
     }
     if (sweep > max_sweeps) sweep = max_sweeps;
+    if (refused) { sweep = 0; moved = __builtin_nan(""); }
     __builtin_amdgcn_s_setprio(0);
     // per-aircraft sub-problem cost and gradient with everybody's final positions
     for (int a = 0; a < n_ac; ++a) {
@@ -1203,7 +1209,7 @@ fit_groups_kernel(int R, int n_ac, int nds, FitGeom g, FusedLds L, d2d_fit_opts 
       if (act) g_out[(size_t)b * n + lane] = gi;
       if (lane == 0) {
         cost_out[b] = c;
-        flags[4 * b + FL_STATUS] = settled ? D2D_ST_CONVERGED : D2D_ST_MAXITER;
+        flags[4 * b + FL_STATUS] = refused ? D2D_ST_NONFINITE : (settled ? D2D_ST_CONVERGED : D2D_ST_MAXITER);
         flags[4 * b + FL_ITERS] = sweep;
         flags[4 * b + FL_NEVAL] = (a == 0) ? nev_total : 0;
       }
@@ -1840,7 +1846,9 @@ fit_count_below_kernel(int B, const int32_t *__restrict__ flags, int cap, int32_
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(counter, (int)__popcll(m));
 }
 
-// stats[0] += cost, stats[1] = max gmax, stats[2] += not converged, stats[3] += evaluations
+// stats[0] += cost (the finite ones), stats[1] = max gmax (finite entries of the fits not refused), stats[2] += neither converged nor stalled,
+// stats[3] += evaluations.  A refused fit (D2D_ST_NONFINITE: cost NaN or inf) adds to stats[2] only: one refusal must not erase
+// the batch's sum, which is also the local term of the cross-GPU all-reduce (d2dhip/dist.py).
 __global__ void __launch_bounds__(256)
 fit_stats_kernel(int B, int n, const double *__restrict__ cost, const double *__restrict__ g,
                  const int32_t *__restrict__ flags, double *__restrict__ stats) {
@@ -1848,8 +1856,13 @@ fit_stats_kernel(int B, int n, const double *__restrict__ cost, const double *__
   double c = 0.0, gm = 0.0, nr = 0.0, ne = 0.0;
   if (b < B) {
     c = cost[b];
-    for (int j = 0; j < n; ++j) gm = fmax(gm, fabs(g[(size_t)b * n + j]));
+    if (!(fabs(c) <= 1.79e308)) c = 0.0;
     const int st = flags[4 * b + FL_STATUS];
+    if (st != D2D_ST_NONFINITE)                     // (the J^T r of a refused fit is unspecified: finite and huge beside a cost that overflowed)
+      for (int j = 0; j < n; ++j) {
+        const double gj = fabs(g[(size_t)b * n + j]);
+        if (gj <= 1.79e308) gm = fmax(gm, gj);
+      }
     nr = (st == D2D_ST_CONVERGED || st == D2D_ST_STALLED) ? 0.0 : 1.0;
     ne = 0.5 * flags[4 * b + FL_NEVAL];            // evaluations in units of a Gauss-Newton one (200 rows; second-order: 1.5)
   }

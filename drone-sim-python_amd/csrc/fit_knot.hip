@@ -1126,7 +1126,9 @@ fit_lm_knot_kernel(int B, KnotGeom kg, KnotLds L, d2d_fit_opts opts, int iter_ca
           a0 = fma(bt[4 * j + 2], gv[8 * j + 2], a0); a1 = fma(bt[4 * j + 3], gv[8 * j + 3], a1);
         }
         gq = a0 + a1;
-        q_io[(size_t)b * N + lane_io] = qv;
+        // (a refused fit -- first evaluation not finite -- keeps the caller's q: Bq (u - u0) is the caller's row only to rounding,
+        // and NaN when the end pose is)
+        if (status != D2D_ST_NONFINITE) q_io[(size_t)b * N + lane_io] = qv;
         g_io[(size_t)b * N + lane_io] = gq;
         if (status == D2D_ST_RUNNING) u_io[(size_t)b * 64 + lane_io] = ui;      // (only a fit that will be resumed needs its knot vector kept)
       }

@@ -1131,7 +1131,8 @@ class FitPlan:
         _check(self.ctx.lib.d2d_fit_plan_set_group_order(self.ctx.h, self.h, R, 1 if enable else 0))
 
     def group_report(self, R):
-        """(sweeps int32 [R], last-sweep largest relative move float64 [R]) of the last solve_groups over R scenarios."""
+        """(sweeps int32 [R], last-sweep largest relative move float64 [R]) of the last solve_groups over R scenarios.
+        A refused scenario (a first evaluation that is not finite: include/d2d.h d2d_fit_group_report) reports 0 sweeps and a NaN move."""
         sw = np.zeros(R, np.int32); mv = np.zeros(R)
         _check(self.ctx.lib.d2d_fit_group_report(self.ctx.h, self.h, R, _hptr(sw), _hptr(mv)))
         return sw, mv

@@ -60,7 +60,7 @@ int d2d_ctx_sync(d2d_ctx *ctx);   /* hipStreamSynchronize on the context's strea
  *                       host has (a file, MPI, a TCP store);
  *   d2d_comm_create     every rank, same id: ncclCommInitRank on the context's device;
  *   d2d_allreduce_stats stats dev double[3] in place, enqueued on the context's stream as ONE grouped exchange:
- *                       [0] sum (cost), [1] max (|J^T r|_inf), [2] sum (trajectories still running) -- the three scalars
+ *                       [0] sum (cost), [1] max (|J^T r|_inf), [2] sum (trajectories neither converged nor stalled) -- the three scalars
  *                       d2d_fit_finish reports in stats[0..2].  The caller synchronises the stream before reading them. */
 typedef struct d2d_comm d2d_comm;
 #define D2D_COMM_ID_BYTES 128
@@ -565,9 +565,28 @@ int d2d_fit_jtj(d2d_ctx *ctx, d2d_fit_plan *plan, int B, float *H);
 
 /* Full Levenberg-Marquardt solve from q (in/out).  cost dev [B], iters / status dev int32 [B]
  * (any may be NULL).  stats host double[4] (may be NULL): sum cost, max |J^T r|_inf,
- * trajectories still running, evaluations performed (in units of one Gauss-Newton evaluation = 200
- * contracted rows at K = 50; an evaluation with the second-order blocks contracts 1.5 times as many and counts
- * 1.5) -- the local contribution to the cross-GPU convergence all-reduce.  Synchronises the stream before returning. */
+ * trajectories that ended neither D2D_ST_CONVERGED nor D2D_ST_STALLED, evaluations performed (in units of one Gauss-Newton
+ * evaluation = 200 contracted rows at K = 50; an evaluation with the second-order blocks contracts 1.5 times as many and counts
+ * 1.5) -- the local contribution to the cross-GPU convergence all-reduce.  Synchronises the stream before returning.
+ *
+ * Terminal states of a fit (every kernel of the family -- knot, fused, long horizon, launch pairs -- keeps them; the reference is
+ * oracle/fit.py lm_solve / solve_minpack and oracle/fit_knot.py solve_minpack_knot; tests/test_fit_terminal_cpu.py,
+ * tests/test_gpu_fit_terminal.py):
+ *   D2D_ST_CONVERGED, D2D_ST_STALLED   the solver's own stop tests; q is the last accepted point, cost the cost there.
+ *   D2D_ST_NONFINITE   a REFUSED fit: its first evaluation is not finite -- a NaN or inf anywhere its row is read (end poses, wind,
+ *                      weights), or a finite row whose cost overflows.  iters = 0; cost is the non-finite value of that evaluation
+ *                      (NaN for a NaN input; +inf for an overflow; an inf input gives NaN or inf as the arithmetic has it); its q row
+ *                      keeps the caller's bits; its J^T r is unspecified.  It is never RUNNING: the
+ *                      count of d2d_fit_iterate leaves it out, every loop on that count ends.  The other fits of the launch
+ *                      have the bits they have when the bad rows are replaced by healthy ones, whatever the hand-out order.
+ *   D2D_ST_MAXITER     a CAPPED fit: it has used exactly opts->max_iter trial points (iters == max_iter) and none of the stop
+ *                      tests held.  q is the last accepted point (the start point if no trial was accepted), cost the cost there:
+ *                      never above the cost at the start.  Every other status comes with iters <= max_iter.
+ * stats: [0] sums the FINITE costs only (a refused fit adds nothing: one refusal does not turn the batch's sum, or the job's
+ * all-reduced sum, into NaN; without refusals nothing differs), [1] is the largest finite |J^T r| entry of the fits that were not
+ * refused, [2] counts the fits
+ * that ended neither CONVERGED nor STALLED -- capped and refused fits (and, from d2d_fit_finish before the cap, the running ones):
+ * a count of unsettled fits, not a loop condition.  Loop on d2d_fit_iterate's n_running. */
 int d2d_fit_solve(d2d_ctx *ctx, const d2d_fit_plan *plan, int B, const double *scen, double *q,
                   const d2d_fit_opts *opts, double *cost, int32_t *iters, int32_t *status,
                   double *stats);
@@ -577,6 +596,11 @@ int d2d_fit_solve(d2d_ctx *ctx, const d2d_fit_plan *plan, int B, const double *s
  * iterate runs up to n_iters more damped solves (never beyond opts->max_iter in total) and,
  * if n_running != NULL, synchronises and returns how many trajectories are still running (once max_iter is
  * reached it returns 0 without synchronising); finish refreshes cost / J^T r and exports as d2d_fit_solve.
+ * n_running counts D2D_ST_RUNNING alone: a refused fit (D2D_ST_NONFINITE, see d2d_fit_solve) leaves the count at its first
+ * evaluation, a capped one at max_iter, so `while (n_running > 0)` ends whatever the rows hold.  d2d_fit_finish before the cap
+ * exports the fits that were still running as they stand -- D2D_ST_RUNNING, iters = the trials used, q the last accepted point,
+ * cost the cost there: bit for bit the q and cost of a solve capped at that many trials by max_iter, which names the same fits
+ * D2D_ST_MAXITER -- and counts them in stats[2].
  * Between begin and finish the solve owns q: every d2d_fit_iterate and the d2d_fit_finish of one solve take the SAME q buffer
  * (another pointer is D2D_EINVAL -- the persistent kernels keep the state of the fits that are still running against it, the knot
  * kernel in its own coordinates, so an edited or swapped buffer would be ignored) and options that select the same kernel (a change
@@ -639,7 +663,13 @@ int d2d_fit_solve_groups(d2d_ctx *ctx, d2d_fit_plan *plan, int R, const double *
                          double *cost, int32_t *sweeps_done, double *stats);
 /* Per-scenario report of the last d2d_fit_solve_groups of this plan (persistent-kernel path): sweeps HOST int32 [R] = sweeps each
  * scenario used, moved HOST double [R] = its largest relative move in the last of them (<= tol: settled); either may be NULL.
- * D2D_ESTATE if the plan holds no such solve over R scenarios.  Synchronous. */
+ * D2D_ESTATE if the plan holds no such solve over R scenarios.  Synchronous.
+ * A REFUSED scenario reports sweeps = 0 and moved = NaN: a scenario is refused whole when the first evaluation of any of its
+ * aircraft is not finite (d2d_fit_solve's D2D_ST_NONFINITE; the partners of an aircraft with a NaN end pose read NaN positions).
+ * No aircraft of it is visited, every q row of it keeps the caller's bits, its costs are the non-finite values of that
+ * evaluation (a finite one for an aircraft that is not coupled to the bad one), and d2d_fit_solve_groups' stats leave it out:
+ * [0] sums the finite costs, [2] is the largest move of the scenarios that swept.  The other scenarios of the launch are
+ * bit for bit what they are beside a healthy row. */
 int d2d_fit_group_report(d2d_ctx *ctx, d2d_fit_plan *plan, int R, int32_t *sweeps, double *moved);
 
 /* Per-launch timing of the LM loop with HIP events on the context's stream: enable = 1

@@ -963,8 +963,8 @@ def solve_minpack(basis, sc, q0=None, finish=MP_FINISH, max_iter=200, mp_tol=1e-
                                        hess_dtype=hess_dtype, chol_dtype=chol_dtype, finish=finish if finish > 0 else None,
                                        slow=slow if finish > 0 else None)
     it = nfev - 1
-    out = {'nfac': info['nfac'], 'mp_trials': it, 'handover': info['handover']}
-    if info['handover'] and it < max_iter:
+    out = {'nfac': info.get('nfac', 0), 'mp_trials': it, 'handover': info.get('handover', False)}      # (a refused fit: lmder_solve's info is empty)
+    if out['handover'] and it < max_iter:
         q, c, it2, st = lm_solve(basis, sc, q0=q, max_iter=max_iter - it, ftol=ftol, gtol=gtol, xtol=xtol, hess_dtype=hess_dtype,
                                  chol_dtype=chol_dtype, so_lambda=1e300)
         it += it2
