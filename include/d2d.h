@@ -1079,7 +1079,9 @@ int d2d_flight_audit(d2d_ctx *ctx, const d2d_audit_params *p, const double *X_hi
  * no fused multiply-add; within 2 ulp for |psi| <= 1e6) that the CPU statement repeats, so that m is the same bits on both sides.
  * Rejection, counted by reason, in this order: (1) one of the ten numbers of the two rows (or, with nt > 1, the sample time) is not
  * finite; (2) the midpoint is outside the grid's box [x0, x0 + (nx - 3) hx] x [y0, y0 + (ny - 3) hy] (x [t0, t0 + (nt - 3) ht] when
- * nt > 1) -- rejected, not clamped: clamping would bias the boundary control points; (3) |m_x| or |m_y| > w_max.
+ * nt > 1) -- rejected, not clamped: clamping would bias the boundary control points; (3) |m_x| or |m_y| > w_max.  The box is closed
+ * and so is the limit: a midpoint exactly on an edge is used (s = -0.0 counts as the lower edge; on the upper edge s = n - 3, segment
+ * n - 4, r = 1) and so is a sample with |m| = w_max exactly.
  * Unknowns.  c [nt ny nx] per component, nt ny nx <= D2D_WINDFIT_MAX_CP; wx and wy share the design matrix (two right-hand sides).
  * Design row.  The 16 (nt = 1: by[a] bx[b]) or 64 (bt[c] (by[a] bx[b])) tensor-product weights of the sample's cell, with the axis
  * weights of d2d_wind_field (segment i = min(floor(s), n - 4), r = s - i, B_k(r)), evaluated without fused multiply-add.
@@ -1101,14 +1103,25 @@ int d2d_flight_audit(d2d_ctx *ctx, const d2d_audit_params *p, const double *X_hi
  * in time order.  The workspace does not grow with the number of samples.
  * Solve.  (H + penalties + mu I) c = A^T m + mu c_prior for both components by Jacobi-preconditioned conjugate gradients in fp64, one
  * workgroup, every reduction in a fixed order, from c = c_prior, until |r| <= cg_tol |rhs| per component or cg_max iterations.
- * Outputs.  cp_out dev [nt][2][ny][nx]: with the caller's geometry a d2d_wind_field, no host visit.  d2d_windfit_out (any NULL):
- *   support dev [nt ny nx]   diag A^T A: how much data backs each control point
+ * Terminal states.  A component that has met its tolerance is frozen while the other goes on: its control points are the same bits
+ * whatever the other component's right-hand side and prior are.  A component whose right-hand side is exactly zero and whose prior
+ * is zero is frozen at once, at c = 0, and counts as residual 0.  At the cap cp_out is iterate cg_max (not an error, not the
+ * prior): stats[6] == cg_max, and stats[7] > cg_tol is the residual of that iterate (the recursively updated one, which is the true
+ * |M c - rhs| / |rhs| of cp_out within about iterations x eps x cond(M)); the caller reads stats to tell.
+ * Outputs.  cp_out dev [nt][2][ny][nx]: with the caller's geometry a d2d_wind_field, no host visit.  d2d_windfit_out (any NULL, and
+ * out itself may be NULL: cp_out and every member given are the same bits for every selection; a NULL member is not written, and
+ * with stats NULL the residual pass is not launched):
+ *   support dev [nt ny nx]   diag A^T A in the fixed point below: how much data backs each control point.  A control point whose
+ *                            weight stays below 2^-16.5 in every sample has support 0 (each square rounds to 0) though its
+ *                            products with larger weights need not vanish: support == 0 does not say that the row of H is zero.
+ *                            With lam = 0, cp_out is the prior bit for bit at every control point whose row of H_out is zero.
  *   stats   dev double [8]   samples used; rejected as non-finite, outside the box, above w_max; residual sum of squares of the fitted
  *                            field over the used samples, x and y (a second streaming pass whose partials are folded in a fixed order;
  *                            the RMS residual is about the gust level); CG iterations; largest relative CG residual reached
  *   H_out, b_out             as above
  * A formation with fewer than two valid rows contributes nothing; with no sample at all the answer is the prior (not an error).
- * work: device memory of d2d_wind_fit_workspace(p, grid) bytes (negative: D2D_EINVAL), 16-byte aligned, overwritten.
+ * work: device memory of d2d_wind_fit_workspace(p, grid) bytes (negative: D2D_EINVAL), 16-byte aligned, overwritten: what it holds
+ * on entry does not matter (no output depends on it), and nothing is written beyond that size or beyond the sizes of the outputs.
  * D2D_EINVAL before anything is launched: NULL ctx, p, X_hist, grid, cp_out or work; a geometry d2d_wind_sample refuses (grid->cp may
  * be NULL here); nt ny nx > D2D_WINDFIT_MAX_CP; n_rows < 2, n_form < 1, n_ac outside 1 .. 64; dt_row, w_max or mu not > 0 or not
  * finite; a negative or non-finite lam_*; cg_tol not in (0, 1); cg_max < 1; waves < 0; (n_rows - 1) N >= 2^31.  Asynchronous on the

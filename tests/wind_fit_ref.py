@@ -7,7 +7,9 @@
   fit(...)                         measurements -> A -> (A^T A + penalties + mu I) c = A^T m + mu c_prior, a direct sparse solve, stats
   replay(ms, grid, w_max)          the kernel's fixed-point rule: every product rounded to 2^-32 and summed as an integer ->
                                    H [ncp][49 | 343] and b [2][ncp] as the kernel converts them back: bit for bit its H_out, b_out
-  stencil_of(H, grid)              a sparse / dense ncp x ncp matrix in the kernel's stencil layout
+  stencil_of(H, grid)              a sparse / dense ncp x ncp matrix in the kernel's stencil layout (matrix_of: back again)
+  pcg(M, rhs, x0, k)               iterate k of the header's Jacobi-preconditioned CG for one component, fp64 or long double
+  edge_history, edge_grid, ...     the inputs of tests/test_gpu_wind_fit_edges.py (the last section of this file)
 
 A grid is a Grid(nt, ny, nx, t0, ht, x0, hx, y0, hy): the geometry of a d2d_wind_field (n control points, first knot u0, spacing h:
 the box is [u0, u0 + (n - 3) h])."""
@@ -264,3 +266,142 @@ def recovery_error(cp, grid, F, ms):
     tx, ty = F.sample_many(ms['tm'][use], ms['px'][use], ms['py'][use])
     return (max(np.abs(fx - tx).max(), np.abs(fy - ty).max()),
             max(np.abs(ms['m'][0][use] - tx).max(), np.abs(ms['m'][1][use] - ty).max()))
+
+
+# ---- the geometry-edge cases shared by tests/test_wind_fit_cpu.py (which proves what each input is) and
+# ---- tests/test_gpu_wind_fit_edges.py (which holds the kernels to replay() on them) -------------------------------------------------
+EDGE_ROWS, EDGE_DT, EDGE_W_MAX = 130, 0.05, 30.0
+EDGE_LAM, EDGE_MU, EDGE_CG_TOL, EDGE_CG_MAX = (1e-2, 2e-2, 5e-3), 1e-4, 1e-10, 4000
+EDGE_SHAPES = {                                        # (n_form, n_ac) -> (rows, t_start)
+    (3, 3): ([130, 65, 2], [0.0, 3.0, 7.5]),           # N = 9: the last quad holds one drone, quads straddle formations
+    (2, 5): ([66, 64], [0.0, 7.5]),                    # N = 10: the last quad holds two; one unit plus two samples, one unit exactly
+    (1, 1): ([129], [2.0]),                            # three of a workgroup's four wavefronts leave at once
+    (1, 64): ([129], [2.0]),                           # the largest formation
+}
+EDGE_BIG = dict(shape=(3, 4), rows=[40, 30, 33], t_start=[0.0, 3.0, 12.0], corners=(3, 11))     # about 400 samples for the large grids
+EDGE_BIG_GRIDS = {'steady-23x29': (1, 23, 29), 'unsteady-5x11x13': (5, 11, 13), 'steady-64x64': (1, 64, 64), 'unsteady-4x32x32': (4, 32, 32)}
+
+
+def edge_grid(nt, ny, nx):
+    """The Grid of nt x ny x nx control points whose box is x in [-120, 120], y in [-100, 100] (t in [-1, 15]): around edge_history."""
+    return Grid(nt, ny, nx, -1.0 if nt > 1 else 0.0, 16.0 / (nt - 3) if nt > 1 else 1.0, -120.0, 240.0 / (nx - 3), -100.0, 200.0 / (ny - 3))
+
+
+def edge_history(n_form, n_ac, seed=5, corners=None):
+    """[EDGE_ROWS][5][n_form n_ac]: drones on arcs through a wind that varies in space (not a simulation: any history is one).  The
+    recorded headings carry offsets of both signs up to 1e5 (the positions are integrated from the recorded heading, so the
+    measurements stay the wind).  With three drones or more: drone 0 has a NaN row, drone 1 leaves the box, drone 2 jumps (a
+    measurement above w_max).  corners = (d_lo, d_hi): those two start half a metre inside the box's lower and upper corner and fly
+    inwards, so that the first and the last cell of every grid of edge_grid hold samples."""
+    rng = np.random.default_rng(seed)
+    N = n_form * n_ac
+    t = np.arange(EDGE_ROWS) * EDGE_DT
+    X = np.zeros((EDGE_ROWS, 5, N))
+    offs = (0.0, -40.0 * np.pi, 1e5, -1e5 - 3.0, 80.0 * np.pi)
+    for d in range(N):
+        v, om, psi0, xs, ys = rng.uniform(9.0, 14.0), rng.uniform(-0.35, 0.35), rng.uniform(-np.pi, np.pi), rng.uniform(-25.0, 25.0), rng.uniform(-20.0, 20.0)
+        off = offs[d % 5]
+        if N >= 3 and d == 1:
+            om, psi0, xs, off = 0.0, 0.0, 110.0, 0.0                  # straight out of the box through x = 120
+        if corners is not None and d == corners[0]:
+            v, om, psi0, xs, ys = 10.0, 0.0, 0.25 * np.pi, -119.5, -99.5
+        if corners is not None and d == corners[1]:
+            v, om, psi0, xs, ys = 10.0, 0.0, -0.75 * np.pi, 119.5, 99.5
+        psi = (psi0 + om * t) + off
+        x = xs + np.cumsum(np.r_[0.0, (v * np.cos(psi[:-1]) + 2.0) * EDGE_DT])
+        y = ys + np.cumsum(np.r_[0.0, (v * np.sin(psi[:-1]) - 1.0 + 0.02 * x[:-1]) * EDGE_DT])
+        X[:, 0, d], X[:, 1, d], X[:, 2, d], X[:, 3, d], X[:, 4, d] = x, y, psi, 0.1 * om, v
+    if N >= 3:
+        X[17, 3, 0] = np.nan
+        X[70:, 1, 2] += 4.0
+    return X
+
+
+def edge_prior(grid, y_shift=0.0):
+    """A prior [nt][2][ny][nx] that differs in every entry: a transposed or mis-strided plane shows.  y_shift moves the y planes only."""
+    t, k, y, x = np.meshgrid(np.arange(grid.nt), np.arange(2), np.arange(grid.ny), np.arange(grid.nx), indexing='ij')
+    return 1.0 + 0.1 * t + 10.0 * k + 0.7 * y + 0.09 * x + y_shift * k
+
+
+def zero_rhs_history(n_ac=4, n_rows=40):
+    """Due east (psi = 0 exactly) at constant y: sin(0) = 0 in sincos, so every m_y is exactly 0 and the y right-hand side is too."""
+    X = np.zeros((n_rows, 5, n_ac))
+    t = np.arange(n_rows) * EDGE_DT
+    for d in range(n_ac):
+        X[:, 0, d] = -60.0 + 7.0 * d + (11.0 + d + 2.0) * t
+        X[:, 1, d] = -30.0 + 25.0 * d
+        X[:, 4, d] = 11.0 + d
+    return X
+
+
+SAMPLE_EDGE_DT = 0.0625
+SAMPLE_EDGE_ROWS = [3, 2, 3, 3]                        # four formations of one drone, three rows
+SAMPLE_EDGE_COUNTS = {32.0: [5, 0, 1, 1], 33.0: [6, 0, 1, 0], 30.0: [4, 0, 1, 2]}       # w_max -> used, not finite, outside, over: by hand
+
+
+def sample_edge_case(origin=False):
+    """(X [3][5][4], Grid) of the hand-built history on the 5 x 6 grid, dt_row = 1 / 16; every number is exact in binary.
+      drone 0  v = 0; the first midpoint is the box's upper corner exactly (used, segment n - 4, r = 1: 16 m/s), the second is outside
+      drone 1  v = 0; two rows: the midpoint is the box's lower corner exactly
+      drone 2  v = 0, 2 m a row: m_x = 32 exactly (used at w_max >= 32), then 2 + 2^-40 m: m_x = 32 + 2^-36 (over at w_max = 32)
+      drone 3  psi = -1e6, 1e6, -0.0 at 10 m/s
+    origin: the box's lower corner moved to (0, 0) (every coordinate shifted exactly) and drone 1 parked at (-0.0, -0.0): the lower
+    edge reached through s = -0.0."""
+    g = Grid(1, 5, 6, 0.0, 1.0, -120.0, 80.0, -100.0, 100.0)
+    X = np.zeros((3, 5, 4))
+    X[:, 0, 0], X[:, 1, 0], X[:, 2, 0] = [119.5, 120.5, 121.5], [99.5, 100.5, 101.5], 0.3
+    X[:, 0, 1], X[:, 1, 1] = [-120.5, -119.5, 0.0], [-100.5, -99.5, 0.0]
+    X[:, 0, 2], X[:, 1, 2] = [0.0, 2.0, 4.0 + 2.0 ** -40], 10.0
+    X[:, 0, 3], X[:, 1, 3], X[:, 2, 3], X[:, 4, 3] = [-50.0, -49.75, -49.5], [-50.0, -50.125, -50.25], [-1e6, 1e6, -0.0], 10.0
+    if origin:
+        X[:, 0] += 120.0; X[:, 1] += 100.0
+        X[:, 0, 1] = X[:, 1, 1] = -0.0
+        g = g._replace(x0=0.0, y0=0.0)
+    return X, g
+
+
+def matrix_of(Hs, grid):
+    """The inverse of stencil_of: the sparse ncp x ncp matrix of a stencil array [ncp][49 | 343]."""
+    q = stencil_index(grid)
+    on = q >= 0
+    p = np.broadcast_to(np.arange(q.shape[0])[:, None], q.shape)
+    return sp.csr_matrix((np.asarray(Hs)[on], (p[on], q[on])), shape=(q.shape[0],) * 2)
+
+
+def replay_blocks(ms, grid, w_max, block=8):
+    """replay for a history of many drones: `block` drones at a time, the integer sums added (they are integers: exactly what the
+    kernel's atomics do), so that the S x 64 x 64 product array stays small.  Returns H, b as replay does."""
+    N = ms['why'].shape[1]
+    Hq = bq = None
+    for d0 in range(0, N, block):
+        why = np.full_like(ms['why'], -1)
+        why[:, d0:d0 + block] = ms['why'][:, d0:d0 + block]
+        _, _, hq, q = replay(dict(ms, why=why), grid, w_max)
+        Hq, bq = (hq, q) if Hq is None else (Hq + hq, bq + q)
+    return Hq.astype(np.float64) * (1.0 / SCALE), bq.astype(np.float64) * (1.0 / SCALE) * w_pow2(w_max)
+
+
+def pcg(M, rhs, x0, k, tol=0.0, longdouble=False):
+    """Iterate k of the solve as include/d2d.h states it, for ONE component: Jacobi-preconditioned conjugate gradients from x0, frozen
+    once |r| <= tol |rhs| (a zero right-hand side with x0 = 0 is frozen at once) or when p^T M p is not positive.  Plain numpy, in
+    fp64 or (longdouble) in np.longdouble with the same M, rhs and x0."""
+    ty = np.longdouble if longdouble else np.float64
+    Md = np.asarray(M.todense() if sp.issparse(M) else M).astype(ty)
+    b, x = np.asarray(rhs).astype(ty), np.asarray(x0).astype(ty).copy()
+    dinv = 1.0 / np.diag(Md)
+    r = b - Md @ x
+    p = dinv * r
+    rz, bb = r @ p, b @ b
+    for _ in range(k):
+        if r @ r <= ty(tol) * ty(tol) * bb:
+            break
+        Ap = Md @ p
+        pa = p @ Ap
+        if not pa > 0.0:
+            break
+        al = rz / pa
+        x, r = x + al * p, r - al * Ap
+        z = dinv * r
+        nz = r @ z
+        p, rz = z + (nz / rz) * p, nz
+    return x
