@@ -114,6 +114,21 @@ class AuditOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in AUDIT_OUT]
 
 
+class FleetParams(C.Structure):
+    """d2d_fleet_params (include/d2d.h)."""
+    _fields_ = [('n_form', C.c_int32), ('n_ac', C.c_int32), ('n_rows', C.c_int32), ('g_rows', C.c_int32), ('tile_rows', C.c_int32),
+                ('slots', C.c_int32), ('dt_row', C.c_double), ('d_look', C.c_double), ('step_max', C.c_double), ('d_safe', C.c_double)]
+
+
+FLEET_OUT = ('near_dist', 'near_partner', 'near_time', 'near_count', 'status')
+FLEET_NONFINITE, FLEET_STEP, FLEET_BAD_ROW0, FLEET_RANGE = 1, 2, 4, 8     # include/d2d.h D2D_FLEET_*: the bits of a refused formation's status
+
+
+class FleetOut(C.Structure):
+    """d2d_fleet_out (include/d2d.h): device addresses of the outputs, None for one that is not wanted."""
+    _fields_ = [(k, C.c_void_p) for k in FLEET_OUT]
+
+
 WINDFIT_MAX_CP, WINDFIT_CHUNK = 4096, 64     # include/d2d.h D2D_WINDFIT_*
 WINDFIT_STATS = ('used', 'nonfinite', 'outside', 'over', 'rss_x', 'rss_y', 'cg_iters', 'cg_resid')   # the eight numbers of stats
 
@@ -250,6 +265,8 @@ _SIGS = {
     'd2d_fit_profile_read': (C.c_int, [_P, _P]),
     'd2d_fit_coeffs': (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     'd2d_fit_sample': (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P]),
+    'd2d_fleet_audit_workspace': (C.c_int64, [C.POINTER(FleetParams)]),
+    'd2d_fleet_audit': (C.c_int, [_P, C.POINTER(FleetParams), _P, _P, _P, _P, _P, C.POINTER(FleetOut)]),
     'd2d_wind_fit_workspace': (C.c_int64, [C.POINTER(WindFitParams), C.POINTER(WindFieldC)]),
     'd2d_wind_fit': (C.c_int, [_P, C.POINTER(WindFitParams), _P, _P, _P, C.POINTER(WindFieldC), _P, _P, C.POINTER(WindFitOut)]),
 }
@@ -914,6 +931,52 @@ class Context:
                                          C.byref(m), _ptr(mov_work), _ptr(work), C.byref(o)))
         out['mov_work'] = mov_work                    # (work is released here: the context's stream is torch's, whose allocator orders its reuse)
         return out
+
+    def fleet_audit(self, X_hist, n_ac, dt_row, d_look, step_max, rows=None, row0=None, world=None, d_safe=0.0, g_rows=None, tile_rows=0,
+                    slots=0, layout='hist', outputs=None):
+        """Audit the separation between aircraft of DIFFERENT formations (d2d_fleet_audit): X_hist dev [n_rows][5][N], N = n_form * n_ac
+        (layout='plan': a collocation plan [N][5][K], transposed here).  rows dev int32 [n_form]: the valid rows (None: all); row0 dev
+        int32 [n_form]: the global row of each formation's row 0 (None: 0); world dev int32 [n_form]: only formations of one world are
+        compared (None: one world).  d_look (m): nothing farther is reported; step_max (m): the largest step of any aircraft between
+        two rows, checked; d_safe (m, <= d_look): rows closer than it are counted.  g_rows: the global rows swept (None: n_rows
+        without row0, else max(row0 + rows), read from the device).  Returns a dict of device tensors: near_dist, near_time (at
+        (g + s) dt_row), near_partner (a global drone index), near_count [N]; status int32 [n_form] (0, or the FLEET_* bits of a
+        refused formation: its floating outputs are NaN, its counts and partners -1, and no other formation sees it).  Nothing within
+        d_look: +inf, -1, NaN, 0.  tile_rows and slots only schedule (0: the library's choice): the result is the same bits for
+        every value.  outputs: the names to compute (None: all five)."""
+        torch = _torch()
+        if layout == 'plan':
+            X_hist = X_hist.permute(2, 1, 0).contiguous()
+        elif layout != 'hist':
+            raise ValueError(f"layout={layout!r}: 'hist' ([n_rows][5][N]) or 'plan' ([N][5][K])")
+        assert X_hist.dim() == 3 and X_hist.shape[1] == 5 and X_hist.is_contiguous() and X_hist.dtype == torch.float64 and X_hist.device.type == 'cuda'
+        n_rows, _, N = X_hist.shape
+        n_ac = int(n_ac)
+        n_form = N // n_ac if n_ac >= 1 else 0
+        assert n_ac < 1 or N == n_form * n_ac
+        for t in (rows, row0, world):
+            assert t is None or (t.is_contiguous() and tuple(t.shape) == (n_form,) and t.dtype == torch.int32 and t.device == X_hist.device)
+        if g_rows is None:
+            if row0 is None:
+                g_rows = n_rows
+            else:
+                r = torch.full_like(row0, n_rows) if rows is None else torch.clamp(rows, 0, n_rows)
+                g_rows = max(int((row0.to(torch.int64) + r).max().item()), 1)
+        p = FleetParams(n_form, n_ac, n_rows, int(g_rows), int(tile_rows), int(slots), float(dt_row), float(d_look), float(step_max), float(d_safe))
+        nbytes = self.lib.d2d_fleet_audit_workspace(C.byref(p))
+        if nbytes < 0:
+            _check(int(nbytes))
+        work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=self.device)     # noqa: E731
+        out = dict(near_dist=self.empty(N), near_partner=i32(N), near_time=self.empty(N), near_count=i32(N), status=i32(n_form))
+        if outputs is not None:
+            unknown = set(outputs) - set(FLEET_OUT)
+            if unknown:
+                raise ValueError(f'outputs: unknown names {sorted(unknown)}')
+            out = {k: v for k, v in out.items() if k in outputs}
+        o = FleetOut(**{k: v.data_ptr() for k, v in out.items()})
+        _check(self.lib.d2d_fleet_audit(self.h, C.byref(p), _ptr(X_hist), _ptr(rows), _ptr(row0), _ptr(world), _ptr(work), C.byref(o)))
+        return out                                    # (work is released here: the context's stream is torch's, whose allocator orders its reuse)
 
     def wind_fit(self, X_hist, n_ac, dt_row, grid, rows=None, t_start=None, prior=None, w_max=50.0, lam=(1e-2, 1e-2, 1e-2), mu=1e-6,
                  cg_tol=1e-10, cg_max=2000, outputs=None, waves=0):

@@ -59,6 +59,41 @@ def _audit_kw(ctx, audit, n_form, what):
     return kw
 
 
+def fleet_row0(t_start, dt_row):
+    """The global rows of formations that start at t_start [n_form] on a history of row spacing dt_row: (t_start - min t_start) /
+    dt_row as int32.  The fleet audit compares formations on integer rows: a formation more than 1e-9 rows off the common grid is
+    refused by name (host only)."""
+    t = np.asarray(t_start, dtype=np.float64).reshape(-1)
+    u = (t - t.min()) / float(dt_row)
+    r = np.rint(u)
+    bad = np.nonzero(~(np.abs(u - r) <= 1e-9))[0]
+    if bad.size:
+        f = int(bad[0])
+        raise ValueError(f'fleet audit: formation {f} starts {float(u[f])!r} rows after the earliest formation, off the common row grid '
+                         f'(dt_row = {float(dt_row)!r}): the cross-formation audit compares formations on whole rows')
+    return r.astype(np.int32)
+
+
+def _fleet_audit(ctx, audit, X, n_ac, dt_row, n_form, rows=None, t_start=None, layout='hist'):
+    """Context.fleet_audit of a history for the `fleet=` entry of an `audit=` value (None when there is none): a dict of d_look and
+    step_max (m, required), world ((n_form,) integers, optional), d_safe, tile_rows, slots.  t_start: None or a float (one clock) or
+    a device tensor [n_form] of the formations' own start times, which fleet_row0 turns into rows (read on the host)."""
+    fleet = None if audit is True or audit is None else audit.get('fleet')
+    if fleet is None:
+        return None
+    fleet = dict(fleet)
+    unknown = set(fleet) - {'d_look', 'step_max', 'world', 'd_safe', 'tile_rows', 'slots'}
+    if unknown or 'd_look' not in fleet or 'step_max' not in fleet:
+        raise ValueError(f'audit: fleet needs d_look and step_max and takes world, d_safe, tile_rows, slots (unknown: {sorted(unknown)})')
+    kw = {k: fleet[k] for k in ('d_safe', 'tile_rows', 'slots') if k in fleet}
+    if fleet.get('world') is not None:
+        kw['world'] = ctx.dev(np.array(np.broadcast_to(np.asarray(fleet['world'], dtype=np.int32), (n_form,))))
+    if t_start is not None and np.ndim(t_start) > 0:
+        ts = t_start.cpu().numpy() if hasattr(t_start, 'cpu') else np.asarray(t_start)
+        kw['row0'] = ctx.dev(fleet_row0(ts, dt_row))
+    return ctx.fleet_audit(X, n_ac, dt_row, float(fleet['d_look']), float(fleet['step_max']), rows=rows, layout=layout, **kw)
+
+
 def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, t_end=1000, X0=None,
                                tau_phi=None, rec_stride=1, record=('X', 'U', 'Rr', 'eth'), W=(0., 0.), etheta_tol_deg=None,
                                t_opt_comp=0.0, windfield=None, audit=None, gust=None, gust_state=None, gust_phase=0, gust_stream_base=0,
@@ -69,7 +104,9 @@ def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, 
     which it holds).  windfield: a SplineWindField the plant flies instead of W (row i at t_start + i t_step; the GVF law never reads
     the wind).  Returns the raw device dictionary of d2dhip.Context.gvf_run plus `time`.
     audit: True or a dict (d_safe, err_tol, static: _audit_kw) -- out['audit'] is Context.flight_audit of the recorded history: every
-    formation's rows up to its stop row (derived on the device), dt_row = t_step rec_stride; needs 'X' in record.
+    formation's rows up to its stop row (derived on the device), dt_row = t_step rec_stride; needs 'X' in record.  With
+    fleet=dict(d_look=, step_max=, world=...) in the dict, out['audit']['fleet'] is Context.fleet_audit of the same rows: the
+    separation between aircraft of different formations (_fleet_audit; times from the first row).
     gust: a d2d.wind.GustModel flown on top of W or the field (the law sees none of it); gust_state dev [4][N] or None (the stationary
     start), gust_phase: the loop's phase word, gust_stream_base: the global index of the first drone (a shard of a larger batch).
     out['gust_state'] dev [4][N]: the state after each formation's last executed step; with 'g' in record out['g'] dev [n_rec][2][N].
@@ -102,8 +139,11 @@ def CircularFormationGVF_batch(c, r, v, n_ac, X0f=None, t_start=0, t_step=0.05, 
         torch = d2dhip._torch()
         rows = ((torch.clamp(out['stop_row'], max=len(time)) + (rec_stride - 1)) // rec_stride).to(torch.int32)
     if audit is not None:
-        kw = _audit_kw(ctx, audit, n_form, ())
+        kw = _audit_kw(ctx, audit, n_form, ('fleet',))
         out['audit'] = ctx.flight_audit(out['X'], n_ac, t_step * rec_stride, rows=rows, t_start=float(time[0]), **kw)
+        fleet = _fleet_audit(ctx, audit, out['X'], n_ac, t_step * rec_stride, n_form, rows=rows)
+        if fleet is not None:
+            out['audit']['fleet'] = fleet
     if est is not None:
         out['wind_estimate'] = est.fit(ctx, out['X'], n_ac, t_step * rec_stride, rows=rows, t_start=float(time[0]))
     return out
@@ -214,6 +254,7 @@ def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr
     flies (row i at time[i]); the controller keeps w, as DiffController(w) does (src/11_full_sim_case1.py:241-291).
     audit: True or a dict (d_safe, err_tol, static: _audit_kw; n_ac: consecutive drones that form a formation, default 1 -- the
     drones are independent) -- out['audit'] is Context.flight_audit of the flown history against x_ref, y_ref; needs 'X' in record.
+    With fleet=dict(d_look=, step_max=, ...) in the dict, out['audit']['fleet'] is Context.fleet_audit of the same history.
     gust: a d2d.wind.GustModel flown on top of w or the field (the controller sees none of it); gust_state, gust_phase,
     gust_stream_base as in CircularFormationGVF_batch, gust_n_ac: consecutive drones that share the formation part of the gust.
     out['gust_state'] dev [4][n]; with 'g' in record out['g'] dev [T][2][n].
@@ -236,8 +277,11 @@ def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr
                         **({} if fld is None else dict(wind=fld, t_start=float(time[0]))), **gkw)
     if audit is not None:
         n_ac = 1 if audit is True else int(audit.get('n_ac', 1))
-        kw = _audit_kw(ctx, audit, xr.shape[1] // n_ac, ('n_ac',))
+        kw = _audit_kw(ctx, audit, xr.shape[1] // n_ac, ('n_ac', 'fleet'))
         out['audit'] = ctx.flight_audit(out['X'], n_ac, float(dt), t_start=float(time[0]), x_ref=xr, y_ref=yr, **kw)
+        fleet = _fleet_audit(ctx, audit, out['X'], n_ac, float(dt), xr.shape[1] // n_ac)
+        if fleet is not None:
+            out['audit']['fleet'] = fleet
     if est is not None:
         out['wind_estimate'] = est.fit(ctx, out['X'], 1, float(dt), t_start=float(time[0]))
     return out
@@ -433,7 +477,11 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     then holds Context.flight_audit dictionaries of what was planned and what was flown: plan (the plan Xs as a history with
     dt_row = dt2), phase2 (the flown X against the plan's x, y) and phase3 (a list, one per repetition, against the phase-3
     reference) -- on the chain's clock where it has one (a field or moving discs: t_start = t2, repetition k of phase 3 from
-    t2 + dur2 + k time_3[-1]) and around the chain's moving discs.  'X' must be in record2 / record3.
+    t2 + dur2 + k time_3[-1]) and around the chain's moving discs.  'X' must be in record2 / record3.  With fleet=dict(d_look=,
+    step_max=, world=...) in the dict every one of these dictionaries gains 'fleet': Context.fleet_audit of the same plan or history
+    across the formations.  Every formation starts its transition when ITS phase 1 ended, t2[f] (in every chain, with or without a
+    field), so formation f is placed at row0 = (t2[f] - min t2) / dt_row (read on the host; a formation more than 1e-9 rows off the
+    common grid: ValueError naming it -- fleet_row0; the repetitions of phase 3 keep the same offsets on their own dt_row).
     gust: None (nothing new is launched, the result is what it was) or a d2d.wind.GustModel the PLANT flies through all three phases
     on top of w or F -- an unmeasured disturbance: neither the controllers nor the plan see it.  Every loop counts its steps from 1
     under its own phase word (phase 1: 0, phase 2: 1, repetition k of phase 3: 2 + k) and hands its gust state to the next on the
@@ -481,8 +529,12 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     dsc = ctx.dev(rows)
     dsc[:, d2dhip.SC_X0], dsc[:, d2dhip.SC_Y0], dsc[:, d2dhip.SC_PSI0] = Xs1[0], Xs1[1], Xs1[2]
     moving = list(moving_obstacles or [])
-    if known is not None or moving:
+    fleet = audit is not None and audit is not True and audit.get('fleet') is not None
+    if known is not None or moving or fleet:
         t2 = (torch.clamp(ph1['stop_row'], max=len(ph1['time'])) - 1).to(torch.float64) * float(t_step)      # dev [n_form]
+    if fleet:               # refuse an off-grid formation before anything is planned or flown for it
+        for dt_row in [dt2] + ([] if ref3 is None else [ref3[0][1] - ref3[0][0]]):
+            fleet_row0(t2.cpu().numpy(), float(dt_row))
     if known is not None:
         t2d = t2.repeat_interleave(n_ac).contiguous()                                                       # dev [N]: per drone
         w0 = ctx.wind_sample(known, t2d, Xs1[:2].contiguous())         # (the rows store -w of the planner's wind: -(-F) = F)
@@ -527,12 +579,15 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     gs = ph2.get('gust_state')
     out = dict(phase1=ph1, plan=pl, phase2=ph2, phase3=[])
     if audit is not None:
-        akw = _audit_kw(ctx, audit, n_form, ())
+        akw = _audit_kw(ctx, audit, n_form, ('fleet',))
         if moving:
             akw.update(knots=pl['moving'][0], disc=pl['moving'][1])
         t2a = t2 if (F is not None or moving) else None
         out['audit'] = dict(plan=ctx.flight_audit(Xs, n_ac, float(dt2), t_start=t2a, layout='plan', **akw),
                             phase2=ctx.flight_audit(ph2['X'], n_ac, float(dt2), t_start=t2a, x_ref=x_ref2, y_ref=y_ref2, **akw), phase3=[])
+        for key, hist, lay in (('plan', Xs, 'plan'), ('phase2', ph2['X'], 'hist')):
+            if fleet:       # every formation's transition starts where ITS phase 1 ended, with or without a clock of the chain
+                out['audit'][key]['fleet'] = _fleet_audit(ctx, audit, hist, n_ac, float(dt2), n_form, t_start=t2, layout=lay)
     # ---- phase 3: the periodic formation-flight reference, restarted from the last state until t_sim_end (:466-474) ----
     if ref3 is not None:
         time_3, x3, y3 = ref3
@@ -554,6 +609,8 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
                 t3 = float(dur2) + k * float(time_3[-1])
                 out['audit']['phase3'].append(ctx.flight_audit(ph3['X'], n_ac, dt3, t_start=t3 if t2a is None else t2a + t3, x_ref=x3,
                                                                y_ref=y3, **akw))
+                if fleet:
+                    out['audit']['phase3'][-1]['fleet'] = _fleet_audit(ctx, audit, ph3['X'], n_ac, dt3, n_form, t_start=t2)
             X_last = ph3['X_final']
             t_final += float(time_3[-1])
             k += 1

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 122
+#define D2D_VERSION 123
 
 /* error codes */
 #define D2D_OK 0
@@ -1146,6 +1146,86 @@ typedef struct {
 int64_t d2d_wind_fit_workspace(const d2d_windfit_params *p, const d2d_wind_field *grid);
 int d2d_wind_fit(d2d_ctx *ctx, const d2d_windfit_params *p, const double *X_hist, const int32_t *rows, const double *t_start,
                  const d2d_wind_field *grid, double *cp_out, void *work, const d2d_windfit_out *out);
+
+/* ---- Fleet audit: separation between aircraft of DIFFERENT formations (version 123) ----------------------------------------------------
+ * d2d_flight_audit looks inside a formation; this call looks across them.  Per aircraft: the closest approach, continuous in time
+ * between rows, to any aircraft of another formation that shares its airspace, found through a spatial grid so that the cost grows
+ * with the history and not with N^2.  tests/fleet_audit_ref.py is the CPU statement: brute force over all pairs.
+ * History.  X_hist dev [n_rows][5][N], N = n_form * n_ac, drone d = formation d / n_ac: the layout of d2d_flight_audit.  Only the x and
+ * y planes are read.  rows dev int32 [n_form] (NULL: n_rows; clamped to 0 .. n_rows) is the number of valid rows of each formation: a
+ * row at an index >= rows[f] is never read.
+ * Common clock.  Formations are compared on integer rows: row0 dev int32 [n_form] (NULL: 0) places row i of formation f at the global
+ * row row0[f] + i, and the global rows 0 .. g_rows - 1 are swept.  Formation f is VALID at the global row g when 0 <= g - row0[f] <
+ * rows[f].  A reported time is (g + s) dt_row: the caller adds the epoch.  Start times that are not a whole number of rows apart cannot
+ * be stated here.
+ * Worlds.  world dev int32 [n_form] (NULL: one world): only aircraft of different formations in the SAME world are compared (Monte-Carlo
+ * replicas that lie on top of each other get one world each).
+ * Candidates and key: those of d2d_flight_audit, by the same device function (csrc/audit_device.h).  For aircraft A and B of different
+ * formations and the same world and a global row g at which both are valid, with p = (position of B) - (position of A): the row's own
+ * |p0|^2 is a candidate at time g; if both are also valid at g + 1, so is the interior closest approach |p0 + s* d|^2 at g + s* where
+ * 0 < s* < 1 (s* = 1 is the next row's own candidate).  The answer of A is the lexicographic minimum of the keys (d^2, g + s, B's global
+ * drone index) -- the smallest distance, then the earliest time, then the smallest index -- and the square root is drawn once, at the end.
+ * Look radius.  d_look > 0: a candidate counts only when d^2 < d_look^2, strictly.  Nothing within d_look is "nothing seen": distance
+ * +inf, partner -1, time NaN, count 0.  The answer is therefore a property of the history alone: it equals the brute-force minimum over
+ * all pairs whenever that minimum is below d_look, and the grid below only schedules the search.
+ * Step bound.  step_max > 0: no aircraft moves farther than step_max between two consecutive valid rows.  It is checked, not trusted
+ * (D2D_FLEET_STEP: dx^2 + dy^2 > step_max^2).  If the closest approach q = p0 + s d of a segment is below d_look then |p0| <= |q| + s |d| <
+ * d_look + 2 step_max: at the segment's FIRST row the pair is less than E0 = d_look + 2 step_max apart on either axis.  (E0 is reached
+ * only by s = 1, the next row's own candidate; an INTERIOR approach below d_look starts within sqrt(d_look^2 + 4 step_max^2), since
+ * q is perpendicular to d there.  The grid keeps the simpler, larger E0; tests/test_gpu_fleet_audit.py places pairs at the interior
+ * bound, which an edge of d_look + step_max loses when step_max > 2/3 d_look.)  The grid has
+ * square cells of edge E = E0 (1 + 2^-16) and cell index floor(coordinate * (1 / E)) per axis; every valid aircraft is binned at every
+ * row, and an aircraft looks into its own cell and the eight around it.  Rounding cannot lose a pair: a formation with a coordinate
+ * whose |coordinate * (1 / E)| exceeds 2^30 is refused (D2D_FLEET_RANGE), so a computed quotient is within 2^30 * 3 * 2^-53 < 2^-21 of the
+ * true one, while two coordinates less than E0 apart have true quotients less than 1 / (1 + 2^-16) < 1 - 2^-17 apart: the computed
+ * quotients differ by less than 1 and their floors by at most 1.  The roundings of the step check and of d^2 < d_look^2 move E0 by a
+ * few parts in 2^53 and disappear in the same margin.
+ * Outputs (d2d_fleet_out; any pointer may be NULL: not stored):
+ *   near_dist, near_time   double [N]  the closest approach to an aircraft of another formation and its time (g + s) dt_row
+ *   near_partner           int32 [N]   that aircraft's global drone index
+ *   near_count             int32 [N]   the global rows at which the nearest other-formation aircraft AT THE ROW is closer than d_safe
+ *                                      (d_safe <= 0: no count, 0; d_safe > d_look: D2D_EINVAL, the grid would not see every such row)
+ *   status                 int32 [n_form]  0, or the D2D_FLEET_* bits of a refusal
+ * Refusals, per formation, decided by a first pass over the x and y planes before anything is compared (the conditions are evaluated
+ * independently, so bits can come together: an infinite coordinate is NONFINITE and RANGE):
+ *   D2D_FLEET_NONFINITE  a non-finite x or y in a valid row          D2D_FLEET_STEP   a step between two valid rows longer than step_max
+ *   D2D_FLEET_BAD_ROW0   row0[f] < 0 or row0[f] + rows[f] > g_rows   D2D_FLEET_RANGE  |coordinate / E| > 2^30 in a valid row
+ * A refused formation has NaN floating outputs and -1 counts and partners, and it is invisible to every other formation: those are
+ * audited as if it were absent.
+ * Scheduling.  The global rows are binned tile_rows at a time (0: the library's choice, a function of N alone; at most 32768); per binned row a hash table of
+ * `slots` list heads (0: the library's choice; rounded up to a power of two, at most 2^24) keyed by (world, cell) holds the valid
+ * aircraft as linked lists, built with one integer exchange per aircraft.  Cells that share a slot cost a second look and nothing else
+ * (slots = 1 compares every aircraft with every other: brute force on the device).  Each (aircraft, row) of a tile is searched by one
+ * lane, and one lane per aircraft folds the tile's keys into the aircraft's running key in ascending row order.  The fold is a minimum
+ * of keys and the count an integer sum: no floating-point atomic, no floating-point sum, and the order in which a list was built is
+ * not seen.  Every output is bit-identical for every tile_rows and slots and from call to call.
+ * work: device memory of d2d_fleet_audit_workspace(p) bytes (negative: D2D_EINVAL), 16-byte aligned, overwritten; its size depends on N,
+ * tile_rows and slots, not on n_rows.
+ * D2D_EINVAL before anything is launched: NULL ctx, p, X_hist, work or out; n_form < 1; n_ac outside 1 .. 64; n_rows < 1; g_rows < 1;
+ * dt_row, d_look or step_max not > 0 or not finite; d_safe > d_look (or NaN); tile_rows < 0 or slots < 0; a history or a tile too large
+ * to index (N >= 2^31, 5 N n_rows >= 2^40, N tile_rows >= 2^31).  Asynchronous on the context's stream. */
+#define D2D_FLEET_NONFINITE 1
+#define D2D_FLEET_STEP 2
+#define D2D_FLEET_BAD_ROW0 4
+#define D2D_FLEET_RANGE 8
+typedef struct {
+  int32_t n_form, n_ac;       /* n_ac 1 .. 64 */
+  int32_t n_rows;             /* rows of X_hist */
+  int32_t g_rows;             /* global rows swept */
+  int32_t tile_rows;          /* global rows binned per pass, 0: the library's choice (schedules only: same bits) */
+  int32_t slots;              /* list heads per binned row, 0: the library's choice (schedules only: same bits) */
+  double dt_row;
+  double d_look;              /* > 0 */
+  double step_max;            /* > 0 */
+  double d_safe;              /* <= 0: no count; <= d_look */
+} d2d_fleet_params;
+typedef struct {
+  double *near_dist; int32_t *near_partner; double *near_time; int32_t *near_count;
+  int32_t *status;
+} d2d_fleet_out;
+int64_t d2d_fleet_audit_workspace(const d2d_fleet_params *p);
+int d2d_fleet_audit(d2d_ctx *ctx, const d2d_fleet_params *p, const double *X_hist, const int32_t *rows, const int32_t *row0,
+                    const int32_t *world, void *work, const d2d_fleet_out *out);
 
 #ifdef __cplusplus
 }
