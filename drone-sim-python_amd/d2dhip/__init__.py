@@ -129,6 +129,23 @@ class FleetOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in FLEET_OUT]
 
 
+GUESS_OUT = ('status', 'word', 'v', 'rho', 'L', 't_nat')
+GUESS_FIT, GUESS_SHORT, GUESS_LOOSE, GUESS_LOOSE_UNMET, GUESS_LINE, GUESS_INVALID = range(6)     # include/d2d.h D2D_GUESS_*
+GUESS_STATUS = ('FIT', 'SHORT', 'LOOSE', 'LOOSE_UNMET', 'LINE', 'INVALID')
+GUESS_WORDS = ('LSL', 'RSR', 'LSR', 'RSL', 'RLR', 'LRL')      # the word index of d2d_nlp_guess_dubins (-1: none)
+GUESS_KAPPA = 0.9                      # include/d2d.h D2D_GUESS_KAPPA
+
+
+class NlpGuessOpts(C.Structure):
+    """d2d_nlp_guess_opts (include/d2d.h): bounds and v_pref are device addresses or None."""
+    _fields_ = [('kappa', C.c_double), ('bounds', C.c_void_p), ('v_pref', C.c_void_p), ('waves', C.c_int32), ('reserved', C.c_int32)]
+
+
+class NlpGuessOut(C.Structure):
+    """d2d_nlp_guess_out (include/d2d.h): device addresses of the outputs, None for one that is not wanted."""
+    _fields_ = [(k, C.c_void_p) for k in GUESS_OUT]
+
+
 WINDFIT_MAX_CP, WINDFIT_CHUNK = 4096, 64     # include/d2d.h D2D_WINDFIT_*
 WINDFIT_STATS = ('used', 'nonfinite', 'outside', 'over', 'rss_x', 'rss_y', 'cg_iters', 'cg_resid')   # the eight numbers of stats
 
@@ -265,6 +282,7 @@ _SIGS = {
     'd2d_fit_profile_read': (C.c_int, [_P, _P]),
     'd2d_fit_coeffs': (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     'd2d_fit_sample': (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P]),
+    'd2d_nlp_guess_dubins': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpGuessOpts), _P, C.POINTER(NlpGuessOut)]),
     'd2d_fleet_audit_workspace': (C.c_int64, [C.POINTER(FleetParams)]),
     'd2d_fleet_audit': (C.c_int, [_P, C.POINTER(FleetParams), _P, _P, _P, _P, _P, C.POINTER(FleetOut)]),
     'd2d_wind_fit_workspace': (C.c_int64, [C.POINTER(WindFitParams), C.POINTER(WindFieldC)]),
@@ -707,6 +725,33 @@ class Context:
         assert partner is None or (partner.is_contiguous() and partner.shape == (B, 2, N))
         return self._nlp_core(self.lib.d2d_nlp_solve, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
                               want_mult=want_mult, slots=slots, order=order, mid=(_ptr(partner),))
+
+    def nlp_guess_dubins(self, scen, N, h, bounds=None, v_pref=None, kappa=GUESS_KAPPA, W=None, outputs=None, waves=0):
+        """The start of a collocation solve from a Dubins path (d2d_nlp_guess_dubins; tests/nlp_guess_ref.py is its CPU statement): scen
+        dev [B][SCEN_STRIDE], N nodes of step h; bounds dev [B][4] as nlp_solve's or None; v_pref dev [B] or None (the rows' VSP / VREF);
+        kappa: the fraction of the bank limit the arcs use.  W: dev [B][5][N] to fill (a refused row keeps its values) or None (zeros).
+        Returns (W, dict of device tensors: status, word int32 [B] (GUESS_STATUS, GUESS_WORDS; word -1: none), v, rho, L, t_nat [B]).
+        t_nat is a suggestion for nlp_solve_free's start step, t_nat / (N - 1), not a lower bound on the duration.  outputs: the names
+        to compute (None: all six).  waves only schedules: the same bytes for every value."""
+        torch = _torch()
+        assert scen.dim() == 2 and scen.shape[1] == SCEN_STRIDE and scen.is_contiguous() and scen.dtype == torch.float64 and scen.device.type == 'cuda'
+        B, N = scen.shape[0], int(N)
+        assert bounds is None or (bounds.is_contiguous() and tuple(bounds.shape) == (B, 4) and bounds.dtype == torch.float64)
+        assert v_pref is None or (v_pref.is_contiguous() and tuple(v_pref.shape) == (B,) and v_pref.dtype == torch.float64)
+        if W is None:
+            W = self.zeros(B, 5, max(N, 0))
+        assert W.is_contiguous() and tuple(W.shape) == (B, 5, N) and W.dtype == torch.float64
+        i32 = lambda: torch.empty(B, dtype=torch.int32, device=self.device)     # noqa: E731
+        out = dict(status=i32(), word=i32(), v=self.empty(B), rho=self.empty(B), L=self.empty(B), t_nat=self.empty(B))
+        if outputs is not None:
+            unknown = set(outputs) - set(GUESS_OUT)
+            if unknown:
+                raise ValueError(f'outputs: unknown names {sorted(unknown)}')
+            out = {k: v for k, v in out.items() if k in outputs}
+        o = NlpGuessOut(**{k: v.data_ptr() for k, v in out.items()})
+        opts = NlpGuessOpts(float(kappa), None if bounds is None else bounds.data_ptr(), None if v_pref is None else v_pref.data_ptr(), int(waves), 0)
+        _check(self.lib.d2d_nlp_guess_dubins(self.h, B, N, float(h), _ptr(scen), C.byref(opts), _ptr(W), C.byref(o)))
+        return W, out
 
     def nlp_solve_free(self, scen, W, h, free_rows, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX,
                        outer_max=NLP_OUTER_MAX, want_mult=False, bounds=None, slots=0, order=None):

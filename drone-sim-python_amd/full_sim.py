@@ -338,7 +338,10 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
     (d2d_nlp_solve_groups; CostCollision couples aircraft 0 and 1 of a scenario whose rows carry KCOL > 0): W0 (B, 5, K) node
     values of the initial guess, h the time step -> dict with device tensors W (the solution), cost, feas, iters, status per
-    aircraft and sweeps, moved per scenario.  windfield (backend='nlp'): a SplineWindField the problems are planned in, AS GIVEN -- it is the
+    aircraft and sweeps, moved per scenario.  W0='dubins' (backend='nlp'): every row's start is its Dubins path, built on the device
+    from the row (d2d_nlp_guess_dubins: the row's constant wind, solve_kw's bounds; each aircraft of a scenario on its own; discs and a
+    field are not seen) -- the result gains guess_status (device int32 [B], d2dhip.GUESS_STATUS; a refused row starts from zeros and
+    its solve says so); not with via=.  windfield (backend='nlp'): a SplineWindField the problems are planned in, AS GIVEN -- it is the
     planner's field, whose model adds it to the residual, so a plan for a plant that flies F takes -F -- with node i of scenario r at
     t_start[r] + i h (d2d_nlp_solve_groups_wind); t_start a float or a device tensor [B / n_ac]; the rows' wind columns are not read.
     Rows whose SC_PMASK name other partners than the pair (0, 1) (multi_opt_planner.scenario_rows for a cost with `pairs`) are solved
@@ -388,9 +391,20 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     ctx = d2dhip.default_context()
     if backend == 'nlp':
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
-        W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
-        assert W.shape == (dsc.shape[0], 5, K) and h is not None
+        assert h is not None
         h, n_ac = float(h), int(n_ac)
+        guess_status = None
+        if isinstance(W0, str):                             # the start is built on the device from the rows: no host copy
+            if W0 != 'dubins':
+                raise ValueError(f"W0={W0!r}: an array (B, 5, K) of node values or 'dubins'")
+            if via is not None:
+                raise NotImplementedError("W0='dubins' with via=: a Dubins path knows no pins; the 'via' guess does "
+                                          "(d2d.opty_utils.via_guess, Planner.get_initial_guess('via')): pass its node values as W0")
+            W, g = ctx.nlp_guess_dubins(dsc, K, h, bounds=solve_kw.get('bounds'), outputs=('status',))
+            guess_status = g['status']
+        else:
+            W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
+        assert W.shape == (dsc.shape[0], 5, K)
         if keep_out is not None:
             B = dsc.shape[0]
             if len(keep_out) and hasattr(keep_out[0], 'lowered'):
@@ -429,7 +443,11 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
                 Wh = W.cpu().numpy()
                 out.update(via=ex['via'], waypoint_error=max(d2ou.waypoint_error(table[b], Wh[b]) for b in range(len(Wh))))
         out.update(W=W, scen=dsc)
+        if guess_status is not None:
+            out['guess_status'] = guess_status
         return out
+    if isinstance(W0, str):
+        raise NotImplementedError(f"W0={W0!r} is a start of the collocation backend (backend='nlp'): the polynomial fit starts from q0")
     plan = sop.get_plan(K, duration, obj_scale_over_n)
     dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
     q = plan.init(dsc) if q0 is None else q0

@@ -141,6 +141,12 @@ class Planner:
             for i, ig in enumerate(self.initial_guesses):
                 (g[self._slice_x[i]], g[self._slice_y[i]], g[self._slice_psi[i]], g[self._slice_phi[i]],
                  g[self._slice_v[i]]) = ig
+        elif what == 'dubins':                     # every aircraft its own Dubins path, built on the device (d2d_nlp_guess_dubins)
+            W, self.guess_status = sop.dubins_guess(self.prob)
+            self.initial_guesses = [tuple(w) for w in W]
+            for i, ig in enumerate(self.initial_guesses):
+                (g[self._slice_x[i]], g[self._slice_y[i]], g[self._slice_psi[i]], g[self._slice_phi[i]],
+                 g[self._slice_v[i]]) = ig
         else:
             self.initial_guesses = [d2ou.triangle(np.array(p0)[:2], np.array(p1)[:2], self.scen.vref, self.duration, N, go_left=-1.)
                                     for p0, p1 in zip(self.scen.p0s, self.scen.p1s)]

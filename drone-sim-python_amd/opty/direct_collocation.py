@@ -267,6 +267,27 @@ class Problem:
         # length of a Newton step, csrc/nlp_kernels.hip nlp_assemble / oracle/nlp.py)
         return rows, coupled
 
+    def dubins_guess(self):
+        """Node values (n_aircraft, 5, N) of the Dubins start of every aircraft and its status per aircraft (d2d_nlp_guess_dubins on the
+        rows and the bounds table of solve(); a free interval at the planner's own step).  What a Dubins path does not know is refused
+        by name."""
+        what = ('a wind field that varies in space and time (the guess is built in the air frame of a constant wind)' if self.field is not None else
+                'moving obstacles' if self.moving else
+                "waypoints (the 'via' guess is the one that knows pins)" if self.via is not None else
+                'hard keep-out discs (the path would have to go round them)' if self.keep_out else None)
+        if what:
+            raise NotImplementedError(f"the 'dubins' initial guess together with {what} is not supported")
+        rows, bnd = (self._rows()[0], self._bounds_table()) if self.objective == 'lowered' else self._host_rows()
+        ctx = d2dhip.default_context()
+        W, out = ctx.nlp_guess_dubins(ctx.dev(rows), self.num_nodes, float(self.planner.time_step), bounds=None if bnd is None else ctx.dev(bnd),
+                                      outputs=('status',))
+        ctx.sync()
+        status = out['status'].cpu().numpy()
+        if (status == d2dhip.GUESS_INVALID).any():
+            raise ValueError(f"the 'dubins' initial guess refuses the rows of aircraft {np.flatnonzero(status == d2dhip.GUESS_INVALID).tolist()} "
+                             '(non-finite entries, v bounds or a phi interval without a bank to either side)')
+        return W.cpu().numpy(), status
+
     def _solver_kw(self):
         """The solver options of every path, from IPOPT's.  Its max_iter counts Newton steps; here they are grouped as outer (multiplier /
         barrier updates) x inner (<= D2D_NLP_INNER_MAX): between 720 and 3600 steps in all, as in rounds 2-3 (12 .. 60 batches of 60).

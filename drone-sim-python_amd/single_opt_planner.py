@@ -277,6 +277,14 @@ def bound_violation(phi, v, phi_constraint, v_constraint):
     return vp, vv
 
 
+def dubins_guess(prob):
+    """The 'dubins' initial guess of a planner's Problem: node values (n_aircraft, 5, N) and the status per aircraft.  It is a start of
+    the collocation problem; the polynomial fit projects its start onto its basis and has no use for one."""
+    if not hasattr(prob, 'dubins_guess'):
+        raise NotImplementedError("get_initial_guess('dubins') is a start of the collocation backend: build the planner with backend='nlp'")
+    return prob.dubins_guess()
+
+
 class _FitProblem:
     """Stands where the reference keeps its opty Problem (`Planner.prob`): num_free, the two
     option spellings the reference uses, and solve(x0) -> (solution, info)."""
@@ -409,6 +417,9 @@ class Planner:
         elif kind == 'via':
             g[self._slice_x], g[self._slice_y], g[self._slice_psi], g[self._slice_phi], g[self._slice_v] = d2ou.via_guess(
                 self.exp.p0, self.exp.p1, self.waypoints, self.exp.t0, self.time_step, N, self.exp.vref)
+        elif kind == 'dubins':                     # the row's Dubins path, built on the device (d2d_nlp_guess_dubins)
+            W, self.guess_status = dubins_guess(self.prob)
+            g[self._slice_x], g[self._slice_y], g[self._slice_psi], g[self._slice_phi], g[self._slice_v] = W[0]
         elif kind == 'tri':
             x, y, psi, phi, v = d2ou.triangle(self.exp.p0[:2], self.exp.p1[:2], self.exp.vref, self.duration, N, go_left=-1.)
             g[self._slice_x], g[self._slice_y], g[self._slice_psi], g[self._slice_phi], g[self._slice_v] = x, y, psi, phi, v

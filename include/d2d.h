@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 123
+#define D2D_VERSION 124
 
 /* error codes */
 #define D2D_OK 0
@@ -1226,6 +1226,67 @@ typedef struct {
 int64_t d2d_fleet_audit_workspace(const d2d_fleet_params *p);
 int d2d_fleet_audit(d2d_ctx *ctx, const d2d_fleet_params *p, const double *X_hist, const int32_t *rows, const int32_t *row0,
                     const int32_t *world, void *work, const d2d_fleet_out *out);
+
+/* ---- the start of a collocation solve from a Dubins path (version 124) ----
+ * d2d_nlp_guess_dubins fills W [B][5][N] with node values (x, y, psi, phi, v) that are almost a feasible point of the collocation
+ * NLP of d2d_nlp_solve and its family: circular arcs at the fraction kappa of the bank limit joined by a straight line or a third
+ * arc, flown at ONE speed, in the air frame of the row's constant wind.  tests/nlp_guess_ref.py is the CPU statement; the kernel
+ * follows it decision for decision (DESIGN 5.23 has the rule in words).  Per problem, from its scenario row as nlp_load_scen reads it:
+ *   end poses p0, p1 (D2D_SC_X0 .. PSI1); the drift w = (D2D_SC_WX, D2D_SC_WY) of the solver's equalities x' = v cos psi + w_x;
+ *   v_lo, v_hi = D2D_SC_VMIN, VMAX; phi_max = D2D_SC_PHIMAX, or min(|phi_lo|, |phi_hi|) of opts->bounds where phi_lo < phi_hi;
+ *   v_pref = opts->v_pref[b], or with v_pref NULL: D2D_SC_VSP where D2D_SC_KV > 0, else D2D_SC_VREF where > 0, else (v_lo + v_hi) / 2;
+ *   clamped into [v_lo, v_hi].
+ * T = (N - 1) h; the path runs from p0 to p1' = (x1 - w_x T, y1 - w_y T, psi1) and node i is shifted by w i h.  Turn radius
+ * rho(v) = v^2 / (g tan(kappa phi_max)).  Of the six words LSL, RSR, LSR, RSL, RLR, LRL (the word index, in this order) only those
+ * whose NET TURNING equals psi1 - psi0 to D2D_GUESS_TURN_TOL are admissible -- the NLP pins psi at both ends as numbers, not modulo
+ * 2 pi -- and L*(rho) is the shortest admissible length (+inf: none; ties to the lower index).  F(v) = L*(rho(v)) - v T.
+ *   F(v_pref) > 0, the duration is tight: v in [v_pref, v_hi] with F = 0 (D2D_GUESS_FIT), or v = v_hi where F(v_hi) > 0
+ *     (D2D_GUESS_SHORT: the path is longer than v_hi T and is sampled by arc-length fraction all the same).
+ *   F(v_pref) <= 0, loose: v = v_pref and rho >= rho(v_pref) with L*(rho) = v T (D2D_GUESS_LOOSE); the bracket grows by factors of
+ *     D2D_GUESS_GROW at most D2D_GUESS_GROW_MAX times; never reached: the last radius (D2D_GUESS_LOOSE_UNMET).
+ *   The search: D2D_GUESS_ROUNDS rounds of 64-section -- the 63 interior points a + (b - a) k / 64 of the bracket, the first
+ *   sub-interval from the lower end whose ends are on different sides (the bracket's own ends keep the sides they had).  The result
+ *   is the upper end of the last speed bracket and the LOWER end of the last radius bracket: the side where L* <= v T.  L* can jump
+ *   (a word stops existing or being admissible); the search still ends on that side, and L then falls short of v T.
+ * Node i lies at arc length L i / (N - 1) (a node on a junction belongs to the earlier segment); phi = +- atan(v^2 / (g rho)) on a
+ * left / right arc, 0 on the straight; v constant; nodes 0 and N - 1 carry the end poses as the numbers of the row.
+ * D2D_GUESS_LINE: |psi1 - psi0| >= 2 pi, no admissible word, or L* = 0 -- x, y, psi linear between the ends, phi = 0, v = v_pref.
+ * D2D_GUESS_INVALID: a non-finite entry among those read, v_lo <= 0, v_lo > v_hi, phi_max outside (0, pi/2): W of the row is NOT
+ * written, word = -1, v = rho = L = t_nat = NaN.
+ * Outputs (d2d_nlp_guess_out; the struct or any pointer may be NULL: not stored): status, word (-1: LINE / INVALID) int32 [B];
+ * v, rho (+inf: LINE), L (the path's length in the air frame; LINE: the ground distance), t_nat double [B].
+ * t_nat = L*(rho(v_pref)) / v_pref (NaN: no admissible word there) is the duration at which the preferred speed flies the shortest
+ * path: a SUGGESTION for the start step of d2d_nlp_solve_free, h = t_nat / (N - 1).  It is NOT a lower bound on the duration: a
+ * slower aircraft turns tighter, and problems whose t_nat exceeds T by several per cent converge at T.
+ * Not done here (refuse upstream): paths round static, moving or keep-out discs or through pins, spatial wind fields (the row's
+ * constant wind is used), loops for durations that no widened turn fills.
+ * D2D_EINVAL before anything is launched: NULL ctx, scen or W; B < 1; N < 2; h not > 0 or not finite; kappa outside (0, 1].
+ * opts NULL: kappa = D2D_GUESS_KAPPA, no bounds, no v_pref.  Asynchronous on the context's stream; one owner per output, no atomics:
+ * the same bytes from call to call and for every grid (opts->waves, 0: the library's choice; scheduling only). */
+#define D2D_GUESS_FIT 0
+#define D2D_GUESS_SHORT 1
+#define D2D_GUESS_LOOSE 2
+#define D2D_GUESS_LOOSE_UNMET 3
+#define D2D_GUESS_LINE 4
+#define D2D_GUESS_INVALID 5
+#define D2D_GUESS_KAPPA 0.9
+#define D2D_GUESS_TURN_TOL 1e-9
+#define D2D_GUESS_ROUNDS 3
+#define D2D_GUESS_GROW 1.5
+#define D2D_GUESS_GROW_MAX 24
+typedef struct {
+  double kappa;           /* fraction of the bank limit the arcs use, in (0, 1] (D2D_GUESS_KAPPA) */
+  const double *bounds;   /* dev [B][4] as d2d_nlp_opts.bounds, or NULL */
+  const double *v_pref;   /* dev [B], or NULL */
+  int32_t waves;          /* wavefronts of the launch, 0: the library's choice (schedules only: same bytes) */
+  int32_t reserved;
+} d2d_nlp_guess_opts;
+typedef struct {
+  int32_t *status; int32_t *word;
+  double *v; double *rho; double *L; double *t_nat;
+} d2d_nlp_guess_out;
+int d2d_nlp_guess_dubins(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_guess_opts *opts, double *W,
+                         const d2d_nlp_guess_out *out);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,12 @@ python tools/bench_nlp_wind.py keepout [B] hard keep-out discs (d2d_nlp_solve_ke
     with one disc of 15 m whose centre lies on the middle of its leg moved 3 m sideways (node radius: KeepOut.lowered with the row's
     VMAX and h, no margin), against the same rows without a disc through d2d_nlp_solve, from the same guess.  The two entries
     alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians, the spread of each, statuses, mean and longest
-    step counts, and the smallest g / R^2 of the converged plans."""
+    step counts, and the smallest g / R^2 of the converged plans.
+python tools/bench_nlp_wind.py guess [B]   the start of the solve (d2d_nlp_guess_dubins): B (default 4096) perturbed exp_14 at 121 nodes through
+    d2d_nlp_solve from the host dog-leg (d2d.opty_utils.triangle, copied to the device) and from the Dubins start built on the device
+    from the same rows.  The two starts alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians and the spread
+    of each solve, the guess kernel's own time (at B and at 65 536 problems) beside the host's time for the dog-leg and its copy,
+    statuses, mean and longest step counts, and the costs of the problems both starts converge on."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 'tests')):
@@ -302,7 +307,71 @@ def keepout_leg(B):
     ctx.close()
 
 
+def guess_leg(B):
+    import time
+    import torch, d2dhip
+    from d2dhip import synth
+    from d2d.opty_utils import triangle
+    ctx = d2dhip.Context(0)
+    rows, W0, h = synth.nlp_problems(B)
+    N = W0.shape[2]
+    dsc = ctx.dev(rows)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(); e0.record()
+        r = fn()
+        e1.record(); torch.cuda.synchronize()
+        return r, e0.elapsed_time(e1) * 1e-3
+
+    # the host dog-leg and its copy: what the device start replaces (wall clock, the loop of synth.nlp_problems on the same end poses)
+    host = []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        Wh = np.stack([np.stack(triangle(r[d2dhip.SC_X0:d2dhip.SC_X0 + 2], r[d2dhip.SC_X1:d2dhip.SC_X1 + 2], 12., 12.0, N, go_left=-1.), 0) for r in rows])
+        ctx.dev(Wh); torch.cuda.synchronize()
+        host.append(time.perf_counter() - t0)
+    assert np.array_equal(Wh, W0)
+    kern = {}
+    for Bk in sorted({B, 65536}):
+        big = ctx.dev(np.ascontiguousarray(np.tile(rows, (-(-Bk // B), 1))[:Bk]))
+        Wk = ctx.empty(Bk, 5, N)
+        ts = [timed(lambda: ctx.nlp_guess_dubins(big, N, h, W=Wk))[1] for rep in range(6)]
+        kern[Bk] = dict(seconds_median=float(np.median(ts[1:])), seconds_min=min(ts[1:]), seconds_max=max(ts[1:]))
+    print(json.dumps({'leg': 'guess', 'what': 'start alone', 'nodes': N, 'host_dogleg_and_copy_seconds': {'B': B, 'min': min(host), 'max': max(host)},
+                      'guess_kernel': kern}), flush=True)
+    times = {'dogleg': [], 'dubins': []}
+    outs, gst = {}, None
+    for rep in range(6):                                     # the first launch of each is the warm-up; the starts alternate
+        for what in ('dogleg', 'dubins'):
+            if what == 'dogleg':
+                W = ctx.dev(np.ascontiguousarray(W0))
+            else:
+                W, g = ctx.nlp_guess_dubins(dsc, N, h)
+                gst = g['status']
+            outs[what], t = timed(lambda: ctx.nlp_solve(dsc, W, h))
+            times[what].append(t)
+    med = {k: float(np.median(v[1:])) for k, v in times.items()}
+    st = {k: o['status'].cpu().numpy() for k, o in outs.items()}
+    both = (st['dogleg'] == 1) & (st['dubins'] == 1)
+    dc = np.abs(outs['dogleg']['cost'].cpu().numpy() - outs['dubins']['cost'].cpu().numpy())
+    gs = gst.cpu().numpy()
+    for what in ('dogleg', 'dubins'):
+        it = outs[what]['iters'].cpu().numpy()
+        ok = st[what] == 1
+        print(json.dumps({'leg': 'guess', 'B': B, 'nodes': N, 'start': what, 'seconds_median': med[what], 'seconds_min': min(times[what][1:]),
+                          'seconds_max': max(times[what][1:]), 'problems_per_s': B / med[what], 'dubins_over_dogleg': med['dubins'] / med['dogleg'],
+                          'status_counts': {int(k): int((st[what] == k).sum()) for k in np.unique(st[what])}, 'mean_newton_steps': float(it.mean()),
+                          'max_newton_steps': int(it.max()), 'mean_newton_steps_converged': float(it[ok].mean()) if ok.any() else None,
+                          'same_status_as_the_other_start': int((st['dogleg'] == st['dubins']).sum()), 'converged_from_both': int(both.sum()),
+                          'largest_cost_difference_converged_from_both': float(dc[both].max()) if both.any() else None,
+                          'guess_status_counts': {d2dhip.GUESS_STATUS[int(k)]: int((gs == k).sum()) for k in np.unique(gs)}}), flush=True)
+    ctx.close()
+
+
 def main():
+    if sys.argv[1:2] == ['guess']:
+        return guess_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['keepout']:
         return keepout_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['free']:

@@ -6,7 +6,9 @@ status, duration and cost per case.  Cases that a free step is not combined with
 cost) report the refusal.
 --keep-out: every case with its soft discs (the cost's static obstacles) turned into hard ones (the scenario protocol's keep_out,
 d2d_nlp_solve_keepout; no margin): status, cost and the polyline's clearance per disc.  Cases without a disc, and those a hard disc is not
-combined with, say so."""
+combined with, say so.
+--guess dubins: every case from the device Dubins start (Planner.get_initial_guess('dubins'), d2d_nlp_guess_dubins) beside the case's
+own start: verdict and Newton steps of both, the status of the guess, and the difference of the two costs.  Combines with --free-time."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd')):
@@ -17,6 +19,9 @@ import numpy as np
 def main():
     free = '--free-time' in sys.argv[1:]
     hard = '--keep-out' in sys.argv[1:]
+    guess = sys.argv[sys.argv.index('--guess') + 1] if '--guess' in sys.argv[1:] else None
+    if guess not in (None, 'dubins'):
+        sys.exit(f"--guess {guess}: 'dubins' is the only start surveyed beside the case's own")
     import d2d.optyplan_scenarios as sc
     import single_opt_planner as sop
     # the reference's sweeps mutate exp_0 (exp_0_1: t1, exp_0_2: wind, exp_6: p0 / p1) and every exp_0-based scenario sees it:
@@ -49,6 +54,18 @@ def main():
                     rec.update(duration=p.duration, asked=s.t1 - s.t0)
                 if hard:
                     rec.update(discs=len(exp.keep_out), keep_out_clearance=p.info.get('keep_out_clearance'))
+                if guess:                               # the same case from the Dubins start, beside the start it names
+                    try:
+                        q = sop.Planner(exp, initialize=True, backend='nlp')
+                        g = q.get_initial_guess(guess)
+                        q.run(g)
+                        import d2dhip
+                        rec.update(guess=[d2dhip.GUESS_STATUS[k] for k in q.guess_status], guess_status=q.info['status'], guess_iters=q.info['iters'],
+                                   guess_cost_diff=q.info['obj_val'] - p.info['obj_val'])
+                        if free:
+                            rec.update(guess_duration=q.duration)
+                    except (NotImplementedError, ValueError) as e:
+                        rec.update(guess=f'{type(e).__name__}: {e}'[:160])
                 print(json.dumps(rec), flush=True)
             except Exception as e:                      # noqa: BLE001 -- a survey: report and go on
                 print(json.dumps({'scen': s.name, 'case': case, 'error': f'{type(e).__name__}: {e}'[:200]}), flush=True)
