@@ -129,6 +129,15 @@ class FleetOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in FLEET_OUT]
 
 
+TRACKS_OUT = ('knots', 'disc', 'partner', 'part_dist', 'part_time', 'chord_err', 'n_conf', 'status')
+TRACKS_SHORT = 16                                 # include/d2d.h D2D_TRACKS_SHORT: fewer valid rows than knots
+
+
+class TracksOut(C.Structure):
+    """d2d_tracks_out (include/d2d.h): device addresses of the outputs, None for one that is not wanted."""
+    _fields_ = [(k, C.c_void_p) for k in TRACKS_OUT]
+
+
 GUESS_OUT = ('status', 'word', 'v', 'rho', 'L', 't_nat')
 GUESS_FIT, GUESS_SHORT, GUESS_LOOSE, GUESS_LOOSE_UNMET, GUESS_LINE, GUESS_INVALID = range(6)     # include/d2d.h D2D_GUESS_*
 GUESS_STATUS = ('FIT', 'SHORT', 'LOOSE', 'LOOSE_UNMET', 'LINE', 'INVALID')
@@ -285,6 +294,9 @@ _SIGS = {
     'd2d_nlp_guess_dubins': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpGuessOpts), _P, C.POINTER(NlpGuessOut)]),
     'd2d_fleet_audit_workspace': (C.c_int64, [C.POINTER(FleetParams)]),
     'd2d_fleet_audit': (C.c_int, [_P, C.POINTER(FleetParams), _P, _P, _P, _P, _P, C.POINTER(FleetOut)]),
+    'd2d_fleet_tracks_workspace': (C.c_int64, [C.POINTER(FleetParams), C.c_int]),
+    'd2d_fleet_tracks': (C.c_int, [_P, C.POINTER(FleetParams), _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _P,
+                                   C.POINTER(TracksOut)]),
     'd2d_wind_fit_workspace': (C.c_int64, [C.POINTER(WindFitParams), C.POINTER(WindFieldC)]),
     'd2d_wind_fit': (C.c_int, [_P, C.POINTER(WindFitParams), _P, _P, _P, C.POINTER(WindFieldC), _P, _P, C.POINTER(WindFitOut)]),
 }
@@ -1021,6 +1033,58 @@ class Context:
             out = {k: v for k, v in out.items() if k in outputs}
         o = FleetOut(**{k: v.data_ptr() for k, v in out.items()})
         _check(self.lib.d2d_fleet_audit(self.h, C.byref(p), _ptr(X_hist), _ptr(rows), _ptr(row0), _ptr(world), _ptr(work), C.byref(o)))
+        return out                                    # (work is released here: the context's stream is torch's, whose allocator orders its reuse)
+
+    def fleet_tracks(self, X_hist, n_ac, dt_row, d_look, step_max, r_disc, rows=None, row0=None, world=None, prio=None, n_mov=MAX_MOV, n_knot=MOV_MAX_KNOT,
+                     kind=1, t0=0.0, g_rows=None, tile_rows=0, slots=0, layout='hist', outputs=None):
+        """The aircraft every formation must give way to, as moving-obstacle tables (d2d_fleet_tracks).  The history arguments are those
+        of fleet_audit (X_hist dev [n_rows][5][N], layout='plan': a collocation plan [N][5][K]; rows, row0, world dev int32 [n_form];
+        d_look, step_max; g_rows).  prio dev int32 [n_form]: the formation with the smaller (prio, index) keeps its plan (None: the
+        index).  Per formation the n_mov nearest aircraft of formations that outrank it, by the audit's candidates below d_look, are
+        written as tracks of n_knot knots across the formation's own window, global row g at t0 + g dt_row, with discs (r_disc, kind).
+        Returns a dict of device tensors: knots [n_form][n_mov][n_knot][3] and disc [n_form][n_mov][2] (the tables of
+        nlp_solve_groups_moving with R = n_form; an absent slot has r = 0 and a valid dummy track), partner int32, part_dist, part_time,
+        chord_err [n_form][n_mov] (partner -1: absent; chord_err: what the decimation to n_knot knots gives away, to be added to the
+        radius), n_conf int32 [n_form] (the partners found, n_mov + 1: more than slots; -1: a formation with a status), status int32
+        [n_form] (the FLEET_* bits and TRACKS_SHORT).  tile_rows and slots only schedule: the same bits for every value.  outputs: the
+        names to compute (None: all)."""
+        torch = _torch()
+        if layout == 'plan':
+            X_hist = X_hist.permute(2, 1, 0).contiguous()
+        elif layout != 'hist':
+            raise ValueError(f"layout={layout!r}: 'hist' ([n_rows][5][N]) or 'plan' ([N][5][K])")
+        assert X_hist.dim() == 3 and X_hist.shape[1] == 5 and X_hist.is_contiguous() and X_hist.dtype == torch.float64 and X_hist.device.type == 'cuda'
+        n_rows, _, N = X_hist.shape
+        n_ac = int(n_ac)
+        n_form = N // n_ac if n_ac >= 1 else 0
+        assert n_ac < 1 or N == n_form * n_ac
+        for t in (rows, row0, world, prio):
+            assert t is None or (t.is_contiguous() and tuple(t.shape) == (n_form,) and t.dtype == torch.int32 and t.device == X_hist.device)
+        if g_rows is None:
+            if row0 is None:
+                g_rows = n_rows
+            else:
+                r = torch.full_like(row0, n_rows) if rows is None else torch.clamp(rows, 0, n_rows)
+                g_rows = max(int((row0.to(torch.int64) + r).max().item()), 1)
+        n_mov, n_knot = int(n_mov), int(n_knot)
+        p = FleetParams(n_form, n_ac, n_rows, int(g_rows), int(tile_rows), int(slots), float(dt_row), float(d_look), float(step_max), 0.0)
+        nbytes = self.lib.d2d_fleet_tracks_workspace(C.byref(p), n_mov)
+        if nbytes < 0:
+            _check(int(nbytes))
+        work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self.device)
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=self.device)     # noqa: E731
+        kn = max(n_knot, 0)                           # (a bad n_knot is the library's to refuse)
+        out = dict(knots=self.empty(n_form, n_mov, kn, 3), disc=self.empty(n_form, n_mov, 2), partner=i32(n_form, n_mov),
+                   part_dist=self.empty(n_form, n_mov), part_time=self.empty(n_form, n_mov), chord_err=self.empty(n_form, n_mov),
+                   n_conf=i32(n_form), status=i32(n_form))
+        if outputs is not None:
+            unknown = set(outputs) - set(TRACKS_OUT)
+            if unknown:
+                raise ValueError(f'outputs: unknown names {sorted(unknown)}')
+            out = {k: v for k, v in out.items() if k in outputs}
+        o = TracksOut(**{k: v.data_ptr() for k, v in out.items()})
+        _check(self.lib.d2d_fleet_tracks(self.h, C.byref(p), _ptr(X_hist), _ptr(rows), _ptr(row0), _ptr(world), _ptr(prio), n_mov, n_knot,
+                                         float(r_disc), int(kind), float(t0), _ptr(work), C.byref(o)))
         return out                                    # (work is released here: the context's stream is torch's, whose allocator orders its reuse)
 
     def wind_fit(self, X_hist, n_ac, dt_row, grid, rows=None, t_start=None, prior=None, w_max=50.0, lam=(1e-2, 1e-2, 1e-2), mu=1e-6,

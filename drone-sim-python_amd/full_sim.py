@@ -331,8 +331,99 @@ def _via_table(dsc, n_ac, N, h, t_start, via):
     return np.stack([d2ou.lower_waypoints(v, float(ts[b // n_ac]), h, N, n_via) for b, v in enumerate(via)])
 
 
+def _dev_i32(ctx, v, n, name):
+    """None, or (n,) integers as a device int32 tensor (a tensor is taken as it is)."""
+    if v is None or hasattr(v, 'data_ptr'):
+        return v
+    a = np.asarray(v)
+    if a.shape != (n,):
+        raise ValueError(f'{name}: one integer per formation ({n}) is required, got shape {a.shape}')
+    return ctx.dev(np.ascontiguousarray(a, dtype=np.int32))
+
+
+def deconflict_plans(ctx, scen, W, h, n_ac, world=None, prio=None, row0=None, *, d_sep, margin, d_look, n_knot=32, n_mov=8, max_rounds=4,
+                     field=None, t0=0.0, step_max=None, kind=1, **solve_kw):
+    """Prioritised re-planning of formations that share an airspace.  scen dev [R n_ac][SCEN_STRIDE] and W dev [R n_ac][5][N] are the
+    rows and the plans of R formations of n_ac aircraft, from any collocation entry, node i of formation r at t0 + (row0[r] + i) h;
+    world, prio, row0: (R,) integers or device int32 tensors (None: one world, the formation index, 0).  The formation with the smaller
+    (prio, index) keeps its plan; the others give way.  Per round, on the device:
+      1. the plans are viewed as a history [N][5][R n_ac] with dt_row = h;
+      2. Context.fleet_tracks lists, per formation, up to n_mov aircraft of formations that outrank it and come within d_look, as
+         moving discs of radius d_sep + margin + chord_err (what n_knot knots give away of the partner's path), kind `kind`;
+      3. the formations that have such partners and whose tables can differ from those of their last solve -- solved for the first
+         time, another set of partners, or a partner whose plan changed in the round before -- are gathered and re-solved around
+         their discs from their current plan (nlp_solve_groups_moving; nlp_solve_moving when n_ac == 1) with t_start = t0 + row0 h;
+         their number is the only scalar that visits the host;
+      4. the solutions are scattered back; a formation whose re-solve does not converge keeps the plan it had and is reported.
+    The loop ends when nothing is left to re-solve or after max_rounds.  (A formation that has given way still flies within d_look of
+    the one it avoided, so "has partners" alone would never end; a formation none of whose partners moved is at its fixed point.)
+    step_max (m): the longest step of any plan between two nodes, for the grid of fleet_tracks; None: h (max SC_VMAX + max |row wind|)
+    x 1.05, read once before the first round (with a field it must be given).  solve_kw: the solver's keywords; bounds dev [R n_ac][4]
+    are gathered with the rows.
+    The moving discs are a SOFT cost (the rows' KOBS and S weigh them): the function REPORTS the separation it reached and never
+    asserts it.  Returns W (changed in place) and info: rounds; replanned (formations re-solved, per round); solves (per round:
+    dict(forms, cost, status, feas) of device tensors); truncated (some formation had more partners than n_mov in some round);
+    not_converged (formation indices); tracks_status (dev int32 [R] of the last round); audit: the final Context.fleet_audit
+    (near_dist, near_partner, ... with d_safe = d_sep); unresolved: the formations with an aircraft still below d_sep."""
+    import torch                    # (tensor plumbing on the device of W; everything computed goes through ctx)
+    n_ac, n_mov, n_knot = int(n_ac), int(n_mov), int(n_knot)
+    B, _, N = W.shape
+    R = B // n_ac
+    if R * n_ac != B or scen.shape[0] != B:
+        raise ValueError(f'deconflict_plans: {B} plans and {scen.shape[0]} rows are not whole formations of {n_ac}')
+    h, t0, r_disc = float(h), float(t0), float(d_sep) + float(margin)
+    world, prio, row0 = (_dev_i32(ctx, v, R, k) for v, k in ((world, 'world'), (prio, 'prio'), (row0, 'row0')))
+    if step_max is None:
+        if field is not None:
+            raise ValueError('deconflict_plans: with a wind field step_max (the longest step between two nodes, m) must be given')
+        step_max = 1.05 * h * float((scen[:, d2dhip.SC_VMAX].max() + torch.hypot(scen[:, d2dhip.SC_WX], scen[:, d2dhip.SC_WY]).max()).item())
+    bounds = solve_kw.pop('bounds', None)
+    t_start = torch.full((R,), t0, dtype=torch.float64, device=W.device)
+    if row0 is not None:
+        t_start = t_start + row0.to(torch.float64) * h
+    ac = torch.arange(n_ac, device=W.device)
+    last_set = torch.full((R, n_mov), -2, dtype=torch.int32, device=W.device)       # the partners a formation was last solved against
+    changed = torch.zeros(R, dtype=torch.bool, device=W.device)                       # plans that the round before replaced
+    bad = torch.zeros(R, dtype=torch.bool, device=W.device)
+    trunc = torch.zeros((), dtype=torch.bool, device=W.device)
+    replanned, solves, tr = [], [], None
+    fleet_kw = dict(row0=row0, world=world)
+    for _ in range(int(max_rounds)):
+        tr = ctx.fleet_tracks(W.permute(2, 1, 0).contiguous(), n_ac, h, float(d_look), step_max, r_disc, prio=prio, n_mov=n_mov, n_knot=n_knot,
+                              kind=kind, t0=t0, **fleet_kw)
+        partner, n_conf, disc = tr['partner'], tr['n_conf'], tr['disc']
+        disc[:, :, 0] += torch.where(partner >= 0, tr['chord_err'], torch.zeros_like(tr['chord_err']))
+        trunc |= (n_conf == n_mov + 1).any()
+        pset = torch.sort(partner, dim=1).values
+        moved = (changed[torch.clamp(partner, min=0) // n_ac] & (partner >= 0)).any(dim=1)
+        forms = torch.nonzero((n_conf > 0) & (moved | (pset != last_set).any(dim=1))).flatten()
+        n = int(forms.numel())                                                        # the round's one scalar on the host
+        if n == 0:
+            break
+        sel = (forms[:, None] * n_ac + ac[None, :]).flatten()
+        Wg = W[sel].contiguous()
+        args = (scen[sel].contiguous(), Wg, h)
+        kw = dict(knots=tr['knots'][forms].contiguous(), disc=disc[forms].contiguous(), field=field, t_start=t_start[forms].contiguous(),
+                  **({} if bounds is None else dict(bounds=bounds[sel].contiguous())), **solve_kw)
+        res = ctx.nlp_solve_moving(*args, **kw) if n_ac == 1 else ctx.nlp_solve_groups_moving(*args, n_ac, **kw)
+        ok = (res['status'] == d2dhip.ST_CONVERGED).view(n, n_ac).all(dim=1)
+        W[sel] = torch.where(ok.repeat_interleave(n_ac)[:, None, None], Wg, W[sel])
+        changed = torch.zeros_like(changed)
+        changed[forms] = ok
+        bad[forms] = ~ok
+        last_set[forms] = pset[forms]
+        replanned.append(n)
+        solves.append(dict(forms=forms, cost=res['cost'], status=res['status'], feas=res['feas']))
+    audit = ctx.fleet_audit(W.permute(2, 1, 0).contiguous(), n_ac, h, float(d_look), step_max, d_safe=float(d_sep), **fleet_kw)
+    low = (audit['near_dist'] < float(d_sep)).view(R, n_ac).any(dim=1)
+    info = dict(rounds=len(replanned), replanned=replanned, solves=solves, truncated=bool(trunc.item()),
+                not_converged=[int(f) for f in torch.nonzero(bad).flatten().cpu()], tracks_status=None if tr is None else tr['status'],
+                audit=audit, unresolved=[int(f) for f in torch.nonzero(low).flatten().cpu()])
+    return W, info
+
+
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, **solve_kw):
+               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, deconflict=None, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -360,7 +451,13 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     keep_out (backend='nlp', n_ac = 1): hard keep-out discs -- an array (B, n, 3) of (cx, cy, R), the node constraint as the kernel reads
     it, or a list of d2d.opty_utils.KeepOut for all problems, lowered with each row's VMAX and h (d2d_nlp_solve_keepout, with and
     without a field); the result carries keep_mult (device [B][n][K]) and keep (the lowered table, a host array (B, n, 3)).  Not combined with n_ac > 1, moving,
-    via or free_time: raised by name."""
+    via or free_time: raised by name.
+    deconflict (backend='nlp'): None -- today's call, bit for bit -- or a dict of deconflict_plans' keywords (d_sep, margin, d_look
+    required; world, prio, n_knot, n_mov, max_rounds, step_max, kind): after the solve the formations (the scenarios) that share a
+    world give way to each other by priority (deconflict_plans, which re-solves with this call's solve_kw, in the field and from the
+    start times of this call); W is updated in place and the result carries deconflict, its info.  Start times must be whole multiples
+    of h apart (fleet_row0 names the formation that is not).  Not with the fit backend, free_time, keep_out, via or moving -- the
+    re-solve entry does not carry them: raised by name."""
     import single_opt_planner as sop
     from d2d.wind import planner_wind
     if gust is not None:
@@ -388,6 +485,23 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
             if given:
                 raise NotImplementedError(f'keep_out with {name} is not supported: hard discs are held for one aircraft on static discs, '
                                           'without pins, with a fixed step')
+    if deconflict is not None:
+        if backend != 'nlp':
+            raise NotImplementedError("the polynomial fit has no deconfliction: plan_batch(backend='nlp', deconflict=...) re-plans by priority")
+        for name, given in (('free_time', free_time is not None), ('keep_out', keep_out is not None), ('via', via is not None), ('moving', bool(moving))):
+            if given:
+                raise NotImplementedError(f'deconflict with {name} is not supported: the re-solve around the committed plans '
+                                          f'(d2d_nlp_solve_groups_moving) does not carry {name}')
+        deconflict = dict(deconflict)
+        unknown = set(deconflict) - {'d_sep', 'margin', 'd_look', 'world', 'prio', 'n_knot', 'n_mov', 'max_rounds', 'step_max', 'kind'}
+        missing = {'d_sep', 'margin', 'd_look'} - set(deconflict)
+        if unknown or missing:
+            raise ValueError(f'deconflict: needs d_sep, margin and d_look and takes world, prio, n_knot, n_mov, max_rounds, step_max, kind '
+                             f'(unknown: {sorted(unknown)}, missing: {sorted(missing)})')
+        n_scen = len(scen_rows) // int(n_ac)
+        ts = t_start.cpu().numpy() if hasattr(t_start, 'cpu') else np.full(n_scen, float(t_start))
+        dec_row0 = fleet_row0(ts, float(h))                 # refuses an off-grid start by name, before anything is solved
+        dec_t0 = float(ts.min())
     ctx = d2dhip.default_context()
     if backend == 'nlp':
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
@@ -442,6 +556,12 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
                 ctx.sync()
                 Wh = W.cpu().numpy()
                 out.update(via=ex['via'], waypoint_error=max(d2ou.waypoint_error(table[b], Wh[b]) for b in range(len(Wh))))
+        if deconflict is not None:
+            dsc_d = dsc
+            if n_ac >= 2 and not pairs:                         # the reference's pair (0, 1) as the partner sets the re-solve entry reads
+                dsc_d = dsc.clone()
+                d2mou.default_pair_masks(dsc_d, n_ac, (dsc_d[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc_d[1::n_ac, d2dhip.SC_KCOL] > 0))
+            _, out['deconflict'] = deconflict_plans(ctx, dsc_d, W, h, n_ac, row0=dec_row0, field=fld, t0=dec_t0, **deconflict, **solve_kw)
         out.update(W=W, scen=dsc)
         if guess_status is not None:
             out['guess_status'] = guess_status

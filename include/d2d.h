@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 124
+#define D2D_VERSION 125
 
 /* error codes */
 #define D2D_OK 0
@@ -1226,6 +1226,58 @@ typedef struct {
 int64_t d2d_fleet_audit_workspace(const d2d_fleet_params *p);
 int d2d_fleet_audit(d2d_ctx *ctx, const d2d_fleet_params *p, const double *X_hist, const int32_t *rows, const int32_t *row0,
                     const int32_t *world, void *work, const d2d_fleet_out *out);
+
+/* ---- Fleet tracks: the aircraft a formation must give way to, as moving-obstacle tables (version 125) -------------------------------------
+ * d2d_fleet_audit says who came near whom; this call turns the same search into the input of a re-plan.  Formations are ranked by the
+ * pair (prio[f], f), smaller first (prio dev int32 [n_form]; NULL: the formation index): the formation with the smaller pair keeps its
+ * plan, the other one gives way.  For every formation f the call writes the tracks of the nearest aircraft that OUTRANK it, in the
+ * layout of d2d_moving_obstacles with G = n_form, ready for d2d_nlp_solve_groups_moving (R = n_form) or d2d_nlp_solve_moving (n_ac = 1).
+ * tests/fleet_tracks_ref.py is the CPU statement: brute force over all pairs.
+ * History, clock, worlds, look radius, step bound, refusals, scheduling: the arguments of d2d_fleet_audit with the same meanings
+ * (p->d_safe is not used beyond its rule d_safe <= d_look).
+ * Definition -- a property of the history alone.  C(f) holds every aircraft B of another, non-refused formation of f's world whose
+ * (prio, formation) is smaller than f's and for which some aircraft A of f and some candidate of the audit (a row's own distance, or an
+ * interior closest approach between two rows: csrc/audit_device.h) has d^2 < d_look^2, strictly.  The key of B is the lexicographic
+ * minimum over those A and candidates of (d^2, g + s, A's global index).  C(f) is ordered by (key, B's global index) and its first n_mov
+ * members are written, member m to slot m.
+ * Outputs (d2d_tracks_out; any pointer may be NULL: not stored):
+ *   knots      double [n_form][n_mov][n_knot][3] = (t, x, y).  Knot k of formation f lies at the global row
+ *              g_k = row0[f] + (k (rows[f] - 1)) / (n_knot - 1) (integer division: knot 0 at f's first row, the last knot at its last),
+ *              at the time t0 + g_k dt_row (the product rounded, then the sum: one multiply and one add, not accumulated; t0 is the time
+ *              of global row 0), at B's own history values at its local row clamp(g_k - row0[B's formation], 0, rows[B's formation] - 1):
+ *              a partner outside its own window is held at its first or last row, as the table holds a track outside its knots.
+ *   disc       double [n_form][n_mov][2] = (r_disc, kind); an absent slot (fewer than n_mov members) has r = 0, the same kind, and a
+ *              valid dummy track: the knot times above, positions 0 (the solve kernels validate absent discs too).
+ *   partner    int32 [n_form][n_mov]   B's global drone index, -1: absent
+ *   part_dist, part_time  double [n_form][n_mov]  the root of the key's d^2, drawn once at the end, and (g + s) dt_row; absent: +inf, NaN
+ *   chord_err  double [n_form][n_mov]  what the decimation to n_knot knots gives away: the largest distance, over the global rows g of
+ *              f's window at which B has a row of its own, between B's position at that row and the written track at the row's time.
+ *              With k the largest index <= n_knot - 2 with g_k <= g and (xa, ya), (xb, yb) the written knots k and k + 1:
+ *              s = (g - g_k) / (g_k+1 - g_k), p = a + s (b - a), e^2 = (x - px)^2 + (y - py)^2, every operation rounded on its own (nothing
+ *              fused), the maximum of e^2 over the rows exact, the root drawn once.  Absent: 0.  The caller adds it to r_disc.
+ *   n_conf     int32 [n_form]   min(|C(f)|, n_mov + 1): the value n_mov + 1 says "more partners than slots"
+ *   status     int32 [n_form]   the D2D_FLEET_* bits, plus D2D_TRACKS_SHORT when rows[f] (clamped) < n_knot: the knot times would not
+ *              increase strictly
+ * A formation with a non-zero status has n_conf = -1, partners -1, NaN floating outputs, absent discs and dummy tracks with one knot per
+ * row from row0[f] (times t0 + (row0[f] + k) dt_row, positions 0).  A formation refused by a D2D_FLEET_* bit is invisible to the others;
+ * one that is only D2D_TRACKS_SHORT has a sound history and is seen.
+ * Every output is bit-identical for every tile_rows and slots (slots = 1: brute force on the device) and from call to call: the
+ * n_mov + 1 smallest distinct partners, each with the minimum of its keys, are kept through a merge that is commutative and
+ * associative; a member of the final list cannot be lost on the way, since fewer than n_mov + 1 others ever stand before it.  No
+ * floating-point atomic, no floating-point sum.
+ * work: device memory of d2d_fleet_tracks_workspace(p, n_mov) bytes (negative: D2D_EINVAL), 16-byte aligned, overwritten; its size
+ * depends on N, tile_rows, slots and n_mov, not on n_rows.
+ * D2D_EINVAL before anything is launched: the rules of d2d_fleet_audit; n_mov outside 1 .. D2D_MAX_MOV; n_knot outside 2 ..
+ * D2D_MOV_MAX_KNOT; r_disc not > 0 or not finite; kind neither 0 nor 1; t0 not finite.  Asynchronous on the context's stream. */
+#define D2D_TRACKS_SHORT 16
+typedef struct {
+  double *knots; double *disc; int32_t *partner; double *part_dist; double *part_time; double *chord_err;
+  int32_t *n_conf; int32_t *status;
+} d2d_tracks_out;
+int64_t d2d_fleet_tracks_workspace(const d2d_fleet_params *p, int n_mov);
+int d2d_fleet_tracks(d2d_ctx *ctx, const d2d_fleet_params *p, const double *X_hist, const int32_t *rows, const int32_t *row0,
+                     const int32_t *world, const int32_t *prio, int n_mov, int n_knot, double r_disc, int kind, double t0, void *work,
+                     const d2d_tracks_out *out);
 
 /* ---- the start of a collocation solve from a Dubins path (version 124) ----
  * d2d_nlp_guess_dubins fills W [B][5][N] with node values (x, y, psi, phi, v) that are almost a feasible point of the collocation
