@@ -253,11 +253,29 @@ struct NlpKeepSet {
 struct NlpKeepProb : NlpProb {
   NlpKeepSet keep;
 };
-template <bool MOV, bool VIA = false, bool FREE = false, bool KEEP = false>
-using NlpProbT = std::conditional_t<KEEP, NlpKeepProb,
+// KMOV instantiations (d2d_nlp_solve_keepout_moving, d2d_nlp_solve_groups_keepout): hard discs that MOVE.  discs is the table disc [n][2]
+// of d2d_moving_obstacles, (R, kind) with R the node radius and R <= 0 absent (the kind is checked with the track and not read), and
+// ctr the centre planes [n][2][N] that nlp_mov_sample_kernel wrote ahead of the solve: disc m's centre at node i is ctr[(2 m) * N + i],
+// ctr[(2 m + 1) * N + i], lane = node.  The centres are data: every pass is the static one with the node's own centre, both planes
+// requested BEFORE the branch on R > 0 (absent slots hold valid planes; a load inside the branch is a memory wait of its own).
+struct NlpKeepMovSet : NlpKeepSet {
+  const double *ctr;
+};
+struct NlpKeepMovProb : NlpProb {
+  NlpKeepMovSet keep;
+};
+// KMOV: the discs' sums of two products, with the contraction the STATIC kernels have pinned by hand: ax bx + ay by as fma(ax, bx, ay by)
+// and g as fma(-R, R, .).  Left to the compiler, the instantiations with centres in vector registers fuse the other product (seen in
+// the ISA: dy dy + dx dx for the static kernels' dx dx + dy dy), an ulp per step that a full solve amplifies -- and tracks that stand
+// still are to give d2d_nlp_solve_keepout's bytes.  The static instantiations keep their expressions: their code does not change.
+__device__ __forceinline__ double nlp_dot2(double ax, double bx, double ay, double by) { return fma(ax, bx, ay * by); }
+__device__ __forceinline__ double nlp_keep_g(double dx, double dy, double R) { return fma(-R, R, nlp_dot2(dx, dx, dy, dy)); }
+template <bool MOV, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false>
+using NlpProbT = std::conditional_t<KEEP, std::conditional_t<KMOV, NlpKeepMovProb, NlpKeepProb>,
                                     std::conditional_t<FREE, NlpFreeProb, std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>>>;
-template <bool VIA, bool KEEP = false>
-using NlpProbV = std::conditional_t<KEEP, NlpKeepProb, std::conditional_t<VIA, NlpViaProb, NlpProb>>;       // for the passes that read no soft disc
+template <bool VIA, bool KEEP = false, bool KMOV = false>
+using NlpProbV = std::conditional_t<KEEP, std::conditional_t<KMOV, NlpKeepMovProb, NlpKeepProb>,
+                                    std::conditional_t<VIA, NlpViaProb, NlpProb>>;       // for the passes that read no soft disc
 template <bool MOV, typename PB> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const PB &pb) {
   if constexpr (MOV) return &pb.mv;
   else return nullptr;
@@ -341,8 +359,8 @@ __device__ __forceinline__ int nlp_via_mask(const PB &pb, int i) {
 // FREE: ut is the trial value of u = 1 / h (u + a du): the equalities are read at 1 / ut, and the duration term kd / ut, the barrier of
 // u's box and the value +inf outside it join the sums (cost_ref_out: the reference's cost() + k_dur (N - 1) h).
 // KEEP: - mub log g of every (interior node, disc) joins the barrier (one more log per node, of the product), +inf when a g <= 0.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false>
-__device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false>
+__device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
                             double mub, double *cost_ref_out, double *feas_out, const NlpModel &md, [[maybe_unused]] double ut = 0.0) {
   const int N = pb.N;
   [[maybe_unused]] const double ht = FREE ? 1.0 / ut : 0.0;
@@ -381,10 +399,12 @@ __device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP> &pb, const NlpS
           double pk = 1.0;            // at most D2D_MAX_KEEP values g in [1e-12, 1e8]: in range too
 #pragma clang loop unroll(disable)
           for (int m = 0; m < pb.keep.n; ++m) {
-            const double R = dk[3 * m + 2];
+            [[maybe_unused]] double cxm = 0.0, cym = 0.0;
+            if constexpr (KMOV) { cxm = pb.keep.ctr[(size_t)(2 * m) * N + i]; cym = pb.keep.ctr[(size_t)(2 * m + 1) * N + i]; }
+            const double R = dk[KMOV ? 2 * m : 3 * m + 2];
             if (!(R > 0.0)) continue;
-            const double dx = w[0] - dk[3 * m], dy = w[1] - dk[3 * m + 1];
-            const double gk = dx * dx + dy * dy - R * R;
+            const double dx = w[0] - (KMOV ? cxm : dk[3 * m]), dy = w[1] - (KMOV ? cym : dk[3 * m + 1]);
+            const double gk = KMOV ? nlp_keep_g(dx, dy, R) : dx * dx + dy * dy - R * R;
             if (!(gk > 0.0)) outside = 1;
             pk *= (gk > 0.0 ? gk : 1.0);
           }
@@ -488,8 +508,8 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // side + (mub / g) 2d, the (x, y) corner of D (half convention)  2 (z / g) d d^T - z I  -- the - z I is the constraint's own, negative,
 // curvature: a corner that it makes indefinite fails a pivot of the reduced system and the caller raises the damping -- and the KKT
 // error |z g - mub|.  Nothing else of the pass changes.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false>
-__device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false>
+__device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
                                double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md, [[maybe_unused]] NlpFreeRow *fr_out = nullptr) {
   const int N = pb.N;
   const double h = pb.h, ih = 1.0 / h;
@@ -584,10 +604,12 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP> &pb, const N
           const double *__restrict__ dk = pb.keep.discs;
 #pragma clang loop unroll(disable)
           for (int m = 0; m < pb.keep.n; ++m) {
-            const double R = dk[3 * m + 2];
+            [[maybe_unused]] double cxm = 0.0, cym = 0.0;
+            if constexpr (KMOV) { cxm = pb.keep.ctr[(size_t)(2 * m) * N + i]; cym = pb.keep.ctr[(size_t)(2 * m + 1) * N + i]; }
+            const double R = dk[KMOV ? 2 * m : 3 * m + 2];
             if (!(R > 0.0)) continue;
-            const double dx = wc[0] - dk[3 * m], dy = wc[1] - dk[3 * m + 1];
-            const double gk = dx * dx + dy * dy - R * R, z = pb.keep.z[(size_t)m * N + i], ig = 1.0 / gk, zg = z * ig, mg = mub * ig;
+            const double dx = wc[0] - (KMOV ? cxm : dk[3 * m]), dy = wc[1] - (KMOV ? cym : dk[3 * m + 1]);
+            const double gk = KMOV ? nlp_keep_g(dx, dy, R) : dx * dx + dy * dy - R * R, z = pb.keep.z[(size_t)m * N + i], ig = 1.0 / gk, zg = z * ig, mg = mub * ig;
             kst[0] += 2.0 * z * dx; kst[1] += 2.0 * z * dy;
             krh[0] += 2.0 * mg * dx; krh[1] += 2.0 * mg * dy;
             D[0][0] += 2.0 * zg * dx * dx - z; D[0][1] += 2.0 * zg * dx * dy; D[1][1] += 2.0 * zg * dy * dy - z;
@@ -1295,8 +1317,8 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
 // g(a) >= (1 - tau) g is the smaller positive root of  |s|^2 a^2 + 2 (d.s) a + tau g = 0  (none when d.s >= 0 or the discriminant is not
 // positive), in the form tau g / (sqrt(disc) - d.s) that does not cancel; the dual's step is dz = mub / g - z - (z / g) 2 d.s.  The
 // directional derivative needs nothing: the right-hand side carries the discs' terms.
-template <bool VIA = false, bool KEEP = false>
-__device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
+template <bool VIA = false, bool KEEP = false, bool KMOV = false>
+__device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP, KMOV> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
                                   double *amax_out, double *az_out) {
   const int N = pb.N;
   double dphi = 0.0, amax = 1.0, az = 1.0;
@@ -1347,16 +1369,18 @@ __device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP> &pb, const NlpScen &
     if constexpr (KEEP) {
       if (i >= 1 && i < N - 1) {
         const double *__restrict__ dk = pb.keep.discs;
-        const double aa = dwv[0] * dwv[0] + dwv[1] * dwv[1];
+        const double aa = KMOV ? nlp_dot2(dwv[0], dwv[0], dwv[1], dwv[1]) : dwv[0] * dwv[0] + dwv[1] * dwv[1];
 #pragma clang loop unroll(disable)
         for (int m = 0; m < pb.keep.n; ++m) {
-          const double R = dk[3 * m + 2];
+          [[maybe_unused]] double cxm = 0.0, cym = 0.0;
+          if constexpr (KMOV) { cxm = pb.keep.ctr[(size_t)(2 * m) * N + i]; cym = pb.keep.ctr[(size_t)(2 * m + 1) * N + i]; }
+          const double R = dk[KMOV ? 2 * m : 3 * m + 2];
           if (!(R > 0.0)) continue;
-          const double dx = wv[0] - dk[3 * m], dy = wv[1] - dk[3 * m + 1];
-          const double gk = dx * dx + dy * dy - R * R, z = pb.keep.z[(size_t)m * N + i];
-          const double bh = dx * dwv[0] + dy * dwv[1];
+          const double dx = wv[0] - (KMOV ? cxm : dk[3 * m]), dy = wv[1] - (KMOV ? cym : dk[3 * m + 1]);
+          const double gk = KMOV ? nlp_keep_g(dx, dy, R) : dx * dx + dy * dy - R * R, z = pb.keep.z[(size_t)m * N + i];
+          const double bh = KMOV ? nlp_dot2(dx, dwv[0], dy, dwv[1]) : dx * dwv[0] + dy * dwv[1];
           if (bh < 0.0) {
-            const double cq = tau * gk, disc = bh * bh - aa * cq;
+            const double cq = tau * gk, disc = KMOV ? fma(bh, bh, -(aa * cq)) : bh * bh - aa * cq;
             if (disc > 0.0) amax = fmin(amax, cq / (sqrt(disc) - bh));
           }
           const double dz = (mub - 2.0 * z * bh) / gk - z;
@@ -1461,8 +1485,8 @@ __device__ bool nlp_recover_free(const NlpFreeProb &pb, const NlpScen &s, int la
 
 // Take the step (node-parallel): W += a dw, duals += az dz (dz from the step's dw), duals kept near the central path.
 // KEEP: the discs' duals move and are clipped like the box duals, with g at the new point.
-template <bool VIA = false, bool KEEP = false>
-__device__ void nlp_apply(const NlpProbV<VIA, KEEP> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
+template <bool VIA = false, bool KEEP = false, bool KMOV = false>
+__device__ void nlp_apply(const NlpProbV<VIA, KEEP, KMOV> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
   const int N = pb.N;
   for (int i0 = 0; i0 < N; i0 += 64) {
     const int i = i0 + lane;
@@ -1497,11 +1521,15 @@ __device__ void nlp_apply(const NlpProbV<VIA, KEEP> &pb, const NlpScen &s, int l
         const double xn = wv[0] + a * dwl[0], yn = wv[1] + a * dwl[1];
 #pragma clang loop unroll(disable)
         for (int m = 0; m < pb.keep.n; ++m) {
-          const double R = dk[3 * m + 2];
+          [[maybe_unused]] double cxm = 0.0, cym = 0.0;
+          if constexpr (KMOV) { cxm = pb.keep.ctr[(size_t)(2 * m) * N + i]; cym = pb.keep.ctr[(size_t)(2 * m + 1) * N + i]; }
+          const double R = dk[KMOV ? 2 * m : 3 * m + 2];
           if (!(R > 0.0)) continue;
-          const double dx = wv[0] - dk[3 * m], dy = wv[1] - dk[3 * m + 1], ex = xn - dk[3 * m], ey = yn - dk[3 * m + 1];
-          const double gk = dx * dx + dy * dy - R * R, gn = ex * ex + ey * ey - R * R, z = pb.keep.z[(size_t)m * N + i];
-          const double bh = dx * dwl[0] + dy * dwl[1], mn = mub / gn;
+          const double dx = wv[0] - (KMOV ? cxm : dk[3 * m]), dy = wv[1] - (KMOV ? cym : dk[3 * m + 1]);
+          const double ex = xn - (KMOV ? cxm : dk[3 * m]), ey = yn - (KMOV ? cym : dk[3 * m + 1]);
+          const double gk = KMOV ? nlp_keep_g(dx, dy, R) : dx * dx + dy * dy - R * R, gn = KMOV ? nlp_keep_g(ex, ey, R) : ex * ex + ey * ey - R * R;
+          const double z = pb.keep.z[(size_t)m * N + i];
+          const double bh = KMOV ? nlp_dot2(dx, dwl[0], dy, dwl[1]) : dx * dwl[0] + dy * dwl[1], mn = mub / gn;
           double zn = z + az * ((mub - 2.0 * z * bh) / gk - z);
           zn = fmin(fmax(zn, 1e-10 * mn), 1e10 * mn);
           pb.keep.z[(size_t)m * N + i] = zn;
@@ -1560,7 +1588,7 @@ struct NlpExtra {
   const NlpViaSet *via;      // VIA
   const double *free_row;    // FREE: (h_lo, h_hi, k_dur, h_start; 0 = the launch's h) of the problem, and where its solved h goes
   double *h_out;
-  const NlpKeepSet *keep;    // KEEP
+  const NlpKeepSet *keep;    // KEEP (KMOV: the NlpKeepMovSet it is the base of)
 };
 
 // KEEP: the start of a free node's position.  The box push of the start pass, then every disc in index order, twice (a push out of one
@@ -1575,7 +1603,9 @@ __device__ __forceinline__ double nlp_box_push(double w, double lo, double hi) {
   if (hu) w = fmin(w, hi - kap);
   return w;
 }
-__device__ __forceinline__ void nlp_keep_start(const NlpScen &s, const NlpKeepSet &k, double &x, double &y) {
+// KMOV: the discs' centres are node i's own (N: the planes' stride).
+template <bool KMOV = false, typename KS = NlpKeepSet>
+__device__ __forceinline__ void nlp_keep_start(const NlpScen &s, const KS &k, double &x, double &y, [[maybe_unused]] int i = 0, [[maybe_unused]] int N = 0) {
   x = nlp_box_push(x, s.lo[0], s.hi[0]); y = nlp_box_push(y, s.lo[1], s.hi[1]);
   const double lx = s.p1[0] - s.p0[0], ly = s.p1[1] - s.p0[1], ll = sqrt(lx * lx + ly * ly);
   const double nx = ll > 0.0 ? -ly / ll : 0.0, ny = ll > 0.0 ? lx / ll : 1.0;
@@ -1583,15 +1613,20 @@ __device__ __forceinline__ void nlp_keep_start(const NlpScen &s, const NlpKeepSe
 #pragma clang loop unroll(disable)
   for (int q = 0; q < 2 * k.n; ++q) {
     const int m = q < k.n ? q : q - k.n;
-    const double R = dk[3 * m + 2];
+    [[maybe_unused]] double cxm = 0.0, cym = 0.0;
+    if constexpr (KMOV) { cxm = k.ctr[(size_t)(2 * m) * N + i]; cym = k.ctr[(size_t)(2 * m + 1) * N + i]; }
+    const double R = dk[KMOV ? 2 * m : 3 * m + 2];
     if (!(R > 0.0)) continue;
-    const double cx = dk[3 * m], cy = dk[3 * m + 1], Rt = R * (1.0 + 1e-2);
-    const double dx = x - cx, dy = y - cy, d2 = dx * dx + dy * dy;
-    if (d2 - R * R <= Rt * Rt - R * R) {
+    const double cx = KMOV ? cxm : dk[3 * m], cy = KMOV ? cym : dk[3 * m + 1], Rt = R * (1.0 + 1e-2);
+    const double dx = x - cx, dy = y - cy, d2 = KMOV ? nlp_dot2(dx, dx, dy, dy) : dx * dx + dy * dy;
+    if (KMOV ? fma(-R, R, d2) <= fma(Rt, Rt, -(R * R)) : d2 - R * R <= Rt * Rt - R * R) {
       const double dn = sqrt(d2);
       const bool deg = dn < 1e-12 * R;
       const double ux = deg ? nx : dx / dn, uy = deg ? ny : dy / dn;
+      if constexpr (KMOV) { x = fma(Rt, ux, cx); y = fma(Rt, uy, cy); }
+      else {
       x = cx + Rt * ux; y = cy + Rt * uy;
+      }
     }
   }
 }
@@ -1625,6 +1660,39 @@ __device__ __forceinline__ bool nlp_keep_bad(const NlpScen &s, const NlpKeepSet 
   }
   return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
 }
+// KMOV: nlp_keep_bad for discs that move (the tracks and the start time are the caller's to check: nlp_mov_bad).  A radius that is not
+// finite, an end pose on or inside a disc AT ITS OWN NODE'S TIME (the centres of node 0 and of node N - 1), or a free node that the
+// start rule, taken with the node's own centres, leaves on or inside one.
+__device__ __forceinline__ bool nlp_keep_bad(const NlpScen &s, const NlpKeepMovSet &k, const double *__restrict__ Wb, int N, int lane) {
+  int bad = 0;
+  const double *__restrict__ dk = k.discs;
+#pragma clang loop unroll(disable)
+  for (int m = 0; m < k.n; ++m) {
+    const double *__restrict__ cxp = k.ctr + (size_t)(2 * m) * N, *__restrict__ cyp = cxp + N;
+    const double ax = s.p0[0] - cxp[0], ay = s.p0[1] - cyp[0], bx = s.p1[0] - cxp[N - 1], by = s.p1[1] - cyp[N - 1];
+    const double R = dk[2 * m];
+    bad |= !(fabs(R) <= 1.79e308);
+    if (!(R > 0.0)) continue;
+    bad |= !(ax * ax + ay * ay - R * R > 0.0) || !(bx * bx + by * by - R * R > 0.0);
+  }
+  if (bad) return true;                      // (wave-uniform so far: the table and the two end centres are)
+  for (int i0 = 0; i0 < N; i0 += 64) {
+    const int i = i0 + lane;
+    if (i < 1 || i >= N - 1) continue;
+    double x = Wb[i], y = Wb[N + i];
+    nlp_keep_start<true>(s, k, x, y, i, N);
+    x = nlp_box_push(x, s.lo[0], s.hi[0]); y = nlp_box_push(y, s.lo[1], s.hi[1]);
+#pragma clang loop unroll(disable)
+    for (int m = 0; m < k.n; ++m) {
+      const double cxm = k.ctr[(size_t)(2 * m) * N + i], cym = k.ctr[(size_t)(2 * m + 1) * N + i];
+      const double R = dk[2 * m];
+      if (!(R > 0.0)) continue;
+      const double dx = x - cxm, dy = y - cym;
+      bad |= !(nlp_keep_g(dx, dy, R) > 0.0);
+    }
+  }
+  return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
+}
 
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
@@ -1642,7 +1710,10 @@ __device__ __forceinline__ bool nlp_keep_bad(const NlpScen &s, const NlpKeepSet 
 // KEEP (d2d_nlp_solve_keepout): ex.keep the problem's hard discs and the planes of their duals; g > 0 is held at every interior node by
 // the same primal-dual barrier as the box (nlp_merit, nlp_assemble, nlp_recover_stats, nlp_apply), the start is moved out of the discs
 // (nlp_keep_start) and unusable discs refuse the problem (nlp_keep_bad).  cost does not see the discs.
-template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false>
+// KMOV (d2d_nlp_solve_keepout_moving, d2d_nlp_solve_groups_keepout): KEEP with ex.keep a NlpKeepMovSet, discs that move: g at node i is taken with the
+// disc's centre at that node's time (NlpKeepMovSet).  Nothing else changes: the centres are data.
+template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false,
+          bool KMOV = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
                                               const double *__restrict__ bnd, const NlpExtra &ex = NlpExtra{}) {
@@ -1655,7 +1726,9 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   if (st_on) st_t = __builtin_amdgcn_s_memtime();
   NlpScen s = nlp_load_scen(sc, o, bnd);
   if (sc[D2D_SC_BANKMAX] != 0.0) { s.sbank = s.skphi * (double)N; s.skphi = 0.0; }     // obj_scale * kbank (the row's S is obj_scale / N)
-  NlpProbT<MOV, VIA, FREE, KEEP> pb;
+  NlpProbT<MOV, VIA, FREE, KEEP, KMOV> pb;
+  if constexpr (KEEP && KMOV) pb.keep = *static_cast<const NlpKeepMovSet *>(ex.keep);
+  else
   if constexpr (KEEP) pb.keep = *ex.keep;
   if constexpr (MOV) pb.mv = *ex.mv;
   if constexpr (VIA) pb.vm = via->vm;
@@ -1717,7 +1790,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     [[maybe_unused]] double kxy[2] = {0.0, 0.0};
     if constexpr (KEEP) {
       kxy[0] = NLP_W(0, i); kxy[1] = NLP_W(1, i);
-      nlp_keep_start(s, pb.keep, kxy[0], kxy[1]);
+      nlp_keep_start<KMOV>(s, pb.keep, kxy[0], kxy[1], i, N);
     }
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) {
@@ -1746,8 +1819,11 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       const double *__restrict__ dk = pb.keep.discs;
 #pragma clang loop unroll(disable)
       for (int m = 0; m < pb.keep.n; ++m) {
-        const double R = dk[3 * m + 2], dx = kxy[0] - dk[3 * m], dy = kxy[1] - dk[3 * m + 1];
-        pb.keep.z[(size_t)m * N + i] = (R > 0.0 && i >= 1 && i < N - 1) ? mub / (dx * dx + dy * dy - R * R) : 0.0;
+        [[maybe_unused]] double cxm = 0.0, cym = 0.0;
+        if constexpr (KMOV) { cxm = pb.keep.ctr[(size_t)(2 * m) * N + i]; cym = pb.keep.ctr[(size_t)(2 * m + 1) * N + i]; }
+        const double R = dk[KMOV ? 2 * m : 3 * m + 2], dx = kxy[0] - (KMOV ? cxm : dk[3 * m]), dy = kxy[1] - (KMOV ? cym : dk[3 * m + 1]);
+        // (KMOV: the static kernels fuse the OTHER product in this one place)
+        pb.keep.z[(size_t)m * N + i] = (R > 0.0 && i >= 1 && i < N - 1) ? mub / (KMOV ? nlp_keep_g(dy, dx, R) : dx * dx + dy * dy - R * R) : 0.0;
       }
     }
 #pragma unroll
@@ -1780,7 +1856,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     double phi0;
     if constexpr (FREE) phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md, pb.u);
     else
-    phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1803,7 +1879,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
           const double d0 = pb.kd / (u * u * u) + fr.dd + 0.5 * (pb.zul / sl + pb.zuu / su);
           dfull = d0 + lam * fmax(fabs(d0), 1e-12);
         } else
-        err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -1834,7 +1910,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
           NLP_STAMP(4)
           if (!spd) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
         } else {
-        nlp_recover_stats<VIA, KEEP>(pb, s, lane, mub, tau, &dphi, &amax, &az);
+        nlp_recover_stats<VIA, KEEP, KMOV>(pb, s, lane, mub, tau, &dphi, &amax, &az);
         nlp_phase_sync();
         NLP_STAMP(4)
         }
@@ -1844,14 +1920,14 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         for (int ls = 0; ls < 8; ++ls) {
           if constexpr (FREE) pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md, pb.u + a * du);
           else
-          pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
+          pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
         NLP_STAMP(0)
         if (ok) {
           phi0 = pt;
-          nlp_apply<VIA, KEEP>(pb, s, lane, a, az, mub);
+          nlp_apply<VIA, KEEP, KMOV>(pb, s, lane, a, az, mub);
           if constexpr (FREE) {              // u and its duals move like a node variable (nlp_apply)
             const double u = pb.u, un = u + a * du, sl = u - pb.ulo, su = pb.uhi - u;
             const double ml = mub / (un - pb.ulo), mh = mub / (pb.uhi - un);
@@ -1871,7 +1947,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     }
     if constexpr (FREE) (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
     else
-    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -1916,7 +1992,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
     if (lane == 0) *ex.h_out = pb.h;
   } else
-  (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+  (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -2048,7 +2124,9 @@ __device__ __forceinline__ void nlp_report(int b, int lane, const NlpOut &out, d
 // workspace has the planes of the border behind the others (WSF_TOTAL).
 // KEEP (nlp_solve_keepout_kernel): the problems' hard discs keep->discs [B][n_keep][3] and the planes of their duals kwork [B][n_keep][N]
 // (the problem's, not the slot's: they are a result).
-template <bool WIND, bool MOV, bool VIA, bool T_AT, bool FREE = false, bool KEEP = false>
+// KMOV (nlp_solve_keepout_moving_kernel): KEEP with the hard discs in mv and ctr -- the tracks are checked like MOV's, the planes of the
+// duals kwork [B][n_mov][N].
+template <bool WIND, bool MOV, bool VIA, bool T_AT, bool FREE = false, bool KEEP = false, bool KMOV = false>
 __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d2d_nlp_opts &o, const double *scen, double *W, double *work,
                                                  double *mult, double *cost_out, double *feas_out, int32_t *iters_out, int32_t *status_out,
                                                  int32_t *queue, const d2d_wind_field *wf, double t_start, const double *t_at = nullptr,
@@ -2072,12 +2150,15 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
     bool bad = false;
     if constexpr (T_AT) {
       t0 = 0.0;
-      if (WIND || (MOV && mv->n_mov > 0)) {
+      if (WIND || ((MOV || KMOV) && mv->n_mov > 0)) {
         t0 = nlp_first_lane(t_at[b]);
         bad = !(fabs(t0) <= 1.79e308);
       }
     }
     [[maybe_unused]] NlpMovSet ms{nullptr, nullptr, 0};
+    if constexpr (KMOV) {
+      if (mv->n_mov > 0) bad = bad || nlp_mov_bad(*mv, b, lane);
+    }
     if constexpr (MOV) {
       if (mv->n_mov > 0) bad = bad || nlp_mov_bad(*mv, b, lane);
       ms = NlpMovSet{ctr + (size_t)b * mv->n_mov * 2 * N, mv->disc + (size_t)b * mv->n_mov * 2, mv->n_mov};
@@ -2094,6 +2175,11 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
       nlp_solve_one<false, false, false, false, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
                                                              lane, out, b == 0 ? stamps : nullptr, nlp_lds, bnd,
                                                              NlpExtra{{nullptr, nullptr, nullptr}, nullptr, 0.0, 0u, nullptr, nullptr, free_rows + (size_t)b * 4, h_out + b});
+    } else if constexpr (KEEP && KMOV) {
+      const NlpKeepMovSet ks{{mv->disc + (size_t)b * mv->n_mov * 2, kwork + (size_t)b * mv->n_mov * N, mv->n_mov}, ctr + (size_t)b * mv->n_mov * 2 * N};
+      nlp_solve_one<false, WIND, false, false, false, false, true, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
+                                                                         lane, out, nullptr, nlp_lds, bnd,
+                                                                         NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, nullptr, nullptr, nullptr, nullptr, &ks});
     } else if constexpr (KEEP) {
       const NlpKeepSet ks{keep->discs + (size_t)b * keep->n_keep * 3, kwork + (size_t)b * keep->n_keep * N, keep->n_keep};
       nlp_solve_one<false, WIND, false, false, false, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
@@ -2136,6 +2222,17 @@ nlp_solve_keepout_kernel(int B, int N, double h, d2d_nlp_opts o, const double *_
                          d2d_keep_out keep, double *kwork) {
   nlp_handout_body<WIND, false, false, true, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, 0.0,
                                                           t_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &keep, kwork);
+}
+
+// d2d_nlp_solve_keepout_moving: outside every problem's hard discs that move -- the centre planes ctr [B][n_mov][2][N] sampled ahead
+template <bool WIND>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_keepout_moving_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                                double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                                int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
+                                d2d_moving_obstacles mv, const double *ctr, double *kwork) {
+  nlp_handout_body<WIND, false, false, true, false, true, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf,
+                                                                0.0, t_start, &mv, ctr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kwork);
 }
 
 // d2d_nlp_solve_moving: around the problems' moving discs -- the rows' constant wind or the field (WIND), the start time per problem.
@@ -2257,14 +2354,19 @@ __device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
 // went from 256 VGPRs / 624 B of scratch to 255 / 608 and the field kernel from 752 B to 784.
 // Registers: 512 threads per workgroup are 8 wavefronts on 4 SIMDs, two per SIMD, so a wavefront gets at most 256 of the SIMD's 512
 // registers whatever amdgpu_waves_per_eu says -- the workgroup size binds, and (2, 2) states what the hardware does.
-template <bool WIND, bool PAIRS, bool MOV = false, bool VIA = false>
+// KMOV (d2d_nlp_solve_groups_keepout): mv and ctr are the scenario's HARD moving discs (NlpKeepMovSet), held by every aircraft in the
+//   uncoupled sweep and in every turn; kwork [R n_ac][n_mov][N] the planes of their duals, every aircraft its own.  Tracks, radii and the
+//   start time are checked like MOV's; an aircraft whose end pose lies inside a disc or that the start rule cannot place outside the
+//   discs refuses the SCENARIO -- every wavefront checks every aircraft of the scenario, before the first barrier, as VIA checks the pins.
+template <bool WIND, bool PAIRS, bool MOV = false, bool VIA = false, bool KMOV = false>
 __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h, const d2d_nlp_opts &o, int max_sweeps, double tol,
                                                 const double *scen, double *W, double *work, double *mult, double *prev,
                                                 double *cost_out, double *feas_out, int32_t *iters_out,
                                                 int32_t *status_out, int32_t *sweeps_out, double *moved_out,
                                                 const d2d_wind_field *wf, const double *t_start,
                                                 const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr,
-                                                const d2d_via_points *via = nullptr, int32_t *vwork = nullptr) {
+                                                const d2d_via_points *via = nullptr, int32_t *vwork = nullptr,
+                                                [[maybe_unused]] double *kwork = nullptr) {
   __shared__ double moved_s[PAIRS ? 8 : 2];
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -2313,6 +2415,23 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
     vs = NlpViaSet{via->pts + (size_t)b * via->n_via * 5, vwork + (size_t)b * N, via->n_via};
     vsp = &vs;
   }
+  [[maybe_unused]] NlpKeepMovSet kms{{nullptr, nullptr, 0}, nullptr};
+  if constexpr (KMOV) {
+    if (mv->n_mov > 0) {
+      if constexpr (!WIND) bad = bad || !(fabs(nlp_first_lane(t_start[r])) <= 1.79e308);
+      bad = bad || nlp_mov_bad(*mv, r, lane);
+    }
+    kms = NlpKeepMovSet{{mv->disc + (size_t)r * mv->n_mov * 2, kwork + (size_t)b * mv->n_mov * N, mv->n_mov}, ctr + (size_t)r * mv->n_mov * 2 * N};
+    if (!bad && mv->n_mov > 0) {             // (the centre planes are read only behind a good track)
+      for (int a = 0; a < n_ac; ++a) {
+        const size_t ba = (size_t)r * n_ac + a;
+        const double *sca = scen + ba * D2D_SCEN_STRIDE;
+        const NlpScen sa = nlp_load_scen(sca, o, o.bounds ? o.bounds + ba * 4 : nullptr);
+        bad = bad || nlp_keep_bad(sa, kms, W + ba * NLP_NV * N, N, lane);
+      }
+    }
+    __syncthreads();                         // (every wavefront has read every aircraft's start before the first solve writes one)
+  }
   if (bad) {                                 // (uniform over the workgroup: before the first barrier)
     nlp_groups_refuse(b, r, wave, lane, cost_out, feas_out, iters_out, status_out, sweeps_out, moved_out);
     return;
@@ -2330,7 +2449,8 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
   double *ldsw = nlp_lds + (size_t)wave * NLP_LDS_DOUBLES;
   const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
   NlpExtra ex{{nullptr, nullptr, nullptr}, wf, t0, 0u, msp, vsp};      // sweep 0: no partner
-  nlp_solve_one<false, WIND, PAIRS, MOV, VIA>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
+  if constexpr (KMOV) ex.keep = &kms;
+  nlp_solve_one<false, WIND, PAIRS, MOV, VIA, false, KMOV, KMOV>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
   ex.pmask = pmask;
   iters_total += out.iters;
   if (threadIdx.x < (PAIRS ? 8 : 2)) moved_s[threadIdx.x] = 0.0;
@@ -2348,7 +2468,7 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
           // fixed pair: the partner's x and y planes; PAIRS: the scenario's W and the set
           const double *pw = PAIRS ? Wr : W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;
           for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
-          nlp_solve_one<false, WIND, PAIRS, MOV, VIA>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
+          nlp_solve_one<false, WIND, PAIRS, MOV, VIA, false, KMOV, KMOV>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
           iters_total += out.iters;
           double m = 0.0;
           for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
@@ -2418,6 +2538,18 @@ nlp_groups_moving_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int m
                          const double *__restrict__ ctr) {
   nlp_groups_body<WIND, true, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
                                     sweeps_out, moved_out, &wf, t_start, &mv, ctr);
+}
+
+// d2d_nlp_solve_groups_keepout: the pairs of the masks, every aircraft outside the scenario's hard moving discs; WIND as above
+template <bool WIND>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
+nlp_groups_keepout_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                          double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                          int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                          double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start, d2d_moving_obstacles mv,
+                          const double *__restrict__ ctr, double *kwork) {
+  nlp_groups_body<WIND, true, false, false, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out,
+                                                  status_out, sweeps_out, moved_out, &wf, t_start, &mv, ctr, nullptr, nullptr, kwork);
 }
 
 // d2d_nlp_solve_groups_via: the pairs of the masks around the scenarios' moving discs, through every aircraft's own pins; WIND as above
@@ -2724,6 +2856,39 @@ int d2d_nlp_solve_keepout(d2d_ctx *ctx, int B, int N, double h, const double *sc
   return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
     return nlp_handout_launch(nlp_solve_keepout_kernel<decltype(wind)::value>, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status, wf,
                               t_start, *keep, kwork);
+  });
+}
+
+int d2d_nlp_solve_keepout_moving(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
+                                 double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
+                                 const double *t_start, const d2d_moving_obstacles *mov, double *mov_work, double *kwork) {
+  if (int rc = nlp_single_check(ctx, B, N, h, scen, W, work, cost, feas, "d2d_nlp_solve_keepout_moving")) return rc;
+  D2D_REQUIRE(!mov || mov->n_mov == 0 || kwork, "d2d_nlp_solve_keepout_moving: null kwork with n_mov = %d", mov->n_mov);
+  d2d_nlp_opts o;
+  if (int rc = nlp_moving_prologue(ctx, B, N, h, opts, f, t_start, mov, mov_work, "d2d_nlp_solve_keepout_moving", &o)) return rc;
+  if (mov->n_mov == 0)                                     // no discs: the solve of d2d_nlp_solve_moving with nothing moving
+    return d2d_nlp_solve_moving(ctx, B, N, h, scen, opts, W, work, mult, cost, feas, iters, status, f, t_start, mov, mov_work);
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_handout_launch(nlp_solve_keepout_moving_kernel<decltype(wind)::value>, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status,
+                              wf, t_start, *mov, (const double *)mov_work, kwork);
+  });
+}
+
+int d2d_nlp_solve_groups_keepout(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                                 double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                                 int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
+                                 const d2d_moving_obstacles *mov, double *mov_work, double *kwork) {
+  if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_keepout")) return rc;
+  D2D_REQUIRE(!mov || mov->n_mov == 0 || kwork, "d2d_nlp_solve_groups_keepout: null kwork with n_mov = %d", mov->n_mov);
+  d2d_nlp_opts o;
+  if (int rc = nlp_moving_prologue(ctx, R, N, h, opts, f, t_start, mov, mov_work, "d2d_nlp_solve_groups_keepout", &o)) return rc;
+  if (mov->n_mov == 0)                                     // no discs: the solve of d2d_nlp_solve_groups_pairs
+    return d2d_nlp_solve_groups_pairs(ctx, R, n_ac, N, h, scen, opts, max_sweeps, tol, W, work, mult, cost, feas, iters, status, sweeps, moved, f,
+                                      t_start);
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_groups_launch(nlp_groups_keepout_kernel<decltype(wind)::value>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
+                             nlp_groups_prev(work, R, n_ac, N), cost, feas, iters, status, sweeps, moved, wf, t_start, *mov,
+                             (const double *)mov_work, kwork);
   });
 }
 

@@ -394,6 +394,75 @@ def keep_out_clearance(keep_out, x, y):
     return out
 
 
+class MovingKeepOut:
+    """A HARD keep-out disc that moves (include/d2d.h d2d_nlp_solve_keepout_moving): no point of the plan comes closer than `margin` to
+    the disc of radius r round the piecewise-linear track (t, xy) -- knots as MovingObstacle's, validated alike, times absolute.
+    Scenarios list them in `keep_out`, beside static KeepOut discs.  The solver holds |p_i - c(t_i)|^2 >= R^2 at the nodes; lowered()
+    inflates R for what happens between them: between two nodes the RELATIVE displacement of aircraft and disc is what cuts the chord,
+    at most (v_max + v_c) h with v_c the track's fastest knot segment."""
+
+    def __init__(self, t, xy, r, margin=0.0):
+        trk = MovingObstacle(t, xy, r, kind=1)       # (the track's checks are MovingObstacle's)
+        self.t, self.xy, self.r, self.margin = trk.t, trk.xy, float(r), float(margin)
+        if not (np.isfinite(self.r) and np.isfinite(self.margin)) or not self.r > 0.0 or not self.margin >= 0.0:
+            raise ValueError(f'MovingKeepOut: r > 0 and margin >= 0 are required, got r = {self.r}, margin = {self.margin}')
+
+    @classmethod
+    def linear(cls, c0, v, r, t0=0., t1=60., margin=0.0):
+        c0, v = np.asarray(c0, dtype=np.float64), np.asarray(v, dtype=np.float64)
+        return cls((t0, t1), (c0, c0 + v * (t1 - t0)), r, margin)
+
+    def at(self, t):
+        return track_at(self.t, self.xy, t)
+
+    @property
+    def v_c(self):
+        """the track's fastest knot segment (m/s)"""
+        return float((np.hypot(*np.diff(self.xy, axis=0).T) / np.diff(self.t)).max())
+
+    def lowered(self, v_max, h):
+        """R of the node constraint: two nodes whose relative positions lie on the circle R and differ by at most s = (v_max + v_c) h
+        have their relative chord pass the centre at sqrt(R^2 - (s / 2)^2) = r + margin."""
+        return float(np.sqrt((self.r + self.margin) ** 2 + (0.5 * (v_max + self.v_c) * h) ** 2))
+
+    def track(self, v_max, h):
+        """The MovingObstacle whose table row the kernel reads: the track with the node radius in the place of r."""
+        return MovingObstacle(self.t, self.xy, self.lowered(v_max, h), kind=1)
+
+    def __repr__(self):
+        return f'MovingKeepOut({len(self.t)} knots, r={self.r}, margin={self.margin})'
+
+
+def lower_keep_moving(keep_out, v_max, h, n_knot=None):
+    """The tables of d2d_nlp_solve_keepout_moving for one problem: knots (n, n_knot, 3) and disc (n, 2) = (R, 1) of a list of
+    MovingKeepOut and KeepOut -- a static disc lowers to a two-knot track that stands still (its R is KeepOut.lowered's)."""
+    trk = []
+    for k in keep_out:
+        if isinstance(k, MovingKeepOut):
+            trk.append(k.track(v_max, h))
+        else:
+            cx, cy, R = k.lowered(v_max, h)
+            trk.append(MovingObstacle((0.0, 1.0), ((cx, cy), (cx, cy)), R, kind=1))
+    return lower_moving(trk, n_knot)
+
+
+def moving_keep_clearance(keep_out, t, x, y):
+    """Per disc of a keep_out list (MovingKeepOut or KeepOut): the smallest |p(t) - c(t)| - r, continuous in time, over the plan's
+    polyline (t_i, x_i, y_i) -- the relative position is taken piecewise linear between the plan's nodes and the track's knots."""
+    t, x, y = (np.asarray(v, dtype=np.float64) for v in (t, x, y))
+    out = []
+    for k in keep_out:
+        if not isinstance(k, MovingKeepOut):
+            out.append(keep_out_clearance([k], x, y)[0])
+            continue
+        tt = np.union1d(t, k.t[(k.t > t[0]) & (k.t < t[-1])])
+        d = np.stack([np.interp(tt, t, x), np.interp(tt, t, y)], -1) - k.at(tt)
+        a, ab = d[:-1], d[1:] - d[:-1]
+        s = np.clip(-np.sum(a * ab, 1) / np.maximum(np.sum(ab * ab, 1), 1e-300), 0.0, 1.0)
+        out.append(float(np.hypot(*(a + s[:, None] * ab).T).min() - k.r))
+    return out
+
+
 class Waypoint:
     """A timed waypoint of the collocation planner (include/d2d.h d2d_via_points): at time t -- absolute, on the clock of the scenario's
     t0 -- the given ones of x, y, psi hold exactly; None leaves a component free.  The time must be that of an interior node of the

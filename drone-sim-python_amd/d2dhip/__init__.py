@@ -257,6 +257,10 @@ _SIGS = {
                                     + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P]),
     'd2d_nlp_solve_keepout': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
                               + [C.POINTER(WindFieldC), _P, C.POINTER(KeepOutC), _P]),
+    'd2d_nlp_solve_keepout_moving': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
+                                     + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, _P]),
+    'd2d_nlp_solve_groups_keepout': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
+                                     + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, _P]),
     'd2d_nlp_solve_via': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
                           + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, C.POINTER(ViaPointsC), _P]),
     'd2d_nlp_solve_groups_via': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
@@ -665,7 +669,8 @@ class Context:
         return out
 
     def _nlp_core(self, entry, scen, W, h, opts, bounds, n_ac=None, sweeps=None, want_mult=False, slots=0, order=None, mid=(),
-                  field=_ABSENT, t_start=None, t_scalar=False, moving=_ABSENT, via=_ABSENT, free_rows=None, keep=_ABSENT):
+                  field=_ABSENT, t_start=None, t_scalar=False, moving=_ABSENT, via=_ABSENT, free_rows=None, keep=_ABSENT,
+                  hard_moving=False):
         """What the nlp_solve* methods share: the shape checks, the workspace and the outputs, d2d_nlp_opts from opts = (rho0, mub0,
         mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), the call of `entry` and the result.  n_ac: a group entry (sweeps =
         (max_sweeps, tol)), R = B / n_ac scenarios with one start time and one set of tracks each; else B problems.  mid: arguments
@@ -673,7 +678,8 @@ class Context:
         none (it takes t_start with the field: a device array, or with t_scalar a float); each adds its entries to the result.
         free_rows: the entry is d2d_nlp_solve_free -- the rows go in front of W, the solved steps `h` [B] behind status, and the
         workspace is the larger one.  keep: the entry is d2d_nlp_solve_keepout -- discs dev [B][n_keep][3] or None (no discs) behind the
-        field; the result carries keep_mult [B][n_keep][N], the discs' duals."""
+        field; the result carries keep_mult [B][n_keep][N], the discs' duals.  hard_moving: the moving discs are HARD (d2d_nlp_solve_keepout_moving,
+        d2d_nlp_solve_groups_keepout): kwork follows mov_work, and the result carries keep_mult [B][n_mov][N]."""
         torch = _torch()
         B, _, N = W.shape
         groups = n_ac is not None
@@ -714,6 +720,9 @@ class Context:
         if m is not None:
             out['mov_work'] = self.empty(G, m.n_mov, 2, N) if m.n_mov > 0 else None
             args += [C.byref(m), _ptr(out['mov_work'])]
+            if hard_moving:
+                out['keep_mult'] = self.zeros(B, m.n_mov, N) if m.n_mov > 0 else None
+                args += [_ptr(out['keep_mult'])]
         if v is not None:
             out['via_work'] = torch.zeros(B, N, dtype=torch.int32, device=self.device) if v.n_via > 0 else None
             args += [C.byref(v), _ptr(out['via_work'])]
@@ -876,6 +885,30 @@ class Context:
             t_start = 0.0
         return self._nlp_core(self.lib.d2d_nlp_solve_keepout, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
                               want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, keep=discs)
+
+    def nlp_solve_keepout_moving(self, scen, W, h, knots=None, disc=None, field=None, t_start=None, rho0=10.0, mub0=0.1, mub_min=1e-9,
+                                 feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0,
+                                 bounds=None, slots=0, order=None):
+        """nlp_solve_keepout outside hard discs that MOVE (d2d_nlp_solve_keepout_moving): the tables of nlp_solve_moving, knots dev
+        [B][n_mov][n_knot][3] = (t, x, y) and disc dev [B][n_mov][2] = (R, kind) with R the NODE RADIUS of the hard constraint (R <= 0:
+        absent; the kind is validated and not read).  Every interior node i is held at |p_i - c(t_start + i h)|^2 - R^2 > 0.  t_start dev
+        [B] or a float is required when discs are given.  Refused on the device (status ST_NONFINITE, cost = feas = NaN, W untouched): an
+        unusable track or start time, a non-finite R, an end pose on or inside a disc at its own node's time, no start outside the discs.
+        Returns nlp_solve_moving's dict plus keep_mult [B][n_mov][N]: the multipliers of the disc constraints."""
+        return self._nlp_core(self.lib.d2d_nlp_solve_keepout_moving, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial),
+                              bounds, want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, moving=(knots, disc),
+                              hard_moving=True)
+
+    def nlp_solve_groups_keepout(self, scen, W, h, n_ac, knots=None, disc=None, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0,
+                                 mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0,
+                                 bounds=None):
+        """nlp_solve_groups_pairs with every aircraft outside its scenario's hard moving discs (d2d_nlp_solve_groups_keepout): knots dev
+        [R][n_mov][n_knot][3] and disc dev [R][n_mov][2] = (R, kind) per SCENARIO, read as nlp_solve_keepout_moving reads them.  A
+        scenario with an unusable track, radius or start time, or with an aircraft whose end pose lies inside a disc or that cannot be
+        started outside the discs, is refused like one with a malformed mask.  Returns nlp_solve_groups_moving's dict plus keep_mult
+        [R*n_ac][n_mov][N]: every aircraft's multipliers."""
+        return self._nlp_core(self.lib.d2d_nlp_solve_groups_keepout, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial),
+                              bounds, n_ac=n_ac, sweeps=(max_sweeps, tol), field=field, t_start=t_start, moving=(knots, disc), hard_moving=True)
 
     def _via_c(self, via, G):
         """d2d_via_points over a device table [G][n_via][5] = (node, mask, x, y, psi), or None: no pins.  Shapes only -- the range of

@@ -2,16 +2,34 @@
 
 
 def nlp_plan(ctx, scen, W, h, *, n_ac=None, field=None, t_start=None, knots=None, disc=None, via=None, free_rows=None, pairs=False, keep=None,
-             **opts):
+             hard_knots=None, hard_disc=None, **opts):
     """The planners' one rule for choosing among the nlp_solve* methods of `ctx` (a Context, or any object that has them) -- the first
     optional input that is given names the entry, which also takes the inputs below it in its column (free_rows: none):
       n_ac given, R scenarios of n_ac aircraft:  via -> _groups_via, knots -> _groups_moving, pairs -> _groups_pairs, field -> _groups_wind,
                                                  none -> nlp_solve_groups;
       n_ac None, B problems handed out:          free_rows -> _free, via -> _via, knots -> _moving, field -> _wind, none -> nlp_solve.
     keep given (n_ac None, no free_rows, via or knots -- each pair refused by name): nlp_solve_keepout with field and t_start.
+    hard_knots / hard_disc given (HARD discs that move: the tables of nlp_solve_moving with disc[.., 0] the node radius): n_ac None ->
+    nlp_solve_keepout_moving, n_ac given -> nlp_solve_groups_keepout, with field and t_start; refused by name together with keep, knots /
+    disc, via or free_rows.
     opts: the entry's own keywords (solver options, bounds, max_sweeps ...).  Returns the entry's dictionary plus `entry`, its name.
     (nlp_solve_model is not chosen here: its objective model is another problem, not an optional input of a plan -- DESIGN.md 5.16.)"""
     wind = dict(field=field, t_start=t_start)
+    if hard_knots is not None or hard_disc is not None:
+        for name, given in (('keep', keep is not None), ('knots', knots is not None), ('disc', disc is not None), ('via', via is not None),
+                            ('free_rows', free_rows is not None)):
+            if given:
+                raise NotImplementedError(f'hard_knots together with {name}: hard moving discs go with neither static hard discs, soft moving '
+                                          'discs, pins nor a free step')
+        if hard_knots is None or hard_disc is None:
+            raise ValueError('hard_knots and hard_disc go together')
+        entry = 'nlp_solve_keepout_moving' if n_ac is None else 'nlp_solve_groups_keepout'
+        kw = dict(knots=hard_knots, disc=hard_disc, **wind)
+        if n_ac is not None:
+            kw['n_ac'] = n_ac
+        out = getattr(ctx, entry)(scen, W, h, **kw, **opts)
+        out['entry'] = entry
+        return out
     if keep is not None:
         # hard keep-out discs (dev [B][n_keep][3]): nlp_solve_keepout, with the field and the start times; alone among the optional inputs
         for name, given in (('n_ac', n_ac is not None), ('free_rows', free_rows is not None), ('via', via is not None), ('knots', knots is not None)):

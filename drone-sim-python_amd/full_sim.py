@@ -319,6 +319,22 @@ def _moving_tables(ctx, moving, n_scen):
     return ctx.dev(np.stack([t[0] for t in tabs])), ctx.dev(np.stack([t[1] for t in tabs]))
 
 
+def _hard_moving_tables(ctx, hard, rows, n_ac, h):
+    """Device tables (knots [n_scen][n][n_knot][3], disc [n_scen][n][2] = (R, 1)) of `hard`: a list of d2d.opty_utils.MovingKeepOut /
+    KeepOut that every scenario holds, or one such list per scenario (the same number of discs in each), lowered with the largest
+    VMAX of the scenario's rows and h."""
+    import d2d.opty_utils as d2ou
+    n_scen = len(rows) // n_ac
+    hard = list(hard)
+    per = [list(m) for m in hard] if hard and not hasattr(hard[0], 'lowered') else [hard] * n_scen
+    if len(per) != n_scen or len({len(m) for m in per}) != 1 or not per[0]:
+        raise ValueError(f'hard_moving: one non-empty list for all scenarios or one list per scenario ({n_scen}) with the same number of discs')
+    n_knot = max([len(o.t) for m in per for o in m if hasattr(o, 't')] + [2])
+    vmax = rows[:, d2dhip.SC_VMAX].reshape(n_scen, n_ac).max(axis=1)
+    tabs = [d2ou.lower_keep_moving(m, float(vmax[r]), h, n_knot) for r, m in enumerate(per)]
+    return ctx.dev(np.stack([t[0] for t in tabs])), ctx.dev(np.stack([t[1] for t in tabs]))
+
+
 def _via_table(dsc, n_ac, N, h, t_start, via):
     """plan_batch's timed waypoints: the table (B, n_via, 5) of every problem on its scenario's clock."""
     import d2d.opty_utils as d2ou
@@ -342,7 +358,7 @@ def _dev_i32(ctx, v, n, name):
 
 
 def deconflict_plans(ctx, scen, W, h, n_ac, world=None, prio=None, row0=None, *, d_sep, margin, d_look, n_knot=32, n_mov=8, max_rounds=4,
-                     field=None, t0=0.0, step_max=None, kind=1, **solve_kw):
+                     field=None, t0=0.0, step_max=None, kind=1, hard=False, **solve_kw):
     """Prioritised re-planning of formations that share an airspace.  scen dev [R n_ac][SCEN_STRIDE] and W dev [R n_ac][5][N] are the
     rows and the plans of R formations of n_ac aircraft, from any collocation entry, node i of formation r at t0 + (row0[r] + i) h;
     world, prio, row0: (R,) integers or device int32 tensors (None: one world, the formation index, 0).  The formation with the smaller
@@ -360,10 +376,18 @@ def deconflict_plans(ctx, scen, W, h, n_ac, world=None, prio=None, row0=None, *,
     step_max (m): the longest step of any plan between two nodes, for the grid of fleet_tracks; None: h (max SC_VMAX + max |row wind|)
     x 1.05, read once before the first round (with a field it must be given).  solve_kw: the solver's keywords; bounds dev [R n_ac][4]
     are gathered with the rows.
-    The moving discs are a SOFT cost (the rows' KOBS and S weigh them): the function REPORTS the separation it reached and never
-    asserts it.  Returns W (changed in place) and info: rounds; replanned (formations re-solved, per round); solves (per round:
+    hard=False: the moving discs are a SOFT cost (the rows' KOBS and S weigh them) and the function reports the separation it reached.
+    hard=True: the discs are HARD constraints of the re-solve (nlp_solve_groups_keepout; nlp_solve_keepout_moving when n_ac == 1), with
+    the node radius R = sqrt((d_sep + margin)^2 + step_max^2) + chord_err, computed on the device; the rows' soft static discs still
+    count, `kind` is not read.  step_max is the longest step of any plan between two nodes, so two aircraft move at most 2 step_max
+    relative to each other between two rows, and a relative chord between two relative positions on the circle R passes the centre at
+    sqrt(R^2 - step_max^2) >= d_sep + margin.  THE THEOREM: if truncated is false and not_converged, refused and unresolved are empty
+    at a fixed point of the loop (rounds < max_rounds), every aircraft's continuous closest approach to every outranking aircraft
+    within d_look is >= d_sep + margin.
+    Returns W (changed in place) and info: rounds; replanned (formations re-solved, per round); solves (per round:
     dict(forms, cost, status, feas) of device tensors); truncated (some formation had more partners than n_mov in some round);
-    not_converged (formation indices); tracks_status (dev int32 [R] of the last round); audit: the final Context.fleet_audit
+    not_converged (formation indices); refused (hard=True: formations whose re-solve was refused on the device -- e.g. an outranking
+    aircraft inside R of their pinned start pose; they keep their plan, like not_converged; else []); tracks_status (dev int32 [R] of the last round); audit: the final Context.fleet_audit
     (near_dist, near_partner, ... with d_safe = d_sep); unresolved: the formations with an aircraft still below d_sep."""
     import torch                    # (tensor plumbing on the device of W; everything computed goes through ctx)
     n_ac, n_mov, n_knot = int(n_ac), int(n_mov), int(n_knot)
@@ -385,6 +409,9 @@ def deconflict_plans(ctx, scen, W, h, n_ac, world=None, prio=None, row0=None, *,
     last_set = torch.full((R, n_mov), -2, dtype=torch.int32, device=W.device)       # the partners a formation was last solved against
     changed = torch.zeros(R, dtype=torch.bool, device=W.device)                       # plans that the round before replaced
     bad = torch.zeros(R, dtype=torch.bool, device=W.device)
+    refused = torch.zeros(R, dtype=torch.bool, device=W.device)
+    if hard:
+        r_disc = float(np.sqrt(r_disc ** 2 + float(step_max) ** 2))
     trunc = torch.zeros((), dtype=torch.bool, device=W.device)
     replanned, solves, tr = [], [], None
     fleet_kw = dict(row0=row0, world=world)
@@ -405,25 +432,32 @@ def deconflict_plans(ctx, scen, W, h, n_ac, world=None, prio=None, row0=None, *,
         args = (scen[sel].contiguous(), Wg, h)
         kw = dict(knots=tr['knots'][forms].contiguous(), disc=disc[forms].contiguous(), field=field, t_start=t_start[forms].contiguous(),
                   **({} if bounds is None else dict(bounds=bounds[sel].contiguous())), **solve_kw)
-        res = ctx.nlp_solve_moving(*args, **kw) if n_ac == 1 else ctx.nlp_solve_groups_moving(*args, n_ac, **kw)
+        if hard:
+            res = ctx.nlp_solve_keepout_moving(*args, **kw) if n_ac == 1 else ctx.nlp_solve_groups_keepout(*args, n_ac, **kw)
+        else:
+            res = ctx.nlp_solve_moving(*args, **kw) if n_ac == 1 else ctx.nlp_solve_groups_moving(*args, n_ac, **kw)
         ok = (res['status'] == d2dhip.ST_CONVERGED).view(n, n_ac).all(dim=1)
         W[sel] = torch.where(ok.repeat_interleave(n_ac)[:, None, None], Wg, W[sel])
         changed = torch.zeros_like(changed)
         changed[forms] = ok
         bad[forms] = ~ok
+        if hard:
+            refused[forms] = (res['status'] == d2dhip.ST_NONFINITE).view(n, n_ac).any(dim=1)
+            bad[forms] &= ~refused[forms]
         last_set[forms] = pset[forms]
         replanned.append(n)
         solves.append(dict(forms=forms, cost=res['cost'], status=res['status'], feas=res['feas']))
     audit = ctx.fleet_audit(W.permute(2, 1, 0).contiguous(), n_ac, h, float(d_look), step_max, d_safe=float(d_sep), **fleet_kw)
     low = (audit['near_dist'] < float(d_sep)).view(R, n_ac).any(dim=1)
     info = dict(rounds=len(replanned), replanned=replanned, solves=solves, truncated=bool(trunc.item()),
-                not_converged=[int(f) for f in torch.nonzero(bad).flatten().cpu()], tracks_status=None if tr is None else tr['status'],
+                not_converged=[int(f) for f in torch.nonzero(bad).flatten().cpu()],
+                refused=[int(f) for f in torch.nonzero(refused).flatten().cpu()], tracks_status=None if tr is None else tr['status'],
                 audit=audit, unresolved=[int(f) for f in torch.nonzero(low).flatten().cpu()])
     return W, info
 
 
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, deconflict=None, **solve_kw):
+               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, deconflict=None, hard_moving=None, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -452,8 +486,13 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     it, or a list of d2d.opty_utils.KeepOut for all problems, lowered with each row's VMAX and h (d2d_nlp_solve_keepout, with and
     without a field); the result carries keep_mult (device [B][n][K]) and keep (the lowered table, a host array (B, n, 3)).  Not combined with n_ac > 1, moving,
     via or free_time: raised by name.
+    hard_moving (backend='nlp', any n_ac): hard keep-out discs that MOVE -- a list of d2d.opty_utils.MovingKeepOut (and KeepOut) for all
+    scenarios or one list per scenario -- that every aircraft of the scenario holds, node i at t_start[r] + i h, lowered with the
+    scenario's largest VMAX and h (d2d_nlp_solve_groups_keepout; d2d_nlp_solve_keepout_moving when n_ac = 1; with and without a field);
+    the result carries keep_mult (device [B][n][K]) and hard_knots, hard_disc (the lowered device tables).  Not combined with moving,
+    via, free_time, keep_out or deconflict: raised by name.
     deconflict (backend='nlp'): None -- today's call, bit for bit -- or a dict of deconflict_plans' keywords (d_sep, margin, d_look
-    required; world, prio, n_knot, n_mov, max_rounds, step_max, kind): after the solve the formations (the scenarios) that share a
+    required; world, prio, n_knot, n_mov, max_rounds, step_max, kind, hard): after the solve the formations (the scenarios) that share a
     world give way to each other by priority (deconflict_plans, which re-solves with this call's solve_kw, in the field and from the
     start times of this call); W is updated in place and the result carries deconflict, its info.  Start times must be whole multiples
     of h apart (fleet_row0 names the formation that is not).  Not with the fit backend, free_time, keep_out, via or moving -- the
@@ -485,6 +524,15 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
             if given:
                 raise NotImplementedError(f'keep_out with {name} is not supported: hard discs are held for one aircraft on static discs, '
                                           'without pins, with a fixed step')
+    if hard_moving is not None:
+        if backend != 'nlp':
+            raise NotImplementedError("the polynomial fit has no hard moving discs: plan_batch(backend='nlp', hard_moving=...) holds them")
+        for name, given in (('moving', bool(moving)), ('via', via is not None), ('free_time', free_time is not None),
+                            ('keep_out', keep_out is not None), ('deconflict', deconflict is not None)):
+            if given:
+                raise NotImplementedError(f'hard_moving with {name} is not supported: hard moving discs go with neither soft moving discs, '
+                                          'pins, a free step nor static hard discs (list a KeepOut in hard_moving), and the re-solve of '
+                                          'deconflict does not carry them')
     if deconflict is not None:
         if backend != 'nlp':
             raise NotImplementedError("the polynomial fit has no deconfliction: plan_batch(backend='nlp', deconflict=...) re-plans by priority")
@@ -493,7 +541,7 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
                 raise NotImplementedError(f'deconflict with {name} is not supported: the re-solve around the committed plans '
                                           f'(d2d_nlp_solve_groups_moving) does not carry {name}')
         deconflict = dict(deconflict)
-        unknown = set(deconflict) - {'d_sep', 'margin', 'd_look', 'world', 'prio', 'n_knot', 'n_mov', 'max_rounds', 'step_max', 'kind'}
+        unknown = set(deconflict) - {'d_sep', 'margin', 'd_look', 'world', 'prio', 'n_knot', 'n_mov', 'max_rounds', 'step_max', 'kind', 'hard'}
         missing = {'d_sep', 'margin', 'd_look'} - set(deconflict)
         if unknown or missing:
             raise ValueError(f'deconflict: needs d_sep, margin and d_look and takes world, prio, n_knot, n_mov, max_rounds, step_max, kind '
@@ -531,6 +579,16 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
                     raise ValueError(f'keep_out: an array (B, n, 3) of (cx, cy, R) or a list of KeepOut is required, got shape {keep.shape}')
             out = d2dhip.nlp_plan(ctx, dsc, W, h, keep=ctx.dev(keep), field=fld, t_start=t_start if fld is not None else None, **solve_kw)
             out['keep'] = keep
+        elif hard_moving is not None:
+            hk, hd = _hard_moving_tables(ctx, hard_moving, np.asarray(scen_rows, dtype=np.float64), n_ac, h)
+            pairs = _rows_select_pairs(scen_rows, n_ac)
+            dsc_h = dsc
+            if n_ac >= 2 and not pairs:                         # the reference's pair (0, 1) as the partner sets the group entry reads
+                dsc_h = dsc.clone()
+                d2mou.default_pair_masks(dsc_h, n_ac, (dsc_h[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc_h[1::n_ac, d2dhip.SC_KCOL] > 0))
+            out = d2dhip.nlp_plan(ctx, dsc_h, W, h, n_ac=None if n_ac == 1 else n_ac, field=fld, t_start=t_start, hard_knots=hk, hard_disc=hd,
+                                  **solve_kw)
+            out.update(hard_knots=hk, hard_disc=hd)
         elif free_time is not None:
             B = dsc.shape[0]
             fr = np.zeros((B, 4))

@@ -212,7 +212,12 @@ class Problem:
             if what:
                 raise NotImplementedError(f'keep_out together with {what} is not supported')
             import d2d.opty_utils as d2ou
-            self.keep_rows = d2ou.lower_keep_out(self.keep_out, self.bounds[0]['v'][1], self.time_step)
+            # a list with a MovingKeepOut plans through d2d_nlp_solve_keepout_moving: every disc as a track (a static one stands still)
+            self.keep_moving = any(isinstance(k, d2ou.MovingKeepOut) for k in self.keep_out)
+            if self.keep_moving:
+                self.keep_knots, self.keep_disc = d2ou.lower_keep_moving(self.keep_out, self.bounds[0]['v'][1], self.time_step)
+            else:
+                self.keep_rows = d2ou.lower_keep_out(self.keep_out, self.bounds[0]['v'][1], self.time_step)
         if self.free_step is not None:                  # what a free interval is not combined with (d2d_nlp_solve_free)
             what = ('more than one aircraft (they share one interval: the joint system is not built)' if self.n_aircraft != 1 else
                     'moving obstacles (their node times move with the step)' if self.moving else
@@ -345,7 +350,9 @@ class Problem:
         # its own pairs every aircraft with a partner.
         group = False if self.keep_out else multi if tabled else self.field is None
         ex = dict(field=self.field, t_start=self.t_start if (self.moving or self.field is not None) else None)
-        if self.keep_out:
+        if self.keep_out and self.keep_moving:
+            ex.update(hard_knots=ctx.dev(self.keep_knots[None]), hard_disc=ctx.dev(self.keep_disc[None]), t_start=self.t_start)
+        elif self.keep_out:
             ex['keep'] = ctx.dev(self.keep_rows[None])
         if self.moving:
             import d2d.opty_utils as d2ou
@@ -383,7 +390,10 @@ class Problem:
             info['cost'] = float(out['cost'].sum().item())
         if self.keep_out:                         # per disc: the polyline's clearance from the user's disc (>= its margin)
             import d2d.opty_utils as d2ou
-            info['keep_out_clearance'] = d2ou.keep_out_clearance(self.keep_out, Wh[0, 0], Wh[0, 1])
+            if self.keep_moving:                  # continuous in time, against the moving centre
+                info['keep_out_clearance'] = d2ou.moving_keep_clearance(self.keep_out, self.t_start + np.arange(N) * self.time_step, Wh[0, 0], Wh[0, 1])
+            else:
+                info['keep_out_clearance'] = d2ou.keep_out_clearance(self.keep_out, Wh[0, 0], Wh[0, 1])
         if self.via is not None:                  # 0.0 by construction: a pinned component never leaves its value
             import d2d.opty_utils as d2ou
             info['waypoint_error'] = max(d2ou.waypoint_error(self.via[a], Wh[a]) for a in range(n))

@@ -105,7 +105,8 @@ def check_moving(exp, backend):
 
 
 def check_keep_out(exp, backend, moving=(), waypoints=(), t1_free=None):
-    """The scenario's hard keep-out discs (exp.keep_out, a list of d2d.opty_utils.KeepOut; absent or empty: none) as a list, refused where
+    """The scenario's hard keep-out discs (exp.keep_out, a list of d2d.opty_utils.KeepOut and MovingKeepOut -- with one that moves the
+    list plans through d2d_nlp_solve_keepout_moving; absent or empty: none) as a list, refused where
     they cannot be planned: backend='fit', more than d2dhip.MAX_KEEP, or together with moving obstacles, waypoints or t1_free."""
     keep = list(getattr(exp, 'keep_out', None) or [])
     if not keep:
@@ -115,8 +116,8 @@ def check_keep_out(exp, backend, moving=(), waypoints=(), t1_free=None):
                                   "backend='nlp' (or 'auto') solves the collocation problem with the discs as hard constraints")
     for name, given in (('moving obstacles (moving_obstacles)', bool(moving)), ('waypoints', bool(waypoints)), ('a free duration (t1_free)', t1_free is not None)):
         if given:
-            raise NotImplementedError(f'keep_out together with {name} is not supported: hard discs are planned on static discs, '
-                                      'without pins, with a fixed step (d2d_nlp_solve_keepout)')
+            raise NotImplementedError(f'keep_out together with {name} is not supported: hard discs are planned without soft moving '
+                                      'discs, without pins, with a fixed step (d2d_nlp_solve_keepout, d2d_nlp_solve_keepout_moving)')
     if len(keep) > d2dhip.MAX_KEEP:
         raise NotImplementedError(f'at most {d2dhip.MAX_KEEP} keep-out discs per problem in this build ({len(keep)} given)')
     return keep

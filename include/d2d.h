@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 125
+#define D2D_VERSION 126
 
 /* error codes */
 #define D2D_OK 0
@@ -962,6 +962,45 @@ int d2d_nlp_solve_groups_moving(d2d_ctx *ctx, int R, int n_ac, int N, double h, 
                                 double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
                                 int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
                                 const d2d_moving_obstacles *mov, double *mov_work);
+
+/* d2d_nlp_solve_keepout outside hard discs that MOVE: a committed aircraft is such a disc.  The tracks are a d2d_moving_obstacles table as
+ * it is (d2d_fleet_tracks' output goes straight in), read differently: disc[m][0] is the NODE RADIUS R of the hard constraint (R <= 0:
+ * the disc is absent), disc[m][1] is validated as in d2d_nlp_solve_moving (0 or 1) and otherwise not read.  For problem b, interior node i
+ * and disc m with the centre c_m(t) of d2d_mov_sample:   g_im = |p_i - c_m(t_start[b] + i h)|^2 - R_m^2 > 0.   Merit, stationarity,
+ * right-hand side, KKT error, the Newton block, dz, the exact ratio test, the start rule and the dual clip are d2d_nlp_solve_keepout's
+ * with the node's own centre in the place of c; the centres are data, no derivative is added.  The row's soft static discs still count;
+ * soft moving discs, pins and a free step are not carried.  At most D2D_MAX_MOV (= D2D_MAX_KEEP) discs.
+ * Refused per problem before its first store (D2D_ST_NONFINITE, cost = feas = NaN, iters = 0, W untouched, the rest of the launch
+ * solved): an unusable track (d2d_nlp_solve_moving's rules), a start time that is not finite, a non-finite R, an end pose with g <= 0
+ * at ITS OWN node's time (node 0 at t_start, node N - 1 at t_start + (N - 1) h), a free node with g <= 0 after the start rule.
+ * field, t_start: the rules of d2d_nlp_solve_moving (t_start is required when n_mov > 0).  mov_work dev [B][n_mov][2][N]: the centres,
+ * written by the sampling pass on the context's stream; kwork dev [B][n_mov][N]: the duals, afterwards the constraints' multipliers.
+ * n_mov = 0: the solve of d2d_nlp_solve / d2d_nlp_solve_wind, bit for bit (mov_work and kwork may be NULL).  The constraint holds at the
+ * nodes; between two rows the RELATIVE displacement of aircraft and disc cuts the chord: R = sqrt(d^2 + (s / 2)^2) with s the largest
+ * relative displacement between two nodes keeps the continuous distance >= d (d2d.opty_utils.MovingKeepOut.lowered).
+ * tests/nlp_keepout_moving_ref.py is the CPU statement.  Asynchronous on the context's stream.  (version 126) */
+int d2d_nlp_solve_keepout_moving(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W,
+                                 double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
+                                 const d2d_wind_field *field, const double *t_start, const d2d_moving_obstacles *mov, double *mov_work,
+                                 double *kwork);
+
+/* d2d_nlp_solve_groups_pairs with every aircraft outside its scenario's hard moving discs: the arguments of d2d_nlp_solve_groups_moving
+ * (tracks [R][n_mov][..] per SCENARIO, read as above) plus kwork dev [R n_ac][n_mov][N], every aircraft's own duals.  The block
+ * Gauss-Seidel is d2d_nlp_solve_groups_pairs's (masks in the rows, checked on the device); every aircraft of scenario r holds the
+ * scenario's discs in the uncoupled sweep and in every turn.  Each turn is a full solve from the aircraft's current nodes: the start rule
+ * moves nodes that sit on a boundary back to 1.01 R and the duals restart at mub / g.  A bad track, radius or start time refuses the
+ * whole scenario exactly as a malformed mask does, and so does an aircraft whose end pose lies on or inside a disc at its node's time
+ * or that the start rule cannot place outside the discs -- decided before the first barrier by every wavefront alike.  That decision
+ * is taken on the aircraft's GUESSES.  A later turn starts from the aircraft's current nodes and applies the start rule again; if it
+ * cannot place them (a node the partners' term has moved between two overlapping discs, say), that AIRCRAFT alone reports
+ * D2D_ST_NONFINITE with NaN cost and feas, its W stays what its previous solve left, the other aircraft go on, and `iters` counts the
+ * solves before.  Callers that need all-or-nothing treat any D2D_ST_NONFINITE of a scenario as its refusal (full_sim.deconflict_plans
+ * does: the formation keeps its plan and is listed in `refused`).  With n_mov = 0
+ * the call is d2d_nlp_solve_groups_pairs; with every R <= 0 its results.  (version 126) */
+int d2d_nlp_solve_groups_keepout(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts,
+                                 int max_sweeps, double tol, double *W, double *work, double *mult, double *cost, double *feas,
+                                 int32_t *iters, int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *field,
+                                 const double *t_start, const d2d_moving_obstacles *mov, double *mov_work, double *kwork);
 
 /* Timed waypoints of the collocation planner: components of x, y, psi of INTERIOR nodes held at given values -- a point to fly
  * through at a given time, a gate, a heading at a hand-over.  A pinned component is a fixed variable exactly as x, y, psi of the two end

@@ -4,8 +4,9 @@ four, about four aircraft per 3 x 3 grid cells): 65 536 drones x 256 rows and 81
 of five windows of launches in ms per call (device events) for both calls, their ratio, and what the lists held (formations with
 partners, with more partners than slots).  Then one deconflict_plans run over worlds of four formations of one aircraft whose legs
 cross in the middle of the world (41 nodes): the time of every round (host clock around a synchronised round: the loop reads one
-scalar per round) and what the final audit says.
-python tools/bench_fleet_tracks.py [n_rows] [worlds]"""
+scalar per round) and what the final audit says -- once with the discs a soft cost (margin 4 m) and once with hard=True at margin 0
+(d2d_nlp_solve_keepout_moving: the separation is then held, not reached), both from the same independent plans.
+python tools/bench_fleet_tracks.py [n_rows] [worlds] [deconflict]     (a third argument: the deconflict runs only)"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'drone-sim-python_amd'), os.path.join(ROOT, 'tools')):
@@ -56,12 +57,20 @@ def deconflict_run(ctx, worlds):
     scen, W = ctx.dev(rows), ctx.dev(W0)
     world = np.repeat(np.arange(worlds), 4)
     full_sim.deconflict_plans(ctx, scen[:4].contiguous(), ctx.dev(W0[:4]), h, 1, d_sep=4.0, margin=4.0, d_look=10.0, step_max=2.0)      # warm-up: one world
+    full_sim.deconflict_plans(ctx, scen[:4].contiguous(), ctx.dev(W0[:4]), h, 1, d_sep=4.0, margin=0.0, d_look=10.0, step_max=2.0, hard=True)
     t = time.perf_counter()
     ctx.nlp_solve(scen, W, h)
     torch.cuda.synchronize()
     t_plan = time.perf_counter() - t
-    stamps = []
     tracks = ctx.fleet_tracks
+    W_indep = W.clone()
+    for label, kw in (('soft', dict(margin=4.0)), ('hard', dict(margin=0.0, hard=True))):
+        _deconflict_timed(ctx, tracks, label, kw, scen, W_indep.clone(), h, world, worlds, R, N, t_plan)
+
+
+def _deconflict_timed(ctx, tracks, label, kw, scen, W, h, world, worlds, R, N, t_plan):
+    import torch, full_sim
+    stamps = []
 
     def timed_tracks(*a, **kw):                      # a round begins with its fleet_tracks call
         torch.cuda.synchronize()
@@ -70,15 +79,17 @@ def deconflict_run(ctx, worlds):
 
     ctx.fleet_tracks = timed_tracks
     try:
-        _, info = full_sim.deconflict_plans(ctx, scen, W, h, 1, world=world, d_sep=4.0, margin=4.0, d_look=10.0, step_max=2.0, max_rounds=6)
+        _, info = full_sim.deconflict_plans(ctx, scen, W, h, 1, world=world, d_sep=4.0, d_look=10.0, step_max=2.0, max_rounds=6, **kw)
     finally:
         del ctx.fleet_tracks
     torch.cuda.synchronize()
     stamps.append(time.perf_counter())
     near = info['audit']['near_dist']
-    print(json.dumps({'config': 'deconflict', 'worlds': worlds, 'formations': R, 'n_ac': 1, 'nodes': N, 'independent_plan_ms': t_plan * 1e3,
+    st = torch.cat([sv['status'] for sv in info['solves']]).cpu().numpy() if info['solves'] else np.zeros(0, int)
+    print(json.dumps({'config': 'deconflict', 'discs': label, 'margin': kw['margin'], 'worlds': worlds, 'formations': R, 'n_ac': 1, 'nodes': N, 'independent_plan_ms': t_plan * 1e3,
                       'rounds': info['rounds'], 'replanned': info['replanned'], 'round_ms': [(b - a) * 1e3 for a, b in zip(stamps, stamps[1:])],
-                      'truncated': info['truncated'], 'not_converged': len(info['not_converged']), 'unresolved': len(info['unresolved']),
+                      'truncated': info['truncated'], 'not_converged': len(info['not_converged']), 'refused': len(info['refused']),
+                      'unresolved': len(info['unresolved']), 'status_counts': {int(k): int((st == k).sum()) for k in np.unique(st)},
                       'min_near_dist': float(near[torch.isfinite(near)].min().item())}), flush=True)
 
 
@@ -87,8 +98,9 @@ def main():
     n_rows = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     worlds = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
     ctx = d2dhip.Context(0)
-    tracks_vs_audit(ctx, 65536, n_rows)
-    tracks_vs_audit(ctx, 8192, 8)
+    if len(sys.argv) <= 3:
+        tracks_vs_audit(ctx, 65536, n_rows)
+        tracks_vs_audit(ctx, 8192, 8)
     deconflict_run(ctx, worlds)
     return 0
 

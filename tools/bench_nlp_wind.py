@@ -32,6 +32,11 @@ python tools/bench_nlp_wind.py keepout [B] hard keep-out discs (d2d_nlp_solve_ke
     VMAX and h, no margin), against the same rows without a disc through d2d_nlp_solve, from the same guess.  The two entries
     alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians, the spread of each, statuses, mean and longest
     step counts, and the smallest g / R^2 of the converged plans.
+python tools/bench_nlp_wind.py keepout-moving [B] hard keep-out discs that move (d2d_nlp_solve_keepout_moving): the rows, the disc and the
+    guess of `keepout`, the disc once held still through d2d_nlp_solve_keepout, once as a track that stands still and once crossing
+    the leg at 3 m/s (at the static centre at mid-time; node radius MovingKeepOut.lowered) through d2d_nlp_solve_keepout_moving.  The
+    three alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians, the spread of each, statuses, mean and
+    longest step counts, the smallest g / R^2 of the converged plans, and whether the still track gives the static entry's bytes.
 python tools/bench_nlp_wind.py guess [B]   the start of the solve (d2d_nlp_guess_dubins): B (default 4096) perturbed exp_14 at 121 nodes through
     d2d_nlp_solve from the host dog-leg (d2d.opty_utils.triangle, copied to the device) and from the Dubins start built on the device
     from the same rows.  The two starts alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians and the spread
@@ -307,6 +312,57 @@ def keepout_leg(B):
     ctx.close()
 
 
+def keepout_moving_leg(B):
+    import torch, d2dhip
+    import d2dhip as D
+    from d2dhip import synth
+    from d2d.opty_utils import KeepOut, MovingKeepOut, lower_keep_moving
+    ctx = d2dhip.Context(0)
+    rows, W0, h = synth.nlp_problems(B)
+    N = W0.shape[2]
+    T = (N - 1) * h
+    p0, p1 = rows[:, D.SC_X0:D.SC_X0 + 2], rows[:, D.SC_X1:D.SC_X1 + 2]
+    d = p1 - p0
+    d /= np.hypot(d[:, 0], d[:, 1])[:, None]
+    nrm = np.stack([-d[:, 1], d[:, 0]], 1)
+    c = 0.5 * (p0 + p1) + 3.0 * nrm
+    discs = np.array([[KeepOut(c[b], 15.0).lowered(rows[b, D.SC_VMAX], h)] for b in range(B)])
+    still = [lower_keep_moving([KeepOut(c[b], 15.0)], rows[b, D.SC_VMAX], h) for b in range(B)]
+    cross = [lower_keep_moving([MovingKeepOut((-1.0, T + 1.0), (c[b] - 3.0 * nrm[b] * (0.5 * T + 1.0), c[b] + 3.0 * nrm[b] * (0.5 * T + 1.0)), 15.0)],
+                               rows[b, D.SC_VMAX], h) for b in range(B)]
+    tabs = {k: (ctx.dev(np.stack([t[0] for t in v])), ctx.dev(np.stack([t[1] for t in v]))) for k, v in (('still', still), ('crossing', cross))}
+    dsc, dk = ctx.dev(rows), ctx.dev(discs)
+    names = ('static', 'still', 'crossing')
+    times = {k: [] for k in names}
+    outs, Ws = {}, {}
+    for rep in range(6):                                     # the first launch of each is the warm-up; the entries alternate
+        for what in names:
+            W = ctx.dev(np.ascontiguousarray(W0))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            outs[what] = ctx.nlp_solve_keepout(dsc, W, h, dk) if what == 'static' else ctx.nlp_solve_keepout_moving(dsc, W, h, *tabs[what], t_start=0.0)
+            e1.record(); torch.cuda.synchronize()
+            times[what].append(e0.elapsed_time(e1) * 1e-3)
+            Ws[what] = W
+    med = {k: float(np.median(v[1:])) for k, v in times.items()}
+    same = bool(torch.equal(Ws['static'], Ws['still']) and torch.equal(outs['static']['iters'], outs['still']['iters'])
+                and torch.equal(outs['static']['keep_mult'], outs['still']['keep_mult']))
+    for what in names:
+        st = outs[what]['status'].cpu().numpy(); it = outs[what]['iters'].cpu().numpy()
+        Wh = Ws[what].cpu().numpy()
+        ctr = outs[what]['mov_work'].cpu().numpy()[:, 0] if what != 'static' else np.repeat(discs[:, 0, :2, None], N, axis=2)
+        R = discs[:, 0, 2] if what != 'crossing' else tabs['crossing'][1].cpu().numpy()[:, 0, 0]
+        g = ((Wh[:, 0, 1:-1] - ctr[:, 0, 1:-1]) ** 2 + (Wh[:, 1, 1:-1] - ctr[:, 1, 1:-1]) ** 2) / R[:, None] ** 2 - 1.0
+        ok = st == 1
+        print(json.dumps({'leg': 'keepout-moving', 'B': B, 'nodes': N, 'entry': what, 'seconds_median': med[what], 'seconds_min': min(times[what][1:]),
+                          'seconds_max': max(times[what][1:]), 'problems_per_s': B / med[what], 'over_static': med[what] / med['static'],
+                          'status_counts': {int(k): int((st == k).sum()) for k in np.unique(st)}, 'mean_newton_steps': float(it.mean()),
+                          'max_newton_steps': int(it.max()), 'mean_newton_steps_converged': float(it[ok].mean()) if ok.any() else None,
+                          'min_g_over_R2_converged': float(g[ok].min()) if ok.any() else None,
+                          'still_track_is_the_static_entry_bit_for_bit': same}), flush=True)
+    ctx.close()
+
+
 def guess_leg(B):
     import time
     import torch, d2dhip
@@ -372,6 +428,8 @@ def guess_leg(B):
 def main():
     if sys.argv[1:2] == ['guess']:
         return guess_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    if sys.argv[1:2] == ['keepout-moving']:
+        return keepout_moving_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['keepout']:
         return keepout_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['free']:
