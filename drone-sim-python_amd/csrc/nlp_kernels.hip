@@ -270,12 +270,34 @@ struct NlpKeepMovProb : NlpProb {
 // still are to give d2d_nlp_solve_keepout's bytes.  The static instantiations keep their expressions: their code does not change.
 __device__ __forceinline__ double nlp_dot2(double ax, double bx, double ay, double by) { return fma(ax, bx, ay * by); }
 __device__ __forceinline__ double nlp_keep_g(double dx, double dy, double R) { return fma(-R, R, nlp_dot2(dx, dx, dy, dy)); }
-template <bool MOV, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false>
-using NlpProbT = std::conditional_t<KEEP, std::conditional_t<KMOV, NlpKeepMovProb, NlpKeepProb>,
-                                    std::conditional_t<FREE, NlpFreeProb, std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>>>;
-template <bool VIA, bool KEEP = false, bool KMOV = false>
-using NlpProbV = std::conditional_t<KEEP, std::conditional_t<KMOV, NlpKeepMovProb, NlpKeepProb>,
-                                    std::conditional_t<VIA, NlpViaProb, NlpProb>>;       // for the passes that read no soft disc
+// FENCE instantiations (d2d_nlp_solve_fence, d2d_nlp_solve_groups_fence): the problem INSIDE a convex polygon, a set of half-planes.
+// edges [n][4] = (ax, ay, b, kap), wave-uniform, |a| = 1 the outward normal, a row with ax = ay = 0 absent; z [n][N] the duals of
+// g_ik = b_k - (ax_k x_i + ay_k y_i) > 0  (edge k's plane: z[k * N + i], lane = node), 0 at the two end nodes and for absent edges.  The
+// constraint is linear: grad g = -a, no curvature of its own, and the ratio test is exact.  Every pass walks the edges in a ROLLED loop,
+// ascending k, after the discs; a . p is fma(ax, x, ay y) everywhere (nlp_fence_g, nlp_dot2), so that every instantiation -- and a later
+// one that holds the edges in other registers -- rounds alike (the KMOV note below says why that is not left to the compiler).
+struct NlpFenceSet {
+  const double *edges;
+  double *z;
+  int n;
+};
+// (the static hard discs ride along: KEEP && FENCE reads both sets; FENCE alone, the group kernel, leaves keep unread)
+struct NlpFenceProb : NlpKeepProb {
+  NlpFenceSet fence;
+};
+// (how both sets travel in NlpExtra: through its keep pointer, as NlpKeepMovSet does -- the aggregate keeps its size, and with it the
+// code of every instantiation that was there before)
+struct NlpKeepFenceSet : NlpKeepSet {
+  NlpFenceSet fence;
+};
+__device__ __forceinline__ bool nlp_fence_present(const double *__restrict__ e) { return e[0] != 0.0 || e[1] != 0.0; }
+__device__ __forceinline__ double nlp_fence_g(const double *__restrict__ e, double x, double y) { return e[2] - nlp_dot2(e[0], x, e[1], y); }
+template <bool MOV, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false, bool FENCE = false>
+using NlpProbT = std::conditional_t<FENCE, NlpFenceProb, std::conditional_t<KEEP, std::conditional_t<KMOV, NlpKeepMovProb, NlpKeepProb>,
+                                    std::conditional_t<FREE, NlpFreeProb, std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>>>>;
+template <bool VIA, bool KEEP = false, bool KMOV = false, bool FENCE = false>
+using NlpProbV = std::conditional_t<FENCE, NlpFenceProb, std::conditional_t<KEEP, std::conditional_t<KMOV, NlpKeepMovProb, NlpKeepProb>,
+                                    std::conditional_t<VIA, NlpViaProb, NlpProb>>>;       // for the passes that read no soft disc
 template <bool MOV, typename PB> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const PB &pb) {
   if constexpr (MOV) return &pb.mv;
   else return nullptr;
@@ -359,8 +381,10 @@ __device__ __forceinline__ int nlp_via_mask(const PB &pb, int i) {
 // FREE: ut is the trial value of u = 1 / h (u + a du): the equalities are read at 1 / ut, and the duration term kd / ut, the barrier of
 // u's box and the value +inf outside it join the sums (cost_ref_out: the reference's cost() + k_dur (N - 1) h).
 // KEEP: - mub log g of every (interior node, disc) joins the barrier (one more log per node, of the product), +inf when a g <= 0.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false>
-__device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
+// FENCE: - mub log g of every (interior node, edge) likewise, a log of its own behind the discs'.
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false,
+          bool FENCE = false>
+__device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
                             double mub, double *cost_ref_out, double *feas_out, const NlpModel &md, [[maybe_unused]] double ut = 0.0) {
   const int N = pb.N;
   [[maybe_unused]] const double ht = FREE ? 1.0 / ut : 0.0;
@@ -409,6 +433,20 @@ __device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV> &pb, cons
             pk *= (gk > 0.0 ? gk : 1.0);
           }
           bar += log(pk);
+        }
+      }
+      if constexpr (FENCE) {
+        if (i >= 1 && i < N - 1) {
+          double pf = 1.0;            // at most D2D_MAX_FENCE values g in [1e-12, 1e4]: in range too
+#pragma clang loop unroll(disable)
+          for (int k = 0; k < pb.fence.n; ++k) {
+            const double *__restrict__ e = pb.fence.edges + 4 * k;
+            if (!nlp_fence_present(e)) continue;
+            const double gk = nlp_fence_g(e, w[0], w[1]);
+            if (!(gk > 0.0)) outside = 1;
+            pf *= (gk > 0.0 ? gk : 1.0);
+          }
+          bar += log(pf);
         }
       }
       const double dv = w[4] - s.vsp;
@@ -508,8 +546,12 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // side + (mub / g) 2d, the (x, y) corner of D (half convention)  2 (z / g) d d^T - z I  -- the - z I is the constraint's own, negative,
 // curvature: a corner that it makes indefinite fails a pivot of the reduced system and the caller raises the damping -- and the KKT
 // error |z g - mub|.  Nothing else of the pass changes.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false>
-__device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
+// FENCE: edge k at an interior node i, g = b - a . p, grad g = -a, dual z: the stationarity rows of (x, y) gain + z a, the right-hand side
+// - (mub / g) a, the (x, y) corner of D (half convention)  1/2 (z / g) a a^T  -- positive semidefinite, the constraint has no curvature --
+// and the KKT error |z g - mub|.  The sums kst, krh are the discs' (of grad g), so both families leave through the same two lines below.
+template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false,
+          bool FENCE = false>
+__device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
                                double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md, [[maybe_unused]] NlpFreeRow *fr_out = nullptr) {
   const int N = pb.N;
   const double h = pb.h, ih = 1.0 / h;
@@ -617,6 +659,20 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV> &pb, c
           }
         }
       }
+      if constexpr (FENCE) {
+        if (i >= 1 && i < N - 1) {
+#pragma clang loop unroll(disable)
+          for (int k = 0; k < pb.fence.n; ++k) {
+            const double *__restrict__ e = pb.fence.edges + 4 * k;
+            if (!nlp_fence_present(e)) continue;
+            const double ax = e[0], ay = e[1], gk = nlp_fence_g(e, wc[0], wc[1]), z = pb.fence.z[(size_t)k * N + i], ig = 1.0 / gk, zg = 0.5 * (z * ig), mg = mub * ig;
+            kst[0] = fma(-z, ax, kst[0]); kst[1] = fma(-z, ay, kst[1]);
+            krh[0] = fma(-mg, ax, krh[0]); krh[1] = fma(-mg, ay, krh[1]);
+            D[0][0] = fma(zg * ax, ax, D[0][0]); D[0][1] = fma(zg * ax, ay, D[0][1]); D[1][1] = fma(zg * ay, ay, D[1][1]);
+            err = fmax(err, fabs(z * gk - mub));
+          }
+        }
+      }
       D[1][0] = D[0][1];
     }
     double E[NLP_NV][3];                        // block (i, i-1): only the (x, y, psi) columns of node i-1 are non-zero
@@ -697,7 +753,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV> &pb, c
         sig += z * isu; r -= mub * isu; st += z;
         err = fmax(err, fabs(z * su - mub));
       }
-      if constexpr (KEEP) {
+      if constexpr (KEEP || FENCE) {
         if (c < 2 && !fx) { r += krh[c]; st -= kst[c]; }
       }
       if (!fx) err = fmax(err, fabs(st));
@@ -1317,8 +1373,10 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
 // g(a) >= (1 - tau) g is the smaller positive root of  |s|^2 a^2 + 2 (d.s) a + tau g = 0  (none when d.s >= 0 or the discriminant is not
 // positive), in the form tau g / (sqrt(disc) - d.s) that does not cancel; the dual's step is dz = mub / g - z - (z / g) 2 d.s.  The
 // directional derivative needs nothing: the right-hand side carries the discs' terms.
-template <bool VIA = false, bool KEEP = false, bool KMOV = false>
-__device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP, KMOV> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
+// FENCE: g is linear in the step, g(a) = g - a (a . s): the rule is a <= tau g / (a . s) where a . s > 0, taken like a box bound's; the
+// dual's step is dz = (mub + z a . s) / g - z.
+template <bool VIA = false, bool KEEP = false, bool KMOV = false, bool FENCE = false>
+__device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP, KMOV, FENCE> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
                                   double *amax_out, double *az_out) {
   const int N = pb.N;
   double dphi = 0.0, amax = 1.0, az = 1.0;
@@ -1384,6 +1442,19 @@ __device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP, KMOV> &pb, const Nlp
             if (disc > 0.0) amax = fmin(amax, cq / (sqrt(disc) - bh));
           }
           const double dz = (mub - 2.0 * z * bh) / gk - z;
+          if (-dz * az > tau * z) az = -tau * z / dz;
+        }
+      }
+    }
+    if constexpr (FENCE) {
+      if (i >= 1 && i < N - 1) {
+#pragma clang loop unroll(disable)
+        for (int k = 0; k < pb.fence.n; ++k) {
+          const double *__restrict__ e = pb.fence.edges + 4 * k;
+          if (!nlp_fence_present(e)) continue;
+          const double gk = nlp_fence_g(e, wv[0], wv[1]), z = pb.fence.z[(size_t)k * N + i], as = nlp_dot2(e[0], dwv[0], e[1], dwv[1]);
+          if (as * amax > tau * gk) amax = tau * gk / as;
+          const double dz = fma(z, as, mub) / gk - z;
           if (-dz * az > tau * z) az = -tau * z / dz;
         }
       }
@@ -1485,8 +1556,9 @@ __device__ bool nlp_recover_free(const NlpFreeProb &pb, const NlpScen &s, int la
 
 // Take the step (node-parallel): W += a dw, duals += az dz (dz from the step's dw), duals kept near the central path.
 // KEEP: the discs' duals move and are clipped like the box duals, with g at the new point.
-template <bool VIA = false, bool KEEP = false, bool KMOV = false>
-__device__ void nlp_apply(const NlpProbV<VIA, KEEP, KMOV> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
+// FENCE: the edges' duals likewise.
+template <bool VIA = false, bool KEEP = false, bool KMOV = false, bool FENCE = false>
+__device__ void nlp_apply(const NlpProbV<VIA, KEEP, KMOV, FENCE> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
   const int N = pb.N;
   for (int i0 = 0; i0 < N; i0 += 64) {
     const int i = i0 + lane;
@@ -1533,6 +1605,21 @@ __device__ void nlp_apply(const NlpProbV<VIA, KEEP, KMOV> &pb, const NlpScen &s,
           double zn = z + az * ((mub - 2.0 * z * bh) / gk - z);
           zn = fmin(fmax(zn, 1e-10 * mn), 1e10 * mn);
           pb.keep.z[(size_t)m * N + i] = zn;
+        }
+      }
+    }
+    if constexpr (FENCE) {
+      if (i >= 1 && i < N - 1) {
+        const double xn = fma(a, dwl[0], wv[0]), yn = fma(a, dwl[1], wv[1]);      // (the new node, for the clip's bounds only)
+#pragma clang loop unroll(disable)
+        for (int k = 0; k < pb.fence.n; ++k) {
+          const double *__restrict__ e = pb.fence.edges + 4 * k;
+          if (!nlp_fence_present(e)) continue;
+          const double gk = nlp_fence_g(e, wv[0], wv[1]), gn = nlp_fence_g(e, xn, yn), z = pb.fence.z[(size_t)k * N + i];
+          const double as = nlp_dot2(e[0], dwl[0], e[1], dwl[1]), mn = mub / gn;
+          double zn = z + az * (fma(z, as, mub) / gk - z);
+          zn = fmin(fmax(zn, 1e-10 * mn), 1e10 * mn);
+          pb.fence.z[(size_t)k * N + i] = zn;
         }
       }
     }
@@ -1588,7 +1675,7 @@ struct NlpExtra {
   const NlpViaSet *via;      // VIA
   const double *free_row;    // FREE: (h_lo, h_hi, k_dur, h_start; 0 = the launch's h) of the problem, and where its solved h goes
   double *h_out;
-  const NlpKeepSet *keep;    // KEEP (KMOV: the NlpKeepMovSet it is the base of)
+  const NlpKeepSet *keep;    // KEEP (KMOV: the NlpKeepMovSet it is the base of; FENCE: the NlpKeepFenceSet)
 };
 
 // KEEP: the start of a free node's position.  The box push of the start pass, then every disc in index order, twice (a push out of one
@@ -1693,6 +1780,65 @@ __device__ __forceinline__ bool nlp_keep_bad(const NlpScen &s, const NlpKeepMovS
   }
   return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
 }
+// FENCE: the start of a free node's position, behind the discs' rule where both are present (the caller has applied the box push, or
+// nlp_keep_start has): every edge in index order, twice (at a corner a push off one edge can land in its neighbour's margin: the second
+// pass undoes that) -- a node with g_k < kap_k moves along -a_k, the inward normal, to g_k = kap_k.  A node with g >= kap at every edge
+// is not touched.  The caller re-applies the box push.
+__device__ __forceinline__ void nlp_fence_start(const NlpFenceSet &f, double &x, double &y) {
+#pragma clang loop unroll(disable)
+  for (int q = 0; q < 2 * f.n; ++q) {
+    const double *__restrict__ e = f.edges + 4 * (q < f.n ? q : q - f.n);
+    if (!nlp_fence_present(e)) continue;
+    const double gk = nlp_fence_g(e, x, y);
+    if (gk < e[3]) {
+      const double t = e[3] - gk;
+      x = fma(-t, e[0], x); y = fma(-t, e[1], y);
+    }
+  }
+}
+// FENCE: what refuses a problem before its first store (wave-uniform): an edge with a non-finite entry, a present edge whose normal is
+// off unit length by more than 1e-12 or whose kap is not positive, an end pose on or outside an edge, or a free node that the start
+// rules -- the discs', then the edges', then the box push -- leave on or outside an edge or (KEEP) on or inside a disc.
+template <bool KEEP>
+__device__ __forceinline__ bool nlp_fence_bad(const NlpScen &s, const NlpFenceProb &pb, const double *__restrict__ Wb, int N, int lane) {
+  int bad = 0;
+  const NlpFenceSet &f = pb.fence;
+#pragma clang loop unroll(disable)
+  for (int k = 0; k < f.n; ++k) {
+    const double *__restrict__ e = f.edges + 4 * k;
+    bad |= !(fabs(e[0]) <= 1.79e308) || !(fabs(e[1]) <= 1.79e308) || !(fabs(e[2]) <= 1.79e308) || !(fabs(e[3]) <= 1.79e308);
+    if (!nlp_fence_present(e)) continue;
+    bad |= !(fabs(sqrt(nlp_dot2(e[0], e[0], e[1], e[1])) - 1.0) <= 1e-12) || !(e[3] > 0.0);
+    bad |= !(nlp_fence_g(e, s.p0[0], s.p0[1]) > 0.0) || !(nlp_fence_g(e, s.p1[0], s.p1[1]) > 0.0);
+  }
+  if (bad) return true;                      // (wave-uniform so far: the edges' table is)
+  for (int i0 = 0; i0 < N; i0 += 64) {
+    const int i = i0 + lane;
+    if (i < 1 || i >= N - 1) continue;
+    double x = Wb[i], y = Wb[N + i];
+    if constexpr (KEEP) nlp_keep_start(s, pb.keep, x, y);
+    else { x = nlp_box_push(x, s.lo[0], s.hi[0]); y = nlp_box_push(y, s.lo[1], s.hi[1]); }
+    nlp_fence_start(f, x, y);
+    x = nlp_box_push(x, s.lo[0], s.hi[0]); y = nlp_box_push(y, s.lo[1], s.hi[1]);
+#pragma clang loop unroll(disable)
+    for (int k = 0; k < f.n; ++k) {
+      const double *__restrict__ e = f.edges + 4 * k;
+      if (!nlp_fence_present(e)) continue;
+      bad |= !(nlp_fence_g(e, x, y) > 0.0);
+    }
+    if constexpr (KEEP) {
+      const double *__restrict__ dk = pb.keep.discs;
+#pragma clang loop unroll(disable)
+      for (int m = 0; m < pb.keep.n; ++m) {
+        const double R = dk[3 * m + 2];
+        if (!(R > 0.0)) continue;
+        const double dx = x - dk[3 * m], dy = y - dk[3 * m + 1];
+        bad |= !(dx * dx + dy * dy - R * R > 0.0);
+      }
+    }
+  }
+  return __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
+}
 
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
@@ -1712,8 +1858,11 @@ __device__ __forceinline__ bool nlp_keep_bad(const NlpScen &s, const NlpKeepMovS
 // (nlp_keep_start) and unusable discs refuse the problem (nlp_keep_bad).  cost does not see the discs.
 // KMOV (d2d_nlp_solve_keepout_moving, d2d_nlp_solve_groups_keepout): KEEP with ex.keep a NlpKeepMovSet, discs that move: g at node i is taken with the
 // disc's centre at that node's time (NlpKeepMovSet).  Nothing else changes: the centres are data.
+// FENCE (d2d_nlp_solve_fence, d2d_nlp_solve_groups_fence): ex.fence the problem's half-planes and the planes of their duals; g > 0 is held at
+// every interior node by the same barrier (the four passes above), the start is moved inside (nlp_fence_start, behind nlp_keep_start) and
+// unusable edges refuse the problem (nlp_fence_bad).  With KEEP the static hard discs are held too.  cost does not see the edges.
 template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false,
-          bool KMOV = false>
+          bool KMOV = false, bool FENCE = false>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
                                               const double *__restrict__ bnd, const NlpExtra &ex = NlpExtra{}) {
@@ -1726,7 +1875,8 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   if (st_on) st_t = __builtin_amdgcn_s_memtime();
   NlpScen s = nlp_load_scen(sc, o, bnd);
   if (sc[D2D_SC_BANKMAX] != 0.0) { s.sbank = s.skphi * (double)N; s.skphi = 0.0; }     // obj_scale * kbank (the row's S is obj_scale / N)
-  NlpProbT<MOV, VIA, FREE, KEEP, KMOV> pb;
+  NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> pb;
+  if constexpr (FENCE) pb.fence = static_cast<const NlpKeepFenceSet *>(ex.keep)->fence;
   if constexpr (KEEP && KMOV) pb.keep = *static_cast<const NlpKeepMovSet *>(ex.keep);
   else
   if constexpr (KEEP) pb.keep = *ex.keep;
@@ -1761,6 +1911,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       if (lane == 0) *ex.h_out = __builtin_nan("");
     }
     if constexpr (KEEP) bad = bad || nlp_keep_bad(s, pb.keep, Wb, N, lane);
+    if constexpr (FENCE) bad = bad || nlp_fence_bad<KEEP>(s, pb, Wb, N, lane);
     if (bad) {
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
       return;
@@ -1792,10 +1943,14 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       kxy[0] = NLP_W(0, i); kxy[1] = NLP_W(1, i);
       nlp_keep_start<KMOV>(s, pb.keep, kxy[0], kxy[1], i, N);
     }
+    if constexpr (FENCE) {
+      if constexpr (!KEEP) { kxy[0] = nlp_box_push(NLP_W(0, i), s.lo[0], s.hi[0]); kxy[1] = nlp_box_push(NLP_W(1, i), s.lo[1], s.hi[1]); }
+      nlp_fence_start(pb.fence, kxy[0], kxy[1]);
+    }
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) {
       double w = NLP_W(c, i);
-      if constexpr (KEEP) { if (c < 2) w = kxy[c]; }
+      if constexpr (KEEP || FENCE) { if (c < 2) w = kxy[c]; }
       double zl = 0.0, zu = 0.0;
       if (nlp_fixed_at<VIA>(i, N, c, vmi)) {
         if constexpr (VIA) w = (i == 0) ? s.p0[c] : (i == N - 1 ? s.p1[c] : pin[c]);
@@ -1811,7 +1966,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         if (hu) zu = mub / (s.hi[c] - w);
       }
       NLP_W(c, i) = w;
-      if constexpr (KEEP) { if (c < 2) kxy[c] = w; }
+      if constexpr (KEEP || FENCE) { if (c < 2) kxy[c] = w; }
       NLP_P(WS_ZL + c, i) = zl; NLP_P(WS_ZU + c, i) = zu;
       NLP_DW(c, i) = 0.0;
     }
@@ -1824,6 +1979,13 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         const double R = dk[KMOV ? 2 * m : 3 * m + 2], dx = kxy[0] - (KMOV ? cxm : dk[3 * m]), dy = kxy[1] - (KMOV ? cym : dk[3 * m + 1]);
         // (KMOV: the static kernels fuse the OTHER product in this one place)
         pb.keep.z[(size_t)m * N + i] = (R > 0.0 && i >= 1 && i < N - 1) ? mub / (KMOV ? nlp_keep_g(dy, dx, R) : dx * dx + dy * dy - R * R) : 0.0;
+      }
+    }
+    if constexpr (FENCE) {                   // the edges' duals on the central path; 0 at the end nodes and for absent edges
+#pragma clang loop unroll(disable)
+      for (int k = 0; k < pb.fence.n; ++k) {
+        const double *__restrict__ e = pb.fence.edges + 4 * k;
+        pb.fence.z[(size_t)k * N + i] = (nlp_fence_present(e) && i >= 1 && i < N - 1) ? mub / nlp_fence_g(e, kxy[0], kxy[1]) : 0.0;
       }
     }
 #pragma unroll
@@ -1856,7 +2018,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     double phi0;
     if constexpr (FREE) phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md, pb.u);
     else
-    phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -1879,7 +2041,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
           const double d0 = pb.kd / (u * u * u) + fr.dd + 0.5 * (pb.zul / sl + pb.zuu / su);
           dfull = d0 + lam * fmax(fabs(d0), 1e-12);
         } else
-        err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -1910,7 +2072,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
           NLP_STAMP(4)
           if (!spd) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
         } else {
-        nlp_recover_stats<VIA, KEEP, KMOV>(pb, s, lane, mub, tau, &dphi, &amax, &az);
+        nlp_recover_stats<VIA, KEEP, KMOV, FENCE>(pb, s, lane, mub, tau, &dphi, &amax, &az);
         nlp_phase_sync();
         NLP_STAMP(4)
         }
@@ -1920,14 +2082,14 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         for (int ls = 0; ls < 8; ++ls) {
           if constexpr (FREE) pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md, pb.u + a * du);
           else
-          pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
+          pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
         NLP_STAMP(0)
         if (ok) {
           phi0 = pt;
-          nlp_apply<VIA, KEEP, KMOV>(pb, s, lane, a, az, mub);
+          nlp_apply<VIA, KEEP, KMOV, FENCE>(pb, s, lane, a, az, mub);
           if constexpr (FREE) {              // u and its duals move like a node variable (nlp_apply)
             const double u = pb.u, un = u + a * du, sl = u - pb.ulo, su = pb.uhi - u;
             const double ml = mub / (un - pb.ulo), mh = mub / (pb.uhi - un);
@@ -1947,7 +2109,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     }
     if constexpr (FREE) (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
     else
-    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -1992,7 +2154,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
     if (lane == 0) *ex.h_out = pb.h;
   } else
-  (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+  (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -2126,7 +2288,9 @@ __device__ __forceinline__ void nlp_report(int b, int lane, const NlpOut &out, d
 // (the problem's, not the slot's: they are a result).
 // KMOV (nlp_solve_keepout_moving_kernel): KEEP with the hard discs in mv and ctr -- the tracks are checked like MOV's, the planes of the
 // duals kwork [B][n_mov][N].
-template <bool WIND, bool MOV, bool VIA, bool T_AT, bool FREE = false, bool KEEP = false, bool KMOV = false>
+// FENCE (nlp_solve_fence_kernel): KEEP with the problems' half-planes fence->edges [B][n_edge][4] and the planes of their duals fwork
+// [B][n_edge][N] beside the discs' (n_keep may be 0: keep->discs and kwork are then not read).
+template <bool WIND, bool MOV, bool VIA, bool T_AT, bool FREE = false, bool KEEP = false, bool KMOV = false, bool FENCE = false>
 __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d2d_nlp_opts &o, const double *scen, double *W, double *work,
                                                  double *mult, double *cost_out, double *feas_out, int32_t *iters_out, int32_t *status_out,
                                                  int32_t *queue, const d2d_wind_field *wf, double t_start, const double *t_at = nullptr,
@@ -2134,7 +2298,8 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
                                                  const d2d_via_points *via = nullptr, int32_t *vwork = nullptr,
                                                  const double *free_rows = nullptr, double *h_out = nullptr,
                                                  [[maybe_unused]] unsigned long long *stamps = nullptr,
-                                                 [[maybe_unused]] const d2d_keep_out *keep = nullptr, [[maybe_unused]] double *kwork = nullptr) {
+                                                 [[maybe_unused]] const d2d_keep_out *keep = nullptr, [[maybe_unused]] double *kwork = nullptr,
+                                                 [[maybe_unused]] const d2d_fence *fence = nullptr, [[maybe_unused]] double *fwork = nullptr) {
   const int lane = threadIdx.x;
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   double *wsb = work + (size_t)blockIdx.x * (FREE ? WSF_TOTAL : WS_TOTAL) * N;
@@ -2175,6 +2340,12 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
       nlp_solve_one<false, false, false, false, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
                                                              lane, out, b == 0 ? stamps : nullptr, nlp_lds, bnd,
                                                              NlpExtra{{nullptr, nullptr, nullptr}, nullptr, 0.0, 0u, nullptr, nullptr, free_rows + (size_t)b * 4, h_out + b});
+    } else if constexpr (FENCE) {
+      const NlpKeepFenceSet ks{{keep->discs + (size_t)b * keep->n_keep * 3, kwork + (size_t)b * keep->n_keep * N, keep->n_keep},
+                               {fence->edges + (size_t)b * fence->n_edge * 4, fwork + (size_t)b * fence->n_edge * N, fence->n_edge}};
+      nlp_solve_one<false, WIND, false, false, false, false, true, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb,
+                                                                                mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds, bnd,
+                                                                                NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, nullptr, nullptr, nullptr, nullptr, &ks});
     } else if constexpr (KEEP && KMOV) {
       const NlpKeepMovSet ks{{mv->disc + (size_t)b * mv->n_mov * 2, kwork + (size_t)b * mv->n_mov * N, mv->n_mov}, ctr + (size_t)b * mv->n_mov * 2 * N};
       nlp_solve_one<false, WIND, false, false, false, false, true, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
@@ -2222,6 +2393,18 @@ nlp_solve_keepout_kernel(int B, int N, double h, d2d_nlp_opts o, const double *_
                          d2d_keep_out keep, double *kwork) {
   nlp_handout_body<WIND, false, false, true, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, 0.0,
                                                           t_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &keep, kwork);
+}
+
+// d2d_nlp_solve_fence: inside every problem's convex polygon and outside its hard discs
+template <bool WIND>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_fence_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                       double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                       int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
+                       d2d_keep_out keep, double *kwork, d2d_fence fence, double *fwork) {
+  nlp_handout_body<WIND, false, false, true, false, true, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue,
+                                                                       &wf, 0.0, t_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                       &keep, kwork, &fence, fwork);
 }
 
 // d2d_nlp_solve_keepout_moving: outside every problem's hard discs that move -- the centre planes ctr [B][n_mov][2][N] sampled ahead
@@ -2358,7 +2541,11 @@ __device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
 //   uncoupled sweep and in every turn; kwork [R n_ac][n_mov][N] the planes of their duals, every aircraft its own.  Tracks, radii and the
 //   start time are checked like MOV's; an aircraft whose end pose lies inside a disc or that the start rule cannot place outside the
 //   discs refuses the SCENARIO -- every wavefront checks every aircraft of the scenario, before the first barrier, as VIA checks the pins.
-template <bool WIND, bool PAIRS, bool MOV = false, bool VIA = false, bool KMOV = false>
+// FENCE (d2d_nlp_solve_groups_fence): fence->edges [R][n_edge][4] is the SCENARIO's polygon, held by every aircraft in the uncoupled sweep
+//   and in every turn; fwork [R n_ac][n_edge][N] the planes of the duals, every aircraft its own.  No hard discs.  An unusable edge, or an
+//   aircraft whose end pose lies on or outside an edge or that the start rule cannot place inside, refuses the SCENARIO -- every wavefront
+//   checks every aircraft, before the first barrier, as KMOV does.  A later turn that cannot start refuses that aircraft alone.
+template <bool WIND, bool PAIRS, bool MOV = false, bool VIA = false, bool KMOV = false, bool FENCE = false>
 __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h, const d2d_nlp_opts &o, int max_sweeps, double tol,
                                                 const double *scen, double *W, double *work, double *mult, double *prev,
                                                 double *cost_out, double *feas_out, int32_t *iters_out,
@@ -2366,7 +2553,8 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
                                                 const d2d_wind_field *wf, const double *t_start,
                                                 const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr,
                                                 const d2d_via_points *via = nullptr, int32_t *vwork = nullptr,
-                                                [[maybe_unused]] double *kwork = nullptr) {
+                                                [[maybe_unused]] double *kwork = nullptr,
+                                                [[maybe_unused]] const d2d_fence *fence = nullptr, [[maybe_unused]] double *fwork = nullptr) {
   __shared__ double moved_s[PAIRS ? 8 : 2];
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -2432,6 +2620,20 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
     }
     __syncthreads();                         // (every wavefront has read every aircraft's start before the first solve writes one)
   }
+  [[maybe_unused]] NlpKeepFenceSet kfs{{nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
+  if constexpr (FENCE) {
+    kfs.fence = NlpFenceSet{fence->edges + (size_t)r * fence->n_edge * 4, fwork + (size_t)b * fence->n_edge * N, fence->n_edge};
+    if (!bad) {
+      NlpFenceProb fp;                       // (nlp_fence_bad<false> reads its fence alone)
+      fp.fence = kfs.fence;
+      for (int a = 0; a < n_ac; ++a) {
+        const size_t ba = (size_t)r * n_ac + a;
+        const NlpScen sa = nlp_load_scen(scen + ba * D2D_SCEN_STRIDE, o, o.bounds ? o.bounds + ba * 4 : nullptr);
+        bad = bad || nlp_fence_bad<false>(sa, fp, W + ba * NLP_NV * N, N, lane);
+      }
+    }
+    __syncthreads();                         // (every wavefront has read every aircraft's start before the first solve writes one)
+  }
   if (bad) {                                 // (uniform over the workgroup: before the first barrier)
     nlp_groups_refuse(b, r, wave, lane, cost_out, feas_out, iters_out, status_out, sweeps_out, moved_out);
     return;
@@ -2450,7 +2652,8 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
   const double *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
   NlpExtra ex{{nullptr, nullptr, nullptr}, wf, t0, 0u, msp, vsp};      // sweep 0: no partner
   if constexpr (KMOV) ex.keep = &kms;
-  nlp_solve_one<false, WIND, PAIRS, MOV, VIA, false, KMOV, KMOV>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
+  if constexpr (FENCE) ex.keep = &kfs;
+  nlp_solve_one<false, WIND, PAIRS, MOV, VIA, false, KMOV, KMOV, FENCE>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
   ex.pmask = pmask;
   iters_total += out.iters;
   if (threadIdx.x < (PAIRS ? 8 : 2)) moved_s[threadIdx.x] = 0.0;
@@ -2468,7 +2671,7 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
           // fixed pair: the partner's x and y planes; PAIRS: the scenario's W and the set
           const double *pw = PAIRS ? Wr : W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;
           for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
-          nlp_solve_one<false, WIND, PAIRS, MOV, VIA, false, KMOV, KMOV>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
+          nlp_solve_one<false, WIND, PAIRS, MOV, VIA, false, KMOV, KMOV, FENCE>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
           iters_total += out.iters;
           double m = 0.0;
           for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
@@ -2550,6 +2753,18 @@ nlp_groups_keepout_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int 
                           const double *__restrict__ ctr, double *kwork) {
   nlp_groups_body<WIND, true, false, false, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out,
                                                   status_out, sweeps_out, moved_out, &wf, t_start, &mv, ctr, nullptr, nullptr, kwork);
+}
+
+// d2d_nlp_solve_groups_fence: the pairs of the masks, every aircraft inside the scenario's convex polygon; WIND as above
+template <bool WIND>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NLP_GROUPS_WIND_WAVES_PER_SIMD, NLP_GROUPS_WIND_WAVES_PER_SIMD)))
+nlp_groups_fence_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_sweeps, double tol, const double *__restrict__ scen, double *W,
+                        double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
+                        int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
+                        double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start, d2d_fence fence, double *fwork) {
+  nlp_groups_body<WIND, true, false, false, false, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out,
+                                                         status_out, sweeps_out, moved_out, &wf, t_start, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                         &fence, fwork);
 }
 
 // d2d_nlp_solve_groups_via: the pairs of the masks around the scenarios' moving discs, through every aircraft's own pins; WIND as above
@@ -2859,6 +3074,27 @@ int d2d_nlp_solve_keepout(d2d_ctx *ctx, int B, int N, double h, const double *sc
   });
 }
 
+int d2d_nlp_solve_fence(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
+                        double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
+                        const double *t_start, const d2d_keep_out *keep, double *kwork, const d2d_fence *fence, double *fwork) {
+  D2D_REQUIRE(fence, "d2d_nlp_solve_fence: null fence (n_edge = 0: no edges)");
+  D2D_REQUIRE(fence->n_edge >= 0 && fence->n_edge <= D2D_MAX_FENCE, "d2d_nlp_solve_fence: n_edge = %d outside 0 .. %d", fence->n_edge, D2D_MAX_FENCE);
+  if (fence->n_edge == 0)                                  // no edges: the solve of d2d_nlp_solve_keepout, its kernels and its checks
+    return d2d_nlp_solve_keepout(ctx, B, N, h, scen, opts, W, work, mult, cost, feas, iters, status, f, t_start, keep, kwork);
+  D2D_REQUIRE(fence->edges && fwork, "d2d_nlp_solve_fence: null edges or fwork with n_edge = %d", fence->n_edge);
+  D2D_REQUIRE(keep, "d2d_nlp_solve_fence: null keep-out table (n_keep = 0: no discs)");
+  D2D_REQUIRE(keep->n_keep >= 0 && keep->n_keep <= D2D_MAX_KEEP, "d2d_nlp_solve_fence: n_keep = %d outside 0 .. %d", keep->n_keep, D2D_MAX_KEEP);
+  D2D_REQUIRE(keep->n_keep == 0 || (keep->discs && kwork), "d2d_nlp_solve_fence: null discs or kwork with n_keep = %d", keep->n_keep);
+  if (int rc = nlp_single_check(ctx, B, N, h, scen, W, work, cost, feas, "d2d_nlp_solve_fence")) return rc;
+  if (int rc = nlp_field_check(f, t_start, nullptr, "d2d_nlp_solve_fence")) return rc;
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_fence", &o)) return rc;
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_handout_launch(nlp_solve_fence_kernel<decltype(wind)::value>, ctx, B, N, h, o, scen, W, work, mult, cost, feas, iters, status, wf,
+                              t_start, *keep, kwork, *fence, fwork);
+  });
+}
+
 int d2d_nlp_solve_keepout_moving(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W, double *work,
                                  double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, const d2d_wind_field *f,
                                  const double *t_start, const d2d_moving_obstacles *mov, double *mov_work, double *kwork) {
@@ -2889,6 +3125,27 @@ int d2d_nlp_solve_groups_keepout(d2d_ctx *ctx, int R, int n_ac, int N, double h,
     return nlp_groups_launch(nlp_groups_keepout_kernel<decltype(wind)::value>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
                              nlp_groups_prev(work, R, n_ac, N), cost, feas, iters, status, sweeps, moved, wf, t_start, *mov,
                              (const double *)mov_work, kwork);
+  });
+}
+
+int d2d_nlp_solve_groups_fence(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,
+                               double tol, double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters,
+                               int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *f, const double *t_start,
+                               const d2d_fence *fence, double *fwork) {
+  D2D_REQUIRE(fence, "d2d_nlp_solve_groups_fence: null fence (n_edge = 0: no edges)");
+  D2D_REQUIRE(fence->n_edge >= 0 && fence->n_edge <= D2D_MAX_FENCE, "d2d_nlp_solve_groups_fence: n_edge = %d outside 0 .. %d", fence->n_edge,
+              D2D_MAX_FENCE);
+  if (fence->n_edge == 0)                                  // no edges: the solve of d2d_nlp_solve_groups_pairs
+    return d2d_nlp_solve_groups_pairs(ctx, R, n_ac, N, h, scen, opts, max_sweeps, tol, W, work, mult, cost, feas, iters, status, sweeps, moved, f,
+                                      t_start);
+  D2D_REQUIRE(fence->edges && fwork, "d2d_nlp_solve_groups_fence: null edges or fwork with n_edge = %d", fence->n_edge);
+  if (int rc = nlp_groups_check(ctx, R, n_ac, N, h, scen, max_sweeps, tol, W, work, cost, feas, "d2d_nlp_solve_groups_fence")) return rc;
+  if (int rc = nlp_field_check(f, t_start, nullptr, "d2d_nlp_solve_groups_fence")) return rc;
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, "d2d_nlp_solve_groups_fence", &o)) return rc;
+  return nlp_with_field(f, [&](auto wind, const d2d_wind_field &wf) {
+    return nlp_groups_launch(nlp_groups_fence_kernel<decltype(wind)::value>, ctx, R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult,
+                             nlp_groups_prev(work, R, n_ac, N), cost, feas, iters, status, sweeps, moved, wf, t_start, *fence, fwork);
   });
 }
 

@@ -463,6 +463,99 @@ def moving_keep_clearance(keep_out, t, x, y):
     return out
 
 
+class GeoFence:
+    """A HARD geofence of the collocation planner (include/d2d.h d2d_fence): every point of the plan's polyline stays inside the strictly
+    convex polygon `vertices` (3 to 8 of them, either orientation), at least `margin` from every edge.  Scenarios carry one in `fence`.
+    The solver holds b_k - a_k . p_i > 0 at the nodes, with a_k edge k's outward unit normal; the half-planes' intersection is convex, so
+    the segment between two nodes that hold them holds them too -- unlike a KeepOut, nothing is inflated for the chords."""
+
+    MAX_VERTICES = 8                        # include/d2d.h D2D_MAX_FENCE
+
+    def __init__(self, vertices, margin=0.0):
+        v = np.array(vertices, dtype=np.float64)
+        if v.ndim != 2 or v.shape[1] != 2 or not 3 <= len(v) <= self.MAX_VERTICES or not np.isfinite(v).all():
+            raise ValueError(f'GeoFence: 3 to {self.MAX_VERTICES} finite vertices (x, y) are required, got an array of shape {v.shape}')
+        n = len(v)
+        e = np.roll(v, -1, axis=0) - v                                   # edge k: vertex k -> vertex k + 1
+        ln = np.hypot(e[:, 0], e[:, 1])
+        for k in range(n):
+            if not ln[k] > 0.0:
+                raise ValueError(f'GeoFence: vertex {(k + 1) % n} repeats vertex {k}')
+        ein = np.roll(e, 1, axis=0); lin = np.roll(ln, 1)                # the edge that ARRIVES at vertex k
+        cr = ein[:, 0] * e[:, 1] - ein[:, 1] * e[:, 0]                   # the turn at vertex k
+        for k in range(n):
+            if abs(cr[k]) <= 1e-12 * lin[k] * ln[k]:
+                raise ValueError(f'GeoFence: vertex {k} is collinear with its neighbours')
+        sg = 1.0 if float(np.sum(v[:, 0] * np.roll(v[:, 1], -1) - np.roll(v[:, 0], -1) * v[:, 1])) > 0.0 else -1.0     # +1: counter-clockwise
+        for k in range(n):
+            if cr[k] * sg < 0.0:
+                raise ValueError(f'GeoFence: the polygon is not convex at vertex {k}')
+        turn = float(np.sum(np.arctan2(cr, np.sum(ein * e, 1))))          # a simple polygon turns once round
+        if abs(abs(turn) - 2.0 * np.pi) > 1e-6:
+            raise ValueError('GeoFence: the polygon crosses itself (vertex 0 is passed more than once round)')
+        self.vertices = v
+        self.margin = float(margin)
+        if not np.isfinite(self.margin) or not self.margin >= 0.0:
+            raise ValueError(f'GeoFence: margin >= 0 is required, got {self.margin}')
+        self.a = sg * np.stack([e[:, 1], -e[:, 0]], 1) / ln[:, None]     # outward unit normals
+        self.b = np.sum(self.a * v, 1)
+        shrunk = self._clip(v if sg > 0 else v[::-1], self.a, self.b - self.margin)
+        if len(shrunk) < 3:
+            raise ValueError(f'GeoFence: margin = {self.margin} leaves nothing of the polygon')
+        # kap_k, where the start rule puts a node that is closer to edge k: 1e-2 of the shrunk polygon's width along a_k
+        self.kap = 1e-2 * np.array([float(np.max(self.b[k] - self.margin - shrunk @ self.a[k])) for k in range(n)])
+        if not (self.kap > 0.0).all():
+            raise ValueError(f'GeoFence: margin = {self.margin} leaves nothing of the polygon')
+
+    @staticmethod
+    def _clip(poly, a, b):
+        """The counter-clockwise polygon `poly` cut by every half-plane a_k . p <= b_k (Sutherland-Hodgman)."""
+        for ak, bk in zip(a, b):
+            out = []
+            for j in range(len(poly)):
+                p, q = poly[j], poly[(j + 1) % len(poly)]
+                gp, gq = bk - float(ak @ p), bk - float(ak @ q)
+                if gp >= 0.0:
+                    out.append(p)
+                if (gp > 0.0 and gq < 0.0) or (gp < 0.0 and gq > 0.0):
+                    out.append(p + (q - p) * (gp / (gp - gq)))
+            poly = np.array(out).reshape(-1, 2)
+            if len(poly) < 3:
+                break
+        return poly
+
+    def lowered(self):
+        """The rows (n, 4) = (ax, ay, b - margin, kap) of d2d_fence for one problem."""
+        return np.column_stack([self.a, self.b - self.margin, self.kap])
+
+    def __repr__(self):
+        return f'GeoFence({len(self.vertices)} vertices, margin={self.margin})'
+
+
+def lower_fence(fence):
+    """The rows (n, 4) of d2d_fence for one problem from a GeoFence (or rows already lowered: checked for their shape and passed on)."""
+    if isinstance(fence, GeoFence):
+        return fence.lowered()
+    rows = np.array(fence, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 4 or len(rows) > GeoFence.MAX_VERTICES:
+        raise ValueError(f'fence: a GeoFence or rows (n <= {GeoFence.MAX_VERTICES}, 4) = (ax, ay, b, kap) are required, got shape {rows.shape}')
+    return rows
+
+
+def fence_clearance(fence, x, y):
+    """Per edge: the smallest b_k - a_k . p over the plan's nodes (x_i, y_i).  With a GeoFence that is the distance from the USER's polygon
+    (margin not taken off): every plan the solver returns has it >= margin, and by convexity so has every point of the polyline between
+    the nodes.  With lowered rows (n, 4) -- what plan_batch also takes -- it is the distance from the rows' own half-planes, whose margin
+    is already taken off: >= 0 for every returned plan; absent rows (ax = ay = 0) give +inf."""
+    p = np.stack([np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)], -1)
+    if isinstance(fence, GeoFence):
+        a, b = fence.a, fence.b
+    else:
+        rows = lower_fence(fence)
+        a, b = rows[:, :2], np.where((rows[:, 0] != 0.0) | (rows[:, 1] != 0.0), rows[:, 2], np.inf)
+    return [float(np.min(b[k] - p @ a[k])) for k in range(len(a))]
+
+
 class Waypoint:
     """A timed waypoint of the collocation planner (include/d2d.h d2d_via_points): at time t -- absolute, on the clock of the scenario's
     t0 -- the given ones of x, y, psi hold exactly; None leaves a component free.  The time must be that of an interior node of the

@@ -19,6 +19,7 @@ MAX_OBS = 16
 MAX_MOV, MOV_MAX_KNOT = 8, 32          # include/d2d.h D2D_MAX_MOV / D2D_MOV_MAX_KNOT (tests compare)
 MAX_VIA = 16                           # include/d2d.h D2D_MAX_VIA
 MAX_KEEP = 8                           # include/d2d.h D2D_MAX_KEEP
+MAX_FENCE = 8                          # include/d2d.h D2D_MAX_FENCE
 (SC_X0, SC_Y0, SC_PSI0, SC_X1, SC_Y1, SC_PSI1, SC_VREF, SC_VSP, SC_KV, SC_KPHI, SC_KOBS, SC_S,
  SC_WWP, SC_WX, SC_WY, SC_GOLEFT, SC_O0X, SC_O0Y, SC_O0R, SC_O1X, SC_O1Y, SC_O1R, SC_WBND,
  SC_PHIMAX, SC_VMIN, SC_VMAX, SC_KCOL, SC_RCOL, SC_SCOL, SC_PMASK, SC_OKIND, SC_BANKMAX, SC_OEXT) = range(33)
@@ -96,6 +97,11 @@ class ViaPointsC(C.Structure):
 class KeepOutC(C.Structure):
     """d2d_keep_out (include/d2d.h): discs dev [B][n_keep][3] = (cx, cy, R), a row with R <= 0 absent."""
     _fields_ = [('n_keep', C.c_int32), ('pad', C.c_int32), ('discs', C.c_void_p)]
+
+
+class FenceC(C.Structure):
+    """d2d_fence (include/d2d.h): edges dev [B][n_edge][4] = (ax, ay, b, kap), a row with ax = ay = 0 absent."""
+    _fields_ = [('n_edge', C.c_int32), ('pad', C.c_int32), ('edges', C.c_void_p)]
 
 
 class AuditParams(C.Structure):
@@ -257,6 +263,10 @@ _SIGS = {
                                     + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P]),
     'd2d_nlp_solve_keepout': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
                               + [C.POINTER(WindFieldC), _P, C.POINTER(KeepOutC), _P]),
+    'd2d_nlp_solve_fence': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
+                            + [C.POINTER(WindFieldC), _P, C.POINTER(KeepOutC), _P, C.POINTER(FenceC), _P]),
+    'd2d_nlp_solve_groups_fence': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
+                                   + [C.POINTER(WindFieldC), _P, C.POINTER(FenceC), _P]),
     'd2d_nlp_solve_keepout_moving': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
                                      + [C.POINTER(WindFieldC), _P, C.POINTER(MovingObstaclesC), _P, _P]),
     'd2d_nlp_solve_groups_keepout': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
@@ -670,7 +680,7 @@ class Context:
 
     def _nlp_core(self, entry, scen, W, h, opts, bounds, n_ac=None, sweeps=None, want_mult=False, slots=0, order=None, mid=(),
                   field=_ABSENT, t_start=None, t_scalar=False, moving=_ABSENT, via=_ABSENT, free_rows=None, keep=_ABSENT,
-                  hard_moving=False):
+                  hard_moving=False, fence=_ABSENT):
         """What the nlp_solve* methods share: the shape checks, the workspace and the outputs, d2d_nlp_opts from opts = (rho0, mub0,
         mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), the call of `entry` and the result.  n_ac: a group entry (sweeps =
         (max_sweeps, tol)), R = B / n_ac scenarios with one start time and one set of tracks each; else B problems.  mid: arguments
@@ -679,7 +689,9 @@ class Context:
         free_rows: the entry is d2d_nlp_solve_free -- the rows go in front of W, the solved steps `h` [B] behind status, and the
         workspace is the larger one.  keep: the entry is d2d_nlp_solve_keepout -- discs dev [B][n_keep][3] or None (no discs) behind the
         field; the result carries keep_mult [B][n_keep][N], the discs' duals.  hard_moving: the moving discs are HARD (d2d_nlp_solve_keepout_moving,
-        d2d_nlp_solve_groups_keepout): kwork follows mov_work, and the result carries keep_mult [B][n_mov][N]."""
+        d2d_nlp_solve_groups_keepout): kwork follows mov_work, and the result carries keep_mult [B][n_mov][N].  fence: the entry is
+        d2d_nlp_solve_fence -- edges dev [B][n_edge][4] or None (no edges) behind keep -- or, with n_ac, d2d_nlp_solve_groups_fence -- edges
+        dev [R][n_edge][4], one polygon per scenario, behind the field; the result carries fence_mult [B][n_edge][N]."""
         torch = _torch()
         B, _, N = W.shape
         groups = n_ac is not None
@@ -731,6 +743,11 @@ class Context:
             k = KeepOutC(0 if keep is None else int(keep.shape[1]), 0, None if keep is None else keep.data_ptr())
             out['keep_mult'] = self.zeros(B, k.n_keep, N) if k.n_keep > 0 else None
             args += [C.byref(k), _ptr(out['keep_mult'])]
+        if fence is not _ABSENT:
+            assert fence is None or (fence.is_contiguous() and fence.dtype == torch.float64 and fence.dim() == 3 and fence.shape[0] == G and fence.shape[2] == 4)
+            fc = FenceC(0 if fence is None else int(fence.shape[1]), 0, None if fence is None else fence.data_ptr())
+            out['fence_mult'] = self.zeros(B, fc.n_edge, N) if fc.n_edge > 0 else None
+            args += [C.byref(fc), _ptr(out['fence_mult'])]
         _check(entry(*args))
         if want_mult:
             out['mult'] = mult
@@ -885,6 +902,37 @@ class Context:
             t_start = 0.0
         return self._nlp_core(self.lib.d2d_nlp_solve_keepout, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
                               want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, keep=discs)
+
+    def nlp_solve_fence(self, scen, W, h, edges, discs=None, field=None, t_start=None, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9,
+                        opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0, bounds=None, slots=0,
+                        order=None):
+        """nlp_solve_keepout INSIDE a convex polygon (d2d_nlp_solve_fence): edges dev [B][n_edge][4] = (ax, ay, b, kap) per problem, a the
+        outward unit normal (ax = ay = 0: absent; None: no edges; d2d.opty_utils.GeoFence.lowered() gives the rows), every interior node
+        held at b - a . p > 0 by the solver's barrier; discs as nlp_solve_keepout's (None: none), held in the same solve.  Refused on the
+        device (status ST_NONFINITE, cost = feas = NaN, W untouched): a non-finite edge, a normal off unit length, kap <= 0, an end pose
+        on or outside an edge, no start inside the edges and outside the discs -- and nlp_solve_keepout's causes.  The feasible set is
+        convex: the polyline between the returned nodes stays inside.  Returns nlp_solve_keepout's dict plus fence_mult [B][n_edge][N]:
+        the multipliers of the edge constraints."""
+        if field is None:
+            t_start = None
+        elif t_start is None:
+            t_start = 0.0
+        return self._nlp_core(self.lib.d2d_nlp_solve_fence, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
+                              want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, keep=discs, fence=edges)
+
+    def nlp_solve_groups_fence(self, scen, W, h, n_ac, edges, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0, mub0=0.1, mub_min=1e-9,
+                               feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0, bounds=None, want_mult=False):
+        """nlp_solve_groups_pairs with every aircraft inside its scenario's convex polygon (d2d_nlp_solve_groups_fence): edges dev
+        [R][n_edge][4] per SCENARIO, read as nlp_solve_fence reads them (None: no edges, nlp_solve_groups_pairs).  No hard discs.  A
+        scenario with an unusable edge, or with an aircraft whose end pose lies on or outside an edge or that cannot be started inside,
+        is refused like one with a malformed mask.  Returns nlp_solve_groups_pairs's dict plus fence_mult [R*n_ac][n_edge][N]: every
+        aircraft's multipliers."""
+        if field is None:
+            t_start = None
+        elif t_start is None:
+            t_start = 0.0
+        return self._nlp_core(self.lib.d2d_nlp_solve_groups_fence, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial),
+                              bounds, n_ac=n_ac, sweeps=(max_sweeps, tol), want_mult=want_mult, field=field, t_start=t_start, fence=edges)
 
     def nlp_solve_keepout_moving(self, scen, W, h, knots=None, disc=None, field=None, t_start=None, rho0=10.0, mub0=0.1, mub_min=1e-9,
                                  feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, serial=0,

@@ -2,7 +2,7 @@
 
 
 def nlp_plan(ctx, scen, W, h, *, n_ac=None, field=None, t_start=None, knots=None, disc=None, via=None, free_rows=None, pairs=False, keep=None,
-             hard_knots=None, hard_disc=None, **opts):
+             hard_knots=None, hard_disc=None, fence=None, **opts):
     """The planners' one rule for choosing among the nlp_solve* methods of `ctx` (a Context, or any object that has them) -- the first
     optional input that is given names the entry, which also takes the inputs below it in its column (free_rows: none):
       n_ac given, R scenarios of n_ac aircraft:  via -> _groups_via, knots -> _groups_moving, pairs -> _groups_pairs, field -> _groups_wind,
@@ -12,9 +12,28 @@ def nlp_plan(ctx, scen, W, h, *, n_ac=None, field=None, t_start=None, knots=None
     hard_knots / hard_disc given (HARD discs that move: the tables of nlp_solve_moving with disc[.., 0] the node radius): n_ac None ->
     nlp_solve_keepout_moving, n_ac given -> nlp_solve_groups_keepout, with field and t_start; refused by name together with keep, knots /
     disc, via or free_rows.
+    fence given (the rows of d2d.opty_utils.GeoFence.lowered()): n_ac None -> nlp_solve_fence (dev [B][n_edge][4]) with keep (its static
+    hard discs), n_ac given -> nlp_solve_groups_fence (dev [R][n_edge][4], one polygon per scenario; keep refused by name), with field and
+    t_start; refused by name together with free_rows, via, knots / disc or hard_knots / hard_disc.
     opts: the entry's own keywords (solver options, bounds, max_sweeps ...).  Returns the entry's dictionary plus `entry`, its name.
     (nlp_solve_model is not chosen here: its objective model is another problem, not an optional input of a plan -- DESIGN.md 5.16.)"""
     wind = dict(field=field, t_start=t_start)
+    if fence is not None:
+        for name, given in (('free_rows', free_rows is not None), ('via', via is not None), ('knots', knots is not None),
+                            ('disc', disc is not None), ('hard_knots', hard_knots is not None), ('hard_disc', hard_disc is not None)):
+            if given:
+                raise NotImplementedError(f'fence together with {name}: a geofence goes with static hard discs (one aircraft) and a fixed step, '
+                                          'not with moving discs, pins or a free step')
+        if n_ac is not None:
+            if keep is not None:
+                raise NotImplementedError('fence together with keep and n_ac: the group entry carries no hard discs; plan one aircraft at a '
+                                          'time (nlp_solve_fence)')
+            out = ctx.nlp_solve_groups_fence(scen, W, h, n_ac, fence, **wind, **opts)
+            out['entry'] = 'nlp_solve_groups_fence'
+            return out
+        out = ctx.nlp_solve_fence(scen, W, h, fence, discs=keep, **wind, **opts)
+        out['entry'] = 'nlp_solve_fence'
+        return out
     if hard_knots is not None or hard_disc is not None:
         for name, given in (('keep', keep is not None), ('knots', knots is not None), ('disc', disc is not None), ('via', via is not None),
                             ('free_rows', free_rows is not None)):

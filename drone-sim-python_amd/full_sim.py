@@ -457,7 +457,7 @@ def deconflict_plans(ctx, scen, W, h, n_ac, world=None, prio=None, row0=None, *,
 
 
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, deconflict=None, hard_moving=None, **solve_kw):
+               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, deconflict=None, hard_moving=None, fence=None, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -491,6 +491,12 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     scenario's largest VMAX and h (d2d_nlp_solve_groups_keepout; d2d_nlp_solve_keepout_moving when n_ac = 1; with and without a field);
     the result carries keep_mult (device [B][n][K]) and hard_knots, hard_disc (the lowered device tables).  Not combined with moving,
     via, free_time, keep_out or deconflict: raised by name.
+    fence (backend='nlp', any n_ac): a hard geofence -- one d2d.opty_utils.GeoFence for all scenarios, one per scenario (a list of
+    B / n_ac), or the lowered rows, an array (B / n_ac, n, 4) of (ax, ay, b, kap) -- that every aircraft's plan stays inside, its polyline
+    included (n_ac = 1: d2d_nlp_solve_fence, with and without keep_out's static hard discs in the same solve; n_ac > 1:
+    d2d_nlp_solve_groups_fence, which carries no hard discs; both with and without a field); the result carries fence_mult (device
+    [B][n][K]) and fence (the lowered table, a host array).  Not combined with moving, via, free_time, hard_moving or deconflict, nor
+    with keep_out when n_ac > 1: raised by name.
     deconflict (backend='nlp'): None -- today's call, bit for bit -- or a dict of deconflict_plans' keywords (d_sep, margin, d_look
     required; world, prio, n_knot, n_mov, max_rounds, step_max, kind, hard): after the solve the formations (the scenarios) that share a
     world give way to each other by priority (deconflict_plans, which re-solves with this call's solve_kw, in the field and from the
@@ -524,6 +530,14 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
             if given:
                 raise NotImplementedError(f'keep_out with {name} is not supported: hard discs are held for one aircraft on static discs, '
                                           'without pins, with a fixed step')
+    if fence is not None:
+        if backend != 'nlp':
+            raise NotImplementedError("the polynomial fit has no geofence: plan_batch(backend='nlp', fence=...) holds one")
+        for name, given in (('moving', bool(moving)), ('via', via is not None), ('free_time', free_time is not None),
+                            ('hard_moving', hard_moving is not None), ('deconflict', deconflict is not None)):    # (keep_out with n_ac > 1: above)
+            if given:
+                raise NotImplementedError(f'fence with {name} is not supported: a geofence is held with static hard discs for one aircraft, '
+                                          'without them for several, without moving discs or pins, with a fixed step')
     if hard_moving is not None:
         if backend != 'nlp':
             raise NotImplementedError("the polynomial fit has no hard moving discs: plan_batch(backend='nlp', hard_moving=...) holds them")
@@ -567,6 +581,49 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
         else:
             W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
         assert W.shape == (dsc.shape[0], 5, K)
+        if fence is not None:
+            import d2d.opty_utils as d2ou
+            B = dsc.shape[0]
+            G = B // n_ac
+            rows = np.asarray(scen_rows, dtype=np.float64)
+            if isinstance(fence, d2ou.GeoFence):
+                ftab = np.stack([fence.lowered()] * G)
+            elif isinstance(fence, (list, tuple)) and len(fence) and isinstance(fence[0], d2ou.GeoFence):
+                if len(fence) != G or len({len(f.a) for f in fence}) != 1:
+                    raise ValueError(f'fence: one GeoFence for all scenarios or one per scenario ({G}) with the same number of edges')
+                ftab = np.stack([f.lowered() for f in fence])
+            else:
+                ftab = np.ascontiguousarray(fence, dtype=np.float64)
+                if ftab.ndim != 3 or ftab.shape[0] != G or ftab.shape[2] != 4:
+                    raise ValueError(f'fence: a GeoFence, a list of them or an array ({G}, n, 4) of (ax, ay, b, kap) is required, got shape {ftab.shape}')
+            if n_ac > 1:
+                dsc_f = dsc
+                if not _rows_select_pairs(scen_rows, n_ac):     # the reference's pair (0, 1) as the partner sets the group entry reads
+                    dsc_f = dsc.clone()
+                    d2mou.default_pair_masks(dsc_f, n_ac, (dsc_f[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc_f[1::n_ac, d2dhip.SC_KCOL] > 0))
+                out = d2dhip.nlp_plan(ctx, dsc_f, W, h, n_ac=n_ac, fence=ctx.dev(ftab), field=fld, t_start=t_start if fld is not None else None,
+                                      **solve_kw)
+                out.update(fence=ftab, W=W, scen=dsc)
+                if guess_status is not None:
+                    out['guess_status'] = guess_status
+                return out
+            keep = None
+            if keep_out is not None:
+                if len(keep_out) and hasattr(keep_out[0], 'lowered'):
+                    keep = np.stack([d2ou.lower_keep_out(keep_out, rows[b, d2dhip.SC_VMAX], h) for b in range(B)])
+                else:
+                    keep = np.ascontiguousarray(keep_out, dtype=np.float64)
+                    if keep.ndim != 3 or keep.shape[0] != B or keep.shape[2] != 3:
+                        raise ValueError(f'keep_out: an array (B, n, 3) of (cx, cy, R) or a list of KeepOut is required, got shape {keep.shape}')
+            out = d2dhip.nlp_plan(ctx, dsc, W, h, fence=ctx.dev(ftab), keep=None if keep is None else ctx.dev(keep), field=fld,
+                                  t_start=t_start if fld is not None else None, **solve_kw)
+            out['fence'] = ftab
+            if keep is not None:
+                out['keep'] = keep
+            out.update(W=W, scen=dsc)
+            if guess_status is not None:
+                out['guess_status'] = guess_status
+            return out
         if keep_out is not None:
             B = dsc.shape[0]
             if len(keep_out) and hasattr(keep_out[0], 'lowered'):
@@ -692,6 +749,9 @@ def full_sim_phases_batch(c, r, v, n_ac, X1_f, scen, X2_f, t_opt, ref3=None, t_s
     import multi_opt_planner as mop
     if audit is not None and ('X' not in record2 or (ref3 is not None and 'X' not in record3)):
         raise ValueError("audit needs the flown histories: 'X' must be in record2 and record3")
+    if getattr(scen, 'fence', None) is not None:
+        raise NotImplementedError('the mission chain has no geofence (scen.fence): its transit is the multi-aircraft fit; plan one aircraft '
+                                  "with plan_batch(backend='nlp', fence=...) (d2d_nlp_solve_fence)")
     if getattr(scen, 'keep_out', None):
         raise NotImplementedError('the mission chain has no hard keep-out discs (scen.keep_out): its transit is the multi-aircraft fit; plan '
                                   'one aircraft with single_opt_planner.Planner (d2d_nlp_solve_keepout)')

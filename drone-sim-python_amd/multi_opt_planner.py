@@ -79,6 +79,8 @@ class Planner:
         self.moving_obstacles = sop.check_moving(scen, self.backend)
         self.waypoints = sop.check_waypoints(scen, self.backend, len(scen.p0s))       # one list per aircraft
         self._has_via = any(self.waypoints)
+        # an optional hard geofence (scen.fence): every aircraft inside it, through the group entry (d2d_nlp_solve_groups_fence)
+        self.fence = sop.check_fence(scen, self.backend, self.moving_obstacles, self._has_via)
         self.acs = d2mou.AircraftSet(n=len(scen.p0s))
         self.num_nodes, self.time_step, self.duration = d2ou.planner_timing(scen.t0, scen.t1, scen.hz)
         N, n = self.num_nodes, self.acs.nb_aicraft
@@ -96,7 +98,9 @@ class Planner:
             raise NotImplementedError(sop.MOVING_HOST_COST)
         if self._host_cost and self._has_via:
             raise NotImplementedError(sop.VIA_HOST_COST)
-        if initialize and (self.backend == 'nlp' or self._host_cost or self.moving_obstacles or self._has_via):
+        if self._host_cost and self.fence is not None:
+            raise NotImplementedError(sop.FENCE_HOST_COST)
+        if initialize and (self.backend == 'nlp' or self._host_cost or self.moving_obstacles or self._has_via or self.fence is not None):
             import itertools
             import opty.direct_collocation
 
@@ -118,7 +122,8 @@ class Planner:
                                                         lambda _free: obj.cost_grad(_free, self),
                                                         self.acs.get_eom(self.wind), self.acs._state_symbols, self.num_nodes,
                                                         self.time_step, known_parameter_map={},
-                                                        instance_constraints=self._instance_constraints, bounds=self._bounds, parallel=False)
+                                                        instance_constraints=self._instance_constraints, bounds=self._bounds, parallel=False,
+                                                        **(dict(fence=self.fence) if self.fence is not None else {}))
         elif initialize:
             self.prob = sop._FitProblem(self, n)
 
@@ -196,9 +201,9 @@ class Planner:
         self.prob.add_option('tol', tol)
         self.prob.addOption('max_iter', max_iter)
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self.backend == 'nlp' or self._host_cost or self.moving_obstacles or self._has_via:
+        if self.backend == 'nlp' or self._host_cost or self.moving_obstacles or self._has_via or self.fence is not None:
             self.fit_q = self.fit_plan = self.fit_scen = self.fit_coefs = None
-            if self._host_cost or self.moving_obstacles or self._has_via:
+            if self._host_cost or self.moving_obstacles or self._has_via or self.fence is not None:
                 self.info['backend_used'] = 'nlp'
         else:
             sop.Planner._harden(self)      # backend='auto': a plan that overshoots a bound is re-planned by the collocation backend

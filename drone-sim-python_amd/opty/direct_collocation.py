@@ -119,7 +119,7 @@ def _closure_objects(fn):
 
 class Problem:
     def __init__(self, obj, obj_grad, eom, state_symbols, num_nodes, time_step, known_parameter_map=None,
-                 instance_constraints=(), bounds=None, parallel=False, cost=None, planner=None, keep_out=None):
+                 instance_constraints=(), bounds=None, parallel=False, cost=None, planner=None, keep_out=None, fence=None):
         self.obj, self.obj_grad = obj, obj_grad
         # a symbol for the interval: variable duration (the interval is the last free entry); a number: the fixed step
         self.free_step = time_step if (hasattr(time_step, 'name') and not isinstance(time_step, (int, float, np.number))) else None
@@ -218,6 +218,19 @@ class Problem:
                 self.keep_knots, self.keep_disc = d2ou.lower_keep_moving(self.keep_out, self.bounds[0]['v'][1], self.time_step)
             else:
                 self.keep_rows = d2ou.lower_keep_out(self.keep_out, self.bounds[0]['v'][1], self.time_step)
+        # a hard geofence (d2d.opty_utils.GeoFence, or its lowered rows): every node inside the convex polygon (d2d_nlp_solve_fence; with
+        # several aircraft d2d_nlp_solve_groups_fence: one polygon for all of them)
+        self.fence = fence
+        if fence is not None:
+            what = ('moving obstacles' if self.moving else
+                    'instance_constraints at interior times (waypoints)' if self.via is not None else
+                    f'a variable duration (time_step = {self.free_step})' if self.free_step is not None else
+                    'the host objective (a cost plug-in without a kernel)' if self.objective == 'host' else
+                    'a MovingKeepOut in keep_out (hard discs that move)' if self.keep_out and self.keep_moving else None)
+            if what:
+                raise NotImplementedError(f'fence together with {what} is not supported')
+            import d2d.opty_utils as d2ou
+            self.fence_rows = d2ou.lower_fence(fence)
         if self.free_step is not None:                  # what a free interval is not combined with (d2d_nlp_solve_free)
             what = ('more than one aircraft (they share one interval: the joint system is not built)' if self.n_aircraft != 1 else
                     'moving obstacles (their node times move with the step)' if self.moving else
@@ -279,7 +292,8 @@ class Problem:
         what = ('a wind field that varies in space and time (the guess is built in the air frame of a constant wind)' if self.field is not None else
                 'moving obstacles' if self.moving else
                 "waypoints (the 'via' guess is the one that knows pins)" if self.via is not None else
-                'hard keep-out discs (the path would have to go round them)' if self.keep_out else None)
+                'hard keep-out discs (the path would have to go round them)' if self.keep_out else
+                'a geofence (the path would have to stay inside it)' if self.fence is not None else None)
         if what:
             raise NotImplementedError(f"the 'dubins' initial guess together with {what} is not supported")
         rows, bnd = (self._rows()[0], self._bounds_table()) if self.objective == 'lowered' else self._host_rows()
@@ -348,12 +362,14 @@ class Problem:
         # Everything else is ONE launch of a group entry: wavefront a of a workgroup solves aircraft a; the aircraft coupled by
         # CostCollision alternate on the device (block Gauss-Seidel) until none moves -- the pair (0, 1), or with a cost that selects
         # its own pairs every aircraft with a partner.
-        group = False if self.keep_out else multi if tabled else self.field is None
+        group = False if self.keep_out else n > 1 if self.fence is not None else multi if tabled else self.field is None
         ex = dict(field=self.field, t_start=self.t_start if (self.moving or self.field is not None) else None)
         if self.keep_out and self.keep_moving:
             ex.update(hard_knots=ctx.dev(self.keep_knots[None]), hard_disc=ctx.dev(self.keep_disc[None]), t_start=self.t_start)
         elif self.keep_out:
             ex['keep'] = ctx.dev(self.keep_rows[None])
+        if self.fence is not None:                # one polygon for the problem: every aircraft of the scenario holds it
+            ex['fence'] = ctx.dev(self.fence_rows[None])
         if self.moving:
             import d2d.opty_utils as d2ou
             knots, disc = d2ou.lower_moving(self.moving)
@@ -361,7 +377,7 @@ class Problem:
         if self.via is not None:
             ex['via'] = ctx.dev(self.via)
         if group:
-            if tabled and coupled and self._pairs is None:       # (these entries read the partner sets: the pair (0, 1) as such)
+            if (tabled or self.fence is not None) and coupled and self._pairs is None:       # (these entries read the partner sets: the pair (0, 1) as such)
                 import d2d.multiopty_utils as d2mou
                 d2mou.default_pair_masks(dsc, n, True)
             ex.update(n_ac=n, pairs=self._pairs is not None, max_sweeps=int(self.options.get('max_sweeps', 12)),
@@ -394,6 +410,10 @@ class Problem:
                 info['keep_out_clearance'] = d2ou.moving_keep_clearance(self.keep_out, self.t_start + np.arange(N) * self.time_step, Wh[0, 0], Wh[0, 1])
             else:
                 info['keep_out_clearance'] = d2ou.keep_out_clearance(self.keep_out, Wh[0, 0], Wh[0, 1])
+        if self.fence is not None:                # per edge: the nodes' distance from the user's polygon (>= its margin; by convexity the polyline's too)
+            import d2d.opty_utils as d2ou
+            fc = [d2ou.fence_clearance(self.fence, Wh[a, 0], Wh[a, 1]) for a in range(n)]
+            info['fence_clearance'] = fc if multi else fc[0]
         if self.via is not None:                  # 0.0 by construction: a pinned component never leaves its value
             import d2d.opty_utils as d2ou
             info['waypoint_error'] = max(d2ou.waypoint_error(self.via[a], Wh[a]) for a in range(n))

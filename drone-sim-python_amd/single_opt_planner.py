@@ -123,6 +123,29 @@ def check_keep_out(exp, backend, moving=(), waypoints=(), t1_free=None):
     return keep
 
 
+def check_fence(exp, backend, moving=(), waypoints=(), t1_free=None, keep=()):
+    """The scenario's hard geofence (exp.fence, a d2d.opty_utils.GeoFence; absent or None: none), refused where it cannot be planned:
+    backend='fit', or together with moving obstacles, waypoints, t1_free or a MovingKeepOut in keep_out."""
+    fence = getattr(exp, 'fence', None)
+    if fence is None:
+        return None
+    if backend == 'fit':
+        raise NotImplementedError("backend='fit' cannot hold a geofence (fence): the polynomial fit has soft rows only.  "
+                                  "backend='nlp' (or 'auto') solves the collocation problem with the edges as hard constraints")
+    import d2d.opty_utils as d2ou
+    for name, given in (('moving obstacles (moving_obstacles)', bool(moving)), ('waypoints', bool(waypoints)), ('a free duration (t1_free)', t1_free is not None),
+                        ('a MovingKeepOut in keep_out', any(isinstance(k, d2ou.MovingKeepOut) for k in keep))):
+        if given:
+            raise NotImplementedError(f'fence together with {name} is not supported: a geofence is planned with static hard discs, without '
+                                      'moving discs, without pins, with a fixed step (d2d_nlp_solve_fence)')
+    d2ou.lower_fence(fence)                       # (a GeoFence or its rows: anything else is refused here)
+    return fence
+
+
+FENCE_HOST_COST = ('fence together with a host objective (a cost plug-in without a kernel, d2d_nlp_solve_model) is not supported: '
+                   'use one of the cost classes of d2d.opty_utils')
+
+
 def lowerable(cost):
     """True if lower_cost knows the plug-in (the fit and the lowered collocation kernel can express it)."""
     try:
@@ -331,6 +354,8 @@ class Planner:
         self.t1_free = check_free_time(exp, self.backend)
         # optional hard keep-out discs (exp.keep_out): held by the collocation backend (d2d_nlp_solve_keepout), to which 'auto' goes straight
         self.keep_out = check_keep_out(exp, self.backend, self.moving_obstacles, self.waypoints, self.t1_free)
+        # an optional hard geofence (exp.fence): held by the collocation backend (d2d_nlp_solve_fence), to which 'auto' goes straight
+        self.fence = check_fence(exp, self.backend, self.moving_obstacles, self.waypoints, self.t1_free, self.keep_out)
         self.aircraft = d2ou.Aircraft()
         N = self.num_nodes
         self._slice_x, self._slice_y, self._slice_psi, self._slice_phi, self._slice_v = (
@@ -344,7 +369,9 @@ class Planner:
             raise NotImplementedError(VIA_HOST_COST)
         if self._host_cost and self.keep_out:
             raise NotImplementedError(KEEP_HOST_COST)
-        if initialize and (self.keep_out or self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints
+        if self._host_cost and self.fence is not None:
+            raise NotImplementedError(FENCE_HOST_COST)
+        if initialize and (self.keep_out or self.fence is not None or self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints
                            or self.t1_free is not None):
             import opty.direct_collocation
             _g = self.aircraft
@@ -368,7 +395,8 @@ class Planner:
                                                         _g.get_eom(self.wind), _g._state_symbols, self.num_nodes, step,
                                                         known_parameter_map={}, instance_constraints=self._instance_constraints,
                                                         bounds=self._bounds, parallel=False,
-                                                        **(dict(keep_out=self.keep_out) if self.keep_out else {}))
+                                                        **(dict(keep_out=self.keep_out) if self.keep_out else {}),
+                                                        **(dict(fence=self.fence) if self.fence is not None else {}))
         elif initialize:
             self.prob = _FitProblem(self, 1)
 
@@ -461,7 +489,7 @@ class Planner:
             self.time_step = float(self.solution[-1])
             self.duration = self.time_step * (self.num_nodes - 1)
             self.info['backend_used'] = 'nlp'
-        elif self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints or self.keep_out:
+        elif self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints or self.keep_out or self.fence is not None:
             self.info['backend_used'] = 'nlp'
         elif self.backend != 'nlp':
             self._harden()

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 126
+#define D2D_VERSION 127
 
 /* error codes */
 #define D2D_OK 0
@@ -1001,6 +1001,57 @@ int d2d_nlp_solve_groups_keepout(d2d_ctx *ctx, int R, int n_ac, int N, double h,
                                  int max_sweeps, double tol, double *W, double *work, double *mult, double *cost, double *feas,
                                  int32_t *iters, int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *field,
                                  const double *t_start, const d2d_moving_obstacles *mov, double *mov_work, double *kwork);
+
+/* d2d_nlp_solve_keepout INSIDE a convex polygon: a geofence.  For problem b, interior node i and edge k = (ax, ay, b, kap) of
+ * fence->edges [B][n_edge][4], a the edge's outward unit normal:   g_ik = b_k - (ax_k x_i + ay_k y_i) > 0,   a true inequality of the NLP held
+ * by the same primal-dual log barrier as the box and the discs (a dual z_ik > 0 per (node, edge), started at mub / g); a row with
+ * ax = ay = 0 is absent.  The constraint is linear, grad g = -a: the merit gains - mub log g (+inf when a g <= 0), the stationarity rows of
+ * (x_i, y_i) + z a, the right-hand side - (mub / g) a, the KKT error |z g - mub|, and the (x, y) corner of the node's diagonal block the
+ * full Hessian (z / g) a a^T -- positive semidefinite: the edges add no negative curvature.  With the step s of (x_i, y_i):
+ * dz = (mub + z a.s) / g - z, ratio test and clip to [mub / (1e10 g), 1e10 mub / g] as for the box duals, and the primal
+ * fraction-to-the-boundary rule is a <= tau g / (a.s) where a.s > 0, exact.  Every a.p is taken as fma(ax, x, ay y).
+ * Start, behind the discs' rule: two passes over the edges in index order, a free node with g_k < kap_k moves along -a_k to g_k = kap_k;
+ * then the box push again.  A guess with g >= kap at every edge (and outside 1.01 R of every disc) is not moved.
+ * Refused per problem before its first store (D2D_ST_NONFINITE, cost = feas = NaN, iters = 0, W untouched, the rest of the launch
+ * solved): a non-finite entry of an edge, a present edge with | |a| - 1 | > 1e-12 or kap <= 0, an end pose with g <= 0, a free node
+ * with g <= 0 at an edge or a disc after the start rules -- and what refuses d2d_nlp_solve_keepout.
+ * keep, kwork: the static hard discs of d2d_nlp_solve_keepout, held in the same solve (a permitted area with no-fly zones inside it is
+ * one call); keep must not be NULL, n_keep = 0: no discs (discs and kwork may be NULL).  The row's soft static discs still count; moving
+ * discs, pins and a free step are not carried.  cost is the reference's cost(): discs and edges add nothing.
+ * Guarantee: the feasible set of the edges is convex, so the straight segment between two feasible nodes is feasible -- the whole polyline
+ * of a returned plan keeps every g > 0 with no chord inflation (d2d.opty_utils.GeoFence lowers a polygon and a margin to the rows).
+ * fwork dev [B][n_edge][N]: the duals z, afterwards the multipliers of the edge constraints (0 at the end nodes and for absent edges).
+ * n_edge = 0: the call is d2d_nlp_solve_keepout (edges and fwork may be NULL), and with n_keep = 0 as well d2d_nlp_solve /
+ * d2d_nlp_solve_wind.  fence NULL, n_edge outside 0 .. D2D_MAX_FENCE, NULL edges or fwork with n_edge > 0: D2D_EINVAL before any launch.
+ * field, t_start, opts, W, work, mult, iters, status as d2d_nlp_solve_keepout.  tests/nlp_fence_ref.py is the CPU statement.
+ * Asynchronous on the context's stream.  (version 127) */
+#define D2D_MAX_FENCE 8
+typedef struct {
+  int32_t n_edge, pad;  /* 0 .. D2D_MAX_FENCE */
+  const double *edges;  /* dev [B][n_edge][4] = (ax, ay, b, kap) */
+} d2d_fence;
+int d2d_nlp_solve_fence(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_opts *opts, double *W,
+                        double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
+                        const d2d_wind_field *field, const double *t_start, const d2d_keep_out *keep, double *kwork,
+                        const d2d_fence *fence, double *fwork);
+
+/* d2d_nlp_solve_groups_pairs with every aircraft inside its scenario's convex polygon: the arguments of d2d_nlp_solve_groups_pairs, then
+ * fence with edges dev [R][n_edge][4], one polygon per SCENARIO read as above, then fwork dev [R n_ac][n_edge][N], every aircraft's own
+ * duals (afterwards the multipliers).  No hard discs are carried.  The block Gauss-Seidel is d2d_nlp_solve_groups_pairs's (masks in the
+ * rows, checked on the device); every aircraft holds the scenario's edges in the uncoupled sweep and in every turn.  The constraint is
+ * per aircraft, so a fixed point of the alternation is still a KKT point of the joint problem.  Each turn is a full solve from the
+ * aircraft's current nodes: the start rule moves nodes closer than kap to an edge back to g = kap and the duals restart at mub / g.
+ * A bad edge (the rules above) refuses the whole scenario exactly as a malformed mask does (D2D_ST_NONFINITE, cost = feas = NaN,
+ * sweeps = 0, W untouched), and so does an aircraft whose end pose has g <= 0 or whose guess the start rule cannot place inside --
+ * decided before the first barrier by every wavefront alike, on the aircraft's GUESSES.  A later turn that cannot start refuses that
+ * AIRCRAFT alone, as d2d_nlp_solve_groups_keepout describes.  By convexity every aircraft's polyline stays inside.  n_edge = 0: the
+ * call is d2d_nlp_solve_groups_pairs (edges, fwork may be NULL); with every edge absent its bytes.  fence NULL, n_edge outside
+ * 0 .. D2D_MAX_FENCE, NULL edges or fwork with n_edge > 0: D2D_EINVAL before any launch.  f NULL: the rows' constant wind (t_start is
+ * not read).  tests/nlp_fence_ref.py solve_groups is the CPU statement.  Asynchronous on the context's stream.  (version 127) */
+int d2d_nlp_solve_groups_fence(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts,
+                               int max_sweeps, double tol, double *W, double *work, double *mult, double *cost, double *feas,
+                               int32_t *iters, int32_t *status, int32_t *sweeps, double *moved, const d2d_wind_field *field,
+                               const double *t_start, const d2d_fence *fence, double *fwork);
 
 /* Timed waypoints of the collocation planner: components of x, y, psi of INTERIOR nodes held at given values -- a point to fly
  * through at a given time, a gate, a heading at a hand-over.  A pinned component is a fixed variable exactly as x, y, psi of the two end

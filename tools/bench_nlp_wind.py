@@ -37,6 +37,14 @@ python tools/bench_nlp_wind.py keepout-moving [B] hard keep-out discs that move 
     the leg at 3 m/s (at the static centre at mid-time; node radius MovingKeepOut.lowered) through d2d_nlp_solve_keepout_moving.  The
     three alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians, the spread of each, statuses, mean and
     longest step counts, the smallest g / R^2 of the converged plans, and whether the still track gives the static entry's bytes.
+python tools/bench_nlp_wind.py fence [B]   a hard geofence (d2d_nlp_solve_fence): the rows, the disc and the guess of `keepout`, once through
+    d2d_nlp_solve_keepout with the disc, once through d2d_nlp_solve_fence WITHOUT the disc inside a corridor round the leg (a
+    d2d.opty_utils.GeoFence per problem: the side towards which the problem's free plan -- an untimed d2d_nlp_solve first -- leaves its
+    leg's axis most lies at 0.8 of that excursion, the other three sides stand far off; beside the disc no edge can bind, a plan
+    touches the disc in one point and the start rule needs kap of room there) and once through d2d_nlp_solve_fence with the disc and
+    four ABSENT edges -- the price of the code path.  The three alternate, 1 warm-up + 5 timed launches each, HIP
+    events, one process; medians, the spread of each, statuses, mean and longest step counts, the smallest g of the converged plans at
+    the edges, and whether the absent edges give d2d_nlp_solve_keepout's bytes.
 python tools/bench_nlp_wind.py guess [B]   the start of the solve (d2d_nlp_guess_dubins): B (default 4096) perturbed exp_14 at 121 nodes through
     d2d_nlp_solve from the host dog-leg (d2d.opty_utils.triangle, copied to the device) and from the Dubins start built on the device
     from the same rows.  The two starts alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians and the spread
@@ -312,6 +320,64 @@ def keepout_leg(B):
     ctx.close()
 
 
+def fence_leg(B):
+    import torch, d2dhip
+    import d2dhip as D
+    from d2dhip import synth
+    from d2d.opty_utils import KeepOut, GeoFence
+    ctx = d2dhip.Context(0)
+    rows, W0, h = synth.nlp_problems(B)
+    N = W0.shape[2]
+    p0, p1 = rows[:, D.SC_X0:D.SC_X0 + 2], rows[:, D.SC_X1:D.SC_X1 + 2]
+    d = p1 - p0
+    ll = np.hypot(d[:, 0], d[:, 1])
+    d /= ll[:, None]
+    nrm = np.stack([-d[:, 1], d[:, 0]], 1)
+    c = 0.5 * (p0 + p1) + 3.0 * nrm
+    discs = np.array([[KeepOut(c[b], 15.0).lowered(rows[b, D.SC_VMAX], h)] for b in range(B)])
+    dsc, dk = ctx.dev(rows), ctx.dev(discs)
+    Wf = ctx.dev(np.ascontiguousarray(W0))
+    ctx.nlp_solve(dsc, Wf, h)                                # the free plans: where each leaves its leg's axis most
+    ctx.sync()
+    Wf = Wf.cpu().numpy()
+    lat = (Wf[:, 0] - p0[:, 0:1]) * nrm[:, 0:1] + (Wf[:, 1] - p0[:, 1:2]) * nrm[:, 1:2]
+    up = lat.max(1) >= -lat.min(1)
+    cut = np.maximum(0.8 * np.abs(lat).max(1), 0.05)         # (half of it is infeasible for these legs: 4095 of 4096 end STALLED)
+    left, right = np.where(up, cut, ll), np.where(up, ll, cut)
+    edges = np.stack([GeoFence([p0[b] - 0.5 * ll[b] * d[b] - right[b] * nrm[b], p1[b] + 0.5 * ll[b] * d[b] - right[b] * nrm[b],
+                                p1[b] + 0.5 * ll[b] * d[b] + left[b] * nrm[b], p0[b] - 0.5 * ll[b] * d[b] + left[b] * nrm[b]]).lowered() for b in range(B)])
+    de, dz = ctx.dev(edges), ctx.dev(np.zeros_like(edges))
+    names = ('keepout', 'fence', 'fence-absent')
+    times = {k: [] for k in names}
+    outs, Ws = {}, {}
+    for rep in range(6):                                     # the first launch of each is the warm-up; the entries alternate
+        for what in names:
+            W = ctx.dev(np.ascontiguousarray(W0))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            outs[what] = ctx.nlp_solve_keepout(dsc, W, h, dk) if what == 'keepout' else (ctx.nlp_solve_fence(dsc, W, h, de) if what == 'fence' else ctx.nlp_solve_fence(dsc, W, h, dz, discs=dk))
+            e1.record(); torch.cuda.synchronize()
+            times[what].append(e0.elapsed_time(e1) * 1e-3)
+            Ws[what] = W
+    med = {k: float(np.median(v[1:])) for k, v in times.items()}
+    same = bool(torch.equal(Ws['keepout'], Ws['fence-absent']) and torch.equal(outs['keepout']['iters'], outs['fence-absent']['iters'])
+                and torch.equal(outs['keepout']['keep_mult'], outs['fence-absent']['keep_mult']))
+    for what in names:
+        st = outs[what]['status'].cpu().numpy(); it = outs[what]['iters'].cpu().numpy()
+        Wh = Ws[what].cpu().numpy()
+        g = edges[:, :, 2, None] - (edges[:, :, 0, None] * Wh[:, None, 0, 1:-1] + edges[:, :, 1, None] * Wh[:, None, 1, 1:-1])
+        ok = st == 1
+        zf = outs['fence']['fence_mult'].cpu().numpy()
+        print(json.dumps({'leg': 'fence', 'B': B, 'nodes': N, 'entry': what, 'seconds_median': med[what], 'seconds_min': min(times[what][1:]),
+                          'seconds_max': max(times[what][1:]), 'problems_per_s': B / med[what], 'over_keepout': med[what] / med['keepout'],
+                          'status_counts': {int(k): int((st == k).sum()) for k in np.unique(st)}, 'mean_newton_steps': float(it.mean()),
+                          'max_newton_steps': int(it.max()), 'mean_newton_steps_converged': float(it[ok].mean()) if ok.any() else None,
+                          'min_g_at_the_edges_converged': float(g[ok].min()) if ok.any() else None,
+                          'plans_whose_edge_dual_exceeds_1e-3': int((zf[ok].max(axis=(1, 2)) > 1e-3).sum()) if what == 'fence' and ok.any() else None,
+                          'absent_edges_are_the_keepout_entry_bit_for_bit': same}), flush=True)
+    ctx.close()
+
+
 def keepout_moving_leg(B):
     import torch, d2dhip
     import d2dhip as D
@@ -428,6 +494,8 @@ def guess_leg(B):
 def main():
     if sys.argv[1:2] == ['guess']:
         return guess_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    if sys.argv[1:2] == ['fence']:
+        return fence_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['keepout-moving']:
         return keepout_moving_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['keepout']:
