@@ -104,6 +104,19 @@ class FenceC(C.Structure):
     _fields_ = [('n_edge', C.c_int32), ('pad', C.c_int32), ('edges', C.c_void_p)]
 
 
+class DispersionIn(C.Structure):
+    """d2d_dispersion_in (include/d2d.h): the gust's a, s, sigma and S_in, a device address [28][n] or None."""
+    _fields_ = [('a', C.c_double), ('s', C.c_double), ('sigma', C.c_double), ('S_in', C.c_void_p)]
+
+
+DISPERSION_OUT = ('Ppos_hist', 'S_out', 'sig_max', 'sig_row', 'fence_sn', 'fence_k', 'fence_row', 'disc_k', 'disc_row')
+
+
+class DispersionOut(C.Structure):
+    """d2d_dispersion_out (include/d2d.h): device addresses, any may be None."""
+    _fields_ = [(k, C.c_void_p) for k in DISPERSION_OUT]
+
+
 class AuditParams(C.Structure):
     """d2d_audit_params (include/d2d.h)."""
     _fields_ = [('n_form', C.c_int32), ('n_ac', C.c_int32), ('n_rows', C.c_int32), ('rows_per_block', C.c_int32), ('n_stat', C.c_int32),
@@ -313,6 +326,8 @@ _SIGS = {
                                    C.POINTER(TracksOut)]),
     'd2d_wind_fit_workspace': (C.c_int64, [C.POINTER(WindFitParams), C.POINTER(WindFieldC)]),
     'd2d_wind_fit': (C.c_int, [_P, C.POINTER(WindFitParams), _P, _P, _P, C.POINTER(WindFieldC), _P, _P, C.POINTER(WindFitOut)]),
+    'd2d_track_dispersion': (C.c_int, [_P, C.POINTER(TrackParams), _P, _P, C.POINTER(DispersionIn), C.POINTER(FenceC), C.POINTER(KeepOutC),
+                                       C.POINTER(DispersionOut)]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -1244,6 +1259,70 @@ class Context:
         else:
             _check(self.lib.d2d_sim_track_run_wind(*args, C.byref(f), float(t_start), _ptr(out['iter_max'])))
         return out
+
+    def _constraint_rows(self, rows, n, width, cap, what):
+        """A per-drone constraint table for track_dispersion -> a contiguous device tensor [n][k][width] or None.  rows: None, an
+        object with lowered() (d2d.opty_utils.GeoFence: the same rows for every drone), an array (k, width) shared by every drone, or
+        an array / device tensor [n][k][width]."""
+        torch = _torch()
+        if rows is None:
+            return None
+        if hasattr(rows, 'lowered'):
+            rows = rows.lowered()
+        if not hasattr(rows, 'data_ptr'):
+            rows = np.asarray(rows, dtype=np.float64)
+            if rows.ndim == 2:
+                rows = np.broadcast_to(rows[None], (n,) + rows.shape)
+            rows = self.dev(np.ascontiguousarray(rows))
+        if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != width or rows.dtype != torch.float64 or rows.device.type != 'cuda':
+            raise ValueError(f'{what}: rows [{n}][k][{width}] of float64 on the device are required, got {tuple(rows.shape)} {rows.dtype}')
+        if not 1 <= rows.shape[1] <= cap:
+            raise ValueError(f'{what}: 1 .. {cap} rows per drone, got {rows.shape[1]}')
+        return rows.contiguous()
+
+    def track_dispersion(self, x_ref, y_ref, w=(0.0, 0.0), gust=None, time=None, dt=None, fence=None, keep_out=None, S0=None, record_P=False,
+                         **kw):
+        """The gust dispersion of tracked plans (d2d_track_dispersion): the covariance of the deviation of track_run(gust=...) from the
+        gust-free flight of the same references, by one deterministic pass per plan.  x_ref, y_ref dev [T][n] as track_run takes them;
+        time (its first two entries give the step) or dt; w: the constant wind handed to the controller and the plant; gust: a
+        d2d.wind.GustModel (only sigma and tau enter: the prediction is per aircraft, see full_sim.dispersion_margin for pairs).
+        fence: a d2d.opty_utils.GeoFence, lowered rows (k, 4), or rows per drone [n][k][4]; keep_out: discs (k, 3) = (cx, cy, R) or
+        [n][k][3].  S0 dev [28][n]: the packed covariance to start from (S_out of an earlier call), None: no tracking error and the
+        stationary gust.  kw: track_params' controller constants (tau_phi, tau_v, Q, R, ...).
+        Returns a dict of device tensors: S [28][n], sig_max, sig_row [n], with record_P Ppos [T][3][n] (xx, xy, yy), with a fence
+        fence_sn, fence_k, fence_row [k][n], with discs disc_k, disc_row [k][n]."""
+        if not hasattr(gust, 'numbers'):
+            raise TypeError(f'{type(gust).__name__} is not a gust model: build one with d2d.wind.GustModel')
+        if (time is None) == (dt is None):
+            raise ValueError('give the time grid as time= or its step as dt=, not both')
+        torch = _torch()
+        if dt is None:
+            dt = float(time[1] - time[0])
+        T, n = x_ref.shape
+        assert y_ref.shape == x_ref.shape and x_ref.is_contiguous() and y_ref.is_contiguous() and x_ref.dtype == y_ref.dtype == torch.float64
+        p = self.track_params(n, T, float(dt), w=(float(w[0]), float(w[1])), **kw)
+        k = gust.numbers(float(dt))
+        if S0 is not None:
+            assert S0.is_contiguous() and tuple(S0.shape) == (28, n) and S0.dtype == torch.float64 and S0.device.type == 'cuda'
+        din = DispersionIn(k['a'], k['s'], k['sigma'], None if S0 is None else S0.data_ptr())
+        edges = self._constraint_rows(fence, n, 4, MAX_FENCE, 'track_dispersion: fence')
+        discs = self._constraint_rows(keep_out, n, 3, MAX_KEEP, 'track_dispersion: keep_out')
+        i32 = torch.int32
+        out = dict(S=self.empty(28, n), sig_max=self.empty(n), sig_row=self.empty(n, dtype=i32))
+        if record_P:
+            out['Ppos'] = self.empty(T, 3, n)
+        if edges is not None:
+            ne = edges.shape[1]
+            out.update(fence_sn=self.empty(ne, n), fence_k=self.empty(ne, n), fence_row=self.empty(ne, n, dtype=i32))
+        if discs is not None:
+            out.update(disc_k=self.empty(discs.shape[1], n), disc_row=self.empty(discs.shape[1], n, dtype=i32))
+        names = dict(Ppos_hist='Ppos', S_out='S')
+        dout = DispersionOut(*[None if out.get(names.get(f, f)) is None else out[names.get(f, f)].data_ptr() for f in DISPERSION_OUT])
+        fc = None if edges is None else FenceC(edges.shape[1], 0, edges.data_ptr())
+        kc = None if discs is None else KeepOutC(discs.shape[1], 0, discs.data_ptr())
+        _check(self.lib.d2d_track_dispersion(self.h, C.byref(p), _ptr(x_ref), _ptr(y_ref), C.byref(din), None if fc is None else C.byref(fc),
+                                             None if kc is None else C.byref(kc), C.byref(dout)))
+        return out                                    # (edges, discs are released here: the context's stream is torch's, whose allocator orders reuse)
 
 
 _default_ctx = None

@@ -273,7 +273,7 @@ def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr
     dt = time[1] - time[0]
     xr, yr = ctx.dev(np.ascontiguousarray(x_ref, dtype=np.float64)), ctx.dev(np.ascontiguousarray(y_ref, dtype=np.float64))
     out = ctx.track_run(xr, yr, ctx.dev(_planes(np.asarray(X0s, dtype=np.float64))), float(dt), record=record,
-                        w=(float(w[0]), float(w[1])), tau_phi=ac.tau_phi, tau_v=ac.tau_v,
+                        w=(float(w[0]), float(w[1])), **_track_constants(ac),
                         **({} if fld is None else dict(wind=fld, t_start=float(time[0]))), **gkw)
     if audit is not None:
         n_ac = 1 if audit is True else int(audit.get('n_ac', 1))
@@ -284,6 +284,72 @@ def implement_controller_batch(time, x_ref, y_ref, w, X0s, record=('X', 'U', 'Xr
             out['audit']['fleet'] = fleet
     if est is not None:
         out['wind_estimate'] = est.fit(ctx, out['X'], 1, float(dt), t_start=float(time[0]))
+    return out
+
+
+def _track_constants(ac=None):
+    """The controller constants of the tracking loop that are not Context.track_params' defaults (Q, R, the saturations): the lags of
+    d2d.dynamic.Aircraft.  implement_controller_batch and track_dispersion both take them from here."""
+    ac = ddyn.Aircraft() if ac is None else ac
+    return dict(tau_phi=ac.tau_phi, tau_v=ac.tau_v)
+
+
+def track_dispersion(time, x_ref, y_ref, w, gust, fence=None, keep_out=None, S0=None, record_P=False, windfield=None, loop='track'):
+    """The gust dispersion of implement_controller_batch(time, x_ref, y_ref, w, X0s, gust=gust): how far the LQR-tracked flight
+    strays from its gust-free self, as a covariance per row, from ONE deterministic pass per plan (Context.track_dispersion,
+    include/d2d.h d2d_track_dispersion) instead of thousands of flown replicas.  x_ref, y_ref (T, n) for n independent drones, w the
+    constant wind, gust a d2d.wind.GustModel; fence: a d2d.opty_utils.GeoFence or lowered rows, keep_out: discs (k, 3) = (cx, cy, R);
+    S0 dev [28][n] to continue an earlier report's 'S'; record_P: keep 'Ppos' dev [T][3][n].  The controller constants are
+    implement_controller_batch's own (_track_constants and Context.track_params' defaults).
+    Returns Context.track_dispersion's dict of device tensors plus 'gust', the model; dispersion_margin turns it into margins.
+    The saturations (err_sats, phi_lim, v_min / v_max) and the heading wrap are not modelled.  Refused: a SplineWindField (its
+    gradient would enter the plant's Jacobian), the GVF formation loop and the legacy dfff_run loop (loop='gvf' / 'dfff')."""
+    if loop == 'gvf':
+        raise NotImplementedError('track_dispersion covers the LQR tracking loop only: the GVF formation loop (CircularFormationGVF_batch) '
+                                  'is a nonlinear guidance law with a coupled formation controller')
+    if loop == 'dfff':
+        raise NotImplementedError('track_dispersion covers the LQR tracking loop only: the legacy dfff_run loop (run_simulation_batch) has '
+                                  'another gain and another reference pairing')
+    if loop != 'track':
+        raise ValueError(f"loop={loop!r}: 'track' (or 'gvf', 'dfff', both refused)")
+    if windfield is not None:
+        raise NotImplementedError(f'track_dispersion in a {type(windfield).__name__}: the gradient of a SplineWindField would enter the '
+                                  "plant's Jacobian; only the constant wind w is covered")
+    if plant_gust(gust) is None:
+        raise TypeError('NoneType is not a gust model: build one with d2d.wind.GustModel(sigma, tau=...)')
+    ctx = d2dhip.default_context()
+    xr, yr = ctx.dev(np.ascontiguousarray(x_ref, dtype=np.float64)), ctx.dev(np.ascontiguousarray(y_ref, dtype=np.float64))
+    out = ctx.track_dispersion(xr, yr, w=(float(w[0]), float(w[1])), gust=gust, dt=float(time[1] - time[0]), fence=fence, keep_out=keep_out,
+                               S0=S0, record_P=record_P, **_track_constants())
+    out['gust'] = gust
+    return out
+
+
+def dispersion_margin(report, prob, pair=None):
+    """Margins from a track_dispersion report: z_prob times the predicted standard deviation, z_prob the one-sided normal quantile of
+    `prob` (1.35e-3 -> 3.0).  Returns dict(z, disc [n]: z sig_max, what KeepOut(margin=) of any disc may take; fence [k][n]:
+    z fence_sn per edge, what GeoFence(margin=) may take (with a fence in the report); pair: with pair=(i, j) the same for the
+    distance between drones i and j, z sqrt(sig_max_i^2 + sig_max_j^2), for deconflict(d_sep=)).
+    What the figure is: `prob` is the chance that the GUST SHARE of the deviation, along one constraint's normal, exceeds the margin
+    at ONE row -- per row and per constraint.  It is NOT a probability over the whole flight (a flight has many rows and their
+    deviations are correlated; the chance of one exceedance somewhere is larger), and it does NOT contain the gust-free tracking
+    error, which flight_audit reports as err_max and the caller adds.
+    pair needs form_corr = 0: with a shared gust part the two aircraft's deviations are correlated and their cross-covariance is
+    not computed (refused); with form_corr = 0 the relative covariance is P_i + P_j, bounded here by the two largest eigenvalues."""
+    from statistics import NormalDist
+    if not (np.isfinite(prob) and 0.0 < prob < 0.5):
+        raise ValueError(f'prob={prob!r} must be in (0, 0.5): a one-sided exceedance probability per row and constraint')
+    z = NormalDist().inv_cdf(1.0 - float(prob))
+    sig = report['sig_max']
+    out = dict(z=z, disc=z * sig)
+    if report.get('fence_sn') is not None:
+        out['fence'] = z * report['fence_sn']
+    if pair is not None:
+        if report['gust'].form_corr > 0.0:
+            raise NotImplementedError(f"pair margins with form_corr = {report['gust'].form_corr} > 0: the cross-covariance between two "
+                                      'aircraft of a formation is not computed')
+        i, j = pair
+        out['pair'] = z * (sig[i] ** 2 + sig[j] ** 2) ** 0.5
     return out
 
 

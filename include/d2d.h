@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 127
+#define D2D_VERSION 128
 
 /* error codes */
 #define D2D_OK 0
@@ -1429,6 +1429,55 @@ typedef struct {
 } d2d_nlp_guess_out;
 int d2d_nlp_guess_dubins(d2d_ctx *ctx, int B, int N, double h, const double *scen, const d2d_nlp_guess_opts *opts, double *W,
                          const d2d_nlp_guess_out *out);
+
+/* Gust dispersion of a tracked plan: the covariance of the deviation that d2d_sim_track_run_gust's flight shows from the gust-free flight
+ * of the same references, predicted by ONE deterministic pass per plan -- no sampling.  The tracking loop is a linear feedback round a
+ * known reference whose gain depends on the reference alone (ComputeGain evaluates cont_jac and the Riccati equation at Xr), and the
+ * gust g = w_own o + w_form h is, per axis, one first-order Gauss-Markov process of variance sigma^2 (w_own^2 + w_form^2 = 1) held over a
+ * step.  Deviation state of a drone: z = (dx, dy, dpsi, dphi, dv, gx, gy), covariance S (7 x 7).
+ *   Start     S_0 = blockdiag(P0 or 0_5, sigma^2 I_2): S_in, or without one the stationary start of the loops without state_in.
+ *   Step i = 1 .. n_rows - 1, with reference sample i as the tracking loop pairs them (derivatives: its two passes of
+ *   numpy.gradient(edge_order=2) / dt; n_rows = 2: the one first difference, the second derivative 0):
+ *     Xr_i, K_i (2 x 5)  those of d2d_ctrl_gain at X = Xr_i -- the same flatness map, cont_jac with its quirk entries, the CARE, Yddd = 0;
+ *     A_i     the TRUE Jacobian of the plant's equations of motion at (psi, phi, v) = Xr_i: cont_jac's rows 0, 1, 3, 4 and
+ *             d psi'/d phi = g / (v cos^2 phi), d psi'/d v = -g tan phi / v^2;  B = [0; 0; 0; 1/tau_phi, 0; 0, 1/tau_v];
+ *             E = d f / d w: ones in rows 0 and 1;
+ *     [Ad Bd Ed] = the first five rows of expm(dt [[A B E], [0 0 0]]) (9 x 9): input and gust are zero-order holds over the step
+ *             (evaluated in closed form: the phi and v lags are decoupled, psi and (x, y) are integrals of their exponentials);
+ *     F_i = [[Ad - Bd K_i, Ed], [0, a I_2]],   S_i = F_i S_{i-1} F_i^T + diag(0_5, s^2, s^2).
+ *   The error saturations, phi_lim, v_min / v_max and the wrap of psi are ignored: that is the approximation.  p->n_rows, dt, tau_phi,
+ *   tau_v, wx, wy, q_diag, r_diag are read as d2d_sim_track_run reads them; x_ref, y_ref dev [n_rows][n].
+ * in:   a, s, sigma of d2d_gust; S_in dev [28][n] or NULL.  S is stored as its packed lower triangle, entry (i, j), i >= j, at
+ *       i (i + 1) / 2 + j, plane-major across drones.
+ * out (any pointer may be NULL: not stored), Ppos_i = S_i[0:2, 0:2]:
+ *   Ppos_hist dev [n_rows][3][n] = xx, xy, yy: row i pairs with X_hist row i of the flight (row 0: the start);  S_out dev [28][n]: S after
+ *   the last row (a call that continues with S_in = S_out from the LAST row of this one reproduces one long call where the references'
+ *   derivatives agree);
+ *   sig_max [n] = max_i sqrt(lambda_max(Ppos_i)) and sig_row, its row;
+ *   per edge e = (ax, ay, b, .) of fence->edges [n][n_edge][4] (kap is not read; ax = ay = 0: absent):
+ *     fence_sn [n_edge][n] = max_i sqrt(a^T Ppos_i a),  fence_k = min_i (b - a . p_ref_i) / sqrt(a^T Ppos_i a)  and fence_row, its row;
+ *   per disc (cx, cy, R) of keep->discs [n][n_keep][3] (R <= 0: absent):
+ *     disc_k [n_keep][n] = min_i (|p_ref_i - c| - R) / sqrt(u^T Ppos_i u), u the unit vector from the centre, and disc_row, its row.
+ *   The reductions run over i >= 1 and keep the first row of an extreme; a zero variance gives k = +inf (every row: row 1); an absent
+ *   row gives fence_sn = 0, k = +inf, row -1.  fence_k / fence_row and disc_k / disc_row are given together.
+ * D2D_EINVAL before any launch: a NULL in or out; n < 1 or n_rows < 2; a outside [0, 1); s or sigma negative or not finite; n_edge
+ * beyond D2D_MAX_FENCE or n_keep beyond D2D_MAX_KEEP, a count > 0 with a NULL table; a fence or disc output without its table (fence or
+ * keep NULL, or a count of 0).  fence, keep may be NULL.  One drone per lane and no exchange between lanes in the new arithmetic: a
+ * drone's result does not depend on the batch beyond what d2d_ctrl_gain's Riccati solver already shares with its wavefront.
+ * tests/dispersion_ref.py is the CPU statement.  Asynchronous on the context's stream.  (version 128) */
+typedef struct {
+  double a, s, sigma;   /* exp(-dt / tau), sigma sqrt(1 - a^2), sigma (m/s): d2d_gust's */
+  const double *S_in;   /* dev [28][n] or NULL */
+} d2d_dispersion_in;
+typedef struct {
+  double *Ppos_hist;    /* dev [n_rows][3][n] = xx, xy, yy, or NULL */
+  double *S_out;        /* dev [28][n] or NULL */
+  double *sig_max; int32_t *sig_row;                        /* dev [n] */
+  double *fence_sn; double *fence_k; int32_t *fence_row;    /* dev [n_edge][n] */
+  double *disc_k; int32_t *disc_row;                        /* dev [n_keep][n] */
+} d2d_dispersion_out;
+int d2d_track_dispersion(d2d_ctx *ctx, const d2d_track_params *p, const double *x_ref, const double *y_ref,
+                         const d2d_dispersion_in *in, const d2d_fence *fence, const d2d_keep_out *keep, const d2d_dispersion_out *out);
 
 #ifdef __cplusplus
 }
