@@ -25,6 +25,45 @@
 #define NLP_WIND_NEXT_SHUFFLE 1    // (A/B: -DNLP_WIND_NEXT_SHUFFLE=0 evaluates the field at the next node a second time)
 #endif
 
+// ---- the feature set of an instantiation ------------------------------------------------------------------------------------
+// nlp_merit, nlp_assemble, nlp_recover_stats, nlp_apply, nlp_solve_one, the loop bodies nlp_handout_body and nlp_groups_body and their
+// helpers take ONE template argument, the set F of these bits, named at the call: nlp_solve_one<NLP_WIND * WIND | NLP_KEEP | NLP_FENCE>.
+//   MODEL (d2d_nlp_solve_model): the objective is the quadratic model ex.md on top of the row's structured terms; cost = its value.
+//   WIND  (d2d_nlp_solve_wind): the equalities read the field ex.wf at node i's own (t_start + i h, x_i, y_i), not the row's constant.
+//   PAIRS (d2d_nlp_solve_groups_pairs): partner is the scenario's W and ex.pmask this aircraft's partner set (nlp_exp_terms); 0: none.
+//   MOV   (d2d_nlp_solve_moving, _groups_moving): ex.mv the soft moving discs (nlp_exp_terms), centre planes sampled at the node times.
+//   VIA   (d2d_nlp_solve_via, _groups_via): ex.via the pins, checked by the caller (nlp_via_bad): a pinned component starts at its value
+//         and stays there -- no duals, no barrier, no step, an identity row in the Newton system -- exactly as x, y, psi of the two end
+//         nodes do.  The terms of the objective still count at a pinned node.
+//   FREE  (d2d_nlp_solve_free): h is the problem's own unknown in the box of ex.free_row, started from the row's value or the launch's h;
+//         the Newton system is bordered by the row of u = 1 / h (nlp_assemble, nlp_recover_free), every pass reads the equalities at the
+//         current u, the line search at the trial one, and cost carries the duration term.  An unusable row of the box refuses the
+//         problem like an unusable scenario row; *ex.h_out gets the solved h (NaN for a refused problem).
+//   KEEP  (d2d_nlp_solve_keepout): ex.keep the hard discs and the planes of their duals; g > 0 is held at every interior node by the
+//         box's primal-dual barrier (the four passes), the start is moved out of the discs (nlp_keep_start) and unusable discs refuse
+//         the problem (nlp_keep_bad).  cost does not see the discs.  KMOV brings KEEP with it.
+//   KMOV  (d2d_nlp_solve_keepout_moving, _groups_keepout): ex.keep a NlpKeepMovSet, discs that move: g at node i is taken with the disc's
+//         centre at that node's time.  Nothing else changes: the centres are data.
+//   FENCE (d2d_nlp_solve_fence, _groups_fence): ex.keep a NlpKeepFenceSet, whose fence holds the half-planes and the planes of their
+//         duals; g > 0 is held like the discs', the start is moved inside (nlp_fence_start, behind nlp_keep_start), unusable edges refuse
+//         the problem (nlp_fence_bad).  With KEEP the static hard discs are held too; alone (the group kernel) keep is not read.
+//   T_AT  (nlp_handout_body alone): the start time is the problem's own, t_at [B] in device memory, read and checked per problem.
+constexpr unsigned NLP_MODEL = 1u << 0, NLP_WIND = 1u << 1, NLP_PAIRS = 1u << 2, NLP_MOV = 1u << 3, NLP_VIA = 1u << 4, NLP_FREE = 1u << 5,
+                   NLP_KEEP = 1u << 6, NLP_KMOV = 1u << 7, NLP_FENCE = 1u << 8, NLP_T_AT = 1u << 9;
+template <unsigned F> struct NlpFeatures {
+  static constexpr bool MODEL = (F & NLP_MODEL) != 0, WIND = (F & NLP_WIND) != 0, PAIRS = (F & NLP_PAIRS) != 0, MOV = (F & NLP_MOV) != 0,
+                        VIA = (F & NLP_VIA) != 0, FREE = (F & NLP_FREE) != 0, KMOV = (F & NLP_KMOV) != 0, KEEP = KMOV || (F & NLP_KEEP) != 0,
+                        FENCE = (F & NLP_FENCE) != 0, T_AT = (F & NLP_T_AT) != 0;
+  static_assert(F < (NLP_T_AT << 1), "unknown feature bit");
+  static_assert(!MODEL || F == NLP_MODEL, "MODEL excludes every other feature");
+  static_assert(!FREE || !(WIND || MOV || VIA || KEEP || FENCE), "FREE excludes WIND, MOV, VIA, KEEP, KMOV and FENCE");
+  static_assert(!(KEEP || FENCE) || !(MOV || VIA), "KEEP, KMOV and FENCE exclude MOV and VIA: their problem types carry no soft discs or pins");
+  static_assert(!(KMOV && FENCE), "FENCE holds static hard discs only");
+};
+#define NLP_FEATURES(F)   /* the members of NlpFeatures<F> under their own names, for a function body */                                                \
+  [[maybe_unused]] constexpr bool MODEL = NlpFeatures<F>::MODEL, WIND = NlpFeatures<F>::WIND, PAIRS = NlpFeatures<F>::PAIRS, MOV = NlpFeatures<F>::MOV, VIA = NlpFeatures<F>::VIA, \
+                                  FREE = NlpFeatures<F>::FREE, KEEP = NlpFeatures<F>::KEEP, KMOV = NlpFeatures<F>::KMOV, FENCE = NlpFeatures<F>::FENCE, T_AT = NlpFeatures<F>::T_AT
+
 // per-problem scenario constants in registers
 struct NlpScen {
   double p0[3], p1[3];
@@ -88,11 +127,12 @@ struct NlpMovSet {
   const double *disc;
   int n;
 };
-template <bool PAIRS = false, bool MOV = false>
+template <unsigned F>
 __device__ __forceinline__ void nlp_exp_terms(const NlpScen &s, const double *__restrict__ sc, const double *__restrict__ partner,
-                                              long pidx, long pstride, double x, double y, double &obj, double &cost_ref,
-                                              double *gx, double *gy, double *dxx, double *dxy, double *dyy, unsigned pmask = 0u,
-                                              const NlpMovSet *mv = nullptr) {
+                                              long pidx, long pstride, double x, double y, double &obj, double &cost_ref, unsigned pmask,
+                                              const NlpMovSet *mv, double *gx = nullptr, double *gy = nullptr, double *dxx = nullptr,
+                                              double *dxy = nullptr, double *dyy = nullptr) {
+  NLP_FEATURES(F);
   for (int i = 0; i < s.n_obs; ++i) {
     double cx, cy, r;
     nlp_obs(sc, i, cx, cy, r);
@@ -292,14 +332,14 @@ struct NlpKeepFenceSet : NlpKeepSet {
 };
 __device__ __forceinline__ bool nlp_fence_present(const double *__restrict__ e) { return e[0] != 0.0 || e[1] != 0.0; }
 __device__ __forceinline__ double nlp_fence_g(const double *__restrict__ e, double x, double y) { return e[2] - nlp_dot2(e[0], x, e[1], y); }
-template <bool MOV, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false, bool FENCE = false>
-using NlpProbT = std::conditional_t<FENCE, NlpFenceProb, std::conditional_t<KEEP, std::conditional_t<KMOV, NlpKeepMovProb, NlpKeepProb>,
-                                    std::conditional_t<FREE, NlpFreeProb, std::conditional_t<VIA, NlpViaProb, std::conditional_t<MOV, NlpMovProb, NlpProb>>>>>;
-template <bool VIA, bool KEEP = false, bool KMOV = false, bool FENCE = false>
-using NlpProbV = std::conditional_t<FENCE, NlpFenceProb, std::conditional_t<KEEP, std::conditional_t<KMOV, NlpKeepMovProb, NlpKeepProb>,
-                                    std::conditional_t<VIA, NlpViaProb, NlpProb>>>;       // for the passes that read no soft disc
-template <bool MOV, typename PB> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const PB &pb) {
-  if constexpr (MOV) return &pb.mv;
+template <unsigned F, typename X = NlpFeatures<F>>
+using NlpProbT = std::conditional_t<X::FENCE, NlpFenceProb, std::conditional_t<X::KEEP, std::conditional_t<X::KMOV, NlpKeepMovProb, NlpKeepProb>,
+                                    std::conditional_t<X::FREE, NlpFreeProb, std::conditional_t<X::VIA, NlpViaProb, std::conditional_t<X::MOV, NlpMovProb, NlpProb>>>>>;
+template <unsigned F> using NlpProbV = NlpProbT<F & ~(NLP_MOV | NLP_FREE)>;       // for the passes that read no soft disc and no u
+template <unsigned F, typename X = NlpFeatures<F>>             // the set type that NlpExtra's keep pointer stands for
+using NlpKeepSetT = std::conditional_t<X::FENCE, NlpKeepFenceSet, std::conditional_t<X::KMOV, NlpKeepMovSet, NlpKeepSet>>;
+template <unsigned F, typename PB> __device__ __forceinline__ const NlpMovSet *nlp_mov_set(const PB &pb) {
+  if constexpr (NlpFeatures<F>::MOV) return &pb.mv;
   else return nullptr;
 }
 // Objective model of d2d_nlp_solve_model (user cost plug-ins, opty/direct_collocation.py): this problem's planes.  The objective of
@@ -365,14 +405,14 @@ __device__ __forceinline__ void nlp_constraint(const NlpScen &s, double h, const
 
 __device__ __forceinline__ bool nlp_fixed(int i, int N, int c) { return c < 3 && (i == 0 || i == N - 1); }
 // VIA: the node's mask m = vm[i] answers instead (nlp_via_mask: 0 in the other instantiations, where it is not read)
-template <bool VIA>
+template <unsigned F>
 __device__ __forceinline__ bool nlp_fixed_at(int i, int N, int c, int m) {
-  if constexpr (VIA) return c < 3 && ((m >> c) & 1) != 0;
+  if constexpr (NlpFeatures<F>::VIA) return c < 3 && ((m >> c) & 1) != 0;
   else return nlp_fixed(i, N, c);
 }
-template <bool VIA, typename PB>
+template <unsigned F, typename PB>
 __device__ __forceinline__ int nlp_via_mask(const PB &pb, int i) {
-  if constexpr (VIA) return pb.vm[i];
+  if constexpr (NlpFeatures<F>::VIA) return pb.vm[i];
   else return 0;
 }
 
@@ -382,10 +422,10 @@ __device__ __forceinline__ int nlp_via_mask(const PB &pb, int i) {
 // u's box and the value +inf outside it join the sums (cost_ref_out: the reference's cost() + k_dur (N - 1) h).
 // KEEP: - mub log g of every (interior node, disc) joins the barrier (one more log per node, of the product), +inf when a g <= 0.
 // FENCE: - mub log g of every (interior node, edge) likewise, a log of its own behind the discs'.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false,
-          bool FENCE = false>
-__device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
+template <unsigned F>
+__device__ double nlp_merit(const NlpProbT<F> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double a, double rho,
                             double mub, double *cost_ref_out, double *feas_out, const NlpModel &md, [[maybe_unused]] double ut = 0.0) {
+  NLP_FEATURES(F);
   const int N = pb.N;
   [[maybe_unused]] const double ht = FREE ? 1.0 / ut : 0.0;
   double val = 0.0, bar = 0.0, cref = 0.0, feas = 0.0, phi2max = 0.0;
@@ -401,7 +441,7 @@ __device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> &p
       for (int c = 0; c < NLP_NV; ++c) { w[c] = NLP_W(c, i); dwl[c] = NLP_DW(c, i); }
 #pragma unroll
       for (int c = 0; c < 3; ++c) { wp[c] = NLP_W(c, im); dwp[c] = NLP_DW(c, im); muv[c] = NLP_MU(c, i); }
-      [[maybe_unused]] const int vmi = nlp_via_mask<VIA>(pb, i);
+      [[maybe_unused]] const int vmi = nlp_via_mask<F>(pb, i);
       if (a != 0.0) {
 #pragma unroll
         for (int c = 0; c < NLP_NV; ++c) w[c] += a * dwl[c];
@@ -412,7 +452,7 @@ __device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> &p
       double prod = 1.0;
 #pragma unroll
       for (int c = 0; c < NLP_NV; ++c) {
-        if (nlp_fixed_at<VIA>(i, N, c, vmi)) continue;
+        if (nlp_fixed_at<F>(i, N, c, vmi)) continue;
         if (s.lo[c] > -1e299) { const double sl = w[c] - s.lo[c]; if (!(sl > 0.0)) outside = 1; prod *= (sl > 0.0 ? sl : 1.0); }
         if (s.hi[c] < 1e299) { const double su = s.hi[c] - w[c]; if (!(su > 0.0)) outside = 1; prod *= (su > 0.0 ? su : 1.0); }
       }
@@ -465,7 +505,7 @@ __device__ double nlp_merit(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> &p
       }
       phi2max = fmax(phi2max, w[3] * w[3]);
       cref += obj;
-      nlp_exp_terms<PAIRS, MOV>(s, sc, pb.partner, i, N, w[0], w[1], obj, cref, nullptr, nullptr, nullptr, nullptr, nullptr, pb.pmask, nlp_mov_set<MOV>(pb));
+      nlp_exp_terms<F>(s, sc, pb.partner, i, N, w[0], w[1], obj, cref, pb.pmask, nlp_mov_set<F>(pb));
       val += obj;
       if (i >= 1) {
         double c3[3];
@@ -549,10 +589,10 @@ __device__ int nlp_bank_argmax(const NlpProb &pb, int lane) {
 // FENCE: edge k at an interior node i, g = b - a . p, grad g = -a, dual z: the stationarity rows of (x, y) gain + z a, the right-hand side
 // - (mub / g) a, the (x, y) corner of D (half convention)  1/2 (z / g) a a^T  -- positive semidefinite, the constraint has no curvature --
 // and the KKT error |z g - mub|.  The sums kst, krh are the discs' (of grad g), so both families leave through the same two lines below.
-template <bool MODEL, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false, bool KMOV = false,
-          bool FENCE = false>
-__device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
+template <unsigned F>
+__device__ double nlp_assemble(const NlpProbT<F> &pb, const NlpScen &s, const double *__restrict__ sc, int lane, double rho, double mub,
                                double lam, bool *pd_out, int imax, bool rec_lds, const NlpModel &md, [[maybe_unused]] NlpFreeRow *fr_out = nullptr) {
+  NLP_FEATURES(F);
   const int N = pb.N;
   const double h = pb.h, ih = 1.0 / h;
   double err = 0.0;
@@ -582,7 +622,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE>
     for (int c = 0; c < NLP_NV; ++c) { wc[c] = NLP_W(c, i); wn[c] = NLP_W(c, ip); zlv[c] = NLP_P(WS_ZL + c, i); zuv[c] = NLP_P(WS_ZU + c, i); }
 #pragma unroll
     for (int c = 0; c < 3; ++c) { wp[c] = NLP_W(c, im); mu_c[c] = NLP_MU(c, i); mu_n[c] = NLP_MU(c, ip); }
-    [[maybe_unused]] const int vmi = nlp_via_mask<VIA>(pb, i), vmp = nlp_via_mask<VIA>(pb, im);
+    [[maybe_unused]] const int vmi = nlp_via_mask<F>(pb, i), vmp = nlp_via_mask<F>(pb, im);
     if (i < 1) { wp[0] = 0.0; wp[1] = 0.0; wp[2] = 0.0; }
     // WIND: the field at this node -- value, Jacobian, second derivatives in one pass -- for every live lane; the value at the
     // NEXT node, which cn needs, comes from the neighbouring lane (NLP_WIND_NEXT_SHUFFLE, the default) or from a second, value-only
@@ -640,7 +680,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE>
     }
     {
       double obj = 0.0, cref = 0.0;
-      nlp_exp_terms<PAIRS, MOV>(s, sc, pb.partner, i, N, wc[0], wc[1], obj, cref, &g[0], &g[1], &D[0][0], &D[0][1], &D[1][1], pb.pmask, nlp_mov_set<MOV>(pb));
+      nlp_exp_terms<F>(s, sc, pb.partner, i, N, wc[0], wc[1], obj, cref, pb.pmask, nlp_mov_set<F>(pb), &g[0], &g[1], &D[0][0], &D[0][1], &D[1][1]);
       if constexpr (KEEP) {
         if (i >= 1 && i < N - 1) {
           const double *__restrict__ dk = pb.keep.discs;
@@ -741,7 +781,7 @@ __device__ double nlp_assemble(const NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE>
     // barrier terms, stationarity / complementarity error, right-hand side
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) {
-      const bool fx = nlp_fixed_at<VIA>(i, N, c, vmi);
+      const bool fx = nlp_fixed_at<F>(i, N, c, vmi);
       double sig = 0.0, r = -2.0 * g[c], st = 2.0 * g[c];
       if (!fx && s.lo[c] > -1e299) {
         const double sl = wc[c] - s.lo[c], z = zlv[c], isl = 1.0 / sl;
@@ -1375,9 +1415,10 @@ __device__ __attribute__((noinline)) void nlp_backsolve(double *sf_generic, doub
 // directional derivative needs nothing: the right-hand side carries the discs' terms.
 // FENCE: g is linear in the step, g(a) = g - a (a . s): the rule is a <= tau g / (a . s) where a . s > 0, taken like a box bound's; the
 // dual's step is dz = (mub + z a . s) / g - z.
-template <bool VIA = false, bool KEEP = false, bool KMOV = false, bool FENCE = false>
-__device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP, KMOV, FENCE> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
+template <unsigned F>
+__device__ void nlp_recover_stats(const NlpProbV<F> &pb, const NlpScen &s, int lane, double mub, double tau, double *dphi_out,
                                   double *amax_out, double *az_out) {
+  NLP_FEATURES(F);
   const int N = pb.N;
   double dphi = 0.0, amax = 1.0, az = 1.0;
   for (int i0 = 0; i0 < N; i0 += 64) {
@@ -1396,7 +1437,7 @@ __device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP, KMOV, FENCE> &pb, co
     for (int k = 0; k < 3; ++k) ellp[k] = NLP_EL(EL_LP + k, i);
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) { wv[c] = NLP_W(c, i); rhv[c] = NLP_RHS(c, i); zlv[c] = NLP_P(WS_ZL + c, i); zuv[c] = NLP_P(WS_ZU + c, i); }
-    [[maybe_unused]] const int vmi = nlp_via_mask<VIA>(pb, i);
+    [[maybe_unused]] const int vmi = nlp_via_mask<F>(pb, i);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       z0 -= elq[k] * dwv[k] + elr[k] * dsp[k];
@@ -1409,7 +1450,7 @@ __device__ void nlp_recover_stats(const NlpProbV<VIA, KEEP, KMOV, FENCE> &pb, co
       const double dw = dwv[c];
       NLP_DW(c, i) = dw;
       dphi -= rhv[c] * dw;
-      if (nlp_fixed_at<VIA>(i, N, c, vmi)) continue;
+      if (nlp_fixed_at<F>(i, N, c, vmi)) continue;
       const double w = wv[c];
       if (s.lo[c] > -1e299) {
         const double sl = w - s.lo[c], z = zlv[c];
@@ -1557,8 +1598,9 @@ __device__ bool nlp_recover_free(const NlpFreeProb &pb, const NlpScen &s, int la
 // Take the step (node-parallel): W += a dw, duals += az dz (dz from the step's dw), duals kept near the central path.
 // KEEP: the discs' duals move and are clipped like the box duals, with g at the new point.
 // FENCE: the edges' duals likewise.
-template <bool VIA = false, bool KEEP = false, bool KMOV = false, bool FENCE = false>
-__device__ void nlp_apply(const NlpProbV<VIA, KEEP, KMOV, FENCE> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
+template <unsigned F>
+__device__ void nlp_apply(const NlpProbV<F> &pb, const NlpScen &s, int lane, double a, double az, double mub) {
+  NLP_FEATURES(F);
   const int N = pb.N;
   for (int i0 = 0; i0 < N; i0 += 64) {
     const int i = i0 + lane;
@@ -1567,10 +1609,10 @@ __device__ void nlp_apply(const NlpProbV<VIA, KEEP, KMOV, FENCE> &pb, const NlpS
     double wv[NLP_NV], dwl[NLP_NV], zlv[NLP_NV], zuv[NLP_NV];
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) { wv[c] = NLP_W(c, i); dwl[c] = NLP_DW(c, i); zlv[c] = NLP_P(WS_ZL + c, i); zuv[c] = NLP_P(WS_ZU + c, i); }
-    [[maybe_unused]] const int vmi = nlp_via_mask<VIA>(pb, i);
+    [[maybe_unused]] const int vmi = nlp_via_mask<F>(pb, i);
 #pragma unroll
     for (int c = 0; c < NLP_NV; ++c) {
-      if (nlp_fixed_at<VIA>(i, N, c, vmi)) continue;
+      if (nlp_fixed_at<F>(i, N, c, vmi)) continue;
       const double w = wv[c], dw = dwl[c];
       const double wn = w + a * dw;
       NLP_W(c, i) = wn;
@@ -1665,7 +1707,8 @@ __device__ __forceinline__ bool nlp_via_bad(const double *__restrict__ pts, int 
 }
 
 // The optional inputs of nlp_solve_one in one aggregate, so that one call expression serves every instantiation: each reads the
-// members of its own template arguments and ignores the others (NlpExtra{}: none).
+// members of its own feature set and ignores the others (NlpExtra{}: none).  A plain aggregate, initialised in the call expression, on
+// purpose: default member initialisers, or a named object whose members are set one by one, moved kernels.
 struct NlpExtra {
   NlpModel md;               // MODEL
   const d2d_wind_field *wf;  // WIND: the field and the problem's start time
@@ -1675,7 +1718,7 @@ struct NlpExtra {
   const NlpViaSet *via;      // VIA
   const double *free_row;    // FREE: (h_lo, h_hi, k_dur, h_start; 0 = the launch's h) of the problem, and where its solved h goes
   double *h_out;
-  const NlpKeepSet *keep;    // KEEP (KMOV: the NlpKeepMovSet it is the base of; FENCE: the NlpKeepFenceSet)
+  const NlpKeepSet *keep;    // KEEP: the problem's NlpKeepSetT<F> (KMOV: a NlpKeepMovSet, FENCE: a NlpKeepFenceSet)
 };
 
 // KEEP: the start of a free node's position.  The box push of the start pass, then every disc in index order, twice (a push out of one
@@ -1691,8 +1734,9 @@ __device__ __forceinline__ double nlp_box_push(double w, double lo, double hi) {
   return w;
 }
 // KMOV: the discs' centres are node i's own (N: the planes' stride).
-template <bool KMOV = false, typename KS = NlpKeepSet>
-__device__ __forceinline__ void nlp_keep_start(const NlpScen &s, const KS &k, double &x, double &y, [[maybe_unused]] int i = 0, [[maybe_unused]] int N = 0) {
+template <unsigned F = NLP_KEEP>
+__device__ __forceinline__ void nlp_keep_start(const NlpScen &s, const NlpKeepSetT<F & ~NLP_FENCE> &k, double &x, double &y, [[maybe_unused]] int i = 0, [[maybe_unused]] int N = 0) {
+  constexpr bool KMOV = NlpFeatures<F>::KMOV;
   x = nlp_box_push(x, s.lo[0], s.hi[0]); y = nlp_box_push(y, s.lo[1], s.hi[1]);
   const double lx = s.p1[0] - s.p0[0], ly = s.p1[1] - s.p0[1], ll = sqrt(lx * lx + ly * ly);
   const double nx = ll > 0.0 ? -ly / ll : 0.0, ny = ll > 0.0 ? lx / ll : 1.0;
@@ -1767,7 +1811,7 @@ __device__ __forceinline__ bool nlp_keep_bad(const NlpScen &s, const NlpKeepMovS
     const int i = i0 + lane;
     if (i < 1 || i >= N - 1) continue;
     double x = Wb[i], y = Wb[N + i];
-    nlp_keep_start<true>(s, k, x, y, i, N);
+    nlp_keep_start<NLP_KMOV>(s, k, x, y, i, N);
     x = nlp_box_push(x, s.lo[0], s.hi[0]); y = nlp_box_push(y, s.lo[1], s.hi[1]);
 #pragma clang loop unroll(disable)
     for (int m = 0; m < k.n; ++m) {
@@ -1799,8 +1843,9 @@ __device__ __forceinline__ void nlp_fence_start(const NlpFenceSet &f, double &x,
 // FENCE: what refuses a problem before its first store (wave-uniform): an edge with a non-finite entry, a present edge whose normal is
 // off unit length by more than 1e-12 or whose kap is not positive, an end pose on or outside an edge, or a free node that the start
 // rules -- the discs', then the edges', then the box push -- leave on or outside an edge or (KEEP) on or inside a disc.
-template <bool KEEP>
+template <unsigned F>
 __device__ __forceinline__ bool nlp_fence_bad(const NlpScen &s, const NlpFenceProb &pb, const double *__restrict__ Wb, int N, int lane) {
+  constexpr bool KEEP = NlpFeatures<F>::KEEP;
   int bad = 0;
   const NlpFenceSet &f = pb.fence;
 #pragma clang loop unroll(disable)
@@ -1842,30 +1887,12 @@ __device__ __forceinline__ bool nlp_fence_bad(const NlpScen &s, const NlpFencePr
 
 // The solve of ONE problem by one wavefront (lane = threadIdx.x & 63): sc its scenario row, Wb [5][N] in/out, wsb its workspace,
 // multb [3][N] or null, partner [2][N] frozen positions of the CostCollision partner or null.  Wave-uniform control flow.
-// MODEL: the objective is the quadratic model md (d2d_nlp_solve_model) on top of the row's structured terms; cost = its value.
-// WIND: the equalities read the field wf at node i's own (t_start + i h, x_i, y_i) instead of the row's constant (d2d_nlp_solve_wind).
-// PAIRS: partner is the scenario's W and pmask this aircraft's partner set (nlp_exp_terms); pmask = 0: no partner.
-// MOV: mv the problem's moving discs (nlp_exp_terms), their centre planes sampled at this problem's node times.
-// VIA: via the problem's pins, checked by the caller (nlp_via_bad): a pinned component starts at its value and stays there -- no duals,
-// no barrier, no step, an identity row in the Newton system -- exactly as x, y, psi of the two end nodes do.  The terms of the objective
-// still count at a pinned node.
-// FREE (d2d_nlp_solve_free): h is the problem's own unknown in the box of ex.free_row, started from the row's value or from the
-// launch's h; the Newton system is bordered by the row of u = 1 / h (nlp_assemble, nlp_recover_free), every pass reads the
-// equalities at the current u, the line search at the trial one, and cost carries the duration term.  An unusable row of the box
-// refuses the problem like an unusable scenario row; *ex.h_out gets the solved h (NaN for a refused problem).
-// KEEP (d2d_nlp_solve_keepout): ex.keep the problem's hard discs and the planes of their duals; g > 0 is held at every interior node by
-// the same primal-dual barrier as the box (nlp_merit, nlp_assemble, nlp_recover_stats, nlp_apply), the start is moved out of the discs
-// (nlp_keep_start) and unusable discs refuse the problem (nlp_keep_bad).  cost does not see the discs.
-// KMOV (d2d_nlp_solve_keepout_moving, d2d_nlp_solve_groups_keepout): KEEP with ex.keep a NlpKeepMovSet, discs that move: g at node i is taken with the
-// disc's centre at that node's time (NlpKeepMovSet).  Nothing else changes: the centres are data.
-// FENCE (d2d_nlp_solve_fence, d2d_nlp_solve_groups_fence): ex.fence the problem's half-planes and the planes of their duals; g > 0 is held at
-// every interior node by the same barrier (the four passes above), the start is moved inside (nlp_fence_start, behind nlp_keep_start) and
-// unusable edges refuse the problem (nlp_fence_bad).  With KEEP the static hard discs are held too.  cost does not see the edges.
-template <bool MODEL = false, bool WIND = false, bool PAIRS = false, bool MOV = false, bool VIA = false, bool FREE = false, bool KEEP = false,
-          bool KMOV = false, bool FENCE = false>
+// F: the feature set (NlpFeatures, at the head of the file); ex: the optional inputs that its members name (NlpExtra).
+template <unsigned F = 0u>
 __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opts &o, const double *__restrict__ sc, const double *partner,
                                               double *Wb, double *wsb, double *multb, int lane, NlpOut &out, unsigned long long *stamps, double *ldsw,
                                               const double *__restrict__ bnd, const NlpExtra &ex = NlpExtra{}) {
+  NLP_FEATURES(F);
   const NlpModel md = ex.md;
   [[maybe_unused]] const NlpViaSet *via = ex.via;
   // diagnostics (D2D_NLP_STAMPS): cycles per phase -- merit, assembly, factorisation, back substitution, ratio tests, update
@@ -1875,11 +1902,9 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
   if (st_on) st_t = __builtin_amdgcn_s_memtime();
   NlpScen s = nlp_load_scen(sc, o, bnd);
   if (sc[D2D_SC_BANKMAX] != 0.0) { s.sbank = s.skphi * (double)N; s.skphi = 0.0; }     // obj_scale * kbank (the row's S is obj_scale / N)
-  NlpProbT<MOV, VIA, FREE, KEEP, KMOV, FENCE> pb;
+  NlpProbT<F> pb;
   if constexpr (FENCE) pb.fence = static_cast<const NlpKeepFenceSet *>(ex.keep)->fence;
-  if constexpr (KEEP && KMOV) pb.keep = *static_cast<const NlpKeepMovSet *>(ex.keep);
-  else
-  if constexpr (KEEP) pb.keep = *ex.keep;
+  if constexpr (KEEP) pb.keep = *static_cast<const NlpKeepSetT<F & ~NLP_FENCE> *>(ex.keep);
   if constexpr (MOV) pb.mv = *ex.mv;
   if constexpr (VIA) pb.vm = via->vm;
   pb.N = N; pb.h = h;
@@ -1911,7 +1936,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       if (lane == 0) *ex.h_out = __builtin_nan("");
     }
     if constexpr (KEEP) bad = bad || nlp_keep_bad(s, pb.keep, Wb, N, lane);
-    if constexpr (FENCE) bad = bad || nlp_fence_bad<KEEP>(s, pb, Wb, N, lane);
+    if constexpr (FENCE) bad = bad || nlp_fence_bad<F>(s, pb, Wb, N, lane);
     if (bad) {
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
       return;
@@ -1941,7 +1966,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     [[maybe_unused]] double kxy[2] = {0.0, 0.0};
     if constexpr (KEEP) {
       kxy[0] = NLP_W(0, i); kxy[1] = NLP_W(1, i);
-      nlp_keep_start<KMOV>(s, pb.keep, kxy[0], kxy[1], i, N);
+      nlp_keep_start<F>(s, pb.keep, kxy[0], kxy[1], i, N);
     }
     if constexpr (FENCE) {
       if constexpr (!KEEP) { kxy[0] = nlp_box_push(NLP_W(0, i), s.lo[0], s.hi[0]); kxy[1] = nlp_box_push(NLP_W(1, i), s.lo[1], s.hi[1]); }
@@ -1952,7 +1977,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       double w = NLP_W(c, i);
       if constexpr (KEEP || FENCE) { if (c < 2) w = kxy[c]; }
       double zl = 0.0, zu = 0.0;
-      if (nlp_fixed_at<VIA>(i, N, c, vmi)) {
+      if (nlp_fixed_at<F>(i, N, c, vmi)) {
         if constexpr (VIA) w = (i == 0) ? s.p0[c] : (i == N - 1 ? s.p1[c] : pin[c]);
         else
         w = (i == 0) ? s.p0[c] : s.p1[c];
@@ -1991,7 +2016,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
 #pragma unroll
     for (int k = 0; k < 3; ++k) NLP_MU(k, i) = 0.0;
   }
-  [[maybe_unused]] double du = 0.0;
+  [[maybe_unused]] double du = 0.0, ut = 0.0;          // FREE: the step of u, and the value of u that nlp_merit reads the equalities at
   if constexpr (FREE) {                      // u = 1 / h pushed strictly inside its box like a node variable, its duals on the central path
     const double hs = ex.free_row[3] != 0.0 ? ex.free_row[3] : h;
     pb.ulo = 1.0 / ex.free_row[1]; pb.uhi = 1.0 / ex.free_row[0]; pb.kd = ex.free_row[2] * (double)(N - 1);
@@ -2016,9 +2041,8 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     // merit value of the current point for this (mub, rho, mu): one pass here, afterwards the accepted trial's value
     NLP_STAMP(7)
     double phi0;
-    if constexpr (FREE) phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md, pb.u);
-    else
-    phi0 = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md);
+    if constexpr (FREE) ut = pb.u;
+    phi0 = nlp_merit<F>(pb, s, sc, lane, 0.0, rho, mub, nullptr, nullptr, md, ut);
     const double phi_first = phi0;
     NLP_STAMP(0)
     bool accepted = false;
@@ -2032,7 +2056,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         [[maybe_unused]] double ru = 0.0, dfull = 0.0;
         if constexpr (FREE) {
           NlpFreeRow fr;
-          err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, rho, mub, lam, &pd, imax, false, md, &fr);
+          err = nlp_assemble<F>(pb, s, sc, lane, rho, mub, lam, &pd, imax, false, md, &fr);
           // the row of u: half gradient, KKT error, right-hand side, damped half curvature
           const double u = pb.u, sl = u - pb.ulo, su = pb.uhi - u;
           const double g_u = -0.5 * pb.kd / (u * u) + fr.gu;
@@ -2041,7 +2065,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
           const double d0 = pb.kd / (u * u * u) + fr.dd + 0.5 * (pb.zul / sl + pb.zuu / su);
           dfull = d0 + lam * fmax(fabs(d0), 1e-12);
         } else
-        err = nlp_assemble<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
+        err = nlp_assemble<F>(pb, s, sc, lane, rho, mub, lam, &pd, imax, rec_lds, md);  // (a retry with another damping assembles again: rare)
         nlp_phase_sync();
         NLP_STAMP(1)
         if (tr == 0 && err <= tol_in) { converged = true; break; }
@@ -2072,7 +2096,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
           NLP_STAMP(4)
           if (!spd) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
         } else {
-        nlp_recover_stats<VIA, KEEP, KMOV, FENCE>(pb, s, lane, mub, tau, &dphi, &amax, &az);
+        nlp_recover_stats<F>(pb, s, lane, mub, tau, &dphi, &amax, &az);
         nlp_phase_sync();
         NLP_STAMP(4)
         }
@@ -2080,16 +2104,15 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         double a = amax, pt = 0.0;
         bool ok = false;
         for (int ls = 0; ls < 8; ++ls) {
-          if constexpr (FREE) pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md, pb.u + a * du);
-          else
-          pt = nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md);
+          if constexpr (FREE) ut = pb.u + a * du;
+          pt = nlp_merit<F>(pb, s, sc, lane, a, rho, mub, nullptr, nullptr, md, ut);
           if (pt <= phi0 + 1e-4 * a * dphi) { ok = true; break; }
           a *= 0.5;
         }
         NLP_STAMP(0)
         if (ok) {
           phi0 = pt;
-          nlp_apply<VIA, KEEP, KMOV, FENCE>(pb, s, lane, a, az, mub);
+          nlp_apply<F>(pb, s, lane, a, az, mub);
           if constexpr (FREE) {              // u and its duals move like a node variable (nlp_apply)
             const double u = pb.u, un = u + a * du, sl = u - pb.ulo, su = pb.uhi - u;
             const double ml = mub / (un - pb.ulo), mh = mub / (pb.uhi - un);
@@ -2107,9 +2130,8 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
       }
       if (converged || !accepted) break;
     }
-    if constexpr (FREE) (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
-    else
-    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+    if constexpr (FREE) ut = pb.u;
+    (void)nlp_merit<F>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, ut);
     if (!(fabs(phi0) <= 1.79e308) || !(fabs(err) <= 1.79e308)) { status = D2D_ST_NONFINITE; break; }
     if (feas <= o.feas_tol && mub <= o.mub_min * 1.0001 && err <= tol_in) { status = D2D_ST_CONVERGED; break; }
     // CostBank max mode: the one-hot cost_grad has no zero where two nodes share the maximum (they do at a min-max optimum): the
@@ -2150,11 +2172,9 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
     feas_prev = feas;
     mub = fmax(o.mub_min, fmin(0.2 * mub, mub * sqrt(mub)));
   }
-  if constexpr (FREE) {
-    (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, true>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, pb.u);
-    if (lane == 0) *ex.h_out = pb.h;
-  } else
-  (void)nlp_merit<MODEL, WIND, PAIRS, MOV, VIA, false, KEEP, KMOV, FENCE>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md);
+  if constexpr (FREE) ut = pb.u;
+  (void)nlp_merit<F>(pb, s, sc, lane, 0.0, rho, mub, &cost_ref, &feas, md, ut);
+  if constexpr (FREE) { if (lane == 0) *ex.h_out = pb.h; }
   out.cost = cost_ref; out.feas = feas; out.iters = total_inner; out.status = status;
   if (lane == 0 && st_on) {
     NLP_STAMP(7)
@@ -2272,34 +2292,29 @@ __device__ __forceinline__ void nlp_report(int b, int lane, const NlpOut &out, d
   }
 }
 
-// nlp_solve_kernel's persistent hand-out around the WIND, MOV and VIA instantiations of the solve (no partner, no stamps): one body
-// for nlp_solve_wind_kernel and the two nlp_solve_via_kernel below, switched at compile time.  The field is shared by the batch and travels as a kernel argument (scalar
-// registers); its control points are a small table that every wavefront reads and that stays in L2.
-// T_AT: the start time is the problem's own, t_at [B] (device memory), read when the equalities or a track need it and checked: a
-//   problem whose start time is not finite is refused before its solve.  Else it is the scalar t_start of d2d_nlp_solve_wind, which
-//   the host has checked.
-// MOV: the centre planes ctr [B][n_mov][2][N] were sampled ahead of this launch; a problem whose tracks are unusable is refused.
-// VIA: the problem's pins via->pts [B][n_via][5] and the plane of its nodes' fixed sets vwork [B][N]; unusable pins refuse the problem
-//   like an unusable track.  mv->n_mov = 0: nothing moves.
+// nlp_solve_kernel's persistent hand-out around the other instantiations of the solve (no partner): one body for the hand-out kernels
+// below, switched at compile time by F.  The field is shared by the batch and travels as a kernel argument (scalar registers); its
+// control points are a small table that every wavefront reads and that stays in L2.  What the members of F read HERE, per problem:
+// T_AT: t_at [B], read when the equalities or a track need it; a problem whose start time is not finite is refused before its solve.
+//   Else the start time is the scalar t_start of d2d_nlp_solve_wind, which the host has checked.
+// MOV: the centre planes ctr [B][n_mov][2][N], sampled ahead of this launch; a problem whose tracks are unusable is refused (n_mov = 0:
+//   nothing moves).  VIA: via->pts [B][n_via][5] and the plane of the nodes' fixed sets vwork [B][N]; unusable pins refuse it likewise.
+// FREE: free_rows [B][4] and h_out [B]; the slot's workspace has the planes of the border behind the others (WSF_TOTAL); stamps.
+// KEEP: keep->discs [B][n_keep][3] and the planes of their duals kwork [B][n_keep][N] (the problem's, not the slot's: a result).  KMOV:
+//   the hard discs in mv and ctr, tracks checked like MOV's, kwork [B][n_mov][N].  FENCE: fence->edges [B][n_edge][4] and fwork
+//   [B][n_edge][N] beside the discs' (n_keep may be 0: keep->discs and kwork are then not read).
 // A refused problem's W is not touched.  The pointer parameters carry no __restrict__ (the kernels' do), as in nlp_groups_body.
-// FREE (nlp_solve_free_kernel): the problems' boxes of the time step free_rows [B][4] and their solved steps h_out [B]; the slot's
-// workspace has the planes of the border behind the others (WSF_TOTAL).
-// KEEP (nlp_solve_keepout_kernel): the problems' hard discs keep->discs [B][n_keep][3] and the planes of their duals kwork [B][n_keep][N]
-// (the problem's, not the slot's: they are a result).
-// KMOV (nlp_solve_keepout_moving_kernel): KEEP with the hard discs in mv and ctr -- the tracks are checked like MOV's, the planes of the
-// duals kwork [B][n_mov][N].
-// FENCE (nlp_solve_fence_kernel): KEEP with the problems' half-planes fence->edges [B][n_edge][4] and the planes of their duals fwork
-// [B][n_edge][N] beside the discs' (n_keep may be 0: keep->discs and kwork are then not read).
-template <bool WIND, bool MOV, bool VIA, bool T_AT, bool FREE = false, bool KEEP = false, bool KMOV = false, bool FENCE = false>
+template <unsigned F>
 __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d2d_nlp_opts &o, const double *scen, double *W, double *work,
                                                  double *mult, double *cost_out, double *feas_out, int32_t *iters_out, int32_t *status_out,
                                                  int32_t *queue, const d2d_wind_field *wf, double t_start, const double *t_at = nullptr,
-                                                 const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr,
-                                                 const d2d_via_points *via = nullptr, int32_t *vwork = nullptr,
-                                                 const double *free_rows = nullptr, double *h_out = nullptr,
-                                                 [[maybe_unused]] unsigned long long *stamps = nullptr,
-                                                 [[maybe_unused]] const d2d_keep_out *keep = nullptr, [[maybe_unused]] double *kwork = nullptr,
-                                                 [[maybe_unused]] const d2d_fence *fence = nullptr, [[maybe_unused]] double *fwork = nullptr) {
+                                                 const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr, const d2d_via_points *via = nullptr,
+                                                 int32_t *vwork = nullptr, const double *free_rows = nullptr, double *h_out = nullptr,
+                                                 [[maybe_unused]] unsigned long long *stamps = nullptr, [[maybe_unused]] const d2d_keep_out *keep = nullptr,
+                                                 [[maybe_unused]] double *kwork = nullptr, [[maybe_unused]] const d2d_fence *fence = nullptr,
+                                                 [[maybe_unused]] double *fwork = nullptr) {
+  NLP_FEATURES(F);
+  static_assert(!(MODEL || PAIRS), "the hand-out loop solves single problems under the structured objective");
   const int lane = threadIdx.x;
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   double *wsb = work + (size_t)blockIdx.x * (FREE ? WSF_TOTAL : WS_TOTAL) * N;
@@ -2321,13 +2336,10 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
       }
     }
     [[maybe_unused]] NlpMovSet ms{nullptr, nullptr, 0};
-    if constexpr (KMOV) {
+    if constexpr (MOV || KMOV) {
       if (mv->n_mov > 0) bad = bad || nlp_mov_bad(*mv, b, lane);
     }
-    if constexpr (MOV) {
-      if (mv->n_mov > 0) bad = bad || nlp_mov_bad(*mv, b, lane);
-      ms = NlpMovSet{ctr + (size_t)b * mv->n_mov * 2 * N, mv->disc + (size_t)b * mv->n_mov * 2, mv->n_mov};
-    }
+    if constexpr (MOV) ms = NlpMovSet{ctr + (size_t)b * mv->n_mov * 2 * N, mv->disc + (size_t)b * mv->n_mov * 2, mv->n_mov};
     const double *sc = scen + (size_t)b * D2D_SCEN_STRIDE, *bnd = o.bounds ? o.bounds + (size_t)b * 4 : nullptr;
     [[maybe_unused]] NlpViaSet vs{nullptr, nullptr, 0};
     if constexpr (VIA) {
@@ -2336,29 +2348,17 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
     }
     if (bad) {
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
-    } else if constexpr (FREE) {
-      nlp_solve_one<false, false, false, false, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
-                                                             lane, out, b == 0 ? stamps : nullptr, nlp_lds, bnd,
-                                                             NlpExtra{{nullptr, nullptr, nullptr}, nullptr, 0.0, 0u, nullptr, nullptr, free_rows + (size_t)b * 4, h_out + b});
-    } else if constexpr (FENCE) {
-      const NlpKeepFenceSet ks{{keep->discs + (size_t)b * keep->n_keep * 3, kwork + (size_t)b * keep->n_keep * N, keep->n_keep},
-                               {fence->edges + (size_t)b * fence->n_edge * 4, fwork + (size_t)b * fence->n_edge * N, fence->n_edge}};
-      nlp_solve_one<false, WIND, false, false, false, false, true, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb,
-                                                                                mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds, bnd,
-                                                                                NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, nullptr, nullptr, nullptr, nullptr, &ks});
-    } else if constexpr (KEEP && KMOV) {
-      const NlpKeepMovSet ks{{mv->disc + (size_t)b * mv->n_mov * 2, kwork + (size_t)b * mv->n_mov * N, mv->n_mov}, ctr + (size_t)b * mv->n_mov * 2 * N};
-      nlp_solve_one<false, WIND, false, false, false, false, true, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
-                                                                         lane, out, nullptr, nlp_lds, bnd,
-                                                                         NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, nullptr, nullptr, nullptr, nullptr, &ks});
-    } else if constexpr (KEEP) {
-      const NlpKeepSet ks{keep->discs + (size_t)b * keep->n_keep * 3, kwork + (size_t)b * keep->n_keep * N, keep->n_keep};
-      nlp_solve_one<false, WIND, false, false, false, false, true>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
-                                                                   lane, out, nullptr, nlp_lds, bnd,
-                                                                   NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, nullptr, nullptr, nullptr, nullptr, &ks});
+    } else if constexpr (FREE) {             // (a call of its own: through the one below, this kernel's refusal block came out reordered -- DESIGN 5.28)
+      nlp_solve_one<NLP_FREE>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr, lane, out,
+                              b == 0 ? stamps : nullptr, nlp_lds, bnd,
+                              NlpExtra{{nullptr, nullptr, nullptr}, nullptr, 0.0, 0u, nullptr, nullptr, free_rows + (size_t)b * 4, h_out + b});
     } else {
-      nlp_solve_one<false, WIND, false, MOV, VIA>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr,
-                                                  lane, out, nullptr, nlp_lds, bnd, NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, &ms, &vs});
+      [[maybe_unused]] NlpKeepSetT<F> ks{};  // (filled member by member: assigned from a braced NlpKeepMovSet the KMOV kernels spilled two more scalars)
+      if constexpr (KMOV) { ks.discs = mv->disc + (size_t)b * mv->n_mov * 2; ks.z = kwork + (size_t)b * mv->n_mov * N; ks.n = mv->n_mov; ks.ctr = ctr + (size_t)b * mv->n_mov * 2 * N; }
+      else if constexpr (KEEP) static_cast<NlpKeepSet &>(ks) = NlpKeepSet{keep->discs + (size_t)b * keep->n_keep * 3, kwork + (size_t)b * keep->n_keep * N, keep->n_keep};
+      if constexpr (FENCE) ks.fence = NlpFenceSet{fence->edges + (size_t)b * fence->n_edge * 4, fwork + (size_t)b * fence->n_edge * N, fence->n_edge};
+      nlp_solve_one<F & ~NLP_T_AT>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds,
+                                   bnd, NlpExtra{{nullptr, nullptr, nullptr}, wf, t0, 0u, &ms, &vs, nullptr, nullptr, KEEP ? &ks : nullptr});
     }
     nlp_report(b, lane, out, cost_out, feas_out, iters_out, status_out);
     nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
@@ -2371,7 +2371,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIN
 nlp_solve_wind_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
                       double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
                       int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, double t_start) {
-  nlp_handout_body<true, false, false, false>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, t_start);
+  nlp_handout_body<NLP_WIND>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, t_start);
 }
 
 // d2d_nlp_solve_free: every problem with its own free time step (constant wind, static discs, no partner)
@@ -2380,8 +2380,8 @@ nlp_solve_free_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__re
                       double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
                       int32_t *__restrict__ status_out, int32_t *queue, const double *__restrict__ free_rows, double *__restrict__ h_out,
                       unsigned long long *stamps) {
-  nlp_handout_body<false, false, false, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, nullptr, 0.0,
-                                                     nullptr, nullptr, nullptr, nullptr, nullptr, free_rows, h_out, stamps);
+  nlp_handout_body<NLP_FREE>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, nullptr, 0.0, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, free_rows, h_out, stamps);
 }
 
 // d2d_nlp_solve_keepout: outside every problem's hard discs -- the rows' constant wind or the field (WIND), the start time per problem
@@ -2391,7 +2391,7 @@ nlp_solve_keepout_kernel(int B, int N, double h, d2d_nlp_opts o, const double *_
                          double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
                          int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
                          d2d_keep_out keep, double *kwork) {
-  nlp_handout_body<WIND, false, false, true, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, 0.0,
+  nlp_handout_body<NLP_WIND * WIND | NLP_T_AT | NLP_KEEP>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, 0.0,
                                                           t_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &keep, kwork);
 }
 
@@ -2402,9 +2402,9 @@ nlp_solve_fence_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__r
                        double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
                        int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
                        d2d_keep_out keep, double *kwork, d2d_fence fence, double *fwork) {
-  nlp_handout_body<WIND, false, false, true, false, true, false, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue,
-                                                                       &wf, 0.0, t_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                                       &keep, kwork, &fence, fwork);
+  nlp_handout_body<NLP_WIND * WIND | NLP_T_AT | NLP_KEEP | NLP_FENCE>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out,
+                                                                      queue, &wf, 0.0, t_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                      nullptr, &keep, kwork, &fence, fwork);
 }
 
 // d2d_nlp_solve_keepout_moving: outside every problem's hard discs that move -- the centre planes ctr [B][n_mov][2][N] sampled ahead
@@ -2414,12 +2414,12 @@ nlp_solve_keepout_moving_kernel(int B, int N, double h, d2d_nlp_opts o, const do
                                 double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
                                 int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
                                 d2d_moving_obstacles mv, const double *ctr, double *kwork) {
-  nlp_handout_body<WIND, false, false, true, false, true, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf,
-                                                                0.0, t_start, &mv, ctr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kwork);
+  nlp_handout_body<NLP_WIND * WIND | NLP_T_AT | NLP_KMOV>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, 0.0,
+                                                          t_start, &mv, ctr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kwork);
 }
 
 // d2d_nlp_solve_moving: around the problems' moving discs -- the rows' constant wind or the field (WIND), the start time per problem.
-// nlp_handout_body<WIND, true, false, true> written out: through the body the constant-wind instantiation took 256 VGPRs for its 255
+// nlp_handout_body<NLP_WIND * WIND | NLP_T_AT | NLP_MOV> written out: through the body the constant-wind instantiation took 256 VGPRs for its 255
 // (DESIGN 5.16), so this kernel keeps its loop and shares the ticket, the track check and the report.
 template <bool WIND>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
@@ -2449,9 +2449,9 @@ nlp_solve_moving_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
     } else {
       const NlpMovSet ms{ctr + (size_t)b * mv.n_mov * 2 * N, mv.disc + (size_t)b * mv.n_mov * 2, mv.n_mov};
-      nlp_solve_one<false, WIND, false, true>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + (size_t)b * NLP_NV * N, wsb,
-                                              mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds,
-                                              o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpExtra{{nullptr, nullptr, nullptr}, &wf, t0, 0u, &ms, nullptr});
+      nlp_solve_one<NLP_WIND * WIND | NLP_MOV>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + (size_t)b * NLP_NV * N, wsb,
+                                               mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds,
+                                               o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpExtra{{nullptr, nullptr, nullptr}, &wf, t0, 0u, &ms, nullptr});
     }
     nlp_report(b, lane, out, cost_out, feas_out, iters_out, status_out);
     nlp_phase_sync();                        // (the next problem's first stores to the workspace follow this one's last loads)
@@ -2466,8 +2466,8 @@ nlp_solve_via_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__res
                      double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
                      int32_t *__restrict__ status_out, int32_t *queue, d2d_wind_field wf, const double *__restrict__ t_start,
                      d2d_moving_obstacles mv, const double *ctr, d2d_via_points via, int32_t *vwork) {
-  nlp_handout_body<WIND, true, true, true>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, &wf, 0.0, t_start,
-                                           &mv, ctr, &via, vwork);
+  nlp_handout_body<NLP_WIND * WIND | NLP_T_AT | NLP_MOV | NLP_VIA>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue,
+                                                                   &wf, 0.0, t_start, &mv, ctr, &via, vwork);
 }
 
 // A scenario of the group loop is refused: all its aircraft at once, before the workgroup's first barrier (the caller returns).
@@ -2501,9 +2501,9 @@ __device__ __forceinline__ void nlp_groups_report(int b, int r, int wave, int la
 }
 
 // does aircraft a take turns in sweeps 1..?  Fixed pair: aircraft 0 and 1; PAIRS: the aircraft with a non-empty partner set (cset)
-template <bool PAIRS>
+template <unsigned F>
 __device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
-  if constexpr (PAIRS) return ((cset >> a) & 1u) != 0u;
+  if constexpr (NlpFeatures<F>::PAIRS) return ((cset >> a) & 1u) != 0u;
   else return a < 2;
 }
 
@@ -2514,15 +2514,14 @@ __device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
 // problem.  Sweep 0 solves every aircraft uncoupled, concurrently; then the coupled aircraft take turns in index order (workgroup
 // barriers between the turns; a partner's positions are read from its W in global memory, L2-resident, which its wave does not touch
 // meanwhile) until none moved by more than tol in a sweep, or max_sweeps.  No host round trips.  prev [R][2][N] scratch.
-// One body for the four kernels below, switched at compile time:
-// WIND: every solve is the WIND instantiation -- the collision terms live in the objective and do not meet the field's terms, which
-//   live in the equalities.  The field is shared by the launch and travels as a kernel argument (scalar registers); the start time is
-//   the SCENARIO's (t_start [R], device memory: the mission chain computes it on the device), wave-uniform.  A scenario whose start
-//   time is not finite is refused before its first solve.
+// One body for the group kernels below, switched at compile time by F.  What the solve does with each member stands at NlpFeatures;
+// what the members mean HERE, to a scenario:
+// WIND: the field is shared by the launch and travels as a kernel argument (scalar registers); the start time is the SCENARIO's
+//   (t_start [R], device memory: the mission chain computes it on the device), wave-uniform.  A scenario whose start time is not
+//   finite is refused before its first solve.
 // PAIRS: any set of coupled pairs instead of the pair (0, 1) when the row's KCOL > 0.  D2D_SC_PMASK of aircraft a's row is its
-//   partner set, bit j = aircraft j of the same scenario; each turn solves against ALL partners, which nlp_exp_terms reads through a
-//   rolled loop over the set bits of the mask in a scalar register.  With the masks of the pair (0, 1) every solve, sum and barrier is
-//   that of the fixed pair (tests/test_gpu_collision_pairs.py: equal bit for bit).  The masks of a scenario are checked before its
+//   partner set, bit j = aircraft j of the same scenario; each turn solves against ALL partners.  With the masks of the pair (0, 1)
+//   every solve, sum and barrier is that of the fixed pair (tests/test_gpu_collision_pairs.py: equal bit for bit).  The masks are checked before the scenario's
 //   first solve, by every wavefront alike (scalar loads): an entry that is no integer in [0, 2^n_ac), a self bit or a bit j whose
 //   aircraft j does not name a back -- the term of a pair belongs to both objectives or to none -- refuses the whole scenario
 //   (D2D_ST_NONFINITE, cost = feas = NaN, sweeps = 0, W untouched), like a non-finite start time: no mask ever indexes outside the
@@ -2531,8 +2530,7 @@ __device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
 //   ctr [R][n_mov][2][N] sampled at t_start[r] + i h ahead of this launch.  The tracks are checked before the first solve, by every
 //   wavefront alike; an unusable track, or a start time that is not finite while discs move, refuses the scenario like a bad mask.
 // VIA (d2d_nlp_solve_groups_via): every AIRCRAFT has its own pins, via->pts [R n_ac][n_via][5], and its own plane vwork [R n_ac][N].  The
-//   pins of all aircraft of the scenario are checked before the first solve, by every wavefront alike: one unusable row refuses the
-//   scenario, as a bad mask does.  The partners' terms still count at a pinned node.
+//   pins of all aircraft are checked before the first solve, by every wavefront alike: one unusable row refuses the scenario.
 // The pointer parameters of the body and of its two helpers carry no __restrict__ (the kernels' do): with it the fixed-pair kernel
 // went from 256 VGPRs / 624 B of scratch to 255 / 608 and the field kernel from 752 B to 784.
 // Registers: 512 threads per workgroup are 8 wavefronts on 4 SIMDs, two per SIMD, so a wavefront gets at most 256 of the SIMD's 512
@@ -2545,16 +2543,16 @@ __device__ __forceinline__ bool nlp_takes_turns(unsigned cset, int a) {
 //   and in every turn; fwork [R n_ac][n_edge][N] the planes of the duals, every aircraft its own.  No hard discs.  An unusable edge, or an
 //   aircraft whose end pose lies on or outside an edge or that the start rule cannot place inside, refuses the SCENARIO -- every wavefront
 //   checks every aircraft, before the first barrier, as KMOV does.  A later turn that cannot start refuses that aircraft alone.
-template <bool WIND, bool PAIRS, bool MOV = false, bool VIA = false, bool KMOV = false, bool FENCE = false>
+template <unsigned F>
 __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h, const d2d_nlp_opts &o, int max_sweeps, double tol,
                                                 const double *scen, double *W, double *work, double *mult, double *prev,
-                                                double *cost_out, double *feas_out, int32_t *iters_out,
-                                                int32_t *status_out, int32_t *sweeps_out, double *moved_out,
-                                                const d2d_wind_field *wf, const double *t_start,
-                                                const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr,
-                                                const d2d_via_points *via = nullptr, int32_t *vwork = nullptr,
-                                                [[maybe_unused]] double *kwork = nullptr,
+                                                double *cost_out, double *feas_out, int32_t *iters_out, int32_t *status_out, int32_t *sweeps_out,
+                                                double *moved_out, const d2d_wind_field *wf, const double *t_start,
+                                                const d2d_moving_obstacles *mv = nullptr, const double *ctr = nullptr, const d2d_via_points *via = nullptr,
+                                                int32_t *vwork = nullptr, [[maybe_unused]] double *kwork = nullptr,
                                                 [[maybe_unused]] const d2d_fence *fence = nullptr, [[maybe_unused]] double *fwork = nullptr) {
+  NLP_FEATURES(F);
+  static_assert(!(MODEL || FREE || T_AT) && (!KEEP || KMOV), "the group loop holds moving hard discs or a polygon, under the structured objective");
   __shared__ double moved_s[PAIRS ? 8 : 2];
   extern __shared__ __attribute__((aligned(16))) double nlp_lds[];
   const int r = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -2624,12 +2622,12 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
   if constexpr (FENCE) {
     kfs.fence = NlpFenceSet{fence->edges + (size_t)r * fence->n_edge * 4, fwork + (size_t)b * fence->n_edge * N, fence->n_edge};
     if (!bad) {
-      NlpFenceProb fp;                       // (nlp_fence_bad<false> reads its fence alone)
+      NlpFenceProb fp;                       // (nlp_fence_bad<NLP_FENCE> reads its fence alone)
       fp.fence = kfs.fence;
       for (int a = 0; a < n_ac; ++a) {
         const size_t ba = (size_t)r * n_ac + a;
         const NlpScen sa = nlp_load_scen(scen + ba * D2D_SCEN_STRIDE, o, o.bounds ? o.bounds + ba * 4 : nullptr);
-        bad = bad || nlp_fence_bad<false>(sa, fp, W + ba * NLP_NV * N, N, lane);
+        bad = bad || nlp_fence_bad<NLP_FENCE>(sa, fp, W + ba * NLP_NV * N, N, lane);
       }
     }
     __syncthreads();                         // (every wavefront has read every aircraft's start before the first solve writes one)
@@ -2653,7 +2651,7 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
   NlpExtra ex{{nullptr, nullptr, nullptr}, wf, t0, 0u, msp, vsp};      // sweep 0: no partner
   if constexpr (KMOV) ex.keep = &kms;
   if constexpr (FENCE) ex.keep = &kfs;
-  nlp_solve_one<false, WIND, PAIRS, MOV, VIA, false, KMOV, KMOV, FENCE>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
+  nlp_solve_one<F>(N, h, o, sc, PAIRS ? Wr : nullptr, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
   ex.pmask = pmask;
   iters_total += out.iters;
   if (threadIdx.x < (PAIRS ? 8 : 2)) moved_s[threadIdx.x] = 0.0;
@@ -2666,12 +2664,12 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
     const int n_turns = PAIRS ? n_ac : 2;
     for (sweep = 1; sweep <= max_sweeps; ++sweep) {
       for (int turn = 0; turn < n_turns; ++turn) {
-        if (!nlp_takes_turns<PAIRS>(cset, turn)) continue;
+        if (!nlp_takes_turns<F>(cset, turn)) continue;
         if (wave == turn) {
           // fixed pair: the partner's x and y planes; PAIRS: the scenario's W and the set
           const double *pw = PAIRS ? Wr : W + (size_t)(r * n_ac + (1 - turn)) * NLP_NV * N;
           for (int i = lane; i < 2 * N; i += 64) pv[i] = Wb[i];
-          nlp_solve_one<false, WIND, PAIRS, MOV, VIA, false, KMOV, KMOV, FENCE>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
+          nlp_solve_one<F>(N, h, o, sc, pw, Wb, wsb, mb, lane, out, nullptr, ldsw, bnd, ex);
           iters_total += out.iters;
           double m = 0.0;
           for (int i = lane; i < 2 * N; i += 64) m = fmax(m, fabs(Wb[i] - pv[i]));
@@ -2692,7 +2690,7 @@ __device__ __forceinline__ void nlp_groups_body(int R, int n_ac, int N, double h
     }
     if (sweep > max_sweeps) sweep = max_sweeps;
     // not settled after the last sweep: the coupled aircraft are reported as such (the inner solves each converged, the alternation did not)
-    if (moved > tol && nlp_takes_turns<PAIRS>(cset, wave) && out.status == D2D_ST_CONVERGED) out.status = D2D_ST_MAXITER;
+    if (moved > tol && nlp_takes_turns<F>(cset, wave) && out.status == D2D_ST_CONVERGED) out.status = D2D_ST_MAXITER;
   }
   nlp_groups_report(b, r, wave, lane, out, iters_total, sweep, moved, cost_out, feas_out, iters_out, status_out, sweeps_out, moved_out);
 }
@@ -2706,8 +2704,8 @@ nlp_groups_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_swee
                   double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
                   int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
                   double *__restrict__ moved_out) {
-  nlp_groups_body<false, false>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
-                                sweeps_out, moved_out, nullptr, nullptr);
+  nlp_groups_body<0u>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out, sweeps_out, moved_out,
+                      nullptr, nullptr);
 }
 
 // d2d_nlp_solve_groups_wind: the pair (0, 1) in a field
@@ -2716,8 +2714,8 @@ nlp_groups_wind_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max
                        double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
                        int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
                        double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
-  nlp_groups_body<true, false>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
-                               sweeps_out, moved_out, &wf, t_start);
+  nlp_groups_body<NLP_WIND>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out, sweeps_out,
+                            moved_out, &wf, t_start);
 }
 
 // d2d_nlp_solve_groups_pairs: the pairs of the masks; WIND selects the rows' constant wind or the field
@@ -2727,8 +2725,8 @@ nlp_groups_pairs_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int ma
                         double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
                         int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
                         double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start) {
-  nlp_groups_body<WIND, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
-                              sweeps_out, moved_out, &wf, t_start);
+  nlp_groups_body<NLP_WIND * WIND | NLP_PAIRS>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
+                                               sweeps_out, moved_out, &wf, t_start);
 }
 
 // d2d_nlp_solve_groups_moving: the pairs of the masks around the scenarios' moving discs; WIND as above
@@ -2739,8 +2737,8 @@ nlp_groups_moving_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int m
                          int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
                          double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start, d2d_moving_obstacles mv,
                          const double *__restrict__ ctr) {
-  nlp_groups_body<WIND, true, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
-                                    sweeps_out, moved_out, &wf, t_start, &mv, ctr);
+  nlp_groups_body<NLP_WIND * WIND | NLP_PAIRS | NLP_MOV>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out,
+                                                         status_out, sweeps_out, moved_out, &wf, t_start, &mv, ctr);
 }
 
 // d2d_nlp_solve_groups_keepout: the pairs of the masks, every aircraft outside the scenario's hard moving discs; WIND as above
@@ -2751,8 +2749,8 @@ nlp_groups_keepout_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int 
                           int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
                           double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start, d2d_moving_obstacles mv,
                           const double *__restrict__ ctr, double *kwork) {
-  nlp_groups_body<WIND, true, false, false, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out,
-                                                  status_out, sweeps_out, moved_out, &wf, t_start, &mv, ctr, nullptr, nullptr, kwork);
+  nlp_groups_body<NLP_WIND * WIND | NLP_PAIRS | NLP_KMOV>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out,
+                                                          status_out, sweeps_out, moved_out, &wf, t_start, &mv, ctr, nullptr, nullptr, kwork);
 }
 
 // d2d_nlp_solve_groups_fence: the pairs of the masks, every aircraft inside the scenario's convex polygon; WIND as above
@@ -2762,9 +2760,9 @@ nlp_groups_fence_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int ma
                         double *work, double *mult, double *prev, double *__restrict__ cost_out, double *__restrict__ feas_out,
                         int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
                         double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start, d2d_fence fence, double *fwork) {
-  nlp_groups_body<WIND, true, false, false, false, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out,
-                                                         status_out, sweeps_out, moved_out, &wf, t_start, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                         &fence, fwork);
+  nlp_groups_body<NLP_WIND * WIND | NLP_PAIRS | NLP_FENCE>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out,
+                                                           status_out, sweeps_out, moved_out, &wf, t_start, nullptr, nullptr, nullptr, nullptr,
+                                                           nullptr, &fence, fwork);
 }
 
 // d2d_nlp_solve_groups_via: the pairs of the masks around the scenarios' moving discs, through every aircraft's own pins; WIND as above
@@ -2775,8 +2773,8 @@ nlp_groups_via_kernel(int R, int n_ac, int N, double h, d2d_nlp_opts o, int max_
                       int32_t *__restrict__ iters_out, int32_t *__restrict__ status_out, int32_t *__restrict__ sweeps_out,
                       double *__restrict__ moved_out, d2d_wind_field wf, const double *__restrict__ t_start, d2d_moving_obstacles mv,
                       const double *__restrict__ ctr, d2d_via_points via, int32_t *vwork) {
-  nlp_groups_body<WIND, true, true, true>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out, iters_out, status_out,
-                                          sweeps_out, moved_out, &wf, t_start, &mv, ctr, &via, vwork);
+  nlp_groups_body<NLP_WIND * WIND | NLP_PAIRS | NLP_MOV | NLP_VIA>(R, n_ac, N, h, o, max_sweeps, tol, scen, W, work, mult, prev, cost_out, feas_out,
+                                                                   iters_out, status_out, sweeps_out, moved_out, &wf, t_start, &mv, ctr, &via, vwork);
 }
 
 // d2d_nlp_solve_model: the collocation NLP under the quadratic objective model of a cost that only the host can evaluate (a user's
@@ -2796,7 +2794,7 @@ nlp_model_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restric
   const size_t pl = (size_t)b * N;
   const NlpModel md{m.g + pl * NLP_NV, m.H + pl * 15, m.Wc + pl * NLP_NV};
   NlpOut out;
-  nlp_solve_one<true>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + pl * NLP_NV, work + pl * WS_TOTAL, mult ? mult + pl * 3 : nullptr,
+  nlp_solve_one<NLP_MODEL>(N, h, o, scen + (size_t)b * D2D_SCEN_STRIDE, nullptr, W + pl * NLP_NV, work + pl * WS_TOTAL, mult ? mult + pl * 3 : nullptr,
                       lane, out, nullptr, nlp_lds, o.bounds ? o.bounds + (size_t)b * 4 : nullptr, NlpExtra{md});
   if (lane == 0) {
     cost_out[b] = out.cost;
