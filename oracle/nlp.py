@@ -280,31 +280,95 @@ def _merit(pb, W, mu, rho, mub, hasL, hasU):
 BANKMAX_VALUE_TOL = 1e-7     # include/d2d.h D2D_NLP_BANKMAX_VALUE_TOL
 
 
-def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER_MAX, feas_tol=FEAS_TOL, opt_tol=OPT_TOL):
-    """Equalities by an augmented Lagrangian (scaled multiplier estimate mu, penalty rho), bounds by a primal-dual
-    log barrier (parameter mub, duals zL / zU), both driven by ONE outer loop; the inner problem is solved by damped
-    Newton steps on the block-tridiagonal system (Lagrangian Hessian + barrier diagonal), fraction-to-the-boundary
-    rule and a backtracking line search on the barrier-AL merit function.
-    Returns W, info (cost, feas, outer, inner, status, mult, path)."""
+class Plain:
+    """An oracle Problem in its own constant wind, as the problem object solve_general() asks for."""
+
+    def __init__(self, pb):
+        self.pb = pb
+
+    def constraints(self, W):
+        return constraints(self.pb, W)
+
+    def normal_equations(self, W, mu, rho):
+        return _normal_equations(self.pb, W, mu, rho)
+
+    def merit(self, W, mu, rho, mub, hasL, hasU):
+        return _merit(self.pb, W, mu, rho, mub, hasL, hasU)
+
+    def cost(self, W):
+        return cost(self.pb, W)
+
+
+def _box_push(w, lo, hi, hasL, hasU):
+    """w strictly inside its box: 1 % of max(1, |w|), at most 1 % of the box's width, from every finite bound."""
+    width = np.where(hasL & hasU, hi - lo, np.inf)
+    kap = np.minimum(1e-2 * np.maximum(1.0, np.abs(w)), 1e-2 * width)
+    w = np.where(hasL, np.maximum(w, lo + kap), w)
+    return np.where(hasU, np.minimum(w, hi - kap), w)
+
+
+def interior_start(pb, W0):
+    """solve_general()'s opening move: a copy of W0 with the fixed variables set and the others pushed strictly inside the box."""
     fixed, hasL, hasU = _barrier_sets(pb)
-    free = ~fixed
     W = np.asarray(W0, float).copy()
     W[fixed] = pb.lo[fixed]
-    # push the start strictly inside the box
-    width = np.where(hasL & hasU, pb.hi - pb.lo, np.inf)
-    kap = np.minimum(1e-2 * np.maximum(1.0, np.abs(W)), 1e-2 * width)
-    W = np.where(hasL, np.maximum(W, pb.lo + kap), W)
-    W = np.where(hasU, np.minimum(W, pb.hi - kap), W)
+    return _box_push(W, pb.lo, pb.hi, hasL, hasU)
+
+
+def _merit_general(prob, live, W, u, mu, rho, mub, hasL, hasU):
+    """The problem's barrier-AL merit function plus every family's share, in order; +inf as soon as one of them is."""
+    m = prob.merit(W, *u, mu, rho, mub, hasL, hasU)
+    for f in live:
+        if not np.isfinite(m):
+            return m
+        m = m + f.barrier_value(W, mub)
+    return m
+
+
+def solve_general(prob, W0, families=(), border=None, started=False, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER_MAX,
+                  feas_tol=FEAS_TOL, opt_tol=OPT_TOL):
+    """THE solve loop: every CPU statement of the collocation solver is a call of it (csrc/nlp_kernels.hip states it once too).
+    Equalities by an augmented Lagrangian (scaled multiplier estimate mu, penalty rho), bounds by a primal-dual log barrier (parameter
+    mub, duals zL / zU), both driven by ONE outer loop; the inner problem is solved by damped Newton steps on the block-tridiagonal
+    system (Lagrangian Hessian + barrier diagonal), fraction-to-the-boundary rule and a backtracking line search on the barrier-AL
+    merit function.
+
+    prob      `pb` (an oracle Problem: N, lo, hi, bank_max) and four methods: constraints(W), normal_equations(W, mu, rho) -> half
+              gradient g (N, 5) and half Hessian blocks D, E; merit(W, mu, rho, mub, hasL, hasU); cost(W), the value reported.  Plain
+              above, or a statement's own (tests/nlp_wind_ref.py FieldProblem, tests/nlp_model_ref.py ModelProblem).
+    families  node-inequality families g > 0 on (x, y) of the interior nodes 1 .. N-2, each with a dual z (n, N-2) treated like the box
+              duals; they contribute in the order given, and one with len() == 0 contributes nothing.  A family supplies g(W) (n, N-2);
+              barrier_terms(W, z, mub) -> rhs (N, 2) [full convention], stationarity (N, 2), half-convention blocks (N, 2, 2);
+              barrier_value(W, mub), its share of the merit (+inf when a g <= 0); ratio(W, dw, tau), its fraction-to-the-boundary
+              ratios for the step dw; dual_step(W, dw, z, mub).  The duals start at mub / g, take the step length of the ratio test on
+              all duals and are clipped to [mub / (1e10 g), 1e10 mub / g].  (tests/nlp_keepout_ref.py Discs, tests/nlp_fence_ref.py Edges.)
+    border    None, or one more scalar unknown u in a box with two duals (tests/nlp_free_ref.py Border: u = 1 / h).  prob's methods
+              then take u after W, normal_equations returns the u row (g_u, b, d_u) after E, and the Newton system is the bordered one.
+    started   W0 is interior_start()'s result, moved by the caller's start rules: do not push it again.
+
+    Returns W, info (cost, feas, outer, inner, status, rho, mult, zL, zU, path) and the state the loop ended in (mu, mub, z: the
+    families' duals in the order given).  path holds, per accepted Newton step, its length a, the largest change it made, the number of
+    times its damping was raised eightfold and the number of halvings of its line search."""
+    pb = prob.pb
+    fixed, hasL, hasU = _barrier_sets(pb)
+    free = ~fixed
+    W = np.asarray(W0, float).copy() if started else interior_start(pb, W0)
+    live = [(k, f) for k, f in enumerate(families) if len(f)]        # (an empty family adds nothing at all, not even zeros)
+    fams = [f for _, f in live]
+    u = () if border is None else (border.u,)           # what prob's methods take after W
     mu = np.zeros((pb.N - 1, 3)); rho = rho0
     mub = MUB0
     zL = np.where(hasL, mub / np.where(hasL, W - pb.lo, 1.0), 0.0)
     zU = np.where(hasU, mub / np.where(hasU, pb.hi - W, 1.0), 0.0)
+    z = [mub / f.g(W) for f in families]
+    if border is not None:
+        border.start_duals(mub)
     lam = LAM0
     feas_prev = np.inf
     total_inner = 0
     status = 2
     n_stalled = 0
-    path = []                       # per accepted step: its length, the largest |dW| it made, eightfold raises of its damping, halvings of its length
+    path = []
     if pb.bank_max:                 # the value test of the max mode needs a window of its own length (include/d2d.h D2D_NLP_BANKMAX_BATCHES)
         inner_max, outer_max = BANKMAX_BATCHES * inner_max, (outer_max + BANKMAX_BATCHES - 1) // BANKMAX_BATCHES
     for outer in range(1, outer_max + 1):
@@ -313,11 +377,18 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
         for it in range(inner_max):
             total_inner += 1
             sl = np.where(hasL, W - pb.lo, 1.0); su = np.where(hasU, pb.hi - W, 1.0)
-            g, D, E = _normal_equations(pb, W, mu, rho)          # half gradient / half Hessian of the AL function
+            g, D, E, *row_u = prob.normal_equations(W, *u, mu, rho)          # half gradient / half Hessian of the AL function
             # barrier KKT error of the inner problem: stationarity with the duals + complementarity
             stat = np.where(free, 2.0 * g - zL + zU, 0.0)
             comp = max(float(np.abs(np.where(hasL, zL * sl - mub, 0.0)).max()), float(np.abs(np.where(hasU, zU * su - mub, 0.0)).max()))
+            terms = [f.barrier_terms(W, z[k], mub) for k, f in live]
+            for (k, f), (_, fst, _) in zip(live, terms):
+                stat[1:-1, :2] += fst[1:-1]
+                comp = max(comp, float(np.abs(z[k] * f.g(W) - mub).max()))
             err = max(float(np.abs(stat).max()), comp)
+            if border is not None:
+                g_u, b_u, d_u = row_u
+                err = max(err, *border.kkt_error(g_u, mub))
             if err <= tol_in:
                 break
             # primal-dual Newton step: (H + Sigma) dw = -(grad - mub / sl + mub / su)
@@ -326,17 +397,26 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
             Dh = D.copy()
             idx = np.arange(NV)
             Dh[:, idx, idx] += 0.5 * sig                        # (half convention: D holds H / 2)
-            phi0 = _merit(pb, W, mu, rho, mub, hasL, hasU)
+            for frhs, _, fblk in terms:
+                rhs[1:-1, :2] += frhs[1:-1]
+                Dh[1:-1, :2, :2] += fblk[1:-1]
+            if border is not None:
+                r_u, d0 = border.row(g_u, d_u, mub)
+            phi0 = _merit_general(prob, fams, W, u, mu, rho, mub, hasL, hasU)
             if phi_first is None:
                 phi_first = phi_last = phi0
             accepted = False
             raised = 0
             for _ in range(30):
                 try:
-                    dw = _solve_block_tridiag(Dh, E, 0.5 * rhs, free, lam)
+                    if border is None:
+                        dw = _solve_block_tridiag(Dh, E, 0.5 * rhs, free, lam)
+                    else:
+                        dw, du = border.solve(Dh, E, 0.5 * rhs, free, lam, b_u, d0 + lam * max(abs(d0), 1e-12), 0.5 * r_u)
                 except np.linalg.LinAlgError:
                     lam = min(lam * 8.0, LAM_MAX); raised += 1; continue
-                dphi = -float(np.sum(rhs * dw))                  # directional derivative of the merit function (< 0: descent)
+                # directional derivative of the merit function (< 0: descent)
+                dphi = -float(np.sum(rhs * dw)) if border is None else -(float(np.sum(rhs * dw)) + r_u * du)
                 if not dphi < 0.0:
                     lam = min(lam * 8.0, LAM_MAX); raised += 1; continue
                 # fraction to the boundary
@@ -345,11 +425,16 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
                     aL = np.where(hasL & (dw < 0), -tau * sl / dw, np.inf)
                     aU = np.where(hasU & (dw > 0), tau * su / dw, np.inf)
                 amax = min(1.0, float(aL.min()), float(aU.min()))
+                for f in fams:
+                    amax = min(amax, float(f.ratio(W, dw, tau).min()))
+                if border is not None:
+                    amax = min(amax, border.ratio(du, tau))
                 a = amax
                 ok = False
                 for _ls in range(8):
                     Wt = W + a * dw
-                    pt = _merit(pb, Wt, mu, rho, mub, hasL, hasU)
+                    ut = () if border is None else (border.u + a * du,)
+                    pt = _merit_general(prob, fams, Wt, ut, mu, rho, mub, hasL, hasU)
                     if np.isfinite(pt) and pt <= phi0 + 1e-4 * a * dphi:
                         ok = True
                         break
@@ -361,7 +446,16 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
                         azL = np.where(hasL & (dzL < 0), -tau * zL / dzL, np.inf)
                         azU = np.where(hasU & (dzU < 0), -tau * zU / dzU, np.inf)
                     az = min(1.0, float(azL.min()), float(azU.min()))
-                    path.append((a, float(np.abs(Wt - W).max()), raised, _ls))
+                    dz = {k: f.dual_step(W, dw, z[k], mub) for k, f in live}
+                    for k, _ in live:
+                        with np.errstate(divide='ignore', invalid='ignore'):
+                            az = min(az, float(np.where(dz[k] < 0, -tau * z[k] / dz[k], np.inf).min()))
+                    moved = float(np.abs(Wt - W).max())
+                    if border is not None:
+                        dzu, azu = border.dual_step(du, mub, tau)
+                        az = min(az, azu)
+                        moved = max(moved, abs(ut[0] - border.u))
+                    path.append((a, moved, raised, _ls))
                     W = Wt
                     phi_last = pt
                     zL = zL + az * dzL; zU = zU + az * dzU
@@ -369,16 +463,22 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
                     slp = np.where(hasL, W - pb.lo, 1.0); sup = np.where(hasU, pb.hi - W, 1.0)
                     zL = np.where(hasL, np.clip(zL, mub / (1e10 * slp), 1e10 * mub / slp), 0.0)
                     zU = np.where(hasU, np.clip(zU, mub / (1e10 * sup), 1e10 * mub / sup), 0.0)
+                    for k, f in live:
+                        gn = f.g(W)
+                        z[k] = np.clip(z[k] + az * dz[k], mub / (1e10 * gn), 1e10 * mub / gn)
+                    if border is not None:
+                        border.accept(ut[0], az, dzu, mub)
+                        u = ut
                     lam = max(lam / 3.0, LAM_MIN) if a == amax else lam
                     accepted = True
                     break
                 lam = min(lam * 4.0, LAM_MAX)
             if not accepted:
                 break
-        c = constraints(pb, W)
+        c = prob.constraints(W, *u)
         feas = float(np.abs(c).max())
         if verbose:
-            print(f'outer {outer:2d} rho {rho:.1e} mub {mub:.1e} inner {it + 1:3d} cost {cost(pb, W):.10f} feas {feas:.2e} err {err:.2e} lam {lam:.1e}')
+            print(f'outer {outer:2d} rho {rho:.1e} mub {mub:.1e} inner {it + 1:3d} cost {prob.cost(W, *u):.10f} feas {feas:.2e} err {err:.2e} lam {lam:.1e}')
         if feas <= feas_tol and mub <= MUB_MIN * 1.0001 and err <= tol_in:
             status = 1
             break
@@ -404,8 +504,16 @@ def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER
             mu = mu / RHO_GROW; rho *= RHO_GROW              # (mu is the multiplier divided by 2 rho: rescale with rho)
         feas_prev = feas
         mub = max(MUB_MIN, min(0.2 * mub, mub ** 1.5))
-    return W, dict(cost=cost(pb, W), feas=float(np.abs(constraints(pb, W)).max()), outer=outer, inner=total_inner, status=status,
-                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU, path=path)
+    info = dict(cost=prob.cost(W, *u), feas=float(np.abs(prob.constraints(W, *u)).max()), outer=outer, inner=total_inner, status=status,
+                rho=rho, mult=2 * rho * mu, zL=zL, zU=zU, path=path)
+    return W, info, dict(mu=mu, mub=mub, z=z)
+
+
+def solve(pb, W0, verbose=False, rho0=RHO0, inner_max=INNER_MAX, outer_max=OUTER_MAX, feas_tol=FEAS_TOL, opt_tol=OPT_TOL):
+    """solve_general() of the Problem in its own constant wind: no families, no border.
+    Returns W, info (cost, feas, outer, inner, status, rho, mult, zL, zU, path)."""
+    return solve_general(Plain(pb), W0, verbose=verbose, rho0=rho0, inner_max=inner_max, outer_max=outer_max, feas_tol=feas_tol,
+                         opt_tol=opt_tol)[:2]
 
 
 def _apply(D, E, s):

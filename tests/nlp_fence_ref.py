@@ -1,7 +1,7 @@
 """CPU statement of the collocation solver INSIDE a convex polygon (include/d2d.h d2d_nlp_solve_fence; test infrastructure only).
 
-It is tests/nlp_keepout_ref.py's loop -- oracle/nlp.py's augmented Lagrangian, primal-dual log barrier and damped Newton steps, with the
-hard discs of d2d_nlp_solve_keepout -- with one more family of inequalities: for every interior node i (1 .. N-2) and edge
+It is tests/nlp_keepout_ref.py's statement -- oracle/nlp.py's augmented Lagrangian, primal-dual log barrier and damped Newton steps, with
+the hard discs of d2d_nlp_solve_keepout -- with one more family of node inequalities: for every interior node i (1 .. N-2) and edge
 k = (ax, ay, b, kap), a the outward unit normal, a row with ax = ay = 0 absent,
 
     g_ik = b - (ax x_i + ay y_i) > 0,        grad g = -a,  no second derivative,   s = the step of (x_i, y_i)
@@ -21,7 +21,9 @@ each with a dual z_ik > 0 that is treated exactly like the box duals and the dis
                  g <= 0 (edge or disc) after the start rules -- and what nlp_keepout_ref refuses: status 3, NaN cost, W untouched
 
 The feasible set of the edges is convex: the polyline between feasible nodes is feasible (segment_inside; no chord inflation).
-With no edge present solve() is nlp_keepout_ref.solve bit for bit (it calls it), and so oracle.nlp.solve without discs.
+The loop is oracle.nlp.solve_general with two families, nlp_keepout_ref.Discs before the family Edges that this file supplies, beside the
+edges' start rule and refusals.  With no edge present solve() hands the problem to nlp_keepout_ref.solve, and is so oracle.nlp.solve
+without discs.
 """
 import functools
 
@@ -53,30 +55,12 @@ def segment_inside(edges, p, q):
 
 
 def _disc_rule(pb, W, discs):
-    """nlp_keepout_ref.start's loop over the discs, without its closing box push (the edges' rule comes first)."""
-    W = W.copy()
-    leg = pb.p1[:2] - pb.p0[:2]; ll = float(np.sqrt(leg[0] * leg[0] + leg[1] * leg[1]))
-    nrm = (-leg[1] / ll, leg[0] / ll) if ll > 0.0 else (0.0, 1.0)
-    for i in range(1, pb.N - 1):
-        x, y = W[i, 0], W[i, 1]
-        for _pass in range(2):
-            for cx, cy, R in discs:
-                if not R > 0.0:
-                    continue
-                Rt = R * (1.0 + K.PUSH)
-                dx, dy = x - cx, y - cy
-                d2 = dx * dx + dy * dy
-                if d2 - R * R <= Rt * Rt - R * R:
-                    dn = np.sqrt(d2)
-                    ux, uy = nrm if dn < 1e-12 * R else (dx / dn, dy / dn)
-                    x, y = cx + Rt * ux, cy + Rt * uy
-        W[i, 0], W[i, 1] = x, y
-    return W
+    """nlp_keepout_ref's rule for the discs, without its closing box push (the edges' rule comes first)."""
+    return K.disc_rule(pb, W, *K.constant_centres(discs, pb.N))
 
 
 def start(pb, W, discs, edges):
     """The start rules on a W that has had the box push: the discs' rule, the edges' rule, then the box push again on x and y."""
-    _, hasL, hasU = nlp._barrier_sets(pb)
     W = _disc_rule(pb, W, discs) if len(discs) else W.copy()
     for i in range(1, pb.N - 1):
         x, y = W[i, 0], W[i, 1]
@@ -89,8 +73,7 @@ def start(pb, W, discs, edges):
                     t = kap - g
                     x, y = x - t * ax, y - t * ay
         W[i, 0], W[i, 1] = x, y
-    W[:, :2] = K._box_push(W[:, :2], pb.lo[:, :2], pb.hi[:, :2], hasL[:, :2], hasU[:, :2])
-    return W
+    return K.push_xy(pb, W)
 
 
 def refused(pb, discs, edges, Wp):
@@ -125,7 +108,7 @@ def barrier_value(W, act, mub):
 
 
 def barrier_terms(W, act, zf, mub):
-    """What solve() adds for the edges at (W, zf): rhs (N, 2) [full convention, the negative merit gradient with mub / g], the stationarity
+    """What the loop adds for the edges at (W, zf): rhs (N, 2) [full convention, the negative merit gradient with mub / g], the stationarity
     term (N, 2) and the half-convention 2x2 blocks (N, 2, 2)."""
     N = len(W)
     g = g_values(W[1:-1], act)
@@ -139,11 +122,43 @@ def barrier_terms(W, act, zf, mub):
     return rhs, st, blk
 
 
-def _merit(prob, W, mu, rho, mub, hasL, hasU, dact, fact):
-    m = K._keep_merit(prob, W, mu, rho, mub, hasL, hasU, dact)
-    if not len(fact) or not np.isfinite(m):
-        return m
-    return m + barrier_value(W, fact, mub)
+class Edges:
+    """The family of edges that oracle.nlp.solve_general asks for: the present rows of edges (n, 4)."""
+
+    def __init__(self, edges):
+        self.n = len(edges)
+        self.ja = np.flatnonzero(present(edges))
+        self.act = edges[self.ja]
+
+    def __len__(self):
+        return len(self.ja)
+
+    def g(self, W):
+        return g_values(W[1:-1], self.act)
+
+    def barrier_value(self, W, mub):
+        return barrier_value(W, self.act, mub)
+
+    def barrier_terms(self, W, z, mub):
+        return barrier_terms(W, self.act, z, mub)
+
+    def _as(self, dw):
+        """a.s at the interior nodes"""
+        return self.act[:, 0, None] * dw[1:-1, 0] + self.act[:, 1, None] * dw[1:-1, 1]
+
+    def ratio(self, W, dw, tau):
+        as_ = self._as(dw)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(as_ > 0, tau * self.g(W) / as_, np.inf)
+
+    def dual_step(self, W, dw, z, mub):
+        return (mub + z * self._as(dw)) / self.g(W) - z
+
+    def scatter(self, z, N):
+        """the duals (n_present, N - 2) -> zf (n, N): 0 at the end nodes and for absent edges"""
+        zfull = np.zeros((self.n, N))
+        zfull[self.ja, 1:-1] = z
+        return zfull
 
 
 def solve(prob, W0, discs, edges, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX, feas_tol=nlp.FEAS_TOL, opt_tol=nlp.OPT_TOL):
@@ -152,163 +167,20 @@ def solve(prob, W0, discs, edges, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_
     pb = prob.pb
     discs = np.asarray(discs, float).reshape(-1, 3)
     edges = np.asarray(edges, float).reshape(-1, 4)
+    schedule = dict(rho0=rho0, inner_max=inner_max, outer_max=outer_max, feas_tol=feas_tol, opt_tol=opt_tol)
     if not len(edges) or (np.isfinite(edges).all() and not present(edges).any()):
-        W, info = K.solve(prob, W0, discs, rho0=rho0, inner_max=inner_max, outer_max=outer_max, feas_tol=feas_tol, opt_tol=opt_tol)
+        W, info = K.solve(prob, W0, discs, **schedule)
         info['zf'] = np.zeros((len(edges), pb.N))
         return W, info
-    fixed, hasL, hasU = nlp._barrier_sets(pb)
-    free = ~fixed
-    W = np.asarray(W0, float).copy()
-    W[fixed] = pb.lo[fixed]
-    width = np.where(hasL & hasU, pb.hi - pb.lo, np.inf)
-    kap = np.minimum(1e-2 * np.maximum(1.0, np.abs(W)), 1e-2 * width)
-    W = np.where(hasL, np.maximum(W, pb.lo + kap), W)
-    W = np.where(hasU, np.minimum(W, pb.hi - kap), W)
+    W = nlp.interior_start(pb, W0)
     if refused(pb, discs, edges, W):
         return np.asarray(W0, float).copy(), dict(cost=np.nan, feas=np.nan, outer=0, inner=0, status=ST_NONFINITE, path=[],
                                                   zk=np.zeros((len(discs), pb.N)), zf=np.zeros((len(edges), pb.N)))
     W = start(pb, W, discs, edges)
-    ia = np.flatnonzero(discs[:, 2] > 0.0) if len(discs) else np.zeros(0, int)
-    dact = discs[ia]
-    K_ = len(dact) > 0
-    ja = np.flatnonzero(present(edges))
-    fact = edges[ja]
-    fax, fay = fact[:, 0, None], fact[:, 1, None]
-    mu = np.zeros((pb.N - 1, 3)); rho = rho0
-    mub = nlp.MUB0
-    zL = np.where(hasL, mub / np.where(hasL, W - pb.lo, 1.0), 0.0)
-    zU = np.where(hasU, mub / np.where(hasU, pb.hi - W, 1.0), 0.0)
-    zk = mub / K.g_values(W[1:-1], dact)[0] if K_ else np.zeros((0, pb.N - 2))
-    zf = mub / g_values(W[1:-1], fact)
-    lam = nlp.LAM0
-    feas_prev = np.inf
-    total_inner = 0
-    status = 2
-    n_stalled = 0
-    path = []
-    if pb.bank_max:
-        inner_max, outer_max = nlp.BANKMAX_BATCHES * inner_max, (outer_max + nlp.BANKMAX_BATCHES - 1) // nlp.BANKMAX_BATCHES
-    for outer in range(1, outer_max + 1):
-        tol_in = max(opt_tol, min(1e-1, 10.0 * mub), nlp.GRAD_FLOOR * rho)
-        phi_first = phi_last = None
-        for it in range(inner_max):
-            total_inner += 1
-            sl = np.where(hasL, W - pb.lo, 1.0); su = np.where(hasU, pb.hi - W, 1.0)
-            g, D, E = prob.normal_equations(W, mu, rho)
-            stat = np.where(free, 2.0 * g - zL + zU, 0.0)
-            comp = max(float(np.abs(np.where(hasL, zL * sl - mub, 0.0)).max()), float(np.abs(np.where(hasU, zU * su - mub, 0.0)).max()))
-            if K_:
-                gk, dx, dy = K.g_values(W[1:-1], dact)
-                krhs, kst, kblk = K.barrier_terms(W, dact, zk, mub)
-                stat[1:-1, :2] += kst[1:-1]
-                comp = max(comp, float(np.abs(zk * gk - mub).max()))
-            gf = g_values(W[1:-1], fact)
-            frhs, fst, fblk = barrier_terms(W, fact, zf, mub)
-            stat[1:-1, :2] += fst[1:-1]
-            comp = max(comp, float(np.abs(zf * gf - mub).max()))
-            err = max(float(np.abs(stat).max()), comp)
-            if err <= tol_in:
-                break
-            sig = np.where(hasL, zL / sl, 0.0) + np.where(hasU, zU / su, 0.0)
-            rhs = -(2.0 * g - np.where(hasL, mub / sl, 0.0) + np.where(hasU, mub / su, 0.0))
-            Dh = D.copy()
-            idx = np.arange(NV)
-            Dh[:, idx, idx] += 0.5 * sig
-            if K_:
-                rhs[1:-1, :2] += krhs[1:-1]
-                Dh[1:-1, :2, :2] += kblk[1:-1]
-            rhs[1:-1, :2] += frhs[1:-1]
-            Dh[1:-1, :2, :2] += fblk[1:-1]
-            phi0 = _merit(prob, W, mu, rho, mub, hasL, hasU, dact, fact)
-            if phi_first is None:
-                phi_first = phi_last = phi0
-            accepted = False
-            raised = 0
-            for _ in range(30):
-                try:
-                    dw = nlp._solve_block_tridiag(Dh, E, 0.5 * rhs, free, lam)
-                except np.linalg.LinAlgError:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                dphi = -float(np.sum(rhs * dw))
-                if not dphi < 0.0:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                tau = max(0.99, 1.0 - mub)
-                with np.errstate(divide='ignore', invalid='ignore'):
-                    aL = np.where(hasL & (dw < 0), -tau * sl / dw, np.inf)
-                    aU = np.where(hasU & (dw > 0), tau * su / dw, np.inf)
-                amax = min(1.0, float(aL.min()), float(aU.min()))
-                sx, sy = dw[1:-1, 0], dw[1:-1, 1]
-                if K_:
-                    bh = dx * sx + dy * sy
-                    amax = min(amax, float(K.ratio_disc(gk, bh, sx * sx + sy * sy, tau).min()))
-                as_ = fax * sx + fay * sy
-                with np.errstate(divide='ignore', invalid='ignore'):
-                    amax = min(amax, float(np.where(as_ > 0, tau * gf / as_, np.inf).min()))
-                a = amax
-                ok = False
-                for _ls in range(8):
-                    Wt = W + a * dw
-                    pt = _merit(prob, Wt, mu, rho, mub, hasL, hasU, dact, fact)
-                    if np.isfinite(pt) and pt <= phi0 + 1e-4 * a * dphi:
-                        ok = True
-                        break
-                    a *= 0.5
-                if ok:
-                    dzL = np.where(hasL, mub / sl - zL - zL / sl * dw, 0.0)
-                    dzU = np.where(hasU, mub / su - zU + zU / su * dw, 0.0)
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        azL = np.where(hasL & (dzL < 0), -tau * zL / dzL, np.inf)
-                        azU = np.where(hasU & (dzU < 0), -tau * zU / dzU, np.inf)
-                    az = min(1.0, float(azL.min()), float(azU.min()))
-                    if K_:
-                        dzk = (mub - 2.0 * zk * bh) / gk - zk
-                        with np.errstate(divide='ignore', invalid='ignore'):
-                            az = min(az, float(np.where(dzk < 0, -tau * zk / dzk, np.inf).min()))
-                    dzf = (mub + zf * as_) / gf - zf
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        az = min(az, float(np.where(dzf < 0, -tau * zf / dzf, np.inf).min()))
-                    path.append((a, float(np.abs(Wt - W).max()), raised, _ls))
-                    W = Wt
-                    phi_last = pt
-                    zL = zL + az * dzL; zU = zU + az * dzU
-                    slp = np.where(hasL, W - pb.lo, 1.0); sup = np.where(hasU, pb.hi - W, 1.0)
-                    zL = np.where(hasL, np.clip(zL, mub / (1e10 * slp), 1e10 * mub / slp), 0.0)
-                    zU = np.where(hasU, np.clip(zU, mub / (1e10 * sup), 1e10 * mub / sup), 0.0)
-                    if K_:
-                        gn = K.g_values(W[1:-1], dact)[0]
-                        zk = np.clip(zk + az * dzk, mub / (1e10 * gn), 1e10 * mub / gn)
-                    gfn = g_values(W[1:-1], fact)
-                    zf = np.clip(zf + az * dzf, mub / (1e10 * gfn), 1e10 * mub / gfn)
-                    lam = max(lam / 3.0, nlp.LAM_MIN) if a == amax else lam
-                    accepted = True
-                    break
-                lam = min(lam * 4.0, nlp.LAM_MAX)
-            if not accepted:
-                break
-        c = prob.constraints(W)
-        feas = float(np.abs(c).max())
-        if feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and err <= tol_in:
-            status = 1
-            break
-        if pb.bank_max and feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and phi_first is not None \
-                and (phi_first - phi_last) <= nlp.BANKMAX_VALUE_TOL * (1.0 + abs(phi_last)):
-            status = 1
-            break
-        if err > tol_in and accepted and (phi_first - phi_last) > (nlp.BANKMAX_VALUE_TOL if pb.bank_max else nlp.GATE_PROGRESS) * (1.0 + abs(phi_last)):
-            continue
-        n_stalled = n_stalled + 1 if (feas > 0.5 * feas_prev and feas > 1e3 * feas_tol) else 0
-        if n_stalled >= (3 if rho >= nlp.RHO_MAX else nlp.STALL_OUTERS):
-            status = 4
-            break
-        mu = mu + c
-        if feas > 0.25 * feas_prev and rho < nlp.RHO_MAX:
-            mu = mu / nlp.RHO_GROW; rho *= nlp.RHO_GROW
-        feas_prev = feas
-        mub = max(nlp.MUB_MIN, min(0.2 * mub, mub ** 1.5))
-    zkfull = np.zeros((len(discs), pb.N)); zkfull[ia, 1:-1] = zk
-    zffull = np.zeros((len(edges), pb.N)); zffull[ja, 1:-1] = zf
-    return W, dict(cost=prob.cost(W), feas=float(np.abs(prob.constraints(W)).max()), outer=outer, inner=total_inner, status=status,
-                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU, zk=zkfull, zf=zffull, mub=mub, path=path)
+    fd, fe = K.Discs(*K.constant_centres(discs, pb.N)), Edges(edges)
+    W, info, end = nlp.solve_general(prob, W, families=(fd, fe), started=True, **schedule)
+    info.update(zk=fd.scatter(end['z'][0], pb.N), zf=fe.scatter(end['z'][1], pb.N), mub=end['mub'])
+    return W, info
 
 
 # ---- geometry of the cases ---------------------------------------------------------------------------------------------------------

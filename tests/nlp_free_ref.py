@@ -14,8 +14,9 @@ u = 1 / h, in which every equality is LINEAR,  c_i = (s_i - s_{i-1}) u - f(s_i):
                  solved by the Schur complement on d:  x0 = A^-1 r / 2,  y = A^-1 b,  du = (r_u / 2 - b.x0) / (d - b.y),  dW = x0 - y du;
                  d - b.y <= 0: the bordered matrix is not positive definite -- the damping is raised as for a failed pivot
 
-Everything that does not see h is oracle/nlp.py's own code, called at a copy of the Problem with h = 1 / u.  The interface speaks h:
-solve() takes the start interval and returns the solved one.
+Everything that does not see h is oracle/nlp.py's own code, called at a copy of the Problem with h = 1 / u -- the solve loop too:
+oracle.nlp.solve_general, to which this file supplies the border (Border: u, its box, its two duals, bordered_solve) and a problem
+object whose methods take u (FreeProblem).  The interface speaks h: solve() takes the start interval and returns the solved one.
 """
 import copy
 import functools
@@ -91,138 +92,67 @@ def bordered_solve(Dh, E, rhs_half, free, lam, b, d, ru_half):
     return x0 - yb * du, du
 
 
+class Border:
+    """The bordered unknown oracle.nlp.solve_general asks for: u = 1 / h strictly inside (u_lo, u_hi), with the duals zl, zu of its
+    two bounds on the same log barrier as the node variables."""
+    solve = staticmethod(bordered_solve)
+
+    def __init__(self, fp, h_start):
+        self.lo, self.hi = fp.u_lo, fp.u_hi
+        u = 1.0 / float(h_start)
+        ku = min(1e-2 * max(1.0, abs(u)), 1e-2 * (self.hi - self.lo))
+        self.u = min(max(u, self.lo + ku), self.hi - ku)
+
+    def start_duals(self, mub):
+        self.zl, self.zu = mub / (self.u - self.lo), mub / (self.hi - self.u)
+
+    def kkt_error(self, g_u, mub):
+        """stationarity of the u row and the complementarity of its two bounds"""
+        sl, su = self.u - self.lo, self.hi - self.u
+        return abs(2.0 * g_u - self.zl + self.zu), abs(self.zl * sl - mub), abs(self.zu * su - mub)
+
+    def row(self, g_u, d_u, mub):
+        """r_u, the right-hand side of the u row (full convention), and d0, its half curvature with the barrier diagonal (undamped)"""
+        sl, su = self.u - self.lo, self.hi - self.u
+        return -(2.0 * g_u - mub / sl + mub / su), d_u + 0.5 * (self.zl / sl + self.zu / su)
+
+    def ratio(self, du, tau):
+        """fraction to the boundary of u for the step du"""
+        if du < 0:
+            return -tau * (self.u - self.lo) / du
+        if du > 0:
+            return tau * (self.hi - self.u) / du
+        return np.inf
+
+    def dual_step(self, du, mub, tau):
+        """the steps of the two duals and their ratio test"""
+        sl, su = self.u - self.lo, self.hi - self.u
+        dzl = mub / sl - self.zl - self.zl / sl * du
+        dzu = mub / su - self.zu + self.zu / su * du
+        az = np.inf
+        if dzl < 0:
+            az = min(az, -tau * self.zl / dzl)
+        if dzu < 0:
+            az = min(az, -tau * self.zu / dzu)
+        return (dzl, dzu), az
+
+    def accept(self, u, az, dz, mub):
+        """the accepted step: the new u, and the duals stepped by az and clipped like the box duals"""
+        self.u = u
+        zl, zu = self.zl + az * dz[0], self.zu + az * dz[1]
+        self.zl = float(np.clip(zl, mub / (1e10 * (u - self.lo)), 1e10 * mub / (u - self.lo)))
+        self.zu = float(np.clip(zu, mub / (1e10 * (self.hi - u)), 1e10 * mub / (self.hi - u)))
+
+
 def solve(fp, W0, h_start, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX, feas_tol=nlp.FEAS_TOL, opt_tol=nlp.OPT_TOL):
     """oracle.nlp.solve with the interval free.  Returns W, info (cost, feas, h, u, outer, inner, status, rho, mult, zL, zU, zu = the two
     duals of u, path).  mult = 2 rho mu is what the kernel returns: the estimate the last inner problem STARTED from; mult_last =
     2 rho (mu + c) is the one that problem is stationary with (what the next update would store): the multipliers of the KKT check."""
-    pb = fp.pb
-    fixed, hasL, hasU = nlp._barrier_sets(pb)
-    free = ~fixed
-    W = np.asarray(W0, float).copy()
-    W[fixed] = pb.lo[fixed]
-    width = np.where(hasL & hasU, pb.hi - pb.lo, np.inf)
-    kap = np.minimum(1e-2 * np.maximum(1.0, np.abs(W)), 1e-2 * width)
-    W = np.where(hasL, np.maximum(W, pb.lo + kap), W)
-    W = np.where(hasU, np.minimum(W, pb.hi - kap), W)
-    u = 1.0 / float(h_start)
-    ku = min(1e-2 * max(1.0, abs(u)), 1e-2 * (fp.u_hi - fp.u_lo))
-    u = min(max(u, fp.u_lo + ku), fp.u_hi - ku)
-    mu = np.zeros((pb.N - 1, 3)); rho = rho0
-    mub = nlp.MUB0
-    zL = np.where(hasL, mub / np.where(hasL, W - pb.lo, 1.0), 0.0)
-    zU = np.where(hasU, mub / np.where(hasU, pb.hi - W, 1.0), 0.0)
-    zul, zuu = mub / (u - fp.u_lo), mub / (fp.u_hi - u)
-    lam = nlp.LAM0
-    feas_prev = np.inf
-    total_inner = 0
-    status = 2
-    n_stalled = 0
-    path = []
-    if pb.bank_max:
-        inner_max, outer_max = nlp.BANKMAX_BATCHES * inner_max, (outer_max + nlp.BANKMAX_BATCHES - 1) // nlp.BANKMAX_BATCHES
-    for outer in range(1, outer_max + 1):
-        tol_in = max(opt_tol, min(1e-1, 10.0 * mub), nlp.GRAD_FLOOR * rho)
-        phi_first = phi_last = None
-        for it in range(inner_max):
-            total_inner += 1
-            sl = np.where(hasL, W - pb.lo, 1.0); su = np.where(hasU, pb.hi - W, 1.0)
-            sul, suu = u - fp.u_lo, fp.u_hi - u
-            g, D, E, g_u, b, d_u = fp.normal_equations(W, u, mu, rho)
-            stat = np.where(free, 2.0 * g - zL + zU, 0.0)
-            comp = max(float(np.abs(np.where(hasL, zL * sl - mub, 0.0)).max()), float(np.abs(np.where(hasU, zU * su - mub, 0.0)).max()))
-            err = max(float(np.abs(stat).max()), comp, abs(2.0 * g_u - zul + zuu), abs(zul * sul - mub), abs(zuu * suu - mub))
-            if err <= tol_in:
-                break
-            sig = np.where(hasL, zL / sl, 0.0) + np.where(hasU, zU / su, 0.0)
-            rhs = -(2.0 * g - np.where(hasL, mub / sl, 0.0) + np.where(hasU, mub / su, 0.0))
-            r_u = -(2.0 * g_u - mub / sul + mub / suu)
-            Dh = D.copy()
-            idx = np.arange(NV)
-            Dh[:, idx, idx] += 0.5 * sig
-            d0 = d_u + 0.5 * (zul / sul + zuu / suu)
-            phi0 = fp.merit(W, u, mu, rho, mub, hasL, hasU)
-            if phi_first is None:
-                phi_first = phi_last = phi0
-            accepted = False
-            raised = 0
-            for _ in range(30):
-                try:
-                    dw, du = bordered_solve(Dh, E, 0.5 * rhs, free, lam, b, d0 + lam * max(abs(d0), 1e-12), 0.5 * r_u)
-                except np.linalg.LinAlgError:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                dphi = -(float(np.sum(rhs * dw)) + r_u * du)
-                if not dphi < 0.0:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                tau = max(0.99, 1.0 - mub)
-                with np.errstate(divide='ignore', invalid='ignore'):
-                    aL = np.where(hasL & (dw < 0), -tau * sl / dw, np.inf)
-                    aU = np.where(hasU & (dw > 0), tau * su / dw, np.inf)
-                amax = min(1.0, float(aL.min()), float(aU.min()))
-                if du < 0:
-                    amax = min(amax, -tau * sul / du)
-                if du > 0:
-                    amax = min(amax, tau * suu / du)
-                a = amax
-                ok = False
-                for _ls in range(8):
-                    Wt, ut = W + a * dw, u + a * du
-                    pt = fp.merit(Wt, ut, mu, rho, mub, hasL, hasU)
-                    if np.isfinite(pt) and pt <= phi0 + 1e-4 * a * dphi:
-                        ok = True
-                        break
-                    a *= 0.5
-                if ok:
-                    dzL = np.where(hasL, mub / sl - zL - zL / sl * dw, 0.0)
-                    dzU = np.where(hasU, mub / su - zU + zU / su * dw, 0.0)
-                    dzul = mub / sul - zul - zul / sul * du
-                    dzuu = mub / suu - zuu + zuu / suu * du
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        azL = np.where(hasL & (dzL < 0), -tau * zL / dzL, np.inf)
-                        azU = np.where(hasU & (dzU < 0), -tau * zU / dzU, np.inf)
-                    az = min(1.0, float(azL.min()), float(azU.min()))
-                    if dzul < 0:
-                        az = min(az, -tau * zul / dzul)
-                    if dzuu < 0:
-                        az = min(az, -tau * zuu / dzuu)
-                    path.append((a, max(float(np.abs(Wt - W).max()), abs(ut - u)), raised, _ls))
-                    W, u = Wt, ut
-                    phi_last = pt
-                    zL = zL + az * dzL; zU = zU + az * dzU
-                    zul, zuu = zul + az * dzul, zuu + az * dzuu
-                    slp = np.where(hasL, W - pb.lo, 1.0); sup = np.where(hasU, pb.hi - W, 1.0)
-                    zL = np.where(hasL, np.clip(zL, mub / (1e10 * slp), 1e10 * mub / slp), 0.0)
-                    zU = np.where(hasU, np.clip(zU, mub / (1e10 * sup), 1e10 * mub / sup), 0.0)
-                    zul = float(np.clip(zul, mub / (1e10 * (u - fp.u_lo)), 1e10 * mub / (u - fp.u_lo)))
-                    zuu = float(np.clip(zuu, mub / (1e10 * (fp.u_hi - u)), 1e10 * mub / (fp.u_hi - u)))
-                    lam = max(lam / 3.0, nlp.LAM_MIN) if a == amax else lam
-                    accepted = True
-                    break
-                lam = min(lam * 4.0, nlp.LAM_MAX)
-            if not accepted:
-                break
-        c = fp.constraints(W, u)
-        feas = float(np.abs(c).max())
-        if feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and err <= tol_in:
-            status = 1
-            break
-        if pb.bank_max and feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and phi_first is not None \
-                and (phi_first - phi_last) <= nlp.BANKMAX_VALUE_TOL * (1.0 + abs(phi_last)):
-            status = 1
-            break
-        if err > tol_in and accepted and (phi_first - phi_last) > (nlp.BANKMAX_VALUE_TOL if pb.bank_max else nlp.GATE_PROGRESS) * (1.0 + abs(phi_last)):
-            continue
-        n_stalled = n_stalled + 1 if (feas > 0.5 * feas_prev and feas > 1e3 * feas_tol) else 0
-        if n_stalled >= (3 if rho >= nlp.RHO_MAX else nlp.STALL_OUTERS):
-            status = 4
-            break
-        mu = mu + c
-        if feas > 0.25 * feas_prev and rho < nlp.RHO_MAX:
-            mu = mu / nlp.RHO_GROW; rho *= nlp.RHO_GROW
-        feas_prev = feas
-        mub = max(nlp.MUB_MIN, min(0.2 * mub, mub ** 1.5))
-    return W, dict(cost=fp.cost(W, u), feas=float(np.abs(fp.constraints(W, u)).max()), h=1.0 / u, u=u, outer=outer, inner=total_inner,
-                   status=status, rho=rho, mult=2 * rho * mu, mult_last=2 * rho * (mu + fp.constraints(W, u)), zL=zL, zU=zU, zu=(zul, zuu),
-                   path=path)
+    bd = Border(fp, h_start)
+    W, info, end = nlp.solve_general(fp, W0, border=bd, rho0=rho0, inner_max=inner_max, outer_max=outer_max, feas_tol=feas_tol,
+                                     opt_tol=opt_tol)
+    info.update(h=1.0 / bd.u, u=bd.u, zu=(bd.zl, bd.zu), mult_last=2 * info['rho'] * (end['mu'] + fp.constraints(W, bd.u)))
+    return W, info
 
 
 def kkt_residual(fp, W, h, mult, zL, zU, zu):

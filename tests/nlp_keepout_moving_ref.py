@@ -5,8 +5,10 @@ It is tests/nlp_keepout_ref.py with one change: disc m's centre at node i is the
 
     g_im = (x_i - ctr[m, i, 0])^2 + (y_i - ctr[m, i, 1])^2 - R_m^2 > 0,        d = p_i - ctr[m, i].
 
-The centres are data -- no derivative is added -- and merit, stationarity, right-hand side, Newton block, dual step, the exact
-quadratic ratio test (nlp_keepout_ref.ratio_disc, imported), the start rule and the dual clip are the static statement's with d above.
+The centres are data -- no derivative is added.  The family of inequalities is nlp_keepout_ref.Discs, which is written on per-node
+centres in the first place: merit, stationarity, right-hand side, Newton block, dual step, the exact quadratic ratio test, the start
+rule, the refusals and the dual clip are one code for both statements (the names below are nlp_keepout_ref's disc_* functions), and
+the loop is oracle.nlp.solve_general.  This file supplies the centres of tracks at the node times and what goes round the solve.
 The refusals: a non-finite R or centre, an end pose with g <= 0 AT ITS OWN NODE'S TIME (node 0 against ctr[:, 0], node N - 1 against
 ctr[:, N - 1]), a free node with g <= 0 after the start rule.  With centres that do not depend on i, solve() is nlp_keepout_ref.solve
 bit for bit; with no discs it is oracle.nlp.solve.
@@ -25,7 +27,9 @@ so s <= 2 step_max and R^2 = d^2 + step_max^2 keeps the continuous distance >= d
 import numpy as np
 
 import nlp_keepout_ref as K
-from nlp_keepout_ref import Plain, ratio_disc, ST_NONFINITE, PUSH, _box_push      # noqa: F401  (the static statement's pieces)
+from nlp_keepout_ref import Plain, ratio_disc, ST_NONFINITE, PUSH, _box_push, constant_centres      # noqa: F401  (the static statement's pieces)
+from nlp_keepout_ref import disc_g as g_values, disc_start as start, disc_refused as refused      # noqa: F401
+from nlp_keepout_ref import disc_barrier_value as barrier_value, disc_barrier_terms as barrier_terms      # noqa: F401
 from oracle import nlp
 
 NV = nlp.NV
@@ -38,229 +42,11 @@ def centres(moving, t_start, N, h):
     return ctr, np.array([o.r for o in moving], dtype=np.float64)
 
 
-def constant_centres(discs, N):
-    """The tables of static discs (n, 3) = (cx, cy, R) as tracks that stand still."""
-    discs = np.asarray(discs, float).reshape(-1, 3)
-    return np.repeat(discs[:, None, :2], N, axis=1), discs[:, 2].copy()
-
-
-def g_values(W, ctr, R):
-    """(n, M) g of every (disc, row of W) against ctr (n, M, 2) -- the rows' own centres -- and dx, dy (n, M)."""
-    dx = W[None, :, 0] - ctr[:, :, 0]; dy = W[None, :, 1] - ctr[:, :, 1]
-    return dx * dx + dy * dy - R[:, None] ** 2, dx, dy
-
-
-def start(pb, W, ctr, R):
-    """nlp_keepout_ref.start with node i's own centres."""
-    W = W.copy()
-    _, hasL, hasU = nlp._barrier_sets(pb)
-    leg = pb.p1[:2] - pb.p0[:2]; ll = float(np.sqrt(leg[0] * leg[0] + leg[1] * leg[1]))
-    nrm = (-leg[1] / ll, leg[0] / ll) if ll > 0.0 else (0.0, 1.0)
-    for i in range(1, pb.N - 1):
-        x, y = W[i, 0], W[i, 1]
-        for _pass in range(2):
-            for m in range(len(R)):
-                Rm = R[m]
-                if not Rm > 0.0:
-                    continue
-                cx, cy = ctr[m, i]
-                Rt = Rm * (1.0 + PUSH)
-                dx, dy = x - cx, y - cy
-                d2 = dx * dx + dy * dy
-                if d2 - Rm * Rm <= Rt * Rt - Rm * Rm:
-                    dn = np.sqrt(d2)
-                    ux, uy = nrm if dn < 1e-12 * Rm else (dx / dn, dy / dn)
-                    x, y = cx + Rt * ux, cy + Rt * uy
-        W[i, 0], W[i, 1] = x, y
-    W[:, :2] = _box_push(W[:, :2], pb.lo[:, :2], pb.hi[:, :2], hasL[:, :2], hasU[:, :2])
-    return W
-
-
-def refused(pb, ctr, R, W):
-    """discs unusable for this problem (W: after start())?"""
-    if not (np.isfinite(R).all() and np.isfinite(ctr).all()):
-        return True
-    ia = np.flatnonzero(R > 0.0)
-    if not len(ia):
-        return False
-    ends = np.array([pb.p0, pb.p1])
-    if (g_values(ends, ctr[ia][:, [0, -1]], R[ia])[0] <= 0.0).any():
-        return True
-    return bool((g_values(W[1:-1], ctr[ia][:, 1:-1], R[ia])[0] <= 0.0).any())
-
-
-def barrier_value(W, ctr, R, mub):
-    """- mub sum log g over the interior nodes (one log per node, of the product over the discs); +inf when a g <= 0."""
-    gk = g_values(W[1:-1], ctr[:, 1:-1], R)[0]
-    if (gk <= 0.0).any():
-        return np.inf
-    return -mub * float(np.sum(np.log(np.prod(gk, axis=0))))
-
-
-def barrier_terms(W, ctr, R, zk, mub):
-    """nlp_keepout_ref.barrier_terms with per-node centres: rhs (N, 2), the stationarity term (N, 2), the half-convention blocks (N, 2, 2)."""
-    N = len(W)
-    gk, dx, dy = g_values(W[1:-1], ctr[:, 1:-1], R)
-    mg, zg = mub / gk, zk / gk
-    rhs = np.zeros((N, 2)); st = np.zeros((N, 2)); blk = np.zeros((N, 2, 2))
-    rhs[1:-1, 0] = np.sum(2.0 * mg * dx, axis=0); rhs[1:-1, 1] = np.sum(2.0 * mg * dy, axis=0)
-    st[1:-1, 0] = -np.sum(2.0 * zk * dx, axis=0); st[1:-1, 1] = -np.sum(2.0 * zk * dy, axis=0)
-    blk[1:-1, 0, 0] = np.sum(2.0 * zg * dx * dx - zk, axis=0); blk[1:-1, 1, 1] = np.sum(2.0 * zg * dy * dy - zk, axis=0)
-    blk[1:-1, 0, 1] = blk[1:-1, 1, 0] = np.sum(2.0 * zg * dx * dy, axis=0)
-    return rhs, st, blk
-
-
-def _keep_merit(prob, W, mu, rho, mub, hasL, hasU, ctr, R):
-    m = prob.merit(W, mu, rho, mub, hasL, hasU)
-    if not len(R) or not np.isfinite(m):
-        return m
-    return m + barrier_value(W, ctr, R, mub)
-
-
 def solve(prob, W0, ctr, R, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX, feas_tol=nlp.FEAS_TOL, opt_tol=nlp.OPT_TOL):
     """nlp_keepout_ref.solve outside the discs of centres ctr (n, N, 2) and node radii R (n,) (R <= 0: absent).  Returns W and the info
     of nlp_keepout_ref.solve (zk (n, N): the discs' duals).  A refused problem: W0 itself, status 3, NaN cost and feas."""
-    pb = prob.pb
-    ctr = np.asarray(ctr, float).reshape(-1, pb.N, 2); R = np.asarray(R, float).reshape(-1)
-    n = len(R)
-    fixed, hasL, hasU = nlp._barrier_sets(pb)
-    free = ~fixed
-    W = np.asarray(W0, float).copy()
-    W[fixed] = pb.lo[fixed]
-    width = np.where(hasL & hasU, pb.hi - pb.lo, np.inf)
-    kap = np.minimum(1e-2 * np.maximum(1.0, np.abs(W)), 1e-2 * width)
-    W = np.where(hasL, np.maximum(W, pb.lo + kap), W)
-    W = np.where(hasU, np.minimum(W, pb.hi - kap), W)
-    if n:
-        if np.isfinite(R).all() and np.isfinite(ctr).all():
-            W = start(pb, W, ctr, R)
-        if refused(pb, ctr, R, W):
-            return np.asarray(W0, float).copy(), dict(cost=np.nan, feas=np.nan, outer=0, inner=0, status=ST_NONFINITE, path=[],
-                                                      zk=np.zeros((n, pb.N)))
-    ia = np.flatnonzero(R > 0.0)
-    ca, Ra = ctr[ia], R[ia]
-    ci = ca[:, 1:-1]
-    Kk = len(ia) > 0
-    mu = np.zeros((pb.N - 1, 3)); rho = rho0
-    mub = nlp.MUB0
-    zL = np.where(hasL, mub / np.where(hasL, W - pb.lo, 1.0), 0.0)
-    zU = np.where(hasU, mub / np.where(hasU, pb.hi - W, 1.0), 0.0)
-    zk = mub / g_values(W[1:-1], ci, Ra)[0] if Kk else np.zeros((0, pb.N - 2))
-    lam = nlp.LAM0
-    feas_prev = np.inf
-    total_inner = 0
-    status = 2
-    n_stalled = 0
-    path = []
-    if pb.bank_max:
-        inner_max, outer_max = nlp.BANKMAX_BATCHES * inner_max, (outer_max + nlp.BANKMAX_BATCHES - 1) // nlp.BANKMAX_BATCHES
-    for outer in range(1, outer_max + 1):
-        tol_in = max(opt_tol, min(1e-1, 10.0 * mub), nlp.GRAD_FLOOR * rho)
-        phi_first = phi_last = None
-        for it in range(inner_max):
-            total_inner += 1
-            sl = np.where(hasL, W - pb.lo, 1.0); su = np.where(hasU, pb.hi - W, 1.0)
-            g, D, E = prob.normal_equations(W, mu, rho)
-            stat = np.where(free, 2.0 * g - zL + zU, 0.0)
-            comp = max(float(np.abs(np.where(hasL, zL * sl - mub, 0.0)).max()), float(np.abs(np.where(hasU, zU * su - mub, 0.0)).max()))
-            if Kk:
-                gk, dx, dy = g_values(W[1:-1], ci, Ra)
-                krhs, kst, kblk = barrier_terms(W, ca, Ra, zk, mub)
-                stat[1:-1, :2] += kst[1:-1]
-                comp = max(comp, float(np.abs(zk * gk - mub).max()))
-            err = max(float(np.abs(stat).max()), comp)
-            if err <= tol_in:
-                break
-            sig = np.where(hasL, zL / sl, 0.0) + np.where(hasU, zU / su, 0.0)
-            rhs = -(2.0 * g - np.where(hasL, mub / sl, 0.0) + np.where(hasU, mub / su, 0.0))
-            Dh = D.copy()
-            idx = np.arange(NV)
-            Dh[:, idx, idx] += 0.5 * sig
-            if Kk:
-                rhs[1:-1, :2] += krhs[1:-1]
-                Dh[1:-1, :2, :2] += kblk[1:-1]
-            phi0 = _keep_merit(prob, W, mu, rho, mub, hasL, hasU, ca, Ra)
-            if phi_first is None:
-                phi_first = phi_last = phi0
-            accepted = False
-            raised = 0
-            for _ in range(30):
-                try:
-                    dw = nlp._solve_block_tridiag(Dh, E, 0.5 * rhs, free, lam)
-                except np.linalg.LinAlgError:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                dphi = -float(np.sum(rhs * dw))
-                if not dphi < 0.0:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                tau = max(0.99, 1.0 - mub)
-                with np.errstate(divide='ignore', invalid='ignore'):
-                    aL = np.where(hasL & (dw < 0), -tau * sl / dw, np.inf)
-                    aU = np.where(hasU & (dw > 0), tau * su / dw, np.inf)
-                amax = min(1.0, float(aL.min()), float(aU.min()))
-                if Kk:
-                    sx, sy = dw[1:-1, 0], dw[1:-1, 1]
-                    bh = dx * sx + dy * sy
-                    amax = min(amax, float(ratio_disc(gk, bh, sx * sx + sy * sy, tau).min()))
-                a = amax
-                ok = False
-                for _ls in range(8):
-                    Wt = W + a * dw
-                    pt = _keep_merit(prob, Wt, mu, rho, mub, hasL, hasU, ca, Ra)
-                    if np.isfinite(pt) and pt <= phi0 + 1e-4 * a * dphi:
-                        ok = True
-                        break
-                    a *= 0.5
-                if ok:
-                    dzL = np.where(hasL, mub / sl - zL - zL / sl * dw, 0.0)
-                    dzU = np.where(hasU, mub / su - zU + zU / su * dw, 0.0)
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        azL = np.where(hasL & (dzL < 0), -tau * zL / dzL, np.inf)
-                        azU = np.where(hasU & (dzU < 0), -tau * zU / dzU, np.inf)
-                    az = min(1.0, float(azL.min()), float(azU.min()))
-                    if Kk:
-                        dzk = (mub - 2.0 * zk * bh) / gk - zk
-                        with np.errstate(divide='ignore', invalid='ignore'):
-                            az = min(az, float(np.where(dzk < 0, -tau * zk / dzk, np.inf).min()))
-                    path.append((a, float(np.abs(Wt - W).max()), raised, _ls))
-                    W = Wt
-                    phi_last = pt
-                    zL = zL + az * dzL; zU = zU + az * dzU
-                    slp = np.where(hasL, W - pb.lo, 1.0); sup = np.where(hasU, pb.hi - W, 1.0)
-                    zL = np.where(hasL, np.clip(zL, mub / (1e10 * slp), 1e10 * mub / slp), 0.0)
-                    zU = np.where(hasU, np.clip(zU, mub / (1e10 * sup), 1e10 * mub / sup), 0.0)
-                    if Kk:
-                        gn = g_values(W[1:-1], ci, Ra)[0]
-                        zk = np.clip(zk + az * dzk, mub / (1e10 * gn), 1e10 * mub / gn)
-                    lam = max(lam / 3.0, nlp.LAM_MIN) if a == amax else lam
-                    accepted = True
-                    break
-                lam = min(lam * 4.0, nlp.LAM_MAX)
-            if not accepted:
-                break
-        c = prob.constraints(W)
-        feas = float(np.abs(c).max())
-        if feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and err <= tol_in:
-            status = 1
-            break
-        if pb.bank_max and feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and phi_first is not None \
-                and (phi_first - phi_last) <= nlp.BANKMAX_VALUE_TOL * (1.0 + abs(phi_last)):
-            status = 1
-            break
-        if err > tol_in and accepted and (phi_first - phi_last) > (nlp.BANKMAX_VALUE_TOL if pb.bank_max else nlp.GATE_PROGRESS) * (1.0 + abs(phi_last)):
-            continue
-        n_stalled = n_stalled + 1 if (feas > 0.5 * feas_prev and feas > 1e3 * feas_tol) else 0
-        if n_stalled >= (3 if rho >= nlp.RHO_MAX else nlp.STALL_OUTERS):
-            status = 4
-            break
-        mu = mu + c
-        if feas > 0.25 * feas_prev and rho < nlp.RHO_MAX:
-            mu = mu / nlp.RHO_GROW; rho *= nlp.RHO_GROW
-        feas_prev = feas
-        mub = max(nlp.MUB_MIN, min(0.2 * mub, mub ** 1.5))
-    zfull = np.zeros((n, pb.N))
-    zfull[ia, 1:-1] = zk
-    return W, dict(cost=prob.cost(W), feas=float(np.abs(prob.constraints(W)).max()), outer=outer, inner=total_inner, status=status,
-                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU, zk=zfull, mub=mub, path=path)
+    return K.solve_discs(prob, W0, np.asarray(ctr, float).reshape(-1, prob.pb.N, 2), np.asarray(R, float).reshape(-1), rho0=rho0,
+                         inner_max=inner_max, outer_max=outer_max, feas_tol=feas_tol, opt_tol=opt_tol)
 
 
 def problem_of(pb, field=None, t_start=0.0):

@@ -1,7 +1,7 @@
 """CPU statement of the collocation solver with HARD keep-out discs (include/d2d.h d2d_nlp_solve_keepout; test infrastructure only).
 
 It is oracle/nlp.py's loop -- augmented Lagrangian, primal-dual log barrier, damped Newton steps on the block-tridiagonal Lagrangian
-Hessian -- with one more family of inequalities: for every interior node i (x and y free: 1 .. N-2) and disc m = (cx, cy, R), R > 0,
+Hessian -- with one family of node inequalities: for every interior node i (x and y free: 1 .. N-2) and disc m = (cx, cy, R), R > 0,
 
     g_im = (x_i - cx)^2 + (y_i - cy)^2 - R^2 > 0,        d = (x_i - cx, y_i - cy),   s = the step of (x_i, y_i)
 
@@ -19,37 +19,21 @@ each with a dual z_im > 0 that is treated exactly like the box duals zL, zU:
                  of the leg p0 -> p1 if |d| < 1e-12 R); discs in index order, two passes; then the box push again on x and y
   refusals       a non-finite disc, an end pose with g <= 0, a free node with g <= 0 after the start: status 3, NaN cost, W untouched
 
-The problem object is nlp_wind_ref.solve's: `pb` and the four methods constraints, normal_equations, merit, cost -- Plain (oracle.nlp's
-own functions, the rows' constant wind) or nlp_wind_ref.FieldProblem.  With no discs solve() is oracle.nlp.solve bit for bit.
+The loop is oracle.nlp.solve_general; this file supplies the family Discs, on per-node centres ctr (n, N, 2) and radii R (n,) -- a static
+disc is a track that stands still (constant_centres) -- the start rule, the refusals and the scatter of the duals into zk (n, N).
+tests/nlp_keepout_moving_ref.py and tests/nlp_fence_ref.py use the same family.  The problem object is solve_general's: Plain
+(oracle.nlp's own functions, the rows' constant wind) or nlp_wind_ref.FieldProblem.  With no discs solve() is oracle.nlp.solve bit for bit.
 """
 import functools
 
 import numpy as np
 
 from oracle import nlp
+from oracle.nlp import Plain, _box_push      # noqa: F401  (tests and the other statements reach them as K.Plain, K._box_push)
 
 NV = nlp.NV
 ST_NONFINITE = 3
 PUSH = 1e-2
-
-
-class Plain:
-    """An oracle Problem in its own constant wind, with the four methods solve() asks for."""
-
-    def __init__(self, pb):
-        self.pb = pb
-
-    def constraints(self, W):
-        return nlp.constraints(self.pb, W)
-
-    def normal_equations(self, W, mu, rho):
-        return nlp._normal_equations(self.pb, W, mu, rho)
-
-    def merit(self, W, mu, rho, mub, hasL, hasU):
-        return nlp._merit(self.pb, W, mu, rho, mub, hasL, hasU)
-
-    def cost(self, W):
-        return nlp.cost(self.pb, W)
 
 
 def lowered_radius(r, margin, v_max, h):
@@ -58,10 +42,10 @@ def lowered_radius(r, margin, v_max, h):
     return float(np.sqrt((r + margin) ** 2 + (0.5 * v_max * h) ** 2))
 
 
-def g_values(W, discs):
-    """(n, N) g of every (disc, node), and dx, dy (n, N)."""
-    dx = W[None, :, 0] - discs[:, 0, None]; dy = W[None, :, 1] - discs[:, 1, None]
-    return dx * dx + dy * dy - discs[:, 2, None] ** 2, dx, dy
+def constant_centres(discs, N):
+    """The tables of static discs (n, 3) = (cx, cy, R) as tracks that stand still: ctr (n, N, 2), R (n,)."""
+    discs = np.asarray(discs, float).reshape(-1, 3)
+    return np.repeat(discs[:, None, :2], N, axis=1), discs[:, 2].copy()
 
 
 def ratio_disc(g, bh, aa, tau):
@@ -74,216 +58,27 @@ def ratio_disc(g, bh, aa, tau):
     return np.where(ok, cq / (np.sqrt(np.where(ok, disc, 1.0)) - np.where(ok, bh, -1.0)), np.inf)
 
 
-def _box_push(w, lo, hi, hasL, hasU):
-    width = np.where(hasL & hasU, hi - lo, np.inf)
-    kap = np.minimum(1e-2 * np.maximum(1.0, np.abs(w)), 1e-2 * width)
-    w = np.where(hasL, np.maximum(w, lo + kap), w)
-    return np.where(hasU, np.minimum(w, hi - kap), w)
+# ---- the discs on per-node centres: the one implementation (the finite-difference tests pin these through the adapters below) --------
+def disc_g(W, ctr, R):
+    """(n, M) g of every (disc, row of W) against ctr (n, M, 2) -- the rows' own centres -- and dx, dy (n, M)."""
+    dx = W[None, :, 0] - ctr[:, :, 0]; dy = W[None, :, 1] - ctr[:, :, 1]
+    return dx * dx + dy * dy - R[:, None] ** 2, dx, dy
 
 
-def start(pb, W, discs):
-    """The start rule on a W that has had the box push: every interior node out of the discs, then the box push again on x and y."""
-    W = W.copy()
-    _, hasL, hasU = nlp._barrier_sets(pb)
-    leg = pb.p1[:2] - pb.p0[:2]; ll = float(np.sqrt(leg[0] * leg[0] + leg[1] * leg[1]))
-    nrm = (-leg[1] / ll, leg[0] / ll) if ll > 0.0 else (0.0, 1.0)
-    for i in range(1, pb.N - 1):
-        x, y = W[i, 0], W[i, 1]
-        for _pass in range(2):
-            for cx, cy, R in discs:
-                if not R > 0.0:
-                    continue
-                Rt = R * (1.0 + PUSH)
-                dx, dy = x - cx, y - cy
-                d2 = dx * dx + dy * dy
-                if d2 - R * R <= Rt * Rt - R * R:
-                    dn = np.sqrt(d2)
-                    ux, uy = nrm if dn < 1e-12 * R else (dx / dn, dy / dn)
-                    x, y = cx + Rt * ux, cy + Rt * uy
-        W[i, 0], W[i, 1] = x, y
-    W[:, :2] = _box_push(W[:, :2], pb.lo[:, :2], pb.hi[:, :2], hasL[:, :2], hasU[:, :2])
-    return W
-
-
-def refused(pb, discs, W):
-    """discs unusable for this problem (W: after start())?"""
-    if not np.isfinite(discs).all():
-        return True
-    act = discs[discs[:, 2] > 0.0]
-    if not len(act):
-        return False
-    ends = np.array([pb.p0, pb.p1])
-    if (g_values(ends, act)[0] <= 0.0).any():
-        return True
-    return bool((g_values(W[1:-1], act)[0] <= 0.0).any())
-
-
-def _keep_merit(prob, W, mu, rho, mub, hasL, hasU, act):
-    m = prob.merit(W, mu, rho, mub, hasL, hasU)
-    if not len(act) or not np.isfinite(m):
-        return m
-    return m + barrier_value(W, act, mub)
-
-
-def solve(prob, W0, discs, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX, feas_tol=nlp.FEAS_TOL, opt_tol=nlp.OPT_TOL):
-    """oracle.nlp.solve outside the discs (n, 3) = (cx, cy, R) (R <= 0: absent).  Returns W, info of oracle.nlp.solve plus zk (n, N): the
-    discs' duals (0 at the end nodes and for absent discs).  A refused problem: W0 itself, status 3, NaN cost and feas."""
-    pb = prob.pb
-    discs = np.asarray(discs, float).reshape(-1, 3)
-    fixed, hasL, hasU = nlp._barrier_sets(pb)
-    free = ~fixed
-    W = np.asarray(W0, float).copy()
-    W[fixed] = pb.lo[fixed]
-    width = np.where(hasL & hasU, pb.hi - pb.lo, np.inf)
-    kap = np.minimum(1e-2 * np.maximum(1.0, np.abs(W)), 1e-2 * width)
-    W = np.where(hasL, np.maximum(W, pb.lo + kap), W)
-    W = np.where(hasU, np.minimum(W, pb.hi - kap), W)
-    if len(discs):
-        if np.isfinite(discs).all():
-            W = start(pb, W, discs)
-        if refused(pb, discs, W):
-            return np.asarray(W0, float).copy(), dict(cost=np.nan, feas=np.nan, outer=0, inner=0, status=ST_NONFINITE, path=[],
-                                                      zk=np.zeros((len(discs), pb.N)))
-    ia = np.flatnonzero(discs[:, 2] > 0.0)
-    act = discs[ia]
-    K = len(act) > 0
-    mu = np.zeros((pb.N - 1, 3)); rho = rho0
-    mub = nlp.MUB0
-    zL = np.where(hasL, mub / np.where(hasL, W - pb.lo, 1.0), 0.0)
-    zU = np.where(hasU, mub / np.where(hasU, pb.hi - W, 1.0), 0.0)
-    zk = mub / g_values(W[1:-1], act)[0] if K else np.zeros((0, pb.N - 2))        # (n_act, N - 2)
-    lam = nlp.LAM0
-    feas_prev = np.inf
-    total_inner = 0
-    status = 2
-    n_stalled = 0
-    path = []
-    if pb.bank_max:
-        inner_max, outer_max = nlp.BANKMAX_BATCHES * inner_max, (outer_max + nlp.BANKMAX_BATCHES - 1) // nlp.BANKMAX_BATCHES
-    for outer in range(1, outer_max + 1):
-        tol_in = max(opt_tol, min(1e-1, 10.0 * mub), nlp.GRAD_FLOOR * rho)
-        phi_first = phi_last = None
-        for it in range(inner_max):
-            total_inner += 1
-            sl = np.where(hasL, W - pb.lo, 1.0); su = np.where(hasU, pb.hi - W, 1.0)
-            g, D, E = prob.normal_equations(W, mu, rho)
-            stat = np.where(free, 2.0 * g - zL + zU, 0.0)
-            comp = max(float(np.abs(np.where(hasL, zL * sl - mub, 0.0)).max()), float(np.abs(np.where(hasU, zU * su - mub, 0.0)).max()))
-            if K:                                            # the discs' terms: barrier_terms, which the finite-difference test pins
-                gk, dx, dy = g_values(W[1:-1], act)
-                krhs, kst, kblk = barrier_terms(W, act, zk, mub)
-                stat[1:-1, :2] += kst[1:-1]
-                comp = max(comp, float(np.abs(zk * gk - mub).max()))
-            err = max(float(np.abs(stat).max()), comp)
-            if err <= tol_in:
-                break
-            sig = np.where(hasL, zL / sl, 0.0) + np.where(hasU, zU / su, 0.0)
-            rhs = -(2.0 * g - np.where(hasL, mub / sl, 0.0) + np.where(hasU, mub / su, 0.0))
-            Dh = D.copy()
-            idx = np.arange(NV)
-            Dh[:, idx, idx] += 0.5 * sig
-            if K:
-                rhs[1:-1, :2] += krhs[1:-1]
-                Dh[1:-1, :2, :2] += kblk[1:-1]
-            phi0 = _keep_merit(prob, W, mu, rho, mub, hasL, hasU, act)
-            if phi_first is None:
-                phi_first = phi_last = phi0
-            accepted = False
-            raised = 0
-            for _ in range(30):
-                try:
-                    dw = nlp._solve_block_tridiag(Dh, E, 0.5 * rhs, free, lam)
-                except np.linalg.LinAlgError:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                dphi = -float(np.sum(rhs * dw))
-                if not dphi < 0.0:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                tau = max(0.99, 1.0 - mub)
-                with np.errstate(divide='ignore', invalid='ignore'):
-                    aL = np.where(hasL & (dw < 0), -tau * sl / dw, np.inf)
-                    aU = np.where(hasU & (dw > 0), tau * su / dw, np.inf)
-                amax = min(1.0, float(aL.min()), float(aU.min()))
-                if K:
-                    sx, sy = dw[1:-1, 0], dw[1:-1, 1]
-                    bh = dx * sx + dy * sy
-                    amax = min(amax, float(ratio_disc(gk, bh, sx * sx + sy * sy, tau).min()))
-                a = amax
-                ok = False
-                for _ls in range(8):
-                    Wt = W + a * dw
-                    pt = _keep_merit(prob, Wt, mu, rho, mub, hasL, hasU, act)
-                    if np.isfinite(pt) and pt <= phi0 + 1e-4 * a * dphi:
-                        ok = True
-                        break
-                    a *= 0.5
-                if ok:
-                    dzL = np.where(hasL, mub / sl - zL - zL / sl * dw, 0.0)
-                    dzU = np.where(hasU, mub / su - zU + zU / su * dw, 0.0)
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        azL = np.where(hasL & (dzL < 0), -tau * zL / dzL, np.inf)
-                        azU = np.where(hasU & (dzU < 0), -tau * zU / dzU, np.inf)
-                    az = min(1.0, float(azL.min()), float(azU.min()))
-                    if K:
-                        dzk = (mub - 2.0 * zk * bh) / gk - zk
-                        with np.errstate(divide='ignore', invalid='ignore'):
-                            az = min(az, float(np.where(dzk < 0, -tau * zk / dzk, np.inf).min()))
-                    path.append((a, float(np.abs(Wt - W).max()), raised, _ls))
-                    W = Wt
-                    phi_last = pt
-                    zL = zL + az * dzL; zU = zU + az * dzU
-                    slp = np.where(hasL, W - pb.lo, 1.0); sup = np.where(hasU, pb.hi - W, 1.0)
-                    zL = np.where(hasL, np.clip(zL, mub / (1e10 * slp), 1e10 * mub / slp), 0.0)
-                    zU = np.where(hasU, np.clip(zU, mub / (1e10 * sup), 1e10 * mub / sup), 0.0)
-                    if K:
-                        gn = g_values(W[1:-1], act)[0]
-                        zk = np.clip(zk + az * dzk, mub / (1e10 * gn), 1e10 * mub / gn)
-                    lam = max(lam / 3.0, nlp.LAM_MIN) if a == amax else lam
-                    accepted = True
-                    break
-                lam = min(lam * 4.0, nlp.LAM_MAX)
-            if not accepted:
-                break
-        c = prob.constraints(W)
-        feas = float(np.abs(c).max())
-        if feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and err <= tol_in:
-            status = 1
-            break
-        if pb.bank_max and feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and phi_first is not None \
-                and (phi_first - phi_last) <= nlp.BANKMAX_VALUE_TOL * (1.0 + abs(phi_last)):
-            status = 1
-            break
-        if err > tol_in and accepted and (phi_first - phi_last) > (nlp.BANKMAX_VALUE_TOL if pb.bank_max else nlp.GATE_PROGRESS) * (1.0 + abs(phi_last)):
-            continue
-        n_stalled = n_stalled + 1 if (feas > 0.5 * feas_prev and feas > 1e3 * feas_tol) else 0
-        if n_stalled >= (3 if rho >= nlp.RHO_MAX else nlp.STALL_OUTERS):
-            status = 4
-            break
-        mu = mu + c
-        if feas > 0.25 * feas_prev and rho < nlp.RHO_MAX:
-            mu = mu / nlp.RHO_GROW; rho *= nlp.RHO_GROW
-        feas_prev = feas
-        mub = max(nlp.MUB_MIN, min(0.2 * mub, mub ** 1.5))
-    zfull = np.zeros((len(discs), pb.N))
-    zfull[ia, 1:-1] = zk
-    return W, dict(cost=prob.cost(W), feas=float(np.abs(prob.constraints(W)).max()), outer=outer, inner=total_inner, status=status,
-                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU, zk=zfull, mub=mub, path=path)
-
-
-# ---- the pieces the finite-difference tests pin --------------------------------------------------------------------------------------
-def barrier_value(W, act, mub):
+def disc_barrier_value(W, ctr, R, mub):
     """- mub sum log g over the interior nodes (one log per node, of the product over the discs, as the kernel takes it); +inf when a
-    g <= 0.  This is what solve()'s merit adds for the discs."""
-    gk = g_values(W[1:-1], act)[0]
+    g <= 0.  This is what the loop's merit adds for the discs."""
+    gk = disc_g(W[1:-1], ctr[:, 1:-1], R)[0]
     if (gk <= 0.0).any():
         return np.inf
     return -mub * float(np.sum(np.log(np.prod(gk, axis=0))))
 
 
-def barrier_terms(W, act, zk, mub):
-    """What solve() adds for the discs at (W, zk) -- solve() calls this: rhs (N, 2) [full convention, the negative merit gradient with mub / g], the
+def disc_barrier_terms(W, ctr, R, zk, mub):
+    """What the loop adds for the discs at (W, zk): rhs (N, 2) [full convention, the negative merit gradient with mub / g], the
     stationarity term (N, 2) and the half-convention 2x2 blocks (N, 2, 2)."""
     N = len(W)
-    gk, dx, dy = g_values(W[1:-1], act)
+    gk, dx, dy = disc_g(W[1:-1], ctr[:, 1:-1], R)
     mg, zg = mub / gk, zk / gk
     rhs = np.zeros((N, 2)); st = np.zeros((N, 2)); blk = np.zeros((N, 2, 2))
     rhs[1:-1, 0] = np.sum(2.0 * mg * dx, axis=0); rhs[1:-1, 1] = np.sum(2.0 * mg * dy, axis=0)
@@ -291,6 +86,146 @@ def barrier_terms(W, act, zk, mub):
     blk[1:-1, 0, 0] = np.sum(2.0 * zg * dx * dx - zk, axis=0); blk[1:-1, 1, 1] = np.sum(2.0 * zg * dy * dy - zk, axis=0)
     blk[1:-1, 0, 1] = blk[1:-1, 1, 0] = np.sum(2.0 * zg * dx * dy, axis=0)
     return rhs, st, blk
+
+
+def disc_rule(pb, W, ctr, R):
+    """The discs' start rule, node i against its own centres: every interior node out of the discs (no box push)."""
+    W = W.copy()
+    leg = pb.p1[:2] - pb.p0[:2]; ll = float(np.sqrt(leg[0] * leg[0] + leg[1] * leg[1]))
+    nrm = (-leg[1] / ll, leg[0] / ll) if ll > 0.0 else (0.0, 1.0)
+    for i in range(1, pb.N - 1):
+        x, y = W[i, 0], W[i, 1]
+        for _pass in range(2):
+            for m in range(len(R)):
+                Rm = R[m]
+                if not Rm > 0.0:
+                    continue
+                cx, cy = ctr[m, i]
+                Rt = Rm * (1.0 + PUSH)
+                dx, dy = x - cx, y - cy
+                d2 = dx * dx + dy * dy
+                if d2 - Rm * Rm <= Rt * Rt - Rm * Rm:
+                    dn = np.sqrt(d2)
+                    ux, uy = nrm if dn < 1e-12 * Rm else (dx / dn, dy / dn)
+                    x, y = cx + Rt * ux, cy + Rt * uy
+        W[i, 0], W[i, 1] = x, y
+    return W
+
+
+def push_xy(pb, W):
+    """The box push on x and y alone, in place: what closes every start rule."""
+    _, hasL, hasU = nlp._barrier_sets(pb)
+    W[:, :2] = _box_push(W[:, :2], pb.lo[:, :2], pb.hi[:, :2], hasL[:, :2], hasU[:, :2])
+    return W
+
+
+def disc_start(pb, W, ctr, R):
+    """The start rule on a W that has had the box push: disc_rule, then the box push again on x and y."""
+    return push_xy(pb, disc_rule(pb, W, ctr, R))
+
+
+def disc_refused(pb, ctr, R, W):
+    """discs unusable for this problem (W: after disc_start())?  The end poses are held against their own nodes' centres."""
+    if not (np.isfinite(R).all() and np.isfinite(ctr).all()):
+        return True
+    ia = np.flatnonzero(R > 0.0)
+    if not len(ia):
+        return False
+    ends = np.array([pb.p0, pb.p1])
+    if (disc_g(ends, ctr[ia][:, [0, -1]], R[ia])[0] <= 0.0).any():
+        return True
+    return bool((disc_g(W[1:-1], ctr[ia][:, 1:-1], R[ia])[0] <= 0.0).any())
+
+
+class Discs:
+    """The family of hard discs that oracle.nlp.solve_general asks for: the present ones (R > 0) of ctr (n, N, 2), R (n,)."""
+
+    def __init__(self, ctr, R):
+        self.n = len(R)
+        self.ia = np.flatnonzero(R > 0.0)
+        self.ctr, self.R = ctr[self.ia], R[self.ia]
+
+    def __len__(self):
+        return len(self.ia)
+
+    def _at(self, W, dw=None):
+        """g, and with a step dw: bh = d.s, aa = |s|^2 at the interior nodes"""
+        gk, dx, dy = disc_g(W[1:-1], self.ctr[:, 1:-1], self.R)
+        if dw is None:
+            return gk
+        sx, sy = dw[1:-1, 0], dw[1:-1, 1]
+        return gk, dx * sx + dy * sy, sx * sx + sy * sy
+
+    def g(self, W):
+        return self._at(W)
+
+    def barrier_value(self, W, mub):
+        return disc_barrier_value(W, self.ctr, self.R, mub)
+
+    def barrier_terms(self, W, z, mub):
+        return disc_barrier_terms(W, self.ctr, self.R, z, mub)
+
+    def ratio(self, W, dw, tau):
+        return ratio_disc(*self._at(W, dw), tau)
+
+    def dual_step(self, W, dw, z, mub):
+        gk, bh, _ = self._at(W, dw)
+        return (mub - 2.0 * z * bh) / gk - z
+
+    def scatter(self, z, N):
+        """the duals (n_present, N - 2) -> zk (n, N): 0 at the end nodes and for absent discs"""
+        zfull = np.zeros((self.n, N))
+        zfull[self.ia, 1:-1] = z
+        return zfull
+
+
+# ---- the static table (n, 3): thin adapters, under the names the tests and the SLSQP golden generators call -------------------------
+def g_values(W, discs):
+    """(n, N) g of every (disc, node), and dx, dy (n, N)."""
+    return disc_g(W, *constant_centres(discs, len(W)))
+
+
+def barrier_value(W, act, mub):
+    return disc_barrier_value(W, *constant_centres(act, len(W)), mub)
+
+
+def barrier_terms(W, act, zk, mub):
+    return disc_barrier_terms(W, *constant_centres(act, len(W)), zk, mub)
+
+
+def start(pb, W, discs):
+    """The start rule on a W that has had the box push: every interior node out of the discs, then the box push again on x and y."""
+    return disc_start(pb, W, *constant_centres(discs, pb.N))
+
+
+def refused(pb, discs, W):
+    """discs unusable for this problem (W: after start())?"""
+    return disc_refused(pb, *constant_centres(discs, pb.N), W)
+
+
+def solve_discs(prob, W0, ctr, R, **schedule):
+    """oracle.nlp.solve_general outside the discs of centres ctr (n, N, 2) and node radii R (n,) (R <= 0: absent): the box push, the
+    start rule, the refusal, the loop with the family Discs, the scatter of its duals.  solve() here and nlp_keepout_moving_ref.solve
+    are this."""
+    pb = prob.pb
+    W = nlp.interior_start(pb, W0)
+    if len(R):
+        if np.isfinite(R).all() and np.isfinite(ctr).all():
+            W = disc_start(pb, W, ctr, R)
+        if disc_refused(pb, ctr, R, W):
+            return np.asarray(W0, float).copy(), dict(cost=np.nan, feas=np.nan, outer=0, inner=0, status=ST_NONFINITE, path=[],
+                                                      zk=np.zeros((len(R), pb.N)))
+    fam = Discs(ctr, R)
+    W, info, end = nlp.solve_general(prob, W, families=(fam,), started=True, **schedule)
+    info.update(zk=fam.scatter(end['z'][0], pb.N), mub=end['mub'])
+    return W, info
+
+
+def solve(prob, W0, discs, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX, feas_tol=nlp.FEAS_TOL, opt_tol=nlp.OPT_TOL):
+    """oracle.nlp.solve outside the discs (n, 3) = (cx, cy, R) (R <= 0: absent).  Returns W, info of oracle.nlp.solve plus zk (n, N): the
+    discs' duals (0 at the end nodes and for absent discs) and mub.  A refused problem: W0 itself, status 3, NaN cost and feas."""
+    return solve_discs(prob, W0, *constant_centres(discs, prob.pb.N), rho0=rho0, inner_max=inner_max, outer_max=outer_max,
+                       feas_tol=feas_tol, opt_tol=opt_tol)
 
 
 def polyline_clearance(xy, c, r):

@@ -11,7 +11,7 @@ added in the three places that see the objective:
                        convention: its g and D are halves)
   cost reported        m(W)
 
-The solve loop is tests/nlp_wind_ref.py solve(), which reaches these through the problem object.  H travels to the device as 15
+The solve loop is oracle.nlp.solve_general (through nlp_wind_ref.solve), which reaches these through the problem object.  H travels to the device as 15
 planes, the upper triangle of each node's block row by row (include/d2d.h: plane a*5 - a*(a-1)/2 + (c-a) holds H[a][c], a <= c);
 pack() / unpack() below state that order by enumeration, not by the formula.
 """

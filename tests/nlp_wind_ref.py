@@ -13,9 +13,8 @@ F.derivatives: the numpy twin of the kernel's wind_eval2):
   kkt_residual       the multipliers act on (x, y) of their own node through (I/h + J)^T
 
 Everything that does not touch the wind is oracle/nlp.py's own code: the objective and its gradient, the banded solve, the barrier
-sets, the constants.  solve() below is oracle.nlp.solve line for line with these three functions in place of its own; it reaches
-them through the problem object, so that another statement of the same solver (tests/nlp_model_ref.py) supplies its own without a
-copy of the loop.
+sets, the constants -- and the solve loop, oracle.nlp.solve_general, which reaches the first two through the problem object
+(FieldProblem below; tests/nlp_model_ref.py supplies another).  This statement supplies no family of node inequalities and no border.
 """
 import numpy as np
 
@@ -35,7 +34,7 @@ class FieldProblem:
         """w (2, N), J (2, 2, N), H (2, 3, N) of the field at the nodes."""
         return self.field.derivatives(self.t, W[:, 0], W[:, 1])
 
-    # what solve() asks of a problem object: the places that see the wind (below), and the value it reports.  Another statement of
+    # what oracle.nlp.solve_general asks of a problem object: the places that see the wind (below), and the value it reports.  Another statement of
     # the same solver (tests/nlp_model_ref.py) is a class with these four methods and `pb`.
     def constraints(self, W):
         return constraints(self, W)
@@ -124,117 +123,9 @@ def _merit(fp, W, mu, rho, mub, hasL, hasU):
 
 
 def solve(fp, W0, rho0=nlp.RHO0, inner_max=nlp.INNER_MAX, outer_max=nlp.OUTER_MAX, feas_tol=nlp.FEAS_TOL, opt_tol=nlp.OPT_TOL):
-    """oracle.nlp.solve in the field.  fp: a FieldProblem, or any object with `pb` and its four methods constraints,
-    normal_equations, merit and cost.  Returns W, info (cost, feas, outer, inner, status, rho, mult, zL, zU, path).  path holds, per
-    accepted Newton step, its length a, the largest |dW| it made, the number of times its damping was raised eightfold and the number
-    of halvings of its line search."""
-    pb = fp.pb
-    fixed, hasL, hasU = nlp._barrier_sets(pb)
-    free = ~fixed
-    W = np.asarray(W0, float).copy()
-    W[fixed] = pb.lo[fixed]
-    width = np.where(hasL & hasU, pb.hi - pb.lo, np.inf)
-    kap = np.minimum(1e-2 * np.maximum(1.0, np.abs(W)), 1e-2 * width)
-    W = np.where(hasL, np.maximum(W, pb.lo + kap), W)
-    W = np.where(hasU, np.minimum(W, pb.hi - kap), W)
-    mu = np.zeros((pb.N - 1, 3)); rho = rho0
-    mub = nlp.MUB0
-    zL = np.where(hasL, mub / np.where(hasL, W - pb.lo, 1.0), 0.0)
-    zU = np.where(hasU, mub / np.where(hasU, pb.hi - W, 1.0), 0.0)
-    lam = nlp.LAM0
-    feas_prev = np.inf
-    total_inner = 0
-    status = 2
-    n_stalled = 0
-    path = []
-    if pb.bank_max:
-        inner_max, outer_max = nlp.BANKMAX_BATCHES * inner_max, (outer_max + nlp.BANKMAX_BATCHES - 1) // nlp.BANKMAX_BATCHES
-    for outer in range(1, outer_max + 1):
-        tol_in = max(opt_tol, min(1e-1, 10.0 * mub), nlp.GRAD_FLOOR * rho)
-        phi_first = phi_last = None
-        for it in range(inner_max):
-            total_inner += 1
-            sl = np.where(hasL, W - pb.lo, 1.0); su = np.where(hasU, pb.hi - W, 1.0)
-            g, D, E = fp.normal_equations(W, mu, rho)
-            stat = np.where(free, 2.0 * g - zL + zU, 0.0)
-            comp = max(float(np.abs(np.where(hasL, zL * sl - mub, 0.0)).max()), float(np.abs(np.where(hasU, zU * su - mub, 0.0)).max()))
-            err = max(float(np.abs(stat).max()), comp)
-            if err <= tol_in:
-                break
-            sig = np.where(hasL, zL / sl, 0.0) + np.where(hasU, zU / su, 0.0)
-            rhs = -(2.0 * g - np.where(hasL, mub / sl, 0.0) + np.where(hasU, mub / su, 0.0))
-            Dh = D.copy()
-            idx = np.arange(NV)
-            Dh[:, idx, idx] += 0.5 * sig
-            phi0 = fp.merit(W, mu, rho, mub, hasL, hasU)
-            if phi_first is None:
-                phi_first = phi_last = phi0
-            accepted = False
-            raised = 0
-            for _ in range(30):
-                try:
-                    dw = nlp._solve_block_tridiag(Dh, E, 0.5 * rhs, free, lam)
-                except np.linalg.LinAlgError:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                dphi = -float(np.sum(rhs * dw))
-                if not dphi < 0.0:
-                    lam = min(lam * 8.0, nlp.LAM_MAX); raised += 1; continue
-                tau = max(0.99, 1.0 - mub)
-                with np.errstate(divide='ignore', invalid='ignore'):
-                    aL = np.where(hasL & (dw < 0), -tau * sl / dw, np.inf)
-                    aU = np.where(hasU & (dw > 0), tau * su / dw, np.inf)
-                amax = min(1.0, float(aL.min()), float(aU.min()))
-                a = amax
-                ok = False
-                for _ls in range(8):
-                    Wt = W + a * dw
-                    pt = fp.merit(Wt, mu, rho, mub, hasL, hasU)
-                    if np.isfinite(pt) and pt <= phi0 + 1e-4 * a * dphi:
-                        ok = True
-                        break
-                    a *= 0.5
-                if ok:
-                    dzL = np.where(hasL, mub / sl - zL - zL / sl * dw, 0.0)
-                    dzU = np.where(hasU, mub / su - zU + zU / su * dw, 0.0)
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        azL = np.where(hasL & (dzL < 0), -tau * zL / dzL, np.inf)
-                        azU = np.where(hasU & (dzU < 0), -tau * zU / dzU, np.inf)
-                    az = min(1.0, float(azL.min()), float(azU.min()))
-                    path.append((a, float(np.abs(Wt - W).max()), raised, _ls))
-                    W = Wt
-                    phi_last = pt
-                    zL = zL + az * dzL; zU = zU + az * dzU
-                    slp = np.where(hasL, W - pb.lo, 1.0); sup = np.where(hasU, pb.hi - W, 1.0)
-                    zL = np.where(hasL, np.clip(zL, mub / (1e10 * slp), 1e10 * mub / slp), 0.0)
-                    zU = np.where(hasU, np.clip(zU, mub / (1e10 * sup), 1e10 * mub / sup), 0.0)
-                    lam = max(lam / 3.0, nlp.LAM_MIN) if a == amax else lam
-                    accepted = True
-                    break
-                lam = min(lam * 4.0, nlp.LAM_MAX)
-            if not accepted:
-                break
-        c = fp.constraints(W)
-        feas = float(np.abs(c).max())
-        if feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and err <= tol_in:
-            status = 1
-            break
-        if pb.bank_max and feas <= feas_tol and mub <= nlp.MUB_MIN * 1.0001 and phi_first is not None \
-                and (phi_first - phi_last) <= nlp.BANKMAX_VALUE_TOL * (1.0 + abs(phi_last)):
-            status = 1
-            break
-        if err > tol_in and accepted and (phi_first - phi_last) > (nlp.BANKMAX_VALUE_TOL if pb.bank_max else nlp.GATE_PROGRESS) * (1.0 + abs(phi_last)):
-            continue
-        n_stalled = n_stalled + 1 if (feas > 0.5 * feas_prev and feas > 1e3 * feas_tol) else 0
-        if n_stalled >= (3 if rho >= nlp.RHO_MAX else nlp.STALL_OUTERS):
-            status = 4
-            break
-        mu = mu + c
-        if feas > 0.25 * feas_prev and rho < nlp.RHO_MAX:
-            mu = mu / nlp.RHO_GROW; rho *= nlp.RHO_GROW
-        feas_prev = feas
-        mub = max(nlp.MUB_MIN, min(0.2 * mub, mub ** 1.5))
-    return W, dict(cost=fp.cost(W), feas=float(np.abs(fp.constraints(W)).max()), outer=outer, inner=total_inner, status=status,
-                   rho=rho, mult=2 * rho * mu, zL=zL, zU=zU, path=path)
+    """oracle.nlp.solve_general in the field: no families, no border.  fp: a FieldProblem, or any object with `pb` and its four methods
+    constraints, normal_equations, merit and cost.  Returns W, info (cost, feas, outer, inner, status, rho, mult, zL, zU, path)."""
+    return nlp.solve_general(fp, W0, rho0=rho0, inner_max=inner_max, outer_max=outer_max, feas_tol=feas_tol, opt_tol=opt_tol)[:2]
 
 
 def kkt_residual(fp, W, mult, zL=None, zU=None):
