@@ -39,6 +39,9 @@
 //         the Newton system is bordered by the row of u = 1 / h (nlp_assemble, nlp_recover_free), every pass reads the equalities at the
 //         current u, the line search at the trial one, and cost carries the duration term.  An unusable row of the box refuses the
 //         problem like an unusable scenario row; *ex.h_out gets the solved h (NaN for a refused problem).
+//         FREE with KEEP and FENCE (d2d_nlp_solve_free_fence): the static hard discs and the half-planes beside the free step.  Both read
+//         (x, y) of the interior nodes alone, so the border column b, the scalar d and the residual of the row of u gain no term: what the
+//         families add sits in A, and with it in both solves of the Schur complement.  FREE with FENCE brings KEEP (either count may be 0).
 //   KEEP  (d2d_nlp_solve_keepout): ex.keep the hard discs and the planes of their duals; g > 0 is held at every interior node by the
 //         box's primal-dual barrier (the four passes), the start is moved out of the discs (nlp_keep_start) and unusable discs refuse
 //         the problem (nlp_keep_bad).  cost does not see the discs.  KMOV brings KEEP with it.
@@ -56,7 +59,8 @@ template <unsigned F> struct NlpFeatures {
                         FENCE = (F & NLP_FENCE) != 0, T_AT = (F & NLP_T_AT) != 0;
   static_assert(F < (NLP_T_AT << 1), "unknown feature bit");
   static_assert(!MODEL || F == NLP_MODEL, "MODEL excludes every other feature");
-  static_assert(!FREE || !(WIND || MOV || VIA || KEEP || FENCE), "FREE excludes WIND, MOV, VIA, KEEP, KMOV and FENCE");
+  static_assert(!FREE || !(WIND || MOV || VIA || KMOV), "FREE excludes WIND, MOV, VIA and KMOV");
+  static_assert(!(FREE && FENCE) || KEEP, "FREE with FENCE brings KEEP, as the fence kernel does (either count may be 0)");
   static_assert(!(KEEP || FENCE) || !(MOV || VIA), "KEEP, KMOV and FENCE exclude MOV and VIA: their problem types carry no soft discs or pins");
   static_assert(!(KMOV && FENCE), "FENCE holds static hard discs only");
 };
@@ -330,11 +334,15 @@ struct NlpFenceProb : NlpKeepProb {
 struct NlpKeepFenceSet : NlpKeepSet {
   NlpFenceSet fence;
 };
+// FREE with KEEP and FENCE (d2d_nlp_solve_free_fence): both sets and the free step (the members of NlpFreeProb, under the same names)
+struct NlpFreeFenceProb : NlpFenceProb {
+  double u, ulo, uhi, zul, zuu, kd;
+};
 __device__ __forceinline__ bool nlp_fence_present(const double *__restrict__ e) { return e[0] != 0.0 || e[1] != 0.0; }
 __device__ __forceinline__ double nlp_fence_g(const double *__restrict__ e, double x, double y) { return e[2] - nlp_dot2(e[0], x, e[1], y); }
 template <unsigned F, typename X = NlpFeatures<F>>
-using NlpProbT = std::conditional_t<X::FENCE, NlpFenceProb, std::conditional_t<X::KEEP, std::conditional_t<X::KMOV, NlpKeepMovProb, NlpKeepProb>,
-                                    std::conditional_t<X::FREE, NlpFreeProb, std::conditional_t<X::VIA, NlpViaProb, std::conditional_t<X::MOV, NlpMovProb, NlpProb>>>>>;
+using NlpProbT = std::conditional_t<X::FREE && (X::KEEP || X::FENCE), NlpFreeFenceProb, std::conditional_t<X::FENCE, NlpFenceProb, std::conditional_t<X::KEEP, std::conditional_t<X::KMOV, NlpKeepMovProb, NlpKeepProb>,
+                                    std::conditional_t<X::FREE, NlpFreeProb, std::conditional_t<X::VIA, NlpViaProb, std::conditional_t<X::MOV, NlpMovProb, NlpProb>>>>>>;
 template <unsigned F> using NlpProbV = NlpProbT<F & ~(NLP_MOV | NLP_FREE)>;       // for the passes that read no soft disc and no u
 template <unsigned F, typename X = NlpFeatures<F>>             // the set type that NlpExtra's keep pointer stands for
 using NlpKeepSetT = std::conditional_t<X::FENCE, NlpKeepFenceSet, std::conditional_t<X::KMOV, NlpKeepMovSet, NlpKeepSet>>;
@@ -1510,8 +1518,12 @@ __device__ void nlp_recover_stats(const NlpProbV<F> &pb, const NlpScen &s, int l
 //   du = (r_u / 2 - b.x0) / (d - b.y),   dW = x0 - y du
 // and the second pass is nlp_recover_stats' own: directional derivative and the two ratio tests, with u and its duals included.
 // false: d - b.y is not positive -- the bordered matrix is not positive definite (the caller raises the damping).
-__device__ bool nlp_recover_free(const NlpFreeProb &pb, const NlpScen &s, int lane, double mub, double tau, double ru, double d,
+// KEEP, FENCE: the second pass takes the families' ratio tests and dual steps of nlp_recover_stats behind the box's, discs then edges,
+// ahead of u's: the order of oracle.nlp.solve_general.  The first pass does not change: b holds nothing of them.
+template <unsigned F>
+__device__ bool nlp_recover_free(const NlpProbT<F> &pb, const NlpScen &s, int lane, double mub, double tau, double ru, double d,
                                  double *dphi_out, double *amax_out, double *az_out, double *du_out) {
+  NLP_FEATURES(F);
   const int N = pb.N;
   double bx = 0.0, by = 0.0;
   for (int i0 = 0; i0 < N; i0 += 64) {
@@ -1579,6 +1591,39 @@ __device__ bool nlp_recover_free(const NlpFreeProb &pb, const NlpScen &s, int la
         if (dw * amax > tau * su) amax = tau * su / dw;
         const double dz = (mub + z * dw) / su - z;
         if (-dz * az > tau * z) az = -tau * z / dz;
+      }
+    }
+    if constexpr (KEEP) {
+      if (i >= 1 && i < N - 1) {
+        const double *__restrict__ dk = pb.keep.discs;
+        const double sx = xv[0] - yv[0] * du, sy = xv[1] - yv[1] * du, aa = sx * sx + sy * sy;
+#pragma clang loop unroll(disable)
+        for (int m = 0; m < pb.keep.n; ++m) {
+          const double R = dk[3 * m + 2];
+          if (!(R > 0.0)) continue;
+          const double dx = wv[0] - dk[3 * m], dy = wv[1] - dk[3 * m + 1];
+          const double gk = dx * dx + dy * dy - R * R, z = pb.keep.z[(size_t)m * N + i], bh = dx * sx + dy * sy;
+          if (bh < 0.0) {
+            const double cq = tau * gk, disc = bh * bh - aa * cq;
+            if (disc > 0.0) amax = fmin(amax, cq / (sqrt(disc) - bh));
+          }
+          const double dz = (mub - 2.0 * z * bh) / gk - z;
+          if (-dz * az > tau * z) az = -tau * z / dz;
+        }
+      }
+    }
+    if constexpr (FENCE) {
+      if (i >= 1 && i < N - 1) {
+        const double sx = xv[0] - yv[0] * du, sy = xv[1] - yv[1] * du;
+#pragma clang loop unroll(disable)
+        for (int k = 0; k < pb.fence.n; ++k) {
+          const double *__restrict__ e = pb.fence.edges + 4 * k;
+          if (!nlp_fence_present(e)) continue;
+          const double gk = nlp_fence_g(e, wv[0], wv[1]), z = pb.fence.z[(size_t)k * N + i], as = nlp_dot2(e[0], sx, e[1], sy);
+          if (as * amax > tau * gk) amax = tau * gk / as;
+          const double dz = fma(z, as, mub) / gk - z;
+          if (-dz * az > tau * z) az = -tau * z / dz;
+        }
       }
     }
   }
@@ -2091,7 +2136,7 @@ __device__ __forceinline__ void nlp_solve_one(int N, double h, const d2d_nlp_opt
         const double tau = fmax(0.99, 1.0 - mub);
         double dphi, amax, az;
         if constexpr (FREE) {
-          const bool spd = nlp_recover_free(pb, s, lane, mub, tau, ru, dfull, &dphi, &amax, &az, &du);
+          const bool spd = nlp_recover_free<F>(pb, s, lane, mub, tau, ru, dfull, &dphi, &amax, &az, &du);
           nlp_phase_sync();
           NLP_STAMP(4)
           if (!spd) { lam = fmin(lam * 8.0, D2D_LM_LAMBDA_MAX); continue; }
@@ -2348,6 +2393,12 @@ __device__ __forceinline__ void nlp_handout_body(int B, int N, double h, const d
     }
     if (bad) {
       out.cost = out.feas = __builtin_nan(""); out.iters = 0; out.status = D2D_ST_NONFINITE;
+    } else if constexpr (FREE && FENCE) {    // the free step inside both families: the sets of the common call below, the row of the one that follows
+      NlpKeepFenceSet ks{};
+      static_cast<NlpKeepSet &>(ks) = NlpKeepSet{keep->discs + (size_t)b * keep->n_keep * 3, kwork + (size_t)b * keep->n_keep * N, keep->n_keep};
+      ks.fence = NlpFenceSet{fence->edges + (size_t)b * fence->n_edge * 4, fwork + (size_t)b * fence->n_edge * N, fence->n_edge};
+      nlp_solve_one<F>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr, lane, out, nullptr, nlp_lds, bnd,
+                       NlpExtra{{nullptr, nullptr, nullptr}, nullptr, 0.0, 0u, nullptr, nullptr, free_rows + (size_t)b * 4, h_out + b, &ks});
     } else if constexpr (FREE) {             // (a call of its own: through the one below, this kernel's refusal block came out reordered -- DESIGN 5.28)
       nlp_solve_one<NLP_FREE>(N, h, o, sc, nullptr, W + (size_t)b * NLP_NV * N, wsb, mult ? mult + (size_t)b * 3 * N : nullptr, lane, out,
                               b == 0 ? stamps : nullptr, nlp_lds, bnd,
@@ -2382,6 +2433,16 @@ nlp_solve_free_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__re
                       unsigned long long *stamps) {
   nlp_handout_body<NLP_FREE>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, nullptr, 0.0, nullptr, nullptr,
                              nullptr, nullptr, nullptr, free_rows, h_out, stamps);
+}
+
+// d2d_nlp_solve_free_fence: the free time step outside every problem's static hard discs and inside its convex polygon (constant wind)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLP_WIND_WAVES_PER_SIMD, NLP_WIND_WAVES_PER_SIMD)))
+nlp_solve_free_fence_kernel(int B, int N, double h, d2d_nlp_opts o, const double *__restrict__ scen, double *W, double *work, double *mult,
+                            double *__restrict__ cost_out, double *__restrict__ feas_out, int32_t *__restrict__ iters_out,
+                            int32_t *__restrict__ status_out, int32_t *queue, const double *__restrict__ free_rows, double *__restrict__ h_out,
+                            d2d_keep_out keep, double *kwork, d2d_fence fence, double *fwork) {
+  nlp_handout_body<NLP_FREE | NLP_KEEP | NLP_FENCE>(B, N, h, o, scen, W, work, mult, cost_out, feas_out, iters_out, status_out, queue, nullptr, 0.0,
+                                                    nullptr, nullptr, nullptr, nullptr, nullptr, free_rows, h_out, nullptr, &keep, kwork, &fence, fwork);
 }
 
 // d2d_nlp_solve_keepout: outside every problem's hard discs -- the rows' constant wind or the field (WIND), the start time per problem
@@ -2996,6 +3057,27 @@ int d2d_nlp_solve_free(d2d_ctx *ctx, int B, int N, double h0, const double *scen
   if (int rc = nlp_handout_launch(nlp_solve_free_kernel, ctx, B, N, h0, o, scen, W, work, mult, cost, feas, iters, status, free_rows, h_out, stamps))
     return rc;
   return nlp_stamps_report(ctx, stamps);                   // (factor: both passes of the cyclic reduction)
+}
+
+int d2d_nlp_solve_free_fence(d2d_ctx *ctx, int B, int N, double h0, const double *scen, const d2d_nlp_opts *opts, const double *free_rows,
+                             double *W, double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status, double *h_out,
+                             const d2d_keep_out *keep, double *kwork, const d2d_fence *fence, double *fwork) {
+  const char *who = "d2d_nlp_solve_free_fence";
+  D2D_REQUIRE(fence, "%s: null fence (n_edge = 0: no edges)", who);
+  D2D_REQUIRE(fence->n_edge >= 0 && fence->n_edge <= D2D_MAX_FENCE, "%s: n_edge = %d outside 0 .. %d", who, fence->n_edge, D2D_MAX_FENCE);
+  D2D_REQUIRE(fence->n_edge == 0 || (fence->edges && fwork), "%s: null edges or fwork with n_edge = %d", who, fence->n_edge);
+  D2D_REQUIRE(keep, "%s: null keep-out table (n_keep = 0: no discs)", who);
+  D2D_REQUIRE(keep->n_keep >= 0 && keep->n_keep <= D2D_MAX_KEEP, "%s: n_keep = %d outside 0 .. %d", who, keep->n_keep, D2D_MAX_KEEP);
+  D2D_REQUIRE(keep->n_keep == 0 || (keep->discs && kwork), "%s: null discs or kwork with n_keep = %d", who, keep->n_keep);
+  if (keep->n_keep == 0 && fence->n_edge == 0)             // neither family: the solve of d2d_nlp_solve_free, its kernel and its checks
+    return d2d_nlp_solve_free(ctx, B, N, h0, scen, opts, free_rows, W, work, mult, cost, feas, iters, status, h_out);
+  if (int rc = nlp_single_check(ctx, B, N, h0, scen, W, work, cost, feas, who)) return rc;
+  D2D_REQUIRE(free_rows && h_out, "%s: null free_rows or h_out", who);
+  d2d_nlp_opts o;
+  if (int rc = nlp_options(opts, who, &o)) return rc;
+  D2D_REQUIRE(o.serial == 0, "%s: opts->serial = 1 (the twisted recursion) is not available with a free time step", who);
+  return nlp_handout_launch(nlp_solve_free_fence_kernel, ctx, B, N, h0, o, scen, W, work, mult, cost, feas, iters, status, free_rows, h_out, *keep,
+                            kwork, *fence, fwork);
 }
 
 int d2d_nlp_solve_groups(d2d_ctx *ctx, int R, int n_ac, int N, double h, const double *scen, const d2d_nlp_opts *opts, int max_sweeps,

@@ -366,7 +366,9 @@ class KeepOut:
     def lowered(self, v_max, h):
         """(cx, cy, R) of the node constraint: two nodes on the circle R at the largest spacing v_max h have their chord pass the centre
         at sqrt(R^2 - (v_max h / 2)^2) = r + margin.  v_max: the largest speed over the ground, which the planners take to be the upper
-        airspeed bound (the class docstring says what a tail wind asks for)."""
+        airspeed bound (the class docstring says what a tail wind asks for).  With a FREE time step (t1_window, plan_batch(window=),
+        d2d_nlp_solve_free_fence) h is the LARGEST step of the box, h_hi: the chord term grows with h, so the radius lowered with h_hi is
+        conservative for every step the solver may end at."""
         return self.c[0], self.c[1], float(np.sqrt((self.r + self.margin) ** 2 + (0.5 * v_max * h) ** 2))
 
     def __repr__(self):

@@ -278,6 +278,8 @@ _SIGS = {
                               + [C.POINTER(WindFieldC), _P, C.POINTER(KeepOutC), _P]),
     'd2d_nlp_solve_fence': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
                             + [C.POINTER(WindFieldC), _P, C.POINTER(KeepOutC), _P, C.POINTER(FenceC), _P]),
+    'd2d_nlp_solve_free_fence': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 9
+                                 + [C.POINTER(KeepOutC), _P, C.POINTER(FenceC), _P]),
     'd2d_nlp_solve_groups_fence': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts), C.c_int, C.c_double] + [_P] * 9
                                    + [C.POINTER(WindFieldC), _P, C.POINTER(FenceC), _P]),
     'd2d_nlp_solve_keepout_moving': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(NlpOpts)] + [_P] * 7
@@ -934,6 +936,17 @@ class Context:
             t_start = 0.0
         return self._nlp_core(self.lib.d2d_nlp_solve_fence, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, serial), bounds,
                               want_mult=want_mult, slots=slots, order=order, field=field, t_start=t_start, keep=discs, fence=edges)
+
+    def nlp_solve_free_fence(self, scen, W, h, free_rows, discs=None, edges=None, rho0=10.0, mub0=0.1, mub_min=1e-9, feas_tol=1e-9, opt_tol=1e-7,
+                             inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, want_mult=False, bounds=None, slots=0, order=None):
+        """nlp_solve_free outside static HARD discs and inside a convex polygon (d2d_nlp_solve_free_fence): the leg's duration is free
+        while both families are held.  free_rows as nlp_solve_free's; discs dev [B][n_keep][3] as nlp_solve_keepout's and edges dev
+        [B][n_edge][4] as nlp_solve_fence's (None: none; both None: nlp_solve_free's kernel and bytes).  The rows' constant wind; no
+        field, nothing moves, no pins.  Refused on the device (ST_NONFINITE, cost = feas = h = NaN, W untouched): nlp_solve_free's
+        causes and nlp_solve_fence's.  The discs are held at the nodes: inflate R for the chord with the LARGEST step of the box.
+        Returns nlp_solve_free's dict plus keep_mult [B][n_keep][N] and fence_mult [B][n_edge][N], as nlp_solve_fence."""
+        return self._nlp_core(self.lib.d2d_nlp_solve_free_fence, scen, W, h, (rho0, mub0, mub_min, feas_tol, opt_tol, inner_max, outer_max, 0), bounds,
+                              want_mult=want_mult, slots=slots, order=order, free_rows=free_rows, keep=discs, fence=edges)
 
     def nlp_solve_groups_fence(self, scen, W, h, n_ac, edges, field=None, t_start=None, max_sweeps=12, tol=1e-7, rho0=10.0, mub0=0.1, mub_min=1e-9,
                                feas_tol=1e-9, opt_tol=1e-7, inner_max=NLP_INNER_MAX, outer_max=NLP_OUTER_MAX, serial=0, bounds=None, want_mult=False):

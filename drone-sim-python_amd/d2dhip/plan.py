@@ -2,7 +2,7 @@
 
 
 def nlp_plan(ctx, scen, W, h, *, n_ac=None, field=None, t_start=None, knots=None, disc=None, via=None, free_rows=None, pairs=False, keep=None,
-             hard_knots=None, hard_disc=None, fence=None, **opts):
+             hard_knots=None, hard_disc=None, fence=None, window=None, **opts):
     """The planners' one rule for choosing among the nlp_solve* methods of `ctx` (a Context, or any object that has them) -- the first
     optional input that is given names the entry, which also takes the inputs below it in its column (free_rows: none):
       n_ac given, R scenarios of n_ac aircraft:  via -> _groups_via, knots -> _groups_moving, pairs -> _groups_pairs, field -> _groups_wind,
@@ -15,9 +15,22 @@ def nlp_plan(ctx, scen, W, h, *, n_ac=None, field=None, t_start=None, knots=None
     fence given (the rows of d2d.opty_utils.GeoFence.lowered()): n_ac None -> nlp_solve_fence (dev [B][n_edge][4]) with keep (its static
     hard discs), n_ac given -> nlp_solve_groups_fence (dev [R][n_edge][4], one polygon per scenario; keep refused by name), with field and
     t_start; refused by name together with free_rows, via, knots / disc or hard_knots / hard_disc.
+    window given (the rows of free_rows, dev [B][4] = (h_lo, h_hi, k_dur, h_start): the leg's duration free WHILE static hard discs and
+    a geofence are held): nlp_solve_free_fence with keep and fence (either or both may be None); refused by name together with n_ac,
+    field, via, knots / disc, hard_knots / hard_disc or free_rows.  (free_rows keeps refusing keep and fence: window is the spelling.)
     opts: the entry's own keywords (solver options, bounds, max_sweeps ...).  Returns the entry's dictionary plus `entry`, its name.
     (nlp_solve_model is not chosen here: its objective model is another problem, not an optional input of a plan -- DESIGN.md 5.16.)"""
     wind = dict(field=field, t_start=t_start)
+    if window is not None:
+        for name, given in (('n_ac', n_ac is not None), ('field', field is not None), ('via', via is not None), ('knots', knots is not None),
+                            ('disc', disc is not None), ('hard_knots', hard_knots is not None), ('hard_disc', hard_disc is not None),
+                            ('free_rows', free_rows is not None)):
+            if given:
+                raise NotImplementedError(f'window together with {name}: a free step holds static hard discs and a geofence for one aircraft '
+                                          'in the rows\' constant wind, without pins or anything that moves (window replaces free_rows)')
+        out = ctx.nlp_solve_free_fence(scen, W, h, window, discs=keep, edges=fence, **opts)
+        out['entry'] = 'nlp_solve_free_fence'
+        return out
     if fence is not None:
         for name, given in (('free_rows', free_rows is not None), ('via', via is not None), ('knots', knots is not None),
                             ('disc', disc is not None), ('hard_knots', hard_knots is not None), ('hard_disc', hard_disc is not None)):

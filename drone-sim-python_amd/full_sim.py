@@ -522,8 +522,75 @@ def deconflict_plans(ctx, scen, W, h, n_ac, world=None, prio=None, row0=None, *,
     return W, info
 
 
+def _start_nodes(ctx, dsc, K, h, W0, bounds):
+    """The start of a collocation solve on the device: W0 an array (B, 5, K) of node values, or 'dubins' -- every row's Dubins path,
+    built there from the rows (d2d_nlp_guess_dubins).  -> W (device), the guess's status (device int32 [B]; None for an array)."""
+    if isinstance(W0, str):
+        if W0 != 'dubins':
+            raise ValueError(f"W0={W0!r}: an array (B, 5, K) of node values or 'dubins'")
+        W, g = ctx.nlp_guess_dubins(dsc, K, h, bounds=bounds, outputs=('status',))
+        return W, g['status']
+    return ctx.dev(np.ascontiguousarray(W0, dtype=np.float64)), None
+
+
+def _keep_table(keep_out, rows, steps):
+    """keep_out -> the table (B, n, 3) of (cx, cy, R) that the kernel reads: an array is taken as it is; a list of d2d.opty_utils.KeepOut is
+    lowered per problem with the row's VMAX and that problem's step steps[b] (a free step: the largest one of its box)."""
+    B = len(rows)
+    if len(keep_out) and hasattr(keep_out[0], 'lowered'):
+        import d2d.opty_utils as d2ou
+        return np.stack([d2ou.lower_keep_out(keep_out, rows[b, d2dhip.SC_VMAX], steps[b]) for b in range(B)])
+    keep = np.ascontiguousarray(keep_out, dtype=np.float64)
+    if keep.ndim != 3 or keep.shape[0] != B or keep.shape[2] != 3:
+        raise ValueError(f'keep_out: an array (B, n, 3) of (cx, cy, R) or a list of KeepOut is required, got shape {keep.shape}')
+    return keep
+
+
+def _fence_table(fence, G):
+    """fence -> the table (G, n, 4) of (ax, ay, b, kap): one d2d.opty_utils.GeoFence for all G scenarios, one per scenario, or the rows."""
+    import d2d.opty_utils as d2ou
+    if isinstance(fence, d2ou.GeoFence):
+        return np.stack([fence.lowered()] * G)
+    if isinstance(fence, (list, tuple)) and len(fence) and isinstance(fence[0], d2ou.GeoFence):
+        if len(fence) != G or len({len(f.a) for f in fence}) != 1:
+            raise ValueError(f'fence: one GeoFence for all scenarios or one per scenario ({G}) with the same number of edges')
+        return np.stack([f.lowered() for f in fence])
+    ftab = np.ascontiguousarray(fence, dtype=np.float64)
+    if ftab.ndim != 3 or ftab.shape[0] != G or ftab.shape[2] != 4:
+        raise ValueError(f'fence: a GeoFence, a list of them or an array ({G}, n, 4) of (ax, ay, b, kap) is required, got shape {ftab.shape}')
+    return ftab
+
+
+def _plan_batch_window(scen_rows, K, W0, h, window, kdur, keep_out, fence, solve_kw):
+    """plan_batch(window=): one aircraft per row, the step free in its box, keep_out's static hard discs and the fence in the same solve."""
+    if h is None:
+        raise ValueError('plan_batch(window=): h, the start step, is required')
+    ctx = d2dhip.default_context()
+    rows = np.ascontiguousarray(scen_rows, dtype=np.float64)
+    dsc = ctx.dev(rows)
+    B, h = rows.shape[0], float(h)
+    W, guess_status = _start_nodes(ctx, dsc, K, h, W0, solve_kw.get('bounds'))
+    assert W.shape == (B, 5, K)
+    fr = np.zeros((B, 4))
+    fr[:, :2] = np.broadcast_to(np.asarray(window, dtype=np.float64), (B, 2))
+    fr[:, 2] = np.broadcast_to(np.asarray(kdur, dtype=np.float64), (B,))
+    keep = None if keep_out is None else _keep_table(keep_out, rows, fr[:, 1])       # the chord term at the largest step of the box
+    ftab = None if fence is None else _fence_table(fence, B)
+    out = d2dhip.nlp_plan(ctx, dsc, W, h, window=ctx.dev(fr), keep=None if keep is None else ctx.dev(keep),
+                          fence=None if ftab is None else ctx.dev(ftab), **solve_kw)
+    out['free_rows'] = fr
+    if keep is not None:
+        out['keep'] = keep
+    if ftab is not None:
+        out['fence'] = ftab
+    out.update(W=W, scen=dsc)
+    if guess_status is not None:
+        out['guess_status'] = guess_status
+    return out
+
+
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
-               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, deconflict=None, hard_moving=None, fence=None, **solve_kw):
+               moving=None, via=None, gust=None, free_time=None, kdur=0.0, keep_out=None, deconflict=None, hard_moving=None, fence=None, window=None, **solve_kw):
     """Batched planning entry point: scen_rows (B, d2dhip.SCEN_STRIDE) in the d2dhip layout -> dict with device
     tensors q, cost, iters, status and host stats (polynomial fit, backend='fit').
     backend='nlp': the reference's direct-collocation Problem (hard bounds) for B / n_ac scenarios of n_ac aircraft in one launch
@@ -563,6 +630,12 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     d2d_nlp_solve_groups_fence, which carries no hard discs; both with and without a field); the result carries fence_mult (device
     [B][n][K]) and fence (the lowered table, a host array).  Not combined with moving, via, free_time, hard_moving or deconflict, nor
     with keep_out when n_ac > 1: raised by name.
+    window (backend='nlp', n_ac = 1): free_time's box -- (h_lo, h_hi) for all problems or an array (B, 2), with kdur -- for a plan that also
+    holds keep_out's static hard discs and a fence (either, both or neither) in the same solve (d2d_nlp_solve_free_fence): the spelling
+    of a free step beside hard constraints (free_time keeps refusing them).  A list of KeepOut is lowered with each row's VMAX and the
+    LARGEST step of its box, h_hi: conservative for every step the solve may end at; the fence is convex and needs none.  The result
+    carries h and free_rows as free_time's, keep / keep_mult and fence / fence_mult as keep_out's and fence's.  Not combined with
+    n_ac > 1, windfield, moving, via, hard_moving, deconflict, free_time or the fit backend: raised by name.
     deconflict (backend='nlp'): None -- today's call, bit for bit -- or a dict of deconflict_plans' keywords (d_sep, margin, d_look
     required; world, prio, n_knot, n_mov, max_rounds, step_max, kind, hard): after the solve the formations (the scenarios) that share a
     world give way to each other by priority (deconflict_plans, which re-solves with this call's solve_kw, in the field and from the
@@ -589,6 +662,15 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
                                       'Gauss-Seidel over the aircraft cannot hold; plan them one at a time')
         if fld is not None or moving or via is not None:
             raise NotImplementedError('free_time together with windfield, moving or via is not supported: node times move with the step')
+    if window is not None:
+        if backend != 'nlp':
+            raise NotImplementedError("the polynomial fit has no free time step: plan_batch(backend='nlp', window=...) plans with one (fit backend)")
+        for name, given in (('n_ac > 1', int(n_ac) != 1), ('windfield', fld is not None), ('moving', bool(moving)), ('via', via is not None),
+                            ('hard_moving', hard_moving is not None), ('deconflict', deconflict is not None), ('free_time', free_time is not None)):
+            if given:
+                raise NotImplementedError(f'window with {name} is not supported: a free step beside static hard discs and a geofence is held '
+                                          'for one aircraft in the rows\' constant wind, without pins or anything that moves')
+        return _plan_batch_window(scen_rows, K, W0, h, window, kdur, keep_out, fence, solve_kw)
     if keep_out is not None:
         if backend != 'nlp':
             raise NotImplementedError("the polynomial fit has no hard keep-out discs: plan_batch(backend='nlp', keep_out=...) holds them")
@@ -635,33 +717,15 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
         dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
         assert h is not None
         h, n_ac = float(h), int(n_ac)
-        guess_status = None
-        if isinstance(W0, str):                             # the start is built on the device from the rows: no host copy
-            if W0 != 'dubins':
-                raise ValueError(f"W0={W0!r}: an array (B, 5, K) of node values or 'dubins'")
-            if via is not None:
-                raise NotImplementedError("W0='dubins' with via=: a Dubins path knows no pins; the 'via' guess does "
-                                          "(d2d.opty_utils.via_guess, Planner.get_initial_guess('via')): pass its node values as W0")
-            W, g = ctx.nlp_guess_dubins(dsc, K, h, bounds=solve_kw.get('bounds'), outputs=('status',))
-            guess_status = g['status']
-        else:
-            W = ctx.dev(np.ascontiguousarray(W0, dtype=np.float64))
+        if isinstance(W0, str) and W0 == 'dubins' and via is not None:
+            raise NotImplementedError("W0='dubins' with via=: a Dubins path knows no pins; the 'via' guess does "
+                                      "(d2d.opty_utils.via_guess, Planner.get_initial_guess('via')): pass its node values as W0")
+        W, guess_status = _start_nodes(ctx, dsc, K, h, W0, solve_kw.get('bounds'))      # ('dubins': built on the device from the rows, no host copy)
         assert W.shape == (dsc.shape[0], 5, K)
         if fence is not None:
-            import d2d.opty_utils as d2ou
             B = dsc.shape[0]
-            G = B // n_ac
             rows = np.asarray(scen_rows, dtype=np.float64)
-            if isinstance(fence, d2ou.GeoFence):
-                ftab = np.stack([fence.lowered()] * G)
-            elif isinstance(fence, (list, tuple)) and len(fence) and isinstance(fence[0], d2ou.GeoFence):
-                if len(fence) != G or len({len(f.a) for f in fence}) != 1:
-                    raise ValueError(f'fence: one GeoFence for all scenarios or one per scenario ({G}) with the same number of edges')
-                ftab = np.stack([f.lowered() for f in fence])
-            else:
-                ftab = np.ascontiguousarray(fence, dtype=np.float64)
-                if ftab.ndim != 3 or ftab.shape[0] != G or ftab.shape[2] != 4:
-                    raise ValueError(f'fence: a GeoFence, a list of them or an array ({G}, n, 4) of (ax, ay, b, kap) is required, got shape {ftab.shape}')
+            ftab = _fence_table(fence, B // n_ac)
             if n_ac > 1:
                 dsc_f = dsc
                 if not _rows_select_pairs(scen_rows, n_ac):     # the reference's pair (0, 1) as the partner sets the group entry reads
@@ -673,14 +737,7 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
                 if guess_status is not None:
                     out['guess_status'] = guess_status
                 return out
-            keep = None
-            if keep_out is not None:
-                if len(keep_out) and hasattr(keep_out[0], 'lowered'):
-                    keep = np.stack([d2ou.lower_keep_out(keep_out, rows[b, d2dhip.SC_VMAX], h) for b in range(B)])
-                else:
-                    keep = np.ascontiguousarray(keep_out, dtype=np.float64)
-                    if keep.ndim != 3 or keep.shape[0] != B or keep.shape[2] != 3:
-                        raise ValueError(f'keep_out: an array (B, n, 3) of (cx, cy, R) or a list of KeepOut is required, got shape {keep.shape}')
+            keep = None if keep_out is None else _keep_table(keep_out, rows, np.full(B, h))
             out = d2dhip.nlp_plan(ctx, dsc, W, h, fence=ctx.dev(ftab), keep=None if keep is None else ctx.dev(keep), field=fld,
                                   t_start=t_start if fld is not None else None, **solve_kw)
             out['fence'] = ftab
@@ -691,15 +748,7 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
                 out['guess_status'] = guess_status
             return out
         if keep_out is not None:
-            B = dsc.shape[0]
-            if len(keep_out) and hasattr(keep_out[0], 'lowered'):
-                import d2d.opty_utils as d2ou
-                rows = np.asarray(scen_rows, dtype=np.float64)
-                keep = np.stack([d2ou.lower_keep_out(keep_out, rows[b, d2dhip.SC_VMAX], h) for b in range(B)])
-            else:
-                keep = np.ascontiguousarray(keep_out, dtype=np.float64)
-                if keep.ndim != 3 or keep.shape[0] != B or keep.shape[2] != 3:
-                    raise ValueError(f'keep_out: an array (B, n, 3) of (cx, cy, R) or a list of KeepOut is required, got shape {keep.shape}')
+            keep = _keep_table(keep_out, np.asarray(scen_rows, dtype=np.float64), np.full(dsc.shape[0], h))
             out = d2dhip.nlp_plan(ctx, dsc, W, h, keep=ctx.dev(keep), field=fld, t_start=t_start if fld is not None else None, **solve_kw)
             out['keep'] = keep
         elif hard_moving is not None:

@@ -39,7 +39,9 @@ instead of a float.  The interval is then the LAST entry of the free vector (num
 ({h_sym: (lo, hi)}; without one: (h / 4, 4 h) of the start value x0[-1]), and is solved with the node values by d2d_nlp_solve_free; a
 duration term of the cost (d2d.opty_utils.CostDuration, CostComposit(kdur=)) is its weight.  One aircraft, the constant wind, static
 obstacles and a lowered objective: with timed waypoints, moving obstacles, a wind field, the host objective or several aircraft the
-constructor raises NotImplementedError naming the combination.  info carries time_step and duration."""
+constructor raises NotImplementedError naming the combination.  info carries time_step and duration.  keep_out= (static KeepOuts) and
+fence= go with it (d2d_nlp_solve_free_fence): the discs are lowered with the LARGEST step of the bound, which the bounds must then
+give -- conservative for every step inside it -- and info carries keep_out_clearance / fence_clearance at the solved nodes."""
 import numpy as np
 
 import d2dhip
@@ -207,14 +209,23 @@ class Problem:
             what = ('more than one aircraft' if self.n_aircraft != 1 else
                     'moving obstacles' if self.moving else
                     'instance_constraints at interior times (waypoints)' if self.via is not None else
-                    f'a variable duration (time_step = {self.free_step})' if self.free_step is not None else
                     'the host objective (a cost plug-in without a kernel)' if self.objective == 'host' else None)
             if what:
                 raise NotImplementedError(f'keep_out together with {what} is not supported')
             import d2d.opty_utils as d2ou
             # a list with a MovingKeepOut plans through d2d_nlp_solve_keepout_moving: every disc as a track (a static one stands still)
             self.keep_moving = any(isinstance(k, d2ou.MovingKeepOut) for k in self.keep_out)
-            if self.keep_moving:
+            if self.free_step is not None:
+                # a variable duration holds STATIC hard discs (d2d_nlp_solve_free_fence).  The chord between two nodes grows with the
+                # step: the discs are lowered with the LARGEST step of its bound, which is conservative for every step inside it
+                if self.keep_moving:
+                    raise NotImplementedError(f'a MovingKeepOut in keep_out together with a variable duration (time_step = {self.free_step}) '
+                                              'is not supported: its centre at a node depends on the step')
+                if self.step_bounds is None:
+                    raise ValueError(f'keep_out together with a variable duration needs bounds={{{self.free_step}: (lo, hi)}}: the discs are '
+                                     'lowered for the largest step')
+                self.keep_rows = d2ou.lower_keep_out(self.keep_out, self.bounds[0]['v'][1], self.step_bounds[1])
+            elif self.keep_moving:
                 self.keep_knots, self.keep_disc = d2ou.lower_keep_moving(self.keep_out, self.bounds[0]['v'][1], self.time_step)
             else:
                 self.keep_rows = d2ou.lower_keep_out(self.keep_out, self.bounds[0]['v'][1], self.time_step)
@@ -224,14 +235,13 @@ class Problem:
         if fence is not None:
             what = ('moving obstacles' if self.moving else
                     'instance_constraints at interior times (waypoints)' if self.via is not None else
-                    f'a variable duration (time_step = {self.free_step})' if self.free_step is not None else
                     'the host objective (a cost plug-in without a kernel)' if self.objective == 'host' else
                     'a MovingKeepOut in keep_out (hard discs that move)' if self.keep_out and self.keep_moving else None)
             if what:
                 raise NotImplementedError(f'fence together with {what} is not supported')
             import d2d.opty_utils as d2ou
             self.fence_rows = d2ou.lower_fence(fence)
-        if self.free_step is not None:                  # what a free interval is not combined with (d2d_nlp_solve_free)
+        if self.free_step is not None:                  # what a free interval is not combined with (d2d_nlp_solve_free, _free_fence)
             what = ('more than one aircraft (they share one interval: the joint system is not built)' if self.n_aircraft != 1 else
                     'moving obstacles (their node times move with the step)' if self.moving else
                     'a wind field that varies in space and time (its time derivative enters the border)' if self.field is not None else
@@ -420,7 +430,8 @@ class Problem:
         return sol, info
 
     def _solve_free(self, ctx, x0, W, rows):
-        """The variable-duration Problem: one aircraft, the interval x0[-1] free in its bound (d2d_nlp_solve_free)."""
+        """The variable-duration Problem: one aircraft, the interval x0[-1] free in its bound (d2d_nlp_solve_free; with static hard discs
+        or a geofence d2d_nlp_solve_free_fence, through nlp_plan's window=)."""
         import single_opt_planner as sop
         N = self.num_nodes
         h0 = float(x0[-1])
@@ -432,7 +443,12 @@ class Problem:
         dsc[:, d2dhip.SC_KCOL] = 0.0
         dW = ctx.dev(np.ascontiguousarray(W))
         self.free_rows = np.array([[lo, hi, sop.duration_weight(sop.lower_cost(self.cost)), h0]])
-        out = d2dhip.nlp_plan(ctx, dsc, dW, h0, free_rows=ctx.dev(self.free_rows), bounds=None if bnd is None else ctx.dev(bnd), **self._solver_kw())
+        if self.keep_out or self.fence is not None:
+            out = d2dhip.nlp_plan(ctx, dsc, dW, h0, window=ctx.dev(self.free_rows), keep=ctx.dev(self.keep_rows[None]) if self.keep_out else None,
+                                  fence=None if self.fence is None else ctx.dev(self.fence_rows[None]), bounds=None if bnd is None else ctx.dev(bnd),
+                                  **self._solver_kw())
+        else:
+            out = d2dhip.nlp_plan(ctx, dsc, dW, h0, free_rows=ctx.dev(self.free_rows), bounds=None if bnd is None else ctx.dev(bnd), **self._solver_kw())
         ctx.sync()
         Wh = dW.cpu().numpy()
         h = float(out['h'][0].item())
@@ -442,10 +458,17 @@ class Problem:
             sol[s] = Wh[0, c]
         sol[-1] = h
         st = int(out['status'][0].item())
-        return sol, {'status': st, 'feas': float(out['feas'][0].item()), 'iters': out['iters'].cpu().numpy().tolist(), 'sweeps': 0,
-                     'moved': 0.0, 'obj_val': float(self.obj(sol)), 'cost': float(out['cost'][0].item()),
-                     'status_msg': STATUS_MSG.get(st, 'max_iter'), 'time_step': h, 'duration': h * (N - 1),
-                     'box_violation': 0.0, 'phi_violation': 0.0, 'v_violation': 0.0}
+        info = {'status': st, 'feas': float(out['feas'][0].item()), 'iters': out['iters'].cpu().numpy().tolist(), 'sweeps': 0,
+                'moved': 0.0, 'obj_val': float(self.obj(sol)), 'cost': float(out['cost'][0].item()),
+                'status_msg': STATUS_MSG.get(st, 'max_iter'), 'time_step': h, 'duration': h * (N - 1),
+                'box_violation': 0.0, 'phi_violation': 0.0, 'v_violation': 0.0}
+        if self.keep_out or self.fence is not None:       # the clearances of the fixed-step solve, at the solved nodes
+            import d2d.opty_utils as d2ou
+            if self.keep_out:
+                info['keep_out_clearance'] = d2ou.keep_out_clearance(self.keep_out, Wh[0, 0], Wh[0, 1])
+            if self.fence is not None:
+                info['fence_clearance'] = d2ou.fence_clearance(self.fence, Wh[0, 0], Wh[0, 1])
+        return sol, info
 
     # ---- host objective ------------------------------------------------------------------------------------------------------
     def _host_rows(self):

@@ -187,17 +187,42 @@ FREE_TIME_FIT = ("backend='fit' cannot plan with a free duration (t1_free): the 
                  "backend='nlp' (or 'auto') solves the collocation problem with the time step as an unknown")
 
 
-def check_free_time(exp, backend):
-    """The scenario's optional t1_free = (t1_lo, t1_hi) in seconds -> None or the pair, refused where it cannot be planned."""
-    tf = getattr(exp, 't1_free', None)
+def _free_duration(exp, backend, attr):
+    """The free duration (t1_lo, t1_hi) in seconds that the scenario carries as `attr` (t1_free or t1_window) -> None or the pair: its
+    range check and the refusal of the fit backend, the same for either spelling."""
+    tf = getattr(exp, attr, None)
     if tf is None:
         return None
     lo, hi = (float(v) for v in tf)
     if not (np.isfinite(lo) and np.isfinite(hi)) or not lo > exp.t0 or not lo < hi:
-        raise ValueError(f't1_free = ({lo}, {hi}): t0 < t1_lo < t1_hi required (t0 = {exp.t0})')
+        raise ValueError(f'{attr} = ({lo}, {hi}): t0 < t1_lo < t1_hi required (t0 = {exp.t0})')
     if backend == 'fit':
-        raise NotImplementedError(FREE_TIME_FIT)
+        raise NotImplementedError(FREE_TIME_FIT.replace('t1_free', attr))
     return lo, hi
+
+
+def check_free_time(exp, backend):
+    """The scenario's optional t1_free = (t1_lo, t1_hi) in seconds -> None or the pair, refused where it cannot be planned."""
+    return _free_duration(exp, backend, 't1_free')
+
+
+def check_window(exp, backend, moving=(), waypoints=(), t1_free=None, field=None):
+    """The scenario's optional t1_window = (t1_lo, t1_hi) in seconds: t1_free's free duration for a plan that ALSO holds static KeepOuts
+    and a fence (t1_free keeps refusing them; without either the plan is t1_free's) -> None or the pair.  It takes t1_free's checks and
+    is refused by name where it cannot be planned: beside t1_free, moving obstacles, waypoints, a MovingKeepOut, a wind field that
+    varies in space and time, or backend='fit'."""
+    tw = _free_duration(exp, backend, 't1_window')
+    if tw is None:
+        return None
+    import d2d.opty_utils as d2ou
+    for name, given in (('t1_free (one spelling of the free duration per scenario)', t1_free is not None),
+                        ('moving obstacles (moving_obstacles)', bool(moving)), ('waypoints', bool(waypoints)),
+                        ('a MovingKeepOut in keep_out', any(isinstance(k, d2ou.MovingKeepOut) for k in (getattr(exp, 'keep_out', None) or []))),
+                        ('a wind field that varies in space and time (SplineWindField)', field is not None)):
+        if given:
+            raise NotImplementedError(f't1_window together with {name} is not supported: a free duration holds static hard discs and a '
+                                      'geofence for one aircraft in a constant wind (d2d_nlp_solve_free_fence)')
+    return tw
 
 
 def lower_cost(cost):
@@ -356,6 +381,10 @@ class Planner:
         self.keep_out = check_keep_out(exp, self.backend, self.moving_obstacles, self.waypoints, self.t1_free)
         # an optional hard geofence (exp.fence): held by the collocation backend (d2d_nlp_solve_fence), to which 'auto' goes straight
         self.fence = check_fence(exp, self.backend, self.moving_obstacles, self.waypoints, self.t1_free, self.keep_out)
+        # an optional free duration BESIDE static keep_out discs and a fence (exp.t1_window = (t1_lo, t1_hi), seconds): t1_free's unknown
+        # step in the solve that holds both families (d2d_nlp_solve_free_fence); the discs are lowered with the largest step of the window
+        self.t1_window = check_window(exp, self.backend, self.moving_obstacles, self.waypoints, self.t1_free, self.field)
+        self._free = self.t1_free if self.t1_free is not None else self.t1_window        # the free duration under either spelling
         self.aircraft = d2ou.Aircraft()
         N = self.num_nodes
         self._slice_x, self._slice_y, self._slice_psi, self._slice_phi, self._slice_v = (
@@ -372,7 +401,7 @@ class Planner:
         if self._host_cost and self.fence is not None:
             raise NotImplementedError(FENCE_HOST_COST)
         if initialize and (self.keep_out or self.fence is not None or self.backend == 'nlp' or self._host_cost or self.field is not None or self.moving_obstacles or self.waypoints
-                           or self.t1_free is not None):
+                           or self._free is not None):
             import opty.direct_collocation
             _g = self.aircraft
             t0, (x0, y0, psi0, phi0, v0) = exp.t0, exp.p0
@@ -387,9 +416,9 @@ class Planner:
                 self._bounds[_g._sy(_g._st)] = exp.y_constraint
             obj = exp.cost
             step = self.time_step
-            if self.t1_free is not None:           # the interval as a symbol with its bound: opty's variable duration
+            if self._free is not None:             # the interval as a symbol with its bound: opty's variable duration
                 step = d2ou._Sym('h')
-                self._bounds[step] = tuple((t - exp.t0) / (self.num_nodes - 1) for t in self.t1_free)
+                self._bounds[step] = tuple((t - exp.t0) / (self.num_nodes - 1) for t in self._free)
             self.prob = opty.direct_collocation.Problem(lambda _free: obj.cost(_free, self),
                                                         lambda _free: obj.cost_grad(_free, self),
                                                         _g.get_eom(self.wind), _g._state_symbols, self.num_nodes, step,
@@ -434,7 +463,7 @@ class Planner:
         """Node-vector guess [x, y, psi, phi, v] (src/single_opt_planner.py:79-115)."""
         g = np.zeros(self.prob.num_free)
         N = self.num_nodes
-        if self.t1_free is not None:               # the interval is the last entry: the scenario's own step is its start
+        if self._free is not None:                 # the interval is the last entry: the scenario's own step is its start
             g[-1] = self.time_step
         if kind == 'rnd':
             rng = np.random.default_rng(seed)
@@ -485,7 +514,7 @@ class Planner:
         if initial_guess is None:
             initial_guess = self.get_initial_guess('via' if self.waypoints else 'tri')
         self.solution, self.info = self.prob.solve(initial_guess)
-        if self.t1_free is not None:               # the plan's clock follows the solved interval
+        if self._free is not None:                 # the plan's clock follows the solved interval
             self.time_step = float(self.solution[-1])
             self.duration = self.time_step * (self.num_nodes - 1)
             self.info['backend_used'] = 'nlp'
@@ -502,7 +531,7 @@ class Planner:
 
     def save_solution(self, filename):
         wind = np.array([self.wind.sample_num(t, x, y) for t, x, y in zip(self.sol_time, self.sol_x, self.sol_y)])
-        extra = {} if self.t1_free is None else dict(time_step=self.time_step, duration=self.duration)
+        extra = {} if self._free is None else dict(time_step=self.time_step, duration=self.duration)
         np.savez(filename, sol_time=self.sol_time, sol_x=self.sol_x, sol_y=self.sol_y, sol_psi=self.sol_psi,
                  sol_phi=self.sol_phi, sol_v=self.sol_v, wind=wind, **extra)
         print('saved {}'.format(filename))

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define D2D_VERSION 128
+#define D2D_VERSION 129
 
 /* error codes */
 #define D2D_OK 0
@@ -1034,6 +1034,36 @@ int d2d_nlp_solve_fence(d2d_ctx *ctx, int B, int N, double h, const double *scen
                         double *work, double *mult, double *cost, double *feas, int32_t *iters, int32_t *status,
                         const d2d_wind_field *field, const double *t_start, const d2d_keep_out *keep, double *kwork,
                         const d2d_fence *fence, double *fwork);
+
+/* d2d_nlp_solve_free OUTSIDE static hard keep-out discs and INSIDE a convex geofence: the leg's duration is free while both families of
+ * d2d_nlp_solve_fence are held -- the call for a no-fly zone whose detour does not fit a duration guessed in advance.  Formulation: the
+ * unknowns, the box of h, the objective (the row's structured cost + k_dur (N - 1) h) and the bordered Newton system of
+ * d2d_nlp_solve_free; the inequalities g > 0 of d2d_nlp_solve_keepout (discs) and d2d_nlp_solve_fence (edges) at every interior node,
+ * each with its dual on the same primal-dual log barrier.  Discs and edges read (x, y) of the interior nodes alone, so the border
+ * column b, the scalar d and the residual of the row of u = 1 / h gain no term: what the families add -- stationarity rows, right-hand
+ * side, the (x, y) corner of the node's diagonal block with the discs' - 2 z I, KKT error -- sits in the block-tridiagonal matrix A and is
+ * so in BOTH solves of the Schur complement (x0 = A^-1 r / 2 and y = A^-1 b see the same damped matrix).  A failed pivot in either pass
+ * of the cyclic reduction (the second factors copies of the same D', E': it can fail only where the first would) or d - b.y <= 0
+ * raises the damping eightfold.  The line
+ * search reads the equalities at u + a du and the families' barriers at the trial nodes; the step length is the smallest of four ratio
+ * tests -- the box, the exact quadratic root of the discs, tau g / (a.s) of the edges, u's -- and every floating-point sum takes the discs
+ * in ascending index, then the edges.  Start: box push, the discs' rule, the edges' rule, box push, then the step pushed strictly inside
+ * its box; both families' duals start at mub / g.
+ * free_rows, h_out, work (d2d_nlp_free_workspace_doubles(N) per problem) and opts as d2d_nlp_solve_free: opts->serial = 1 is D2D_EINVAL,
+ * constant wind of the rows, no field, nothing moves, no pins.  keep, kwork, fence, fwork as d2d_nlp_solve_fence (the duals live in
+ * kwork dev [B][n_keep][N] and fwork dev [B][n_edge][N], afterwards the multipliers; 0 at the end nodes and for absent rows), with the
+ * same D2D_EINVAL cases before any launch: keep or fence NULL, a count outside 0 .. D2D_MAX_KEEP / D2D_MAX_FENCE, a NULL table or dual
+ * array with a positive count.  Either count may be 0; with n_keep = 0 AND n_edge = 0 the call is d2d_nlp_solve_free, its kernel and
+ * its bytes.  Refused on the device (D2D_ST_NONFINITE, cost = feas = h_out = NaN, iters = 0, W untouched; the rest of the launch is
+ * solved): what refuses a problem of d2d_nlp_solve_free, and what refuses one of d2d_nlp_solve_fence.  cost: the reference's cost() +
+ * k_dur (N - 1) h_out; discs and edges add nothing.  The discs are held AT THE NODES: a caller that inflates R for the chord between two
+ * nodes inflates for the LARGEST step of the box, h_hi (conservative for every h inside); the fence is convex and needs none.
+ * tests/nlp_free_fence_ref.py is the CPU statement.  Asynchronous on the context's stream.  (version 129) */
+int d2d_nlp_solve_free_fence(d2d_ctx *ctx, int B, int N, double h0, const double *scen, const d2d_nlp_opts *opts,
+                             const double *free_rows /* dev [B][4] = (h_lo, h_hi, k_dur, h_start; 0 = h0) */,
+                             double *W, double *work, double *mult, double *cost, double *feas,
+                             int32_t *iters, int32_t *status, double *h_out /* dev [B] */,
+                             const d2d_keep_out *keep, double *kwork, const d2d_fence *fence, double *fwork);
 
 /* d2d_nlp_solve_groups_pairs with every aircraft inside its scenario's convex polygon: the arguments of d2d_nlp_solve_groups_pairs, then
  * fence with edges dev [R][n_edge][4], one polygon per SCENARIO read as above, then fwork dev [R n_ac][n_edge][N], every aircraft's own

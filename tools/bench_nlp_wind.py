@@ -32,6 +32,12 @@ python tools/bench_nlp_wind.py keepout [B] hard keep-out discs (d2d_nlp_solve_ke
     VMAX and h, no margin), against the same rows without a disc through d2d_nlp_solve, from the same guess.  The two entries
     alternate, 1 warm-up + 5 timed launches each, HIP events, one process; medians, the spread of each, statuses, mean and longest
     step counts, and the smallest g / R^2 of the converged plans.
+python tools/bench_nlp_wind.py keepout-free [B] hard keep-out discs with the step free (d2d_nlp_solve_free_fence): the rows, the disc and the
+    guess of `keepout`, once through d2d_nlp_solve_keepout at the fixed step h and twice through d2d_nlp_solve_free_fence with h free in
+    [h / 2, 2 h], k_dur = 0 and no edges -- with the fixed solve's disc table (only the step changes) and with the table lowered for the
+    largest step 2 h, as the planners lower it.  The three alternate, 1 warm-up + 5 timed launches each, HIP events, one process;
+    medians and the spread of each, statuses, mean and longest step counts, what the freed step does to the problems the fixed one
+    leaves STALLED, the solved durations and the smallest g / R^2 of the converged plans.
 python tools/bench_nlp_wind.py keepout-moving [B] hard keep-out discs that move (d2d_nlp_solve_keepout_moving): the rows, the disc and the
     guess of `keepout`, the disc once held still through d2d_nlp_solve_keepout, once as a track that stands still and once crossing
     the leg at 3 m/s (at the static centre at mid-time; node radius MovingKeepOut.lowered) through d2d_nlp_solve_keepout_moving.  The
@@ -320,6 +326,58 @@ def keepout_leg(B):
     ctx.close()
 
 
+def keepout_free_leg(B):
+    import torch, d2dhip
+    import d2dhip as D
+    from d2dhip import synth
+    from d2d.opty_utils import KeepOut
+    ctx = d2dhip.Context(0)
+    rows, W0, h = synth.nlp_problems(B)
+    N = W0.shape[2]
+    p0, p1 = rows[:, D.SC_X0:D.SC_X0 + 2], rows[:, D.SC_X1:D.SC_X1 + 2]
+    d = p1 - p0
+    d /= np.hypot(d[:, 0], d[:, 1])[:, None]
+    c = 0.5 * (p0 + p1) + 3.0 * np.stack([-d[:, 1], d[:, 0]], 1)
+    tabs = {'fixed': np.array([[KeepOut(c[b], 15.0).lowered(rows[b, D.SC_VMAX], h)] for b in range(B)])}
+    tabs['free'] = tabs['fixed']
+    tabs['free_hhi'] = np.array([[KeepOut(c[b], 15.0).lowered(rows[b, D.SC_VMAX], 2.0 * h)] for b in range(B)])
+    dsc = ctx.dev(rows)
+    dk = {k: ctx.dev(v) for k, v in tabs.items()}
+    fr = ctx.dev(np.tile([0.5 * h, 2.0 * h, 0.0, 0.0], (B, 1)))
+    names = ('fixed', 'free', 'free_hhi')
+    times = {k: [] for k in names}
+    outs, Ws = {}, {}
+    for rep in range(6):                                     # the first launch of each is the warm-up; the entries alternate
+        for what in names:
+            W = ctx.dev(np.ascontiguousarray(W0))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            outs[what] = ctx.nlp_solve_keepout(dsc, W, h, dk[what]) if what == 'fixed' else ctx.nlp_solve_free_fence(dsc, W, h, fr, discs=dk[what])
+            e1.record(); torch.cuda.synchronize()
+            times[what].append(e0.elapsed_time(e1) * 1e-3)
+            Ws[what] = W
+    med = {k: float(np.median(v[1:])) for k, v in times.items()}
+    st = {k: outs[k]['status'].cpu().numpy() for k in names}
+    for what in names:
+        it = outs[what]['iters'].cpu().numpy()
+        Wh, discs = Ws[what].cpu().numpy(), tabs[what]
+        g = ((Wh[:, 0, 1:-1] - discs[:, 0, 0:1]) ** 2 + (Wh[:, 1, 1:-1] - discs[:, 0, 1:2]) ** 2) / discs[:, 0, 2:3] ** 2 - 1.0
+        ok = st[what] == 1
+        rec = {'leg': 'keepout-free', 'B': B, 'nodes': N, 'entry': what, 'seconds_median': med[what], 'seconds_min': min(times[what][1:]),
+               'seconds_max': max(times[what][1:]), 'problems_per_s': B / med[what], 'problems_per_s_min_max': [B / max(times[what][1:]), B / min(times[what][1:])],
+               'over_fixed': med[what] / med['fixed'], 'status_counts': {int(k): int((st[what] == k).sum()) for k in np.unique(st[what])},
+               'mean_newton_steps': float(it.mean()), 'max_newton_steps': int(it.max()),
+               'mean_newton_steps_converged': float(it[ok].mean()) if ok.any() else None,
+               'min_g_over_R2_converged': float(g[ok].min()) if ok.any() else None}
+        if what != 'fixed':
+            hh = outs[what]['h'].cpu().numpy()
+            rec.update(fixed_not_converged=int((st['fixed'] != 1).sum()), of_those_free_converged=int((ok & (st['fixed'] != 1)).sum()),
+                       fixed_converged_free_not=int((~ok & (st['fixed'] == 1)).sum()),
+                       duration_min_mean_max=[float(v) * (N - 1) for v in (hh[ok].min(), hh[ok].mean(), hh[ok].max())] if ok.any() else None)
+        print(json.dumps(rec), flush=True)
+    ctx.close()
+
+
 def fence_leg(B):
     import torch, d2dhip
     import d2dhip as D
@@ -498,6 +556,8 @@ def main():
         return fence_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['keepout-moving']:
         return keepout_moving_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    if sys.argv[1:2] == ['keepout-free']:
+        return keepout_free_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['keepout']:
         return keepout_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     if sys.argv[1:2] == ['free']:

@@ -7,6 +7,9 @@ cost) report the refusal.
 --keep-out: every case with its soft discs (the cost's static obstacles) turned into hard ones (the scenario protocol's keep_out,
 d2d_nlp_solve_keepout; no margin): status, cost and the polyline's clearance per disc.  Cases without a disc, and those a hard disc is not
 combined with, say so.
+--free-time --keep-out together: the cases that carry discs with the discs hard AND the duration free in [t / 2, 2 t] (the scenario
+protocol's t1_window beside keep_out, d2d_nlp_solve_free_fence; the discs lowered for the largest step): status, duration, cost and
+clearance per disc.
 --guess dubins: every case from the device Dubins start (Planner.get_initial_guess('dubins'), d2d_nlp_guess_dubins) beside the case's
 own start: verdict and Newton steps of both, the status of the guess, and the difference of the two costs.  Combines with --free-time."""
 import json, os, sys, time
@@ -36,14 +39,14 @@ def main():
                 exp = s
                 if free:                                # the case as it stands, with t1 free in [t0 + t / 2, t0 + 2 t]
                     t = s.t1 - s.t0
-                    exp = type(s.__name__ + '_free', (s,), {'t1_free': (s.t0 + 0.5 * t, s.t0 + 2.0 * t)})
+                    exp = type(s.__name__ + '_free', (s,), {'t1_window' if hard else 't1_free': (s.t0 + 0.5 * t, s.t0 + 2.0 * t)})
                 if hard:                                # the cost's own discs, held instead of priced (they stay in the cost as well)
                     from d2d.opty_utils import KeepOut
                     obss = sop.lower_cost(s.cost)[4]
                     if not obss:
                         print(json.dumps({'scen': s.name, 'case': case, 'keep_out': 'no disc in this case'}), flush=True)
                         continue
-                    exp = type(s.__name__ + '_hard', (s,), {'keep_out': [KeepOut(o[:2], o[2]) for o in obss]})
+                    exp = type(exp.__name__ + '_hard', (exp,), {'keep_out': [KeepOut(o[:2], o[2]) for o in obss]})
                 p = sop.Planner(exp, initialize=True, backend='nlp')
                 t0 = time.perf_counter()
                 p.run(p.get_initial_guess(getattr(s, 'initial_guess', 'tri')))
