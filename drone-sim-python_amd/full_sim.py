@@ -561,32 +561,37 @@ def _fence_table(fence, G):
     return ftab
 
 
-def _plan_batch_window(scen_rows, K, W0, h, window, kdur, keep_out, fence, solve_kw):
-    """plan_batch(window=): one aircraft per row, the step free in its box, keep_out's static hard discs and the fence in the same solve."""
-    if h is None:
-        raise ValueError('plan_batch(window=): h, the start step, is required')
-    ctx = d2dhip.default_context()
-    rows = np.ascontiguousarray(scen_rows, dtype=np.float64)
-    dsc = ctx.dev(rows)
-    B, h = rows.shape[0], float(h)
-    W, guess_status = _start_nodes(ctx, dsc, K, h, W0, solve_kw.get('bounds'))
-    assert W.shape == (B, 5, K)
-    fr = np.zeros((B, 4))
-    fr[:, :2] = np.broadcast_to(np.asarray(window, dtype=np.float64), (B, 2))
-    fr[:, 2] = np.broadcast_to(np.asarray(kdur, dtype=np.float64), (B,))
-    keep = None if keep_out is None else _keep_table(keep_out, rows, fr[:, 1])       # the chord term at the largest step of the box
-    ftab = None if fence is None else _fence_table(fence, B)
-    out = d2dhip.nlp_plan(ctx, dsc, W, h, window=ctx.dev(fr), keep=None if keep is None else ctx.dev(keep),
-                          fence=None if ftab is None else ctx.dev(ftab), **solve_kw)
-    out['free_rows'] = fr
-    if keep is not None:
-        out['keep'] = keep
-    if ftab is not None:
-        out['fence'] = ftab
-    out.update(W=W, scen=dsc)
-    if guess_status is not None:
-        out['guess_status'] = guess_status
+def _default_pair_rows(dsc, n_ac, pairs, clone=True):
+    """The rows as the group entries that read partner sets want them: the reference's pair (0, 1) written as SC_PMASK of the coupled
+    scenarios -- into a copy, or with clone=False into dsc itself -- unless there is one aircraft or the rows select their pairs
+    (`pairs`, _rows_select_pairs): then dsc as it is."""
+    if n_ac < 2 or pairs:
+        return dsc
+    out = dsc.clone() if clone else dsc
+    d2mou.default_pair_masks(out, n_ac, (out[0::n_ac, d2dhip.SC_KCOL] > 0) & (out[1::n_ac, d2dhip.SC_KCOL] > 0))
     return out
+
+
+# plan_batch's optional features in the order they are looked at -> what the polynomial fit lacks and what backend='nlp' does with it ...
+PLAN_BATCH_FIT = {
+    'moving': ('moving obstacles', 'plans around them'), 'via': ('timed waypoints', 'plans through them'), 'windfield': ('wind field', 'plans in one'),
+    'free_time': ('free time step', 'plans with one'), 'window': ('free time step', 'plans with one (fit backend)'),
+    'keep_out': ('hard keep-out discs', 'holds them'), 'fence': ('geofence', 'holds one'), 'hard_moving': ('hard moving discs', 'holds them'),
+    'deconflict': ('deconfliction', 're-plans by priority')}
+# ... and the features each refuses beside it (the first one given is the one named), with the reason.  (free_time's two sentences are
+# its own, in plan_batch; fence with keep_out and n_ac > 1 is keep_out's to refuse.)
+PLAN_BATCH_REFUSES = {
+    'window': (('n_ac > 1', 'windfield', 'moving', 'via', 'hard_moving', 'deconflict', 'free_time'),
+               'a free step beside static hard discs and a geofence is held for one aircraft in the rows\' constant wind, without pins or '
+               'anything that moves'),
+    'keep_out': (('n_ac > 1', 'moving', 'via', 'free_time'), 'hard discs are held for one aircraft on static discs, without pins, with a fixed step'),
+    'fence': (('moving', 'via', 'free_time', 'hard_moving', 'deconflict'),
+              'a geofence is held with static hard discs for one aircraft, without them for several, without moving discs or pins, with a fixed step'),
+    'hard_moving': (('moving', 'via', 'free_time', 'keep_out', 'deconflict'),
+                    'hard moving discs go with neither soft moving discs, pins, a free step nor static hard discs (list a KeepOut in '
+                    'hard_moving), and the re-solve of deconflict does not carry them'),
+    'deconflict': (('free_time', 'keep_out', 'via', 'moving'),
+                   'the re-solve around the committed plans (d2d_nlp_solve_groups_moving) does not carry {name}')}
 
 
 def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit', W0=None, h=None, n_ac=1, windfield=None, t_start=0.0,
@@ -614,94 +619,63 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
     hand-out of d2d_nlp_solve_via -- for large batches of single aircraft call Context.nlp_solve_via (the difference is not measured).
     free_time (backend='nlp', n_ac = 1): (h_lo, h_hi) for all problems or an array (B, 2) -- every problem's time step is an unknown in
     that box, started from h, with kdur (a number or (B,)) the weight of the duration (K - 1) h in its objective (d2d_nlp_solve_free);
-    the result carries h, the solved steps (device [B]).  Not combined with n_ac > 1, windfield, moving or via: raised by name.
+    the result carries h, the solved steps (device [B]).
     keep_out (backend='nlp', n_ac = 1): hard keep-out discs -- an array (B, n, 3) of (cx, cy, R), the node constraint as the kernel reads
     it, or a list of d2d.opty_utils.KeepOut for all problems, lowered with each row's VMAX and h (d2d_nlp_solve_keepout, with and
-    without a field); the result carries keep_mult (device [B][n][K]) and keep (the lowered table, a host array (B, n, 3)).  Not combined with n_ac > 1, moving,
-    via or free_time: raised by name.
+    without a field); the result carries keep_mult (device [B][n][K]) and keep (the lowered table, a host array (B, n, 3)).
     hard_moving (backend='nlp', any n_ac): hard keep-out discs that MOVE -- a list of d2d.opty_utils.MovingKeepOut (and KeepOut) for all
     scenarios or one list per scenario -- that every aircraft of the scenario holds, node i at t_start[r] + i h, lowered with the
     scenario's largest VMAX and h (d2d_nlp_solve_groups_keepout; d2d_nlp_solve_keepout_moving when n_ac = 1; with and without a field);
-    the result carries keep_mult (device [B][n][K]) and hard_knots, hard_disc (the lowered device tables).  Not combined with moving,
-    via, free_time, keep_out or deconflict: raised by name.
+    the result carries keep_mult (device [B][n][K]) and hard_knots, hard_disc (the lowered device tables).
     fence (backend='nlp', any n_ac): a hard geofence -- one d2d.opty_utils.GeoFence for all scenarios, one per scenario (a list of
     B / n_ac), or the lowered rows, an array (B / n_ac, n, 4) of (ax, ay, b, kap) -- that every aircraft's plan stays inside, its polyline
     included (n_ac = 1: d2d_nlp_solve_fence, with and without keep_out's static hard discs in the same solve; n_ac > 1:
     d2d_nlp_solve_groups_fence, which carries no hard discs; both with and without a field); the result carries fence_mult (device
-    [B][n][K]) and fence (the lowered table, a host array).  Not combined with moving, via, free_time, hard_moving or deconflict, nor
-    with keep_out when n_ac > 1: raised by name.
+    [B][n][K]) and fence (the lowered table, a host array).
     window (backend='nlp', n_ac = 1): free_time's box -- (h_lo, h_hi) for all problems or an array (B, 2), with kdur -- for a plan that also
     holds keep_out's static hard discs and a fence (either, both or neither) in the same solve (d2d_nlp_solve_free_fence): the spelling
     of a free step beside hard constraints (free_time keeps refusing them).  A list of KeepOut is lowered with each row's VMAX and the
     LARGEST step of its box, h_hi: conservative for every step the solve may end at; the fence is convex and needs none.  The result
-    carries h and free_rows as free_time's, keep / keep_mult and fence / fence_mult as keep_out's and fence's.  Not combined with
-    n_ac > 1, windfield, moving, via, hard_moving, deconflict, free_time or the fit backend: raised by name.
+    carries h and free_rows as free_time's, keep / keep_mult and fence / fence_mult as keep_out's and fence's.
     deconflict (backend='nlp'): None -- today's call, bit for bit -- or a dict of deconflict_plans' keywords (d_sep, margin, d_look
     required; world, prio, n_knot, n_mov, max_rounds, step_max, kind, hard): after the solve the formations (the scenarios) that share a
     world give way to each other by priority (deconflict_plans, which re-solves with this call's solve_kw, in the field and from the
     start times of this call); W is updated in place and the result carries deconflict, its info.  Start times must be whole multiples
-    of h apart (fleet_row0 names the formation that is not).  Not with the fit backend, free_time, keep_out, via or moving -- the
-    re-solve entry does not carry them: raised by name."""
+    of h apart (fleet_row0 names the formation that is not).
+    What does not combine is refused by name (NotImplementedError), from PLAN_BATCH_FIT and PLAN_BATCH_REFUSES -- the feature on the left
+    is not planned together with those on the right; none of them, nor windfield, moving or via, with the fit backend:
+      free_time    n_ac > 1, windfield, moving, via
+      window       n_ac > 1, windfield, moving, via, hard_moving, deconflict, free_time
+      keep_out     n_ac > 1, moving, via, free_time
+      fence        moving, via, free_time, hard_moving, deconflict
+      hard_moving  moving, via, free_time, keep_out, deconflict
+      deconflict   free_time, keep_out, via, moving"""
     import single_opt_planner as sop
     from d2d.wind import planner_wind
     if gust is not None:
         raise ValueError('a gust is a property of the plant, not of a plan: the planners take none (fly the plan through it with '
                          'implement_controller_batch(gust=...) or full_sim_phases_batch(gust=...))')
     fld = planner_wind(windfield)
-    if moving and backend != 'nlp':
-        raise NotImplementedError("the polynomial fit has no moving obstacles: plan_batch(backend='nlp', moving=...) plans around them")
-    if via is not None and backend != 'nlp':
-        raise NotImplementedError("the polynomial fit has no timed waypoints: plan_batch(backend='nlp', via=...) plans through them")
-    if fld is not None and backend != 'nlp':
-        raise NotImplementedError("the polynomial fit has no wind field: plan_batch(backend='nlp', windfield=...) plans in one")
-    if free_time is not None:
-        if backend != 'nlp':
-            raise NotImplementedError("the polynomial fit has no free time step: plan_batch(backend='nlp', free_time=...) plans with one")
-        if int(n_ac) != 1:
+    given = {'n_ac > 1': int(n_ac) != 1, 'windfield': fld is not None, 'moving': bool(moving), 'via': via is not None, 'free_time': free_time is not None,
+             'keep_out': keep_out is not None, 'deconflict': deconflict is not None, 'hard_moving': hard_moving is not None,
+             'fence': fence is not None, 'window': window is not None}
+    given = {k for k, g in given.items() if g}
+    if backend != 'nlp':
+        for name, (what, does) in PLAN_BATCH_FIT.items():
+            if name in given:
+                raise NotImplementedError(f"the polynomial fit has no {what}: plan_batch(backend='nlp', {name}=...) {does}")
+    if 'free_time' in given:                      # (its two sentences fit no row: one for n_ac, one that names three features)
+        if 'n_ac > 1' in given:
             raise NotImplementedError('free_time with n_ac > 1: the aircraft of a scenario share one time step, which the block '
                                       'Gauss-Seidel over the aircraft cannot hold; plan them one at a time')
-        if fld is not None or moving or via is not None:
+        if given & {'windfield', 'moving', 'via'}:
             raise NotImplementedError('free_time together with windfield, moving or via is not supported: node times move with the step')
-    if window is not None:
-        if backend != 'nlp':
-            raise NotImplementedError("the polynomial fit has no free time step: plan_batch(backend='nlp', window=...) plans with one (fit backend)")
-        for name, given in (('n_ac > 1', int(n_ac) != 1), ('windfield', fld is not None), ('moving', bool(moving)), ('via', via is not None),
-                            ('hard_moving', hard_moving is not None), ('deconflict', deconflict is not None), ('free_time', free_time is not None)):
-            if given:
-                raise NotImplementedError(f'window with {name} is not supported: a free step beside static hard discs and a geofence is held '
-                                          'for one aircraft in the rows\' constant wind, without pins or anything that moves')
-        return _plan_batch_window(scen_rows, K, W0, h, window, kdur, keep_out, fence, solve_kw)
-    if keep_out is not None:
-        if backend != 'nlp':
-            raise NotImplementedError("the polynomial fit has no hard keep-out discs: plan_batch(backend='nlp', keep_out=...) holds them")
-        for name, given in (('n_ac > 1', int(n_ac) != 1), ('moving', bool(moving)), ('via', via is not None), ('free_time', free_time is not None)):
-            if given:
-                raise NotImplementedError(f'keep_out with {name} is not supported: hard discs are held for one aircraft on static discs, '
-                                          'without pins, with a fixed step')
-    if fence is not None:
-        if backend != 'nlp':
-            raise NotImplementedError("the polynomial fit has no geofence: plan_batch(backend='nlp', fence=...) holds one")
-        for name, given in (('moving', bool(moving)), ('via', via is not None), ('free_time', free_time is not None),
-                            ('hard_moving', hard_moving is not None), ('deconflict', deconflict is not None)):    # (keep_out with n_ac > 1: above)
-            if given:
-                raise NotImplementedError(f'fence with {name} is not supported: a geofence is held with static hard discs for one aircraft, '
-                                          'without them for several, without moving discs or pins, with a fixed step')
-    if hard_moving is not None:
-        if backend != 'nlp':
-            raise NotImplementedError("the polynomial fit has no hard moving discs: plan_batch(backend='nlp', hard_moving=...) holds them")
-        for name, given in (('moving', bool(moving)), ('via', via is not None), ('free_time', free_time is not None),
-                            ('keep_out', keep_out is not None), ('deconflict', deconflict is not None)):
-            if given:
-                raise NotImplementedError(f'hard_moving with {name} is not supported: hard moving discs go with neither soft moving discs, '
-                                          'pins, a free step nor static hard discs (list a KeepOut in hard_moving), and the re-solve of '
-                                          'deconflict does not carry them')
+    for lead, (names, why) in PLAN_BATCH_REFUSES.items():
+        if lead in given:
+            for name in names:
+                if name in given:
+                    raise NotImplementedError(f'{lead} with {name} is not supported: ' + why.format(name=name))
     if deconflict is not None:
-        if backend != 'nlp':
-            raise NotImplementedError("the polynomial fit has no deconfliction: plan_batch(backend='nlp', deconflict=...) re-plans by priority")
-        for name, given in (('free_time', free_time is not None), ('keep_out', keep_out is not None), ('via', via is not None), ('moving', bool(moving))):
-            if given:
-                raise NotImplementedError(f'deconflict with {name} is not supported: the re-solve around the committed plans '
-                                          f'(d2d_nlp_solve_groups_moving) does not carry {name}')
         deconflict = dict(deconflict)
         unknown = set(deconflict) - {'d_sep', 'margin', 'd_look', 'world', 'prio', 'n_knot', 'n_mov', 'max_rounds', 'step_max', 'kind', 'hard'}
         missing = {'d_sep', 'margin', 'd_look'} - set(deconflict)
@@ -714,84 +688,56 @@ def plan_batch(scen_rows, K, duration, obj_scale_over_n, q0=None, backend='fit',
         dec_t0 = float(ts.min())
     ctx = d2dhip.default_context()
     if backend == 'nlp':
-        dsc = ctx.dev(np.ascontiguousarray(scen_rows, dtype=np.float64))
+        if window is not None and h is None:
+            raise ValueError('plan_batch(window=): h, the start step, is required')
+        rows = np.ascontiguousarray(scen_rows, dtype=np.float64)
+        dsc = ctx.dev(rows)
         assert h is not None
-        h, n_ac = float(h), int(n_ac)
+        B, h, n_ac = rows.shape[0], float(h), int(n_ac)
         if isinstance(W0, str) and W0 == 'dubins' and via is not None:
             raise NotImplementedError("W0='dubins' with via=: a Dubins path knows no pins; the 'via' guess does "
                                       "(d2d.opty_utils.via_guess, Planner.get_initial_guess('via')): pass its node values as W0")
         W, guess_status = _start_nodes(ctx, dsc, K, h, W0, solve_kw.get('bounds'))      # ('dubins': built on the device from the rows, no host copy)
-        assert W.shape == (dsc.shape[0], 5, K)
-        if fence is not None:
-            B = dsc.shape[0]
-            rows = np.asarray(scen_rows, dtype=np.float64)
-            ftab = _fence_table(fence, B // n_ac)
-            if n_ac > 1:
-                dsc_f = dsc
-                if not _rows_select_pairs(scen_rows, n_ac):     # the reference's pair (0, 1) as the partner sets the group entry reads
-                    dsc_f = dsc.clone()
-                    d2mou.default_pair_masks(dsc_f, n_ac, (dsc_f[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc_f[1::n_ac, d2dhip.SC_KCOL] > 0))
-                out = d2dhip.nlp_plan(ctx, dsc_f, W, h, n_ac=n_ac, fence=ctx.dev(ftab), field=fld, t_start=t_start if fld is not None else None,
-                                      **solve_kw)
-                out.update(fence=ftab, W=W, scen=dsc)
-                if guess_status is not None:
-                    out['guess_status'] = guess_status
-                return out
-            keep = None if keep_out is None else _keep_table(keep_out, rows, np.full(B, h))
-            out = d2dhip.nlp_plan(ctx, dsc, W, h, fence=ctx.dev(ftab), keep=None if keep is None else ctx.dev(keep), field=fld,
-                                  t_start=t_start if fld is not None else None, **solve_kw)
-            out['fence'] = ftab
-            if keep is not None:
-                out['keep'] = keep
-            out.update(W=W, scen=dsc)
-            if guess_status is not None:
-                out['guess_status'] = guess_status
-            return out
-        if keep_out is not None:
-            keep = _keep_table(keep_out, np.asarray(scen_rows, dtype=np.float64), np.full(dsc.shape[0], h))
-            out = d2dhip.nlp_plan(ctx, dsc, W, h, keep=ctx.dev(keep), field=fld, t_start=t_start if fld is not None else None, **solve_kw)
-            out['keep'] = keep
-        elif hard_moving is not None:
-            hk, hd = _hard_moving_tables(ctx, hard_moving, np.asarray(scen_rows, dtype=np.float64), n_ac, h)
-            pairs = _rows_select_pairs(scen_rows, n_ac)
-            dsc_h = dsc
-            if n_ac >= 2 and not pairs:                         # the reference's pair (0, 1) as the partner sets the group entry reads
-                dsc_h = dsc.clone()
-                d2mou.default_pair_masks(dsc_h, n_ac, (dsc_h[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc_h[1::n_ac, d2dhip.SC_KCOL] > 0))
-            out = d2dhip.nlp_plan(ctx, dsc_h, W, h, n_ac=None if n_ac == 1 else n_ac, field=fld, t_start=t_start, hard_knots=hk, hard_disc=hd,
-                                  **solve_kw)
-            out.update(hard_knots=hk, hard_disc=hd)
-        elif free_time is not None:
-            B = dsc.shape[0]
+        assert W.shape == (B, 5, K)
+        step = window if window is not None else free_time
+        # one aircraft with a hard family or a free step: the hand-out entries; everything else the group entries, for every n_ac (the
+        # docstring's note on via= with n_ac = 1)
+        hand = n_ac == 1 and any(v is not None for v in (step, keep_out, fence, hard_moving))
+        pairs = _rows_select_pairs(scen_rows, n_ac)          # partner sets other than the reference's pair (0, 1)
+        host, dev, mov = {}, {}, {}                          # lowered tables: host arrays and device tensors the result carries; the discs' tracks
+        if step is not None:
             fr = np.zeros((B, 4))
-            fr[:, :2] = np.broadcast_to(np.asarray(free_time, dtype=np.float64), (B, 2))
+            fr[:, :2] = np.broadcast_to(np.asarray(step, dtype=np.float64), (B, 2))
             fr[:, 2] = np.broadcast_to(np.asarray(kdur, dtype=np.float64), (B,))
-            out = d2dhip.nlp_plan(ctx, dsc, W, h, free_rows=ctx.dev(fr), **solve_kw)
-            out['free_rows'] = fr
-        else:                                               # always the group entries (the docstring's note on via= with n_ac = 1)
-            pairs = _rows_select_pairs(scen_rows, n_ac)         # partner sets other than the reference's pair (0, 1)
-            ex = {}
-            if via is not None:
-                table = _via_table(dsc, n_ac, K, h, t_start, via)
-                if n_ac >= 2 and not pairs:                     # the reference's pair (0, 1) as partner sets
-                    d2mou.default_pair_masks(dsc, n_ac, (dsc[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc[1::n_ac, d2dhip.SC_KCOL] > 0))
-                if fld is None and not moving:
-                    t_start = None
-                ex['via'] = ctx.dev(table)
-            if moving:
-                ex['knots'], ex['disc'] = _moving_tables(ctx, moving, dsc.shape[0] // n_ac)
-            out = d2dhip.nlp_plan(ctx, dsc, W, h, n_ac=n_ac, field=fld, t_start=t_start, pairs=pairs, **ex, **solve_kw)
-            if via is not None:
-                import d2d.opty_utils as d2ou
-                ctx.sync()
-                Wh = W.cpu().numpy()
-                out.update(via=ex['via'], waypoint_error=max(d2ou.waypoint_error(table[b], Wh[b]) for b in range(len(Wh))))
-        if deconflict is not None:
-            dsc_d = dsc
-            if n_ac >= 2 and not pairs:                         # the reference's pair (0, 1) as the partner sets the re-solve entry reads
-                dsc_d = dsc.clone()
-                d2mou.default_pair_masks(dsc_d, n_ac, (dsc_d[0::n_ac, d2dhip.SC_KCOL] > 0) & (dsc_d[1::n_ac, d2dhip.SC_KCOL] > 0))
-            _, out['deconflict'] = deconflict_plans(ctx, dsc_d, W, h, n_ac, row0=dec_row0, field=fld, t0=dec_t0, **deconflict, **solve_kw)
+            host['free_rows'] = fr
+        if keep_out is not None:                             # (a free step: the chord term at the largest step of the box)
+            host['keep'] = _keep_table(keep_out, rows, np.full(B, h) if window is None else fr[:, 1])
+        if fence is not None:
+            host['fence'] = _fence_table(fence, B // n_ac)
+        if hard_moving is not None:
+            dev['hard_knots'], dev['hard_disc'] = _hard_moving_tables(ctx, hard_moving, rows, n_ac, h)
+        if via is not None:
+            table = _via_table(dsc, n_ac, K, h, t_start, via)
+            dev['via'] = ctx.dev(table)
+        if moving:
+            mov['knots'], mov['disc'] = _moving_tables(ctx, moving, B // n_ac)
+        scen = dsc
+        if fence is not None or hard_moving is not None or via is not None:      # their group entries read the partner sets
+            scen = _default_pair_rows(dsc, n_ac, pairs, clone=via is None)       # (via= writes them into the rows it returns)
+        if fld is None and not moving and (via is not None or keep_out is not None or fence is not None):
+            t_start = None                                   # (no clock but the pins', whose table is on it already)
+        spelt = {'free_rows': 'window'} if window is not None else {}       # (nlp_plan's spelling of a free step beside hard constraints)
+        out = d2dhip.nlp_plan(ctx, scen, W, h, n_ac=None if hand else n_ac, field=fld, t_start=t_start, pairs=pairs, **mov, **dev,
+                              **{spelt.get(k, k): ctx.dev(v) for k, v in host.items()}, **solve_kw)
+        out.update(host, **dev)
+        if via is not None:
+            import d2d.opty_utils as d2ou
+            ctx.sync()
+            Wh = W.cpu().numpy()
+            out['waypoint_error'] = max(d2ou.waypoint_error(table[b], Wh[b]) for b in range(len(Wh)))
+        if deconflict is not None:                           # (the re-solve entry reads the partner sets too)
+            _, out['deconflict'] = deconflict_plans(ctx, _default_pair_rows(dsc, n_ac, pairs), W, h, n_ac, row0=dec_row0, field=fld, t0=dec_t0,
+                                                    **deconflict, **solve_kw)
         out.update(W=W, scen=dsc)
         if guess_status is not None:
             out['guess_status'] = guess_status

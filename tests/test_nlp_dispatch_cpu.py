@@ -4,7 +4,12 @@
    planners) and plan_batch over a recording stand-in of the context; tests/golden/nlp_dispatch_parent.json is what it recorded at
    the commit before the fold.  Every call -- entry, rows, tables, options -- must be the same.
 2. The rule itself: nlp_plan with every combination of the optional inputs lands on the entry its table names, and hands it the
-   inputs that entry takes."""
+   inputs that entry takes.
+3. The same for the entries added since (hard discs, hard moving discs, the geofence, the free step beside them), deconflict= and
+   W0='dubins': nlp_dispatch_abi129.json, recorded at the commit before nlp_plan and plan_batch were restated as tables
+   (d2dhip.plan.ENTRIES / REFUSES).
+4. Every refusal and every route, exhaustively: nlp_dispatch_refusals.json holds the outcome, at that commit, of nlp_plan for every
+   subset of its 13 optional inputs and of plan_batch for backend x n_ac x every subset of its 10 optional features."""
 import importlib.util
 import itertools
 import json
@@ -52,6 +57,68 @@ def test_same_calls_as_the_parent(replay):
             for k in want['args']:
                 assert got['args'][k] == want['args'][k], (name, got['entry'], k)
         assert now[name] == parent[name], name                      # and what the caller made of the result: info keys, rows, result keys
+
+
+def test_the_newer_families_make_the_same_calls(maker):
+    """nlp_dispatch_abi129.json, call by call: entry, every argument by hash, result keys, returned scen."""
+    with open(os.path.join(GOLD, 'nlp_dispatch_abi129.json')) as f:
+        parent = json.load(f)
+    now = json.loads(json.dumps(maker.collect('abi129')))
+    assert sorted(now) == sorted(parent) and len(parent) >= 50
+    for name in sorted(parent):
+        assert [c['entry'] for c in now[name]['calls']] == [c['entry'] for c in parent[name]['calls']], name
+        for got, want in zip(now[name]['calls'], parent[name]['calls']):
+            assert sorted(got['args']) == sorted(want['args']), name
+            for k in want['args']:
+                assert got['args'][k] == want['args'][k], (name, got['entry'], k)
+        assert now[name] == parent[name], name
+    # with the first file every entry nlp_plan can choose is reached through a planner or plan_batch -- but nlp_solve, which neither
+    # ever chooses (the rule's own test below reaches it)
+    with open(os.path.join(GOLD, 'nlp_dispatch_parent.json')) as f:
+        both = list(parent.values()) + list(json.load(f).values())
+    import d2dhip.plan
+    assert len(d2dhip.plan.ENTRIES) == 16
+    assert {c['entry'] for v in both for c in v['calls']} >= {row[0] for row in d2dhip.plan.ENTRIES} - {'nlp_solve'}
+
+
+def test_every_subset_of_the_inputs_ends_as_it_did(maker):
+    """nlp_dispatch_refusals.json: all 8192 subsets of nlp_plan's optional inputs and all 4096 (+1) calls of plan_batch end at the same
+    entry with the same inputs, or raise the same exception with the same text."""
+    with open(os.path.join(GOLD, 'nlp_dispatch_refusals.json')) as f:
+        parent = json.load(f)
+    now = maker.refusals()
+    assert len(parent['nlp_plan']) == 2 ** len(maker.PLAN_INPUTS) == 8192 and len(parent['plan_batch']) == 4 * 2 ** len(maker.BATCH_FEATURES) + 1
+    for what in ('nlp_plan', 'plan_batch'):
+        assert len(now[what]) == len(parent[what])
+        for i, (got, want) in enumerate(zip(now[what], parent[what])):
+            assert now['outcomes'][got] == parent['outcomes'][want], (what, i)
+    ends = [parent['outcomes'][i] for i in parent['nlp_plan']]
+    assert sum('entry' in o for o in ends) == 328 and sum(o.get('raises') == 'NotImplementedError' for o in ends) == 7832
+    assert sum(o.get('raises') == 'ValueError' for o in ends) == 32 and len({o['message'] for o in ends if 'raises' in o}) == 25
+    import d2dhip.plan
+    assert {o['entry'] for o in ends if 'entry' in o} == {row[0] for row in d2dhip.plan.ENTRIES}         # all sixteen
+
+
+def test_plan_batch_docstring_table_is_the_table():
+    """The compatibility table at the end of plan_batch's docstring says what PLAN_BATCH_REFUSES (and free_time's two checks) refuse."""
+    import full_sim as fs
+    lines = fs.plan_batch.__doc__.split('with the fit backend:\n')[1].splitlines()
+    doc = {ln.split()[0]: tuple(ln.split(None, 1)[1].split(', ')) for ln in lines}
+    assert doc == {'free_time': ('n_ac > 1', 'windfield', 'moving', 'via'), **{k: v[0] for k, v in fs.PLAN_BATCH_REFUSES.items()}}
+    assert set(fs.PLAN_BATCH_FIT) == set(doc) | {'windfield', 'moving', 'via'}
+
+
+def test_the_module_table_is_the_pinned_one():
+    """d2dhip.plan.ENTRIES against the literal tables below, for the ten entries they name: precedence, launch shape, naming input, and
+    the inputs handed."""
+    from d2dhip.plan import ENTRIES as rows
+    by = {entry: (groups, named, tuple(k for k in pos if k != 'n_ac') + tuple(takes)) for entry, groups, named, pos, takes in rows}
+    assert len(by) == len(rows) == 16
+    for entry in ENTRIES:
+        assert by[entry][2] == TAKES[entry], entry
+    for table, groups in ((GROUP, True), (HANDOUT, False)):
+        tail = [(named, entry) for entry, g, named, _, _ in rows if g == groups and entry in ENTRIES]
+        assert tuple(tail) == table + ((None, 'nlp_solve_groups' if groups else 'nlp_solve'),)
 
 
 GROUP = ('via', 'nlp_solve_groups_via'), ('knots', 'nlp_solve_groups_moving'), ('pairs', 'nlp_solve_groups_pairs'), ('field', 'nlp_solve_groups_wind')
